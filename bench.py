@@ -11,7 +11,16 @@ top-level `value_one_scan_in_flight`, and the rate with one Python call per scan
 synthetic data of BASELINE.json's headline config: cfg2 = 64-beam x 2048 = 131 072-point scan vs a ~1M-point voxel map
 (voxel 1.0 m, 20 pts/voxel), default ICP parameters (max 10 iterations, 1e-3 stop, adaptive regularisation), tau =
 first-frame adaptive value.  Inputs (scans, map mirror) are resident in HBM when the timed region starts; map
-build/upload is outside it.  `value` = scans per second = K * scans_per_step / wall time of the K timed steps.
+build/upload is outside it.  `value` = scans per second = K * scans_per_step / wall time of the K timed steps;
+`ms_per_step` = that wall time / K.  scans_per_step is fixed by --scans-per-step (default 3200), so a step is the same work
+whatever K is and the same arguments register the same scans in every run.
+
+A plain run sets up, warms up, times the K steps and prints the line with the headline keys and a short `config`.
+--dump-outputs DIR writes what the last timed step returned to its caller (DIR/poses.npy: the step's poses, (scans_per_step, 7)
+float64 [qx, qy, qz, qw, tx, ty, tz]; DIR/iterations.npy: their ICP iteration counts as float64), so that two builds can be
+compared output for output.  Everything else below - the one-scan-in-flight, multi-iteration, per-call and host-input rates, the
+check of the timed poses against single calls and the oracle, the roofline with its PMC passes, the CPU baseline, the `pipeline`
+block, the other exchanges and the replicas at N > 1 - runs with --full only.
 
 The headline scans carry the seeded initial-guess error of SURVEY.md section 8d, for which the reference stops after ONE
 iteration.  A second workload ("multi_iteration" in `config`) times the same scans with an extra 0.05 m / 0.5 deg odometry error
@@ -28,7 +37,7 @@ Every exchange is measured in the same run (value_rccl, value_shm, value_p2p).  
 "scaling_bound" says what sharding one scan can reach at best (Amdahl from the single-GPU floor), "value_replicas" what the same
 GPUs deliver as independent replicas (--mode replicas makes that the headline: every rank registers whole scans, "scaling": "weak").
 
-Prints ONE JSON line on rank 0 with the contract's keys plus
+Prints ONE JSON line on rank 0 with the contract's keys; with --full also
   "roofline"     the dominant kernel (fused association+accumulation pass).  `achieved` / `frac` = HBM bytes per launch MEASURED
                  in this run (rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes over the same registrations) / the kernel's live
                  HIP-event duration, against the 8 TB/s peak.  The kernel is not HBM bound: `frac_latency` (the chain of dependent
@@ -97,10 +106,10 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=40)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--scans-per-step", type=int, default=0,
-                    help="registrations per step (one batch of synthetic scans); 0 (default) = chosen after a calibration batch so that the "
-                         "timed region of the K steps lasts at least --min-timed-s, never fewer than 64; re-sized and re-run if the timed "
-                         "region still comes in short")
+    ap.add_argument("--scans-per-step", type=int, default=3200,
+                    help="registrations per step (one batch of synthetic scans; the default is about what the automatic sizing chose for 20 "
+                         "steps); 0 = chosen after a calibration batch so that the timed region of the K steps lasts at least --min-timed-s, "
+                         "never fewer than 64; re-sized and re-run if the timed region still comes in short (the step then depends on the clock)")
     ap.add_argument("--min-timed-s", type=float, default=0.3, help="shortest acceptable timed region (auto batch size)")
     ap.add_argument("--no-pmc", action="store_true", help="skip the in-run rocprofv3 --pmc passes (FETCH_SIZE / WRITE_SIZE) behind roofline.traffic")
     ap.add_argument("--workload", default="cfg2")
@@ -124,6 +133,9 @@ def main():
     ap.add_argument("--force-comm", action="store_true", help="exercise the multi-GPU code path (all-reduce + separate solve) even with one rank")
     ap.add_argument("--no-sharded-cfg5", action="store_true",
                     help="N>1: skip the second sharded workload (cfg5: 500 000-point scans, 62 500 per GPU at N = 8 - where sharding can pay)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline (see the module docstring): without it the run stops after the K timed steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs as DIR/poses.npy and DIR/iterations.npy (float64)")
     args = ap.parse_args()
 
     # Everything except the final JSON line goes to stderr - also what C libraries print (RCCL writes a version banner to
@@ -145,9 +157,16 @@ def main():
     import torch.distributed as dist
 
     import __graft_entry__ as entry
-    entry.build()
     import kinematic_icp_amd as K
     from kinematic_icp_amd import synthetic as syn
+    # build() rebuilds what is stale, serialised on a lock file in the tree.  A tree this process may not write (built beforehand by
+    # its owner) is run as it stands; a library missing there is still an error (K.lib()).
+    lock = os.path.join(ROOT, ".build.lock")
+    if os.access(ROOT, os.W_OK) and (not os.path.exists(lock) or os.access(lock, os.W_OK)):
+        entry.build()
+    else:
+        print("bench.py: %s is not writable by this process: the libraries built there are used as they stand" % ROOT, file=sys.stderr)
+        K.lib()
 
     if not torch.cuda.is_available():
         raise SystemExit("bench.py needs a GPU (no CPU fallback exists for the product path)")
@@ -416,6 +435,14 @@ def main():
         state["B"] = int(min(8192, max(state["B"] + 1, -(-state["B"] * args.min_timed_s * 1.2 // elapsed))))
         resized += 1
     B = state["B"]
+    iters_timed = timed.last_iterations
+    if args.dump_outputs and rank == 0:
+        # what the caller of the LAST timed step received (not timed): the batches are used in turn, so the last step's batch holds
+        # its poses and iteration counts as that step left them; every rank returns the same poses
+        _, poses_last, iters_last = results_timed[(args.steps - 1) % len(results_timed)]
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "poses.npy"), poses_last.astype(np.float64))
+        np.save(os.path.join(args.dump_outputs, "iterations.npy"), iters_last.astype(np.float64))
     launch_path = ("direct AQL dispatch on the handle's own HSA queue (kicp_aql.hpp), kernel arguments in %s"
                    % {0.0: "host memory", 1.0: "device memory", 2.0: "device memory + HDP flush"}.get(reg.get_option("aql_kernarg"), "?")
                    if reg.get_option("aql_active") == 1.0 else "hipLaunchKernelGGL on the handle's stream")
@@ -435,6 +462,61 @@ def main():
         if batch_threads > 1:
             launch_path += ("; %d such kernels side by side, each serving a contiguous part of the batch from a host thread of its own (option batch_threads)" % batch_threads)
     in_flight = queues if queued_batch else ((depth * max(1, batch_threads)) if resident_batch else 1)
+    n_scans_timed = args.steps * B
+    value = (world if replicas else 1) * n_scans_timed / elapsed  # replicas: every rank completed its own scans
+    med_step = float(np.median(step_s)) if step_s.size else float("nan")
+    headline = {
+        "metric": "scans/sec (ICP registration only), 128k-pt scan vs 1M-pt map",
+        "value": round(value, 2),
+        "unit": "scans/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(1e3 * elapsed / args.steps, 5),
+        "higher_is_better": True,
+        "scaling": "weak" if replicas else "strong",
+        "vs_baseline": None,
+        "dtype": "f64",
+        "data": "synthetic",
+    }
+    config = {"workload": "%s: %d-pt %d-beam scan vs %d-pt / %d-voxel map, voxel %.2f m, tau %.4f m, default ICP iterations (mean %.2f per scan); "
+                          "one step = one kicp_register_device_batch call = %d independent scans against the fixed map, %s; %d distinct scans cycled"
+                          % (cfg.name, n_total, cfg.n_beams, gmap.num_points(), gmap.num_voxels(), cfg.voxel_size, tau, iters_timed, B,
+                             ("up to %d in flight at a time (every scan's result bit-identical to registering it alone)" % in_flight) if in_flight > 1
+                             else "registered one after the other", len(scans)),
+              "scans_in_flight": in_flight,
+              "scans_per_step": B, "distinct_scans": len(scans), "ms_per_scan": round(1e3 * elapsed / n_scans_timed, 5), "timed_region_s": round(elapsed, 4),
+              "batch_resized_after_short_timed_region": resized,
+              "ms_per_step_median": round(1e3 * med_step, 5),
+              "ms_per_step_min_max": [round(1e3 * float(step_s.min()), 5), round(1e3 * float(step_s.max()), 5)] if step_s.size else None,
+              "points_per_gpu": hi - lo,
+              "parallelism": ("%d independent replicas (one robot per GPU), no exchange" % world) if replicas else
+                             (("points sharded x%d, map replicated, %s exchange of the 24 limb words per ICP pass, %d sharded scan(s) in flight per rank"
+                               % (world, args.comm, in_flight)) if use_comm else "single GPU"),
+              "launch_path": launch_path, "host_placement": host_placement,
+              **({"comm_note": comm_note} if comm_note else {})}
+    if elapsed < 0.25:
+        config["warning"] = "timed region shorter than 0.25 s: raise --steps or --scans-per-step (0 = automatic)"
+
+    def emit(out):
+        import ctypes
+        ctypes.CDLL(None).fflush(None)
+        sys.stdout.flush()
+        os.dup2(saved_stdout, 1)
+        print(json.dumps(out), flush=True)
+        if leaked:  # (see the probe above: no destructor for the failed RCCL handle)
+            os._exit(0)
+
+    if not args.full:  # ---- a plain run ends here: the headline and nothing else
+        if exchange:
+            release(reg, comm)
+        del reg
+        if use_comm:
+            dist.barrier()
+            dist.destroy_process_group()
+        if rank == 0:
+            emit({**headline, **({"comm": comm} if exchange and world > 1 else {}), "config": config})
+        return
     # the same batch calls with ONE scan in flight at a time (the batch's scans strictly one after the other: what a caller gets whose
     # next scan depends on the previous result) - informational, next to the headline
     elapsed_serial = None
@@ -725,8 +807,6 @@ def main():
     cpu = None if args.no_cpu_baseline else _cpu_baseline(args, cfg, scans[:8], rel_single[:8], tau, omap, map_points, okicp, rkicp)
     pipeline = _pipeline_block(args.pipeline_frames, with_reference=not args.no_cpu_baseline) if (world == 1 and args.pipeline_frames > 0 and args.workload == "cfg2") else None
 
-    n_scans_timed = args.steps * B
-    value = (world if replicas else 1) * n_scans_timed / elapsed  # replicas: every rank completed its own scans
     if exchange:
         top_exchange["value_" + comm] = round(value, 2)
     # ---- HBM traffic of the pass kernel, measured in THIS run: one rocprofv3 --pmc pass per counter over a bare loop of the
@@ -824,40 +904,20 @@ def main():
             "time_split_us": None if floor_us is None else {"fixed_floor_launch_reduction_handoff": round(floor_us, 2),
                                                             "query_work": round(kernel_us - floor_us, 2)},
             "counters": prof or None}
-    med_step = float(np.median(step_s)) if step_s.size else float("nan")
     out = {
-        "metric": "scans/sec (ICP registration only), 128k-pt scan vs 1M-pt map",
-        "value": round(value, 2),
+        **headline,
         **({} if elapsed_serial is None else {"value_one_scan_in_flight": round(serial_steps * B / elapsed_serial, 2)}),
-        "unit": "scans/s",
-        "n_gpus": world,
         **({"comm": comm, "scaling_bound": _scaling_bound(world)} if exchange and world > 1 else {}),
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(1e3 * elapsed / args.steps, 5),
-        "higher_is_better": True,
-        "scaling": "weak" if replicas else "strong",
-        "vs_baseline": None,
-        "dtype": "f64",
-        "data": "synthetic",
-        "config": {"workload": "%s: %d-pt %d-beam scan vs %d-pt / %d-voxel map, voxel %.2f m, tau %.4f m, default ICP iterations "
+        "config": {**config,
+                   "workload": "%s: %d-pt %d-beam scan vs %d-pt / %d-voxel map, voxel %.2f m, tau %.4f m, default ICP iterations "
                                "(mean %.2f per scan, reference %.2f); one step = one kicp_register_device_batch call = %d independent scans against the fixed map, %s; "
                                "%d distinct scans cycled"
                                % (cfg.name, n_total, cfg.n_beams, gmap.num_points(), gmap.num_voxels(), cfg.voxel_size, tau, iters_gpu,
                                   float(np.mean(iters_ref)), B,
                                   ("up to %d in flight at a time (every scan's result bit-identical to registering it alone)" % in_flight) if in_flight > 1
                                   else "registered one after the other", len(scans)),
-                   "scans_in_flight": in_flight,
-                   "scans_per_step": B, "distinct_scans": len(scans), "ms_per_scan": round(1e3 * elapsed / n_scans_timed, 5), "timed_region_s": round(elapsed, 4),
-                   "batch_resized_after_short_timed_region": resized,
-                   "ms_per_step_median": round(1e3 * med_step, 5),
-                   "ms_per_step_min_max": [round(1e3 * float(step_s.min()), 5), round(1e3 * float(step_s.max()), 5)] if step_s.size else None,
-                   "points_per_gpu": hi - lo,
                    "scans_per_s_one_python_call_per_scan": round((world if replicas else 1) * n_scans_timed / elapsed_py, 2),
-                   "parallelism": ("%d independent replicas (one robot per GPU), no exchange" % world) if replicas else
-                                  (("points sharded x%d, map replicated, %s exchange of the 24 limb words per ICP pass, %d sharded scan(s) in flight per rank"
-                                    % (world, args.comm, in_flight)) if use_comm else "single GPU"),
-                   "pass_kernel": pass_kernel, "launch_path": launch_path, "host_placement": host_placement, "max_pose_abs_diff_vs_oracle": max_pose_err,
+                   "pass_kernel": pass_kernel, "max_pose_abs_diff_vs_oracle": max_pose_err,
                    "poses_checked_against_the_oracle": len(iters_ref_multi) + len(iters_ref),
                    "poses_of_the_timed_region_checked": timed_checked + timed_checked_multi,
                    "poses_of_the_timed_region_check": "every pose the timed batch calls returned (headline %d, multi-iteration %d; the batches as their last step left "
@@ -870,8 +930,7 @@ def main():
                        "ms_per_scan": round(1e3 * elapsed_multi / n_scans_timed, 5),
                        "ms_per_iteration": None if not np.isfinite(iters_gpu_multi) else round(1e3 * elapsed_multi / n_scans_timed / iters_gpu_multi, 5),
                        "pass_kernel_avg_us": round(float(pass_ms_multi.mean() * 1e3), 2) if pass_ms_multi.size else None},
-                   "scans_per_s_with_host_input_incl_pcie": None if host_rate is None else round(host_rate, 1), **other,
-                   **({"comm_note": comm_note} if comm_note else {})},
+                   "scans_per_s_with_host_input_incl_pcie": None if host_rate is None else round(host_rate, 1), **other},
         "value_median_step": None if not np.isfinite(med_step) else
         {"scans_per_s": round((world if replicas else 1) * B / med_step, 2), "ms_per_step": round(1e3 * med_step, 5),
          "what": "the median of the %d timed steps (rank 0's clock between steps; `value` is the contract's K steps / elapsed)" % args.steps},
@@ -899,15 +958,7 @@ def main():
         "cpu_baseline": cpu,
         **({} if pipeline is None else {"pipeline": pipeline}),
     }
-    if elapsed < 0.25:
-        out["config"]["warning"] = "timed region shorter than 0.25 s: raise --steps or --scans-per-step (0 = automatic)"
-    import ctypes
-    ctypes.CDLL(None).fflush(None)
-    sys.stdout.flush()
-    os.dup2(saved_stdout, 1)
-    print(json.dumps(out), flush=True)
-    if leaked:  # (see the probe above: no destructor for the failed RCCL handle)
-        os._exit(0)
+    emit(out)
 
 
 def _scaling_bound(world):

@@ -156,7 +156,7 @@ def test_bench_launch_path_with_two_ranks_on_one_gpu():
     every time.  No retry."""
     env = dict(os.environ, KICP_BENCH_DEVICE="0", HSA_ENABLE_IPC_MODE_LEGACY="0", KICP_BENCH_RANK_SKEW_S="0.3")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--scans-per-step", "4",
+           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--full", "--steps", "3", "--warmup", "1", "--scans-per-step", "4",
            "--workload", "cfg1", "--comm", "shm", "--pg-backend", "gloo", "--no-cpu-baseline", "--no-sharded-cfg5"]
     p = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=600)
     # (the first rank's own traceback first - the other rank only reports the closed connection)

@@ -7,8 +7,8 @@
 #   timeline   one frame's kernels, start offsets and queues, from a kernel trace of the drive
 #   pipeab     the same drive under sets of environment switches (AB_SETS), with the calls' wall times and their laps
 #   pipetrace  rocprofv3 kernel trace of the raw_ahead drive (pre-step / map kernels per frame)
-#   bench      bench.py at the default workload (cfg2), the driver's command
-#   benchall   bench.py for cfg1, cfg4, cfg5 as well
+#   bench      bench.py --full at the default workload (cfg2)
+#   benchall   bench.py --full for cfg1, cfg4, cfg5 as well
 #   trace      rocprofv3 --kernel-trace --stats of the bench command
 #   counters   PMC passes of the pass kernel (cfg2, cfg5)
 #   counters4  the same for cfg4's wave-per-query kernel (FETCH_SIZE / WRITE_SIZE / TCC), one launch per pass
@@ -70,12 +70,12 @@ pipeab)   # A/B of environment switches on the drop-in frame: AB_SETS="A=1,B=2 A
     done
   done 2>&1 | sort -s -k1,2 | tee $O/pipeline_ab.txt ;;
 bench)
-  timeout 600 python bench.py > $O/bench_n1.json 2> $O/bench_n1.err; echo "bench rc=$?"; tail -c 600 $O/bench_n1.json; echo ;;
+  timeout 600 python bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err; echo "bench rc=$?"; tail -c 600 $O/bench_n1.json; echo ;;
 benchall)
-  for w in cfg1 cfg4; do timeout 400 python bench.py --workload $w --cpu-seconds 6 --scans 16 --no-pmc > $O/bench_$w.json 2> $O/bench_$w.err; echo "$w rc=$?"; done
-  timeout 500 python bench.py --workload cfg5 --cpu-seconds 6 --scans 16 > $O/bench_cfg5.json 2> $O/bench_cfg5.err; echo "cfg5 rc=$?" ;;
+  for w in cfg1 cfg4; do timeout 400 python bench.py --full --workload $w --cpu-seconds 6 --scans 16 --no-pmc > $O/bench_$w.json 2> $O/bench_$w.err; echo "$w rc=$?"; done
+  timeout 500 python bench.py --full --workload cfg5 --cpu-seconds 6 --scans 16 > $O/bench_cfg5.json 2> $O/bench_cfg5.err; echo "cfg5 rc=$?" ;;
 trace)
-  timeout 300 rocprofv3 --kernel-trace --stats -d $O/kt_bench -o kt -- python bench.py --steps 10 --no-cpu-baseline --no-pmc --scans 16 > $O/bench_under_rocprofv3.json 2> $O/kt_bench.err
+  timeout 300 rocprofv3 --kernel-trace --stats -d $O/kt_bench -o kt -- python bench.py --full --steps 10 --no-cpu-baseline --no-pmc --scans 16 > $O/bench_under_rocprofv3.json 2> $O/kt_bench.err
   python tools/prof_summary.py $(find $O/kt_bench -name "*.db" | head -1) > $O/kernel_trace_stats.txt 2>&1; head -12 $O/kernel_trace_stats.txt | cut -c1-160
   rm -rf $O/kt_bench ;;
 counters)
@@ -108,7 +108,7 @@ counters4)  # cfg4 (1 080-point scans, the wave-per-query kernel): HBM traffic p
   rm -rf $O/kt_cfg4 $O/pmc_cfg4_* ;;
 ranks2)
   for comm in shm rccl; do
-    KICP_BENCH_DEVICE=0 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29671 bench.py --gpus 2 --comm $comm --pg-backend gloo --no-cpu-baseline --no-pmc --scans 16 > $O/bench_2ranks_1gpu_$comm.json 2> $O/bench_2ranks_1gpu_$comm.err
+    KICP_BENCH_DEVICE=0 timeout 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29671 bench.py --gpus 2 --full --comm $comm --pg-backend gloo --no-cpu-baseline --no-pmc --scans 16 > $O/bench_2ranks_1gpu_$comm.json 2> $O/bench_2ranks_1gpu_$comm.err
     echo "2 ranks / 1 GPU, $comm: rc=$?"; tail -c 400 $O/bench_2ranks_1gpu_$comm.json; echo
   done ;;
 smoke)
