@@ -306,6 +306,23 @@ typedef struct kicp_cloud_layout {
 } kicp_cloud_layout;
 int kicp_pre_ingest(kicp_pre *pre, const void *data, size_t n_points, const kicp_cloud_layout *layout, const double sensor_pose_qt[7],
                     double *out_min_stamp, double *out_max_stamp);
+/* 2-D LaserScan ingest: the raw ranges of a sensor_msgs::msg::LaserScan go to the GPU (4 bytes per beam) and are projected there,
+ * into the slot kicp_pre_ingest fills.  Replaces the 2-D LiDAR mode of the node:
+ *   ros/src/kinematic_icp_ros/nodes/online_node.cpp:44-58  laser_projector_.projectLaser(*msg, cloud, -1.0, channel_option::Timestamp)
+ *                                                          (laser_geometry 2.x: the cosine table, cached per projector - here per
+ *                                                          handle -, the range cutoff, x y z and the per-beam field "stamps")
+ *   then, on that cloud, what kicp_pre_ingest replaces: TimeStampHandler.cpp:42-52,57-106,121-128 (the FLOAT32 stamp branch, min /
+ *   max, normalisation - including its 0/0 when every kept stamp is equal) and RosUtils.cpp:30-39 (float x y z widened to double).
+ * laser_geometry is not part of the reference tree: its rules are RECALLED, all in one place (kicp_pre.hpp, laser_rules).
+ * range_cutoff < 0 (what the node passes) means range_max.  Afterwards kicp_pre_ingested_count is the number of kept beams,
+ * kicp_pre_ingested returns the projected cloud (has_stamps = 1 when a beam was kept), and kicp_pre_preprocess_ingested /
+ * kicp_pre_frame_ingested work on it.  out_min/max_stamp: the kept beams' stamps in seconds (0 when none was kept).  A pending
+ * kicp_pre_ingest_ahead announcement is void.  No validation beyond the pointers: a NaN angle gives NaN points, as in laser_geometry. */
+typedef struct kicp_laser_scan { /* the sensor_msgs::msg::LaserScan fields projectLaser reads */
+    float angle_min, angle_max, angle_increment, time_increment, range_min, range_max;
+} kicp_laser_scan;
+int kicp_pre_ingest_scan(kicp_pre *pre, const float *ranges, size_t n_ranges, const kicp_laser_scan *scan, double range_cutoff,
+                         double *out_min_stamp, double *out_max_stamp);
 /* LOOK-AHEAD (round 5; a node that knows its next message - a bag replay, a queue of depth 2): announce the NEXT cloud.  Nothing is
  * copied yet; the next kicp_pre_frame[_ingested] call - the pre-steps of the CURRENT cloud - uploads and decodes the announced one into
  * a second slot on a stream of its own once its own kernels are queued, so the 2 MB of message k + 1 cross PCIe while the GPU works on

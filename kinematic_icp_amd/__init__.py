@@ -102,6 +102,7 @@ _SIGNATURES = {
                                       C.POINTER(C.c_size_t)]),
     "kicp_pre_ingest": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, _dp, _dp, _dp]),
     "kicp_pre_ingest_ahead": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, _dp]),
+    "kicp_pre_ingest_scan": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_double, _dp, _dp]),
     "kicp_pre_ahead_hits": (C.c_ulonglong, [C.c_void_p]),
     "kicp_pre_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_double]),
     "kicp_pre_get_option": (C.c_double, [C.c_void_p, C.c_char_p]),
@@ -556,6 +557,12 @@ class CloudLayout(C.Structure):
 FIELD_UINT32, FIELD_FLOAT32, FIELD_FLOAT64 = 6, 7, 8  # sensor_msgs::msg::PointField datatype codes
 
 
+class LaserScan(C.Structure):
+    """kicp_laser_scan (include/kicp.h): the sensor_msgs::msg::LaserScan fields laser_geometry's projectLaser reads."""
+    _fields_ = [("angle_min", C.c_float), ("angle_max", C.c_float), ("angle_increment", C.c_float), ("time_increment", C.c_float),
+                ("range_min", C.c_float), ("range_max", C.c_float)]
+
+
 class PreSteps:
     """The pipeline's pre-steps on the GPU: kiss_icp::Preprocessor::Preprocess + transform_points, kiss_icp::VoxelDownsample
     (pipeline/KinematicICP.cpp:54-62).  Results live in numbered device buffers; frame(b) wraps one for ComputeRobotMotion."""
@@ -595,6 +602,17 @@ class PreSteps:
         q = None if sensor_pose is None else _d(sensor_pose)[1]
         lo, hi = C.c_double(), C.c_double()
         _check(lib().kicp_pre_ingest(self._h, buf.ctypes.data if buf.size else None, n_points, C.byref(layout), q, C.byref(lo), C.byref(hi)))
+        return lo.value, hi.value
+
+    def IngestScan(self, ranges, angle_min, angle_max, angle_increment, time_increment, range_min, range_max, range_cutoff=-1.0):
+        """2-D LaserScan ingest (kicp_pre_ingest_scan): laser_geometry's projectLaser(scan, cloud, range_cutoff, Timestamp) of the
+        2-D node (online_node.cpp:44-58) on the GPU, then what Ingest does with the projected cloud.  `ranges`: msg.ranges (float32).
+        Returns (min_stamp, max_stamp) of the kept beams in seconds (0, 0 when none was kept)."""
+        r = np.ascontiguousarray(ranges, dtype=np.float32).ravel()
+        scan = LaserScan(angle_min, angle_max, angle_increment, time_increment, range_min, range_max)
+        lo, hi = C.c_double(), C.c_double()
+        _check(lib().kicp_pre_ingest_scan(self._h, r.ctypes.data if r.size else None, r.size, C.byref(scan), float(range_cutoff),
+                                          C.byref(lo), C.byref(hi)))
         return lo.value, hi.value
 
     def IngestAhead(self, raw, n_points, point_step, offset_x, offset_y, offset_z, stamp_datatype=0, offset_stamp=0, sensor_pose=None):

@@ -142,6 +142,15 @@ public:
         kicp_bridge::check(kicp_pre_ingest(pre_, data, n_points, &layout, nullptr, &lo, &hi), "IngestCloud");
         return {layout.stamp_datatype != 0 && n_points != 0, lo, hi};
     }
+    // IngestScan is the 2-D LiDAR mode of the node (online_node.cpp:44-58): laser_geometry's projectLaser(*msg, cloud, range_cutoff,
+    // channel_option::Timestamp) and then what IngestCloud does with that cloud, on the GPU from the raw ranges (kicp.h
+    // kicp_pre_ingest_scan).  `ranges` = msg->ranges.data(), n = msg->ranges.size().  It returns {a beam was kept, min stamp, max
+    // stamp} like IngestCloud; RegisterIngestedFrame then registers the projected scan.
+    std::tuple<bool, double, double> IngestScan(const float *ranges, size_t n, const kicp_laser_scan &scan, double range_cutoff = -1.0) {
+        double lo = 0.0, hi = 0.0;
+        kicp_bridge::check(kicp_pre_ingest_scan(pre_, ranges, n, &scan, range_cutoff, &lo, &hi), "IngestScan");
+        return {kicp_pre_ingested_count(pre_) != 0, lo, hi};
+    }
     // Look-ahead for callers that already hold the NEXT message (a bag replay; ros/src/kinematic_icp_ros/nodes/offline_node.cpp reads
     // its messages in a loop): announce it before RegisterIngestedFrame of the current one - it is then uploaded and decoded while the
     // current frame's pre-steps run, and its IngestCloud call returns at once.  The bytes must stay valid until that IngestCloud call.

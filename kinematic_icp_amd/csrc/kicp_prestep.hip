@@ -30,7 +30,8 @@ struct kicp_pre {
     // writes for the host, and how often the guess was wrong (the unfused steps then run from buffer 0 on)
     uint32_t spec_tiles_b = 0;  // 256-bucket tiles of the previous frame's second-level table (sizes that level's launches)
     uint32_t spec_n0 = 0, spec_n_in = 0;  // (... and the input count it belonged to: the guess scales with the frame)
-    unsigned long long *h_rec = nullptr;  // pinned, host-coherent: [0..4] the chain's tagged words, [8..10] / [12..14] the ingest records (this call's / the look-ahead's),
+    unsigned long long *h_rec = nullptr;  // pinned, host-coherent: [0..4] the chain's tagged words, [8..10] / [12..14] the ingest records (this call's / the look-ahead's;
+                                          // [11]: a scan's kept beams, k_ingest_scan),
                                           // [16..23] the pushed frame's piece flags (k_push_frame)
     unsigned long long *d_push_tickets = nullptr;  // [kPushPieces] device counters of k_push_frame, never reset
     unsigned long long push_drawn = 0;
@@ -106,6 +107,14 @@ struct kicp_pre {
     hipStream_t ingest_stream2 = nullptr;  // this call's message: its pieces' decodes alternate between the handle's stream and this one
     bool ahead_job_out = false;         // ... and is only waited for where its result (or a buffer it uses) is needed: ahead_join
     HostStage stage_ahead;              // its own pinned staging buffer (the calling thread goes on using `stage` meanwhile)
+    // 2-D LaserScan ingest (kicp_pre_ingest_scan): the projector's cosine table in HBM and the key it was built for (kicp_pre.hpp
+    // laser_rules: one table per projector, kept while n, angle_min and angle_max stay the same)
+    double *d_scan_cs = nullptr;
+    size_t scan_cs_cap = 0;
+    std::vector<double> scan_cs_host;
+    bool scan_table = false;
+    size_t scan_n = 0;
+    float scan_angle_min = 0.0f, scan_angle_max = 0.0f;
     // the chained pre-steps hand the WHOLE download of buffer 0 to the helper thread (its dozen API calls cost the calling thread ~40 us):
     bool copy_job_begins = false;       // the posted job starts with download_queue(0, copy_job_n, after chain_ready)
     bool copy_job_push = false;         // the frame arrives as k_push_frame's pieces, announced in h_rec[16..]: the job only follows them
@@ -235,7 +244,7 @@ void kicp_pre_destroy(kicp_pre *p) {
     if (p->h_src) hipHostFree(p->h_src);
     hipFree(p->d_in), hipFree(p->d_ts), hipFree(p->d_in2), hipFree(p->d_ts2), hipFree(p->d_staged), hipFree(p->d_flags), hipFree(p->d_block_counts), hipFree(p->d_table);
     hipFree(p->d_table2), hipFree(p->d_counts1), hipFree(p->d_counts2);
-    hipFree(p->d_misc), hipFree(p->d_raw), hipFree(p->d_block_minmax), hipFree(p->d_ticket), hipFree(p->d_push_tickets);
+    hipFree(p->d_misc), hipFree(p->d_raw), hipFree(p->d_block_minmax), hipFree(p->d_ticket), hipFree(p->d_push_tickets), hipFree(p->d_scan_cs);
     p->stage.release();
     if (p->copy_thread.joinable()) {  // the helper thread finishes the job it has, then leaves
         {
@@ -310,6 +319,16 @@ int wait_word(const volatile unsigned long long *word, unsigned long long want, 
 // Round 5 pulled the bytes into HBM (k_pull_bytes per piece), decoded them with one more launch, normalised the stamps with another
 // and copied the extrema back: four stream operations and 6 MB of traffic more per frame.
 constexpr size_t kIngestPiece = 512u << 10;
+// d_raw: the message bytes in HBM, where the device cannot read the staging buffer
+int raw_reserve(kicp_pre *p, size_t bytes) {
+    if (bytes <= p->raw_cap) return KICP_OK;
+    HIP_TRY(hipDeviceSynchronize());  // (rare: the buffer grows; nothing may still be reading the old one)
+    hipFree(p->d_raw);
+    p->d_raw = nullptr, p->raw_cap = 0;
+    HIP_TRY(hipMalloc(&p->d_raw, bytes + bytes / 4 + 4096));
+    p->raw_cap = bytes + bytes / 4 + 4096;
+    return KICP_OK;
+}
 int ingest_run(kicp_pre *p, const void *data, size_t n_points, const kicp_cloud_layout &L, const Pose *sensor_pose, hipStream_t stream, double *out_xyz,
                double *out_ts, HostStage &stage, int slot, double *out_lo, double *out_hi) {
     const int st = L.stamp_datatype;
@@ -318,13 +337,8 @@ int ingest_run(kicp_pre *p, const void *data, size_t n_points, const kicp_cloud_
     if (int rc = stage_begin(stage, bytes, stream)) return rc;
     if (slot == 0) trace_lap("staging buffer free");
     const bool direct = stage.dev != nullptr;  // the device reads the staging buffer itself
-    if (!direct && bytes > p->raw_cap) {
-        HIP_TRY(hipDeviceSynchronize());  // (rare: the buffer grows; nothing may still be reading the old one)
-        hipFree(p->d_raw);
-        p->d_raw = nullptr, p->raw_cap = 0;
-        HIP_TRY(hipMalloc(&p->d_raw, bytes + bytes / 4 + 4096));
-        p->raw_cap = bytes + bytes / 4 + 4096;
-    }
+    if (!direct)
+        if (int rc = raw_reserve(p, bytes)) return rc;
     IngestParams ip{};
     ip.point_step = L.point_step;
     ip.off_x = L.offset_x, ip.off_y = L.offset_y, ip.off_z = L.offset_z, ip.off_t = L.offset_stamp, ip.stamp_type = st;
@@ -461,6 +475,77 @@ int kicp_pre_ingest(kicp_pre *p, const void *data, size_t n_points, const kicp_c
     p->ts_raw = st != 0, p->ts_lo = lo, p->ts_hi = hi;
     if (out_min_stamp) *out_min_stamp = lo;
     if (out_max_stamp) *out_max_stamp = hi;
+    return KICP_OK;
+}
+namespace {
+// The projector's cosine table for this scan: rebuilt on the host (glibc cos / sin) and uploaded only when its key changes
+// (laser_geometry's cache, kicp_pre.hpp laser_rules [RECALLED])
+int scan_table(kicp_pre *p, size_t n, const kicp_laser_scan &s) {
+    if (!laser_rules::table_stale(p->scan_table, n, s.angle_min, s.angle_max, p->scan_n, p->scan_angle_min, p->scan_angle_max)) return KICP_OK;
+    p->scan_table = false;  // (until the new one is in place)
+    p->scan_cs_host.resize(2 * n);
+    for (size_t i = 0; i < n; ++i) laser_rules::table_entry(s.angle_min, s.angle_increment, static_cast<uint32_t>(i), p->scan_cs_host[2 * i], p->scan_cs_host[2 * i + 1]);
+    if (n * 16 > p->scan_cs_cap) {
+        hipFree(p->d_scan_cs);  // (nothing reads it: every scan ingest returns after its kernel)
+        p->d_scan_cs = nullptr, p->scan_cs_cap = 0;
+        HIP_TRY(hipMalloc(&p->d_scan_cs, n * 16 + n * 4 + 4096));
+        p->scan_cs_cap = n * 16 + n * 4 + 4096;
+    }
+    if (n)
+        if (int rc = staged_upload(p->stage, 0, p->d_scan_cs, p->scan_cs_host.data(), n * 16, p->stream)) return rc;
+    p->scan_table = true, p->scan_n = n, p->scan_angle_min = s.angle_min, p->scan_angle_max = s.angle_max;
+    return KICP_OK;
+}
+}  // namespace
+int kicp_pre_ingest_scan(kicp_pre *p, const float *ranges, size_t n_ranges, const kicp_laser_scan *scan, double range_cutoff, double *out_min_stamp,
+                         double *out_max_stamp) {
+    KICP_TRACE_CALL();
+    if (!p || !scan || (!ranges && n_ranges)) return fail(KICP_ERR_ARG, "bad argument");
+    if (n_ranges > 0x7FFFFFF0ull / 3) return fail(KICP_ERR_CAPACITY, "scan too large");
+    if (int rc = set_device(p->device)) return rc;
+    if (out_min_stamp) *out_min_stamp = 0.0;
+    if (out_max_stamp) *out_max_stamp = 0.0;
+    if (int rc = ahead_join(p)) return rc;
+    p->ahead.state = 0;  // (another message than the one announced: the announcement is void)
+    p->ingested = false, p->ts_raw = false, p->ts_lo = p->ts_hi = 0.0;
+    const kicp_laser_scan &s = *scan;
+    if (int rc = scan_table(p, n_ranges, s)) return rc;
+    if (n_ranges == 0) {
+        p->ingested = true, p->ingested_n = 0, p->ingested_stamps = false;
+        return KICP_OK;
+    }
+    if (int rc = pre_ensure(p, n_ranges)) return rc;
+    // the ranges go up as a cloud's bytes do (ingest_run): into the pinned staging buffer, read from there by the kernel
+    const size_t bytes = n_ranges * 4;
+    if (int rc = stage_begin(p->stage, bytes, p->stream)) return rc;  // (waits for the table's upload, if there was one)
+    std::memcpy(p->stage.p, ranges, bytes);
+    ScanParams sp{};
+    if (p->stage.dev) {
+        sp.ranges = reinterpret_cast<const float *>(p->stage.dev);
+    } else {
+        if (int rc = raw_reserve(p, bytes)) return rc;
+        HIP_TRY(hipMemcpyAsync(p->d_raw, p->stage.p, bytes, hipMemcpyHostToDevice, p->stream));
+        sp.ranges = reinterpret_cast<const float *>(p->d_raw);
+    }
+    const uint32_t tiles = static_cast<uint32_t>((n_ranges + kScanTile - 1) / kScanTile);
+    sp.tiles_per_wg = (tiles + kScanMaxWgs - 1) / kScanMaxWgs;
+    const uint32_t grid = (tiles + sp.tiles_per_wg - 1) / sp.tiles_per_wg;  // (no workgroup without a tile)
+    sp.cs = p->d_scan_cs, sp.n = static_cast<uint32_t>(n_ranges);
+    sp.range_min = s.range_min, sp.time_increment = s.time_increment, sp.cutoff = laser_rules::cutoff(range_cutoff, s.range_max);
+    sp.out_xyz = p->d_in, sp.out_stamps = p->d_ts, sp.wg_counts = p->d_block_counts, sp.block_minmax = p->d_block_minmax;
+    p->ticket_drawn[0] += grid;
+    sp.ticket = p->d_ticket, sp.ticket_done = p->ticket_drawn[0];
+    unsigned long long *rec = p->h_rec + 8;
+    sp.host_rec = rec, sp.seq = ++p->ingest_seq;
+    hipLaunchKernelGGL(k_ingest_scan, dim3(grid), dim3(256), 0, p->stream, sp);
+    HIP_TRY(hipGetLastError());
+    if (int rc = wait_word(rec + 2, sp.seq, ~0ull, p->stream)) return rc;  // (the staging buffer is free again behind this)
+    const size_t kept = static_cast<size_t>(rec[3]);
+    p->ingested = true, p->ingested_n = kept, p->ingested_stamps = kept != 0;
+    p->ts_raw = kept != 0;
+    if (kept) p->ts_lo = ordered_value(rec[0]), p->ts_hi = ordered_value(rec[1]);
+    if (out_min_stamp) *out_min_stamp = p->ts_lo;
+    if (out_max_stamp) *out_max_stamp = p->ts_hi;
     return KICP_OK;
 }
 int kicp_pre_ingest_ahead(kicp_pre *p, const void *data, size_t n_points, const kicp_cloud_layout *layout, const double sensor_pose_qt[7]) {

@@ -285,3 +285,51 @@ def extra_scans(cfg, scene, n, seed, order="ring", raycast=None):
         last = pose_mul(guess, pose_inverse(rel))
         scans.append(dict(frame=np.ascontiguousarray(pts), last_pose=last, rel_odom=rel, true_pose=true_pose))
     return scans
+
+
+# --------------------------------------------------------------------------------------------
+# 2-D LaserScans (cfg4's sensor: 270 deg at 0.25 deg, 40 Hz) - the raw sensor_msgs::msg::LaserScan fields
+# --------------------------------------------------------------------------------------------
+def laser_scan_params(n_beams=1080, span_deg=270.0, rate_hz=40.0, range_min=0.05, range_max=25.0):
+    """The LaserScan header fields as a driver fills them (float32 values, returned as python floats): angle_max is the last
+    beam's angle, time_increment the scan period spread over the beams."""
+    f32 = np.float32
+    inc = f32(np.deg2rad(span_deg) / n_beams)
+    angle_min = f32(-np.deg2rad(span_deg) / 2)
+    angle_max = f32(angle_min + f32(n_beams - 1) * inc)
+    return dict(angle_min=float(angle_min), angle_max=float(angle_max), angle_increment=float(inc),
+                time_increment=float(f32(1.0 / rate_hz / n_beams)), range_min=float(f32(range_min)), range_max=float(f32(range_max)))
+
+
+def make_laser_drive(n_frames, seed=SEED_BASE + 40, params=None, dropout=0.03, step=0.2):
+    """A seeded planar drive through cfg4's scene with a 2-D scanner at cfg4's height, `step` m forward per frame while turning.
+
+    Returns (params, lidar_to_base, frames): params = laser_scan_params(); frames = [dict(ranges=(n,) float32 - ray-cast ranges with
+    1 cm noise, beams beyond range_max and a `dropout` share of the others without a return (NaN or +inf), two beams exactly on
+    range_min and two exactly on range_max -, rel_odom = the planar wheel-odometry delta since the previous frame (the true motion
+    with a small error), true_pose)]."""
+    cfg = CONFIGS["cfg4"]
+    rng = np.random.Generator(np.random.PCG64(seed))
+    scene = make_scene(rng, **cfg.scene_kw)
+    params = params or laser_scan_params()
+    n = int(round((params["angle_max"] - params["angle_min"]) / params["angle_increment"])) + 1
+    ang = (np.float32(params["angle_min"]) + np.arange(n, dtype=np.float32) * np.float32(params["angle_increment"])).astype(np.float64)
+    dirs = np.stack([np.cos(ang), np.sin(ang), np.zeros(n)], axis=1)
+    lidar_to_base = planar_pose(0.15, 0.0, 0.0, z=cfg.sensor_height)
+    rmin, rmax = np.float32(params["range_min"]), np.float32(params["range_max"])
+    pose = planar_pose(0.0, 0.0, rng.uniform(-np.pi, np.pi))
+    frames = []
+    for k in range(n_frames):
+        delta = planar_pose(step, 0.0, np.deg2rad(rng.uniform(-4.0, 4.0))) if k else IDENTITY.copy()
+        pose = pose_mul(pose, delta)
+        sensor = pose_mul(pose, lidar_to_base)
+        t = scene.raycast(sensor[4:], dirs @ quat_to_matrix(sensor[:4]).T) + rng.normal(0.0, 0.01, n)
+        r = t.astype(np.float32)
+        r[r > rmax] = np.inf                                      # no return within range
+        lost = rng.random(n) < dropout
+        r[lost] = np.where(rng.random(int(lost.sum())) < 0.5, np.nan, np.inf).astype(np.float32)
+        at = rng.choice(n, 4, replace=False)
+        r[at[:2]], r[at[2:]] = rmin, rmax                         # exactly on the bounds (range_min kept, range_max dropped)
+        odom = pose_mul(delta, planar_pose(rng.normal(0.0, 0.005), 0.0, np.deg2rad(rng.normal(0.0, 0.1)))) if k else IDENTITY.copy()
+        frames.append(dict(ranges=r, rel_odom=odom, true_pose=pose.copy()))
+    return params, lidar_to_base, frames
