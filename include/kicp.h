@@ -123,6 +123,14 @@ size_t kicp_map_num_points(const kicp_map *map);
 size_t kicp_map_num_voxels(const kicp_map *map);
 /* Pointcloud() -- KinematicICP.hpp:92.  Writes min(cap_points, total) points, returns total. */
 size_t kicp_map_pointcloud(const kicp_map *map, double *out_xyz, size_t cap_points);
+/* The same cloud as the PointCloud2 `data` the node publishes for it (ros/.../utils/RosUtils.cpp:40-63 EigenToPointCloud2 of
+ * LocalMap(), called from LidarOdometryServer.cpp:240-263 PublishClouds): x y z FLOAT32 records of 12 bytes (offsets 0 4 8,
+ * little-endian), static_cast<float> of kicp_map_pointcloud's doubles, its order and its count.  Writes min(cap_points, total)
+ * records (out_xyz may be NULL with cap_points 0: *out_total only).  A map whose HBM copy is the current one is narrowed on the
+ * GPU, which writes the records into host-mapped memory piece by piece (kicp_mapdev.hpp k_pc_records; no fp64 copy crosses
+ * PCIe); a map that lives on the host is narrowed there, with the same bits.  Unlike kicp_map_pointcloud it returns an error
+ * code: a pending deferred update is collected first and its error is returned. */
+int kicp_map_pointcloud_f32(const kicp_map *map, float *out_xyz, size_t cap_points, size_t *out_total);
 /* GetClosestNeighbor(query) for n queries -- Registration.cpp:74.  Host arrays in/out; runs on `device` the plain fp64 search
  * over the 27 neighbour voxels (kicp_kernels.hpp search_global: the reference's loop, and the exact fallback of the fused pass
  * kernels - NOT their mirror pre-selection: what the shipped pass kernels pick per query is what kicp_pass_correspondences returns).
@@ -368,6 +376,19 @@ int kicp_pre_frame(kicp_pre *pre, const double *frame_xyz, size_t n, const doubl
 int kicp_pre_frame_ingested(kicp_pre *pre, const double relative_motion_qt[7], const double lidar_to_base_qt[7], double max_range,
                             double min_range, int deskew, double voxel_a, double voxel_b, double *out_frame_xyz, size_t cap_points,
                             size_t out_counts[3]);
+/* kicp_pre_frame / kicp_pre_frame_ingested with the returned frame as the PointCloud2 `data` the node publishes for it
+ * (RosUtils.cpp:40-63 EigenToPointCloud2 of the frame, LidarOdometryServer.cpp:240-263 PublishClouds): out_frame_xyz receives
+ * x y z FLOAT32 records, static_cast<float> of the fp64 frame's doubles - the GPU narrows them on the way out, so 12 bytes per
+ * point cross PCIe (kicp_pre.hpp k_push_frame_f32).  out_frame_xyz may be NULL: then nothing is pushed at all (the node's "no
+ * subscriber" case).  Otherwise collect it with kicp_pre_download_finish(pre, 0, NULL, 0, &n), as the fp64 entries' frame; the
+ * first out_counts[0] records are the frame.  Buffer 2's host copy then holds records too: kicp_pre_download_f32(pre, 2, ...)
+ * reads it; kicp_pre_download(pre, 2, ...) still returns the doubles (from HBM).  Everything else as the fp64 entries. */
+int kicp_pre_frame_f32(kicp_pre *pre, const double *frame_xyz, size_t n, const double *timestamps, size_t n_timestamps,
+                       const double relative_motion_qt[7], const double lidar_to_base_qt[7], double max_range, double min_range, int deskew,
+                       double voxel_a, double voxel_b, float *out_frame_xyz, size_t cap_points, size_t out_counts[3]);
+int kicp_pre_frame_ingested_f32(kicp_pre *pre, const double relative_motion_qt[7], const double lidar_to_base_qt[7], double max_range,
+                                double min_range, int deskew, double voxel_a, double voxel_b, float *out_frame_xyz, size_t cap_points,
+                                size_t out_counts[3]);
 size_t kicp_pre_ingested_count(const kicp_pre *pre);
 /* Backend knobs of the chained pre-steps (not part of the reference API):
  *   "fused"  1 (default; KICP_PRE_FUSED=0 in the environment): kicp_pre_frame* run the frame's pre-steps as FIVE launches
@@ -381,6 +402,11 @@ int kicp_pre_set_option(kicp_pre *pre, const char *name, double value);
 double kicp_pre_get_option(const kicp_pre *pre, const char *name);
 int kicp_pre_upload(kicp_pre *pre, int buffer, const double *xyz, size_t n);
 int kicp_pre_download(const kicp_pre *pre, int buffer, double *out_xyz, size_t cap_points, size_t *out_n);
+/* The same buffer as x y z FLOAT32 records, static_cast<float> of its doubles (RosUtils.cpp:40-63 EigenToPointCloud2,
+ * LidarOdometryServer.cpp:240-263 PublishClouds: buffer 2 is the published keypoints).  After a kicp_pre_frame*_f32 call buffer 2's
+ * records are already in host memory (narrowed by the chain's last launch); otherwise the GPU narrows the buffer and 12 bytes per
+ * point are downloaded. */
+int kicp_pre_download_f32(const kicp_pre *pre, int buffer, float *out_xyz, size_t cap_points, size_t *out_n);
 /* The same download in the background: _begin queues the copy of the buffer's current contents on a stream of its own
  * (pinned landing area) and returns at once; the caller goes on with the pipeline's next steps and collects the points
  * with _finish.  One download in flight per handle; the buffer must not be refilled in between.  (RegisterFrame returns the

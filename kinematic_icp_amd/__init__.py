@@ -75,6 +75,7 @@ _SIGNATURES = {
     "kicp_map_num_points": (C.c_size_t, [C.c_void_p]),
     "kicp_map_num_voxels": (C.c_size_t, [C.c_void_p]),
     "kicp_map_pointcloud": (C.c_size_t, [C.c_void_p, _dp, C.c_size_t]),
+    "kicp_map_pointcloud_f32": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "kicp_map_closest": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_size_t, _dp, _dp]),
     "kicp_map_check": (C.c_size_t, [C.c_void_p]),
     "kicp_map_sync": (C.c_int, [C.c_void_p, C.c_int]),
@@ -111,12 +112,17 @@ _SIGNATURES = {
     "kicp_pre_frame": (C.c_int, [C.c_void_p, _dp, C.c_size_t, _dp, C.c_size_t, _dp, _dp, C.c_double, C.c_double, C.c_int, C.c_double, C.c_double, _dp, C.c_size_t,
                                  C.POINTER(C.c_size_t)]),
     "kicp_pre_frame_ingested": (C.c_int, [C.c_void_p, _dp, _dp, C.c_double, C.c_double, C.c_int, C.c_double, C.c_double, _dp, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "kicp_pre_frame_f32": (C.c_int, [C.c_void_p, _dp, C.c_size_t, _dp, C.c_size_t, _dp, _dp, C.c_double, C.c_double, C.c_int, C.c_double, C.c_double,
+                                     C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "kicp_pre_frame_ingested_f32": (C.c_int, [C.c_void_p, _dp, _dp, C.c_double, C.c_double, C.c_int, C.c_double, C.c_double, C.c_void_p, C.c_size_t,
+                                              C.POINTER(C.c_size_t)]),
     "kicp_pre_ingested_count": (C.c_size_t, [C.c_void_p]),
     "kicp_pre_voxel_downsample": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_int, C.POINTER(C.c_size_t)]),
     "kicp_pre_last_max_probe": (C.c_uint, [C.c_void_p]),
     "kicp_pre_set_probe_limit": (C.c_int, [C.c_void_p, C.c_uint]),
     "kicp_pre_upload": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_size_t]),
     "kicp_pre_download": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "kicp_pre_download_f32": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]),
     "kicp_pre_download_begin": (C.c_int, [C.c_void_p, C.c_int]),
     "kicp_pre_download_begin_into": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_size_t]),
     "kicp_pre_download_finish": (C.c_int, [C.c_void_p, C.c_int, _dp, C.c_size_t, C.POINTER(C.c_size_t)]),
@@ -309,6 +315,15 @@ class VoxelHashMap:
         n = self.num_points()
         out = np.empty((n, 3), dtype=np.float64)
         lib().kicp_map_pointcloud(self._h, out.ctypes.data_as(_dp), n)
+        return out
+
+    def PointcloudF32(self):
+        """Pointcloud() as the published map's PointCloud2 records (kicp_map_pointcloud_f32): (n, 3) float32, static_cast<float> of
+        Pointcloud(), narrowed on the GPU where the map lives there.  A pending map update's error is raised here."""
+        n = C.c_size_t()
+        _check(lib().kicp_map_pointcloud_f32(self._h, None, 0, C.byref(n)))
+        out = np.empty((n.value, 3), dtype=np.float32)
+        _check(lib().kicp_map_pointcloud_f32(self._h, out.ctypes.data if n.value else None, n.value, C.byref(n)))
         return out
 
     def GetClosestNeighbor(self, queries, device=0):
@@ -677,6 +692,45 @@ class PreSteps:
             _check(lib().kicp_pre_download_finish(self._h, 0, out.ctypes.data_as(_dp), n_in, C.byref(n)))
             out = out[:counts[0]]
         return [int(c) for c in counts], out
+
+    def FrameF32(self, frame, timestamps, relative_motion, lidar_to_base, max_range, min_range, deskew, voxel_a, voxel_b, want_frame=True):
+        """kicp_pre_frame_f32 / kicp_pre_frame_ingested_f32: Frame() with the preprocessed frame returned as PointCloud2 records, (n, 3)
+        float32 narrowed on the GPU (want_frame=False: nothing is pushed).  Returns (counts, records or None); download_f32(2) then
+        reads the keypoints' records."""
+        _, r = _d(relative_motion)
+        _, e = _d(lidar_to_base)
+        counts = (C.c_size_t * 3)()
+        if frame is None:
+            n_in = lib().kicp_pre_ingested_count(self._h)
+            out = np.empty((n_in, 3), dtype=np.float32) if want_frame else None
+            rc = lib().kicp_pre_frame_ingested_f32(self._h, r, e, max_range, min_range, int(deskew), voxel_a, voxel_b,
+                                                   out.ctypes.data if want_frame and n_in else None, n_in, counts)
+        else:
+            a, p = _d(frame)
+            t, tp = _d(timestamps if timestamps is not None else np.zeros(0))
+            n_in = a.size // 3
+            out = np.empty((n_in, 3), dtype=np.float32) if want_frame else None
+            rc = lib().kicp_pre_frame_f32(self._h, p, n_in, tp, t.size, r, e, max_range, min_range, int(deskew), voxel_a, voxel_b,
+                                          out.ctypes.data if want_frame and n_in else None, n_in, counts)
+        if rc < 0:
+            message = lib().kicp_last_error().decode(errors="replace")
+            if want_frame and n_in:  # (as Frame: the helper thread may hold a pointer into `out`)
+                lib().kicp_pre_download_finish(self._h, 0, None, 0, None)
+            raise KicpError(rc, message)
+        self.last_status = rc
+        if want_frame and n_in:
+            n = C.c_size_t()
+            _check(lib().kicp_pre_download_finish(self._h, 0, None, 0, C.byref(n)))
+            out = out[:counts[0]]
+        return [int(c) for c in counts], out
+
+    def download_f32(self, buffer):
+        """kicp_pre_download_f32: a buffer as PointCloud2 records, (n, 3) float32"""
+        n = C.c_size_t()
+        _check(lib().kicp_pre_download_f32(self._h, buffer, None, 0, C.byref(n)))
+        out = np.empty((n.value, 3), dtype=np.float32)
+        _check(lib().kicp_pre_download_f32(self._h, buffer, out.ctypes.data if n.value else None, n.value, C.byref(n)))
+        return out
 
     def VoxelDownsample(self, src, voxel_size, dst):
         n = C.c_size_t()

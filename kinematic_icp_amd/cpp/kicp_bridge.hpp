@@ -4,6 +4,7 @@
 #include <Eigen/Core>
 #include <Eigen/Geometry>
 #include <chrono>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <sophus/se3.hpp>
@@ -45,6 +46,18 @@ inline int default_device() {
     }();
     return device;
 }
+// The record layout of the FLOAT32 clouds the backend writes (VoxelHashMap::PointcloudF32, KinematicICP::LocalMapF32 /
+// RegisterFrameF32 / RegisterIngestedFrameF32): what EigenToPointCloud2 (ros/.../utils/RosUtils.cpp:40-63) declares in the message,
+// so a ROS-side caller fills msg->fields, point_step, height, width and is_bigendian from it and hands msg->data to the backend.
+struct PointCloud2Xyz32 {
+    static constexpr const char *field_names[3] = {"x", "y", "z"};
+    static constexpr uint32_t field_offsets[3] = {0, 4, 8};
+    static constexpr uint8_t datatype = KICP_FIELD_FLOAT32;  // sensor_msgs::msg::PointField::FLOAT32
+    static constexpr uint32_t count = 1;                     // per field
+    static constexpr uint32_t point_step = 12;
+    static constexpr uint32_t height = 1;                    // width = number of points, row_step = 12 * width
+    static constexpr bool is_bigendian = false;
+};
 // The reference's core throws nothing; a backend failure must not return garbage silently.
 inline int check(int rc, const char *what) {
     if (rc < 0) throw std::runtime_error(std::string(what) + ": " + kicp_last_error());

@@ -173,6 +173,47 @@ public:
         if (order == KICP_WARN_TABLE_ORDER) kicp_bridge::warn_once(kicp_last_error());
         return RegisterChained(result, guard, counts, relative_odometry);
     }
+    // ---- backend extension: the published clouds as PointCloud2 `data` (LidarOdometryServer.cpp:240-263 PublishClouds, which
+    // converts each with EigenToPointCloud2, RosUtils.cpp:40-63) ----
+    // RegisterFrameF32 / RegisterIngestedFrameF32 are RegisterFrame / RegisterIngestedFrame - the same pose, threshold and map update -
+    // with the two returned clouds written as x y z FLOAT32 records (kicp_bridge::PointCloud2Xyz32) into the byte vectors a node hands
+    // over as msg->data: the GPU narrows them, 12 bytes per point cross PCIe and the host makes no pass of its own over them.  A null
+    // pointer means the cloud is not produced at all (a topic without subscriber): the frame is then not even pushed.
+    void RegisterFrameF32(const std::vector<Eigen::Vector3d> &frame, const std::vector<double> &timestamps, const Sophus::SE3d &lidar_to_base,
+                          const Sophus::SE3d &relative_odometry, std::vector<uint8_t> *frame_data, std::vector<uint8_t> *keypoints_data) {
+        const Sophus::SE3d relative_odometry_in_lidar = lidar_to_base.inverse() * relative_odometry * lidar_to_base;
+        double rel_lidar[7], ext[7];
+        kicp_bridge::to_params(relative_odometry_in_lidar, rel_lidar);
+        kicp_bridge::to_params(lidar_to_base, ext);
+        float *out = LandFrame(frame_data, frame.size());
+        DownloadGuard guard{pre_, out != nullptr};
+        size_t counts[3] = {0, 0, 0};
+        const int order = kicp_bridge::check(
+            kicp_pre_frame_f32(pre_, kicp_bridge::xyz(frame), frame.size(), timestamps.data(), timestamps.size(), rel_lidar, ext, config_.max_range,
+                               config_.min_range, config_.deskew ? 1 : 0, config_.voxel_size * 0.5, config_.voxel_size * 1.5, out, frame.size(), counts),
+            "Preprocess + VoxelDownsample");
+        if (order == KICP_WARN_TABLE_ORDER) kicp_bridge::warn_once(kicp_last_error());
+        RegisterChainedF32(guard, counts, relative_odometry, frame_data, keypoints_data);
+    }
+    void RegisterIngestedFrameF32(const Sophus::SE3d &lidar_to_base, const Sophus::SE3d &relative_odometry, std::vector<uint8_t> *frame_data,
+                                  std::vector<uint8_t> *keypoints_data) {
+        const Sophus::SE3d relative_odometry_in_lidar = lidar_to_base.inverse() * relative_odometry * lidar_to_base;
+        double rel_lidar[7], ext[7];
+        kicp_bridge::to_params(relative_odometry_in_lidar, rel_lidar);
+        kicp_bridge::to_params(lidar_to_base, ext);
+        const size_t n_in = kicp_pre_ingested_count(pre_);
+        float *out = LandFrame(frame_data, n_in);
+        DownloadGuard guard{pre_, out != nullptr};
+        size_t counts[3] = {0, 0, 0};
+        const int order = kicp_bridge::check(
+            kicp_pre_frame_ingested_f32(pre_, rel_lidar, ext, config_.max_range, config_.min_range, config_.deskew ? 1 : 0, config_.voxel_size * 0.5,
+                                        config_.voxel_size * 1.5, out, n_in, counts),
+            "Preprocess + VoxelDownsample");
+        if (order == KICP_WARN_TABLE_ORDER) kicp_bridge::warn_once(kicp_last_error());
+        RegisterChainedF32(guard, counts, relative_odometry, frame_data, keypoints_data);
+    }
+    // LocalMap() as the published map's msg->data (kiss_icp::VoxelHashMap::PointcloudF32)
+    void LocalMapF32(std::vector<uint8_t> &data) const { local_map_.PointcloudF32(data); }
 #endif
 
     inline void SetPose(const Sophus::SE3d &pose) {
@@ -193,7 +234,7 @@ protected:
     // the download is collected (and dropped) before the vector is destroyed, so nothing is ever copied into freed memory.
     struct DownloadGuard {
         kicp_pre *pre;
-        bool armed = true;
+        bool armed = true;  // (false: nothing was pushed)
         ~DownloadGuard() {
             if (armed) (void)kicp_pre_download_finish(pre, 0, nullptr, 0, nullptr);
         }
@@ -201,9 +242,8 @@ protected:
     // pipeline/KinematicICP.cpp:65-84 from the pre-steps' three buffers on (0: preprocessed frame, 1: first downsample - what goes
     // into the map, 2: second downsample - the registration source): register, update the threshold and the map - all on the
     // device; only the two returned clouds come back to the host.
-    Vector3dVectorTuple RegisterChained(Vector3dVectorTuple &result, DownloadGuard &guard, const size_t counts[3], const Sophus::SE3d &relative_odometry) {
-        kicp_bridge::Trace trace("registration");
-        auto &frame = std::get<0>(result);
+    // register, update the threshold, begin the map update (shared by the fp64 and the FLOAT32 entries)
+    void RegisterOnDevice(kicp_bridge::Trace &trace, const size_t counts[3], const Sophus::SE3d &relative_odometry) {
         const size_t n_down = counts[1], n_source = counts[2];
         const double tau = correspondence_threshold_.ComputeThreshold();
         const auto new_pose = registration_.ComputeRobotMotionDevice(kicp_pre_device_ptr(pre_, 2, nullptr), n_source, local_map_, last_pose_,
@@ -213,6 +253,12 @@ protected:
         // (the map update's kernels run while this thread collects the two returned clouds: nothing below touches the map or buffer 1)
         local_map_.UpdateDeviceBegin(kicp_pre_device_ptr(pre_, 1, nullptr), n_down, new_pose);
         last_pose_ = new_pose;
+    }
+    Vector3dVectorTuple RegisterChained(Vector3dVectorTuple &result, DownloadGuard &guard, const size_t counts[3], const Sophus::SE3d &relative_odometry) {
+        kicp_bridge::Trace trace("registration");
+        auto &frame = std::get<0>(result);
+        const size_t n_source = counts[2];
+        RegisterOnDevice(trace, counts, relative_odometry);
         trace.lap("collect results");
         auto &source = std::get<1>(result);
         source.resize(n_source);
@@ -230,6 +276,34 @@ protected:
             local_map_.UpdateFinish();
         }
         return std::move(result);  // built in place: no copy of the clouds on the way out
+    }
+    // the frame's records land in `data` (room for every input point; shrunk to the frame afterwards); nullptr: no frame wanted
+    static float *LandFrame(std::vector<uint8_t> *data, size_t n_in) {
+        if (!data) return nullptr;
+        data->resize(n_in * kicp_bridge::PointCloud2Xyz32::point_step);
+        return n_in ? reinterpret_cast<float *>(data->data()) : nullptr;
+    }
+    void RegisterChainedF32(DownloadGuard &guard, const size_t counts[3], const Sophus::SE3d &relative_odometry, std::vector<uint8_t> *frame_data,
+                            std::vector<uint8_t> *keypoints_data) {
+        kicp_bridge::Trace trace("registration");
+        RegisterOnDevice(trace, counts, relative_odometry);
+        trace.lap("collect results");
+        constexpr size_t step = kicp_bridge::PointCloud2Xyz32::point_step;
+        if (keypoints_data) {
+            keypoints_data->resize(counts[2] * step);
+            kicp_bridge::check(kicp_pre_download_f32(pre_, 2, counts[2] ? reinterpret_cast<float *>(keypoints_data->data()) : nullptr, counts[2], nullptr),
+                               "download");
+        }
+        if (guard.armed) {
+            guard.armed = false;
+            kicp_bridge::check(kicp_pre_download_finish(pre_, 0, nullptr, 0, nullptr), "download");
+        }
+        if (frame_data) frame_data->resize(counts[0] * step);
+        static const bool sync_update = [] { const char *e = std::getenv("KICP_SYNC_MAP_UPDATE"); return e && *e && *e != '0'; }();
+        if (sync_update) {
+            trace.lap("map update: wait");
+            local_map_.UpdateFinish();
+        }
     }
 #endif
     Sophus::SE3d last_pose_;

@@ -173,6 +173,15 @@ struct VoxelHashMap {
         if (!points.empty()) kicp_map_pointcloud(handle_, points.front().data(), points.size());
         return points;
     }
+    // Pointcloud() as the PointCloud2 `data` of the published map (RosUtils.cpp:40-63 EigenToPointCloud2, LidarOdometryServer.cpp:
+    // 240-263): resizes `data` to 12 bytes per point and fills it with x y z FLOAT32 records (kicp_bridge::PointCloud2Xyz32), so a
+    // node can hand it msg->data.  Narrowed on the GPU where the map lives there (kicp.h kicp_map_pointcloud_f32); backend extension.
+    void PointcloudF32(std::vector<uint8_t> &data) const {
+        size_t total = 0;
+        kicp_bridge::check(kicp_map_pointcloud_f32(handle_, nullptr, 0, &total), "VoxelHashMap::PointcloudF32");
+        data.resize(total * kicp_bridge::PointCloud2Xyz32::point_step);
+        if (total) kicp_bridge::check(kicp_map_pointcloud_f32(handle_, reinterpret_cast<float *>(data.data()), total, &total), "VoxelHashMap::PointcloudF32");
+    }
     // One query -> (closest point, distance); (0, DBL_MAX) when the 27 voxels hold nothing.  Runs the device search.
     std::tuple<Eigen::Vector3d, double> GetClosestNeighbor(const Eigen::Vector3d &query) const {
         Eigen::Vector3d nn;

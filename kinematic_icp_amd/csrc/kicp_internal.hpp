@@ -196,6 +196,14 @@ struct DeviceMirror {
     double *d_pc = nullptr;
     uint32_t *d_pc_blocks = nullptr;  // per-256-slot-block counts / offsets, then the total
     size_t pc_points = 0, pc_blocks = 0;
+    // kicp_map_pointcloud_f32: kRecSlots landing slots for the records' pieces (pinned, host-mapped), a flag and a ticket per slot
+    static constexpr int kRecSlots = 4;
+    unsigned char *h_records = nullptr, *h_records_dev = nullptr;
+    size_t records_cap = 0;  // bytes
+    unsigned long long *h_rec_flags = nullptr, *h_rec_flags_dev = nullptr;
+    unsigned long long *d_rec_tickets = nullptr;  // never reset
+    unsigned long long rec_drawn[kRecSlots] = {};
+    uint32_t rec_seq = 0;
 };
 }  // namespace host
 }  // namespace kicp

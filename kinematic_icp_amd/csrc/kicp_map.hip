@@ -21,6 +21,9 @@ void free_mirror(DeviceMirror &mr) {
         hipFree(mr.d_world), hipFree(mr.d_slot_of), hipFree(mr.d_order), hipFree(mr.d_touched);
         hipFree(mr.d_pc), hipFree(mr.d_pc_blocks);
         if (mr.h_ctr) hipHostFree(mr.h_ctr);
+        if (mr.h_records) hipHostFree(mr.h_records);
+        if (mr.h_rec_flags) hipHostFree(mr.h_rec_flags);
+        hipFree(mr.d_rec_tickets);
         mr.stage.release();
     }
     mr = DeviceMirror{};
@@ -660,6 +663,117 @@ size_t kicp_map_pointcloud(const kicp_map *cmap, double *out_xyz, size_t cap_poi
         return map->host.Pointcloud(out_xyz, cap_points);
     }
     return total;
+}
+// The local map as the PointCloud2 `data` the node publishes (RosUtils.cpp:40-63 EigenToPointCloud2 of LocalMap(),
+// LidarOdometryServer.cpp:240-263): x y z FLOAT32 records, Pointcloud()'s order, static_cast<float> of its doubles.
+int kicp_map_pointcloud_f32(const kicp_map *cmap, float *out_xyz, size_t cap_points, size_t *out_total) {
+    KICP_TRACE_CALL();
+    if (!cmap || (!out_xyz && cap_points)) return fail(KICP_ERR_ARG, "null argument");
+    kicp_map *map = const_cast<kicp_map *>(cmap);  // logically const, as kicp_map_pointcloud
+    if (int rc = map_finish_pending(map)) return rc;  // (its error is this call's: the map it would list is not the updated one)
+    auto on_host = [&]() -> int {  // the host copy is the current one (or has just been made so): narrow it here, the same bits
+        const size_t total = map->host.num_points(), want = out_xyz ? std::min(total, cap_points) : 0;
+        if (out_total) *out_total = total;
+        if (want == 0) return KICP_OK;
+        std::vector<double> xyz(want * 3);
+        map->host.Pointcloud(xyz.data(), want);
+        for (size_t k = 0; k < want * 3; ++k) out_xyz[k] = static_cast<float>(xyz[k]);
+        return KICP_OK;
+    };
+    if (!map->device_ahead) return on_host();
+    const size_t total = static_cast<size_t>(map->dev.n_points);
+    const size_t want = out_xyz ? std::min(total, cap_points) : 0;
+    if (out_total) *out_total = total;
+    if (want == 0) return KICP_OK;
+    if (total * 3 >= 0xFFFFFFF0ull) return fail(KICP_ERR_CAPACITY, "map too large for 32-bit record offsets");
+    DeviceMirror &mr = map->mirror;
+    constexpr int kSlots = DeviceMirror::kRecSlots;
+    // pieces of up to 64 Ki records (768 KB), at least four of them where the map allows, so that the copy of piece i into the
+    // caller's memory runs while pieces i + 1 .. i + 3 are on their way; a multiple of 4 records keeps every piece 16-byte aligned
+    const size_t piece = std::min<size_t>(65536, std::max<size_t>(1024, ((want + kSlots - 1) / kSlots + 1023) / 1024 * 1024));
+    const size_t pieces = (want + piece - 1) / piece;
+    auto gather = [&]() -> int {
+        if (int rc = set_device(mr.device)) return rc;
+        const size_t slots = mr.live_slots, blocks = (slots + 255) / 256;
+        if (blocks + 1 > mr.pc_blocks) {
+            hipFree(mr.d_pc_blocks);
+            mr.d_pc_blocks = nullptr, mr.pc_blocks = 0;
+            HIP_TRY(hipMalloc(&mr.d_pc_blocks, (blocks + 1) * 4));
+            mr.pc_blocks = blocks + 1;
+        }
+        if (piece * 12 * kSlots > mr.records_cap) {
+            if (mr.h_records) HIP_TRY(hipHostFree(mr.h_records));
+            mr.h_records = mr.h_records_dev = nullptr, mr.records_cap = 0;
+            HIP_TRY(pinned_alloc(reinterpret_cast<void **>(&mr.h_records), piece * 12 * kSlots, hipHostMallocDefault));
+            mr.records_cap = piece * 12 * kSlots;
+            HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void **>(&mr.h_records_dev), mr.h_records, 0));
+        }
+        if (!mr.h_rec_flags) {
+            HIP_TRY(pinned_alloc(reinterpret_cast<void **>(&mr.h_rec_flags), kSlots * sizeof(unsigned long long), hipHostMallocMapped | hipHostMallocCoherent));
+            std::memset(mr.h_rec_flags, 0, kSlots * sizeof(unsigned long long));
+            HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void **>(&mr.h_rec_flags_dev), mr.h_rec_flags, 0));
+        }
+        if (!mr.d_rec_tickets) {
+            HIP_TRY(hipMalloc(&mr.d_rec_tickets, kSlots * sizeof(unsigned long long)));
+            HIP_TRY(hipMemset(mr.d_rec_tickets, 0, kSlots * sizeof(unsigned long long)));
+            for (int s = 0; s < kSlots; ++s) mr.rec_drawn[s] = 0;
+        }
+        hipStream_t st = nullptr;
+        hipLaunchKernelGGL(k_pc_count, dim3(static_cast<uint32_t>(blocks)), dim3(256), 0, st, mr.d_table, mr.d_keys64, static_cast<uint32_t>(slots), map->host.count_bits(), mr.d_pc_blocks);
+        hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(1024), 0, st, mr.d_pc_blocks, static_cast<uint32_t>(blocks), mr.d_pc_blocks + blocks);
+        PcRecordParams q{};
+        q.table = mr.d_table, q.keys64 = mr.d_keys64, q.slots = static_cast<uint32_t>(slots), q.cap = map->host.cap(), q.cbits = map->host.count_bits();
+        q.blocks = static_cast<uint32_t>(blocks), q.pool = mr.d_pool, q.block_offsets = mr.d_pc_blocks;
+        // workgroups per piece: about as many as the piece has table blocks (the map's average records per block), at most 512
+        const size_t per_block = std::max<size_t>(1, total / std::max<size_t>(1, blocks));
+        const uint32_t grid = static_cast<uint32_t>(std::min<size_t>({blocks, 512, piece / per_block + 2}));
+        uint32_t seqs[kSlots] = {};
+        auto queue = [&](size_t i) -> int {
+            const int s = static_cast<int>(i % kSlots);
+            q.lo = static_cast<uint32_t>(i * piece), q.hi = static_cast<uint32_t>(std::min(want, (i + 1) * piece));
+            q.dst = reinterpret_cast<float *>(mr.h_records_dev + static_cast<size_t>(s) * piece * 12);
+            mr.rec_drawn[s] += grid;
+            q.ticket = mr.d_rec_tickets + s, q.ticket_done = mr.rec_drawn[s], q.host_flag = mr.h_rec_flags_dev + s;
+            q.seq = ++mr.rec_seq;
+            if (q.seq == 0u) q.seq = ++mr.rec_seq;  // (0 is what the flags hold before the first piece)
+            seqs[s] = q.seq;
+            hipLaunchKernelGGL(k_pc_records, dim3(grid), dim3(256), 0, st, q);
+            HIP_TRY(hipGetLastError());
+            return KICP_OK;
+        };
+        for (size_t i = 0; i < std::min<size_t>(pieces, kSlots); ++i)
+            if (int rc = queue(i)) return rc;
+        // each piece: wait for its flag, check the table's count it carries, copy the piece out, queue the piece that reuses its slot
+        const volatile unsigned long long *flags = mr.h_rec_flags;
+        for (size_t i = 0; i < pieces; ++i) {
+            const int s = static_cast<int>(i % kSlots);
+            const unsigned long long tag = static_cast<unsigned long long>(seqs[s]) << 32;
+            const auto t0 = std::chrono::steady_clock::now();
+            for (unsigned spins = 0; (flags[s] & 0xFFFFFFFF00000000ull) != tag; ++spins) {
+                if ((spins & 1023u) == 1023u && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > 2.0) {
+                    HIP_TRY(hipStreamSynchronize(st));  // (something is badly wrong: surface it instead of spinning for ever)
+                    if ((flags[s] & 0xFFFFFFFF00000000ull) != tag) return fail(KICP_ERR_HIP, "a piece of the map's records was never announced");
+                    break;
+                }
+                __builtin_ia32_pause();
+            }
+            const uint32_t counted = static_cast<uint32_t>(flags[s] & 0xFFFFFFFFull);
+            if (counted != total) {
+                HIP_TRY(hipStreamSynchronize(st));
+                return fail(KICP_ERR_HIP, "device map counters disagree with the table");
+            }
+            const size_t lo = i * piece, n = std::min(want, lo + piece) - lo;
+            std::memcpy(out_xyz + lo * 3, mr.h_records + static_cast<size_t>(s) * piece * 12, n * 12);
+            if (i + kSlots < pieces)
+                if (int rc = queue(i + kSlots)) return rc;
+        }
+        return KICP_OK;
+    };
+    if (int rc = gather()) {  // as kicp_map_pointcloud: the host copy, refreshed, is the answer then
+        if (ensure_host_current(map) != KICP_OK) return rc;
+        return on_host();
+    }
+    return KICP_OK;
 }
 size_t kicp_map_check(const kicp_map *map) {
     if (!map || ensure_host_current(const_cast<kicp_map *>(map)) != KICP_OK) return 1;

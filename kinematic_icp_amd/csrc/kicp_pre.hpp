@@ -313,6 +313,7 @@ struct FrameParams {
     uint32_t *misc;
     double *buf0, *buf1, *buf2;
     double *host_buf2;    // nullable: host-mapped pinned memory that receives buffer 2 as well (the registration source the pipeline returns)
+    int32_t host_buf2_f32;  // 1: host_buf2 receives buffer 2 as x y z FLOAT32 records (kicp_pre_frame_f32) instead of doubles
     unsigned long long *host_rec;  // 5 words, each (seq << 32) | value: n0, n1, n2, longest probe, flags (1 range error, 2 speculation failed)
     uint32_t seq;
 };
@@ -555,7 +556,12 @@ static __global__ __launch_bounds__(256) void k_frame_src_host(const FrameParams
     __shared__ uint32_t s_last;
     if (f.misc[7]) return;  // (the guess was wrong: the host takes the unfused steps and downloads buffer 2 itself)
     const uint32_t n2 = f.misc[6];
-    for (uint32_t o = blockIdx.x * 256u + threadIdx.x; o < 3u * n2; o += gridDim.x * 256u) f.host_buf2[o] = f.buf2[o];
+    if (f.host_buf2_f32) {  // (the published keypoints' PointCloud2 records: static_cast<float>, RosUtils.cpp:40-63)
+        float *out = reinterpret_cast<float *>(f.host_buf2);
+        for (uint32_t o = blockIdx.x * 256u + threadIdx.x; o < 3u * n2; o += gridDim.x * 256u) out[o] = static_cast<float>(f.buf2[o]);
+    } else {
+        for (uint32_t o = blockIdx.x * 256u + threadIdx.x; o < 3u * n2; o += gridDim.x * 256u) f.host_buf2[o] = f.buf2[o];
+    }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -613,6 +619,46 @@ static __global__ __launch_bounds__(256) void k_push_frame(const PushParams q) {
         }
         __syncthreads();
     }
+}
+// The same push with the frame narrowed on the way out (kicp_pre_frame_f32: the PointCloud2 `data` of the published frame,
+// RosUtils.cpp:40-63).  x y z FLOAT32 records of 12 bytes are the fp64 frame's doubles one by one as floats, so a lane reads 32
+// bytes (four doubles), narrows them with static_cast<float> (round to nearest even, subnormals kept, +-inf beyond the float
+// range, signed zeros kept) and stores one 16-byte unit: half the bytes of k_push_frame cross PCIe.  piece_bytes counts
+// record bytes; the flag protocol is k_push_frame's.
+static __global__ __launch_bounds__(256) void k_push_frame_f32(const PushParams q) {
+    typedef float f32x4 __attribute__((ext_vector_type(4)));
+    typedef double f64x2 __attribute__((ext_vector_type(2)));
+    __shared__ uint32_t s_last;
+    const size_t bytes = static_cast<size_t>(*q.n_points) * 12u;
+    const double *src = reinterpret_cast<const double *>(q.src);
+    float *dst = reinterpret_cast<float *>(q.dst);
+    for (int piece = 0; piece < kPushPieces; ++piece) {
+        const size_t lo = static_cast<size_t>(piece) * q.piece_bytes, hi = lo + q.piece_bytes < bytes ? lo + q.piece_bytes : bytes;
+        const size_t len = hi > lo ? hi - lo : 0u;
+        for (size_t o = (static_cast<size_t>(blockIdx.x) * 256u + threadIdx.x) * 16u; o < len; o += static_cast<size_t>(gridDim.x) * 4096u) {
+            const size_t w = (lo + o) / 4u;  // first word of the unit = index of its first double
+            if (o + 16u <= len) {
+                const f64x2 a = *reinterpret_cast<const f64x2 *>(src + w), b = *reinterpret_cast<const f64x2 *>(src + w + 2);
+                *reinterpret_cast<f32x4 *>(dst + w) = f32x4{static_cast<float>(a.x), static_cast<float>(a.y), static_cast<float>(b.x), static_cast<float>(b.y)};
+            } else {
+                for (size_t k = w; k < (lo + len) / 4u; ++k) dst[k] = static_cast<float>(src[k]);
+            }
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            // system scope: this workgroup's bytes are in host memory before its ticket - and so before the flag, whoever writes it
+            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            s_last = __hip_atomic_fetch_add(q.tickets + piece, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) + 1ull == q.ticket_done ? 1u : 0u;
+            if (s_last) __hip_atomic_store(q.host_flags + piece, (static_cast<unsigned long long>(q.seq) << 32) | static_cast<unsigned long long>(len), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        }
+        __syncthreads();
+    }
+}
+// kicp_pre_download_f32 of a buffer that has no copy in host memory: its doubles narrowed into HBM, then downloaded
+static __global__ __launch_bounds__(256) void k_narrow_f32(const double *src, size_t words, float *dst) {
+    for (size_t k = static_cast<size_t>(blockIdx.x) * 256u + threadIdx.x; k < words; k += static_cast<size_t>(gridDim.x) * 256u) dst[k] = static_cast<float>(src[k]);
 }
 
 // ---- PointCloud2 wire-format ingest ----------------------------------------------------

@@ -41,6 +41,9 @@ struct kicp_pre {
     unsigned char *h_src = nullptr, *h_src_dev = nullptr;
     size_t h_src_cap = 0;
     bool src_on_host = false;  // h_src holds buffer 2's current contents - once word 5 of h_rec carries src_seq (k_frame_src_host)
+    bool src_f32 = false;      // ... as x y z FLOAT32 records (the frame came through kicp_pre_frame*_f32), not as doubles
+    float *d_narrow = nullptr; // kicp_pre_download_f32 of a buffer without a host copy: its records in HBM
+    size_t narrow_cap = 0;
     uint32_t src_seq = 0;
     unsigned char *copy_host_dev = nullptr;  // the landing area as the device sees it (nullptr: not mapped - the DMA engine moves the frame)
     unsigned long long *d_ticket = nullptr;  // [2] the ingest kernels' tickets (never reset), one per record
@@ -78,8 +81,9 @@ struct kicp_pre {
     std::mutex copy_mutex;
     std::condition_variable copy_cv;
     int copy_state = 0;  // 0 idle, 1 job posted, 2 job done, -1 shut down
-    double *copy_dst = nullptr;
+    void *copy_dst = nullptr;
     size_t copy_dst_points = 0;
+    size_t copy_rec_bytes = 24;  // bytes per point of the download in flight: 24 (fp64) or 12 (the FLOAT32 records of kicp_pre_frame*_f32)
     hipError_t copy_error = hipSuccess;
     unsigned long long *d_block_minmax = nullptr;
     size_t ingested_n = 0;
@@ -244,7 +248,7 @@ void kicp_pre_destroy(kicp_pre *p) {
     if (p->h_src) hipHostFree(p->h_src);
     hipFree(p->d_in), hipFree(p->d_ts), hipFree(p->d_in2), hipFree(p->d_ts2), hipFree(p->d_staged), hipFree(p->d_flags), hipFree(p->d_block_counts), hipFree(p->d_table);
     hipFree(p->d_table2), hipFree(p->d_counts1), hipFree(p->d_counts2);
-    hipFree(p->d_misc), hipFree(p->d_raw), hipFree(p->d_block_minmax), hipFree(p->d_ticket), hipFree(p->d_push_tickets), hipFree(p->d_scan_cs);
+    hipFree(p->d_misc), hipFree(p->d_raw), hipFree(p->d_block_minmax), hipFree(p->d_ticket), hipFree(p->d_push_tickets), hipFree(p->d_scan_cs), hipFree(p->d_narrow);
     p->stage.release();
     if (p->copy_thread.joinable()) {  // the helper thread finishes the job it has, then leaves
         {
@@ -641,9 +645,10 @@ static void copy_worker(kicp_pre *p);
 // device and is the next step's input count (every launch is sized for n_in, every kernel derives the reference's bucket count
 // from the real count itself); the three counts come back together at the end.  Buffer 0 - the preprocessed frame the pipeline
 // returns - starts travelling to `out_frame_xyz` (room for n_in points; may be nullptr) as soon as it is complete, on the
+// (f32: as x y z FLOAT32 records, k_push_frame_f32; buffer 2's host copy then holds records too)
 // download stream, while the downsamples run.
 static int pre_frame_chain(kicp_pre *p, size_t n_in, bool do_deskew, const double relative_motion_qt[7], const double lidar_to_base_qt[7], double max_range,
-                           double min_range, double voxel_a, double voxel_b, double *out_frame_xyz, size_t cap_points, size_t counts[3]) {
+                           double min_range, double voxel_a, double voxel_b, void *out_frame_xyz, size_t cap_points, size_t counts[3], bool f32) {
     counts[0] = counts[1] = counts[2] = 0;
     p->buf_n[0] = p->buf_n[1] = p->buf_n[2] = 0;
     p->src_on_host = false;
@@ -686,23 +691,26 @@ static int pre_frame_chain(kicp_pre *p, size_t n_in, bool do_deskew, const doubl
         if (!out_frame_xyz) return KICP_OK;
         if (int rc = download_settle(p)) return rc;  // (an earlier download nobody collected)
         if (!p->copy_thread.joinable()) p->copy_thread = std::thread(copy_worker, p);
-        if (int rc = download_reserve(p, n_in * 24)) return rc;
+        const size_t rec_bytes = f32 ? 12 : 24;
+        if (int rc = download_reserve(p, n_in * rec_bytes)) return rc;
         bool pushed = false;
         static const int push_wgs = [] { const char *e = std::getenv("KICP_PRE_PUSH_WGS"); return e && *e ? std::atoi(e) : 16; }();
-        if (push_wgs <= 0) {  // (A/B: the DMA engine moves the frame, in pieces, queued here instead of by the helper thread)
+        if (f32 && !p->copy_host_dev) return fail(KICP_ERR_HIP, "the frame's FLOAT32 records need a host-mapped landing area");
+        if (push_wgs <= 0 && !f32) {  // (A/B: the DMA engine moves the frame, in pieces, queued here instead of by the helper thread)
             if (int rc = download_queue(p, 0, n_in, p->chain_ready)) return rc;
         } else if (p->copy_host_dev) {
             // k_push_frame on the download stream, behind the event: the frame crosses PCIe as a kernel's stores, piece by piece, each
             // piece announced in host memory; the helper thread needs no HIP call to follow it
             PushParams q{};
             q.src = reinterpret_cast<const unsigned char *>(p->buf[0]), q.dst = p->copy_host_dev, q.n_points = p->d_misc + 4;
-            q.piece_bytes = static_cast<uint32_t>(((n_in * 24 + kPushPieces - 1) / kPushPieces + 4095) / 4096 * 4096);
-            const uint32_t push_grid = static_cast<uint32_t>(push_wgs);
+            q.piece_bytes = static_cast<uint32_t>(((n_in * rec_bytes + kPushPieces - 1) / kPushPieces + 4095) / 4096 * 4096);
+            const uint32_t push_grid = static_cast<uint32_t>(push_wgs > 0 ? push_wgs : 16);
             p->push_drawn += push_grid;
             q.tickets = p->d_push_tickets, q.ticket_done = p->push_drawn, q.host_flags = p->h_rec + 16, q.seq = ++p->push_seq;
             if (q.seq == 0u) q.seq = ++p->push_seq;
             HIP_TRY(hipStreamWaitEvent(p->copy_stream, p->chain_ready, 0));
-            hipLaunchKernelGGL(k_push_frame, dim3(push_grid), dim3(256), 0, p->copy_stream, q);
+            if (f32) hipLaunchKernelGGL(k_push_frame_f32, dim3(push_grid), dim3(256), 0, p->copy_stream, q);
+            else hipLaunchKernelGGL(k_push_frame, dim3(push_grid), dim3(256), 0, p->copy_stream, q);
             HIP_TRY(hipGetLastError());
             p->copy_push_piece = q.piece_bytes, p->copy_push_seq = q.seq;
             pushed = true;
@@ -710,6 +718,7 @@ static int pre_frame_chain(kicp_pre *p, size_t n_in, bool do_deskew, const doubl
         {   // the helper thread moves the pieces into the caller's memory as they land (without the push: it also queues the DMA transfer, in pieces)
             std::lock_guard<std::mutex> lock(p->copy_mutex);
             p->copy_dst = out_frame_xyz, p->copy_dst_points = cap_points, p->copy_job_begins = !pushed && push_wgs > 0, p->copy_job_push = pushed, p->copy_job_n = n_in;
+            p->copy_rec_bytes = rec_bytes;
             p->copy_buffer = 0, p->copy_n = n_in, p->copy_points = n_in, p->copy_state = 1;
         }
         p->copy_cv.notify_all();
@@ -756,6 +765,7 @@ static int pre_frame_chain(kicp_pre *p, size_t n_in, bool do_deskew, const doubl
         }
         static const int src_to_host = [] { const char *e = std::getenv("KICP_PRE_SRC_HOST"); return e && *e ? std::atoi(e) : 1; }();
         f.host_buf2 = src_to_host ? reinterpret_cast<double *>(p->h_src_dev) : nullptr;
+        f.host_buf2_f32 = f32 ? 1 : 0;
         f.host_rec = p->h_rec, f.seq = ++p->chain_seq;
         if (f.seq == 0u) f.seq = ++p->chain_seq;  // (0 is what the device words hold before the first frame)
         // table B's size is known on the device only: its two launches walk the tiles there are with the workgroups they get - as
@@ -793,6 +803,7 @@ static int pre_frame_chain(kicp_pre *p, size_t n_in, bool do_deskew, const doubl
         unfused_tail = (static_cast<uint32_t>(rec[4]) & 2u) != 0u;
         p->spec_n0 = misc[4], p->spec_n_in = static_cast<uint32_t>(n_in);
         p->src_on_host = !unfused_tail && f.host_buf2 != nullptr;
+        p->src_f32 = f32;
         p->src_seq = f.seq;
         p->spec_tiles_b = misc[5] ? static_cast<uint32_t>(reference_bucket_count(misc[5]) + 255) / 256u : 1u;
         if (unfused_tail) {  // a guess was wrong: the tables hold claims made under the wrong size; buffer 0 and its count are in place
@@ -850,20 +861,28 @@ static int pre_frame_chain(kicp_pre *p, size_t n_in, bool do_deskew, const doubl
     }
     return KICP_OK;
 }
-int kicp_pre_frame_ingested(kicp_pre *p, const double relative_motion_qt[7], const double lidar_to_base_qt[7], double max_range, double min_range, int deskew,
-                            double voxel_a, double voxel_b, double *out_frame_xyz, size_t cap_points, size_t out_counts[3]) {
-    KICP_TRACE_CALL();
+static int frame_ingested_impl(kicp_pre *p, const double relative_motion_qt[7], const double lidar_to_base_qt[7], double max_range, double min_range, int deskew,
+                               double voxel_a, double voxel_b, void *out_frame_xyz, size_t cap_points, size_t out_counts[3], bool f32) {
     if (!p || !relative_motion_qt || !lidar_to_base_qt || !out_counts) return fail(KICP_ERR_ARG, "bad argument");
     if (!p->ingested) return fail(KICP_ERR_ARG, "no ingested cloud: call kicp_pre_ingest first");
     if (out_frame_xyz && cap_points < p->ingested_n) return fail(KICP_ERR_ARG, "the frame's landing area must hold every ingested point");
     if (int rc = set_device(p->device)) return rc;
     return pre_frame_chain(p, p->ingested_n, deskew && p->ingested_stamps, relative_motion_qt, lidar_to_base_qt, max_range, min_range, voxel_a, voxel_b,
-                           out_frame_xyz, cap_points, out_counts);
+                           out_frame_xyz, cap_points, out_counts, f32);
 }
-int kicp_pre_frame(kicp_pre *p, const double *frame_xyz, size_t n, const double *timestamps, size_t n_timestamps, const double relative_motion_qt[7],
-                   const double lidar_to_base_qt[7], double max_range, double min_range, int deskew, double voxel_a, double voxel_b, double *out_frame_xyz,
-                   size_t cap_points, size_t out_counts[3]) {
+int kicp_pre_frame_ingested(kicp_pre *p, const double relative_motion_qt[7], const double lidar_to_base_qt[7], double max_range, double min_range, int deskew,
+                            double voxel_a, double voxel_b, double *out_frame_xyz, size_t cap_points, size_t out_counts[3]) {
     KICP_TRACE_CALL();
+    return frame_ingested_impl(p, relative_motion_qt, lidar_to_base_qt, max_range, min_range, deskew, voxel_a, voxel_b, out_frame_xyz, cap_points, out_counts, false);
+}
+int kicp_pre_frame_ingested_f32(kicp_pre *p, const double relative_motion_qt[7], const double lidar_to_base_qt[7], double max_range, double min_range, int deskew,
+                                double voxel_a, double voxel_b, float *out_frame_xyz, size_t cap_points, size_t out_counts[3]) {
+    KICP_TRACE_CALL();
+    return frame_ingested_impl(p, relative_motion_qt, lidar_to_base_qt, max_range, min_range, deskew, voxel_a, voxel_b, out_frame_xyz, cap_points, out_counts, true);
+}
+static int frame_impl(kicp_pre *p, const double *frame_xyz, size_t n, const double *timestamps, size_t n_timestamps, const double relative_motion_qt[7],
+                      const double lidar_to_base_qt[7], double max_range, double min_range, int deskew, double voxel_a, double voxel_b, void *out_frame_xyz,
+                      size_t cap_points, size_t out_counts[3], bool f32) {
     if (!p || (!frame_xyz && n) || !relative_motion_qt || !lidar_to_base_qt || !out_counts) return fail(KICP_ERR_ARG, "bad argument");
     const bool do_deskew = deskew && n_timestamps != 0;
     if (do_deskew && (!timestamps || n_timestamps < n)) return fail(KICP_ERR_ARG, "one timestamp per point is required for deskewing");
@@ -878,7 +897,21 @@ int kicp_pre_frame(kicp_pre *p, const double *frame_xyz, size_t n, const double 
         if (do_deskew)
             if (int rc = staged_upload(p->stage, n * 24, p->d_ts, timestamps, n * 8, p->stream)) return rc;
     }
-    return pre_frame_chain(p, n, do_deskew, relative_motion_qt, lidar_to_base_qt, max_range, min_range, voxel_a, voxel_b, out_frame_xyz, cap_points, out_counts);
+    return pre_frame_chain(p, n, do_deskew, relative_motion_qt, lidar_to_base_qt, max_range, min_range, voxel_a, voxel_b, out_frame_xyz, cap_points, out_counts, f32);
+}
+int kicp_pre_frame(kicp_pre *p, const double *frame_xyz, size_t n, const double *timestamps, size_t n_timestamps, const double relative_motion_qt[7],
+                   const double lidar_to_base_qt[7], double max_range, double min_range, int deskew, double voxel_a, double voxel_b, double *out_frame_xyz,
+                   size_t cap_points, size_t out_counts[3]) {
+    KICP_TRACE_CALL();
+    return frame_impl(p, frame_xyz, n, timestamps, n_timestamps, relative_motion_qt, lidar_to_base_qt, max_range, min_range, deskew, voxel_a, voxel_b, out_frame_xyz,
+                      cap_points, out_counts, false);
+}
+int kicp_pre_frame_f32(kicp_pre *p, const double *frame_xyz, size_t n, const double *timestamps, size_t n_timestamps, const double relative_motion_qt[7],
+                       const double lidar_to_base_qt[7], double max_range, double min_range, int deskew, double voxel_a, double voxel_b, float *out_frame_xyz,
+                       size_t cap_points, size_t out_counts[3]) {
+    KICP_TRACE_CALL();
+    return frame_impl(p, frame_xyz, n, timestamps, n_timestamps, relative_motion_qt, lidar_to_base_qt, max_range, min_range, deskew, voxel_a, voxel_b, out_frame_xyz,
+                      cap_points, out_counts, true);
 }
 unsigned long long kicp_pre_ahead_hits(const kicp_pre *p) { return p ? p->ahead_hits : 0ull; }
 int kicp_pre_set_option(kicp_pre *p, const char *name, double value) {
@@ -922,10 +955,36 @@ int kicp_pre_download(const kicp_pre *p, int buffer, double *out_xyz, size_t cap
     if (int rc = set_device(p->device)) return rc;
     const size_t n = p->buf_n[buffer], k = std::min(n, cap_points);
     if (k && out_xyz) {
-        if (buffer == 2 && p->src_on_host) {  // (the fused chain leaves a copy in host memory)
+        if (buffer == 2 && p->src_on_host && !p->src_f32) {  // (the fused chain leaves a copy in host memory)
             if (int rc = wait_word(p->h_rec + 5, static_cast<unsigned long long>(p->src_seq) << 32, 0xFFFFFFFF00000000ull, p->stream)) return rc;
             std::memcpy(out_xyz, p->h_src, k * 24);
         } else if (int rc = staged_download(p->stage, out_xyz, p->buf[buffer], k * 24, p->stream)) return rc;
+    }
+    if (out_n) *out_n = n;
+    return KICP_OK;
+}
+int kicp_pre_download_f32(const kicp_pre *cp, int buffer, float *out_xyz, size_t cap_points, size_t *out_n) {
+    KICP_TRACE_CALL();
+    kicp_pre *p = const_cast<kicp_pre *>(cp);  // logically const: only the narrowing scratch is touched
+    if (!p || buffer < 0 || buffer >= KICP_PRE_BUFFERS) return fail(KICP_ERR_ARG, "bad argument");
+    if (int rc = set_device(p->device)) return rc;
+    const size_t n = p->buf_n[buffer], k = std::min(n, cap_points);
+    if (k && out_xyz) {
+        if (buffer == 2 && p->src_on_host && p->src_f32) {  // (the fused chain of a kicp_pre_frame*_f32 call left the records in host memory)
+            if (int rc = wait_word(p->h_rec + 5, static_cast<unsigned long long>(p->src_seq) << 32, 0xFFFFFFFF00000000ull, p->stream)) return rc;
+            std::memcpy(out_xyz, p->h_src, k * 12);
+        } else {
+            if (k * 3 > p->narrow_cap) {
+                hipFree(p->d_narrow);
+                p->d_narrow = nullptr, p->narrow_cap = 0;
+                HIP_TRY(hipMalloc(&p->d_narrow, (k * 3 + k / 4 * 3 + 3072) * 4));
+                p->narrow_cap = k * 3 + k / 4 * 3 + 3072;
+            }
+            const size_t words = k * 3;
+            hipLaunchKernelGGL(k_narrow_f32, dim3(static_cast<uint32_t>(std::min<size_t>((words + 255) / 256, 1024))), dim3(256), 0, p->stream, p->buf[buffer], words, p->d_narrow);
+            HIP_TRY(hipGetLastError());
+            if (int rc = staged_download(p->stage, out_xyz, p->d_narrow, words * 4, p->stream)) return rc;
+        }
     }
     if (out_n) *out_n = n;
     return KICP_OK;
@@ -958,7 +1017,7 @@ static int download_queue(kicp_pre *p, int buffer, size_t n, hipEvent_t after);
 static int download_begin_impl(kicp_pre *p, int buffer, size_t n, hipEvent_t after) {
     if (int rc = download_settle(p)) return rc;
     if (int rc = download_queue(p, buffer, n, after)) return rc;
-    p->copy_buffer = buffer, p->copy_n = n, p->copy_points = n;
+    p->copy_buffer = buffer, p->copy_n = n, p->copy_points = n, p->copy_rec_bytes = 24;
     return KICP_OK;
 }
 // the transfer itself (calling thread, or the helper thread for the chained pre-steps)
@@ -1018,7 +1077,7 @@ static void copy_worker(kicp_pre *p) {
             p->copy_job_begins = false;
             if (download_queue(p, 0, p->copy_job_n, p->chain_ready) != KICP_OK) e = hipErrorUnknown;
         }
-        const size_t want = std::min(p->copy_points, p->copy_dst_points) * 24;  // (copy_points, copy_dst*, copy_piece_bytes: written before the job was posted)
+        const size_t want = std::min(p->copy_points, p->copy_dst_points) * p->copy_rec_bytes;  // (copy_points, copy_dst*, copy_piece_bytes: written before the job was posted)
         if (e != hipSuccess) {
         } else if (p->copy_job_push) {
             // k_push_frame's pieces: a flag per piece in host memory, (seq << 32) | bytes - a short piece is the last one
@@ -1043,7 +1102,7 @@ static void copy_worker(kicp_pre *p) {
                 if (e != hipSuccess) break;
                 const size_t len = static_cast<size_t>(f & 0xFFFFFFFFull), off = static_cast<size_t>(p->copy_push_piece) * i;
                 if (g_trace) landed_us[i] = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
-                if (len && p->copy_dst && off < want) std::memcpy(reinterpret_cast<unsigned char *>(p->copy_dst) + off, p->copy_host + off, std::min(len, want - off));
+                if (len && p->copy_dst && off < want) std::memcpy(static_cast<unsigned char *>(p->copy_dst) + off, p->copy_host + off, std::min(len, want - off));
                 if (g_trace) copied_us[i] = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count(), pieces_seen = i + 1;
                 if (len < p->copy_push_piece) break;
             }
@@ -1057,7 +1116,7 @@ static void copy_worker(kicp_pre *p) {
             for (int i = 0; i < kicp_pre::kCopyPieces && e == hipSuccess; ++i) {
                 e = spin_on_event(p->copy_piece_done[i]);
                 const size_t off = std::min(want, p->copy_piece_bytes * i), len = std::min(p->copy_piece_bytes, want - off);
-                if (e == hipSuccess && len) std::memcpy(reinterpret_cast<unsigned char *>(p->copy_dst) + off, p->copy_host + off, len);
+                if (e == hipSuccess && len) std::memcpy(static_cast<unsigned char *>(p->copy_dst) + off, p->copy_host + off, len);
             }
         } else {
             e = spin_on_event(p->copy_done);
@@ -1096,6 +1155,10 @@ int kicp_pre_download_finish(kicp_pre *p, int buffer, double *out_xyz, size_t ca
     if (!delivered) {
         HIP_TRY(hipEventSynchronize(p->copy_done));
         const size_t k = std::min(p->copy_n, cap_points);
+        if (k && out_xyz && p->copy_rec_bytes != 24) {  // (a frame's FLOAT32 records land in the caller's own buffer only)
+            p->copy_buffer = -1;
+            return fail(KICP_ERR_ARG, "the frame's FLOAT32 records went to the kicp_pre_frame*_f32 call's out_frame_xyz: collect with NULL");
+        }
         if (k && out_xyz) std::memcpy(out_xyz, p->copy_host, k * 24);
     }
     if (out_n) *out_n = p->copy_n;
