@@ -136,6 +136,22 @@ int kicp_map_pointcloud_f32(const kicp_map *map, float *out_xyz, size_t cap_poin
  * kernels - NOT their mirror pre-selection: what the shipped pass kernels pick per query is what kicp_pass_correspondences returns).
  * No candidate -> nn = (0,0,0), dist = DBL_MAX, exactly like the reference. */
 int kicp_map_closest(kicp_map *map, int device, const double *queries_xyz, size_t n, double *out_nn_xyz, double *out_dist);
+/* The map as a file: PCD v0.7, DATA binary - FIELDS x y z, SIZE 8 8 8, TYPE F F F, COUNT 1 1 1, WIDTH n, HEIGHT 1, POINTS n, the points of
+ * kicp_map_pointcloud in its order - with one comment line `# kicp_map voxel_size=<%.17g> max_distance=<%.17g> max_points_per_voxel=<u>`.
+ * Written to `path`.tmp and renamed.  Works wherever the newest state lives; a pending update is collected first, its error returned. */
+int kicp_map_save_pcd(const kicp_map *map, const char *path);
+/* The three parameters the map was created with (any of the outputs may be null). */
+int kicp_map_params(const kicp_map *map, double *out_voxel_size, double *out_max_distance, unsigned int *out_max_points_per_voxel);
+/* A new map from a PCD file (this library's or a mapping tool's): binary data only; x, y, z must be TYPE F of SIZE 4 or 8 (floats are
+ * widened with static_cast<double>) and COUNT 1, other fields are skipped; header lines in any order, comments anywhere; the number of
+ * points is POINTS, or WIDTH x HEIGHT without it.  voxel_size <= 0: the three parameters come from the file's `# kicp_map` line
+ * (KICP_ERR_ARG without one).  Non-finite points are dropped and counted; the others are inserted in file order - on `device` through
+ * the bulk insertion of kicp_map_set_device(map, device) when device >= 0, otherwise on the host - which reproduces every voxel's points
+ * in their order (the order of the voxels among themselves may differ; no registration result depends on it).  DATA ascii /
+ * binary_compressed, a missing field, a short file: KICP_ERR_ARG with a message that names the problem, *out = NULL.
+ * out_points_read (rows of the file) and out_points_dropped may be null. */
+int kicp_map_load_pcd(const char *path, double voxel_size, double max_distance, unsigned int max_points_per_voxel, int device, kicp_map **out,
+                      size_t *out_points_read, size_t *out_points_dropped);
 /* Debug aid: verifies the table invariants the kernels rely on (neighbour masks, bucket records, halo entries, fp32
  * mirror, counters) on the host copy; returns the number of violations, 0 when consistent. */
 size_t kicp_map_check(const kicp_map *map);
@@ -155,7 +171,7 @@ void kicp_reg_destroy(kicp_reg *reg);
 int kicp_reg_clone(const kicp_reg *reg, kicp_reg **out);
 int kicp_reg_get_config(const kicp_reg *reg, kicp_reg_config *out);
 int kicp_reg_set_config(kicp_reg *reg, const kicp_reg_config *config); /* the reference's fields are public & mutable */
-/* Backend tuning knobs (not part of the reference API).  Seventeen settable options; everything that lost its A/B over five rounds
+/* Backend tuning knobs (not part of the reference API).  Eighteen settable options; everything that lost its A/B over five rounds
  * (other workgroup sizes and register budgets, the plain fp64 gather, the device-side solve, single-record hand-offs, ...) was deleted
  * in round 6, and the pass kernels' ablation switches ("dbg") exist in libkicp_amd_dbg.so only (make -C kinematic_icp_amd/csrc dbg).
  * Which kernel runs:
@@ -181,6 +197,8 @@ int kicp_reg_set_config(kicp_reg *reg, const kicp_reg_config *config); /* the re
  *   "batch_threads"  (default 8, 0 .. 9) batches of scans that leave most of the device empty: up to this many resident kernels side by
  *                  side, a host thread of the library's pool each (capped by the CPUs this process may use: cpuset and cgroup quota)
  *   "batch_rotate"   1 (default): the workgroups of a resident kernel take turns at the parts of a scan; 0: fixed shares
+ * One frame at many poses (kicp_score_poses, kicp_relocalize):
+ *   "score_chunk"  (default 8 388 608) queries - pose x point pairs - one launch of the scoring kernel may serve; 0: the default
  * Transfers and launches:
  *   "bar_frame"    1 (default): kicp_register writes host frames of up to 8 192 points straight into HBM through the PCIe BAR
  *   "fetch_upload" 1 (default): larger host frames are pulled out of the pinned staging buffer by a small kernel per piece; 0: DMA engine
@@ -188,7 +206,7 @@ int kicp_reg_set_config(kicp_reg *reg, const kicp_reg_config *config); /* the re
  *   "wait"         0 (default): poll the tagged rows in host memory; 1: hipStreamSynchronize
  *   "timing"       1: kicp_stats.gpu_ms from HIP events; 2: also kicp_stats.pass_ms[]
  * Read only: "small_active" (path of the last call: 0 generic, 1 sub-lanes, 2 wave per query), "resident_passes", "batch_queue_passes",
- *   "batch_resident_passes", "batch_threads_active", "small_relaunches", "aql_active", "aql_kernarg", "comm_ranks".
+ *   "batch_resident_passes", "batch_threads_active", "small_relaunches", "score_launches", "aql_active", "aql_kernarg", "comm_ranks".
  * Test hooks (exercise fall-backs that this hardware does not reach by itself): "small_cmd" 0 - workgroup 0 relays the resident kernels'
  *   commands (platforms without a CPU-writable BAR); "debug_tag" - jump next to the 16-bit pass tag's wrap-around; "debug_stall_us" -
  *   be late with one command; "debug_p2p_one_row" - send this rank's total as one mailbox row, as launches of more than 32 groups
@@ -279,6 +297,46 @@ int kicp_pass_correspondences(kicp_reg *reg, kicp_map *map, const double *frame_
  * words' value of the union: this is what the multi-GPU mode all-reduces. */
 int kicp_pass_words(kicp_reg *reg, kicp_map *map, const double *frame_xyz, size_t n, const double pose_qt[7],
                     double max_correspondence_distance, long long out_words[24]);
+
+/* DataAssociation (Registration.cpp:62-81) of ONE frame at `count` poses in one call: per pose the number of accepted correspondences and
+ * the sum of their squared residuals |T s - nn|^2 - elements [6] and [5] of kicp_pass_sums at that pose, bit for bit (the same search,
+ * exact resolution, tie rule and acceptance test; the same term, rounded once to 2^-40 and added as an integer, so the result does not
+ * depend on how the work is cut into workgroups or launches).  What a registration pass computes beyond these two sums is not computed.
+ * The poses (count x 7 doubles, HOST memory) are uploaded once; one launch serves many poses, and no launch serves more than option
+ * "score_chunk" queries (pose x point pairs; default 8 388 608, about a millisecond of the device; rounded down to whole tiles of 256
+ * source points, at least one) - "score_launches" (read only) tells how many the last call used.  An empty map, n == 0 or count == 0
+ * give zeros and KICP_OK; a pose without any correspondence is a result, not a warning; a NaN pose gives what kicp_pass_sums gives
+ * (zeros).  A pending kicp_map_update_pose_device_begin is collected first and its error returned.  count > 2^24 or
+ * n > 0x7FFFFFF0 / 3: KICP_ERR_CAPACITY.  With a multi-GPU exchange attached: KICP_ERR_ARG (poses are scored per device).
+ * kicp_score_poses takes a HOST frame (uploaded inside), kicp_score_poses_device a DEVICE pointer on the handle's device. */
+int kicp_score_poses(kicp_reg *reg, kicp_map *map, const double *frame_xyz, size_t n, const double *poses_qt /* count x 7 */, size_t count,
+                     double max_correspondence_distance, double *out_n_corr, double *out_ssr);
+int kicp_score_poses_device(kicp_reg *reg, kicp_map *map, const double *d_frame_xyz, size_t n, const double *poses_qt, size_t count,
+                            double max_correspondence_distance, double *out_n_corr, double *out_ssr);
+/* Global localisation of one frame in a map that is not updated: score `count` candidate poses, refine the best few, score again.
+ * Cost of a pose, lower is better (truncated least squares: a point without a correspondence costs tau^2):
+ *     cost = (ssr + ((double)n - n_corr) * (tau * tau)) / (double)n        with tau = max_correspondence_distance
+ * (ranking by the number of correspondences is no use on a dense map: the count saturates at many poses).
+ *   1. every candidate is scored (kicp_score_poses_device; the frame is uploaded once);
+ *   2. the min(top_m, count) cheapest are taken, ties to the lower index;
+ *   3. they are refined as independent registrations of the frame (kicp_register_device_batch: last pose = candidate, odometry =
+ *      identity, the handle's own configuration and options);
+ *   4. the refined poses are scored by one more call;
+ *   5. out_pose_qt = the cheapest refined pose (ties to the earlier rank), *out_candidate = the index of the candidate it started
+ *      from, *out_cost_before / *out_cost_after = that candidate's cost and the refined pose's (the last three may be null).
+ * A refinement that ends without correspondences (NaN pose) is out of the running; if all are - or the frame or the map is empty -
+ * the call returns KICP_WARN_NO_CORRESPONDENCES with the cheapest UNREFINED candidate, both costs its own.
+ * The refinement moves along the kinematic model only - a forward arc and a yaw (Registration.cpp:159-167) -, so it cannot remove a
+ * candidate's lateral offset: the candidates' lateral spacing is the caller's accuracy.  count == 0 or top_m == 0: KICP_ERR_ARG. */
+int kicp_relocalize(kicp_reg *reg, kicp_map *map, const double *frame_xyz, size_t n, const double *candidates_qt, size_t count,
+                    double max_correspondence_distance, size_t top_m, double out_pose_qt[7], size_t *out_candidate, double *out_cost_before,
+                    double *out_cost_after);
+
+/* Candidate poses for kicp_relocalize: center * planar(dx, dy, dyaw) for every offset i * step with |i * step| <= half extent, per axis
+ * (a step <= 0 or a half extent of 0 leaves that axis at the centre) - offsets in the centre's BODY frame, x slowest, yaw fastest.
+ * Returns the number of poses of the grid and writes the first min(that, cap_poses) of them (out_poses_qt may be null: count only). */
+size_t kicp_planar_grid(const double center_qt[7], double half_x, double half_y, double half_yaw, double step_x, double step_y, double step_yaw,
+                        double *out_poses_qt, size_t cap_poses);
 
 /* ---- pre-steps of the pipeline on the GPU (pipeline/KinematicICP.cpp:54-62) -----------
  * A kicp_pre owns KICP_PRE_BUFFERS device point buffers.  Results stay in HBM (feed kicp_register_device with

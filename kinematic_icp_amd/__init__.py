@@ -97,6 +97,13 @@ _SIGNATURES = {
     "kicp_pass_sums": (C.c_int, [C.c_void_p, C.c_void_p, _dp, C.c_size_t, _dp, C.c_double, _dp]),
     "kicp_pass_correspondences": (C.c_int, [C.c_void_p, C.c_void_p, _dp, C.c_size_t, _dp, C.c_double, C.POINTER(C.c_int32), _dp, _dp]),
     "kicp_pass_words": (C.c_int, [C.c_void_p, C.c_void_p, _dp, C.c_size_t, _dp, C.c_double, C.POINTER(C.c_longlong)]),
+    "kicp_score_poses": (C.c_int, [C.c_void_p, C.c_void_p, _dp, C.c_size_t, _dp, C.c_size_t, C.c_double, _dp, _dp]),
+    "kicp_score_poses_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, _dp, C.c_size_t, C.c_double, _dp, _dp]),
+    "kicp_relocalize": (C.c_int, [C.c_void_p, C.c_void_p, _dp, C.c_size_t, _dp, C.c_size_t, C.c_double, C.c_size_t, _dp, C.POINTER(C.c_size_t), _dp, _dp]),
+    "kicp_planar_grid": (C.c_size_t, [_dp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _dp, C.c_size_t]),
+    "kicp_map_save_pcd": (C.c_int, [C.c_void_p, C.c_char_p]),
+    "kicp_map_load_pcd": (C.c_int, [C.c_char_p, C.c_double, C.c_double, C.c_uint, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
+    "kicp_map_params": (C.c_int, [C.c_void_p, _dp, _dp, C.POINTER(C.c_uint)]),
     "kicp_pre_create": (C.c_int, [C.c_int, C.POINTER(C.c_void_p)]),
     "kicp_pre_destroy": (None, [C.c_void_p]),
     "kicp_pre_preprocess": (C.c_int, [C.c_void_p, _dp, C.c_size_t, _dp, C.c_size_t, _dp, _dp, C.c_double, C.c_double, C.c_int, C.c_int,
@@ -235,6 +242,17 @@ def cpus_near_gpu(device=0, one_l3_domain=True):
         return cpus
 
 
+def planar_grid(center, half_x, half_y, half_yaw, step_x, step_y, step_yaw):
+    """Candidate poses for Relocalize (kicp_planar_grid): center * planar(dx, dy, dyaw) for every offset i * step with |i * step| <= half
+    extent, per axis - offsets in the centre's body frame, x slowest, yaw fastest -> (count, 7)."""
+    _, c = _d(center)
+    args = (float(half_x), float(half_y), float(half_yaw), float(step_x), float(step_y), float(step_yaw))
+    n = lib().kicp_planar_grid(c, *args, None, 0)
+    out = np.empty((n, 7), dtype=np.float64)
+    lib().kicp_planar_grid(c, *args, out.ctypes.data_as(_dp), n)
+    return out
+
+
 class VoxelHashMap:
     """kiss_icp::VoxelHashMap: host-authoritative voxel map with an HBM mirror (SURVEY.md App. A.2)."""
 
@@ -263,6 +281,28 @@ class VoxelHashMap:
         if getattr(self, "_h", None) and _lib is not None:
             _lib.kicp_map_destroy(self._h)
             self._h = None
+
+    def save_pcd(self, path):
+        """The map as a PCD v0.7 file, DATA binary (kicp_map_save_pcd): Pointcloud() in its order plus a comment line with the three
+        parameters.  A pending map update's error is raised here."""
+        _check(lib().kicp_map_save_pcd(self._h, os.fsencode(path)))
+
+    @staticmethod
+    def load_pcd(path, voxel_size=0.0, max_distance=0.0, max_points_per_voxel=0, device=None):
+        """A new map from a PCD file (kicp_map_load_pcd), its points inserted in file order - on `device` (bulk insertion) or, with None,
+        on the host.  voxel_size <= 0: the parameters come from the file's `# kicp_map` line.  The new map's `points_read` and
+        `points_dropped` tell how many rows the file held and how many of them were not finite."""
+        m = VoxelHashMap.__new__(VoxelHashMap)
+        h, read, dropped = C.c_void_p(), C.c_size_t(), C.c_size_t()
+        m._h = None
+        _check(lib().kicp_map_load_pcd(os.fsencode(path), float(voxel_size), float(max_distance), int(max_points_per_voxel),
+                                       -1 if device is None else int(device), C.byref(h), C.byref(read), C.byref(dropped)))
+        m._h = h
+        vs, md, cap = C.c_double(), C.c_double(), C.c_uint()
+        _check(lib().kicp_map_params(h, C.byref(vs), C.byref(md), C.byref(cap)))
+        m.voxel_size_, m.max_distance_, m.max_points_per_voxel_ = vs.value, md.value, cap.value
+        m.points_read, m.points_dropped = read.value, dropped.value
+        return m
 
     def Clear(self):
         _check(lib().kicp_map_clear(self._h))
@@ -505,6 +545,35 @@ class KinematicRegistration:
         _check(lib().kicp_pass_correspondences(self._h, voxel_map._h, p, n, q, max_correspondence_distance, idx.ctypes.data_as(C.POINTER(C.c_int32)),
                                                d2.ctypes.data_as(_dp), nn.ctypes.data_as(_dp)))
         return idx, d2, nn
+
+    def ScorePoses(self, frame, voxel_map, poses, max_correspondence_distance):
+        """kicp_score_poses: DataAssociation of ONE frame ((N,3) host array or DeviceFrame) at every pose of `poses` (count, 7) in one call
+        -> (n_corr[count], ssr[count]): pass_sums(...)[6] and [5] at each pose, bit for bit."""
+        q = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(-1, 7))
+        count = q.shape[0]
+        n_corr, ssr = np.zeros(count, dtype=np.float64), np.zeros(count, dtype=np.float64)
+        if isinstance(frame, DeviceFrame):
+            _check(lib().kicp_score_poses_device(self._h, voxel_map._h, frame.ptr, frame.n, q.ctypes.data_as(_dp), count, max_correspondence_distance,
+                                                 n_corr.ctypes.data_as(_dp), ssr.ctypes.data_as(_dp)))
+        else:
+            a, p = _d(frame)
+            _check(lib().kicp_score_poses(self._h, voxel_map._h, p, a.size // 3, q.ctypes.data_as(_dp), count, max_correspondence_distance,
+                                          n_corr.ctypes.data_as(_dp), ssr.ctypes.data_as(_dp)))
+        return n_corr, ssr
+
+    def Relocalize(self, frame, voxel_map, candidates, max_correspondence_distance, top_m=8):
+        """kicp_relocalize: score the candidate poses (count, 7), refine the top_m cheapest as independent registrations, score again ->
+        (pose[7], candidate index, cost before, cost after); cost = (ssr + (n - n_corr) tau^2) / n.  last_status is
+        KICP_WARN_NO_CORRESPONDENCES when no refinement kept a correspondence (the cheapest unrefined candidate is returned then).  The
+        refinement moves along the kinematic model only: the candidates' lateral spacing is the caller's accuracy."""
+        a, p = _d(frame)
+        q = np.ascontiguousarray(np.asarray(candidates, dtype=np.float64).reshape(-1, 7))
+        pose = np.zeros(7, dtype=np.float64)
+        cand, before, after = C.c_size_t(), C.c_double(), C.c_double()
+        rc = lib().kicp_relocalize(self._h, voxel_map._h, p, a.size // 3, q.ctypes.data_as(_dp), q.shape[0], max_correspondence_distance, int(top_m),
+                                   pose.ctypes.data_as(_dp), C.byref(cand), C.byref(before), C.byref(after))
+        self.last_status = rc if rc >= 0 else _check(rc)
+        return pose, cand.value, before.value, after.value
 
     def pass_words(self, frame, voxel_map, pose, max_correspondence_distance):
         """The same pass as raw int64[24] limb words (the multi-GPU all-reduce payload; see sharding.py)."""

@@ -37,6 +37,24 @@ inline const double *xyz(const std::vector<Eigen::Vector3d> &v) {
     static_assert(sizeof(Eigen::Vector3d) == 3 * sizeof(double), "Eigen::Vector3d must be 3 packed doubles");
     return v.empty() ? nullptr : v.front().data();
 }
+// Candidate poses for KinematicICP::Relocalize / KinematicRegistration::Relocalize (kicp.h kicp_planar_grid): center * planar(dx, dy,
+// dyaw) for every offset i * step within the half extents, offsets in the centre's body frame, x slowest, yaw fastest.
+inline std::vector<Sophus::SE3d> planar_grid(const Sophus::SE3d &center, double half_x, double half_y, double half_yaw, double step_x, double step_y,
+                                             double step_yaw) {
+    double c[7];
+    to_params(center, c);
+    std::vector<double> flat(7 * kicp_planar_grid(c, half_x, half_y, half_yaw, step_x, step_y, step_yaw, nullptr, 0));
+    kicp_planar_grid(c, half_x, half_y, half_yaw, step_x, step_y, step_yaw, flat.data(), flat.size() / 7);
+    std::vector<Sophus::SE3d> poses;
+    poses.reserve(flat.size() / 7);
+    for (size_t k = 0; k < flat.size() / 7; ++k) poses.push_back(from_params(&flat[7 * k]));
+    return poses;
+}
+inline std::vector<double> to_params(const std::vector<Sophus::SE3d> &poses) {
+    std::vector<double> flat(7 * poses.size());
+    for (size_t k = 0; k < poses.size(); ++k) to_params(poses[k], &flat[7 * k]);
+    return flat;
+}
 // Which GPU the drop-in classes use: the reference API has no notion of a device, so the choice travels out of band -
 // KICP_DEVICE in the environment (default 0), read once per process.
 inline int default_device() {

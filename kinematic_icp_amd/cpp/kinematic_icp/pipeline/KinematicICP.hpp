@@ -14,6 +14,8 @@
 #include <kiss_icp/core/VoxelHashMap.hpp>
 #include <kiss_icp/core/VoxelUtils.hpp>
 #include <sophus/se3.hpp>
+#include <stdexcept>
+#include <string>
 #include <tuple>
 #include <utility>
 #include <vector>
@@ -43,6 +45,9 @@ struct Config {
     double fixed_regularization = 0.0;
     // Motion compensation
     bool deskew = false;
+    // backend extension (last member, so aggregate initialisers of the reference's fields keep their meaning): false = localisation in a
+    // prior map - RegisterFrame and its siblings do everything but the map update, and SetPose leaves the map alone
+    bool update_map = true;
 };
 
 class KinematicICP {
@@ -125,7 +130,7 @@ public:
         const auto new_pose = registration_.ComputeRobotMotion(source, local_map_, last_pose_, relative_odometry, tau);
         const auto odometry_error = (last_pose_ * relative_odometry).inverse() * new_pose;
         correspondence_threshold_.UpdateOdometryError(odometry_error);
-        local_map_.Update(frame_downsample, new_pose);
+        if (config_.update_map) local_map_.Update(frame_downsample, new_pose);
         last_pose_ = new_pose;
         return {preprocessed_frame_in_base, source};
 #endif
@@ -216,10 +221,35 @@ public:
     void LocalMapF32(std::vector<uint8_t> &data) const { local_map_.PointcloudF32(data); }
 #endif
 
+    // (with Config::update_map == false the map is a prior the caller loaded: SetPose then moves the robot, not the map)
     inline void SetPose(const Sophus::SE3d &pose) {
         last_pose_ = pose;
-        local_map_.Clear();
+        if (config_.update_map) local_map_.Clear();
         correspondence_threshold_.Reset();
+    }
+
+    // ---- backend extension: localising in a saved map (INTEGRATION.md "Localising in a saved map") ----
+    // SaveMap writes the local map as a PCD file; LoadMap replaces it by a file's map (its voxel size, range and points per voxel come
+    // from the file's `# kicp_map` line when it has one, from this pipeline's Config otherwise).
+    void SaveMap(const std::string &path) const { local_map_.SavePCD(path); }
+    void LoadMap(const std::string &path) {
+        try {
+            local_map_ = kiss_icp::VoxelHashMap::LoadPCD(path);
+        } catch (const std::runtime_error &) {  // (a foreign file without the parameter line; any other problem throws again)
+            local_map_ = kiss_icp::VoxelHashMap::LoadPCD(path, config_.voxel_size, config_.max_range, config_.max_points_per_voxel);
+        }
+    }
+    // Relocalize: which of `candidates` (kicp_bridge::planar_grid builds a grid) explains `keypoints` - a registration source in the
+    // base frame, e.g. the second cloud RegisterFrame returns - best: all are scored against the map, the top_m cheapest refined and
+    // scored again (kicp.h kicp_relocalize; tau = the threshold of a first frame).  The result becomes the pipeline's pose.  The
+    // refinement moves along the kinematic model only: the candidates' lateral spacing is the accuracy.
+    KinematicRegistration::Relocalization Relocalize(const std::vector<Eigen::Vector3d> &keypoints, const std::vector<Sophus::SE3d> &candidates,
+                                                     size_t top_m = 8) {
+        correspondence_threshold_.Reset();
+        const double tau = correspondence_threshold_.ComputeThreshold();
+        const auto found = registration_.Relocalize(keypoints, local_map_, candidates, tau, top_m);
+        last_pose_ = found.pose;
+        return found;
     }
 
     std::vector<Eigen::Vector3d> LocalMap() const { return local_map_.Pointcloud(); }
@@ -251,7 +281,7 @@ protected:
         trace.lap("threshold + map update");
         correspondence_threshold_.UpdateOdometryError((last_pose_ * relative_odometry).inverse() * new_pose);
         // (the map update's kernels run while this thread collects the two returned clouds: nothing below touches the map or buffer 1)
-        local_map_.UpdateDeviceBegin(kicp_pre_device_ptr(pre_, 1, nullptr), n_down, new_pose);
+        if (config_.update_map) local_map_.UpdateDeviceBegin(kicp_pre_device_ptr(pre_, 1, nullptr), n_down, new_pose);
         last_pose_ = new_pose;
     }
     Vector3dVectorTuple RegisterChained(Vector3dVectorTuple &result, DownloadGuard &guard, const size_t counts[3], const Sophus::SE3d &relative_odometry) {
@@ -271,7 +301,7 @@ protected:
         // next frame's pre-steps instead of this thread's idle wait (round 6; the points they read stay in the pre-step workspace's
         // spare buffer meanwhile).  KICP_SYNC_MAP_UPDATE=1: wait here, as round 5 did.
         static const bool sync_update = [] { const char *e = std::getenv("KICP_SYNC_MAP_UPDATE"); return e && *e && *e != '0'; }();
-        if (sync_update) {
+        if (sync_update && config_.update_map) {
             trace.lap("map update: wait");
             local_map_.UpdateFinish();
         }
@@ -300,7 +330,7 @@ protected:
         }
         if (frame_data) frame_data->resize(counts[0] * step);
         static const bool sync_update = [] { const char *e = std::getenv("KICP_SYNC_MAP_UPDATE"); return e && *e && *e != '0'; }();
-        if (sync_update) {
+        if (sync_update && config_.update_map) {
             trace.lap("map update: wait");
             local_map_.UpdateFinish();
         }

@@ -100,6 +100,41 @@ struct KinematicRegistration {
         return kicp_bridge::from_params(out);
     }
 
+    // backend extension: DataAssociation (Registration.cpp:62-81) of ONE frame at many poses in one call (kicp.h kicp_score_poses):
+    // per pose {number of correspondences, sum of their squared residuals}
+    std::vector<std::pair<double, double>> ScorePoses(const std::vector<Eigen::Vector3d> &frame, const kiss_icp::VoxelHashMap &voxel_map,
+                                                      const std::vector<Sophus::SE3d> &poses, const double max_correspondence_distance) {
+        const std::vector<double> flat = kicp_bridge::to_params(poses);
+        std::vector<double> n_corr(poses.size()), ssr(poses.size());
+        kicp_bridge::check(kicp_score_poses(handle_, voxel_map.handle(), kicp_bridge::xyz(frame), frame.size(), flat.data(), poses.size(),
+                                            max_correspondence_distance, n_corr.data(), ssr.data()),
+                           "KinematicRegistration::ScorePoses");
+        std::vector<std::pair<double, double>> scores(poses.size());
+        for (size_t k = 0; k < poses.size(); ++k) scores[k] = {n_corr[k], ssr[k]};
+        return scores;
+    }
+    // backend extension: localise the frame among candidate poses (kicp.h kicp_relocalize): score all, refine the top_m cheapest, score
+    // again.  `found` (nullable) tells whether a refinement kept correspondences; without one the cheapest unrefined candidate returns.
+    struct Relocalization {
+        Sophus::SE3d pose;
+        size_t candidate = 0;
+        double cost_before = 0.0, cost_after = 0.0;
+        bool refined = false;
+    };
+    Relocalization Relocalize(const std::vector<Eigen::Vector3d> &frame, const kiss_icp::VoxelHashMap &voxel_map, const std::vector<Sophus::SE3d> &candidates,
+                              const double max_correspondence_distance, const size_t top_m = 8) {
+        const kicp_reg_config c = config();
+        kicp_bridge::check(kicp_reg_set_config(handle_, &c), "KinematicRegistration");
+        const std::vector<double> flat = kicp_bridge::to_params(candidates);
+        Relocalization r;
+        double out[7];
+        const int rc = kicp_bridge::check(kicp_relocalize(handle_, voxel_map.handle(), kicp_bridge::xyz(frame), frame.size(), flat.data(), candidates.size(),
+                                                          max_correspondence_distance, top_m, out, &r.candidate, &r.cost_before, &r.cost_after),
+                                          "KinematicRegistration::Relocalize");
+        r.pose = kicp_bridge::from_params(out), r.refined = rc == KICP_OK;
+        return r;
+    }
+
     int max_num_iterations_;
     double convergence_criterion_;
     int max_num_threads_;

@@ -16,6 +16,7 @@
 #include <limits>
 #include <sophus/se3.hpp>
 #include <stdexcept>
+#include <string>
 #include <tuple>
 #include <type_traits>
 #include <unordered_map>
@@ -182,6 +183,16 @@ struct VoxelHashMap {
         data.resize(total * kicp_bridge::PointCloud2Xyz32::point_step);
         if (total) kicp_bridge::check(kicp_map_pointcloud_f32(handle_, reinterpret_cast<float *>(data.data()), total, &total), "VoxelHashMap::PointcloudF32");
     }
+    // The map as a PCD v0.7 file (DATA binary; kicp.h kicp_map_save_pcd / kicp_map_load_pcd); backend extension.  LoadPCD with
+    // voxel_size <= 0 takes the three parameters from the file's `# kicp_map` line; the points are inserted in file order.
+    void SavePCD(const std::string &path) const { kicp_bridge::check(kicp_map_save_pcd(handle_, path.c_str()), "VoxelHashMap::SavePCD"); }
+    static VoxelHashMap LoadPCD(const std::string &path, double voxel_size = 0.0, double max_distance = 0.0, unsigned int max_points_per_voxel = 0,
+                                size_t *points_dropped = nullptr) {
+        kicp_map *h = nullptr;
+        kicp_bridge::check(kicp_map_load_pcd(path.c_str(), voxel_size, max_distance, max_points_per_voxel, kicp_bridge::default_device(), &h, nullptr, points_dropped),
+                           "VoxelHashMap::LoadPCD");
+        return VoxelHashMap(h);
+    }
     // One query -> (closest point, distance); (0, DBL_MAX) when the 27 voxels hold nothing.  Runs the device search.
     std::tuple<Eigen::Vector3d, double> GetClosestNeighbor(const Eigen::Vector3d &query) const {
         Eigen::Vector3d nn;
@@ -200,6 +211,9 @@ struct VoxelHashMap {
     int device_ = kicp_bridge::default_device();  // KICP_DEVICE
 
 private:
+    explicit VoxelHashMap(kicp_map *loaded) : map_(this), handle_(loaded) {  // (LoadPCD: the parameters are the loaded map's)
+        kicp_map_params(handle_, &voxel_size_, &max_distance_, &max_points_per_voxel_);
+    }
     kicp_map *handle_ = nullptr;
     uint64_t version_ = 0;  // bumped by every call that may change the map: map_'s snapshot is rebuilt on its next use
 };

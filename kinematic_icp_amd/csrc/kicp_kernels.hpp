@@ -221,7 +221,16 @@ constexpr int kWaveLimbs = kTermLimbs * kNumSums;
 constexpr int kLendJobs = 32;                     // voxels a wave's loaded queries can give away per round (gather32_pass)
 constexpr int kLendWords = kLendJobs * (1 + 7 + 7);  // per wave: the jobs, the lent lanes' own records, the records they hand back
 struct Acc {
+    static constexpr bool kScoreOnly = false;
     int limb[kWaveLimbs];
+    int range_error;
+};
+// What kicp_score_poses keeps of a correspondence (kicp_score.hpp): the squared residual - the term of sum 5, through the same
+// to_fixed - and the fact that there is one.  No basis, no Jacobian terms, no 28-limb row.
+struct ScoreAcc {
+    static constexpr bool kScoreOnly = true;
+    int limb[kTermLimbs];  // to_fixed(|T s - nn|^2)
+    int hit;               // 1: this lane holds a correspondence
     int range_error;
 };
 // The term as an integer, T = rint(x 2^40) (|T| < 2^83; x 2^40 is exact, rint of a double beyond 2^52 is the double itself), split
@@ -427,6 +436,8 @@ __device__ __forceinline__ double exact_d2(const MapView &m, uint32_t gidx, cons
 // 1e-12 on random data, the parity suite holds the sums and poses to the oracle's, which keeps the literal form); nothing here
 // takes part in a decision - every term is rounded to 2^-40 right afterwards - so the multiply-adds are fused.
 // One function for every pass kernel: their terms are the same doubles.
+// |r|^2 of a residual, the term of sum 5: ONE expression for the pass kernels and for k_score_poses (kicp_score.hpp)
+__device__ __forceinline__ double squared_residual(double rx, double ry, double rz) { return fma(rx, rx, fma(ry, ry, rz * rz)); }
 __device__ __forceinline__ void correspondence_terms(const PassBasis &B, double sx, double sy, double qx, double qy, double qz, double tx, double ty, double tz,
                                                      double (&term)[5]) {
     const double rx = qx - tx, ry = qy - ty, rz = qz - tz;  // residual = T*source - target (Registration.cpp:88)
@@ -436,7 +447,13 @@ __device__ __forceinline__ void correspondence_terms(const PassBasis &B, double 
     term[1] = fma(sx, sx, sy * sy);
     term[2] = a;
     term[3] = fma(sx, b, -(sy * a));
-    term[4] = fma(rx, rx, fma(ry, ry, rz * rz));
+    term[4] = squared_residual(rx, ry, rz);
+}
+// the same residual as correspondence_terms forms it, and nothing else (kicp_score_poses)
+__device__ __forceinline__ void accumulate(ScoreAcc &a, double qx, double qy, double qz, double tx, double ty, double tz) {
+    const double rx = qx - tx, ry = qy - ty, rz = qz - tz;
+    to_fixed(squared_residual(rx, ry, rz), a.limb, a.range_error);
+    a.hit = 1;
 }
 __device__ __forceinline__ void accumulate(Acc &a, const PassBasis &B, double sx, double sy, double qx, double qy, double qz, double tx, double ty, double tz) {
     double term[5];
@@ -1205,8 +1222,10 @@ __device__ __forceinline__ void export_correspondence(const PassParams &p, uint3
     p.corr_d2[i] = idx == kNoIndex32 ? DBL_MAX : d2;
     p.corr_nn[3 * i] = x, p.corr_nn[3 * i + 1] = y, p.corr_nn[3 * i + 2] = z;
 }
-template <bool EXPORT = false>
-__device__ __forceinline__ void resolve_and_accumulate(Acc &acc, const PassParams &p, bool host_pose, const double *__restrict__ src, const Pose &T, uint32_t i,
+// ACC = ScoreAcc (k_score_poses): the same search result, resolution, tie rule and acceptance test; only what is kept of an accepted
+// correspondence differs (its squared residual and the count - no basis, no Jacobian terms)
+template <bool EXPORT = false, class ACC = Acc>
+__device__ __forceinline__ void resolve_and_accumulate(ACC &acc, const PassParams &p, bool host_pose, const double *__restrict__ src, const Pose &T, uint32_t i,
                                                        const Best3 &t, const KeptQuery *kept = nullptr) {
     if (EXPORT && i != kNoIndex32) export_correspondence(p, i, kNoIndex32, 0.0, 0.0, 0.0, 0.0);  // (overwritten below when the query has a correspondence)
     if (i == kNoIndex32 || t.i1 == kNoIndex32 || (kDbgBuild && p.dbg != 0 && p.dbg != 9 && p.dbg != 11 && p.dbg != 12 && p.dbg != 13 && p.dbg != 14)) return;
@@ -1251,17 +1270,21 @@ __device__ __forceinline__ void resolve_and_accumulate(Acc &acc, const PassParam
             wx = tp[0], wy = tp[1], wz = tp[2];
         }
         if (EXPORT) export_correspondence(p, i, best_idx, best, wx, wy, wz);
-        // The basis is taken up HERE - behind an opaque copy of the flag, so that the compiler cannot merge its two sources ahead of
-        // the exact phase and carry sixteen registers through it (the four-waves build spilled them) - and, where it is the host's,
-        // read from the kernarg segment here rather than at the kernel's start (args_at_point_of_use).
-        if (dbg_is(p, 13)) return;  // (attribution, tools/valu_attribution.sh: the exact phase without the terms)
-        int from_args = __builtin_amdgcn_readfirstlane(host_pose ? 1 : 0);
-        asm volatile("; the basis is taken up here" : "+s"(from_args));
-        PassBasis B;
-        if (from_args) B = args_at_point_of_use().sol.basis;
-        else B = basis_of(T);
-        // the untransformed source point again (L1 / L2 hit) unless the build kept it: cheaper than registers kept live through the search
-        accumulate(acc, B, kept ? kept->sx : src[3 * i], kept ? kept->sy : src[3 * i + 1], q.x, q.y, q.z, wx, wy, wz);
+        if constexpr (ACC::kScoreOnly) {
+            accumulate(acc, q.x, q.y, q.z, wx, wy, wz);
+        } else {
+            // The basis is taken up HERE - behind an opaque copy of the flag, so that the compiler cannot merge its two sources ahead of
+            // the exact phase and carry sixteen registers through it (the four-waves build spilled them) - and, where it is the host's,
+            // read from the kernarg segment here rather than at the kernel's start (args_at_point_of_use).
+            if (dbg_is(p, 13)) return;  // (attribution, tools/valu_attribution.sh: the exact phase without the terms)
+            int from_args = __builtin_amdgcn_readfirstlane(host_pose ? 1 : 0);
+            asm volatile("; the basis is taken up here" : "+s"(from_args));
+            PassBasis B;
+            if (from_args) B = args_at_point_of_use().sol.basis;
+            else B = basis_of(T);
+            // the untransformed source point again (L1 / L2 hit) unless the build kept it: cheaper than registers kept live through the search
+            accumulate(acc, B, kept ? kept->sx : src[3 * i], kept ? kept->sy : src[3 * i + 1], q.x, q.y, q.z, wx, wy, wz);
+        }
     }
 }
 
@@ -1282,8 +1305,8 @@ __device__ __forceinline__ void resolve_and_accumulate(Acc &acc, const PassParam
 constexpr int kParkWords = 5;
 // `host_pose`: T is the host's pose (kernel arguments) and p.sol.basis its basis; where the kernel got T from the device the basis
 // is formed right before the exact phase, not kept through the search.
-template <int BLOCK, int G, bool SPLIT, bool LAT, bool PARK = false, bool EXPORT = false>
-__device__ __forceinline__ void gather32_pass(const PassParams &p, const Pose &T, bool host_pose, uint32_t tid, Acc &acc, const double *__restrict__ src, uint32_t n,
+template <int BLOCK, int G, bool SPLIT, bool LAT, bool PARK = false, bool EXPORT = false, class ACC = Acc>
+__device__ __forceinline__ void gather32_pass(const PassParams &p, const Pose &T, bool host_pose, uint32_t tid, ACC &acc, const double *__restrict__ src, uint32_t n,
                                               uint32_t block, int *lend = nullptr, double *park = nullptr) {
     const MapView &m = p.map;
     const float margin = p.search.margin_u;
@@ -1415,11 +1438,12 @@ __device__ __forceinline__ void gather32_pass(const PassParams &p, const Pose &T
         kept.sx = park[3 * BLOCK + tid], kept.sy = park[4 * BLOCK + tid], kept.voxel = false;
     }
     if (sub == 0) {
-        resolve_and_accumulate<EXPORT>(acc, p, host_pose, src, T, L.i, L.t, (LAT || PARK) ? &kept : nullptr);
+        resolve_and_accumulate<EXPORT, ACC>(acc, p, host_pose, src, T, L.i, L.t, (LAT || PARK) ? &kept : nullptr);
     }
     // dbg 10 (bench.py's latency model): no correspondences are formed; the "count" sum carries the number of visiting rounds
     // this WAVE ran - its chain of dependent bucket visits - from lane 0 (as rounds x 2^40: limb 1 holds bits 21..41, limb 2 the rest)
-    if (dbg_is(p, 10) && (tid & 63u) == 0u) acc.limb[6 * kTermLimbs + 1] = static_cast<int>(rounds & 3u) << 19, acc.limb[6 * kTermLimbs + 2] = static_cast<int>(rounds >> 2);
+    if constexpr (!ACC::kScoreOnly)
+        if (dbg_is(p, 10) && (tid & 63u) == 0u) acc.limb[6 * kTermLimbs + 1] = static_cast<int>(rounds & 3u) << 19, acc.limb[6 * kTermLimbs + 2] = static_cast<int>(rounds >> 2);
 }
 template <int BLOCK, int G, int OCC, bool SPLIT, bool LAT = false, bool EXPORT = false>
 __global__ __launch_bounds__(BLOCK, OCC) void k_pass_gather32(const PassParams p) {

@@ -4,8 +4,8 @@
 using namespace kicp;
 using namespace kicp::host;
 
-namespace {
-constexpr size_t kBarFramePoints = 8192;  // host frames up to this size travel through the BAR (kicp_register)
+namespace kicp {
+namespace host {
 int ensure_frame(kicp_reg *r, size_t n) {
     if (n <= r->frame_cap) return KICP_OK;
     if (int rc = aql_quiesce(r)) return rc;
@@ -16,6 +16,10 @@ int ensure_frame(kicp_reg *r, size_t n) {
     r->frame_cap = want;
     return KICP_OK;
 }
+}  // namespace host
+}  // namespace kicp
+namespace {
+constexpr size_t kBarFramePoints = 8192;  // host frames up to this size travel through the BAR (kicp_register)
 // A piece of a host frame, read by the GPU straight out of the handle's pinned staging buffer (host-mapped memory, over PCIe) and
 // written as fp64 into the device frame: float32 sources are widened on the way - static_cast<double>(float) is exact, i.e. what
 // the reference's host-side conversion produces (ros/src/kinematic_icp_ros/utils/RosUtils.cpp:30-39).  16 bytes per lane and load.
@@ -132,6 +136,8 @@ void kicp_reg_destroy(kicp_reg *reg) {
     if (reg->d_tickets) hipFree(reg->d_tickets);
     if (reg->d_group_acc) hipFree(reg->d_group_acc);
     if (reg->d_frame) hipFree(reg->d_frame);
+    if (reg->d_score_poses) hipFree(reg->d_score_poses);
+    if (reg->d_score_acc) hipFree(reg->d_score_acc);
     if (reg->ev0) hipEventDestroy(reg->ev0);
     if (reg->ev1) hipEventDestroy(reg->ev1);
     for (auto &e : reg->evp)
@@ -186,6 +192,7 @@ int kicp_reg_set_option(kicp_reg *reg, const char *name, double value) {
         reg->small_cmd = value != 0.0 ? 1 : 0;
     }
     else if (k == "small_timeout_us") reg->small_timeout_us = value;
+    else if (k == "score_chunk") reg->score_chunk = value >= 1.0 ? std::min(value, 1.0e15) : 8388608.0;  // (0: back to the default)
     else if (k == "debug_stall_us") reg->debug_stall_us = value;
     else if (k == "dbg") {
 #ifdef KICP_DBG_BUILD
@@ -239,6 +246,8 @@ double kicp_reg_get_option(const kicp_reg *reg, const char *name) {
     }
     if (k == "small_cmd") return (reg->small_cmd == 1 && reg->cmd_bar) ? 1.0 : (reg->small_cmd ? 0.5 : 0.0);  // 1: BAR copies in use; 0.5: requested, not yet set up
     if (k == "small_timeout_us") return reg->small_timeout_us;
+    if (k == "score_chunk") return reg->score_chunk;
+    if (k == "score_launches") return reg->score_launches;
     if (k == "small_active") return reg->last_small;  // path of the last registration: 0 generic, 1 small (sub-lanes per query), 2 small (wave per query)
     if (k == "small_relaunches") return static_cast<double>(reg->small_relaunches);
     if (k == "aql_active") return (reg->aql.ready && reg->last_via_aql) ? 1.0 : 0.0;  // was the last pass dispatched through the AQL queue
@@ -422,6 +431,7 @@ int kicp_reg_clone(const kicp_reg *reg, kicp_reg **out) {
     c->small_cmd = reg->cmd_bar ? 1 : reg->small_cmd, c->use_small = reg->use_small, c->small_block = reg->small_block, c->small_wave = reg->small_wave;
     c->wave_block = reg->wave_block, c->small_resident = reg->small_resident, c->small_timeout_us = reg->small_timeout_us, c->small_group_rows = reg->small_group_rows;
     c->resident_generic = reg->resident_generic, c->batch_resident = reg->batch_resident, c->batch_depth = reg->batch_depth, c->batch_rotate = reg->batch_rotate, c->batch_queues = reg->batch_queues, c->batch_threads = reg->batch_threads ;
+    c->score_chunk = reg->score_chunk;
     *out = c;
     return KICP_OK;
 }

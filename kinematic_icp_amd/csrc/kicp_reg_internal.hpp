@@ -8,6 +8,7 @@
 //   kicp_reg_queues.hip   batches with several scans in flight on queues of their own (also sharded: shared segment / RCCL lanes)
 //   kicp_reg_comm.hip     the multi-GPU exchanges: RCCL communicator, host shared segment, peer mailboxes, caller-supplied all-reduce
 //   kicp_reg_api.hip      the C-ABI entry points of include/kicp.h: create / destroy / options / kicp_register* / kicp_pass_*
+// and kicp_score.hip (one frame scored at many poses, kicp_relocalize) works on the same handle.
 #pragma once
 #include <dlfcn.h>
 #include <fcntl.h>
@@ -197,6 +198,12 @@ struct kicp_reg {
     unsigned long long batch_resident_passes = 0;  // passes served that way so far (get-only "batch_resident_passes")
     int last_resident_passes = 0; // passes of the last call that a resident launch of the GENERIC kernel served (get-only "resident_passes")
     int small_prev_iters = 2;     // iterations of the previous small-path call: a scan that converged at once makes the next launch leave after its first pass
+    // kicp_score_poses (kicp_score.hip): the uploaded poses and their accumulator rows, a batch of poses at a time
+    double *d_score_poses = nullptr;
+    unsigned long long *d_score_acc = nullptr;
+    size_t score_cap = 0;             // poses the two buffers hold
+    double score_chunk = 8388608.0;   // option "score_chunk": queries (pose x point pairs) one launch of k_score_poses may serve
+    int score_launches = 0;           // launches the last kicp_score_poses call used (get-only "score_launches")
     uint32_t trace_pass = 1;      // the pass of a launch the stamps are taken on (the option's value)
     long long *d_trace = nullptr; // option "small_trace": device buffer of the kernel's per-pass wall-clock stamps
     double trace_host_us = 0.0, trace_dev_us = 0.0, trace_first_us = 0.0;  // host: rows seen -> command sent; device: command sent -> rows seen; launch -> first rows
@@ -276,6 +283,7 @@ const AqlKernel *aql_small_kernel_for(kicp_reg *r, int block, int g, bool wave);
 int aql_quiesce(kicp_reg *r);
 int launch_pass(kicp_reg *r, const PassParams &p, bool allow_aql = false);
 int ensure_partials(kicp_reg *r, size_t blocks);
+int ensure_frame(kicp_reg *r, size_t n);  // room for a host frame of n points in r->d_frame (kicp_reg_api.hip)
 int ensure_rows(kicp_reg *r, size_t groups);
 int next_tag(kicp_reg *r, uint32_t *tag);
 int enqueue_allreduce(kicp_reg *r);

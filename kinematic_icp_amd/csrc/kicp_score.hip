@@ -1,0 +1,204 @@
+// kicp_score.hip -- one frame scored at many poses (kicp_score_poses*, kernel: kicp_score.hpp) and kicp_relocalize on top of it:
+// score the candidates, refine the best few as independent registrations, score again (see kicp_reg_internal.hpp for the handle)
+#include "kicp_reg_internal.hpp"
+#include "kicp_score.hpp"
+
+using namespace kicp;
+using namespace kicp::host;
+
+namespace {
+constexpr size_t kScoreMaxPoses = static_cast<size_t>(1) << 24;
+constexpr size_t kScoreMaxPoints = 0x7FFFFFF0ull / 3;
+constexpr size_t kScoreBatch = 65536;     // poses uploaded, scored and collected at a time (buffers: 120 bytes per pose)
+constexpr uint32_t kScoreMaxGrid = 2048;  // workgroups of a launch; they stride over the launch's items
+
+int ensure_score(kicp_reg *r, size_t poses) {
+    if (poses <= r->score_cap) return KICP_OK;
+    HIP_TRY(hipStreamSynchronize(r->stream));
+    if (r->d_score_poses) HIP_TRY(hipFree(r->d_score_poses));
+    if (r->d_score_acc) HIP_TRY(hipFree(r->d_score_acc));
+    r->d_score_poses = nullptr, r->d_score_acc = nullptr, r->score_cap = 0;
+    const size_t want = std::min(kScoreBatch, poses + poses / 2 + 64);
+    HIP_TRY(hipMalloc(&r->d_score_poses, want * 7 * sizeof(double)));
+    HIP_TRY(hipMalloc(&r->d_score_acc, want * kScoreWords * sizeof(unsigned long long)));
+    r->score_cap = want;
+    return KICP_OK;
+}
+// The two sums of a pose from its accumulator row: the limb sums (limb k at 2^(21 k)) are put together as ONE integer, cut into
+// the three 40-bit limbs every hand-off of the pass kernels carries (i128_to_limbs) and converted by the same function: the double
+// kicp_pass_sums returns for the same integer.
+void row_to_sums(const unsigned long long *row, double &n_corr, double &ssr) {
+    __int128 t = 0;
+    for (int j = 0; j < kTermLimbs; ++j) t += static_cast<__int128>(static_cast<long long>(row[j])) * (static_cast<__int128>(1) << (21 * j));
+    const unsigned __int128 u = static_cast<unsigned __int128>(t);
+    const unsigned long long m40 = (1ull << 40) - 1;
+    const long long l[3] = {static_cast<long long>(static_cast<unsigned long long>(u) & m40), static_cast<long long>(static_cast<unsigned long long>(u >> 40) & m40),
+                            static_cast<long long>(t >> 80)};
+    ssr = host_limbs_to_double(l);
+    n_corr = static_cast<double>(row[kScoreCountWord]);
+}
+int check_score_args(const kicp_reg *reg, const kicp_map *map, const void *frame, size_t n, const double *poses_qt, size_t count, const double *out_a,
+                     const double *out_b) {
+    if (!reg || !map || (!frame && n) || (count && (!poses_qt || !out_a || !out_b))) return fail(KICP_ERR_ARG, "null argument");
+    if (count > kScoreMaxPoses) return fail(KICP_ERR_CAPACITY, "more than 2^24 poses");
+    if (n > kScoreMaxPoints) return fail(KICP_ERR_CAPACITY, "frame too large");
+    if (reg->comm || reg->allreduce_fn || reg->shm || reg->d_p2p_table) return fail(KICP_ERR_ARG, "detach the multi-GPU exchange first: poses are scored per device");
+    return KICP_OK;
+}
+// (arguments checked; `d_frame` on the handle's device)
+int score_device(kicp_reg *reg, kicp_map *map, const double *d_frame, size_t n, const double *poses_qt, size_t count, double tau, double *out_n_corr,
+                 double *out_ssr) {
+    reg->score_launches = 0;
+    for (size_t k = 0; k < count; ++k) out_n_corr[k] = out_ssr[k] = 0.0;
+    if (int rc = map_finish_pending(map)) return rc;  // (a deferred update's error is this call's: the map it would score against is not the updated one)
+    if (kicp_map_empty(map) || n == 0 || count == 0) return KICP_OK;
+    if (int rc = set_device(reg->device)) return rc;
+    if (int rc = map_sync(map, reg->device, reg->stream)) return rc;
+    if (int rc = aql_quiesce(reg)) return rc;
+    reg->stream_dirty = true;
+    if (int rc = ensure_score(reg, std::min(count, kScoreBatch))) return rc;
+    ScoreParams sp{};
+    sp.pass.src = d_frame, sp.pass.n = static_cast<uint32_t>(n), sp.pass.map = map->mirror.view, sp.pass.tau = tau;
+    sp.pass.search = search_params(tau, map->mirror.view.voxel_size);
+    const unsigned long long tiles = (n + kScoreBlock - 1) / kScoreBlock;
+    // a launch serves whole tiles (256 queries, the frame's last one fewer): as many as fit "score_chunk", at least one
+    const unsigned long long per_launch = std::max<unsigned long long>(1ull, static_cast<unsigned long long>(reg->score_chunk / kScoreBlock));
+    std::vector<unsigned long long> rows;
+    for (size_t first = 0; first < count; first += reg->score_cap) {
+        const size_t m = std::min(reg->score_cap, count - first);
+        if (int rc = staged_upload(reg->stage, 0, reg->d_score_poses, poses_qt + 7 * first, m * 7 * sizeof(double), reg->stream)) return rc;
+        HIP_TRY(hipMemsetAsync(reg->d_score_acc, 0, m * kScoreWords * sizeof(unsigned long long), reg->stream));
+        sp.poses = reg->d_score_poses, sp.acc = reg->d_score_acc, sp.count = static_cast<uint32_t>(m);
+        const unsigned long long total = tiles * m;
+        for (unsigned long long item0 = 0; item0 < total; item0 += per_launch) {
+            sp.item0 = item0, sp.items = std::min(per_launch, total - item0);
+            const uint32_t grid = static_cast<uint32_t>(std::min<unsigned long long>(sp.items, kScoreMaxGrid));
+            hipLaunchKernelGGL(k_score_poses, dim3(grid), dim3(kScoreBlock), 0, reg->stream, sp);
+            ++reg->score_launches;
+        }
+        HIP_TRY(hipGetLastError());
+        rows.resize(m * kScoreWords);
+        if (int rc = staged_download(reg->stage, rows.data(), reg->d_score_acc, rows.size() * sizeof(unsigned long long), reg->stream)) return rc;
+        for (size_t k = 0; k < m; ++k) row_to_sums(&rows[k * kScoreWords], out_n_corr[first + k], out_ssr[first + k]);
+    }
+    return KICP_OK;
+}
+// a host frame into the handle's device frame (nothing to do for an empty frame or map: no kernel will read it)
+int upload_frame(kicp_reg *reg, kicp_map *map, const double *frame_xyz, size_t n) {
+    if (n == 0 || kicp_map_empty(map)) return KICP_OK;
+    if (int rc = set_device(reg->device)) return rc;
+    if (int rc = ensure_frame(reg, n)) return rc;
+    if (int rc = aql_quiesce(reg)) return rc;
+    reg->stream_dirty = true;
+    return staged_upload(reg->stage, 0, reg->d_frame, frame_xyz, n * 24, reg->stream);
+}
+bool pose_is_finite(const double *p) {
+    for (int i = 0; i < 7; ++i)
+        if (!std::isfinite(p[i])) return false;
+    return true;
+}
+}  // namespace
+
+extern "C" {
+
+int kicp_score_poses_device(kicp_reg *reg, kicp_map *map, const double *d_frame_xyz, size_t n, const double *poses_qt, size_t count,
+                            double max_correspondence_distance, double *out_n_corr, double *out_ssr) {
+    KICP_TRACE_CALL();
+    if (int rc = check_score_args(reg, map, d_frame_xyz, n, poses_qt, count, out_n_corr, out_ssr)) return rc;
+    return score_device(reg, map, d_frame_xyz, n, poses_qt, count, max_correspondence_distance, out_n_corr, out_ssr);
+}
+int kicp_score_poses(kicp_reg *reg, kicp_map *map, const double *frame_xyz, size_t n, const double *poses_qt, size_t count,
+                     double max_correspondence_distance, double *out_n_corr, double *out_ssr) {
+    KICP_TRACE_CALL();
+    if (int rc = check_score_args(reg, map, frame_xyz, n, poses_qt, count, out_n_corr, out_ssr)) return rc;
+    if (int rc = map_finish_pending(map)) return rc;
+    if (count)
+        if (int rc = upload_frame(reg, map, frame_xyz, n)) return rc;
+    return score_device(reg, map, reg->d_frame, n, poses_qt, count, max_correspondence_distance, out_n_corr, out_ssr);
+}
+
+int kicp_relocalize(kicp_reg *reg, kicp_map *map, const double *frame_xyz, size_t n, const double *candidates_qt, size_t count,
+                    double max_correspondence_distance, size_t top_m, double out_pose_qt[7], size_t *out_candidate, double *out_cost_before,
+                    double *out_cost_after) {
+    KICP_TRACE_CALL();
+    if (!out_pose_qt) return fail(KICP_ERR_ARG, "null argument");
+    if (count == 0 || top_m == 0) return fail(KICP_ERR_ARG, "kicp_relocalize needs at least one candidate and top_m >= 1");
+    if (int rc = check_score_args(reg, map, frame_xyz, n, candidates_qt, count, out_pose_qt, out_pose_qt)) return rc;
+    if (int rc = map_finish_pending(map)) return rc;
+    const double tau = max_correspondence_distance;
+    auto result = [&](const double *pose, size_t candidate, double before, double after) {
+        std::memcpy(out_pose_qt, pose, 7 * sizeof(double));
+        if (out_candidate) *out_candidate = candidate;
+        if (out_cost_before) *out_cost_before = before;
+        if (out_cost_after) *out_cost_after = after;
+    };
+    if (n == 0 || kicp_map_empty(map)) {  // nothing can correspond: every candidate costs tau^2, none can be refined
+        result(candidates_qt, 0, tau * tau, tau * tau);
+        return KICP_WARN_NO_CORRESPONDENCES;
+    }
+    if (int rc = upload_frame(reg, map, frame_xyz, n)) return rc;  // once: the scoring and the refinements read this copy
+    const double *d_frame = reg->d_frame;
+    // truncated least squares, lower is better: a point without a correspondence costs tau^2
+    auto cost_of = [&](double n_corr, double ssr) { return (ssr + (static_cast<double>(n) - n_corr) * (tau * tau)) / static_cast<double>(n); };
+    // 1. every candidate
+    std::vector<double> n_corr(count), ssr(count), cost(count);
+    if (int rc = score_device(reg, map, d_frame, n, candidates_qt, count, tau, n_corr.data(), ssr.data())) return rc;
+    int launches = reg->score_launches;
+    for (size_t k = 0; k < count; ++k) cost[k] = cost_of(n_corr[k], ssr[k]);
+    // 2. the top_m cheapest, ties to the lower index
+    const size_t m = std::min(top_m, count);
+    std::vector<size_t> rank(count);
+    for (size_t k = 0; k < count; ++k) rank[k] = k;
+    std::partial_sort(rank.begin(), rank.begin() + m, rank.end(), [&](size_t a, size_t b) { return cost[a] < cost[b] || (cost[a] == cost[b] && a < b); });
+    // 3. refined as independent registrations of the same frame (last pose = candidate, odometry = identity)
+    std::vector<const double *> frames(m, d_frame);
+    std::vector<size_t> sizes(m, n);
+    std::vector<double> start(7 * m), odom(7 * m, 0.0), refined(7 * m);
+    for (size_t j = 0; j < m; ++j) {
+        std::memcpy(&start[7 * j], candidates_qt + 7 * rank[j], 7 * sizeof(double));
+        odom[7 * j + 3] = 1.0;
+    }
+    const int rc_reg = kicp_register_device_batch(reg, map, m, frames.data(), sizes.data(), start.data(), odom.data(), tau, refined.data(), nullptr);
+    if (rc_reg < 0) return rc_reg;
+    // 4. the refined poses, scored by one more call
+    std::vector<double> n_after(m), ssr_after(m);
+    if (int rc = score_device(reg, map, d_frame, n, refined.data(), m, tau, n_after.data(), ssr_after.data())) return rc;
+    reg->score_launches += launches;
+    // 5. the cheapest refined pose, ties to the earlier rank; a refinement that ended without correspondences (NaN pose) is out
+    size_t best = m;
+    double best_cost = 0.0;
+    for (size_t j = 0; j < m; ++j) {
+        if (!pose_is_finite(&refined[7 * j])) continue;
+        const double c = cost_of(n_after[j], ssr_after[j]);
+        if (best == m || c < best_cost) best = j, best_cost = c;
+    }
+    if (best == m) {  // none survived: the best unrefined candidate
+        result(candidates_qt + 7 * rank[0], rank[0], cost[rank[0]], cost[rank[0]]);
+        return KICP_WARN_NO_CORRESPONDENCES;
+    }
+    result(&refined[7 * best], rank[best], cost[rank[best]], best_cost);
+    return KICP_OK;
+}
+
+// Candidate poses for kicp_relocalize: center * planar(dx, dy, dyaw) for every offset i * step with |i * step| <= half extent (per
+// axis; a step <= 0 or a half extent of 0 leaves that axis at the centre) - offsets in the centre's body frame, x slowest, yaw fastest.
+size_t kicp_planar_grid(const double center_qt[7], double half_x, double half_y, double half_yaw, double step_x, double step_y, double step_yaw,
+                        double *out_poses_qt, size_t cap_poses) {
+    if (!center_qt) return 0;
+    auto steps_of = [](double half, double step) { return (step > 0.0 && half > 0.0) ? static_cast<long>(std::floor(half / step + 1e-9)) : 0l; };
+    const long kx = steps_of(half_x, step_x), ky = steps_of(half_y, step_y), kw = steps_of(half_yaw, step_yaw);
+    const size_t total = static_cast<size_t>(2 * kx + 1) * static_cast<size_t>(2 * ky + 1) * static_cast<size_t>(2 * kw + 1);
+    if (!out_poses_qt) return total;
+    const Pose center = pose_from(center_qt);
+    size_t at = 0;
+    for (long ix = -kx; ix <= kx; ++ix)
+        for (long iy = -ky; iy <= ky; ++iy)
+            for (long iw = -kw; iw <= kw && at < cap_poses; ++iw, ++at) {
+                const double yaw = static_cast<double>(iw) * step_yaw;
+                const Pose offset{0.0, 0.0, std::sin(0.5 * yaw), std::cos(0.5 * yaw), static_cast<double>(ix) * step_x, static_cast<double>(iy) * step_y, 0.0};
+                pose_to(pose_mul(center, offset), out_poses_qt + 7 * at);
+            }
+    return total;
+}
+
+}  // extern "C"
