@@ -163,6 +163,22 @@ void bind_thread_near_gpu(int device) {
     (void)sched_setaffinity(0, sizeof want, &want);
 }
 
+int wait_word(const volatile unsigned long long *word, unsigned long long want, unsigned long long mask, hipStream_t stream, double limit_ms, const char *what,
+              unsigned long long *seen) {
+    const auto t0 = std::chrono::steady_clock::now();
+    unsigned long long w = *word;
+    for (unsigned spins = 0; (w & mask) != want; ++spins, w = *word) {
+        if ((spins & 255u) == 255u && std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() > limit_ms) {
+            HIP_TRY(hipStreamSynchronize(stream));
+            if (((w = *word) & mask) != want) return fail(KICP_ERR_HIP, what);
+            break;
+        }
+        __builtin_ia32_pause();
+    }
+    if (seen) *seen = w;
+    return KICP_OK;
+}
+
 const bool g_direct_upload = env_flag("KICP_DIRECT_UPLOAD");
 static int stage_wait(HostStage &hs) {
     if (hs.pending) {
@@ -172,15 +188,10 @@ static int stage_wait(HostStage &hs) {
     return KICP_OK;
 }
 int stage_reserve(HostStage &hs, size_t bytes, hipStream_t stream) {
-    if (bytes <= hs.cap) return KICP_OK;
+    if (bytes <= hs.buf.capacity()) return KICP_OK;
     HIP_TRY(hipStreamSynchronize(stream));
     hs.release();
-    const size_t want = bytes + bytes / 2 + (1u << 20);
-    HIP_TRY(pinned_alloc(reinterpret_cast<void **>(&hs.p), want, hipHostMallocDefault));
-    hs.cap = want;
-    hs.dev = nullptr;
-    if (hipHostGetDevicePointer(reinterpret_cast<void **>(&hs.dev), hs.p, 0) != hipSuccess) hs.dev = nullptr, (void)hipGetLastError();
-    return KICP_OK;
+    return hs.buf.reserve(bytes + bytes / 2 + (1u << 20), hipHostMallocDefault, false);
 }
 // a transfer that fills the staging buffer itself (kicp_register's pipelined frame upload): wait for the previous user, make room;
 // stage_end records the event that guards the buffer against the next one
@@ -225,19 +236,19 @@ int staged_upload(HostStage &hs, size_t offset, void *dst, const void *src, size
         if (int rc = stage_wait(hs)) return rc;  // a copy of the previous call may still be reading the buffer
         if (int rc = stage_reserve(hs, bytes, stream)) return rc;
     }
-    if (offset + bytes > hs.cap) return fail(KICP_ERR_ARG, "staging buffer too small for a follow-up transfer");
+    if (offset + bytes > hs.buf.capacity()) return fail(KICP_ERR_ARG, "staging buffer too small for a follow-up transfer");
     // (16-byte loads and stores: both ends and the place in the staging buffer must be 16-byte aligned - device allocations and
     //  the frame / cloud buffers of this library are)
-    const bool pull = g_pull_upload && hs.dev && bytes >= kPullMinBytes && offset % 16 == 0 && reinterpret_cast<uintptr_t>(dst) % 16 == 0;
+    const bool pull = g_pull_upload && hs.buf.dev() && bytes >= kPullMinBytes && offset % 16 == 0 && reinterpret_cast<uintptr_t>(dst) % 16 == 0;
     const size_t piece = pull ? kPullPiece : kStagePiece;
     for (size_t off = 0; off < bytes; off += piece) {
         const size_t len = std::min(piece, bytes - off);
-        std::memcpy(hs.p + offset + off, static_cast<const unsigned char *>(src) + off, len);
+        std::memcpy(hs.buf.get() + offset + off, static_cast<const unsigned char *>(src) + off, len);
         if (pull)
-            hipLaunchKernelGGL(k_pull_bytes, dim3(static_cast<uint32_t>((len + 4095) / 4096)), dim3(256), 0, stream, hs.dev + offset + off,
+            hipLaunchKernelGGL(k_pull_bytes, dim3(static_cast<uint32_t>((len + 4095) / 4096)), dim3(256), 0, stream, hs.buf.dev() + offset + off,
                                static_cast<unsigned char *>(dst) + off, len);
         else
-            HIP_TRY(hipMemcpyAsync(static_cast<unsigned char *>(dst) + off, hs.p + offset + off, len, hipMemcpyHostToDevice, stream));
+            HIP_TRY(hipMemcpyAsync(static_cast<unsigned char *>(dst) + off, hs.buf.get() + offset + off, len, hipMemcpyHostToDevice, stream));
     }
     if (pull) HIP_TRY(hipGetLastError());
     if (!hs.done) HIP_TRY(hipEventCreateWithFlags(&hs.done, hipEventDisableTiming));
@@ -255,9 +266,9 @@ int staged_download(HostStage &hs, void *dst, const void *src, size_t bytes, hip
     }
     if (int rc = stage_wait(hs)) return rc;
     if (int rc = stage_reserve(hs, bytes, stream)) return rc;
-    HIP_TRY(hipMemcpyAsync(hs.p, src, bytes, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(hs.buf.get(), src, bytes, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
-    std::memcpy(dst, hs.p, bytes);
+    std::memcpy(dst, hs.buf.get(), bytes);
     return KICP_OK;
 }
 
@@ -292,18 +303,17 @@ int kicp_probe_dependent_load(int device, size_t working_set_bytes, int workgrou
         std::swap(perm[k], perm[z % (k + 1)]);
     }
     for (size_t k = 0; k < lines; ++k) next[static_cast<size_t>(perm[k]) * 32] = perm[(k + 1) % lines] * 32u;
-    uint32_t *d_next = nullptr, *d_sink = nullptr;
+    DevBuf<uint32_t> d_next, d_sink;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     const size_t lanes = static_cast<size_t>(workgroups) * block;
-    hipError_t e = hipMalloc(&d_next, next.size() * 4);
-    if (e == hipSuccess) e = hipMalloc(&d_sink, lanes * 4);
-    if (e == hipSuccess) e = hipMemcpy(d_next, next.data(), next.size() * 4, hipMemcpyHostToDevice);
+    if (d_next.reserve(next.size()) || d_sink.reserve(lanes)) return fail(KICP_ERR_HIP, "kicp_probe_dependent_load: " + last_error());
+    hipError_t e = hipMemcpy(d_next.get(), next.data(), next.size() * 4, hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipEventCreate(&e0);
     if (e == hipSuccess) e = hipEventCreate(&e1);
     float best = 0.f;
     for (int rep = 0; rep < 4 && e == hipSuccess; ++rep) {  // (the first launch warms the caches as far as the working set lets it)
         hipEventRecord(e0, nullptr);
-        hipLaunchKernelGGL(k_chase, dim3(workgroups), dim3(block), 0, nullptr, d_next, static_cast<uint32_t>(lines), steps, d_sink);
+        hipLaunchKernelGGL(k_chase, dim3(workgroups), dim3(block), 0, nullptr, d_next.get(), static_cast<uint32_t>(lines), steps, d_sink.get());
         hipEventRecord(e1, nullptr);
         e = hipEventSynchronize(e1);
         float ms = 0.f;
@@ -312,7 +322,6 @@ int kicp_probe_dependent_load(int device, size_t working_set_bytes, int workgrou
     }
     if (e0) hipEventDestroy(e0);
     if (e1) hipEventDestroy(e1);
-    hipFree(d_next), hipFree(d_sink);
     if (e != hipSuccess) return fail(KICP_ERR_HIP, std::string("kicp_probe_dependent_load: ") + hipGetErrorString(e));
     *out_ns_per_step = static_cast<double>(best) * 1.0e6 / steps;
     return KICP_OK;

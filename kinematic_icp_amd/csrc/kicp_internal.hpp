@@ -145,17 +145,109 @@ inline int set_device(int device) {
     return KICP_OK;
 }
 
+// Poll a tagged word in host-coherent memory until (*word & mask) == want - a kernel's way of saying "done" without a copy and a
+// stream synchronisation behind it (~15 us of API time per frame).  Bounded: after `limit_ms` the stream is synchronised and the
+// word read once more; still wrong then: KICP_ERR_HIP with `what`.  `seen` (optional): the word as last read.  (kicp_core.hip)
+int wait_word(const volatile unsigned long long *word, unsigned long long want, unsigned long long mask, hipStream_t stream, double limit_ms, const char *what,
+              unsigned long long *seen = nullptr);
+
+// Owners of the library's GPU allocations.  Move-only; get() == nullptr <=> capacity() == 0 after every operation, failed ones
+// included.  reserve(count) keeps what is there when it is large enough and otherwise RELEASES FIRST, then allocates exactly
+// `count` elements - the contents are lost, the growth policy and whatever synchronisation keeps a running kernel off the old
+// memory are the caller's.  No conversion to T *: a kernel launch deduces its argument types, pass get().
+struct BufTestAccess;  // tests/cpp/buffers_test.cpp
+template <class T>
+class DevBuf {  // hipMalloc / hipFree
+public:
+    DevBuf() = default;
+    DevBuf(DevBuf &&o) noexcept : p_(o.p_), cap_(o.cap_) { o.p_ = nullptr, o.cap_ = 0; }
+    DevBuf &operator=(DevBuf &&o) noexcept {
+        if (this != &o) release(), p_ = o.p_, cap_ = o.cap_, o.p_ = nullptr, o.cap_ = 0;
+        return *this;
+    }
+    ~DevBuf() { release(); }
+    T *get() const { return p_; }
+    size_t capacity() const { return cap_; }  // elements
+    int reserve(size_t count) {
+        if (count <= cap_) return KICP_OK;
+        release();
+        const hipError_t e = hipMalloc(reinterpret_cast<void **>(&p_), count * sizeof(T));
+        if (e != hipSuccess) {
+            p_ = nullptr;
+            return fail(KICP_ERR_HIP, "hipMalloc of " + std::to_string(count * sizeof(T)) + " bytes: " + hipGetErrorString(e));
+        }
+        cap_ = count;
+        return KICP_OK;
+    }
+    void release() {
+        if (p_) (void)free_fn(p_);
+        p_ = nullptr, cap_ = 0;
+    }
+    static inline hipError_t (*free_fn)(void *) = hipFree;  // (replaced only by the buffer test, whose pointers are not allocations)
+
+private:
+    friend struct ::kicp::host::BufTestAccess;
+    T *p_ = nullptr;
+    size_t cap_ = 0;
+};
+template <class T>
+class PinnedBuf {  // pinned_alloc / hipHostFree, with the device's view of the same memory
+public:
+    PinnedBuf() = default;
+    PinnedBuf(PinnedBuf &&o) noexcept : p_(o.p_), dev_(o.dev_), cap_(o.cap_) { o.p_ = o.dev_ = nullptr, o.cap_ = 0; }
+    PinnedBuf &operator=(PinnedBuf &&o) noexcept {
+        if (this != &o) release(), p_ = o.p_, dev_ = o.dev_, cap_ = o.cap_, o.p_ = o.dev_ = nullptr, o.cap_ = 0;
+        return *this;
+    }
+    ~PinnedBuf() { release(); }
+    T *get() const { return p_; }
+    T *dev() const { return dev_; }  // nullptr: not mapped (only where reserve was told that this is acceptable)
+    size_t capacity() const { return cap_; }
+    // `flags`: hipHostMalloc's; `need_dev` = false: a platform that cannot map the memory leaves dev() == nullptr instead of failing
+    int reserve(size_t count, unsigned int flags, bool need_dev = true) {
+        if (count <= cap_) return KICP_OK;
+        release();
+        hipError_t e = pinned_alloc(reinterpret_cast<void **>(&p_), count * sizeof(T), flags);
+        if (e != hipSuccess) {
+            p_ = nullptr;
+            return fail(KICP_ERR_HIP, "hipHostMalloc of " + std::to_string(count * sizeof(T)) + " bytes: " + hipGetErrorString(e));
+        }
+        cap_ = count;
+        e = hipHostGetDevicePointer(reinterpret_cast<void **>(&dev_), p_, 0);
+        if (e == hipSuccess) return KICP_OK;
+        dev_ = nullptr, (void)hipGetLastError();
+        if (!need_dev) return KICP_OK;
+        release();
+        return fail(KICP_ERR_HIP, std::string("hipHostGetDevicePointer: ") + hipGetErrorString(e));
+    }
+    void release() {
+        if (p_) (void)free_fn(p_);
+        p_ = dev_ = nullptr, cap_ = 0;
+    }
+    static inline hipError_t (*free_fn)(void *) = hipHostFree;  // (as DevBuf's)
+
+private:
+    friend struct ::kicp::host::BufTestAccess;
+    T *p_ = nullptr, *dev_ = nullptr;
+    size_t cap_ = 0;
+};
+
 // pinned staging buffer for uploads of pageable caller memory (see staged_upload)
 struct HostStage {
-    unsigned char *p = nullptr;
-    unsigned char *dev = nullptr;  // the same memory as a kernel sees it (nullptr: not mapped on this platform)
-    size_t cap = 0;
-    hipEvent_t done = nullptr;  // recorded behind the last asynchronous copy that reads the buffer
-    bool pending = false;       // such a copy may still be in flight: wait on `done` before writing the buffer again
+    PinnedBuf<unsigned char> buf;  // dev() == nullptr: not mapped on this platform
+    hipEvent_t done = nullptr;     // recorded behind the last asynchronous copy that reads the buffer
+    bool pending = false;          // such a copy may still be in flight: wait on `done` before writing the buffer again
+    HostStage() = default;
+    HostStage(HostStage &&o) noexcept : buf(std::move(o.buf)), done(o.done), pending(o.pending) { o.done = nullptr, o.pending = false; }
+    HostStage &operator=(HostStage &&o) noexcept {
+        if (this != &o) release(), buf = std::move(o.buf), done = o.done, pending = o.pending, o.done = nullptr, o.pending = false;
+        return *this;
+    }
+    ~HostStage() { release(); }
     void release() {
         if (done) hipEventSynchronize(done), hipEventDestroy(done);
-        if (p) hipHostFree(p);
-        p = nullptr, dev = nullptr, cap = 0, done = nullptr, pending = false;
+        buf.release();
+        done = nullptr, pending = false;
     }
 };
 // (policy and implementation: kicp_core.hip)
@@ -167,41 +259,36 @@ int staged_download(HostStage &hs, void *dst, const void *src, size_t bytes, hip
 
 struct DeviceMirror {
     int device = -1;
-    Slot *d_table = nullptr;
-    double *d_pool = nullptr;
-    MirrorPoint *d_pool16 = nullptr;
-    size_t table_slots = 0, pool_doubles = 0;  // allocated sizes
-    size_t live_slots = 0;                     // table size the mirror currently represents
+    DevBuf<Slot> d_table;  // capacity(): allocated slots
+    DevBuf<double> d_pool;  // capacity(): allocated doubles; d_pool16 holds mirror_points() of them
+    DevBuf<MirrorPoint> d_pool16;
+    size_t live_slots = 0;  // table size the mirror currently represents
     uint64_t synced_epoch = ~0ull, synced_generation = ~0ull;
     // staging for delta uploads (device)
-    uint2 *d_stage = nullptr;
-    uint32_t *d_index = nullptr;
-    size_t stage_words = 0, index_cap = 0;
+    DevBuf<uint2> d_stage;
+    DevBuf<uint32_t> d_index;
     size_t last_upload_bytes = 0;
     int last_upload_full = 1;
     MapView view{};
     // device-side maintenance (kicp_mapdev.hpp): per-slot and per-update scratch
-    unsigned long long *d_keys64 = nullptr;
-    uint32_t *d_cnt = nullptr, *d_seg_start = nullptr, *d_free_list = nullptr;
-    DevMapCounters *d_ctr = nullptr;
-    size_t aux_slots = 0, free_cap = 0;
-    unsigned long long *h_ctr = nullptr;  // pinned, host-coherent: [0..4] the counters of an update whose end the caller collects later, [7] its sequence number (k_up_publish)
-    unsigned long long *h_ctr_dev = nullptr, ctr_seq = 0;
+    DevBuf<unsigned long long> d_keys64;  // d_keys64, d_cnt, d_seg_start: one element per slot, allocated together
+    DevBuf<uint32_t> d_cnt, d_seg_start;
+    DevBuf<uint32_t> d_free_list;  // capacity(): buckets + 1
+    DevBuf<DevMapCounters> d_ctr;
+    PinnedBuf<unsigned long long> h_ctr;  // host-coherent: [0..4] the counters of an update whose end the caller collects later, [7] its sequence number (k_up_publish)
+    unsigned long long ctr_seq = 0;
     bool ctr_clean = false;  // the per-update counters in d_ctr are zero (left so by k_up_publish): the next frame-sized update skips its memset
-    double *d_world = nullptr;
-    uint32_t *d_slot_of = nullptr, *d_order = nullptr, *d_touched = nullptr;
-    size_t upd_cap = 0;
+    DevBuf<double> d_world;  // d_world (3 doubles per point), d_slot_of, d_order, d_touched: allocated together
+    DevBuf<uint32_t> d_slot_of, d_order, d_touched;
     HostStage stage;  // pinned staging for transfers from / to caller memory (queries, Pointcloud)
     // Pointcloud() from the device copy
-    double *d_pc = nullptr;
-    uint32_t *d_pc_blocks = nullptr;  // per-256-slot-block counts / offsets, then the total
-    size_t pc_points = 0, pc_blocks = 0;
+    DevBuf<double> d_pc;
+    DevBuf<uint32_t> d_pc_blocks;  // per-256-slot-block counts / offsets, then the total
     // kicp_map_pointcloud_f32: kRecSlots landing slots for the records' pieces (pinned, host-mapped), a flag and a ticket per slot
     static constexpr int kRecSlots = 4;
-    unsigned char *h_records = nullptr, *h_records_dev = nullptr;
-    size_t records_cap = 0;  // bytes
-    unsigned long long *h_rec_flags = nullptr, *h_rec_flags_dev = nullptr;
-    unsigned long long *d_rec_tickets = nullptr;  // never reset
+    PinnedBuf<unsigned char> h_records;
+    PinnedBuf<unsigned long long> h_rec_flags;
+    DevBuf<unsigned long long> d_rec_tickets;  // never reset
     unsigned long long rec_drawn[kRecSlots] = {};
     uint32_t rec_seq = 0;
 };
@@ -222,16 +309,17 @@ struct kicp_map {
     bool host_updates_only = false;
     // kicp_map_update_pose_device_begin: the update's kernels and the copy of its counters are queued, nothing has been waited for;
     // kicp_map_update_finish (or any other call on the map) collects it.  The points stay borrowed until then (host fallback).
-    bool pending_update = false;
-    const double *pending_points = nullptr;
-    size_t pending_n = 0;
-    kicp::Pose pending_pose{};
-    double pending_origin[3] = {0.0, 0.0, 0.0};
-    bool pending_has_origin = false;
+    struct PendingUpdate {
+        bool active = false;
+        const double *points = nullptr;
+        size_t n = 0;
+        kicp::Pose pose{};
+        double origin[3] = {0.0, 0.0, 0.0};
+        bool has_origin = false;
+    } pending;
     // preferred device for bulk host-side insertions (kicp_map_set_device; -1 = none: host insertion) and their staging
     int bulk_device = -1;
-    double *d_bulk = nullptr;
-    size_t bulk_cap = 0;
+    kicp::host::DevBuf<double> d_bulk;
     kicp_map(double vs, double md, uint32_t cap) : host(vs, md, cap) {}
 };
 

@@ -12,20 +12,11 @@ using namespace kicp::host;
 namespace {
 // points of the 16-bit mirror that go with `pool_doubles` doubles of the fp64 pool (bucket strides cap / cap16)
 size_t mirror_points(size_t pool_doubles, uint32_t cap) { return pool_doubles / (static_cast<size_t>(cap) * 3) * mirror_stride(cap); }
+// room of the free-list stack in buckets (the allocation holds one more element)
+size_t free_cap(const DeviceMirror &mr) { return mr.d_free_list.capacity() ? mr.d_free_list.capacity() - 1 : 0; }
 // release every device buffer of a mirror (on its own device) and reset it
 void free_mirror(DeviceMirror &mr) {
-    if (mr.device >= 0) {
-        hipSetDevice(mr.device);
-        hipFree(mr.d_table), hipFree(mr.d_pool), hipFree(mr.d_pool16), hipFree(mr.d_stage), hipFree(mr.d_index);
-        hipFree(mr.d_keys64), hipFree(mr.d_cnt), hipFree(mr.d_seg_start), hipFree(mr.d_free_list), hipFree(mr.d_ctr);
-        hipFree(mr.d_world), hipFree(mr.d_slot_of), hipFree(mr.d_order), hipFree(mr.d_touched);
-        hipFree(mr.d_pc), hipFree(mr.d_pc_blocks);
-        if (mr.h_ctr) hipHostFree(mr.h_ctr);
-        if (mr.h_records) hipHostFree(mr.h_records);
-        if (mr.h_rec_flags) hipHostFree(mr.h_rec_flags);
-        hipFree(mr.d_rec_tickets);
-        mr.stage.release();
-    }
+    if (mr.device >= 0) hipSetDevice(mr.device);
     mr = DeviceMirror{};
 }
 
@@ -34,30 +25,24 @@ int sync_aux(kicp_map *map, hipStream_t stream) {
     DeviceMirror &mr = map->mirror;
     const HostMap &h = map->host;
     const size_t slots = h.table().size();
-    if (slots != mr.aux_slots) {
-        hipFree(mr.d_keys64), hipFree(mr.d_cnt), hipFree(mr.d_seg_start);
-        mr.d_keys64 = nullptr, mr.d_cnt = nullptr, mr.d_seg_start = nullptr;
-        HIP_TRY(hipMalloc(&mr.d_keys64, slots * 8));
-        HIP_TRY(hipMalloc(&mr.d_cnt, slots * 4));
-        HIP_TRY(hipMalloc(&mr.d_seg_start, slots * 4));
-        HIP_TRY(hipMemsetAsync(mr.d_cnt, 0, slots * 4, stream));
-        mr.aux_slots = slots;
+    if (slots != mr.d_seg_start.capacity()) {  // (d_seg_start: the last of the three, so that a failed growth is made up for here)
+        mr.d_keys64.release(), mr.d_cnt.release(), mr.d_seg_start.release();
+        if (int rc = mr.d_keys64.reserve(slots)) return rc;
+        if (int rc = mr.d_cnt.reserve(slots)) return rc;
+        if (int rc = mr.d_seg_start.reserve(slots)) return rc;
+        HIP_TRY(hipMemsetAsync(mr.d_cnt.get(), 0, slots * 4, stream));
     }
-    const size_t bucket_cap = mr.pool_doubles / (static_cast<size_t>(h.cap()) * 3);
-    if (bucket_cap > mr.free_cap) {
-        hipFree(mr.d_free_list);
-        mr.d_free_list = nullptr;
-        HIP_TRY(hipMalloc(&mr.d_free_list, (bucket_cap + 1) * 4));
-        mr.free_cap = bucket_cap;
-    }
-    if (!mr.d_ctr) HIP_TRY(hipMalloc(&mr.d_ctr, sizeof(DevMapCounters)));
-    hipLaunchKernelGGL(k_build_keys64, dim3(static_cast<uint32_t>(std::min<size_t>((slots + 255) / 256, 4096))), dim3(256), 0, stream, mr.d_table,
-                       static_cast<uint32_t>(slots), mr.d_keys64);
+    const size_t bucket_cap = mr.d_pool.capacity() / (static_cast<size_t>(h.cap()) * 3);
+    if (bucket_cap > free_cap(mr))
+        if (int rc = mr.d_free_list.reserve(bucket_cap + 1)) return rc;
+    if (int rc = mr.d_ctr.reserve(1)) return rc;
+    hipLaunchKernelGGL(k_build_keys64, dim3(static_cast<uint32_t>(std::min<size_t>((slots + 255) / 256, 4096))), dim3(256), 0, stream, mr.d_table.get(),
+                       static_cast<uint32_t>(slots), mr.d_keys64.get());
     DevMapCounters c{};
     c.n_points = h.num_points(), c.n_voxels = static_cast<uint32_t>(h.num_voxels()), c.n_entries = static_cast<uint32_t>(h.num_entries());
     c.n_buckets_hi = static_cast<uint32_t>(h.buckets_in_use_hi()), c.free_count = static_cast<uint32_t>(h.free_list().size());
-    if (c.free_count) HIP_TRY(hipMemcpyAsync(mr.d_free_list, h.free_list().data(), c.free_count * 4, hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(mr.d_ctr, &c, sizeof c, hipMemcpyHostToDevice, stream));
+    if (c.free_count) HIP_TRY(hipMemcpyAsync(mr.d_free_list.get(), h.free_list().data(), c.free_count * 4, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(mr.d_ctr.get(), &c, sizeof c, hipMemcpyHostToDevice, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     map->dev = c;
     return KICP_OK;
@@ -67,23 +52,15 @@ int sync_aux(kicp_map *map, hipStream_t stream) {
 int upload_rows(DeviceMirror &mr, const std::vector<uint2> &staged, const std::vector<uint32_t> &index, uint32_t row_words, void *dst,
                 hipStream_t stream) {
     if (index.empty()) return KICP_OK;
-    if (staged.size() > mr.stage_words) {
-        if (mr.d_stage) HIP_TRY(hipFree(mr.d_stage));
-        mr.d_stage = nullptr;
-        mr.stage_words = staged.size() + staged.size() / 2;
-        HIP_TRY(hipMalloc(&mr.d_stage, mr.stage_words * sizeof(uint2)));
-    }
-    if (index.size() > mr.index_cap) {
-        if (mr.d_index) HIP_TRY(hipFree(mr.d_index));
-        mr.d_index = nullptr;
-        mr.index_cap = index.size() + index.size() / 2;
-        HIP_TRY(hipMalloc(&mr.d_index, mr.index_cap * sizeof(uint32_t)));
-    }
-    HIP_TRY(hipMemcpyAsync(mr.d_stage, staged.data(), staged.size() * sizeof(uint2), hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(mr.d_index, index.data(), index.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    if (staged.size() > mr.d_stage.capacity())
+        if (int rc = mr.d_stage.reserve(staged.size() + staged.size() / 2)) return rc;
+    if (index.size() > mr.d_index.capacity())
+        if (int rc = mr.d_index.reserve(index.size() + index.size() / 2)) return rc;
+    HIP_TRY(hipMemcpyAsync(mr.d_stage.get(), staged.data(), staged.size() * sizeof(uint2), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(mr.d_index.get(), index.data(), index.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
     const size_t total = staged.size();
     const uint32_t grid = static_cast<uint32_t>(std::min<size_t>((total + 255) / 256, 4096));
-    hipLaunchKernelGGL(k_scatter_rows, dim3(grid), dim3(256), 0, stream, mr.d_stage, mr.d_index, static_cast<uint32_t>(index.size()), row_words,
+    hipLaunchKernelGGL(k_scatter_rows, dim3(grid), dim3(256), 0, stream, mr.d_stage.get(), mr.d_index.get(), static_cast<uint32_t>(index.size()), row_words,
                        static_cast<uint2 *>(dst));
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(stream));  // the staging vectors are reused by the caller
@@ -115,35 +92,30 @@ int map_sync(kicp_map *map, int device, hipStream_t stream) {
     const uint32_t cap = h.cap();
     const size_t pool_doubles = h.buckets_in_use_hi() * static_cast<size_t>(cap) * 3;
     bool full = mr.synced_generation != h.generation() || mr.live_slots != slots;
-    if (slots > mr.table_slots) {
-        if (mr.d_table) HIP_TRY(hipFree(mr.d_table));
-        mr.d_table = nullptr;
-        HIP_TRY(hipMalloc(&mr.d_table, slots * sizeof(Slot)));
-        mr.table_slots = slots;
+    if (slots > mr.d_table.capacity()) {
+        if (int rc = mr.d_table.reserve(slots)) return rc;
         full = true;
     }
-    if (pool_doubles > mr.pool_doubles) {  // grow the pools, keeping what is already there (device-side copy)
+    if (pool_doubles > mr.d_pool.capacity()) {  // grow the pools, keeping what is already there (device-side copy)
         const size_t want = pool_doubles + pool_doubles / 2 + 3 * 1024;
-        double *np = nullptr;
-        MirrorPoint *np32 = nullptr;
-        HIP_TRY(hipMalloc(&np, want * sizeof(double)));
-        HIP_TRY(hipMalloc(&np32, mirror_points(want, cap) * sizeof(MirrorPoint)));
-        if (mr.d_pool && !full) {
-            HIP_TRY(hipMemcpyAsync(np, mr.d_pool, mr.pool_doubles * sizeof(double), hipMemcpyDeviceToDevice, stream));
-            HIP_TRY(hipMemcpyAsync(np32, mr.d_pool16, mirror_points(mr.pool_doubles, cap) * sizeof(MirrorPoint), hipMemcpyDeviceToDevice, stream));
+        DevBuf<double> np;
+        DevBuf<MirrorPoint> np32;
+        if (int rc = np.reserve(want)) return rc;
+        if (int rc = np32.reserve(mirror_points(want, cap))) return rc;
+        if (mr.d_pool.get() && !full) {
+            HIP_TRY(hipMemcpyAsync(np.get(), mr.d_pool.get(), mr.d_pool.capacity() * sizeof(double), hipMemcpyDeviceToDevice, stream));
+            HIP_TRY(hipMemcpyAsync(np32.get(), mr.d_pool16.get(), mirror_points(mr.d_pool.capacity(), cap) * sizeof(MirrorPoint), hipMemcpyDeviceToDevice, stream));
             HIP_TRY(hipStreamSynchronize(stream));
         }
-        if (mr.d_pool) HIP_TRY(hipFree(mr.d_pool));
-        if (mr.d_pool16) HIP_TRY(hipFree(mr.d_pool16));
-        mr.d_pool = np, mr.d_pool16 = np32, mr.pool_doubles = want;
+        std::swap(mr.d_pool, np), std::swap(mr.d_pool16, np32);  // (the old pools go with the locals)
     }
     mr.last_upload_bytes = 0;
     // delta only pays off while the changed part is small
     if (!full && (h.dirty_slots().size() * 4 > slots || h.dirty_buckets().size() * 2 > h.buckets_in_use_hi())) full = true;
     if (full) {
-        HIP_TRY(hipMemcpyAsync(mr.d_table, h.table().data(), slots * sizeof(Slot), hipMemcpyHostToDevice, stream));
-        if (pool_doubles) HIP_TRY(hipMemcpyAsync(mr.d_pool, h.pool().data(), pool_doubles * sizeof(double), hipMemcpyHostToDevice, stream));
-        if (pool_doubles) HIP_TRY(hipMemcpyAsync(mr.d_pool16, h.pool16().data(), mirror_points(pool_doubles, cap) * sizeof(MirrorPoint), hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(mr.d_table.get(), h.table().data(), slots * sizeof(Slot), hipMemcpyHostToDevice, stream));
+        if (pool_doubles) HIP_TRY(hipMemcpyAsync(mr.d_pool.get(), h.pool().data(), pool_doubles * sizeof(double), hipMemcpyHostToDevice, stream));
+        if (pool_doubles) HIP_TRY(hipMemcpyAsync(mr.d_pool16.get(), h.pool16().data(), mirror_points(pool_doubles, cap) * sizeof(MirrorPoint), hipMemcpyHostToDevice, stream));
         HIP_TRY(hipStreamSynchronize(stream));
         mr.last_upload_bytes = slots * sizeof(Slot) + pool_doubles * sizeof(double) + mirror_points(pool_doubles, cap) * sizeof(MirrorPoint);
     } else {
@@ -152,21 +124,21 @@ int map_sync(kicp_map *map, int device, hipStream_t stream) {
         const std::vector<uint32_t> &ds = h.dirty_slots(), &db = h.dirty_buckets();
         staged.resize(ds.size() * (sizeof(Slot) / 8));
         for (size_t i = 0; i < ds.size(); ++i) std::memcpy(&staged[i * (sizeof(Slot) / 8)], &h.table()[ds[i]], sizeof(Slot));
-        if (int rc = upload_rows(mr, staged, ds, sizeof(Slot) / 8, mr.d_table, stream)) return rc;
+        if (int rc = upload_rows(mr, staged, ds, sizeof(Slot) / 8, mr.d_table.get(), stream)) return rc;
         staged.resize(db.size() * static_cast<size_t>(cap) * 3);
         for (size_t i = 0; i < db.size(); ++i)
             std::memcpy(&staged[i * static_cast<size_t>(cap) * 3], &h.pool()[static_cast<size_t>(db[i]) * cap * 3], static_cast<size_t>(cap) * 24);
-        if (int rc = upload_rows(mr, staged, db, cap * 3, mr.d_pool, stream)) return rc;
+        if (int rc = upload_rows(mr, staged, db, cap * 3, mr.d_pool.get(), stream)) return rc;
         const size_t cap16 = h.cap16();
         staged.resize(db.size() * cap16);  // one 8-byte word per mirror point
         for (size_t i = 0; i < db.size(); ++i)
             std::memcpy(&staged[i * cap16], &h.pool16()[static_cast<size_t>(db[i]) * cap16], cap16 * sizeof(MirrorPoint));
-        if (int rc = upload_rows(mr, staged, db, static_cast<uint32_t>(cap16), mr.d_pool16, stream)) return rc;
+        if (int rc = upload_rows(mr, staged, db, static_cast<uint32_t>(cap16), mr.d_pool16.get(), stream)) return rc;
     }
     mr.last_upload_full = full ? 1 : 0;
     if (int rc = sync_aux(map, stream)) return rc;
     h.mark_synced(full);
-    mr.view = MapView{mr.d_table, static_cast<uint32_t>(slots - 1), mr.d_pool, mr.d_pool16, cap, h.cap16(), h.voxel_size(), h.count_bits()};
+    mr.view = MapView{mr.d_table.get(), static_cast<uint32_t>(slots - 1), mr.d_pool.get(), mr.d_pool16.get(), cap, h.cap16(), h.voxel_size(), h.count_bits()};
     mr.synced_epoch = h.epoch(), mr.synced_generation = h.generation(), mr.live_slots = slots;
     return KICP_OK;
 }
@@ -180,16 +152,16 @@ int ensure_host_current(kicp_map *map) {
     if (int rc = set_device(mr.device)) return rc;
     HIP_TRY(hipDeviceSynchronize());
     DevMapCounters c{};
-    HIP_TRY(hipMemcpy(&c, mr.d_ctr, sizeof c, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&c, mr.d_ctr.get(), sizeof c, hipMemcpyDeviceToHost));
     const uint32_t cap = map->host.cap();
     std::vector<Slot> table(mr.live_slots);
     std::vector<double> pool(static_cast<size_t>(c.n_buckets_hi) * cap * 3);
     std::vector<MirrorPoint> pool16(static_cast<size_t>(c.n_buckets_hi) * map->host.cap16());
     std::vector<uint32_t> free_list(c.free_count);
-    HIP_TRY(hipMemcpy(table.data(), mr.d_table, table.size() * sizeof(Slot), hipMemcpyDeviceToHost));
-    if (!pool.empty()) HIP_TRY(hipMemcpy(pool.data(), mr.d_pool, pool.size() * 8, hipMemcpyDeviceToHost));
-    if (!pool16.empty()) HIP_TRY(hipMemcpy(pool16.data(), mr.d_pool16, pool16.size() * sizeof(MirrorPoint), hipMemcpyDeviceToHost));
-    if (!free_list.empty()) HIP_TRY(hipMemcpy(free_list.data(), mr.d_free_list, free_list.size() * 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(table.data(), mr.d_table.get(), table.size() * sizeof(Slot), hipMemcpyDeviceToHost));
+    if (!pool.empty()) HIP_TRY(hipMemcpy(pool.data(), mr.d_pool.get(), pool.size() * 8, hipMemcpyDeviceToHost));
+    if (!pool16.empty()) HIP_TRY(hipMemcpy(pool16.data(), mr.d_pool16.get(), pool16.size() * sizeof(MirrorPoint), hipMemcpyDeviceToHost));
+    if (!free_list.empty()) HIP_TRY(hipMemcpy(free_list.data(), mr.d_free_list.get(), free_list.size() * 4, hipMemcpyDeviceToHost));
     map->host.Adopt(std::move(table), std::move(pool), std::move(pool16), c.n_buckets_hi, std::move(free_list));
     map->host.mark_synced(true);
     mr.synced_epoch = map->host.epoch(), mr.synced_generation = map->host.generation();  // the mirror already holds this state
@@ -202,40 +174,46 @@ int ensure_host_current(kicp_map *map) {
 
 namespace {
 
+// What DevMapCounters::error says at the end of an update: 0 = done (KICP_OK), 1 = a voxel the packed keys cannot express, the host
+// map redoes the update (kRerunOnHost, a positive value no C-ABI call returns), 3 = table full, anything else = out of room.
+constexpr int kRerunOnHost = 1;
+int decode_update_error(uint32_t error) {
+    if (error == 3) return fail(KICP_ERR_CAPACITY, "device-side map update: voxel table full");
+    if (error == 1) return kRerunOnHost;
+    if (error) return fail(KICP_ERR_CAPACITY, "device-side map update ran out of room");
+    return KICP_OK;
+}
+
 // make the device pools (and the free-list stack) hold at least `want_buckets` buckets, keeping their contents
 int grow_pools(kicp_map *map, size_t want_buckets) {
     DeviceMirror &mr = map->mirror;
     const uint32_t cap = map->host.cap();
-    const size_t have = mr.pool_doubles / (static_cast<size_t>(cap) * 3);
-    if (want_buckets <= have && have <= mr.free_cap) return KICP_OK;
+    const size_t have = mr.d_pool.capacity() / (static_cast<size_t>(cap) * 3);
+    if (want_buckets <= have && have <= free_cap(mr)) return KICP_OK;
     const size_t buckets = std::max(want_buckets + want_buckets / 2 + 1024, have);
     const size_t doubles = buckets * cap * 3;
-    double *np = nullptr;
-    MirrorPoint *np32 = nullptr;
-    uint32_t *nf = nullptr;
-    HIP_TRY(hipMalloc(&np, doubles * sizeof(double)));
-    HIP_TRY(hipMalloc(&np32, mirror_points(doubles, cap) * sizeof(MirrorPoint)));
-    HIP_TRY(hipMalloc(&nf, (buckets + 1) * 4));
-    if (mr.d_pool) HIP_TRY(hipMemcpy(np, mr.d_pool, mr.pool_doubles * sizeof(double), hipMemcpyDeviceToDevice));
-    if (mr.d_pool16) HIP_TRY(hipMemcpy(np32, mr.d_pool16, mirror_points(mr.pool_doubles, cap) * sizeof(MirrorPoint), hipMemcpyDeviceToDevice));
-    if (mr.d_free_list && mr.free_cap) HIP_TRY(hipMemcpy(nf, mr.d_free_list, std::min(mr.free_cap, buckets) * 4, hipMemcpyDeviceToDevice));
-    hipFree(mr.d_pool), hipFree(mr.d_pool16), hipFree(mr.d_free_list);
-    mr.d_pool = np, mr.d_pool16 = np32, mr.d_free_list = nf, mr.pool_doubles = doubles, mr.free_cap = buckets;
-    mr.view.pool = mr.d_pool, mr.view.pool16 = mr.d_pool16;
+    DevBuf<double> np;
+    DevBuf<MirrorPoint> np32;
+    DevBuf<uint32_t> nf;
+    if (int rc = np.reserve(doubles)) return rc;
+    if (int rc = np32.reserve(mirror_points(doubles, cap))) return rc;
+    if (int rc = nf.reserve(buckets + 1)) return rc;
+    if (mr.d_pool.get()) HIP_TRY(hipMemcpy(np.get(), mr.d_pool.get(), mr.d_pool.capacity() * sizeof(double), hipMemcpyDeviceToDevice));
+    if (mr.d_pool16.get()) HIP_TRY(hipMemcpy(np32.get(), mr.d_pool16.get(), mirror_points(mr.d_pool.capacity(), cap) * sizeof(MirrorPoint), hipMemcpyDeviceToDevice));
+    if (free_cap(mr)) HIP_TRY(hipMemcpy(nf.get(), mr.d_free_list.get(), std::min(free_cap(mr), buckets) * 4, hipMemcpyDeviceToDevice));
+    std::swap(mr.d_pool, np), std::swap(mr.d_pool16, np32), std::swap(mr.d_free_list, nf);  // (the old ones go with the locals)
+    mr.view.pool = mr.d_pool.get(), mr.view.pool16 = mr.d_pool16.get();
     return KICP_OK;
 }
 
 int ensure_update_scratch(DeviceMirror &mr, size_t n) {
-    if (n <= mr.upd_cap) return KICP_OK;
-    hipFree(mr.d_world), hipFree(mr.d_slot_of), hipFree(mr.d_order), hipFree(mr.d_touched);
-    mr.d_world = nullptr, mr.d_slot_of = nullptr, mr.d_order = nullptr, mr.d_touched = nullptr;
+    if (n <= mr.d_touched.capacity()) return KICP_OK;
+    mr.d_world.release(), mr.d_slot_of.release(), mr.d_order.release(), mr.d_touched.release();  // (d_touched's capacity speaks for all four)
     const size_t cap = n + n / 4 + 1024;
-    HIP_TRY(hipMalloc(&mr.d_world, cap * 24));
-    HIP_TRY(hipMalloc(&mr.d_slot_of, cap * 4));
-    HIP_TRY(hipMalloc(&mr.d_order, cap * 4));
-    HIP_TRY(hipMalloc(&mr.d_touched, cap * 4));
-    mr.upd_cap = cap;
-    return KICP_OK;
+    if (int rc = mr.d_world.reserve(cap * 3)) return rc;
+    if (int rc = mr.d_slot_of.reserve(cap)) return rc;
+    if (int rc = mr.d_order.reserve(cap)) return rc;
+    return mr.d_touched.reserve(cap);
 }
 
 // Move the live entries of the device table into a fresh table with room for `extra_entries` more at a load factor of
@@ -244,38 +222,37 @@ int device_rehash(kicp_map *map, size_t extra_entries) {
     DeviceMirror &mr = map->mirror;
     hipStream_t st = nullptr;
     const size_t old_slots = mr.live_slots;
-    HIP_TRY(hipMemsetAsync(&mr.d_ctr->touched, 0, 8, st));  // touched (borrowed as the live counter) + error
+    HIP_TRY(hipMemsetAsync(&mr.d_ctr.get()->touched, 0, 8, st));  // touched (borrowed as the live counter) + error
     mr.ctr_clean = false;
     const uint32_t grid_old = static_cast<uint32_t>(std::min<size_t>((old_slots + 255) / 256, 8192));
-    hipLaunchKernelGGL(k_rehash_count, dim3(grid_old), dim3(256), 0, st, mr.d_table, static_cast<uint32_t>(old_slots), map->host.count_bits(), &mr.d_ctr->touched);
+    hipLaunchKernelGGL(k_rehash_count, dim3(grid_old), dim3(256), 0, st, mr.d_table.get(), static_cast<uint32_t>(old_slots), map->host.count_bits(), &mr.d_ctr.get()->touched);
     uint32_t live = 0;
-    HIP_TRY(hipMemcpy(&live, &mr.d_ctr->touched, 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&live, &mr.d_ctr.get()->touched, 4, hipMemcpyDeviceToHost));
     size_t want = 1024;
     while ((live + extra_entries) * 4 > want) want *= 2;
     if (want > (1ull << 31)) return fail(KICP_ERR_CAPACITY, "voxel table would exceed 2^31 slots");
-    Slot *nt = nullptr;
-    unsigned long long *nk = nullptr;
-    uint32_t *nc = nullptr, *ns = nullptr;
-    HIP_TRY(hipMalloc(&nt, want * sizeof(Slot)));
-    HIP_TRY(hipMalloc(&nk, want * 8));
-    HIP_TRY(hipMalloc(&nc, want * 4));
-    HIP_TRY(hipMalloc(&ns, want * 4));
+    DevBuf<Slot> nt;
+    DevBuf<unsigned long long> nk;
+    DevBuf<uint32_t> nc, ns;
+    if (int rc = nt.reserve(want)) return rc;
+    if (int rc = nk.reserve(want)) return rc;
+    if (int rc = nc.reserve(want)) return rc;
+    if (int rc = ns.reserve(want)) return rc;
     const uint32_t grid_new = static_cast<uint32_t>(std::min<size_t>((want + 255) / 256, 8192));
-    hipLaunchKernelGGL(k_table_clear, dim3(grid_new), dim3(256), 0, st, nt, static_cast<uint32_t>(want));
-    HIP_TRY(hipMemsetAsync(nk, 0xFF, want * 8, st));
-    HIP_TRY(hipMemsetAsync(nc, 0, want * 4, st));
-    hipLaunchKernelGGL(k_rehash_move, dim3(grid_old), dim3(256), 0, st, mr.d_table, static_cast<uint32_t>(old_slots), nt, nk,
-                       static_cast<uint32_t>(want - 1), map->host.count_bits(), &mr.d_ctr->error);
+    hipLaunchKernelGGL(k_table_clear, dim3(grid_new), dim3(256), 0, st, nt.get(), static_cast<uint32_t>(want));
+    HIP_TRY(hipMemsetAsync(nk.get(), 0xFF, want * 8, st));
+    HIP_TRY(hipMemsetAsync(nc.get(), 0, want * 4, st));
+    hipLaunchKernelGGL(k_rehash_move, dim3(grid_old), dim3(256), 0, st, mr.d_table.get(), static_cast<uint32_t>(old_slots), nt.get(), nk.get(),
+                       static_cast<uint32_t>(want - 1), map->host.count_bits(), &mr.d_ctr.get()->error);
     HIP_TRY(hipGetLastError());
     map->dev.n_entries = live, map->dev.touched = 0;
-    HIP_TRY(hipMemcpyAsync(&mr.d_ctr->n_entries, &map->dev.n_entries, 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(&mr.d_ctr.get()->n_entries, &map->dev.n_entries, 4, hipMemcpyHostToDevice, st));
     uint32_t err = 0;
-    HIP_TRY(hipMemcpy(&err, &mr.d_ctr->error, 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&err, &mr.d_ctr.get()->error, 4, hipMemcpyDeviceToHost));
     HIP_TRY(hipStreamSynchronize(st));
-    hipFree(mr.d_table), hipFree(mr.d_keys64), hipFree(mr.d_cnt), hipFree(mr.d_seg_start);
-    mr.d_table = nt, mr.d_keys64 = nk, mr.d_cnt = nc, mr.d_seg_start = ns;
-    mr.table_slots = mr.live_slots = mr.aux_slots = want;
-    mr.view.table = nt, mr.view.mask = static_cast<uint32_t>(want - 1);
+    std::swap(mr.d_table, nt), std::swap(mr.d_keys64, nk), std::swap(mr.d_cnt, nc), std::swap(mr.d_seg_start, ns);  // (the old ones go with the locals)
+    mr.live_slots = want;
+    mr.view.table = mr.d_table.get(), mr.view.mask = static_cast<uint32_t>(want - 1);
     map->device_ahead = true;
     if (err) return fail(KICP_ERR_CAPACITY, "a voxel coordinate left the +-2^20 range of the device-side map update");
     return KICP_OK;
@@ -318,11 +295,11 @@ int map_update_device(kicp_map *map, int device, const double *d_points, size_t 
     UpdateParams up{};
     DevMapCounters c{};
     auto bind = [&]() {
-        const size_t slots = mr.live_slots, bucket_cap = mr.pool_doubles / (static_cast<size_t>(cap) * 3);
-        up.m = DevMap{mr.d_table, mr.d_keys64, static_cast<uint32_t>(slots - 1), mr.d_pool, mr.d_pool16, cap, map->host.count_bits(), static_cast<uint32_t>(bucket_cap),
-                      map->host.voxel_size(), map->host.max_distance(), mr.d_free_list, mr.d_cnt, mr.d_seg_start, mr.d_ctr};
-        up.in = d_points, up.n = static_cast<uint32_t>(n), up.pose = pose, up.world = mr.d_world, up.slot_of = mr.d_slot_of, up.order = mr.d_order;
-        up.touched = mr.d_touched;
+        const size_t slots = mr.live_slots, bucket_cap = mr.d_pool.capacity() / (static_cast<size_t>(cap) * 3);
+        up.m = DevMap{mr.d_table.get(), mr.d_keys64.get(), static_cast<uint32_t>(slots - 1), mr.d_pool.get(), mr.d_pool16.get(), cap, map->host.count_bits(), static_cast<uint32_t>(bucket_cap),
+                      map->host.voxel_size(), map->host.max_distance(), mr.d_free_list.get(), mr.d_cnt.get(), mr.d_seg_start.get(), mr.d_ctr.get()};
+        up.in = d_points, up.n = static_cast<uint32_t>(n), up.pose = pose, up.world = mr.d_world.get(), up.slot_of = mr.d_slot_of.get(), up.order = mr.d_order.get();
+        up.touched = mr.d_touched.get();
     };
     // steps 3, 4 and the far-voxel sweep; `touched_bound`: the number of touched voxels, or an upper bound of it (the kernels
     // read the exact number on the device)
@@ -346,7 +323,7 @@ int map_update_device(kicp_map *map, int device, const double *d_points, size_t 
     // one synchronisation; a claim step that gives up (voxel coordinate out of range) turns the later steps into no-ops.
     if (n <= 16384 && (map->dev.n_entries + 27ull * n) * 4 <= mr.live_slots * 3ull) {
         bind();
-        if (!mr.ctr_clean) HIP_TRY(hipMemsetAsync(&mr.d_ctr->touched, 0, 12, st));  // touched + error + may_occupy (k_up_publish left them at zero otherwise)
+        if (!mr.ctr_clean) HIP_TRY(hipMemsetAsync(&mr.d_ctr.get()->touched, 0, 12, st));  // touched + error + may_occupy (k_up_publish left them at zero otherwise)
         mr.ctr_clean = false;
         hipLaunchKernelGGL(k_up_claim, dim3(grid), dim3(256), 0, st, up);
         hipLaunchKernelGGL(k_up_scan, dim3(1), dim3(1024), 0, st, up);
@@ -355,31 +332,29 @@ int map_update_device(kicp_map *map, int device, const double *d_points, size_t 
         if (defer) {
             // the caller collects the end of this update later (kicp_map_update_finish, or whatever it calls on the map next):
             // the counters land in pinned memory, nothing is waited for here
-            if (!mr.h_ctr) {
-                HIP_TRY(pinned_alloc(reinterpret_cast<void **>(&mr.h_ctr), 8 * sizeof(unsigned long long), hipHostMallocMapped | hipHostMallocCoherent));
-                std::memset(mr.h_ctr, 0, 8 * sizeof(unsigned long long));
-                HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void **>(&mr.h_ctr_dev), mr.h_ctr, 0));
+            if (!mr.h_ctr.get()) {
+                if (int rc = mr.h_ctr.reserve(8, hipHostMallocMapped | hipHostMallocCoherent)) return rc;
+                std::memset(mr.h_ctr.get(), 0, 8 * sizeof(unsigned long long));
             }
-            hipLaunchKernelGGL(k_up_publish, dim3(1), dim3(64), 0, st, mr.d_ctr, mr.h_ctr_dev, ++mr.ctr_seq);
+            hipLaunchKernelGGL(k_up_publish, dim3(1), dim3(64), 0, st, mr.d_ctr.get(), mr.h_ctr.dev(), ++mr.ctr_seq);
             HIP_TRY(hipGetLastError());
             mr.ctr_clean = true;
             map->device_ahead = true;
-            map->pending_update = true, map->pending_points = d_points, map->pending_n = n, map->pending_pose = pose;
-            map->pending_has_origin = remove_origin != nullptr;
-            if (remove_origin) map->pending_origin[0] = remove_origin[0], map->pending_origin[1] = remove_origin[1], map->pending_origin[2] = remove_origin[2];
+            map->pending.active = true, map->pending.points = d_points, map->pending.n = n, map->pending.pose = pose;
+            map->pending.has_origin = remove_origin != nullptr;
+            if (remove_origin) map->pending.origin[0] = remove_origin[0], map->pending.origin[1] = remove_origin[1], map->pending.origin[2] = remove_origin[2];
             map->last_update_on_device = 1;  // (corrected by the finish step should the host have to take the update over)
             return KICP_OK;
         }
-        HIP_TRY(hipMemcpyAsync(&c, mr.d_ctr, sizeof c, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(&c, mr.d_ctr.get(), sizeof c, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         map->device_ahead = true;
         map->dev = c;
-        if (c.error == 3) return fail(KICP_ERR_CAPACITY, "device-side map update: voxel table full");
-        if (c.error == 1) {  // (see below: the host map takes over)
-            map->host_updates_only = true;
+        if (int rc = decode_update_error(c.error)) {
+            if (rc != kRerunOnHost) return rc;
+            map->host_updates_only = true;  // (see below: the host map takes over)
             return host_fallback();
         }
-        if (c.error) return fail(KICP_ERR_CAPACITY, "device-side map update ran out of room");
         map->last_update_on_device = 1, ++map->device_updates;
         return KICP_OK;
     }
@@ -387,22 +362,22 @@ int map_update_device(kicp_map *map, int device, const double *d_points, size_t 
         if (attempt == 0 && (map->dev.n_entries + n) * 2 > mr.live_slots)
             if (int rc = device_rehash(map, 32 * n + 1024)) return rc;
         bind();
-        HIP_TRY(hipMemsetAsync(&mr.d_ctr->touched, 0, 12, st));  // touched + error + may_occupy
+        HIP_TRY(hipMemsetAsync(&mr.d_ctr.get()->touched, 0, 12, st));  // touched + error + may_occupy
         mr.ctr_clean = false;
         hipLaunchKernelGGL(k_up_claim, dim3(grid), dim3(256), 0, st, up);
         if (n > 16384) {  // bulk: the scan over many workgroups (the number of touched voxels is only known on the device: <= n)
             const uint32_t spans = static_cast<uint32_t>((n + kScanSpan - 1) / kScanSpan);
-            hipLaunchKernelGGL(k_up_scan_local, dim3(spans), dim3(256), 0, st, up, mr.d_order);
-            hipLaunchKernelGGL(k_up_scan_sums, dim3(1), dim3(1024), 0, st, up, mr.d_order);
-            hipLaunchKernelGGL(k_up_scan_add, dim3(grid), dim3(256), 0, st, up, mr.d_order);
+            hipLaunchKernelGGL(k_up_scan_local, dim3(spans), dim3(256), 0, st, up, mr.d_order.get());
+            hipLaunchKernelGGL(k_up_scan_sums, dim3(1), dim3(1024), 0, st, up, mr.d_order.get());
+            hipLaunchKernelGGL(k_up_scan_add, dim3(grid), dim3(256), 0, st, up, mr.d_order.get());
         } else {
             hipLaunchKernelGGL(k_up_scan, dim3(1), dim3(1024), 0, st, up);
         }
-        HIP_TRY(hipMemcpyAsync(&c, mr.d_ctr, sizeof c, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemcpyAsync(&c, mr.d_ctr.get(), sizeof c, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
         map->device_ahead = true;  // the table now carries the new voxels' (still empty) entries
-        if (c.error == 3) return fail(KICP_ERR_CAPACITY, "device-side map update: voxel table full");
-        if (c.error) {
+        if (int rc = decode_update_error(c.error)) {  // (the claim and scan steps raise 1 or 3 only)
+            if (rc != kRerunOnHost) return rc;
             // A voxel coordinate beyond +-2^20 (the packed keys' range; the reference has no such limit): nothing was inserted for
             // such points, and what the claim step did insert are plain halo entries.  The host map takes this update - and every
             // later one of this map - over.
@@ -419,9 +394,10 @@ int map_update_device(kicp_map *map, int device, const double *d_points, size_t 
     }
     enqueue_apply(c.touched);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(&c, mr.d_ctr, sizeof c, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&c, mr.d_ctr.get(), sizeof c, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    if (c.error) return fail(KICP_ERR_CAPACITY, c.error == 3 ? "device-side map update: voxel table full" : "device-side map update ran out of room");
+    // (too late for the host to take over: the points are in)
+    if (int rc = decode_update_error(c.error)) return rc == kRerunOnHost ? fail(KICP_ERR_CAPACITY, "device-side map update ran out of room") : rc;
     map->dev = c;
     map->last_update_on_device = 1, ++map->device_updates;
     return KICP_OK;
@@ -433,38 +409,40 @@ namespace host {
 // The end of an update begun with defer = true: wait for its kernels, take the counters over, and - should the claim step have met
 // a voxel the packed keys cannot express - let the host map redo the update from the (still borrowed) points.
 int map_finish_pending(kicp_map *map) {
-    if (!map->pending_update) return KICP_OK;
-    map->pending_update = false;
+    if (!map->pending.active) return KICP_OK;
+    map->pending.active = false;
     DeviceMirror &mr = map->mirror;
     if (int rc = set_device(mr.device)) return rc;
-    // the update's last launch said so in host memory (k_up_publish); a word that is not there after 2 ms: synchronise, look again
-    const volatile unsigned long long *words = mr.h_ctr;
-    const auto t0 = std::chrono::steady_clock::now();
-    for (unsigned spins = 0; words[7] != mr.ctr_seq; ++spins) {
-        if ((spins & 255u) == 255u && std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() > 2.0) {
-            HIP_TRY(hipStreamSynchronize(nullptr));
-            if (words[7] != mr.ctr_seq) return fail(KICP_ERR_HIP, "the map update finished without handing its counters over");
-            break;
-        }
-        __builtin_ia32_pause();
-    }
+    // the update's last launch said so in host memory (k_up_publish)
+    const volatile unsigned long long *words = mr.h_ctr.get();
+    if (int rc = wait_word(words + 7, mr.ctr_seq, ~0ull, nullptr, 2.0, "the map update finished without handing its counters over")) return rc;
     DevMapCounters c;
     unsigned long long raw[5];
     for (int w = 0; w < 5; ++w) raw[w] = words[w];
     std::memcpy(&c, raw, sizeof c);
     map->dev = c;
-    if (c.error == 3) return fail(KICP_ERR_CAPACITY, "device-side map update: voxel table full");
-    if (c.error == 1) {
+    if (int rc = decode_update_error(c.error)) {
+        if (rc != kRerunOnHost) return rc;
         map->host_updates_only = true;
-        return map_update_device(map, mr.device, map->pending_points, map->pending_n, map->pending_pose, map->pending_has_origin ? map->pending_origin : nullptr);
+        const kicp_map::PendingUpdate &u = map->pending;
+        return map_update_device(map, mr.device, u.points, u.n, u.pose, u.has_origin ? u.origin : nullptr);
     }
-    if (c.error) return fail(KICP_ERR_CAPACITY, "device-side map update ran out of room");
     ++map->device_updates;
     return KICP_OK;
 }
 }  // namespace host
 }  // namespace kicp
 namespace {
+// What both Pointcloud() gathers begin with: the occupied points of every 256-slot block of the device table, then their running
+// sums and, behind them, the total (d_pc_blocks[blocks])
+int pc_count_blocks(kicp_map *map, hipStream_t st) {
+    DeviceMirror &mr = map->mirror;
+    const size_t slots = mr.live_slots, blocks = (slots + 255) / 256;
+    if (int rc = mr.d_pc_blocks.reserve(blocks + 1)) return rc;
+    hipLaunchKernelGGL(k_pc_count, dim3(static_cast<uint32_t>(blocks)), dim3(256), 0, st, mr.d_table.get(), mr.d_keys64.get(), static_cast<uint32_t>(slots), map->host.count_bits(), mr.d_pc_blocks.get());
+    hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(1024), 0, st, mr.d_pc_blocks.get(), static_cast<uint32_t>(blocks), mr.d_pc_blocks.get() + blocks);
+    return KICP_OK;
+}
 // Host-side AddPoints / Update calls with many points go through the device path when the map has a preferred device
 // (kicp_map_set_device): the points are staged into HBM and inserted there - the same map as the host insertion builds
 // (tests/test_gpu_mapdev.py), an order of magnitude faster (the host table's 128-byte slots and 27 neighbour records per
@@ -474,14 +452,10 @@ int bulk_insert(kicp_map *map, const double *xyz, size_t n, const Pose &pose, co
     DeviceMirror &mr = map->mirror;
     const int device = map->bulk_device;
     if (int rc = set_device(device)) return rc;
-    if (n > map->bulk_cap) {
-        hipFree(map->d_bulk);
-        map->d_bulk = nullptr, map->bulk_cap = 0;
-        HIP_TRY(hipMalloc(&map->d_bulk, (n + n / 4 + 1024) * 24));
-        map->bulk_cap = n + n / 4 + 1024;
-    }
-    if (int rc = staged_upload(mr.stage, 0, map->d_bulk, xyz, n * 24, nullptr)) return rc;
-    return map_update_device(map, device, map->d_bulk, n, pose, remove_origin);
+    if (n > map->d_bulk.capacity() / 3)
+        if (int rc = map->d_bulk.reserve((n + n / 4 + 1024) * 3)) return rc;
+    if (int rc = staged_upload(mr.stage, 0, map->d_bulk.get(), xyz, n * 24, nullptr)) return rc;
+    return map_update_device(map, device, map->d_bulk.get(), n, pose, remove_origin);
 }
 bool use_bulk(const kicp_map *map, size_t n) { return map->bulk_device >= 0 && n >= kBulkThreshold; }
 const Pose kIdentityPose{0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0};
@@ -500,9 +474,9 @@ int kicp_map_create(double voxel_size, double max_distance, unsigned int max_poi
 void kicp_map_destroy(kicp_map *map) {
     if (!map) return;
     (void)map_finish_pending(map);
-    if (map->d_bulk) {
+    if (map->d_bulk.get()) {
         hipSetDevice(map->bulk_device >= 0 ? map->bulk_device : 0);
-        hipFree(map->d_bulk);
+        map->d_bulk.release();
     }
     free_mirror(map->mirror);
     delete map;
@@ -523,10 +497,9 @@ int kicp_map_set_device(kicp_map *map, int device) {
         int ndev = 0;
         if (hipGetDeviceCount(&ndev) != hipSuccess || device >= ndev) return fail(KICP_ERR_ARG, "device index out of range");
     }
-    if (map->d_bulk && device != map->bulk_device) {
+    if (map->d_bulk.get() && device != map->bulk_device) {
         hipSetDevice(map->bulk_device);
-        hipFree(map->d_bulk);
-        map->d_bulk = nullptr, map->bulk_cap = 0;
+        map->d_bulk.release();
     }
     map->bulk_device = device < 0 ? -1 : device;
     return KICP_OK;
@@ -634,28 +607,17 @@ size_t kicp_map_pointcloud(const kicp_map *cmap, double *out_xyz, size_t cap_poi
     auto gather = [&]() -> int {
         if (int rc = set_device(mr.device)) return rc;
         const size_t slots = mr.live_slots, blocks = (slots + 255) / 256;
-        if (blocks + 1 > mr.pc_blocks) {
-            hipFree(mr.d_pc_blocks);
-            mr.d_pc_blocks = nullptr, mr.pc_blocks = 0;
-            HIP_TRY(hipMalloc(&mr.d_pc_blocks, (blocks + 1) * 4));
-            mr.pc_blocks = blocks + 1;
-        }
-        if (total > mr.pc_points) {
-            hipFree(mr.d_pc);
-            mr.d_pc = nullptr, mr.pc_points = 0;
-            HIP_TRY(hipMalloc(&mr.d_pc, (total + total / 4 + 1024) * 24));
-            mr.pc_points = total + total / 4 + 1024;
-        }
+        if (total > mr.d_pc.capacity() / 3)
+            if (int rc = mr.d_pc.reserve((total + total / 4 + 1024) * 3)) return rc;
         hipStream_t st = nullptr;
-        hipLaunchKernelGGL(k_pc_count, dim3(static_cast<uint32_t>(blocks)), dim3(256), 0, st, mr.d_table, mr.d_keys64, static_cast<uint32_t>(slots), map->host.count_bits(), mr.d_pc_blocks);
-        hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(1024), 0, st, mr.d_pc_blocks, static_cast<uint32_t>(blocks), mr.d_pc_blocks + blocks);
-        hipLaunchKernelGGL(k_pc_gather, dim3(static_cast<uint32_t>(blocks)), dim3(256), 0, st, mr.d_table, mr.d_keys64, static_cast<uint32_t>(slots),
-                           mr.d_pool, map->host.cap(), map->host.count_bits(), mr.d_pc_blocks, mr.d_pc);
+        if (int rc = pc_count_blocks(map, st)) return rc;
+        hipLaunchKernelGGL(k_pc_gather, dim3(static_cast<uint32_t>(blocks)), dim3(256), 0, st, mr.d_table.get(), mr.d_keys64.get(), static_cast<uint32_t>(slots),
+                           mr.d_pool.get(), map->host.cap(), map->host.count_bits(), mr.d_pc_blocks.get(), mr.d_pc.get());
         HIP_TRY(hipGetLastError());
         uint32_t counted = 0;
-        HIP_TRY(hipMemcpy(&counted, mr.d_pc_blocks + blocks, 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(&counted, mr.d_pc_blocks.get() + blocks, 4, hipMemcpyDeviceToHost));
         if (counted != total) return fail(KICP_ERR_HIP, "device map counters disagree with the table");
-        if (int rc = staged_download(mr.stage, out_xyz, mr.d_pc, want * 24, st)) return rc;
+        if (int rc = staged_download(mr.stage, out_xyz, mr.d_pc.get(), want * 24, st)) return rc;
         return KICP_OK;
     };
     if (gather() != KICP_OK) {  // fall back to refreshing the host copy
@@ -695,35 +657,22 @@ int kicp_map_pointcloud_f32(const kicp_map *cmap, float *out_xyz, size_t cap_poi
     auto gather = [&]() -> int {
         if (int rc = set_device(mr.device)) return rc;
         const size_t slots = mr.live_slots, blocks = (slots + 255) / 256;
-        if (blocks + 1 > mr.pc_blocks) {
-            hipFree(mr.d_pc_blocks);
-            mr.d_pc_blocks = nullptr, mr.pc_blocks = 0;
-            HIP_TRY(hipMalloc(&mr.d_pc_blocks, (blocks + 1) * 4));
-            mr.pc_blocks = blocks + 1;
+        if (piece * 12 * kSlots > mr.h_records.capacity())
+            if (int rc = mr.h_records.reserve(piece * 12 * kSlots, hipHostMallocDefault)) return rc;
+        if (!mr.h_rec_flags.get()) {
+            if (int rc = mr.h_rec_flags.reserve(kSlots, hipHostMallocMapped | hipHostMallocCoherent)) return rc;
+            std::memset(mr.h_rec_flags.get(), 0, kSlots * sizeof(unsigned long long));
         }
-        if (piece * 12 * kSlots > mr.records_cap) {
-            if (mr.h_records) HIP_TRY(hipHostFree(mr.h_records));
-            mr.h_records = mr.h_records_dev = nullptr, mr.records_cap = 0;
-            HIP_TRY(pinned_alloc(reinterpret_cast<void **>(&mr.h_records), piece * 12 * kSlots, hipHostMallocDefault));
-            mr.records_cap = piece * 12 * kSlots;
-            HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void **>(&mr.h_records_dev), mr.h_records, 0));
-        }
-        if (!mr.h_rec_flags) {
-            HIP_TRY(pinned_alloc(reinterpret_cast<void **>(&mr.h_rec_flags), kSlots * sizeof(unsigned long long), hipHostMallocMapped | hipHostMallocCoherent));
-            std::memset(mr.h_rec_flags, 0, kSlots * sizeof(unsigned long long));
-            HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void **>(&mr.h_rec_flags_dev), mr.h_rec_flags, 0));
-        }
-        if (!mr.d_rec_tickets) {
-            HIP_TRY(hipMalloc(&mr.d_rec_tickets, kSlots * sizeof(unsigned long long)));
-            HIP_TRY(hipMemset(mr.d_rec_tickets, 0, kSlots * sizeof(unsigned long long)));
+        if (!mr.d_rec_tickets.get()) {
+            if (int rc = mr.d_rec_tickets.reserve(kSlots)) return rc;
+            HIP_TRY(hipMemset(mr.d_rec_tickets.get(), 0, kSlots * sizeof(unsigned long long)));
             for (int s = 0; s < kSlots; ++s) mr.rec_drawn[s] = 0;
         }
         hipStream_t st = nullptr;
-        hipLaunchKernelGGL(k_pc_count, dim3(static_cast<uint32_t>(blocks)), dim3(256), 0, st, mr.d_table, mr.d_keys64, static_cast<uint32_t>(slots), map->host.count_bits(), mr.d_pc_blocks);
-        hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(1024), 0, st, mr.d_pc_blocks, static_cast<uint32_t>(blocks), mr.d_pc_blocks + blocks);
+        if (int rc = pc_count_blocks(map, st)) return rc;
         PcRecordParams q{};
-        q.table = mr.d_table, q.keys64 = mr.d_keys64, q.slots = static_cast<uint32_t>(slots), q.cap = map->host.cap(), q.cbits = map->host.count_bits();
-        q.blocks = static_cast<uint32_t>(blocks), q.pool = mr.d_pool, q.block_offsets = mr.d_pc_blocks;
+        q.table = mr.d_table.get(), q.keys64 = mr.d_keys64.get(), q.slots = static_cast<uint32_t>(slots), q.cap = map->host.cap(), q.cbits = map->host.count_bits();
+        q.blocks = static_cast<uint32_t>(blocks), q.pool = mr.d_pool.get(), q.block_offsets = mr.d_pc_blocks.get();
         // workgroups per piece: about as many as the piece has table blocks (the map's average records per block), at most 512
         const size_t per_block = std::max<size_t>(1, total / std::max<size_t>(1, blocks));
         const uint32_t grid = static_cast<uint32_t>(std::min<size_t>({blocks, 512, piece / per_block + 2}));
@@ -731,9 +680,9 @@ int kicp_map_pointcloud_f32(const kicp_map *cmap, float *out_xyz, size_t cap_poi
         auto queue = [&](size_t i) -> int {
             const int s = static_cast<int>(i % kSlots);
             q.lo = static_cast<uint32_t>(i * piece), q.hi = static_cast<uint32_t>(std::min(want, (i + 1) * piece));
-            q.dst = reinterpret_cast<float *>(mr.h_records_dev + static_cast<size_t>(s) * piece * 12);
+            q.dst = reinterpret_cast<float *>(mr.h_records.dev() + static_cast<size_t>(s) * piece * 12);
             mr.rec_drawn[s] += grid;
-            q.ticket = mr.d_rec_tickets + s, q.ticket_done = mr.rec_drawn[s], q.host_flag = mr.h_rec_flags_dev + s;
+            q.ticket = mr.d_rec_tickets.get() + s, q.ticket_done = mr.rec_drawn[s], q.host_flag = mr.h_rec_flags.dev() + s;
             q.seq = ++mr.rec_seq;
             if (q.seq == 0u) q.seq = ++mr.rec_seq;  // (0 is what the flags hold before the first piece)
             seqs[s] = q.seq;
@@ -744,26 +693,19 @@ int kicp_map_pointcloud_f32(const kicp_map *cmap, float *out_xyz, size_t cap_poi
         for (size_t i = 0; i < std::min<size_t>(pieces, kSlots); ++i)
             if (int rc = queue(i)) return rc;
         // each piece: wait for its flag, check the table's count it carries, copy the piece out, queue the piece that reuses its slot
-        const volatile unsigned long long *flags = mr.h_rec_flags;
+        const volatile unsigned long long *flags = mr.h_rec_flags.get();
         for (size_t i = 0; i < pieces; ++i) {
             const int s = static_cast<int>(i % kSlots);
             const unsigned long long tag = static_cast<unsigned long long>(seqs[s]) << 32;
-            const auto t0 = std::chrono::steady_clock::now();
-            for (unsigned spins = 0; (flags[s] & 0xFFFFFFFF00000000ull) != tag; ++spins) {
-                if ((spins & 1023u) == 1023u && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > 2.0) {
-                    HIP_TRY(hipStreamSynchronize(st));  // (something is badly wrong: surface it instead of spinning for ever)
-                    if ((flags[s] & 0xFFFFFFFF00000000ull) != tag) return fail(KICP_ERR_HIP, "a piece of the map's records was never announced");
-                    break;
-                }
-                __builtin_ia32_pause();
-            }
-            const uint32_t counted = static_cast<uint32_t>(flags[s] & 0xFFFFFFFFull);
+            unsigned long long flag = 0;  // (2 s: something is badly wrong then - surface it instead of spinning for ever)
+            if (int rc = wait_word(flags + s, tag, 0xFFFFFFFF00000000ull, st, 2000.0, "a piece of the map's records was never announced", &flag)) return rc;
+            const uint32_t counted = static_cast<uint32_t>(flag & 0xFFFFFFFFull);
             if (counted != total) {
                 HIP_TRY(hipStreamSynchronize(st));
                 return fail(KICP_ERR_HIP, "device map counters disagree with the table");
             }
             const size_t lo = i * piece, n = std::min(want, lo + piece) - lo;
-            std::memcpy(out_xyz + lo * 3, mr.h_records + static_cast<size_t>(s) * piece * 12, n * 12);
+            std::memcpy(out_xyz + lo * 3, mr.h_records.get() + static_cast<size_t>(s) * piece * 12, n * 12);
             if (i + kSlots < pieces)
                 if (int rc = queue(i + kSlots)) return rc;
         }
@@ -786,7 +728,7 @@ int kicp_map_sync(kicp_map *map, int device) {
     return map_sync(map, device, nullptr);
 }
 size_t kicp_map_device_bytes(const kicp_map *map) {
-    if (!map || !map->mirror.d_table) return 0;
+    if (!map || !map->mirror.d_table.get()) return 0;
     const DeviceMirror &mr = map->mirror;
     // what a query can touch: the table's entries (occupied + halo) and the buckets of the occupied voxels, not the head-room
     // around them
@@ -809,18 +751,16 @@ int kicp_map_closest(kicp_map *map, int device, const double *queries_xyz, size_
         return KICP_OK;
     }
     if (int rc = kicp_map_sync(map, device)) return rc;
-    double *d_q = nullptr, *d_nn = nullptr, *d_d = nullptr;
-    HIP_TRY(hipMalloc(&d_q, n * 24));
-    HIP_TRY(hipMalloc(&d_nn, n * 24));
-    HIP_TRY(hipMalloc(&d_d, n * 8));
-    if (int rc = staged_upload(map->mirror.stage, 0, d_q, queries_xyz, n * 24, nullptr)) return rc;
-    hipLaunchKernelGGL(k_closest, dim3(static_cast<uint32_t>((n + 255) / 256)), dim3(256), 0, nullptr, d_q, static_cast<uint32_t>(n),
-                       map->mirror.view, d_nn, d_d);
+    DevBuf<double> d_q, d_nn, d_d;
+    if (int rc = d_q.reserve(n * 3)) return rc;
+    if (int rc = d_nn.reserve(n * 3)) return rc;
+    if (int rc = d_d.reserve(n)) return rc;
+    if (int rc = staged_upload(map->mirror.stage, 0, d_q.get(), queries_xyz, n * 24, nullptr)) return rc;
+    hipLaunchKernelGGL(k_closest, dim3(static_cast<uint32_t>((n + 255) / 256)), dim3(256), 0, nullptr, d_q.get(), static_cast<uint32_t>(n),
+                       map->mirror.view, d_nn.get(), d_d.get());
     HIP_TRY(hipGetLastError());
-    if (int rc = staged_download(map->mirror.stage, out_nn_xyz, d_nn, n * 24, nullptr)) return rc;
-    if (int rc = staged_download(map->mirror.stage, out_dist, d_d, n * 8, nullptr)) return rc;
-    hipFree(d_q), hipFree(d_nn), hipFree(d_d);
-    return KICP_OK;
+    if (int rc = staged_download(map->mirror.stage, out_nn_xyz, d_nn.get(), n * 24, nullptr)) return rc;
+    return staged_download(map->mirror.stage, out_dist, d_d.get(), n * 8, nullptr);
 }
 
 }  // extern "C"

@@ -11,42 +11,41 @@ using namespace kicp::host;
 struct kicp_pre {
     int device = 0;
     hipStream_t stream = nullptr;
-    double *buf[KICP_PRE_BUFFERS] = {};
-    size_t buf_cap[KICP_PRE_BUFFERS] = {}, buf_n[KICP_PRE_BUFFERS] = {};
-    double *d_in = nullptr, *d_ts = nullptr, *d_staged = nullptr;
-    uint32_t *d_flags = nullptr, *d_block_counts = nullptr, *d_misc = nullptr;  // misc: [0] total, [1] error, [2] largest robin-hood displacement of the last downsample
+    // Every device and pinned buffer is an owner (kicp_internal.hpp): kicp_pre_destroy tears streams, events and threads down
+    // explicitly, the memory goes with `delete`.
+    DevBuf<double> buf[KICP_PRE_BUFFERS];  // 3 doubles per point
+    size_t buf_n[KICP_PRE_BUFFERS] = {};
+    DevBuf<double> d_in, d_ts, d_staged;  // (these, the second slot, the flags, counts and tables: sized together by pre_ensure, for cap_n points)
+    DevBuf<uint32_t> d_flags, d_block_counts, d_misc;  // misc: [0] total, [1] error, [2] largest robin-hood displacement of the last downsample
     uint32_t last_max_probe = 0;
     // longest probe the reference's tsl::robin_map tolerates before it grows its table instead (kicp_pre_set_probe_limit)
     uint32_t probe_limit = [] {
         const char *e = std::getenv("KICP_ROBIN_PROBE_LIMIT");
         return e && *e ? static_cast<uint32_t>(std::strtoul(e, nullptr, 10)) : 128u;
     }();
-    unsigned char *d_table = nullptr;  // downsampling table: keys | min_index | order | home_at, 20 B per bucket (kicp_pre.hpp)
-    unsigned char *d_table2 = nullptr; // the fused chain's table of the second level (the first level's is still being emptied when it fills)
-    uint32_t *d_counts1 = nullptr, *d_counts2 = nullptr;  // the fused chain's occupied-bucket counts per tile of either table
+    DevBuf<unsigned char> d_table;  // downsampling table: keys | min_index | order | home_at, 20 B per bucket (kicp_pre.hpp)
+    DevBuf<unsigned char> d_table2;  // the fused chain's table of the second level (the first level's is still being emptied when it fills)
+    DevBuf<uint32_t> d_counts1, d_counts2;  // the fused chain's occupied-bucket counts per tile of either table
     size_t cap_n = 0, table_slots = 0;
     bool table_clean = false;  // every byte of d_table / d_table2 is 0xFF (what a downsample needs to find; its gather step leaves it so)
     // the fused chain (k_frame_*): the survivor count its table size is guessed from (0: none yet), the record its last workgroup
     // writes for the host, and how often the guess was wrong (the unfused steps then run from buffer 0 on)
     uint32_t spec_tiles_b = 0;  // 256-bucket tiles of the previous frame's second-level table (sizes that level's launches)
     uint32_t spec_n0 = 0, spec_n_in = 0;  // (... and the input count it belonged to: the guess scales with the frame)
-    unsigned long long *h_rec = nullptr;  // pinned, host-coherent: [0..4] the chain's tagged words, [8..10] / [12..14] the ingest records (this call's / the look-ahead's;
+    PinnedBuf<unsigned long long> h_rec;  // host-coherent: [0..4] the chain's tagged words, [8..10] / [12..14] the ingest records (this call's / the look-ahead's;
                                           // [11]: a scan's kept beams, k_ingest_scan),
                                           // [16..23] the pushed frame's piece flags (k_push_frame)
-    unsigned long long *d_push_tickets = nullptr;  // [kPushPieces] device counters of k_push_frame, never reset
+    DevBuf<unsigned long long> d_push_tickets;  // [kPushPieces] device counters of k_push_frame, never reset
     unsigned long long push_drawn = 0;
     uint32_t push_seq = 0;
     // the registration source (buffer 2, ~100 KB) also lands in host memory as the fused chain's last launch writes it: the pipeline
     // returns it too (KinematicICP.cpp:84), and a copy + stream synchronisation for it cost the frame ~40 us
-    unsigned char *h_src = nullptr, *h_src_dev = nullptr;
-    size_t h_src_cap = 0;
+    PinnedBuf<unsigned char> h_src;  // (dev() == nullptr: not mapped)
     bool src_on_host = false;  // h_src holds buffer 2's current contents - once word 5 of h_rec carries src_seq (k_frame_src_host)
     bool src_f32 = false;      // ... as x y z FLOAT32 records (the frame came through kicp_pre_frame*_f32), not as doubles
-    float *d_narrow = nullptr; // kicp_pre_download_f32 of a buffer without a host copy: its records in HBM
-    size_t narrow_cap = 0;
+    DevBuf<float> d_narrow;    // kicp_pre_download_f32 of a buffer without a host copy: its records in HBM
     uint32_t src_seq = 0;
-    unsigned char *copy_host_dev = nullptr;  // the landing area as the device sees it (nullptr: not mapped - the DMA engine moves the frame)
-    unsigned long long *d_ticket = nullptr;  // [2] the ingest kernels' tickets (never reset), one per record
+    DevBuf<unsigned long long> d_ticket;  // [2] the ingest kernels' tickets (never reset), one per record
     unsigned long long ticket_drawn[2] = {0ull, 0ull};
     uint32_t chain_seq = 0;
     unsigned long long ingest_seq = 0;
@@ -57,8 +56,7 @@ struct kicp_pre {
     }();
     // wire-format ingest: the raw message bytes (only where the device cannot read the staging buffer), the stamps' extrema, what
     // d_in / d_ts currently hold
-    unsigned char *d_raw = nullptr;
-    size_t raw_cap = 0;
+    DevBuf<unsigned char> d_raw;
     double ts_lo = 0.0, ts_hi = 0.0;  // d_ts holds the stamps in seconds; consumers normalise with these (PreprocessParams::ts_normalise)
     bool ts_raw = false;
     mutable HostStage stage;  // pinned staging for transfers from / to caller memory
@@ -71,8 +69,8 @@ struct kicp_pre {
     static constexpr int kCopyPieces = 3;
     hipEvent_t copy_piece_done[kCopyPieces] = {};
     size_t copy_piece_bytes = 0;  // bytes per piece of the transfer in flight (0: one piece, only copy_done)
-    unsigned char *copy_host = nullptr;
-    size_t copy_cap = 0, copy_n = 0;
+    PinnedBuf<unsigned char> copy_host;  // the landing area (dev() == nullptr: not mapped - the DMA engine moves the frame)
+    size_t copy_n = 0;
     size_t copy_points = 0;  // points the helper thread moves (set before the job is posted, never written while it runs; copy_n is what _finish REPORTS)
     int copy_buffer = -1;
     // kicp_pre_download_begin_into: a helper thread of the handle moves the landed bytes into the caller's memory while the
@@ -85,13 +83,13 @@ struct kicp_pre {
     size_t copy_dst_points = 0;
     size_t copy_rec_bytes = 24;  // bytes per point of the download in flight: 24 (fp64) or 12 (the FLOAT32 records of kicp_pre_frame*_f32)
     hipError_t copy_error = hipSuccess;
-    unsigned long long *d_block_minmax = nullptr;
+    DevBuf<unsigned long long> d_block_minmax;
     size_t ingested_n = 0;
     bool ingested = false, ingested_stamps = false;
     // LOOK-AHEAD ingest (kicp_pre_ingest_ahead, round 5): the NEXT message is uploaded and decoded into a second slot (d_in2 / d_ts2) on
     // a stream of its own by the kicp_pre_frame_ingested call of the CURRENT one - while that call's kernels run and its thread would
     // only wait -, and the kicp_pre_ingest call for the same message then just swaps the slots.
-    double *d_in2 = nullptr, *d_ts2 = nullptr;
+    DevBuf<double> d_in2, d_ts2;
     hipStream_t ahead_stream = nullptr;
     struct Ahead {
         const void *data = nullptr;
@@ -113,8 +111,7 @@ struct kicp_pre {
     HostStage stage_ahead;              // its own pinned staging buffer (the calling thread goes on using `stage` meanwhile)
     // 2-D LaserScan ingest (kicp_pre_ingest_scan): the projector's cosine table in HBM and the key it was built for (kicp_pre.hpp
     // laser_rules: one table per projector, kept while n, angle_min and angle_max stay the same)
-    double *d_scan_cs = nullptr;
-    size_t scan_cs_cap = 0;
+    DevBuf<unsigned char> d_scan_cs;  // (doubles; sized in bytes)
     std::vector<double> scan_cs_host;
     bool scan_table = false;
     size_t scan_n = 0;
@@ -133,44 +130,36 @@ int pre_ensure(kicp_pre *p, size_t n) {
     if (int rc = ahead_join(p)) return rc;
     if (p->ahead_stream) HIP_TRY(hipStreamSynchronize(p->ahead_stream));
     p->ahead.state = 0;  // (a cloud waiting in the second slot goes with it: its kicp_pre_ingest call uploads it again)
-    hipFree(p->d_in), hipFree(p->d_ts), hipFree(p->d_in2), hipFree(p->d_ts2), hipFree(p->d_staged), hipFree(p->d_flags), hipFree(p->d_block_counts), hipFree(p->d_table);
-    hipFree(p->d_table2), hipFree(p->d_counts1), hipFree(p->d_counts2), hipFree(p->d_block_minmax);
-    p->d_in = p->d_ts = p->d_in2 = p->d_ts2 = p->d_staged = nullptr, p->d_flags = p->d_block_counts = nullptr, p->d_table = nullptr, p->cap_n = 0;
-    p->d_table2 = nullptr, p->d_counts1 = p->d_counts2 = nullptr, p->d_block_minmax = nullptr;
+    p->cap_n = 0;  // (until all twelve are in place: a failed growth is made up for by the next call)
     const size_t slots = reference_bucket_count(cap);  // >= the reference's bucket count for every frame of <= cap points
-    HIP_TRY(hipMalloc(&p->d_in, cap * 24));
-    HIP_TRY(hipMalloc(&p->d_ts, cap * 8));
-    HIP_TRY(hipMalloc(&p->d_in2, cap * 24));
-    HIP_TRY(hipMalloc(&p->d_ts2, cap * 8));
-    HIP_TRY(hipMalloc(&p->d_staged, cap * 24));
-    HIP_TRY(hipMalloc(&p->d_flags, cap * 4));
-    HIP_TRY(hipMalloc(&p->d_block_counts, (std::max(cap, slots) / 256 + 2) * 4));
-    HIP_TRY(hipMalloc(&p->d_table, slots * 20));
-    HIP_TRY(hipMalloc(&p->d_table2, slots * 20));
-    HIP_TRY(hipMalloc(&p->d_counts1, (slots / 256 + 2) * 4));
-    HIP_TRY(hipMalloc(&p->d_counts2, (slots / 256 + 2) * 4));
-    HIP_TRY(hipMalloc(&p->d_block_minmax, (cap / 256 + 2) * 16));
+    if (int rc = p->d_in.reserve(cap * 3)) return rc;
+    if (int rc = p->d_ts.reserve(cap)) return rc;
+    if (int rc = p->d_in2.reserve(cap * 3)) return rc;
+    if (int rc = p->d_ts2.reserve(cap)) return rc;
+    if (int rc = p->d_staged.reserve(cap * 3)) return rc;
+    if (int rc = p->d_flags.reserve(cap)) return rc;
+    if (int rc = p->d_block_counts.reserve(std::max(cap, slots) / 256 + 2)) return rc;
+    if (int rc = p->d_table.reserve(slots * 20)) return rc;
+    if (int rc = p->d_table2.reserve(slots * 20)) return rc;
+    if (int rc = p->d_counts1.reserve(slots / 256 + 2)) return rc;
+    if (int rc = p->d_counts2.reserve(slots / 256 + 2)) return rc;
+    if (int rc = p->d_block_minmax.reserve((cap / 256 + 2) * 2)) return rc;
     p->cap_n = cap, p->table_slots = slots, p->table_clean = false;
     return KICP_OK;
 }
 int pre_ensure_buf(kicp_pre *p, int b, size_t n) {
     if (b == 2) p->src_on_host = false;  // (every path that refills a buffer comes through here first)
-    if (n <= p->buf_cap[b]) return KICP_OK;
-    if (p->buf[b]) HIP_TRY(hipFree(p->buf[b]));
-    p->buf[b] = nullptr;
-    const size_t cap = n + n / 4 + 1024;
-    HIP_TRY(hipMalloc(&p->buf[b], cap * 24));
-    p->buf_cap[b] = cap;
-    return KICP_OK;
+    if (n <= p->buf[b].capacity() / 3) return KICP_OK;
+    return p->buf[b].reserve((n + n / 4 + 1024) * 3);
 }
 // the survivor count (misc[0]) and the range flag (misc[1]) of the kernels queued so far -> buf_n[dst]
 int pre_finish(kicp_pre *p, int dst, size_t *out_n) {
     uint32_t misc[3] = {0, 0, 0};
-    HIP_TRY(hipMemcpyAsync(misc, p->d_misc, sizeof misc, hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(hipMemcpyAsync(misc, p->d_misc.get(), sizeof misc, hipMemcpyDeviceToHost, p->stream));
     HIP_TRY(hipStreamSynchronize(p->stream));
     p->last_max_probe = misc[2];
     if (misc[1]) {  // report once: the flag must not poison the calls that follow on this handle
-        HIP_TRY(hipMemsetAsync(p->d_misc + 1, 0, 4, p->stream));
+        HIP_TRY(hipMemsetAsync(p->d_misc.get() + 1, 0, 4, p->stream));
         return fail(KICP_ERR_CAPACITY, "a voxel coordinate left the +-2^20 range of the downsampling table");
     }
     p->buf_n[dst] = misc[0];
@@ -182,9 +171,9 @@ int pre_compact(kicp_pre *p, const double *staged, size_t n, int dst, size_t *ou
     const uint32_t grid = static_cast<uint32_t>((n + 255) / 256);
     if (int rc = pre_ensure_buf(p, dst, n)) return rc;
     const int raw = grid <= kFusedScanBlocks ? 1 : 0;  // (frame-sized grids: every workgroup adds up the counts before it itself)
-    if (!raw) hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(1024), 0, p->stream, p->d_block_counts, grid, p->d_misc);
-    hipLaunchKernelGGL(k_compact, dim3(grid), dim3(256), 0, p->stream, staged, static_cast<const uint32_t *>(p->d_flags), static_cast<const uint32_t *>(p->d_block_counts), raw,
-                       p->d_misc, static_cast<uint32_t>(n), p->buf[dst]);
+    if (!raw) hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(1024), 0, p->stream, p->d_block_counts.get(), grid, p->d_misc.get());
+    hipLaunchKernelGGL(k_compact, dim3(grid), dim3(256), 0, p->stream, staged, static_cast<const uint32_t *>(p->d_flags.get()), static_cast<const uint32_t *>(p->d_block_counts.get()), raw,
+                       p->d_misc.get(), static_cast<uint32_t>(n), p->buf[dst].get());
     HIP_TRY(hipGetLastError());
     return pre_finish(p, dst, out_n);
 }
@@ -197,15 +186,15 @@ int pre_run_preprocess(kicp_pre *p, size_t n, bool do_deskew, const double relat
         return KICP_OK;
     }
     PreprocessParams pp{};
-    pp.in = p->d_in, pp.timestamps = p->d_ts, pp.n = static_cast<uint32_t>(n), pp.deskew = do_deskew ? 1 : 0;
+    pp.in = p->d_in.get(), pp.timestamps = p->d_ts.get(), pp.n = static_cast<uint32_t>(n), pp.deskew = do_deskew ? 1 : 0;
     const Pose rel = pose_from(relative_motion_qt);
     pose_log(rel, pp.omega);
     pp.motion_inverse = pose_inverse(rel), pp.lidar_to_base = pose_from(lidar_to_base_qt);
     pp.max_range = max_range, pp.min_range = min_range;
     pp.ts_normalise = p->ts_raw ? 1 : 0, pp.ts_lo = p->ts_lo, pp.ts_hi = p->ts_hi;
-    pp.flags = p->d_flags, pp.staged = p->d_staged, pp.block_counts = p->d_block_counts;
+    pp.flags = p->d_flags.get(), pp.staged = p->d_staged.get(), pp.block_counts = p->d_block_counts.get();
     hipLaunchKernelGGL(k_preprocess, dim3(static_cast<uint32_t>((n + 255) / 256)), dim3(256), 0, p->stream, pp);
-    return pre_compact(p, p->d_staged, n, dst_buffer, out_n);
+    return pre_compact(p, p->d_staged.get(), n, dst_buffer, out_n);
 }
 }  // namespace
 extern "C" {
@@ -218,18 +207,21 @@ int kicp_pre_create(int device, kicp_pre **out) {
     kicp_pre *p = new kicp_pre;
     p->device = device;
     hipError_t e = hipStreamCreateWithFlags(&p->stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipMalloc(&p->d_misc, 64);  // [0] total [1] error [2] longest probe [3] ticket [4..6] the chained pre-steps' three counts [7], [8]: kicp_pre.hpp
-    if (e == hipSuccess) e = hipMemset(p->d_misc, 0, 64);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&p->chain_ready, hipEventDisableTiming);
-    if (e == hipSuccess) e = pinned_alloc(reinterpret_cast<void **>(&p->h_rec), 32 * sizeof(unsigned long long), hipHostMallocMapped | hipHostMallocCoherent);
-    if (e == hipSuccess) std::memset(p->h_rec, 0, 32 * sizeof(unsigned long long));
-    if (e == hipSuccess) e = hipMalloc(&p->d_ticket, 16);
-    if (e == hipSuccess) e = hipMemset(p->d_ticket, 0, 16);
-    if (e == hipSuccess) e = hipMalloc(&p->d_push_tickets, kPushPieces * 8);
-    if (e == hipSuccess) e = hipMemset(p->d_push_tickets, 0, kPushPieces * 8);
-    if (e != hipSuccess) {
+    int rc = KICP_OK;
+    if (e == hipSuccess) rc = p->d_misc.reserve(16);  // [0] total [1] error [2] longest probe [3] ticket [4..6] the chained pre-steps' three counts [7], [8]: kicp_pre.hpp
+    if (e == hipSuccess && !rc) rc = p->h_rec.reserve(32, hipHostMallocMapped | hipHostMallocCoherent, false);  // (the kernels take the host address)
+    if (e == hipSuccess && !rc) rc = p->d_ticket.reserve(2);
+    if (e == hipSuccess && !rc) rc = p->d_push_tickets.reserve(kPushPieces);
+    if (e == hipSuccess && !rc) {
+        std::memset(p->h_rec.get(), 0, 32 * sizeof(unsigned long long));
+        e = hipMemset(p->d_misc.get(), 0, 64);
+        if (e == hipSuccess) e = hipMemset(p->d_ticket.get(), 0, 16);
+        if (e == hipSuccess) e = hipMemset(p->d_push_tickets.get(), 0, kPushPieces * 8);
+        if (e == hipSuccess) e = hipEventCreateWithFlags(&p->chain_ready, hipEventDisableTiming);
+    }
+    if (e != hipSuccess || rc) {
         kicp_pre_destroy(p);
-        return fail(KICP_ERR_HIP, std::string("kicp_pre_create: ") + hipGetErrorString(e));
+        return fail(KICP_ERR_HIP, std::string("kicp_pre_create: ") + (rc ? last_error() : hipGetErrorString(e)));
     }
     *out = p;
     return KICP_OK;
@@ -238,18 +230,10 @@ void kicp_pre_destroy(kicp_pre *p) {
     if (!p) return;
     hipSetDevice(p->device);
     if (p->stream) hipStreamSynchronize(p->stream);
-    for (double *b : p->buf) hipFree(b);
     (void)ahead_join(p);
     p->ahead_thread.stop();
-    p->stage_ahead.release();
     if (p->ahead_stream) hipStreamSynchronize(p->ahead_stream), hipStreamDestroy(p->ahead_stream);
     if (p->ingest_stream2) hipStreamSynchronize(p->ingest_stream2), hipStreamDestroy(p->ingest_stream2);
-    if (p->h_rec) hipHostFree(p->h_rec);
-    if (p->h_src) hipHostFree(p->h_src);
-    hipFree(p->d_in), hipFree(p->d_ts), hipFree(p->d_in2), hipFree(p->d_ts2), hipFree(p->d_staged), hipFree(p->d_flags), hipFree(p->d_block_counts), hipFree(p->d_table);
-    hipFree(p->d_table2), hipFree(p->d_counts1), hipFree(p->d_counts2);
-    hipFree(p->d_misc), hipFree(p->d_raw), hipFree(p->d_block_minmax), hipFree(p->d_ticket), hipFree(p->d_push_tickets), hipFree(p->d_scan_cs), hipFree(p->d_narrow);
-    p->stage.release();
     if (p->copy_thread.joinable()) {  // the helper thread finishes the job it has, then leaves
         {
             std::unique_lock<std::mutex> lock(p->copy_mutex);
@@ -264,9 +248,8 @@ void kicp_pre_destroy(kicp_pre *p) {
     for (hipEvent_t e : p->copy_piece_done)
         if (e) hipEventDestroy(e);
     if (p->chain_ready) hipEventDestroy(p->chain_ready);
-    if (p->copy_host) hipHostFree(p->copy_host);
     if (p->stream) hipStreamDestroy(p->stream);
-    delete p;
+    delete p;  // (the buffers: every stream is synchronised, every helper thread joined)
 }
 int kicp_pre_preprocess(kicp_pre *p, const double *frame_xyz, size_t n, const double *timestamps, size_t n_timestamps,
                         const double relative_motion_qt[7], const double lidar_to_base_qt[7], double max_range, double min_range,
@@ -282,9 +265,9 @@ int kicp_pre_preprocess(kicp_pre *p, const double *frame_xyz, size_t n, const do
         if (int rc = pre_ensure(p, n)) return rc;
         p->ingested = false, p->ts_raw = false;  // d_in / d_ts are overwritten (the caller's stamps are normalised already)
         if (int rc = stage_reserve(p->stage, n * 32, p->stream)) return rc;  // one buffer for both arrays
-        if (int rc = staged_upload(p->stage, 0, p->d_in, frame_xyz, n * 24, p->stream)) return rc;
+        if (int rc = staged_upload(p->stage, 0, p->d_in.get(), frame_xyz, n * 24, p->stream)) return rc;
         if (do_deskew)
-            if (int rc = staged_upload(p->stage, n * 24, p->d_ts, timestamps, n * 8, p->stream)) return rc;
+            if (int rc = staged_upload(p->stage, n * 24, p->d_ts.get(), timestamps, n * 8, p->stream)) return rc;
     }
     return pre_run_preprocess(p, n, do_deskew, relative_motion_qt, lidar_to_base_qt, max_range, min_range, dst_buffer, out_n);
 }
@@ -302,20 +285,6 @@ int ingest_validate(const kicp_pre *p, const void *data, size_t n_points, const 
     if (n_points > 0x7FFFFFF0ull / 3) return fail(KICP_ERR_CAPACITY, "cloud too large");
     return KICP_OK;
 }
-// Poll a tagged word of the handle's host record until it reads `want` - the kernels' way of saying "done" without a copy and a
-// stream synchronisation behind them (~15 us of API time per frame).  Bounded: after 2 ms the stream is synchronised instead
-// (whatever is wrong then surfaces as a HIP error, or the word is there after all).
-int wait_word(const volatile unsigned long long *word, unsigned long long want, unsigned long long mask, hipStream_t stream) {
-    const auto t0 = std::chrono::steady_clock::now();
-    for (unsigned spins = 0;; ++spins) {
-        if ((*word & mask) == want) return KICP_OK;
-        if ((spins & 255u) == 255u && std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() > 2.0) break;
-        __builtin_ia32_pause();
-    }
-    HIP_TRY(hipStreamSynchronize(stream));
-    if ((*word & mask) == want) return KICP_OK;
-    return fail(KICP_ERR_HIP, "the pre-step kernels finished without handing their result over");
-}
 // Upload + decode of one message (n_points > 0, <= p->cap_n) on `stream` into (out_xyz, out_ts: stamps in SECONDS) and wait for it:
 // the CPU copies the message into the pinned staging buffer piece by piece and launches k_ingest behind each piece, which decodes
 // the records straight out of host memory (16 bytes per lane for the usual x y z t layout) while the CPU copies the next piece;
@@ -323,15 +292,12 @@ int wait_word(const volatile unsigned long long *word, unsigned long long want, 
 // Round 5 pulled the bytes into HBM (k_pull_bytes per piece), decoded them with one more launch, normalised the stamps with another
 // and copied the extrema back: four stream operations and 6 MB of traffic more per frame.
 constexpr size_t kIngestPiece = 512u << 10;
+constexpr const char *kPreLost = "the pre-step kernels finished without handing their result over";  // (wait_word, 2 ms)
 // d_raw: the message bytes in HBM, where the device cannot read the staging buffer
 int raw_reserve(kicp_pre *p, size_t bytes) {
-    if (bytes <= p->raw_cap) return KICP_OK;
+    if (bytes <= p->d_raw.capacity()) return KICP_OK;
     HIP_TRY(hipDeviceSynchronize());  // (rare: the buffer grows; nothing may still be reading the old one)
-    hipFree(p->d_raw);
-    p->d_raw = nullptr, p->raw_cap = 0;
-    HIP_TRY(hipMalloc(&p->d_raw, bytes + bytes / 4 + 4096));
-    p->raw_cap = bytes + bytes / 4 + 4096;
-    return KICP_OK;
+    return p->d_raw.reserve(bytes + bytes / 4 + 4096);
 }
 int ingest_run(kicp_pre *p, const void *data, size_t n_points, const kicp_cloud_layout &L, const Pose *sensor_pose, hipStream_t stream, double *out_xyz,
                double *out_ts, HostStage &stage, int slot, double *out_lo, double *out_hi) {
@@ -340,7 +306,7 @@ int ingest_run(kicp_pre *p, const void *data, size_t n_points, const kicp_cloud_
     const size_t bytes = n_points * static_cast<size_t>(L.point_step);
     if (int rc = stage_begin(stage, bytes, stream)) return rc;
     if (slot == 0) trace_lap("staging buffer free");
-    const bool direct = stage.dev != nullptr;  // the device reads the staging buffer itself
+    const bool direct = stage.buf.dev() != nullptr;  // the device reads the staging buffer itself
     if (!direct)
         if (int rc = raw_reserve(p, bytes)) return rc;
     IngestParams ip{};
@@ -351,15 +317,15 @@ int ingest_run(kicp_pre *p, const void *data, size_t n_points, const kicp_cloud_
     ip.aligned = (L.point_step % 4 == 0 && L.offset_x % 4 == 0 && L.offset_y % 4 == 0 && L.offset_z % 4 == 0 &&
                   (st == 0 || (L.offset_stamp % stamp_bytes == 0 && L.point_step % stamp_bytes == 0))) ? 1 : 0;
     if (sensor_pose) ip.T = *sensor_pose;
-    ip.out_xyz = out_xyz, ip.out_stamps = out_ts, ip.block_minmax = p->d_block_minmax;
+    ip.out_xyz = out_xyz, ip.out_stamps = out_ts, ip.block_minmax = p->d_block_minmax.get();
     ip.total_blocks = static_cast<uint32_t>((n_points + 255) / 256);
-    ip.ticket = p->d_ticket + slot;
+    ip.ticket = p->d_ticket.get() + slot;
     // a look-ahead message: few workgroups going round its tiles, so that at most ~200 KB of it are on request at any time (k_ingest;
     // 24 / 48 / 64 workgroups and 0.5 / 1 / 4 MB pieces measured within the boxes' noise of each other, 8 and 512 clearly worse)
     static const uint32_t ahead_wgs = [] { const char *e = std::getenv("KICP_PRE_AHEAD_WGS"); return e && *e ? static_cast<uint32_t>(std::max(1, std::atoi(e))) : 48u; }();
     static const size_t ahead_piece = [] { const char *e = std::getenv("KICP_PRE_AHEAD_PIECE_KB"); return (e && *e ? static_cast<size_t>(std::max(64, std::atoi(e))) : 512u) << 10; }();
     const uint32_t wgs_cap = slot == 1 ? ahead_wgs : 0xFFFFFFFFu;
-    unsigned long long *rec = p->h_rec + 8 + 4 * slot;
+    unsigned long long *rec = p->h_rec.get() + 8 + 4 * slot;
     ip.host_rec = rec, ip.seq = ++p->ingest_seq;
     // pieces, so that the GPU decodes piece k while the CPU copies piece k + 1 (a look-ahead message too: as ONE launch behind the
     // whole 2 MB copy it was not there when the next frame asked for it)
@@ -382,12 +348,12 @@ int ingest_run(kicp_pre *p, const void *data, size_t n_points, const kicp_cloud_
     ip.ticket_done = p->ticket_drawn[slot];
     for (size_t first = 0; first < n_points; first += piece_records) {
         const size_t count = std::min(piece_records, n_points - first), off = first * L.point_step, len = count * L.point_step;
-        std::memcpy(stage.p + off, static_cast<const unsigned char *>(data) + off, len);
+        std::memcpy(stage.buf.get() + off, static_cast<const unsigned char *>(data) + off, len);
         if (direct) {
-            ip.raw = stage.dev + off;
+            ip.raw = stage.buf.dev() + off;
         } else {
-            HIP_TRY(hipMemcpyAsync(p->d_raw + off, stage.p + off, len, hipMemcpyHostToDevice, lanes[piece_index & 1u]));
-            ip.raw = p->d_raw + off;
+            HIP_TRY(hipMemcpyAsync(p->d_raw.get() + off, stage.buf.get() + off, len, hipMemcpyHostToDevice, lanes[piece_index & 1u]));
+            ip.raw = p->d_raw.get() + off;
         }
         ip.first = static_cast<uint32_t>(first), ip.n = static_cast<uint32_t>(count);
         hipLaunchKernelGGL(k_ingest, dim3(std::min<uint32_t>(wgs_cap, static_cast<uint32_t>((count + 255) / 256))), dim3(256), 0, lanes[piece_index & 1u], ip);
@@ -395,7 +361,7 @@ int ingest_run(kicp_pre *p, const void *data, size_t n_points, const kicp_cloud_
         if (slot == 0) trace_lap("piece copied, its decode launched");
     }
     HIP_TRY(hipGetLastError());
-    if (int rc = wait_word(rec + 2, ip.seq, ~0ull, stream)) return rc;  // (`data` and the staging buffer are free again behind this)
+    if (int rc = wait_word(rec + 2, ip.seq, ~0ull, stream, 2.0, kPreLost)) return rc;  // (`data` and the staging buffer are free again behind this)
     if (slot == 0) trace_lap("the decoded cloud's record at the host");
     *out_lo = *out_hi = 0.0;
     if (st != 0) *out_lo = ordered_value(rec[0]), *out_hi = ordered_value(rec[1]);
@@ -421,7 +387,7 @@ int ahead_run(kicp_pre *p) {
             HIP_TRY(hipStreamCreateWithFlags(&p->ahead_stream, hipStreamNonBlocking));
         }
     }
-    if (int rc = ingest_run(p, a.data, a.n, a.layout, a.has_pose ? &a.pose : nullptr, p->ahead_stream, p->d_in2, p->d_ts2, p->stage_ahead, 1, &a.lo, &a.hi)) return rc;
+    if (int rc = ingest_run(p, a.data, a.n, a.layout, a.has_pose ? &a.pose : nullptr, p->ahead_stream, p->d_in2.get(), p->d_ts2.get(), p->stage_ahead, 1, &a.lo, &a.hi)) return rc;
     const size_t bytes = a.n * static_cast<size_t>(a.layout.point_step);
     a.edge_bytes = std::min<size_t>(64, bytes);
     std::memcpy(a.edge, a.data, a.edge_bytes);
@@ -472,7 +438,7 @@ int kicp_pre_ingest(kicp_pre *p, const void *data, size_t n_points, const kicp_c
     Pose T{};
     if (sensor_pose_qt) T = pose_from(sensor_pose_qt);
     double lo = 0.0, hi = 0.0;
-    if (int rc = ingest_run(p, data, n_points, L, sensor_pose_qt ? &T : nullptr, p->stream, p->d_in, p->d_ts, p->stage, 0, &lo, &hi)) {
+    if (int rc = ingest_run(p, data, n_points, L, sensor_pose_qt ? &T : nullptr, p->stream, p->d_in.get(), p->d_ts.get(), p->stage, 0, &lo, &hi)) {
         p->ingested = false;
         return rc;
     }
@@ -489,14 +455,10 @@ int scan_table(kicp_pre *p, size_t n, const kicp_laser_scan &s) {
     p->scan_table = false;  // (until the new one is in place)
     p->scan_cs_host.resize(2 * n);
     for (size_t i = 0; i < n; ++i) laser_rules::table_entry(s.angle_min, s.angle_increment, static_cast<uint32_t>(i), p->scan_cs_host[2 * i], p->scan_cs_host[2 * i + 1]);
-    if (n * 16 > p->scan_cs_cap) {
-        hipFree(p->d_scan_cs);  // (nothing reads it: every scan ingest returns after its kernel)
-        p->d_scan_cs = nullptr, p->scan_cs_cap = 0;
-        HIP_TRY(hipMalloc(&p->d_scan_cs, n * 16 + n * 4 + 4096));
-        p->scan_cs_cap = n * 16 + n * 4 + 4096;
-    }
+    if (n * 16 > p->d_scan_cs.capacity())  // (nothing reads the old one: every scan ingest returns after its kernel)
+        if (int rc = p->d_scan_cs.reserve(n * 16 + n * 4 + 4096)) return rc;
     if (n)
-        if (int rc = staged_upload(p->stage, 0, p->d_scan_cs, p->scan_cs_host.data(), n * 16, p->stream)) return rc;
+        if (int rc = staged_upload(p->stage, 0, p->d_scan_cs.get(), p->scan_cs_host.data(), n * 16, p->stream)) return rc;
     p->scan_table = true, p->scan_n = n, p->scan_angle_min = s.angle_min, p->scan_angle_max = s.angle_max;
     return KICP_OK;
 }
@@ -522,28 +484,28 @@ int kicp_pre_ingest_scan(kicp_pre *p, const float *ranges, size_t n_ranges, cons
     // the ranges go up as a cloud's bytes do (ingest_run): into the pinned staging buffer, read from there by the kernel
     const size_t bytes = n_ranges * 4;
     if (int rc = stage_begin(p->stage, bytes, p->stream)) return rc;  // (waits for the table's upload, if there was one)
-    std::memcpy(p->stage.p, ranges, bytes);
+    std::memcpy(p->stage.buf.get(), ranges, bytes);
     ScanParams sp{};
-    if (p->stage.dev) {
-        sp.ranges = reinterpret_cast<const float *>(p->stage.dev);
+    if (p->stage.buf.dev()) {
+        sp.ranges = reinterpret_cast<const float *>(p->stage.buf.dev());
     } else {
         if (int rc = raw_reserve(p, bytes)) return rc;
-        HIP_TRY(hipMemcpyAsync(p->d_raw, p->stage.p, bytes, hipMemcpyHostToDevice, p->stream));
-        sp.ranges = reinterpret_cast<const float *>(p->d_raw);
+        HIP_TRY(hipMemcpyAsync(p->d_raw.get(), p->stage.buf.get(), bytes, hipMemcpyHostToDevice, p->stream));
+        sp.ranges = reinterpret_cast<const float *>(p->d_raw.get());
     }
     const uint32_t tiles = static_cast<uint32_t>((n_ranges + kScanTile - 1) / kScanTile);
     sp.tiles_per_wg = (tiles + kScanMaxWgs - 1) / kScanMaxWgs;
     const uint32_t grid = (tiles + sp.tiles_per_wg - 1) / sp.tiles_per_wg;  // (no workgroup without a tile)
-    sp.cs = p->d_scan_cs, sp.n = static_cast<uint32_t>(n_ranges);
+    sp.cs = reinterpret_cast<const double *>(p->d_scan_cs.get()), sp.n = static_cast<uint32_t>(n_ranges);
     sp.range_min = s.range_min, sp.time_increment = s.time_increment, sp.cutoff = laser_rules::cutoff(range_cutoff, s.range_max);
-    sp.out_xyz = p->d_in, sp.out_stamps = p->d_ts, sp.wg_counts = p->d_block_counts, sp.block_minmax = p->d_block_minmax;
+    sp.out_xyz = p->d_in.get(), sp.out_stamps = p->d_ts.get(), sp.wg_counts = p->d_block_counts.get(), sp.block_minmax = p->d_block_minmax.get();
     p->ticket_drawn[0] += grid;
-    sp.ticket = p->d_ticket, sp.ticket_done = p->ticket_drawn[0];
-    unsigned long long *rec = p->h_rec + 8;
+    sp.ticket = p->d_ticket.get(), sp.ticket_done = p->ticket_drawn[0];
+    unsigned long long *rec = p->h_rec.get() + 8;
     sp.host_rec = rec, sp.seq = ++p->ingest_seq;
     hipLaunchKernelGGL(k_ingest_scan, dim3(grid), dim3(256), 0, p->stream, sp);
     HIP_TRY(hipGetLastError());
-    if (int rc = wait_word(rec + 2, sp.seq, ~0ull, p->stream)) return rc;  // (the staging buffer is free again behind this)
+    if (int rc = wait_word(rec + 2, sp.seq, ~0ull, p->stream, 2.0, kPreLost)) return rc;  // (the staging buffer is free again behind this)
     const size_t kept = static_cast<size_t>(rec[3]);
     p->ingested = true, p->ingested_n = kept, p->ingested_stamps = kept != 0;
     p->ts_raw = kept != 0;
@@ -576,9 +538,9 @@ int kicp_pre_ingested(const kicp_pre *p, double *out_xyz, double *out_stamps, si
     if (int rc = set_device(p->device)) return rc;
     const size_t k = std::min(p->ingested_n, cap_points);
     if (k && out_xyz)
-        if (int rc = staged_download(p->stage, out_xyz, p->d_in, k * 24, p->stream)) return rc;
+        if (int rc = staged_download(p->stage, out_xyz, p->d_in.get(), k * 24, p->stream)) return rc;
     if (k && out_stamps && p->ingested_stamps) {
-        if (int rc = staged_download(p->stage, out_stamps, p->d_ts, k * 8, p->stream)) return rc;
+        if (int rc = staged_download(p->stage, out_stamps, p->d_ts.get(), k * 8, p->stream)) return rc;
         // TimeStampHandler.cpp:121-128 - the two fp64 operations the device applies where it consumes a stamp (kicp_pre.hpp: ts_normalise)
         if (p->ts_raw)
             for (size_t i = 0; i < k; ++i) out_stamps[i] = (out_stamps[i] - p->ts_lo) / (p->ts_hi - p->ts_lo);
@@ -605,22 +567,22 @@ int kicp_pre_voxel_downsample(kicp_pre *p, int src, double voxel_size, int dst, 
     if (slots > p->table_slots || slots > 0x80000000ull || n > slots / 2)  // n > 2^24: float rounding in reserve() lets the reference re-hash mid-way
         return fail(KICP_ERR_CAPACITY, "frame too large for the downsampling table");
     DownsampleParams dp{};
-    dp.in = p->buf[src], dp.n = static_cast<uint32_t>(n), dp.voxel_size = voxel_size, dp.mask = static_cast<uint32_t>(slots - 1);
-    dp.keys = reinterpret_cast<unsigned long long *>(p->d_table);
-    dp.min_index = reinterpret_cast<uint32_t *>(p->d_table + slots * 8);
+    dp.in = p->buf[src].get(), dp.n = static_cast<uint32_t>(n), dp.voxel_size = voxel_size, dp.mask = static_cast<uint32_t>(slots - 1);
+    dp.keys = reinterpret_cast<unsigned long long *>(p->d_table.get());
+    dp.min_index = reinterpret_cast<uint32_t *>(p->d_table.get() + slots * 8);
     dp.order = dp.min_index + slots, dp.home_at = dp.order + slots;
-    dp.block_counts = p->d_block_counts, dp.error = p->d_misc + 1, dp.probe_max = p->d_misc + 2;
+    dp.block_counts = p->d_block_counts.get(), dp.error = p->d_misc.get() + 1, dp.probe_max = p->d_misc.get() + 2;
     // keys free, no winner yet, buckets of the replay free: all bytes 0xFF.  The gather step puts every bucket it has read back into
     // that state, so only the first call after an allocation (or after a failure) clears the table - one stream operation (~5 us) less
     // per call; the layout inside the buffer depends on `slots`, hence "every byte", not "these fields".
-    if (!p->table_clean) HIP_TRY(hipMemsetAsync(p->d_table, 0xFF, p->table_slots * 20, p->stream));
+    if (!p->table_clean) HIP_TRY(hipMemsetAsync(p->d_table.get(), 0xFF, p->table_slots * 20, p->stream));
     p->table_clean = false;  // (until this call is known to have run to its end)
     const uint32_t grid = static_cast<uint32_t>((n + 255) / 256), sgrid = static_cast<uint32_t>((slots + 255) / 256);
     hipLaunchKernelGGL(k_downsample_claim, dim3(grid), dim3(256), 0, p->stream, dp);
     hipLaunchKernelGGL(k_downsample_replay, dim3(sgrid), dim3(256), 0, p->stream, dp);
     const int raw = sgrid <= kFusedScanBlocks ? 1 : 0;
-    if (!raw) hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(1024), 0, p->stream, p->d_block_counts, sgrid, p->d_misc);
-    hipLaunchKernelGGL(k_downsample_gather, dim3(sgrid), dim3(256), 0, p->stream, dp, static_cast<const uint32_t *>(p->d_block_counts), raw, p->d_misc, p->buf[dst]);
+    if (!raw) hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(1024), 0, p->stream, p->d_block_counts.get(), sgrid, p->d_misc.get());
+    hipLaunchKernelGGL(k_downsample_gather, dim3(sgrid), dim3(256), 0, p->stream, dp, static_cast<const uint32_t *>(p->d_block_counts.get()), raw, p->d_misc.get(), p->buf[dst].get());
     HIP_TRY(hipGetLastError());
     const int rc = pre_finish(p, dst, out_n);
     p->table_clean = rc == KICP_OK;
@@ -656,22 +618,22 @@ static int pre_frame_chain(kicp_pre *p, size_t n_in, bool do_deskew, const doubl
     if (!(voxel_a > 0.0) || !(voxel_b > 0.0)) return fail(KICP_ERR_ARG, "bad voxel size");
     // Buffers 1 and 3 take turns: what the PREVIOUS frame left in buffer 1 - the points a map update that was begun with
     // kicp_map_update_pose_device_begin may still be reading - stays untouched, as buffer 3, until the frame after this one.
-    std::swap(p->buf[1], p->buf[3]), std::swap(p->buf_cap[1], p->buf_cap[3]), std::swap(p->buf_n[1], p->buf_n[3]);
+    std::swap(p->buf[1], p->buf[3]), std::swap(p->buf_n[1], p->buf_n[3]);
     p->buf_n[1] = 0;
     for (int b = 0; b < 3; ++b)
         if (int rc = pre_ensure_buf(p, b, n_in)) return rc;
     const size_t slots_up = reference_bucket_count(n_in);
     if (slots_up > p->table_slots || slots_up > 0x80000000ull || n_in > slots_up / 2) return fail(KICP_ERR_CAPACITY, "frame too large for the downsampling table");
     const uint32_t grid = static_cast<uint32_t>((n_in + 255) / 256), sgrid = static_cast<uint32_t>((slots_up + 255) / 256);
-    uint32_t *cnt = p->d_misc + 4;
+    uint32_t *cnt = p->d_misc.get() + 4;
     PreprocessParams pp{};
-    pp.in = p->d_in, pp.timestamps = p->d_ts, pp.n = static_cast<uint32_t>(n_in), pp.deskew = do_deskew ? 1 : 0;
+    pp.in = p->d_in.get(), pp.timestamps = p->d_ts.get(), pp.n = static_cast<uint32_t>(n_in), pp.deskew = do_deskew ? 1 : 0;
     const Pose rel = pose_from(relative_motion_qt);
     pose_log(rel, pp.omega);
     pp.motion_inverse = pose_inverse(rel), pp.lidar_to_base = pose_from(lidar_to_base_qt);
     pp.max_range = max_range, pp.min_range = min_range;
     pp.ts_normalise = p->ts_raw ? 1 : 0, pp.ts_lo = p->ts_lo, pp.ts_hi = p->ts_hi;
-    pp.flags = p->d_flags, pp.staged = p->d_staged, pp.block_counts = p->d_block_counts;
+    pp.flags = p->d_flags.get(), pp.staged = p->d_staged.get(), pp.block_counts = p->d_block_counts.get();
     // the next message, if one was announced, goes up NOW, from a thread of its own: its 2 MB copy into the staging buffer and its
     // launches run beside this thread's queueing of the frame's kernels, the GPU decodes it on a stream of its own
     bool ahead_out = false;
@@ -695,18 +657,18 @@ static int pre_frame_chain(kicp_pre *p, size_t n_in, bool do_deskew, const doubl
         if (int rc = download_reserve(p, n_in * rec_bytes)) return rc;
         bool pushed = false;
         static const int push_wgs = [] { const char *e = std::getenv("KICP_PRE_PUSH_WGS"); return e && *e ? std::atoi(e) : 16; }();
-        if (f32 && !p->copy_host_dev) return fail(KICP_ERR_HIP, "the frame's FLOAT32 records need a host-mapped landing area");
+        if (f32 && !p->copy_host.dev()) return fail(KICP_ERR_HIP, "the frame's FLOAT32 records need a host-mapped landing area");
         if (push_wgs <= 0 && !f32) {  // (A/B: the DMA engine moves the frame, in pieces, queued here instead of by the helper thread)
             if (int rc = download_queue(p, 0, n_in, p->chain_ready)) return rc;
-        } else if (p->copy_host_dev) {
+        } else if (p->copy_host.dev()) {
             // k_push_frame on the download stream, behind the event: the frame crosses PCIe as a kernel's stores, piece by piece, each
             // piece announced in host memory; the helper thread needs no HIP call to follow it
             PushParams q{};
-            q.src = reinterpret_cast<const unsigned char *>(p->buf[0]), q.dst = p->copy_host_dev, q.n_points = p->d_misc + 4;
+            q.src = reinterpret_cast<const unsigned char *>(p->buf[0].get()), q.dst = p->copy_host.dev(), q.n_points = p->d_misc.get() + 4;
             q.piece_bytes = static_cast<uint32_t>(((n_in * rec_bytes + kPushPieces - 1) / kPushPieces + 4095) / 4096 * 4096);
             const uint32_t push_grid = static_cast<uint32_t>(push_wgs > 0 ? push_wgs : 16);
             p->push_drawn += push_grid;
-            q.tickets = p->d_push_tickets, q.ticket_done = p->push_drawn, q.host_flags = p->h_rec + 16, q.seq = ++p->push_seq;
+            q.tickets = p->d_push_tickets.get(), q.ticket_done = p->push_drawn, q.host_flags = p->h_rec.get() + 16, q.seq = ++p->push_seq;
             if (q.seq == 0u) q.seq = ++p->push_seq;
             HIP_TRY(hipStreamWaitEvent(p->copy_stream, p->chain_ready, 0));
             if (f32) hipLaunchKernelGGL(k_push_frame_f32, dim3(push_grid), dim3(256), 0, p->copy_stream, q);
@@ -726,8 +688,8 @@ static int pre_frame_chain(kicp_pre *p, size_t n_in, bool do_deskew, const doubl
     };
     // the tables' arrays laid out for the LARGEST table this handle can hold: every layout agrees on "all bytes 0xFF = clean"
     if (!p->table_clean) {
-        HIP_TRY(hipMemsetAsync(p->d_table, 0xFF, p->table_slots * 20, p->stream));
-        HIP_TRY(hipMemsetAsync(p->d_table2, 0xFF, p->table_slots * 20, p->stream));
+        HIP_TRY(hipMemsetAsync(p->d_table.get(), 0xFF, p->table_slots * 20, p->stream));
+        HIP_TRY(hipMemsetAsync(p->d_table2.get(), 0xFF, p->table_slots * 20, p->stream));
     }
     p->table_clean = false;
     auto table_at = [p](unsigned char *base) {
@@ -749,24 +711,18 @@ static int pre_frame_chain(kicp_pre *p, size_t n_in, bool do_deskew, const doubl
         if (guess == 0) guess = n_in;
         FrameParams f{};
         f.pre = pp;
-        f.A = table_at(p->d_table), f.B = table_at(p->d_table2);
+        f.A = table_at(p->d_table.get()), f.B = table_at(p->d_table2.get());
         f.voxel_a = voxel_a, f.voxel_b = voxel_b;
         f.spec_mask = static_cast<uint32_t>(reference_bucket_count(guess) - 1);
         f.tiles_pts = grid, f.tiles_spec = (f.spec_mask >> 8) + 1u;
-        f.counts1 = p->d_counts1, f.counts2 = p->d_counts2, f.misc = p->d_misc;
-        f.buf0 = p->buf[0], f.buf1 = p->buf[1], f.buf2 = p->buf[2];
-        if (n_in * 24 > p->h_src_cap) {
-            if (p->h_src) HIP_TRY(hipHostFree(p->h_src));
-            p->h_src = p->h_src_dev = nullptr, p->h_src_cap = 0;
-            const size_t want = n_in * 24 + n_in * 6 + 4096;
-            HIP_TRY(pinned_alloc(reinterpret_cast<void **>(&p->h_src), want, hipHostMallocDefault));
-            p->h_src_cap = want;
-            if (hipHostGetDevicePointer(reinterpret_cast<void **>(&p->h_src_dev), p->h_src, 0) != hipSuccess) p->h_src_dev = nullptr, (void)hipGetLastError();
-        }
+        f.counts1 = p->d_counts1.get(), f.counts2 = p->d_counts2.get(), f.misc = p->d_misc.get();
+        f.buf0 = p->buf[0].get(), f.buf1 = p->buf[1].get(), f.buf2 = p->buf[2].get();
+        if (n_in * 24 > p->h_src.capacity())
+            if (int rc = p->h_src.reserve(n_in * 24 + n_in * 6 + 4096, hipHostMallocDefault, false)) return rc;
         static const int src_to_host = [] { const char *e = std::getenv("KICP_PRE_SRC_HOST"); return e && *e ? std::atoi(e) : 1; }();
-        f.host_buf2 = src_to_host ? reinterpret_cast<double *>(p->h_src_dev) : nullptr;
+        f.host_buf2 = src_to_host ? reinterpret_cast<double *>(p->h_src.dev()) : nullptr;
         f.host_buf2_f32 = f32 ? 1 : 0;
-        f.host_rec = p->h_rec, f.seq = ++p->chain_seq;
+        f.host_rec = p->h_rec.get(), f.seq = ++p->chain_seq;
         if (f.seq == 0u) f.seq = ++p->chain_seq;  // (0 is what the device words hold before the first frame)
         // table B's size is known on the device only: its two launches walk the tiles there are with the workgroups they get - as
         // many as the previous frame's second table had tiles (twice that, for a frame that keeps more), sgrid at most
@@ -794,8 +750,8 @@ static int pre_frame_chain(kicp_pre *p, size_t n_in, bool do_deskew, const doubl
         trace_lap("its way back queued");
         const unsigned long long tag = static_cast<unsigned long long>(f.seq) << 32, hi = 0xFFFFFFFF00000000ull;
         for (int w = 4; w >= 0; --w)
-            if (int rc = wait_word(p->h_rec + w, tag, hi, p->stream)) return rc;
-        const volatile unsigned long long *rec = p->h_rec;
+            if (int rc = wait_word(p->h_rec.get() + w, tag, hi, p->stream, 2.0, kPreLost)) return rc;
+        const volatile unsigned long long *rec = p->h_rec.get();
         trace_lap("the chain's record at the host");
         ++p->fused_frames;
         misc[4] = static_cast<uint32_t>(rec[0]), misc[5] = static_cast<uint32_t>(rec[1]), misc[6] = static_cast<uint32_t>(rec[2]);
@@ -808,15 +764,15 @@ static int pre_frame_chain(kicp_pre *p, size_t n_in, bool do_deskew, const doubl
         p->spec_tiles_b = misc[5] ? static_cast<uint32_t>(reference_bucket_count(misc[5]) + 255) / 256u : 1u;
         if (unfused_tail) {  // a guess was wrong: the tables hold claims made under the wrong size; buffer 0 and its count are in place
             ++p->spec_misses;
-            HIP_TRY(hipMemsetAsync(p->d_table, 0xFF, p->table_slots * 20, p->stream));
-            HIP_TRY(hipMemsetAsync(p->d_table2, 0xFF, p->table_slots * 20, p->stream));
+            HIP_TRY(hipMemsetAsync(p->d_table.get(), 0xFF, p->table_slots * 20, p->stream));
+            HIP_TRY(hipMemsetAsync(p->d_table2.get(), 0xFF, p->table_slots * 20, p->stream));
         }
     } else {
         hipLaunchKernelGGL(k_preprocess, dim3(grid), dim3(256), 0, p->stream, pp);
         const int raw_c = grid <= kFusedScanBlocks ? 1 : 0;
-        if (!raw_c) hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(1024), 0, p->stream, p->d_block_counts, grid, cnt + 0);
-        hipLaunchKernelGGL(k_compact, dim3(grid), dim3(256), 0, p->stream, static_cast<const double *>(p->d_staged), static_cast<const uint32_t *>(p->d_flags),
-                           static_cast<const uint32_t *>(p->d_block_counts), raw_c, cnt + 0, static_cast<uint32_t>(n_in), p->buf[0]);
+        if (!raw_c) hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(1024), 0, p->stream, p->d_block_counts.get(), grid, cnt + 0);
+        hipLaunchKernelGGL(k_compact, dim3(grid), dim3(256), 0, p->stream, static_cast<const double *>(p->d_staged.get()), static_cast<const uint32_t *>(p->d_flags.get()),
+                           static_cast<const uint32_t *>(p->d_block_counts.get()), raw_c, cnt + 0, static_cast<uint32_t>(n_in), p->buf[0].get());
         if (int rc = mark_frame_ready()) return rc;
         if (int rc = start_download()) return rc;
     }
@@ -824,20 +780,20 @@ static int pre_frame_chain(kicp_pre *p, size_t n_in, bool do_deskew, const doubl
         // the downsamples as three launches each; every step's survivor count stays on the device as the next step's input count
         const int raw_g = sgrid <= kFusedScanBlocks ? 1 : 0;
         DownsampleParams dp{};
-        const DsTable A = table_at(p->d_table);
+        const DsTable A = table_at(p->d_table.get());
         dp.keys = A.keys, dp.min_index = A.min_index, dp.order = A.order, dp.home_at = A.home_at;
-        dp.block_counts = p->d_block_counts, dp.error = p->d_misc + 1, dp.probe_max = p->d_misc + 2;
+        dp.block_counts = p->d_block_counts.get(), dp.error = p->d_misc.get() + 1, dp.probe_max = p->d_misc.get() + 2;
         for (int stage = 0; stage < 2; ++stage) {
-            dp.in = p->buf[stage], dp.voxel_size = stage == 0 ? voxel_a : voxel_b, dp.n_dev = cnt + stage;
+            dp.in = p->buf[stage].get(), dp.voxel_size = stage == 0 ? voxel_a : voxel_b, dp.n_dev = cnt + stage;
             dp.probe_max_sticky = stage == 0 ? nullptr : dp.probe_max;
             hipLaunchKernelGGL(k_downsample_claim, dim3(grid), dim3(256), 0, p->stream, dp);
             hipLaunchKernelGGL(k_downsample_replay, dim3(sgrid), dim3(256), 0, p->stream, dp);
-            if (!raw_g) hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(1024), 0, p->stream, p->d_block_counts, sgrid, cnt + stage + 1);
-            hipLaunchKernelGGL(k_downsample_gather, dim3(sgrid), dim3(256), 0, p->stream, dp, static_cast<const uint32_t *>(p->d_block_counts), raw_g, cnt + stage + 1,
-                               p->buf[stage + 1]);
+            if (!raw_g) hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(1024), 0, p->stream, p->d_block_counts.get(), sgrid, cnt + stage + 1);
+            hipLaunchKernelGGL(k_downsample_gather, dim3(sgrid), dim3(256), 0, p->stream, dp, static_cast<const uint32_t *>(p->d_block_counts.get()), raw_g, cnt + stage + 1,
+                               p->buf[stage + 1].get());
         }
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(misc, p->d_misc, sizeof misc, hipMemcpyDeviceToHost, p->stream));
+        HIP_TRY(hipMemcpyAsync(misc, p->d_misc.get(), sizeof misc, hipMemcpyDeviceToHost, p->stream));
         HIP_TRY(hipStreamSynchronize(p->stream));
     }
     if (g_trace) {
@@ -848,7 +804,7 @@ static int pre_frame_chain(kicp_pre *p, size_t n_in, bool do_deskew, const doubl
     }
     p->last_max_probe = misc[2];
     if (misc[1]) {
-        HIP_TRY(hipMemsetAsync(p->d_misc + 1, 0, 4, p->stream));
+        HIP_TRY(hipMemsetAsync(p->d_misc.get() + 1, 0, 4, p->stream));
         return fail(KICP_ERR_CAPACITY, "a voxel coordinate left the +-2^20 range of the downsampling table");
     }
     p->table_clean = true;
@@ -893,9 +849,9 @@ static int frame_impl(kicp_pre *p, const double *frame_xyz, size_t n, const doub
         if (int rc = pre_ensure(p, n)) return rc;
         p->ingested = false, p->ts_raw = false;
         if (int rc = stage_reserve(p->stage, n * 32, p->stream)) return rc;
-        if (int rc = staged_upload(p->stage, 0, p->d_in, frame_xyz, n * 24, p->stream)) return rc;
+        if (int rc = staged_upload(p->stage, 0, p->d_in.get(), frame_xyz, n * 24, p->stream)) return rc;
         if (do_deskew)
-            if (int rc = staged_upload(p->stage, n * 24, p->d_ts, timestamps, n * 8, p->stream)) return rc;
+            if (int rc = staged_upload(p->stage, n * 24, p->d_ts.get(), timestamps, n * 8, p->stream)) return rc;
     }
     return pre_frame_chain(p, n, do_deskew, relative_motion_qt, lidar_to_base_qt, max_range, min_range, voxel_a, voxel_b, out_frame_xyz, cap_points, out_counts, f32);
 }
@@ -944,7 +900,7 @@ int kicp_pre_upload(kicp_pre *p, int buffer, const double *xyz, size_t n) {
     if (int rc = set_device(p->device)) return rc;
     if (int rc = pre_ensure_buf(p, buffer, n ? n : 1)) return rc;
     if (n)
-        if (int rc = staged_upload(p->stage, 0, p->buf[buffer], xyz, n * 24, p->stream)) return rc;
+        if (int rc = staged_upload(p->stage, 0, p->buf[buffer].get(), xyz, n * 24, p->stream)) return rc;
     HIP_TRY(hipStreamSynchronize(p->stream));
     p->buf_n[buffer] = n;
     return KICP_OK;
@@ -956,9 +912,9 @@ int kicp_pre_download(const kicp_pre *p, int buffer, double *out_xyz, size_t cap
     const size_t n = p->buf_n[buffer], k = std::min(n, cap_points);
     if (k && out_xyz) {
         if (buffer == 2 && p->src_on_host && !p->src_f32) {  // (the fused chain leaves a copy in host memory)
-            if (int rc = wait_word(p->h_rec + 5, static_cast<unsigned long long>(p->src_seq) << 32, 0xFFFFFFFF00000000ull, p->stream)) return rc;
-            std::memcpy(out_xyz, p->h_src, k * 24);
-        } else if (int rc = staged_download(p->stage, out_xyz, p->buf[buffer], k * 24, p->stream)) return rc;
+            if (int rc = wait_word(p->h_rec.get() + 5, static_cast<unsigned long long>(p->src_seq) << 32, 0xFFFFFFFF00000000ull, p->stream, 2.0, kPreLost)) return rc;
+            std::memcpy(out_xyz, p->h_src.get(), k * 24);
+        } else if (int rc = staged_download(p->stage, out_xyz, p->buf[buffer].get(), k * 24, p->stream)) return rc;
     }
     if (out_n) *out_n = n;
     return KICP_OK;
@@ -971,19 +927,15 @@ int kicp_pre_download_f32(const kicp_pre *cp, int buffer, float *out_xyz, size_t
     const size_t n = p->buf_n[buffer], k = std::min(n, cap_points);
     if (k && out_xyz) {
         if (buffer == 2 && p->src_on_host && p->src_f32) {  // (the fused chain of a kicp_pre_frame*_f32 call left the records in host memory)
-            if (int rc = wait_word(p->h_rec + 5, static_cast<unsigned long long>(p->src_seq) << 32, 0xFFFFFFFF00000000ull, p->stream)) return rc;
-            std::memcpy(out_xyz, p->h_src, k * 12);
+            if (int rc = wait_word(p->h_rec.get() + 5, static_cast<unsigned long long>(p->src_seq) << 32, 0xFFFFFFFF00000000ull, p->stream, 2.0, kPreLost)) return rc;
+            std::memcpy(out_xyz, p->h_src.get(), k * 12);
         } else {
-            if (k * 3 > p->narrow_cap) {
-                hipFree(p->d_narrow);
-                p->d_narrow = nullptr, p->narrow_cap = 0;
-                HIP_TRY(hipMalloc(&p->d_narrow, (k * 3 + k / 4 * 3 + 3072) * 4));
-                p->narrow_cap = k * 3 + k / 4 * 3 + 3072;
-            }
+            if (k * 3 > p->d_narrow.capacity())
+                if (int rc = p->d_narrow.reserve(k * 3 + k / 4 * 3 + 3072)) return rc;
             const size_t words = k * 3;
-            hipLaunchKernelGGL(k_narrow_f32, dim3(static_cast<uint32_t>(std::min<size_t>((words + 255) / 256, 1024))), dim3(256), 0, p->stream, p->buf[buffer], words, p->d_narrow);
+            hipLaunchKernelGGL(k_narrow_f32, dim3(static_cast<uint32_t>(std::min<size_t>((words + 255) / 256, 1024))), dim3(256), 0, p->stream, p->buf[buffer].get(), words, p->d_narrow.get());
             HIP_TRY(hipGetLastError());
-            if (int rc = staged_download(p->stage, out_xyz, p->d_narrow, words * 4, p->stream)) return rc;
+            if (int rc = staged_download(p->stage, out_xyz, p->d_narrow.get(), words * 4, p->stream)) return rc;
         }
     }
     if (out_n) *out_n = n;
@@ -1022,14 +974,8 @@ static int download_begin_impl(kicp_pre *p, int buffer, size_t n, hipEvent_t aft
 }
 // the transfer itself (calling thread, or the helper thread for the chained pre-steps)
 static int download_reserve(kicp_pre *p, size_t bytes) {
-    if (bytes > p->copy_cap) {
-        if (p->copy_host) HIP_TRY(hipHostFree(p->copy_host));
-        p->copy_host = nullptr, p->copy_host_dev = nullptr, p->copy_cap = 0;
-        HIP_TRY(pinned_alloc(reinterpret_cast<void **>(&p->copy_host), bytes + bytes / 2 + (1u << 20), hipHostMallocDefault));
-        p->copy_cap = bytes + bytes / 2 + (1u << 20);
-        if (hipHostGetDevicePointer(reinterpret_cast<void **>(&p->copy_host_dev), p->copy_host, 0) != hipSuccess) p->copy_host_dev = nullptr, (void)hipGetLastError();
-    }
-    return KICP_OK;
+    if (bytes <= p->copy_host.capacity()) return KICP_OK;
+    return p->copy_host.reserve(bytes + bytes / 2 + (1u << 20), hipHostMallocDefault, false);
 }
 static int download_queue(kicp_pre *p, int buffer, size_t n, hipEvent_t after) {
     const size_t bytes = n * 24;
@@ -1043,12 +989,12 @@ static int download_queue(kicp_pre *p, int buffer, size_t n, hipEvent_t after) {
         for (int i = 0; i < kicp_pre::kCopyPieces; ++i) {
             if (!p->copy_piece_done[i]) HIP_TRY(hipEventCreateWithFlags(&p->copy_piece_done[i], hipEventDisableTiming));
             const size_t off = std::min(bytes, piece * i), len = std::min(piece, bytes - off);
-            if (len) HIP_TRY(hipMemcpyAsync(p->copy_host + off, reinterpret_cast<const unsigned char *>(p->buf[buffer]) + off, len, hipMemcpyDeviceToHost, p->copy_stream));
+            if (len) HIP_TRY(hipMemcpyAsync(p->copy_host.get() + off, reinterpret_cast<const unsigned char *>(p->buf[buffer].get()) + off, len, hipMemcpyDeviceToHost, p->copy_stream));
             HIP_TRY(hipEventRecord(p->copy_piece_done[i], p->copy_stream));
         }
         p->copy_piece_bytes = piece;
     } else if (bytes) {
-        HIP_TRY(hipMemcpyAsync(p->copy_host, p->buf[buffer], bytes, hipMemcpyDeviceToHost, p->copy_stream));
+        HIP_TRY(hipMemcpyAsync(p->copy_host.get(), p->buf[buffer].get(), bytes, hipMemcpyDeviceToHost, p->copy_stream));
     }
     HIP_TRY(hipEventRecord(p->copy_done, p->copy_stream));
     return KICP_OK;
@@ -1081,28 +1027,19 @@ static void copy_worker(kicp_pre *p) {
         if (e != hipSuccess) {
         } else if (p->copy_job_push) {
             // k_push_frame's pieces: a flag per piece in host memory, (seq << 32) | bytes - a short piece is the last one
-            const volatile unsigned long long *flags = p->h_rec + 16;
+            const volatile unsigned long long *flags = p->h_rec.get() + 16;
             const unsigned long long tag = static_cast<unsigned long long>(p->copy_push_seq) << 32;
             const auto t0 = std::chrono::steady_clock::now();
             double landed_us[kPushPieces] = {}, copied_us[kPushPieces] = {};
             int pieces_seen = 0;
             for (int i = 0; i < kPushPieces && e == hipSuccess; ++i) {
-                unsigned long long f = 0;
-                for (unsigned spins = 0;; ++spins) {
-                    f = flags[i];
-                    if ((f & 0xFFFFFFFF00000000ull) == tag) break;
-                    if ((spins & 1023u) == 1023u && std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > 2.0) {
-                        e = hipStreamSynchronize(p->copy_stream);  // (something is badly wrong: surface it instead of spinning for ever)
-                        if (e == hipSuccess && (flags[i] & 0xFFFFFFFF00000000ull) != tag) e = hipErrorUnknown;
-                        f = flags[i];
-                        break;
-                    }
-                    __builtin_ia32_pause();
-                }
+                unsigned long long f = 0;  // (2 s for the whole frame: something is badly wrong then - surface it instead of spinning for ever)
+                const double left_ms = 2000.0 - std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+                if (wait_word(flags + i, tag, 0xFFFFFFFF00000000ull, p->copy_stream, left_ms, "a piece of the frame was never announced", &f) != KICP_OK) e = hipErrorUnknown;
                 if (e != hipSuccess) break;
                 const size_t len = static_cast<size_t>(f & 0xFFFFFFFFull), off = static_cast<size_t>(p->copy_push_piece) * i;
                 if (g_trace) landed_us[i] = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
-                if (len && p->copy_dst && off < want) std::memcpy(static_cast<unsigned char *>(p->copy_dst) + off, p->copy_host + off, std::min(len, want - off));
+                if (len && p->copy_dst && off < want) std::memcpy(static_cast<unsigned char *>(p->copy_dst) + off, p->copy_host.get() + off, std::min(len, want - off));
                 if (g_trace) copied_us[i] = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count(), pieces_seen = i + 1;
                 if (len < p->copy_push_piece) break;
             }
@@ -1116,11 +1053,11 @@ static void copy_worker(kicp_pre *p) {
             for (int i = 0; i < kicp_pre::kCopyPieces && e == hipSuccess; ++i) {
                 e = spin_on_event(p->copy_piece_done[i]);
                 const size_t off = std::min(want, p->copy_piece_bytes * i), len = std::min(p->copy_piece_bytes, want - off);
-                if (e == hipSuccess && len) std::memcpy(static_cast<unsigned char *>(p->copy_dst) + off, p->copy_host + off, len);
+                if (e == hipSuccess && len) std::memcpy(static_cast<unsigned char *>(p->copy_dst) + off, p->copy_host.get() + off, len);
             }
         } else {
             e = spin_on_event(p->copy_done);
-            if (e == hipSuccess && want && p->copy_dst) std::memcpy(p->copy_dst, p->copy_host, want);
+            if (e == hipSuccess && want && p->copy_dst) std::memcpy(p->copy_dst, p->copy_host.get(), want);
         }
         lock.lock();
         p->copy_error = e, p->copy_state = 2;
@@ -1159,7 +1096,7 @@ int kicp_pre_download_finish(kicp_pre *p, int buffer, double *out_xyz, size_t ca
             p->copy_buffer = -1;
             return fail(KICP_ERR_ARG, "the frame's FLOAT32 records went to the kicp_pre_frame*_f32 call's out_frame_xyz: collect with NULL");
         }
-        if (k && out_xyz) std::memcpy(out_xyz, p->copy_host, k * 24);
+        if (k && out_xyz) std::memcpy(out_xyz, p->copy_host.get(), k * 24);
     }
     if (out_n) *out_n = p->copy_n;
     p->copy_buffer = -1;
@@ -1168,7 +1105,7 @@ int kicp_pre_download_finish(kicp_pre *p, int buffer, double *out_xyz, size_t ca
 const double *kicp_pre_device_ptr(const kicp_pre *p, int buffer, size_t *out_n) {
     if (!p || buffer < 0 || buffer >= KICP_PRE_BUFFERS) return nullptr;
     if (out_n) *out_n = p->buf_n[buffer];
-    return p->buf[buffer];
+    return p->buf[buffer].get();
 }
 
 }  // extern "C"

@@ -7,14 +7,9 @@ using namespace kicp::host;
 namespace kicp {
 namespace host {
 int ensure_frame(kicp_reg *r, size_t n) {
-    if (n <= r->frame_cap) return KICP_OK;
+    if (n <= r->d_frame.capacity() / 3) return KICP_OK;
     if (int rc = aql_quiesce(r)) return rc;
-    if (r->d_frame) HIP_TRY(hipFree(r->d_frame));
-    r->d_frame = nullptr;
-    const size_t want = n + n / 4 + 1024;
-    HIP_TRY(hipMalloc(&r->d_frame, want * 3 * sizeof(double)));
-    r->frame_cap = want;
-    return KICP_OK;
+    return r->d_frame.reserve((n + n / 4 + 1024) * 3);
 }
 }  // namespace host
 }  // namespace kicp
@@ -47,23 +42,23 @@ template <typename T>
 int fetch_upload(kicp_reg *r, const T *src, size_t n) {
     const size_t bytes = n * 3 * sizeof(T);
     if (int rc = stage_begin(r->stage, bytes, r->stream)) return rc;
-    if (!r->stage.dev) {  // the platform does not map pinned host memory into the device's address space: the DMA engine moves the frame
+    if (!r->stage.buf.dev()) {  // the platform does not map pinned host memory into the device's address space: the DMA engine moves the frame
         if (int rc = stage_end(r->stage, r->stream)) return rc;
-        if (sizeof(T) == sizeof(double)) return staged_upload(r->stage, 0, r->d_frame, src, bytes, r->stream);
+        if (sizeof(T) == sizeof(double)) return staged_upload(r->stage, 0, r->d_frame.get(), src, bytes, r->stream);
         std::vector<double> wide(n * 3);  // (float32: widened on the host first - static_cast<double>(float) is exact)
         for (size_t i = 0; i < wide.size(); ++i) wide[i] = static_cast<double>(src[i]);
-        if (int rc = staged_upload(r->stage, 0, r->d_frame, wide.data(), wide.size() * sizeof(double), r->stream)) return rc;
+        if (int rc = staged_upload(r->stage, 0, r->d_frame.get(), wide.data(), wide.size() * sizeof(double), r->stream)) return rc;
         HIP_TRY(hipStreamSynchronize(r->stream));  // (`wide` goes out of scope; staged_upload has copied it into the pinned buffer, the DMAs may lag)
         return KICP_OK;
     }
     const unsigned char *from = reinterpret_cast<const unsigned char *>(src);
     for (size_t off = 0; off < bytes; off += kFetchPiece) {
         const size_t len = std::min(kFetchPiece, bytes - off);
-        std::memcpy(r->stage.p + off, from + off, len);
+        std::memcpy(r->stage.buf.get() + off, from + off, len);
         const uint32_t count = static_cast<uint32_t>(len / sizeof(T));
         const uint32_t grid = static_cast<uint32_t>((len + 4095) / 4096);  // 256 lanes x 16 bytes
-        hipLaunchKernelGGL(k_fetch_frame<T>, dim3(grid), dim3(256), 0, r->stream, reinterpret_cast<const T *>(r->stage.dev + off),
-                           r->d_frame + off / sizeof(T), count);
+        hipLaunchKernelGGL(k_fetch_frame<T>, dim3(grid), dim3(256), 0, r->stream, reinterpret_cast<const T *>(r->stage.buf.dev() + off),
+                           r->d_frame.get() + off / sizeof(T), count);
     }
     HIP_TRY(hipGetLastError());
     return stage_end(r->stage, r->stream);
@@ -85,18 +80,18 @@ int kicp_reg_create(const kicp_reg_config *config, int device, kicp_reg **out) {
     hipError_t e = hipStreamCreateWithFlags(&r->stream, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipEventCreate(&r->ev0);
     if (e == hipSuccess) e = hipEventCreate(&r->ev1);
-    if (e == hipSuccess) e = hipMalloc(&r->d_state, sizeof(IcpState));
-    if (e == hipSuccess) e = hipMemset(r->d_state, 0, sizeof(IcpState));
-    if (e == hipSuccess) e = pinned_alloc(reinterpret_cast<void **>(&r->rec), sizeof(HostRecord), hipHostMallocMapped | hipHostMallocCoherent);
-    if (e == hipSuccess) std::memset(r->rec, 0, sizeof(HostRecord));
-    if (e == hipSuccess) e = hipHostGetDevicePointer(reinterpret_cast<void **>(&r->d_rec), r->rec, 0);
+    int rc = KICP_OK;
+    if (e == hipSuccess) rc = r->d_state.reserve(1);
+    if (e == hipSuccess && !rc) e = hipMemset(r->d_state.get(), 0, sizeof(IcpState));
+    if (e == hipSuccess && !rc) rc = r->rec.reserve(1, hipHostMallocMapped | hipHostMallocCoherent);
+    if (e == hipSuccess && !rc) std::memset(r->rec.get(), 0, sizeof(HostRecord));
     if (e == hipSuccess) {
         hipDeviceProp_t prop;
         if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) r->num_cus = prop.multiProcessorCount;
     }
-    if (e != hipSuccess) {
+    if (e != hipSuccess || rc) {
         kicp_reg_destroy(r);
-        return fail(KICP_ERR_HIP, std::string("kicp_reg_create: ") + hipGetErrorString(e));
+        return fail(KICP_ERR_HIP, std::string("kicp_reg_create: ") + (rc ? last_error() : hipGetErrorString(e)));
     }
     if (const char *env = std::getenv("KICP_WAIT")) r->wait_mode = std::atoi(env);
     if (const char *env = std::getenv("KICP_QUERY_EVERY")) r->query_every = std::atoi(env);
@@ -121,23 +116,11 @@ void kicp_reg_destroy(kicp_reg *reg) {
     if (reg->stream) hipStreamSynchronize(reg->stream);
     if (reg->shm) kicp_reg_shm_destroy(reg);
     if (reg->p2p_box) kicp_reg_p2p_destroy(reg);
-    if (reg->d_state) hipFree(reg->d_state);
-    if (reg->rec) hipHostFree(reg->rec);
-    if (reg->rows) hipHostFree(reg->rows);
-    if (reg->cmd) hipHostFree(reg->cmd);
     if (reg->bar_frame) reg->aql.free_bar(reg->bar_frame);
-    if (reg->d_trace) hipFree(reg->d_trace);
     if (reg->scans_bar) reg->aql.free_bar(reg->scans_bar);
     else if (reg->d_scans) hipFree(reg->d_scans);
     if (reg->cmd_bar) reg->aql.free_bar(reg->cmd_bar);
     else if (reg->d_cmd_copies) hipFree(reg->d_cmd_copies);
-    reg->stage.release();
-    if (reg->d_partials) hipFree(reg->d_partials);
-    if (reg->d_tickets) hipFree(reg->d_tickets);
-    if (reg->d_group_acc) hipFree(reg->d_group_acc);
-    if (reg->d_frame) hipFree(reg->d_frame);
-    if (reg->d_score_poses) hipFree(reg->d_score_poses);
-    if (reg->d_score_acc) hipFree(reg->d_score_acc);
     if (reg->ev0) hipEventDestroy(reg->ev0);
     if (reg->ev1) hipEventDestroy(reg->ev1);
     for (auto &e : reg->evp)
@@ -180,9 +163,9 @@ int kicp_reg_set_option(kicp_reg *reg, const char *name, double value) {
     else if (k == "small_resident") reg->small_resident = value == 2.0 ? 2 : (value != 0.0 ? 1 : 0);  // 1 adaptive (default), 2 always, 0 never
     else if (k == "small_wave") reg->small_wave = value != 0.0 ? 1 : 0;
     else if (k == "small_trace") {  // debugging aid: per-pass wall-clock stamps of workgroup 0 + host-side phase times
-        if (value != 0.0 && !reg->d_trace) {
-            HIP_TRY(hipMalloc(reinterpret_cast<void **>(&reg->d_trace), 1024 * 4 * sizeof(long long)));
-            HIP_TRY(hipMemset(reg->d_trace, 0, 1024 * 4 * sizeof(long long)));
+        if (value != 0.0 && !reg->d_trace.get()) {
+            if (int rc = reg->d_trace.reserve(1024 * 4)) return rc;
+            HIP_TRY(hipMemset(reg->d_trace.get(), 0, 1024 * 4 * sizeof(long long)));
         }
         reg->trace_pass = value >= 1.0 ? static_cast<uint32_t>(value) : 1u;  // (the value: which pass of a launch is stamped)
         reg->trace_host_us = reg->trace_dev_us = reg->trace_first_us = 0.0, reg->trace_n = reg->trace_first_n = 0;
@@ -238,10 +221,10 @@ double kicp_reg_get_option(const kicp_reg *reg, const char *name) {
     if (k == "trace_device_us") return reg->trace_n ? reg->trace_dev_us / static_cast<double>(reg->trace_n) : 0.0;
     if (k == "trace_first_us") return reg->trace_first_n ? reg->trace_first_us / static_cast<double>(reg->trace_first_n) : 0.0;
     if (k.rfind("trace_stamp_", 0) == 0) {  // trace_stamp_<i>: word i of the device stamps of the LAST call (100 MHz ticks), [workgroup][4]
-        if (!reg->d_trace) return -1.0;
+        if (!reg->d_trace.get()) return -1.0;
         static long long v[4096];
         const int i = std::atoi(k.c_str() + 12);
-        if (i == 0 && hipMemcpy(v, reg->d_trace, sizeof v, hipMemcpyDeviceToHost) != hipSuccess) return -1.0;  // (word 0 refreshes the copy)
+        if (i == 0 && hipMemcpy(v, reg->d_trace.get(), sizeof v, hipMemcpyDeviceToHost) != hipSuccess) return -1.0;  // (word 0 refreshes the copy)
         return (i >= 0 && i < 4096) ? static_cast<double>(v[i]) : -1.0;
     }
     if (k == "small_cmd") return (reg->small_cmd == 1 && reg->cmd_bar) ? 1.0 : (reg->small_cmd ? 0.5 : 0.0);  // 1: BAR copies in use; 0.5: requested, not yet set up
@@ -383,11 +366,11 @@ int kicp_register(kicp_reg *reg, kicp_map *map, const double *frame_xyz, size_t 
         reg->stream_dirty = true;  // (the kernels of earlier calls have long read d_frame: the host had their results)
         if (reg->fetch_frames) {
             if (int rc = fetch_upload<double>(reg, frame_xyz, n)) return rc;
-        } else if (int rc = staged_upload(reg->stage, 0, reg->d_frame, frame_xyz, n * 24, reg->stream)) {
+        } else if (int rc = staged_upload(reg->stage, 0, reg->d_frame.get(), frame_xyz, n * 24, reg->stream)) {
             return rc;
         }
     }
-    return run_registration(reg, map, reg->d_frame, n, last_pose_qt, rel_odom_qt, max_correspondence_distance, out_pose_qt, stats);
+    return run_registration(reg, map, reg->d_frame.get(), n, last_pose_qt, rel_odom_qt, max_correspondence_distance, out_pose_qt, stats);
 }
 // ComputeRobotMotion on a frame that is still float32 - what a PointCloud2 carries on the wire (RosUtils.cpp:30-39 widens every
 // coordinate with static_cast<double> on the host before the reference ever sees it): half the bytes cross PCIe, the widening
@@ -415,7 +398,7 @@ int kicp_register_f32(kicp_reg *reg, kicp_map *map, const float *frame_xyz_f32, 
         reg->stream_dirty = true;
         if (int rc = fetch_upload<float>(reg, frame_xyz_f32, n)) return rc;
     }
-    return run_registration(reg, map, reg->d_frame, n, last_pose_qt, rel_odom_qt, max_correspondence_distance, out_pose_qt, stats);
+    return run_registration(reg, map, reg->d_frame.get(), n, last_pose_qt, rel_odom_qt, max_correspondence_distance, out_pose_qt, stats);
 }
 // KinematicRegistration(const KinematicRegistration &): the reference's struct is a plain copyable aggregate
 // (Registration.hpp:32-50).  A new handle on the same device with the same parameters and tuning options, and workspaces of its
@@ -447,10 +430,11 @@ int kicp_pass_correspondences(kicp_reg *reg, kicp_map *map, const double *frame_
     if (reg->comm || reg->allreduce_fn || reg->shm || reg->d_p2p_table) return fail(KICP_ERR_ARG, "detach the multi-GPU exchange first: correspondences are exported per device");
     if (int rc = set_device(reg->device)) return rc;
     if (int rc = ensure_frame(reg, n)) return rc;
-    if (int rc = staged_upload(reg->stage, 0, reg->d_frame, frame_xyz, n * 24, reg->stream)) return rc;
+    if (int rc = staged_upload(reg->stage, 0, reg->d_frame.get(), frame_xyz, n * 24, reg->stream)) return rc;
     reg->stream_dirty = true;
-    unsigned char *buf = nullptr;
-    HIP_TRY(hipMalloc(&buf, n * 36));
+    DevBuf<unsigned char> corr;
+    if (int rc = corr.reserve(n * 36)) return rc;
+    unsigned char *const buf = corr.get();
     reg->corr_nn = reinterpret_cast<double *>(buf), reg->corr_d2 = reg->corr_nn + 3 * n, reg->corr_index = reinterpret_cast<int32_t *>(reg->corr_d2 + n);
     hipError_t e = hipMemsetAsync(buf, 0, n * 32, reg->stream);
     if (e == hipSuccess) e = hipMemsetAsync(reg->corr_index, 0xFF, n * 4, reg->stream);  // (-1: an empty map returns before any kernel runs)
@@ -458,14 +442,13 @@ int kicp_pass_correspondences(kicp_reg *reg, kicp_map *map, const double *frame_
     reg->cfg.max_num_iterations = 1;
     const double identity[7] = {0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0};
     double pose_out[7];
-    int rc = e == hipSuccess ? run_registration(reg, map, reg->d_frame, n, pose_qt, identity, max_correspondence_distance, pose_out, nullptr) : KICP_ERR_HIP;
+    int rc = e == hipSuccess ? run_registration(reg, map, reg->d_frame.get(), n, pose_qt, identity, max_correspondence_distance, pose_out, nullptr) : KICP_ERR_HIP;
     reg->cfg.max_num_iterations = max_it;
     reg->corr_index = nullptr, reg->corr_d2 = reg->corr_nn = nullptr;
     if (e == hipSuccess && rc >= 0) e = hipStreamSynchronize(reg->stream);
     if (e == hipSuccess && rc >= 0) e = hipMemcpy(out_nn_xyz, buf, n * 24, hipMemcpyDeviceToHost);
     if (e == hipSuccess && rc >= 0) e = hipMemcpy(out_d2, buf + n * 24, n * 8, hipMemcpyDeviceToHost);
     if (e == hipSuccess && rc >= 0) e = hipMemcpy(out_index, buf + n * 32, n * 4, hipMemcpyDeviceToHost);
-    (void)hipFree(buf);
     if (e != hipSuccess) return fail(KICP_ERR_HIP, std::string("kicp_pass_correspondences: ") + hipGetErrorString(e));
     if (rc < 0) return rc;
     for (size_t i = 0; i < n; ++i)
@@ -496,21 +479,21 @@ static int pass_once(kicp_reg *reg, kicp_map *map, const double *frame_xyz, size
     if (int rc = map_sync(map, reg->device, reg->stream)) return rc;
     if (int rc = ensure_frame(reg, n)) return rc;
     if (int rc = ensure_partials(reg, pass_grid(reg, n))) return rc;
-    if (int rc = staged_upload(reg->stage, 0, reg->d_frame, frame_xyz, n * 24, reg->stream)) return rc;
+    if (int rc = staged_upload(reg->stage, 0, reg->d_frame.get(), frame_xyz, n * 24, reg->stream)) return rc;
     const unsigned long long call_id = ++reg->call_id;
     PassParams pp{};
-    pp.partials = reg->d_partials, pp.tickets = reg->d_tickets;
-    pp.src = reg->d_frame, pp.n = static_cast<uint32_t>(n), pp.map = map->mirror.view, pp.tau = max_correspondence_distance;
-    pp.st = reg->d_state, pp.search = search_params(max_correspondence_distance, map->mirror.view.voxel_size);
+    pp.partials = reg->d_partials.get(), pp.tickets = reg->d_tickets.get();
+    pp.src = reg->d_frame.get(), pp.n = static_cast<uint32_t>(n), pp.map = map->mirror.view, pp.tau = max_correspondence_distance;
+    pp.st = reg->d_state.get(), pp.search = search_params(max_correspondence_distance, map->mirror.view.voxel_size);
     set_pose(pp.sol, pose_from(pose_qt));
-    pp.sol.pass = 0, pp.sol.mode = 1, pp.sol.call_id = call_id, pp.sol.rec = reg->d_rec;
+    pp.sol.pass = 0, pp.sol.mode = 1, pp.sol.call_id = call_id, pp.sol.rec = reg->rec.dev();
     if (int rc = launch_pass(reg, pp)) return rc;
-    hipLaunchKernelGGL(k_publish_sums, dim3(1), dim3(64), 0, reg->stream, reg->d_state, reg->d_rec, call_id);
+    hipLaunchKernelGGL(k_publish_sums, dim3(1), dim3(64), 0, reg->stream, reg->d_state.get(), reg->rec.dev(), call_id);
     HIP_TRY(hipGetLastError());
     unsigned long long seq = 0;
     if (int rc = wait_record(reg, call_id, 1, true, &seq)) return rc;
-    for (int i = 0; i < 7; ++i) out_sums[i] = reg->rec->sums[i];
-    if (out_words) HIP_TRY(hipMemcpy(out_words, reg->d_state->reduce, sizeof(long long) * kReduceWords, hipMemcpyDeviceToHost));
+    for (int i = 0; i < 7; ++i) out_sums[i] = reg->rec.get()->sums[i];
+    if (out_words) HIP_TRY(hipMemcpy(out_words, reg->d_state.get()->reduce, sizeof(long long) * kReduceWords, hipMemcpyDeviceToHost));
     return KICP_OK;
 }
 

@@ -89,11 +89,11 @@ int run_batch_resident(kicp_reg *r, kicp_map *map, size_t count, const double *c
     // (the previous batch's kernel has left: the host had its last rows and sent STOP before it returned)
     if (int rc = aql_quiesce(r)) return rc;
     if (r->scans_bar) {
-        for (size_t k = 0; k < count; ++k) r->scans_bar[k] = ScanRef{n[k] ? d_frames[k] : reinterpret_cast<const double *>(r->d_state), n[k]};  // (an idle lane still reads point 0)
+        for (size_t k = 0; k < count; ++k) r->scans_bar[k] = ScanRef{n[k] ? d_frames[k] : reinterpret_cast<const double *>(r->d_state.get()), n[k]};  // (an idle lane still reads point 0)
         _mm_sfence();
     } else {
         std::vector<ScanRef> table(count);
-        for (size_t k = 0; k < count; ++k) table[k] = ScanRef{n[k] ? d_frames[k] : reinterpret_cast<const double *>(r->d_state), n[k]};
+        for (size_t k = 0; k < count; ++k) table[k] = ScanRef{n[k] ? d_frames[k] : reinterpret_cast<const double *>(r->d_state.get()), n[k]};
         r->stream_dirty = true;
         HIP_TRY(hipMemcpyAsync(r->d_scans, table.data(), count * sizeof(ScanRef), hipMemcpyHostToDevice, r->stream));
         HIP_TRY(hipStreamSynchronize(r->stream));  // (`table` is pageable and about to go out of scope)
@@ -102,12 +102,12 @@ int run_batch_resident(kicp_reg *r, kicp_map *map, size_t count, const double *c
     if (!wave) pl.generic = true, pl.lat = true, pl.g = 1, pl.block = 256, pl.grid = grid;
     SmallParams sp{};
     PassParams &pp = sp.p;
-    pp.src = n[0] ? d_frames[0] : reinterpret_cast<const double *>(r->d_state), pp.n = static_cast<uint32_t>(n[0]), pp.map = map->mirror.view, pp.tau = tau, pp.st = r->d_state;
+    pp.src = n[0] ? d_frames[0] : reinterpret_cast<const double *>(r->d_state.get()), pp.n = static_cast<uint32_t>(n[0]), pp.map = map->mirror.view, pp.tau = tau, pp.st = r->d_state.get();
     pp.search = search_params(tau, map->mirror.view.voxel_size);
     pp.dbg = r->dbg;
     pp.sol.max_iterations = max_it, pp.sol.convergence_criterion = r->cfg.convergence_criterion, pp.sol.mode = 4;
-    pp.partials = r->d_partials, pp.tickets = r->d_tickets, pp.group_acc = r->d_group_acc, pp.sol.pub_rows = r->d_rows, pp.sol.call_id = ++r->call_id, pp.sol.rec = r->d_rec;
-    sp.cmd = r->d_cmd, sp.rows = r->d_rows, sp.cmd_dev = r->d_cmd_copies, sp.relay = (r->small_cmd == 1 && r->cmd_bar) ? 0 : 1;
+    pp.partials = r->d_partials.get(), pp.tickets = r->d_tickets.get(), pp.group_acc = r->d_group_acc.get(), pp.sol.pub_rows = r->rows.dev(), pp.sol.call_id = ++r->call_id, pp.sol.rec = r->rec.dev();
+    sp.cmd = r->cmd.dev(), sp.rows = r->rows.dev(), sp.cmd_dev = r->d_cmd_copies, sp.relay = (r->small_cmd == 1 && r->cmd_bar) ? 0 : 1;
     sp.timeout_ticks = static_cast<long long>(std::max(50.0, r->small_timeout_us) * 100.0);
     sp.scans = r->d_scans;
     sp.group_rows = grouped ? 1 : 0;
@@ -186,7 +186,7 @@ int run_batch_resident(kicp_reg *r, kicp_map *map, size_t count, const double *c
                 set_pose(pp.sol, f.loop.T), pp.sol.pass = f.loop.iter;
                 sp.max_passes = cnt, sp.seq_base = r->cmd_seq, sp.scan0 = static_cast<uint32_t>(f.k);
                 r->cmd_seq += cnt;
-                sp.trace = r->d_trace, sp.trace_pass = r->trace_pass;
+                sp.trace = r->d_trace.get(), sp.trace_pass = r->trace_pass;
                 if (int rc = launch_small(r, sp, pl)) return leave(rc);
                 pass = 0, budget = cnt, stop_sent = false;
             } else {

@@ -84,21 +84,22 @@ struct kicp_reg {
     hipStream_t stream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
     hipEvent_t evp[2 * KICP_MAX_LOG_PASSES] = {};  // per-pass events ("timing" == 2), created on first use
-    IcpState *d_state = nullptr;
-    HostRecord *rec = nullptr;    // host-mapped pinned result record (host view)
-    HostRecord *d_rec = nullptr;  // same memory, device view
+    // The plain buffers are owners (DevBuf / PinnedBuf, kicp_internal.hpp) and go with the handle.  Left as raw pointers, with
+    // allocators and lifetimes of their own (kicp_reg_destroy): memory that is BAR memory in one mode and plain device memory in the
+    // other (d_scans / scans_bar, d_cmd_copies / cmd_bar, bar_frame), the peer mailboxes (p2p_box, the IPC mappings, d_p2p_table),
+    // the shared segment, and everything inside AqlDispatcher.
+    DevBuf<IcpState> d_state;
+    PinnedBuf<HostRecord> rec;  // host-mapped result record: get() the host view, dev() the device's
     unsigned long long call_id = 0;
-    unsigned long long *d_partials = nullptr;  // limb rows of the reduction tree
-    unsigned int *d_tickets = nullptr;
-    unsigned long long *d_group_acc = nullptr;  // the resident kernels' group accumulators (finish_pass, ROWS_ONLY)
+    DevBuf<unsigned long long> d_partials;  // limb rows of the reduction tree
+    DevBuf<unsigned int> d_tickets;
+    DevBuf<unsigned long long> d_group_acc;  // the resident kernels' group accumulators (finish_pass, ROWS_ONLY)
     bool acc_dirty = false;       // a resident launch was left before all its passes were collected: accumulators / tickets may hold partial counts
-    size_t partial_blocks = 0;
+    size_t partial_blocks = 0;    // blocks the three serve (ensure_partials: zero while they are being replaced)
     // mode 4 hand-off: tagged rows of the first-level groups in host-mapped pinned memory, added up by the host
-    unsigned long long *rows = nullptr, *d_rows = nullptr;  // host / device view
-    size_t rows_groups = 0;
+    PinnedBuf<unsigned long long> rows;  // kReduceWords per group
     uint32_t tag = 0;       // tag of the last pass (1..65535)
-    double *d_frame = nullptr;  // device copy of host frames
-    size_t frame_cap = 0;
+    DevBuf<double> d_frame;     // device copy of host frames (3 doubles per point)
     HostStage stage;            // pinned staging for transfers from / to caller memory
     // small host frames skip the DMA engine altogether: the CPU writes them through the PCIe BAR into host-visible HBM
     double *bar_frame = nullptr;  // (the same address on both sides)
@@ -162,7 +163,7 @@ struct kicp_reg {
     std::map<int, const AqlKernel *> aql_kernels;
     // small-scan path (kicp_small.hpp): the command line the resident kernel polls (host-mapped, 64-byte aligned), the
     // sequence number of the last command issued, and the knobs
-    unsigned long long *cmd = nullptr, *d_cmd = nullptr;
+    PinnedBuf<unsigned long long> cmd;
     unsigned long long *d_cmd_copies = nullptr;  // kCmdReplicas copies of the command line in device memory
     unsigned long long *cmd_bar = nullptr;       // host view of the same copies when they live in BAR-writable HBM (option "small_cmd" 1)
     int small_cmd = 1;            // option "small_cmd": 1 (default) the host writes the command copies through the BAR; 0 workgroup 0 relays the host line
@@ -199,13 +200,12 @@ struct kicp_reg {
     int last_resident_passes = 0; // passes of the last call that a resident launch of the GENERIC kernel served (get-only "resident_passes")
     int small_prev_iters = 2;     // iterations of the previous small-path call: a scan that converged at once makes the next launch leave after its first pass
     // kicp_score_poses (kicp_score.hip): the uploaded poses and their accumulator rows, a batch of poses at a time
-    double *d_score_poses = nullptr;
-    unsigned long long *d_score_acc = nullptr;
-    size_t score_cap = 0;             // poses the two buffers hold
+    DevBuf<double> d_score_poses;            // 7 doubles per pose
+    DevBuf<unsigned long long> d_score_acc;  // kScoreWords per pose
     double score_chunk = 8388608.0;   // option "score_chunk": queries (pose x point pairs) one launch of k_score_poses may serve
     int score_launches = 0;           // launches the last kicp_score_poses call used (get-only "score_launches")
     uint32_t trace_pass = 1;      // the pass of a launch the stamps are taken on (the option's value)
-    long long *d_trace = nullptr; // option "small_trace": device buffer of the kernel's per-pass wall-clock stamps
+    DevBuf<long long> d_trace;    // option "small_trace": device buffer of the kernel's per-pass wall-clock stamps
     double trace_host_us = 0.0, trace_dev_us = 0.0, trace_first_us = 0.0;  // host: rows seen -> command sent; device: command sent -> rows seen; launch -> first rows
     unsigned long long trace_n = 0, trace_first_n = 0;
 };

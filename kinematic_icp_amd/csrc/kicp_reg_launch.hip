@@ -141,33 +141,26 @@ int launch_pass(kicp_reg *r, const PassParams &p, bool allow_aql) {
 int ensure_partials(kicp_reg *r, size_t blocks) {
     if (blocks <= r->partial_blocks) return KICP_OK;
     if (int rc = aql_quiesce(r)) return rc;
-    if (r->d_partials) HIP_TRY(hipFree(r->d_partials));
-    if (r->d_tickets) HIP_TRY(hipFree(r->d_tickets));
-    if (r->d_group_acc) HIP_TRY(hipFree(r->d_group_acc));
-    r->d_partials = nullptr, r->d_tickets = nullptr, r->d_group_acc = nullptr;
+    r->partial_blocks = 0;  // (until all three are in place)
     const size_t want = blocks + blocks / 2 + 64, groups = want / kGroup + 2;
-    HIP_TRY(hipMalloc(&r->d_partials, (want + groups) * kReduceWords * sizeof(unsigned long long)));
-    HIP_TRY(hipMalloc(&r->d_tickets, groups * kTicketStride * sizeof(unsigned int)));
-    HIP_TRY(hipMalloc(&r->d_group_acc, 2 * groups * kAccStride * sizeof(unsigned long long)));  // (two sets: an ordinary launch takes the set of its tag's parity)
+    if (int rc = r->d_partials.reserve((want + groups) * kReduceWords)) return rc;
+    if (int rc = r->d_tickets.reserve(groups * kTicketStride)) return rc;
+    if (int rc = r->d_group_acc.reserve(2 * groups * kAccStride)) return rc;  // (two sets: an ordinary launch takes the set of its tag's parity)
     r->stream_dirty = true;
-    HIP_TRY(hipMemsetAsync(r->d_tickets, 0, groups * kTicketStride * sizeof(unsigned int), r->stream));
-    HIP_TRY(hipMemsetAsync(r->d_group_acc, 0, 2 * groups * kAccStride * sizeof(unsigned long long), r->stream));
-    HIP_TRY(hipMemsetAsync(r->d_partials, 0, (want + groups) * kReduceWords * sizeof(unsigned long long), r->stream));  // tag 0 = never valid
+    HIP_TRY(hipMemsetAsync(r->d_tickets.get(), 0, groups * kTicketStride * sizeof(unsigned int), r->stream));
+    HIP_TRY(hipMemsetAsync(r->d_group_acc.get(), 0, 2 * groups * kAccStride * sizeof(unsigned long long), r->stream));
+    HIP_TRY(hipMemsetAsync(r->d_partials.get(), 0, (want + groups) * kReduceWords * sizeof(unsigned long long), r->stream));  // tag 0 = never valid
     r->partial_blocks = want;
     return KICP_OK;
 }
 // host-mapped rows of the first-level groups (mode 4)
 int ensure_rows(kicp_reg *r, size_t groups) {
-    if (groups <= r->rows_groups) return KICP_OK;
+    if (groups <= r->rows.capacity() / kReduceWords) return KICP_OK;
     if (int rc = aql_quiesce(r)) return rc;
     HIP_TRY(hipStreamSynchronize(r->stream));
-    if (r->rows) HIP_TRY(hipHostFree(r->rows));
-    r->rows = nullptr, r->d_rows = nullptr, r->rows_groups = 0;
     const size_t want = groups + groups / 2 + 64;
-    HIP_TRY(pinned_alloc(reinterpret_cast<void **>(&r->rows), want * kReduceWords * sizeof(unsigned long long), hipHostMallocMapped | hipHostMallocCoherent));
-    std::memset(r->rows, 0, want * kReduceWords * sizeof(unsigned long long));
-    HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void **>(&r->d_rows), r->rows, 0));
-    r->rows_groups = want;
+    if (int rc = r->rows.reserve(want * kReduceWords, hipHostMallocMapped | hipHostMallocCoherent)) return rc;
+    std::memset(r->rows.get(), 0, want * kReduceWords * sizeof(unsigned long long));
     return KICP_OK;
 }
 // next pass tag; when the 16-bit tag wraps, every buffer that holds tagged words is cleared so that a word left over
@@ -177,10 +170,10 @@ int next_tag(kicp_reg *r, uint32_t *tag) {
         if (int rc = aql_quiesce(r)) return rc;
         r->stream_dirty = true;
         HIP_TRY(hipStreamSynchronize(r->stream));
-        if (r->rows) std::memset(r->rows, 0, r->rows_groups * kReduceWords * sizeof(unsigned long long));
-        if (r->d_partials) {
+        if (r->rows.get()) std::memset(r->rows.get(), 0, r->rows.capacity() * sizeof(unsigned long long));
+        if (r->d_partials.get()) {
             const size_t groups = r->partial_blocks / kGroup + 2;
-            HIP_TRY(hipMemsetAsync(r->d_partials, 0, (r->partial_blocks + groups) * kReduceWords * sizeof(unsigned long long), r->stream));
+            HIP_TRY(hipMemsetAsync(r->d_partials.get(), 0, (r->partial_blocks + groups) * kReduceWords * sizeof(unsigned long long), r->stream));
         }
         r->tag = 0;
     }
@@ -189,7 +182,7 @@ int next_tag(kicp_reg *r, uint32_t *tag) {
 }
 // enqueue the collective between the limb reduction and the solve (multi-GPU only)
 int enqueue_allreduce(kicp_reg *r) {
-    long long *buf = r->d_state->reduce;
+    long long *buf = r->d_state.get()->reduce;
     if (r->allreduce_fn) {
         if (r->allreduce_fn(r->allreduce_user, buf, kReduceWords, static_cast<void *>(r->stream)) != 0)
             return fail(KICP_ERR_COMM, "user all-reduce callback failed");
@@ -203,7 +196,7 @@ int enqueue_allreduce(kicp_reg *r) {
 // wait until the record carries `call_id` with at least `min_iter` completed iterations (or its done bit);
 // returns the observed seq.  Polls host-mapped memory; falls back to a stream sync when asked to or on a fault.
 int wait_record(kicp_reg *r, unsigned long long call_id, unsigned min_iter, bool need_done, unsigned long long *seq_out) {
-    volatile unsigned long long *seq = &r->rec->seq;
+    volatile unsigned long long *seq = &r->rec.get()->seq;
     auto ready = [&](unsigned long long s) {
         return (s >> 16) == call_id && ((s & 0x8000ull) || (!need_done && (s & 0x7FFFull) >= min_iter));
     };
@@ -257,7 +250,7 @@ int wait_rows(kicp_reg *r, size_t groups, uint32_t tag, long long out_words[kRed
     unsigned long long spins = 0;
     const Deadline deadline;
     for (size_t g = 0; g < groups; ++g) {
-        const unsigned long long *row = r->rows + (first_row + g) * kReduceWords;
+        const unsigned long long *row = r->rows.get() + (first_row + g) * kReduceWords;
         long long v[kReduceWords];
         for (;;) {
             bool ok = true;
@@ -348,10 +341,9 @@ SmallPlan small_plan(const kicp_reg *r, size_t n) {
     return pl;
 }
 int ensure_cmd(kicp_reg *r) {
-    if (!r->cmd) {
-        HIP_TRY(pinned_alloc(reinterpret_cast<void **>(&r->cmd), kPipeSlots * kCmdWords * sizeof(unsigned long long), hipHostMallocMapped | hipHostMallocCoherent));
-        std::memset(r->cmd, 0, kPipeSlots * kCmdWords * sizeof(unsigned long long));
-        HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void **>(&r->d_cmd), r->cmd, 0));
+    if (!r->cmd.get()) {
+        if (int rc = r->cmd.reserve(kPipeSlots * kCmdWords, hipHostMallocMapped | hipHostMallocCoherent)) return rc;
+        std::memset(r->cmd.get(), 0, kPipeSlots * kCmdWords * sizeof(unsigned long long));
     }
     const size_t bytes = static_cast<size_t>(kCmdReplicas) * kCmdStrideWords * sizeof(unsigned long long);
     if (r->small_cmd == 1 && !r->cmd_bar) {  // the copies in host-writable HBM: needs the HSA side of the AQL dispatcher
@@ -398,8 +390,8 @@ void send_command(kicp_reg *r, unsigned long long seq, uint32_t op, const Pose &
         _mm_sfence();
         return;
     }
-    for (int i = 0; i < 7; ++i) __atomic_store_n(r->cmd + slot + i, w[i], __ATOMIC_RELAXED);
-    __atomic_store_n(r->cmd + slot + 7, w[7], __ATOMIC_RELEASE);
+    for (int i = 0; i < 7; ++i) __atomic_store_n(r->cmd.get() + slot + i, w[i], __ATOMIC_RELAXED);
+    __atomic_store_n(r->cmd.get() + slot + 7, w[7], __ATOMIC_RELEASE);
 }
 int launch_small(kicp_reg *r, const SmallParams &sp, const SmallPlan &pl) {
     const int b = pl.block, g = pl.g;
@@ -449,7 +441,7 @@ int wait_rows_small(kicp_reg *r, uint32_t grid, uint32_t tag, uint32_t parity, l
     unsigned long long spins = 0;
     const Deadline deadline;
     for (uint32_t g = 0; g < grid; ++g) {
-        const unsigned long long *row = r->rows + (static_cast<size_t>(parity) * grid + g) * kSmallRowWords;
+        const unsigned long long *row = r->rows.get() + (static_cast<size_t>(parity) * grid + g) * kSmallRowWords;
         unsigned long long w[kSmallRowWords];
         // the rows land within a few microseconds of each other, and every line the device has just written misses the CPU's
         // caches: ask for the lines a few rows ahead while this row is being checked

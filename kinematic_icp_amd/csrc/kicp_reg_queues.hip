@@ -48,7 +48,7 @@ struct BatchFlight {
 int flight_rows(BatchFlight &f, long long out_words[kReduceWords]) {
     kicp_reg *h = f.h;
     if (f.via_comm) {  // the all-reduced totals arrive as ONE record behind the collective (k_publish_words)
-        if (__atomic_load_n(&h->rec->seq, __ATOMIC_ACQUIRE) != f.comm_seq) {
+        if (__atomic_load_n(&h->rec.get()->seq, __ATOMIC_ACQUIRE) != f.comm_seq) {
             if (++f.polls % 256u == 0u) {
                 const hipError_t q = hipStreamQuery(h->stream);
                 if (q != hipSuccess && q != hipErrorNotReady) return fail(KICP_ERR_HIP, std::string("stream fault: ") + hipGetErrorString(q));
@@ -56,14 +56,14 @@ int flight_rows(BatchFlight &f, long long out_words[kReduceWords]) {
             }
             return 0;
         }
-        for (int i = 0; i < kReduceWords; ++i) out_words[i] = h->rec->words[i];
+        for (int i = 0; i < kReduceWords; ++i) out_words[i] = h->rec.get()->words[i];
         out_words[kNumLimbs] = out_words[kNumLimbs] != 0 ? 1 : 0;
         return 1;
     }
     const uint32_t tag = f.tag;
     const int row_words = f.own_rows ? kSmallRowWords : kReduceWords;
     for (; f.row_next < f.rows; ++f.row_next) {
-        const unsigned long long *row = h->rows + f.row_next * row_words;
+        const unsigned long long *row = h->rows.get() + f.row_next * row_words;
         unsigned long long w[kReduceWords];
         bool ok = true;
         for (int i = 0; i < row_words; ++i) {
@@ -115,8 +115,8 @@ int flight_launch(BatchFlight &f, const kicp_map *map, const double *d_frame, si
     for (auto &w : f.words) w = 0;
     for (auto &t : f.total) t = 0;
     PassParams &pp = f.small ? f.sp.p : f.pp;
-    if (n == 0) d_frame = reinterpret_cast<const double *>(h->d_state);  // (an empty shard: the one workgroup's lanes are all idle, but an idle lane still reads point 0)
-    pp.src = d_frame, pp.n = static_cast<uint32_t>(n), pp.map = map->mirror.view, pp.tau = tau, pp.st = h->d_state;
+    if (n == 0) d_frame = reinterpret_cast<const double *>(h->d_state.get());  // (an empty shard: the one workgroup's lanes are all idle, but an idle lane still reads point 0)
+    pp.src = d_frame, pp.n = static_cast<uint32_t>(n), pp.map = map->mirror.view, pp.tau = tau, pp.st = h->d_state.get();
     pp.search = search_params(tau, map->mirror.view.voxel_size);
     pp.dbg = h->dbg;
     SolveParams &sol = pp.sol;
@@ -133,13 +133,13 @@ int flight_launch(BatchFlight &f, const kicp_map *map, const double *d_frame, si
             if (int rc = ensure_partials(h, kPipeSlots * f.pl.grid)) return rc;
             if (int rc = ensure_rows(h, kPipeSlots * f.rows)) return rc;
             if (int rc = clear_stale_tickets(h)) return rc;
-            pp.group_acc = h->d_group_acc, sol.pub_rows = h->d_rows, sol.rec = h->d_rec;
+            pp.group_acc = h->d_group_acc.get(), sol.pub_rows = h->rows.dev(), sol.rec = h->rec.dev();
         }
         if (int rc = ensure_cmd(h)) return rc;
         if (int rc = next_tag(h, &f.tag)) return rc;
         SmallParams &sp = f.sp;
         sp.group_rows = f.own_rows ? 0 : 1;
-        sp.cmd = h->d_cmd, sp.rows = h->d_rows, sp.cmd_dev = h->d_cmd_copies, sp.relay = (h->small_cmd == 1 && h->cmd_bar) ? 0 : 1;
+        sp.cmd = h->cmd.dev(), sp.rows = h->rows.dev(), sp.cmd_dev = h->d_cmd_copies, sp.relay = (h->small_cmd == 1 && h->cmd_bar) ? 0 : 1;
         sp.timeout_ticks = 5000, sp.trace = nullptr, sp.scans = nullptr, sp.rotate = 0;
         sp.tag0 = f.tag, sp.max_passes = 1, sp.seq_base = h->cmd_seq;
         h->cmd_seq += 1;
@@ -151,8 +151,8 @@ int flight_launch(BatchFlight &f, const kicp_map *map, const double *d_frame, si
     if (int rc = ensure_partials(h, grid)) return rc;
     if (int rc = ensure_rows(h, f.rows)) return rc;
     if (int rc = clear_stale_tickets(h)) return rc;  // (nothing to do unless an earlier call left a pass uncollected)
-    pp.partials = h->d_partials, pp.tickets = h->d_tickets, pp.group_acc = h->d_group_acc;
-    sol.call_id = ++h->call_id, sol.rec = h->d_rec, sol.pub_rows = h->d_rows;
+    pp.partials = h->d_partials.get(), pp.tickets = h->d_tickets.get(), pp.group_acc = h->d_group_acc.get();
+    sol.call_id = ++h->call_id, sol.rec = h->rec.dev(), sol.pub_rows = h->rows.dev();
     if (int rc = next_tag(h, &sol.tag)) return rc;
     f.tag = sol.tag;
     f.since = Deadline();
@@ -161,7 +161,7 @@ int flight_launch(BatchFlight &f, const kicp_map *map, const double *d_frame, si
         f.comm_seq = (sol.call_id << 16) | static_cast<unsigned long long>(f.loop.iter + 1);
         if (int rc = launch_pass(h, pp, false)) return rc;
         if (int rc = enqueue_allreduce(h)) return rc;
-        hipLaunchKernelGGL(k_publish_words, dim3(1), dim3(64), 0, h->stream, h->d_state, h->d_rec, sol.call_id, f.loop.iter);
+        hipLaunchKernelGGL(k_publish_words, dim3(1), dim3(64), 0, h->stream, h->d_state.get(), h->rec.dev(), sol.call_id, f.loop.iter);
         HIP_TRY(hipGetLastError());
         return KICP_OK;
     }

@@ -14,12 +14,12 @@ namespace host {
 // or the host left a launch with passes still out: counts of a round that never completed - the call ended first - may be left
 // behind in the groups' accumulators (and tickets).  Clear them before they are counted into this call's passes.
 int clear_stale_tickets(kicp_reg *r) {
-    if ((__atomic_load_n(&r->rec->reserved[0], __ATOMIC_RELAXED) == 0u && !r->acc_dirty) || !r->d_tickets) return KICP_OK;
+    if ((__atomic_load_n(&r->rec.get()->reserved[0], __ATOMIC_RELAXED) == 0u && !r->acc_dirty) || !r->d_tickets.get()) return KICP_OK;
     if (int rc = aql_quiesce(r)) return rc;
     r->stream_dirty = true;
-    HIP_TRY(hipMemsetAsync(r->d_tickets, 0, (r->partial_blocks / kGroup + 2) * kTicketStride * sizeof(unsigned int), r->stream));
-    HIP_TRY(hipMemsetAsync(r->d_group_acc, 0, 2 * (r->partial_blocks / kGroup + 2) * kAccStride * sizeof(unsigned long long), r->stream));
-    __atomic_store_n(&r->rec->reserved[0], 0u, __ATOMIC_RELAXED);
+    HIP_TRY(hipMemsetAsync(r->d_tickets.get(), 0, (r->partial_blocks / kGroup + 2) * kTicketStride * sizeof(unsigned int), r->stream));
+    HIP_TRY(hipMemsetAsync(r->d_group_acc.get(), 0, 2 * (r->partial_blocks / kGroup + 2) * kAccStride * sizeof(unsigned long long), r->stream));
+    __atomic_store_n(&r->rec.get()->reserved[0], 0u, __ATOMIC_RELAXED);
     r->acc_dirty = false;
     return KICP_OK;
 }
@@ -42,15 +42,15 @@ int run_small(kicp_reg *r, kicp_map *map, const double *d_frame, size_t n, const
     if (int rc = ensure_cmd(r)) return rc;
     SmallParams sp{};
     PassParams &pp = sp.p;
-    pp.src = d_frame, pp.n = static_cast<uint32_t>(n), pp.map = map->mirror.view, pp.tau = tau, pp.st = r->d_state;
+    pp.src = d_frame, pp.n = static_cast<uint32_t>(n), pp.map = map->mirror.view, pp.tau = tau, pp.st = r->d_state.get();
     pp.search = search_params(tau, map->mirror.view.voxel_size);
     pp.sol.max_iterations = max_it, pp.sol.convergence_criterion = r->cfg.convergence_criterion, pp.sol.mode = 4;
     pp.dbg = r->dbg;  // (0, or 14: the in-process A/B switch of the plain launch's hand-over)
     pp.corr_index = r->corr_index, pp.corr_d2 = r->corr_d2, pp.corr_nn = r->corr_nn;  // (kicp_pass_correspondences; nullptr otherwise)
-    if (grouped) pp.partials = r->d_partials, pp.tickets = r->d_tickets, pp.group_acc = r->d_group_acc, pp.sol.pub_rows = r->d_rows, pp.sol.call_id = ++r->call_id, pp.sol.rec = r->d_rec;
+    if (grouped) pp.partials = r->d_partials.get(), pp.tickets = r->d_tickets.get(), pp.group_acc = r->d_group_acc.get(), pp.sol.pub_rows = r->rows.dev(), pp.sol.call_id = ++r->call_id, pp.sol.rec = r->rec.dev();
     if (grouped)
         if (int rc = clear_stale_tickets(r)) return rc;
-    sp.cmd = r->d_cmd, sp.rows = r->d_rows, sp.cmd_dev = r->d_cmd_copies, sp.relay = (r->small_cmd == 1 && r->cmd_bar) ? 0 : 1;
+    sp.cmd = r->cmd.dev(), sp.rows = r->rows.dev(), sp.cmd_dev = r->d_cmd_copies, sp.relay = (r->small_cmd == 1 && r->cmd_bar) ? 0 : 1;
     sp.group_rows = grouped ? 1 : 0;
     sp.timeout_ticks = static_cast<long long>(std::max(50.0, r->small_timeout_us) * 100.0);  // 100 MHz wall clock
     HostLoop loop;
@@ -77,7 +77,7 @@ int run_small(kicp_reg *r, kicp_map *map, const double *d_frame, size_t n, const
         set_pose(pp.sol, loop.T), pp.sol.pass = loop.iter;
         sp.max_passes = cnt, sp.seq_base = r->cmd_seq;
         r->cmd_seq += cnt;  // every sequence number this launch may wait for is now spent
-        sp.trace = r->d_trace, sp.trace_pass = r->trace_pass;
+        sp.trace = r->d_trace.get(), sp.trace_pass = r->trace_pass;
         auto t_sent = std::chrono::steady_clock::now();
         const bool plain = pl.generic && cnt == 1;
         const int iter_at_launch = loop.iter;
@@ -104,7 +104,7 @@ int run_small(kicp_reg *r, kicp_map *map, const double *d_frame, size_t n, const
             }
             const auto t_rows = std::chrono::steady_clock::now();
             trace_lap("rows of a pass at the host");
-            if (r->d_trace) {
+            if (r->d_trace.get()) {
                 const double us = std::chrono::duration<double, std::micro>(t_rows - t_sent).count();
                 if (k == 0) r->trace_first_us += us, ++r->trace_first_n;
                 else r->trace_dev_us += us, ++r->trace_n;
@@ -129,7 +129,7 @@ int run_small(kicp_reg *r, kicp_map *map, const double *d_frame, size_t n, const
                 r->debug_stall_us = 0.0;
             }
             send_command(r, sp.seq_base + k + 1, finished ? kCmdStop : kCmdContinue, loop.T);
-            if (r->d_trace) {
+            if (r->d_trace.get()) {
                 t_sent = std::chrono::steady_clock::now();
                 r->trace_host_us += std::chrono::duration<double, std::micro>(t_sent - t_rows).count();
             }
@@ -189,15 +189,15 @@ int run_registration_impl(kicp_reg *r, kicp_map *map, const double *d_frame, siz
     const unsigned long long call_id = ++r->call_id;
 
     PassParams pp{};
-    pp.src = d_frame, pp.n = static_cast<uint32_t>(n), pp.map = map->mirror.view, pp.tau = tau, pp.st = r->d_state;
+    pp.src = d_frame, pp.n = static_cast<uint32_t>(n), pp.map = map->mirror.view, pp.tau = tau, pp.st = r->d_state.get();
     pp.search = search_params(tau, map->mirror.view.voxel_size);
-    pp.partials = r->d_partials, pp.tickets = r->d_tickets, pp.group_acc = r->d_group_acc;
+    pp.partials = r->d_partials.get(), pp.tickets = r->d_tickets.get(), pp.group_acc = r->d_group_acc.get();
     pp.dbg = r->dbg;
     pp.corr_index = r->corr_index, pp.corr_d2 = r->corr_d2, pp.corr_nn = r->corr_nn;  // (kicp_pass_correspondences; nullptr otherwise)
     SolveParams &sp = pp.sol;
     set_pose(sp, T0), sp.max_iterations = max_it, sp.convergence_criterion = r->cfg.convergence_criterion;
     sp.adaptive = r->cfg.use_adaptive_odometry_regularization, sp.fixed_regularization = r->cfg.fixed_regularization;
-    sp.mode = multi ? 1 : 0, sp.call_id = call_id, sp.rec = r->d_rec;
+    sp.mode = multi ? 1 : 0, sp.call_id = call_id, sp.rec = r->rec.dev();
 
     if (r->timing) HIP_TRY(hipEventRecord(r->ev0, r->stream));
     const bool pass_events = r->timing == 2;
@@ -208,7 +208,7 @@ int run_registration_impl(kicp_reg *r, kicp_map *map, const double *d_frame, siz
         // ---- one launch per iteration, the pose travels as a kernel argument, the host solves (Registration.cpp:119-125,159-167,
         //      181-184).  (Round 6: the device-side solve - last workgroup of the launch, stepped or queued up front - is gone: it
         //      lost every A/B since round 2 and no exchange needs it.)
-        HostRecord *rec = r->rec;
+        HostRecord *rec = r->rec.get();
         HostLoop loop;
         loop.T = T0;
         int passes_run = 0;
@@ -236,13 +236,13 @@ int run_registration_impl(kicp_reg *r, kicp_map *map, const double *d_frame, siz
                 mine_host = r->shm + (step & 1) * r->nranks + r->rank;
                 sp.pub_value = shm_value = step + 1;
             } else {
-                sp.pub_words = r->d_rec->words, sp.pub_seq = &r->d_rec->seq;
+                sp.pub_words = r->rec.dev()->words, sp.pub_seq = &r->rec.dev()->seq;
                 sp.pub_value = (call_id << 16) | static_cast<unsigned long long>(it + 1);
             }
             if (rows_mode) {
                 if (int rc = ensure_rows(r, groups)) return rc;
                 if (int rc = next_tag(r, &sp.tag)) return rc;
-                sp.pub_rows = r->d_rows;
+                sp.pub_rows = r->rows.dev();
             } else if (p2p_rows) {
                 if (int rc = next_tag(r, &sp.tag)) return rc;  // (the workgroups' rows inside a group are tagged like mode 4's)
             }
@@ -253,7 +253,7 @@ int run_registration_impl(kicp_reg *r, kicp_map *map, const double *d_frame, siz
             if (ev) HIP_TRY(hipEventRecord(r->evp[2 * it + 1], r->stream));
             if (multi) {
                 if (int rc = enqueue_allreduce(r)) return rc;
-                hipLaunchKernelGGL(k_publish_words, dim3(1), dim3(64), 0, r->stream, r->d_state, r->d_rec, call_id, it);
+                hipLaunchKernelGGL(k_publish_words, dim3(1), dim3(64), 0, r->stream, r->d_state.get(), r->rec.dev(), call_id, it);
             }
             if (rows_mode) {
                 if (int rc = wait_rows(r, groups, sp.tag, words)) {

@@ -12,17 +12,15 @@ constexpr size_t kScoreMaxPoints = 0x7FFFFFF0ull / 3;
 constexpr size_t kScoreBatch = 65536;     // poses uploaded, scored and collected at a time (buffers: 120 bytes per pose)
 constexpr uint32_t kScoreMaxGrid = 2048;  // workgroups of a launch; they stride over the launch's items
 
+// poses the two buffers hold (ensure_score empties both before it replaces them)
+size_t score_cap(const kicp_reg *r) { return r->d_score_acc.capacity() / kScoreWords; }
 int ensure_score(kicp_reg *r, size_t poses) {
-    if (poses <= r->score_cap) return KICP_OK;
+    if (poses <= score_cap(r)) return KICP_OK;
     HIP_TRY(hipStreamSynchronize(r->stream));
-    if (r->d_score_poses) HIP_TRY(hipFree(r->d_score_poses));
-    if (r->d_score_acc) HIP_TRY(hipFree(r->d_score_acc));
-    r->d_score_poses = nullptr, r->d_score_acc = nullptr, r->score_cap = 0;
     const size_t want = std::min(kScoreBatch, poses + poses / 2 + 64);
-    HIP_TRY(hipMalloc(&r->d_score_poses, want * 7 * sizeof(double)));
-    HIP_TRY(hipMalloc(&r->d_score_acc, want * kScoreWords * sizeof(unsigned long long)));
-    r->score_cap = want;
-    return KICP_OK;
+    r->d_score_poses.release(), r->d_score_acc.release();
+    if (int rc = r->d_score_poses.reserve(want * 7)) return rc;
+    return r->d_score_acc.reserve(want * kScoreWords);
 }
 // The two sums of a pose from its accumulator row: the limb sums (limb k at 2^(21 k)) are put together as ONE integer, cut into
 // the three 40-bit limbs every hand-off of the pass kernels carries (i128_to_limbs) and converted by the same function: the double
@@ -64,11 +62,11 @@ int score_device(kicp_reg *reg, kicp_map *map, const double *d_frame, size_t n, 
     // a launch serves whole tiles (256 queries, the frame's last one fewer): as many as fit "score_chunk", at least one
     const unsigned long long per_launch = std::max<unsigned long long>(1ull, static_cast<unsigned long long>(reg->score_chunk / kScoreBlock));
     std::vector<unsigned long long> rows;
-    for (size_t first = 0; first < count; first += reg->score_cap) {
-        const size_t m = std::min(reg->score_cap, count - first);
-        if (int rc = staged_upload(reg->stage, 0, reg->d_score_poses, poses_qt + 7 * first, m * 7 * sizeof(double), reg->stream)) return rc;
-        HIP_TRY(hipMemsetAsync(reg->d_score_acc, 0, m * kScoreWords * sizeof(unsigned long long), reg->stream));
-        sp.poses = reg->d_score_poses, sp.acc = reg->d_score_acc, sp.count = static_cast<uint32_t>(m);
+    for (size_t first = 0; first < count; first += score_cap(reg)) {
+        const size_t m = std::min(score_cap(reg), count - first);
+        if (int rc = staged_upload(reg->stage, 0, reg->d_score_poses.get(), poses_qt + 7 * first, m * 7 * sizeof(double), reg->stream)) return rc;
+        HIP_TRY(hipMemsetAsync(reg->d_score_acc.get(), 0, m * kScoreWords * sizeof(unsigned long long), reg->stream));
+        sp.poses = reg->d_score_poses.get(), sp.acc = reg->d_score_acc.get(), sp.count = static_cast<uint32_t>(m);
         const unsigned long long total = tiles * m;
         for (unsigned long long item0 = 0; item0 < total; item0 += per_launch) {
             sp.item0 = item0, sp.items = std::min(per_launch, total - item0);
@@ -78,7 +76,7 @@ int score_device(kicp_reg *reg, kicp_map *map, const double *d_frame, size_t n, 
         }
         HIP_TRY(hipGetLastError());
         rows.resize(m * kScoreWords);
-        if (int rc = staged_download(reg->stage, rows.data(), reg->d_score_acc, rows.size() * sizeof(unsigned long long), reg->stream)) return rc;
+        if (int rc = staged_download(reg->stage, rows.data(), reg->d_score_acc.get(), rows.size() * sizeof(unsigned long long), reg->stream)) return rc;
         for (size_t k = 0; k < m; ++k) row_to_sums(&rows[k * kScoreWords], out_n_corr[first + k], out_ssr[first + k]);
     }
     return KICP_OK;
@@ -90,7 +88,7 @@ int upload_frame(kicp_reg *reg, kicp_map *map, const double *frame_xyz, size_t n
     if (int rc = ensure_frame(reg, n)) return rc;
     if (int rc = aql_quiesce(reg)) return rc;
     reg->stream_dirty = true;
-    return staged_upload(reg->stage, 0, reg->d_frame, frame_xyz, n * 24, reg->stream);
+    return staged_upload(reg->stage, 0, reg->d_frame.get(), frame_xyz, n * 24, reg->stream);
 }
 bool pose_is_finite(const double *p) {
     for (int i = 0; i < 7; ++i)
@@ -114,7 +112,7 @@ int kicp_score_poses(kicp_reg *reg, kicp_map *map, const double *frame_xyz, size
     if (int rc = map_finish_pending(map)) return rc;
     if (count)
         if (int rc = upload_frame(reg, map, frame_xyz, n)) return rc;
-    return score_device(reg, map, reg->d_frame, n, poses_qt, count, max_correspondence_distance, out_n_corr, out_ssr);
+    return score_device(reg, map, reg->d_frame.get(), n, poses_qt, count, max_correspondence_distance, out_n_corr, out_ssr);
 }
 
 int kicp_relocalize(kicp_reg *reg, kicp_map *map, const double *frame_xyz, size_t n, const double *candidates_qt, size_t count,
@@ -137,7 +135,7 @@ int kicp_relocalize(kicp_reg *reg, kicp_map *map, const double *frame_xyz, size_
         return KICP_WARN_NO_CORRESPONDENCES;
     }
     if (int rc = upload_frame(reg, map, frame_xyz, n)) return rc;  // once: the scoring and the refinements read this copy
-    const double *d_frame = reg->d_frame;
+    const double *d_frame = reg->d_frame.get();
     // truncated least squares, lower is better: a point without a correspondence costs tau^2
     auto cost_of = [&](double n_corr, double ssr) { return (ssr + (static_cast<double>(n) - n_corr) * (tau * tau)) / static_cast<double>(n); };
     // 1. every candidate
