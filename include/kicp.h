@@ -197,7 +197,7 @@ int kicp_reg_set_config(kicp_reg *reg, const kicp_reg_config *config); /* the re
  *   "batch_threads"  (default 8, 0 .. 9) batches of scans that leave most of the device empty: up to this many resident kernels side by
  *                  side, a host thread of the library's pool each (capped by the CPUs this process may use: cpuset and cgroup quota)
  *   "batch_rotate"   1 (default): the workgroups of a resident kernel take turns at the parts of a scan; 0: fixed shares
- * One frame at many poses (kicp_score_poses, kicp_relocalize):
+ * One frame at many poses (kicp_score_poses, kicp_planar_sums, kicp_refine_poses_planar, kicp_relocalize, kicp_relocalize_planar):
  *   "score_chunk"  (default 8 388 608) queries - pose x point pairs - one launch of the scoring kernel may serve; 0: the default
  * Transfers and launches:
  *   "bar_frame"    1 (default): kicp_register writes host frames of up to 8 192 points straight into HBM through the PCIe BAR
@@ -327,10 +327,57 @@ int kicp_score_poses_device(kicp_reg *reg, kicp_map *map, const double *d_frame_
  * A refinement that ends without correspondences (NaN pose) is out of the running; if all are - or the frame or the map is empty -
  * the call returns KICP_WARN_NO_CORRESPONDENCES with the cheapest UNREFINED candidate, both costs its own.
  * The refinement moves along the kinematic model only - a forward arc and a yaw (Registration.cpp:159-167) -, so it cannot remove a
- * candidate's lateral offset: the candidates' lateral spacing is the caller's accuracy.  count == 0 or top_m == 0: KICP_ERR_ARG. */
+ * candidate's lateral offset: with THIS call the candidates' lateral spacing is the caller's accuracy (kicp_relocalize_planar below
+ * refines in the plane instead).  count == 0 or top_m == 0: KICP_ERR_ARG. */
 int kicp_relocalize(kicp_reg *reg, kicp_map *map, const double *frame_xyz, size_t n, const double *candidates_qt, size_t count,
                     double max_correspondence_distance, size_t top_m, double out_pose_qt[7], size_t *out_candidate, double *out_cost_before,
                     double *out_cost_after);
+
+/* The sums of ONE Gauss-Newton step that is free in the plane of the body frame (x, y, yaw), of ONE frame at `count` poses in one call.
+ * Per accepted correspondence (s = source point, r = T s - nn, c0 = R UnitX, c1 = R UnitY) J = [c0 | c1 | R (-s.y, s.x, 0)]; per pose
+ * eight doubles, in this order:
+ *     N      number of accepted correspondences          S_a   sum a,  a = c0 . r
+ *     S_x    sum s.x                                     S_b   sum b,  b = c1 . r
+ *     S_y    sum s.y                                     S_c   sum (s.x b - s.y a)
+ *     S_ss   sum (s.x^2 + s.y^2)                         ssr   sum |r|^2
+ * N, -S_y, S_ss, S_a, S_c and ssr are elements [6], [1], [2], [3], [4] and [5] of kicp_pass_sums at that pose, bit for bit (the pass
+ * kernels' own terms); S_x and S_b are formed next to them, each term rounded once to 2^-40 and added as an integer.  Everything
+ * else - the poses in HOST memory, "score_chunk" / "score_launches", empty inputs (zeros, KICP_OK), a NaN pose (zeros), the pending
+ * map update, the limits and the errors - is kicp_score_poses'. */
+int kicp_planar_sums(kicp_reg *reg, kicp_map *map, const double *frame_xyz, size_t n, const double *poses_qt /* count x 7 */, size_t count,
+                     double max_correspondence_distance, double *out_sums /* count x 8 */);
+int kicp_planar_sums_device(kicp_reg *reg, kicp_map *map, const double *d_frame_xyz, size_t n, const double *poses_qt, size_t count,
+                            double max_correspondence_distance, double *out_sums);
+/* One such step on the host from one row of sums (no device, no handle): dx = -A^-1 g with A = [[N, 0, -S_y], [0, N, S_x],
+ * [-S_y, S_x, S_ss]] and g = (S_a, S_b, S_c), then out_pose_qt = pose_qt * exp({dx, dy, 0, 0, 0, dtheta}).  No odometry prior, no
+ * regularisation.  Returns 1 and writes out_pose_qt and out_dx (dx, dy, dtheta; may be null), or 0 with both untouched when the step
+ * is degenerate: N < 1, a sum that is not finite, or N S_ss - S_x^2 - S_y^2 zero (all accepted points share one (x, y)) to within the
+ * 2^-40 rounding the sums' terms carry, N 2^-41 (N + 2 |S_x| + 2 |S_y|) + 4 eps N S_ss.  Null sums / pose_qt / out_pose_qt:
+ * KICP_ERR_ARG. */
+int kicp_planar_step(const double sums[8], const double pose_qt[7], double out_pose_qt[7], double out_dx[3]);
+/* Planar refinement of `count` poses of ONE frame, all in lock step: iteration j takes the sums of every pose still active from one
+ * kicp_planar_sums_device call (one launch, unless "score_chunk" cuts it), then steps each on the host.  Per pose, independently of
+ * every other pose of the call (the sums are integers: a pose's result does not depend on which poses share its launch):
+ *     status 0  the step just applied had sqrt(dx^2 + dy^2 + dtheta^2) < convergence
+ *     status 1  max_iterations steps applied
+ *     status 2  the step was degenerate (kicp_planar_step: no correspondence, one point, a NaN pose): the pose as it stood
+ * out_poses_qt (count x 7), out_iterations (steps applied) and out_status (the last two may be null).  An empty map or n == 0: the
+ * poses unchanged, status 2.  "score_launches" counts the launches of the whole call.  max_iterations < 1 or convergence < 0:
+ * KICP_ERR_ARG; otherwise the limits and errors of kicp_score_poses.  The registration's max_num_iterations does not apply:
+ * point-to-point steps in the plane need 20 to 80 iterations where the kinematic model needs a handful. */
+int kicp_refine_poses_planar(kicp_reg *reg, kicp_map *map, const double *frame_xyz, size_t n, const double *poses_qt, size_t count,
+                             double max_correspondence_distance, int max_iterations, double convergence, double *out_poses_qt, int *out_iterations,
+                             int *out_status);
+int kicp_refine_poses_planar_device(kicp_reg *reg, kicp_map *map, const double *d_frame_xyz, size_t n, const double *poses_qt, size_t count,
+                                    double max_correspondence_distance, int max_iterations, double convergence, double *out_poses_qt,
+                                    int *out_iterations, int *out_status);
+/* kicp_relocalize with step 3 replaced: the finalists are refined by kicp_refine_poses_planar_device on the frame already uploaded,
+ * and a refinement with status 2 is out of the running.  Cost, ranking, ties, outputs and the KICP_WARN_NO_CORRESPONDENCES fall-back
+ * are kicp_relocalize's.  The step is free in the plane, so a candidate's lateral offset is removed too: the grid only has to put
+ * one candidate into the basin of the truth. */
+int kicp_relocalize_planar(kicp_reg *reg, kicp_map *map, const double *frame_xyz, size_t n, const double *candidates_qt, size_t count,
+                           double max_correspondence_distance, size_t top_m, int max_iterations, double convergence, double out_pose_qt[7],
+                           size_t *out_candidate, double *out_cost_before, double *out_cost_after);
 
 /* Candidate poses for kicp_relocalize: center * planar(dx, dy, dyaw) for every offset i * step with |i * step| <= half extent, per axis
  * (a step <= 0 or a half extent of 0 leaves that axis at the centre) - offsets in the centre's BODY frame, x slowest, yaw fastest.

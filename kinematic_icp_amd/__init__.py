@@ -100,6 +100,15 @@ _SIGNATURES = {
     "kicp_score_poses": (C.c_int, [C.c_void_p, C.c_void_p, _dp, C.c_size_t, _dp, C.c_size_t, C.c_double, _dp, _dp]),
     "kicp_score_poses_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, _dp, C.c_size_t, C.c_double, _dp, _dp]),
     "kicp_relocalize": (C.c_int, [C.c_void_p, C.c_void_p, _dp, C.c_size_t, _dp, C.c_size_t, C.c_double, C.c_size_t, _dp, C.POINTER(C.c_size_t), _dp, _dp]),
+    "kicp_planar_sums": (C.c_int, [C.c_void_p, C.c_void_p, _dp, C.c_size_t, _dp, C.c_size_t, C.c_double, _dp]),
+    "kicp_planar_sums_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, _dp, C.c_size_t, C.c_double, _dp]),
+    "kicp_planar_step": (C.c_int, [_dp, _dp, _dp, _dp]),
+    "kicp_refine_poses_planar": (C.c_int, [C.c_void_p, C.c_void_p, _dp, C.c_size_t, _dp, C.c_size_t, C.c_double, C.c_int, C.c_double, _dp,
+                                           C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "kicp_refine_poses_planar_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, _dp, C.c_size_t, C.c_double, C.c_int, C.c_double, _dp,
+                                                  C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "kicp_relocalize_planar": (C.c_int, [C.c_void_p, C.c_void_p, _dp, C.c_size_t, _dp, C.c_size_t, C.c_double, C.c_size_t, C.c_int, C.c_double, _dp,
+                                         C.POINTER(C.c_size_t), _dp, _dp]),
     "kicp_planar_grid": (C.c_size_t, [_dp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _dp, C.c_size_t]),
     "kicp_map_save_pcd": (C.c_int, [C.c_void_p, C.c_char_p]),
     "kicp_map_load_pcd": (C.c_int, [C.c_char_p, C.c_double, C.c_double, C.c_uint, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
@@ -240,6 +249,18 @@ def cpus_near_gpu(device=0, one_l3_domain=True):
         return (cpus & l3) or cpus
     except OSError:
         return cpus
+
+
+def planar_step(sums, pose):
+    """kicp_planar_step: one planar Gauss-Newton step on the host from one row of PlanarSums -> (pose[7], dx[3]), or None when the step is
+    degenerate (N < 1, a non-finite sum, all accepted points on one (x, y))."""
+    s = np.ascontiguousarray(np.asarray(sums, dtype=np.float64).reshape(8))
+    q = np.ascontiguousarray(np.asarray(pose, dtype=np.float64).reshape(7))
+    out, dx = np.zeros(7, dtype=np.float64), np.zeros(3, dtype=np.float64)
+    rc = lib().kicp_planar_step(s.ctypes.data_as(_dp), q.ctypes.data_as(_dp), out.ctypes.data_as(_dp), dx.ctypes.data_as(_dp))
+    if rc < 0:
+        _check(rc)
+    return (out, dx) if rc == 1 else None
 
 
 def planar_grid(center, half_x, half_y, half_yaw, step_x, step_y, step_yaw):
@@ -572,6 +593,52 @@ class KinematicRegistration:
         cand, before, after = C.c_size_t(), C.c_double(), C.c_double()
         rc = lib().kicp_relocalize(self._h, voxel_map._h, p, a.size // 3, q.ctypes.data_as(_dp), q.shape[0], max_correspondence_distance, int(top_m),
                                    pose.ctypes.data_as(_dp), C.byref(cand), C.byref(before), C.byref(after))
+        self.last_status = rc if rc >= 0 else _check(rc)
+        return pose, cand.value, before.value, after.value
+
+    def PlanarSums(self, frame, voxel_map, poses, max_correspondence_distance):
+        """kicp_planar_sums: the sums of one planar 3-DoF Gauss-Newton step of ONE frame ((N,3) host array or DeviceFrame) at every pose of
+        `poses` (count, 7) -> (count, 8): N, S_x, S_y, S_ss, S_a, S_b, S_c, ssr (include/kicp.h)."""
+        q = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(-1, 7))
+        count = q.shape[0]
+        sums = np.zeros((count, 8), dtype=np.float64)
+        if isinstance(frame, DeviceFrame):
+            _check(lib().kicp_planar_sums_device(self._h, voxel_map._h, frame.ptr, frame.n, q.ctypes.data_as(_dp), count, max_correspondence_distance,
+                                                 sums.ctypes.data_as(_dp)))
+        else:
+            a, p = _d(frame)
+            _check(lib().kicp_planar_sums(self._h, voxel_map._h, p, a.size // 3, q.ctypes.data_as(_dp), count, max_correspondence_distance,
+                                          sums.ctypes.data_as(_dp)))
+        return sums
+
+    def RefinePosesPlanar(self, frame, voxel_map, poses, max_correspondence_distance, max_iterations=100, convergence=1e-4):
+        """kicp_refine_poses_planar: planar (x, y, yaw) Gauss-Newton refinement of every pose of `poses` (count, 7) against ONE frame
+        ((N,3) host array or DeviceFrame), all poses in lock step -> (poses[count, 7], iterations[count], status[count]); status 0:
+        converged, 1: max_iterations steps applied, 2: degenerate (the pose as it stood)."""
+        q = np.ascontiguousarray(np.asarray(poses, dtype=np.float64).reshape(-1, 7))
+        count = q.shape[0]
+        out = np.zeros((count, 7), dtype=np.float64)
+        iterations, status = np.zeros(count, dtype=np.int32), np.zeros(count, dtype=np.int32)
+        ip = C.POINTER(C.c_int)
+        tail = (q.ctypes.data_as(_dp), count, max_correspondence_distance, int(max_iterations), float(convergence), out.ctypes.data_as(_dp),
+                iterations.ctypes.data_as(ip), status.ctypes.data_as(ip))
+        if isinstance(frame, DeviceFrame):
+            _check(lib().kicp_refine_poses_planar_device(self._h, voxel_map._h, frame.ptr, frame.n, *tail))
+        else:
+            a, p = _d(frame)
+            _check(lib().kicp_refine_poses_planar(self._h, voxel_map._h, p, a.size // 3, *tail))
+        return out, iterations, status
+
+    def RelocalizePlanar(self, frame, voxel_map, candidates, max_correspondence_distance, top_m=8, max_iterations=100, convergence=1e-4):
+        """kicp_relocalize_planar: Relocalize with the top_m finalists refined in the plane (RefinePosesPlanar) instead of along the kinematic
+        model -> (pose[7], candidate index, cost before, cost after); a candidate's lateral offset is removed too.  Like Relocalize it
+        takes a HOST frame (uploaded once inside)."""
+        a, p = _d(frame)
+        q = np.ascontiguousarray(np.asarray(candidates, dtype=np.float64).reshape(-1, 7))
+        pose = np.zeros(7, dtype=np.float64)
+        cand, before, after = C.c_size_t(), C.c_double(), C.c_double()
+        rc = lib().kicp_relocalize_planar(self._h, voxel_map._h, p, a.size // 3, q.ctypes.data_as(_dp), q.shape[0], max_correspondence_distance, int(top_m),
+                                          int(max_iterations), float(convergence), pose.ctypes.data_as(_dp), C.byref(cand), C.byref(before), C.byref(after))
         self.last_status = rc if rc >= 0 else _check(rc)
         return pose, cand.value, before.value, after.value
 

@@ -242,12 +242,22 @@ public:
     // Relocalize: which of `candidates` (kicp_bridge::planar_grid builds a grid) explains `keypoints` - a registration source in the
     // base frame, e.g. the second cloud RegisterFrame returns - best: all are scored against the map, the top_m cheapest refined and
     // scored again (kicp.h kicp_relocalize; tau = the threshold of a first frame).  The result becomes the pipeline's pose.  The
-    // refinement moves along the kinematic model only: the candidates' lateral spacing is the accuracy.
+    // refinement moves along the kinematic model only: with this call the candidates' lateral spacing is the accuracy.
     KinematicRegistration::Relocalization Relocalize(const std::vector<Eigen::Vector3d> &keypoints, const std::vector<Sophus::SE3d> &candidates,
                                                      size_t top_m = 8) {
         correspondence_threshold_.Reset();
         const double tau = correspondence_threshold_.ComputeThreshold();
         const auto found = registration_.Relocalize(keypoints, local_map_, candidates, tau, top_m);
+        last_pose_ = found.pose;
+        return found;
+    }
+    // RelocalizePlanar: the same with the finalists refined in the plane - x, y and yaw - instead of along the kinematic model (kicp.h
+    // kicp_relocalize_planar), so the result is not tied to the candidates' lateral spacing.  The result becomes the pipeline's pose.
+    KinematicRegistration::Relocalization RelocalizePlanar(const std::vector<Eigen::Vector3d> &keypoints, const std::vector<Sophus::SE3d> &candidates,
+                                                           size_t top_m = 8, int max_iterations = 100, double convergence = 1e-4) {
+        correspondence_threshold_.Reset();
+        const double tau = correspondence_threshold_.ComputeThreshold();
+        const auto found = registration_.RelocalizePlanar(keypoints, local_map_, candidates, tau, top_m, max_iterations, convergence);
         last_pose_ = found.pose;
         return found;
     }

@@ -134,6 +134,42 @@ struct KinematicRegistration {
         r.pose = kicp_bridge::from_params(out), r.refined = rc == KICP_OK;
         return r;
     }
+    // backend extension: planar (x, y, yaw) Gauss-Newton refinement of many poses of ONE frame, all in lock step (kicp.h
+    // kicp_refine_poses_planar); its own limits, not max_num_iterations_ / convergence_criterion_: a point-to-point step in the plane
+    // needs tens of iterations.  status 0: converged, 1: max_iterations steps applied, 2: degenerate (the pose as it stood)
+    struct PlanarRefinement {
+        Sophus::SE3d pose;
+        int iterations = 0, status = 0;
+    };
+    std::vector<PlanarRefinement> RefinePosesPlanar(const std::vector<Eigen::Vector3d> &frame, const kiss_icp::VoxelHashMap &voxel_map,
+                                                    const std::vector<Sophus::SE3d> &poses, const double max_correspondence_distance,
+                                                    const int max_iterations = 100, const double convergence = 1e-4) {
+        const std::vector<double> flat = kicp_bridge::to_params(poses);
+        std::vector<double> out(flat.size());
+        std::vector<int> iterations(poses.size()), status(poses.size());
+        kicp_bridge::check(kicp_refine_poses_planar(handle_, voxel_map.handle(), kicp_bridge::xyz(frame), frame.size(), flat.data(), poses.size(),
+                                                    max_correspondence_distance, max_iterations, convergence, out.data(), iterations.data(), status.data()),
+                           "KinematicRegistration::RefinePosesPlanar");
+        std::vector<PlanarRefinement> refined(poses.size());
+        // (a degenerate pose comes back as it was given - a NaN pose included, which Sophus would refuse to rebuild)
+        for (size_t k = 0; k < poses.size(); ++k) refined[k] = {status[k] == 2 ? poses[k] : kicp_bridge::from_params(&out[7 * k]), iterations[k], status[k]};
+        return refined;
+    }
+    // backend extension: Relocalize with the finalists refined in the plane (kicp.h kicp_relocalize_planar): a candidate's lateral
+    // offset is removed too, so a coarse grid only has to put one candidate into the basin of the truth
+    Relocalization RelocalizePlanar(const std::vector<Eigen::Vector3d> &frame, const kiss_icp::VoxelHashMap &voxel_map,
+                                    const std::vector<Sophus::SE3d> &candidates, const double max_correspondence_distance, const size_t top_m = 8,
+                                    const int max_iterations = 100, const double convergence = 1e-4) {
+        const std::vector<double> flat = kicp_bridge::to_params(candidates);
+        Relocalization r;
+        double out[7];
+        const int rc = kicp_bridge::check(kicp_relocalize_planar(handle_, voxel_map.handle(), kicp_bridge::xyz(frame), frame.size(), flat.data(), candidates.size(),
+                                                                 max_correspondence_distance, top_m, max_iterations, convergence, out, &r.candidate,
+                                                                 &r.cost_before, &r.cost_after),
+                                          "KinematicRegistration::RelocalizePlanar");
+        r.pose = kicp_bridge::from_params(out), r.refined = rc == KICP_OK;
+        return r;
+    }
 
     int max_num_iterations_;
     double convergence_criterion_;

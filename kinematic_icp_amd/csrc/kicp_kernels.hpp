@@ -220,17 +220,30 @@ constexpr int kTermLimbs = 4;
 constexpr int kWaveLimbs = kTermLimbs * kNumSums;
 constexpr int kLendJobs = 32;                     // voxels a wave's loaded queries can give away per round (gather32_pass)
 constexpr int kLendWords = kLendJobs * (1 + 7 + 7);  // per wave: the jobs, the lent lanes' own records, the records they hand back
+// what a lane keeps of an accepted correspondence (resolve_and_accumulate): the seven terms of a registration pass, the squared
+// residual alone, or the terms of the planar 3-DoF normal equations
+enum class AccKind { Pass, Score, Planar };
 struct Acc {
-    static constexpr bool kScoreOnly = false;
+    static constexpr AccKind kKind = AccKind::Pass;
     int limb[kWaveLimbs];
     int range_error;
 };
 // What kicp_score_poses keeps of a correspondence (kicp_score.hpp): the squared residual - the term of sum 5, through the same
 // to_fixed - and the fact that there is one.  No basis, no Jacobian terms, no 28-limb row.
 struct ScoreAcc {
-    static constexpr bool kScoreOnly = true;
+    static constexpr AccKind kKind = AccKind::Score;
     int limb[kTermLimbs];  // to_fixed(|T s - nn|^2)
     int hit;               // 1: this lane holds a correspondence
+    int range_error;
+};
+// What kicp_planar_sums keeps (kicp_planar.hpp): the terms of the normal equations of a step that is free in the plane (x, y, yaw in
+// the body frame) - s.x, -s.y, s.x^2 + s.y^2, a = c0 . r, b = c1 . r, s.x b - s.y a, |r|^2, in this order, each through to_fixed.  Five
+// of them are the pass kernels' terms (correspondence_terms: the same doubles); s.x and b are the two a pass does not sum.
+constexpr int kPlanarTerms = 7;
+struct PlanarAcc {
+    static constexpr AccKind kKind = AccKind::Planar;
+    int limb[kTermLimbs * kPlanarTerms];
+    int hit;  // 1: this lane holds a correspondence
     int range_error;
 };
 // The term as an integer, T = rint(x 2^40) (|T| < 2^83; x 2^40 is exact, rint of a double beyond 2^52 is the double itself), split
@@ -438,16 +451,22 @@ __device__ __forceinline__ double exact_d2(const MapView &m, uint32_t gidx, cons
 // One function for every pass kernel: their terms are the same doubles.
 // |r|^2 of a residual, the term of sum 5: ONE expression for the pass kernels and for k_score_poses (kicp_score.hpp)
 __device__ __forceinline__ double squared_residual(double rx, double ry, double rz) { return fma(rx, rx, fma(ry, ry, rz * rz)); }
+// `b` = c1 . r leaves the function too: the planar sums (PlanarAcc) add it up, a pass only uses it inside term[3]
 __device__ __forceinline__ void correspondence_terms(const PassBasis &B, double sx, double sy, double qx, double qy, double qz, double tx, double ty, double tz,
-                                                     double (&term)[5]) {
+                                                     double (&term)[5], double &b) {
     const double rx = qx - tx, ry = qy - ty, rz = qz - tz;  // residual = T*source - target (Registration.cpp:88)
     const double a = fma(B.c0x, rx, fma(B.c0y, ry, B.c0z * rz));
-    const double b = fma(B.c1x, rx, fma(B.c1y, ry, B.c1z * rz));
+    b = fma(B.c1x, rx, fma(B.c1y, ry, B.c1z * rz));
     term[0] = -sy;
     term[1] = fma(sx, sx, sy * sy);
     term[2] = a;
     term[3] = fma(sx, b, -(sy * a));
     term[4] = squared_residual(rx, ry, rz);
+}
+__device__ __forceinline__ void correspondence_terms(const PassBasis &B, double sx, double sy, double qx, double qy, double qz, double tx, double ty, double tz,
+                                                     double (&term)[5]) {
+    double b;
+    correspondence_terms(B, sx, sy, qx, qy, qz, tx, ty, tz, term, b);
 }
 // the same residual as correspondence_terms forms it, and nothing else (kicp_score_poses)
 __device__ __forceinline__ void accumulate(ScoreAcc &a, double qx, double qy, double qz, double tx, double ty, double tz) {
@@ -463,6 +482,19 @@ __device__ __forceinline__ void accumulate(Acc &a, const PassBasis &B, double sx
 #pragma unroll
     for (int i = 0; i < 5; ++i) to_fixed(term[i], a.limb + (i + 1) * kTermLimbs, a.range_error);
     a.limb[6 * kTermLimbs + 1] = 1 << 19;  // the count: 1.0 = 2^40 = 2^19 * 2^21 (the other limbs stay 0)
+}
+// the pass kernels' terms from their own function, s.x and b next to them (kicp_planar_sums)
+__device__ __forceinline__ void accumulate(PlanarAcc &a, const PassBasis &B, double sx, double sy, double qx, double qy, double qz, double tx, double ty, double tz) {
+    double term[5], b;
+    correspondence_terms(B, sx, sy, qx, qy, qz, tx, ty, tz, term, b);
+    to_fixed(sx, a.limb, a.range_error);
+    to_fixed(term[0], a.limb + 1 * kTermLimbs, a.range_error);
+    to_fixed(term[1], a.limb + 2 * kTermLimbs, a.range_error);
+    to_fixed(term[2], a.limb + 3 * kTermLimbs, a.range_error);
+    to_fixed(b, a.limb + 4 * kTermLimbs, a.range_error);
+    to_fixed(term[3], a.limb + 5 * kTermLimbs, a.range_error);
+    to_fixed(term[4], a.limb + 6 * kTermLimbs, a.range_error);
+    a.hit = 1;
 }
 
 // (The solve + pose update - Registration.cpp:119-125, 159-167, 181-184 - is the host's: kicp_reg_internal.hpp HostLoop::step.  The device-side
@@ -1224,6 +1256,7 @@ __device__ __forceinline__ void export_correspondence(const PassParams &p, uint3
 }
 // ACC = ScoreAcc (k_score_poses): the same search result, resolution, tie rule and acceptance test; only what is kept of an accepted
 // correspondence differs (its squared residual and the count - no basis, no Jacobian terms)
+// ACC = PlanarAcc (k_planar_poses): likewise; the basis is formed here from T, as for a pass whose pose is the device's
 template <bool EXPORT = false, class ACC = Acc>
 __device__ __forceinline__ void resolve_and_accumulate(ACC &acc, const PassParams &p, bool host_pose, const double *__restrict__ src, const Pose &T, uint32_t i,
                                                        const Best3 &t, const KeptQuery *kept = nullptr) {
@@ -1270,8 +1303,10 @@ __device__ __forceinline__ void resolve_and_accumulate(ACC &acc, const PassParam
             wx = tp[0], wy = tp[1], wz = tp[2];
         }
         if (EXPORT) export_correspondence(p, i, best_idx, best, wx, wy, wz);
-        if constexpr (ACC::kScoreOnly) {
+        if constexpr (ACC::kKind == AccKind::Score) {
             accumulate(acc, q.x, q.y, q.z, wx, wy, wz);
+        } else if constexpr (ACC::kKind == AccKind::Planar) {
+            accumulate(acc, basis_of(T), kept ? kept->sx : src[3 * i], kept ? kept->sy : src[3 * i + 1], q.x, q.y, q.z, wx, wy, wz);
         } else {
             // The basis is taken up HERE - behind an opaque copy of the flag, so that the compiler cannot merge its two sources ahead of
             // the exact phase and carry sixteen registers through it (the four-waves build spilled them) - and, where it is the host's,
@@ -1442,7 +1477,7 @@ __device__ __forceinline__ void gather32_pass(const PassParams &p, const Pose &T
     }
     // dbg 10 (bench.py's latency model): no correspondences are formed; the "count" sum carries the number of visiting rounds
     // this WAVE ran - its chain of dependent bucket visits - from lane 0 (as rounds x 2^40: limb 1 holds bits 21..41, limb 2 the rest)
-    if constexpr (!ACC::kScoreOnly)
+    if constexpr (ACC::kKind == AccKind::Pass)
         if (dbg_is(p, 10) && (tid & 63u) == 0u) acc.limb[6 * kTermLimbs + 1] = static_cast<int>(rounds & 3u) << 19, acc.limb[6 * kTermLimbs + 2] = static_cast<int>(rounds >> 2);
 }
 template <int BLOCK, int G, int OCC, bool SPLIT, bool LAT = false, bool EXPORT = false>

@@ -202,6 +202,7 @@ struct kicp_reg {
     // kicp_score_poses (kicp_score.hip): the uploaded poses and their accumulator rows, a batch of poses at a time
     DevBuf<double> d_score_poses;            // 7 doubles per pose
     DevBuf<unsigned long long> d_score_acc;  // kScoreWords per pose
+    DevBuf<unsigned long long> d_planar_acc; // kicp_planar_sums: kPlanarWords per pose, for as many poses as the two above hold
     double score_chunk = 8388608.0;   // option "score_chunk": queries (pose x point pairs) one launch of k_score_poses may serve
     int score_launches = 0;           // launches the last kicp_score_poses call used (get-only "score_launches")
     uint32_t trace_pass = 1;      // the pass of a launch the stamps are taken on (the option's value)

@@ -3,9 +3,13 @@ as tools/bench_pipeline.py binds it.  For (cfg1 keypoints, 4 096 and 65 536 pose
   (a) one kicp_score_poses_device call (the frame resident in HBM);
   (b) the way without it: a loop of kicp_pass_sums over the same poses, through bare ctypes calls with every pointer prepared
       beforehand (for 65 536 poses 4 096 of them are timed and the time is scaled by 16 - the JSON says so);
-  (c) kicp_relocalize with top_m = 8 on the same candidates.
-Warm; (a) and (b) alternate three times: median and spread (min .. max) of the three, the speed-up of the medians, and whether (a) beats
-(b) by more than both spreads.  Also queries (pose x point pairs) per second of (a).  Prints one JSON line.
+  (c) kicp_relocalize with top_m = 8 on the same candidates;
+  (d) kicp_relocalize_planar (100 iterations, convergence 1e-4) on the same candidates;
+  (e) kicp_relocalize_planar on a coarser grid over the same extent with about a sixth as many candidates (0.55 of the nodes per axis).
+Warm; (a) and (b) alternate three times, then (c), (d) and (e) alternate as often: median, p10 / p90 and spread (min .. max), the
+speed-up of the medians, and whether (a) beats (b) by more than both spreads.  Per row of (c) - (e) also how far the result lies from
+the scan's true pose, and for (d) / (e) the launches of the call (scoring + one per lock-step iteration + scoring).  Also queries
+(pose x point pairs) per second of (a).  Prints one JSON line.
 
     python tools/bench_relocalize.py [--rounds 3] [--top-m 8]
 """
@@ -41,10 +45,17 @@ def candidates(truth, nx, ny, nw, half_xy=2.0, half_yaw=np.deg2rad(20.0)):
 
 
 def spread(v):
-    return {"median_ms": float(np.median(v)), "min_ms": float(np.min(v)), "max_ms": float(np.max(v))}
+    return {"median_ms": float(np.median(v)), "min_ms": float(np.min(v)), "max_ms": float(np.max(v)), "p10_ms": float(np.percentile(v, 10)),
+            "p90_ms": float(np.percentile(v, 90))}
 
 
-def shape(name, cfg, gmap, keypoints, poses, timed_b, rounds, top_m):
+def offset(truth, pose):
+    """(distance [m], |yaw| [deg]) of a planar pose from the truth"""
+    e = syn.pose_mul(syn.pose_inverse(truth), pose)
+    return {"distance_m": float(np.hypot(e[4], e[5])), "yaw_deg": float(np.degrees(2.0 * np.arcsin(min(1.0, abs(e[2])))))}
+
+
+def shape(name, cfg, gmap, keypoints, poses, coarse, truth, timed_b, rounds, top_m):
     lib, dp = K.lib(), C.POINTER(C.c_double)
     reg = K.KinematicRegistration()
     tau = cfg.first_frame_tau()
@@ -81,19 +92,35 @@ def shape(name, cfg, gmap, keypoints, poses, timed_b, rounds, top_m):
     launches = int(reg.get_option("score_launches"))
     pose, cand = np.zeros(7), C.c_size_t()
     before, after = C.c_double(), C.c_double()
-    tc = []
-    for _ in range(rounds + 1):
+    coarse_p = coarse.ctypes.data_as(dp)
+    rows = {"c": [], "d": [], "e": []}
+    found = {}
+
+    def relocalize(row):
         t0 = time.perf_counter()
-        rc = lib.kicp_relocalize(reg._h, gmap._h, frame_p, n, poses_p, count, tau, top_m, pose.ctypes.data_as(dp), C.byref(cand), C.byref(before), C.byref(after))
-        tc.append((time.perf_counter() - t0) * 1e3)
+        if row == "c":
+            rc = lib.kicp_relocalize(reg._h, gmap._h, frame_p, n, poses_p, count, tau, top_m, pose.ctypes.data_as(dp), C.byref(cand), C.byref(before), C.byref(after))
+        else:
+            rc = lib.kicp_relocalize_planar(reg._h, gmap._h, frame_p, n, poses_p if row == "d" else coarse_p, count if row == "d" else len(coarse), tau, top_m,
+                                            100, 1e-4, pose.ctypes.data_as(dp), C.byref(cand), C.byref(before), C.byref(after))
+        rows[row].append((time.perf_counter() - t0) * 1e3)
         assert rc >= 0, rc
+        found[row] = dict(offset(truth, pose), candidate=int(cand.value), cost_before=before.value, cost_after=after.value,
+                          launches=int(reg.get_option("score_launches")))
+
+    for _ in range(rounds + 1):  # (the first round warms)
+        for row in ("c", "d", "e"):
+            relocalize(row)
+    tc = rows["c"]
     med_a, med_b = float(np.median(ta)), float(np.median(tb))
     return {"scan": name, "keypoints": n, "poses": count, "queries": n * count, "launches": launches,
             "score_poses": spread(ta), "pass_sums_loop": dict(spread(tb), timed_poses=timed_b, scaled_by=count / timed_b),
-            "relocalize_top%d" % top_m: spread(tc[1:]), "speedup_of_medians": med_b / med_a,
+            "relocalize_top%d" % top_m: dict(spread(tc[1:]), **found["c"]),
+            "relocalize_planar_top%d" % top_m: dict(spread(rows["d"][1:]), **found["d"]),
+            "relocalize_planar_coarse_top%d" % top_m: dict(spread(rows["e"][1:]), poses=len(coarse), **found["e"]), "speedup_of_medians": med_b / med_a,
             "beats_by_more_than_the_spreads": bool(min(tb) - max(ta) > max(max(ta) - min(ta), max(tb) - min(tb))),
-            "score_poses_queries_per_s": n * count / (med_a * 1e-3), "relocalized_candidate": int(cand.value), "cost_before": before.value,
-            "cost_after": after.value, "best_candidate_correspondences": float(n_corr.max())}
+            "score_poses_queries_per_s": n * count / (med_a * 1e-3), "relocalized_candidate": found["c"]["candidate"], "cost_before": found["c"]["cost_before"],
+            "cost_after": found["c"]["cost_after"], "best_candidate_correspondences": float(n_corr.max())}
 
 
 def main():
@@ -113,7 +140,10 @@ def main():
         keypoints = np.ascontiguousarray(okicp.voxel_downsample(okicp.voxel_downsample(s["frame"], cfg.voxel_size * 0.5), cfg.voxel_size * 1.5))
         for nx, ny, nw in grids:
             poses = candidates(s["true_pose"], nx, ny, nw)
-            res["shapes"].append(shape(name, cfg, gmap, keypoints, poses, min(len(poses), 4096), a.rounds, a.top_m))
+            # 0.55 of the nodes per axis (0.55^3 ~ 1 / 6), an even number of them in x and y: the truth stays between the nodes
+            cx, cy, cw = (int(round(0.55 * k)) for k in (nx, ny, nw))
+            coarse = candidates(s["true_pose"], cx - cx % 2, cy + cy % 2, cw)
+            res["shapes"].append(shape(name, cfg, gmap, keypoints, poses, coarse, s["true_pose"], min(len(poses), 4096), a.rounds, a.top_m))
     print(json.dumps(res))
 
 
