@@ -114,6 +114,16 @@ int kicp_map_last_update_on_device(const kicp_map *map); /* 1 if the last kicp_m
 /* Updates so far that ran on the GPU and have been collected; unlike every other call on the map this one does NOT wait for a pending
  * update (a diagnostic a timed loop can read without disturbing what it measures). */
 unsigned long long kicp_map_device_updates(const kicp_map *map);
+/* Which way this map's updates went so far - a read-only diagnostic for tests and tuning: host-side counters only, no device call, and
+ * like kicp_map_device_updates it does NOT collect a pending update.  kicp_map_clear keeps them.  out[]:
+ *   0  updates queued as ONE queue of kernels (<= 16384 points into a table with room for the worst case)
+ *   1  staged updates (claim, ask the device, then apply)        2  second claims of a staged update after a "too tight" re-hash
+ *   3  device-side re-hashes                                     4  pool growths that reallocated
+ *   5  launches of the wave-per-voxel insertion kernel           6  launches of the thread-per-voxel insertion kernel
+ *   7  scans over many workgroups (> 16384 points)               8  updates handed to the host map
+ *   9  updates left pending by kicp_map_update_pose_device_begin
+ *  10  voxels touched by the last collected device-side update   11 0 (reserved) */
+int kicp_map_update_counts(const kicp_map *map, unsigned long long out[12]);
 /* Preferred device for BULK host-side insertions (not part of the reference API): with device >= 0, kicp_map_add_points /
  * kicp_map_update_origin / kicp_map_update_pose calls of 4096 points or more stage their points into HBM and insert them
  * there (the same map as the sequential host insertion builds, an order of magnitude faster); -1 (default) = always on the

@@ -71,6 +71,7 @@ _SIGNATURES = {
     "kicp_map_update_finish": (C.c_int, [C.c_void_p]),
     "kicp_map_last_update_on_device": (C.c_int, [C.c_void_p]),
     "kicp_map_device_updates": (C.c_ulonglong, [C.c_void_p]),
+    "kicp_map_update_counts": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong)]),
     "kicp_map_set_device": (C.c_int, [C.c_void_p, C.c_int]),
     "kicp_map_num_points": (C.c_size_t, [C.c_void_p]),
     "kicp_map_num_voxels": (C.c_size_t, [C.c_void_p]),
@@ -351,7 +352,8 @@ class VoxelHashMap:
 
     def UpdateDevice(self, device_frame, pose):
         """Update(points, pose) with the points already in HBM (DeviceFrame / PreSteps.frame); returns True if it ran on
-        the GPU, False if the host fallback (table or pool growth) was taken."""
+        the GPU (table and pool growth included), False if the host map took it over: no points, or a map that holds or
+        meets a voxel beyond +-2^20 voxels from the origin."""
         _, q = _d(pose)
         _check(lib().kicp_map_update_pose_device(self._h, device_frame.device, device_frame.ptr, device_frame.n, q))
         return bool(lib().kicp_map_last_update_on_device(self._h))
@@ -365,6 +367,20 @@ class VoxelHashMap:
     def UpdateFinish(self):
         _check(lib().kicp_map_update_finish(self._h))
         return bool(lib().kicp_map_last_update_on_device(self._h))
+
+    def device_updates(self):
+        """Updates that ran on the GPU and have been collected (kicp_map_device_updates); a pending one stays pending."""
+        return lib().kicp_map_device_updates(self._h)
+
+    UPDATE_COUNTS = ("one_queue", "staged", "second_claims", "rehashes", "pool_growths", "apply_wave", "apply_thread", "wide_scans",
+                     "host_updates", "deferred", "touched", "reserved")
+
+    def update_counts(self):
+        """Which way this map's updates went so far (kicp_map_update_counts, include/kicp.h): a dict of the twelve host-side
+        counters; reads no device state and does not collect a pending update."""
+        out = (C.c_ulonglong * 12)()
+        _check(lib().kicp_map_update_counts(self._h, out))
+        return dict(zip(self.UPDATE_COUNTS, out))
 
     def num_points(self):
         return lib().kicp_map_num_points(self._h)

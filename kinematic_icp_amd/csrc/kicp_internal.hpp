@@ -304,6 +304,9 @@ struct kicp_map {
     kicp::DevMapCounters dev{};
     int last_update_on_device = 0;
     unsigned long long device_updates = 0;  // updates that ran (and were collected) on the GPU so far (kicp_map_device_updates)
+    // which way the updates went (kicp_map_update_counts; include/kicp.h lists the entries): host-side bookkeeping only, bumped where
+    // map_update_device / map_finish_pending / device_rehash / grow_pools take the decision; Clear() keeps them
+    unsigned long long update_counts[12] = {};
     // a voxel coordinate beyond +-2^20 was seen: the packed keys of the device-side maintenance cannot hold it, so this map's
     // updates stay on the host from now on (until Clear); registration and queries on the device are unaffected
     bool host_updates_only = false;

@@ -184,6 +184,10 @@ int decode_update_error(uint32_t error) {
     return KICP_OK;
 }
 
+// the entries of kicp_map::update_counts (kicp_map_update_counts, include/kicp.h)
+enum UpdateCount { kCountOneQueue = 0, kCountStaged, kCountSecondClaims, kCountRehashes, kCountPoolGrowths, kCountApplyWave, kCountApplyThread,
+                   kCountWideScans, kCountHostUpdates, kCountDeferred, kCountTouched };
+
 // make the device pools (and the free-list stack) hold at least `want_buckets` buckets, keeping their contents
 int grow_pools(kicp_map *map, size_t want_buckets) {
     DeviceMirror &mr = map->mirror;
@@ -202,6 +206,7 @@ int grow_pools(kicp_map *map, size_t want_buckets) {
     if (mr.d_pool16.get()) HIP_TRY(hipMemcpy(np32.get(), mr.d_pool16.get(), mirror_points(mr.d_pool.capacity(), cap) * sizeof(MirrorPoint), hipMemcpyDeviceToDevice));
     if (free_cap(mr)) HIP_TRY(hipMemcpy(nf.get(), mr.d_free_list.get(), std::min(free_cap(mr), buckets) * 4, hipMemcpyDeviceToDevice));
     std::swap(mr.d_pool, np), std::swap(mr.d_pool16, np32), std::swap(mr.d_free_list, nf);  // (the old ones go with the locals)
+    ++map->update_counts[kCountPoolGrowths];
     mr.view.pool = mr.d_pool.get(), mr.view.pool16 = mr.d_pool16.get();
     return KICP_OK;
 }
@@ -222,6 +227,7 @@ int device_rehash(kicp_map *map, size_t extra_entries) {
     DeviceMirror &mr = map->mirror;
     hipStream_t st = nullptr;
     const size_t old_slots = mr.live_slots;
+    ++map->update_counts[kCountRehashes];
     HIP_TRY(hipMemsetAsync(&mr.d_ctr.get()->touched, 0, 8, st));  // touched (borrowed as the live counter) + error
     mr.ctr_clean = false;
     const uint32_t grid_old = static_cast<uint32_t>(std::min<size_t>((old_slots + 255) / 256, 8192));
@@ -266,6 +272,7 @@ int map_update_device(kicp_map *map, int device, const double *d_points, size_t 
     DeviceMirror &mr = map->mirror;
     map->last_update_on_device = 0;
     auto host_fallback = [&]() -> int {
+        ++map->update_counts[kCountHostUpdates];
         std::vector<double> pts(3 * n);
         if (n) HIP_TRY(hipMemcpy(pts.data(), d_points, n * 24, hipMemcpyDeviceToHost));
         if (int rc = ensure_host_current(map)) return rc;
@@ -305,10 +312,13 @@ int map_update_device(kicp_map *map, int device, const double *d_points, size_t 
     // read the exact number on the device)
     auto enqueue_apply = [&](size_t touched_bound) {
         hipLaunchKernelGGL(k_up_scatter, dim3(grid), dim3(256), 0, st, up);
-        if (touched_bound <= 16384 && cap <= kApplyMaxPoints)  // a frame's worth of voxels: one wave each; bulk insertions: one thread each (kicp_mapdev.hpp steps 4 / 4b)
+        if (touched_bound <= 16384 && cap <= kApplyMaxPoints) {  // a frame's worth of voxels: one wave each; bulk insertions: one thread each (kicp_mapdev.hpp steps 4 / 4b)
             hipLaunchKernelGGL(k_up_apply, dim3(static_cast<uint32_t>((touched_bound + kApplyWaves - 1) / kApplyWaves)), dim3(64 * kApplyWaves), 0, st, up);
-        else
+            ++map->update_counts[kCountApplyWave];
+        } else {
             hipLaunchKernelGGL(k_up_apply_thread, dim3(static_cast<uint32_t>((touched_bound + 63) / 64)), dim3(64), 0, st, up);
+            ++map->update_counts[kCountApplyThread];
+        }
         if (remove_origin)
             hipLaunchKernelGGL(k_up_remove, dim3(static_cast<uint32_t>(std::min<size_t>((mr.live_slots / 4 + 255) / 256, 8192))), dim3(256), 0, st, up.m,
                                remove_origin[0], remove_origin[1], remove_origin[2]);
@@ -323,6 +333,7 @@ int map_update_device(kicp_map *map, int device, const double *d_points, size_t 
     // one synchronisation; a claim step that gives up (voxel coordinate out of range) turns the later steps into no-ops.
     if (n <= 16384 && (map->dev.n_entries + 27ull * n) * 4 <= mr.live_slots * 3ull) {
         bind();
+        ++map->update_counts[kCountOneQueue];
         if (!mr.ctr_clean) HIP_TRY(hipMemsetAsync(&mr.d_ctr.get()->touched, 0, 12, st));  // touched + error + may_occupy (k_up_publish left them at zero otherwise)
         mr.ctr_clean = false;
         hipLaunchKernelGGL(k_up_claim, dim3(grid), dim3(256), 0, st, up);
@@ -344,6 +355,7 @@ int map_update_device(kicp_map *map, int device, const double *d_points, size_t 
             map->pending.has_origin = remove_origin != nullptr;
             if (remove_origin) map->pending.origin[0] = remove_origin[0], map->pending.origin[1] = remove_origin[1], map->pending.origin[2] = remove_origin[2];
             map->last_update_on_device = 1;  // (corrected by the finish step should the host have to take the update over)
+            ++map->update_counts[kCountDeferred];
             return KICP_OK;
         }
         HIP_TRY(hipMemcpyAsync(&c, mr.d_ctr.get(), sizeof c, hipMemcpyDeviceToHost, st));
@@ -356,17 +368,21 @@ int map_update_device(kicp_map *map, int device, const double *d_points, size_t 
             return host_fallback();
         }
         map->last_update_on_device = 1, ++map->device_updates;
+        map->update_counts[kCountTouched] = c.touched;
         return KICP_OK;
     }
+    ++map->update_counts[kCountStaged];
     for (int attempt = 0;; ++attempt) {
         if (attempt == 0 && (map->dev.n_entries + n) * 2 > mr.live_slots)
             if (int rc = device_rehash(map, 32 * n + 1024)) return rc;
         bind();
+        if (attempt) ++map->update_counts[kCountSecondClaims];
         HIP_TRY(hipMemsetAsync(&mr.d_ctr.get()->touched, 0, 12, st));  // touched + error + may_occupy
         mr.ctr_clean = false;
         hipLaunchKernelGGL(k_up_claim, dim3(grid), dim3(256), 0, st, up);
         if (n > 16384) {  // bulk: the scan over many workgroups (the number of touched voxels is only known on the device: <= n)
             const uint32_t spans = static_cast<uint32_t>((n + kScanSpan - 1) / kScanSpan);
+            ++map->update_counts[kCountWideScans];
             hipLaunchKernelGGL(k_up_scan_local, dim3(spans), dim3(256), 0, st, up, mr.d_order.get());
             hipLaunchKernelGGL(k_up_scan_sums, dim3(1), dim3(1024), 0, st, up, mr.d_order.get());
             hipLaunchKernelGGL(k_up_scan_add, dim3(grid), dim3(256), 0, st, up, mr.d_order.get());
@@ -400,6 +416,7 @@ int map_update_device(kicp_map *map, int device, const double *d_points, size_t 
     if (int rc = decode_update_error(c.error)) return rc == kRerunOnHost ? fail(KICP_ERR_CAPACITY, "device-side map update ran out of room") : rc;
     map->dev = c;
     map->last_update_on_device = 1, ++map->device_updates;
+    map->update_counts[kCountTouched] = c.touched;
     return KICP_OK;
 }
 
@@ -428,6 +445,7 @@ int map_finish_pending(kicp_map *map) {
         return map_update_device(map, mr.device, u.points, u.n, u.pose, u.has_origin ? u.origin : nullptr);
     }
     ++map->device_updates;
+    map->update_counts[kCountTouched] = c.touched;  // (k_up_publish sends the counters before it zeroes this one)
     return KICP_OK;
 }
 }  // namespace host
@@ -576,9 +594,11 @@ int kicp_map_update_finish(kicp_map *map) {
     if (!map) return fail(KICP_ERR_ARG, "null map");
     return map_finish_pending(map);
 }
-unsigned long long kicp_map_device_updates(const kicp_map *map) {
-    if (map) (void)map_finish_pending(const_cast<kicp_map *>(map));
-    return map ? map->device_updates : 0ull;
+unsigned long long kicp_map_device_updates(const kicp_map *map) { return map ? map->device_updates : 0ull; }  // (no collecting: kicp.h)
+int kicp_map_update_counts(const kicp_map *map, unsigned long long out[12]) {
+    if (!map || !out) return fail(KICP_ERR_ARG, "null argument");
+    for (int k = 0; k < 12; ++k) out[k] = map->update_counts[k];  // (host-side counters: no device call, a pending update stays pending)
+    return KICP_OK;
 }
 int kicp_map_last_update_on_device(const kicp_map *map) {
     if (map) (void)map_finish_pending(const_cast<kicp_map *>(map));
