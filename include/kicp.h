@@ -181,7 +181,7 @@ void kicp_reg_destroy(kicp_reg *reg);
 int kicp_reg_clone(const kicp_reg *reg, kicp_reg **out);
 int kicp_reg_get_config(const kicp_reg *reg, kicp_reg_config *out);
 int kicp_reg_set_config(kicp_reg *reg, const kicp_reg_config *config); /* the reference's fields are public & mutable */
-/* Backend tuning knobs (not part of the reference API).  Eighteen settable options; everything that lost its A/B over five rounds
+/* Backend tuning knobs (not part of the reference API).  Nineteen settable options; everything that lost its A/B over five rounds
  * (other workgroup sizes and register budgets, the plain fp64 gather, the device-side solve, single-record hand-offs, ...) was deleted
  * in round 6, and the pass kernels' ablation switches ("dbg") exist in libkicp_amd_dbg.so only (make -C kinematic_icp_amd/csrc dbg).
  * Which kernel runs:
@@ -209,6 +209,8 @@ int kicp_reg_set_config(kicp_reg *reg, const kicp_reg_config *config); /* the re
  *   "batch_rotate"   1 (default): the workgroups of a resident kernel take turns at the parts of a scan; 0: fixed shares
  * One frame at many poses (kicp_score_poses, kicp_planar_sums, kicp_refine_poses_planar, kicp_relocalize, kicp_relocalize_planar):
  *   "score_chunk"  (default 8 388 608) queries - pose x point pairs - one launch of the scoring kernel may serve; 0: the default
+ * The branch-and-bound search (kicp_search_poses, kicp_relocalize_search):
+ *   "search_max_nodes" (default 67 108 864 = 2^26) nodes one call may score before it gives up with KICP_ERR_CAPACITY; 0: the default
  * Transfers and launches:
  *   "bar_frame"    1 (default): kicp_register writes host frames of up to 8 192 points straight into HBM through the PCIe BAR
  *   "fetch_upload" 1 (default): larger host frames are pulled out of the pinned staging buffer by a small kernel per piece; 0: DMA engine
@@ -216,7 +218,7 @@ int kicp_reg_set_config(kicp_reg *reg, const kicp_reg_config *config); /* the re
  *   "wait"         0 (default): poll the tagged rows in host memory; 1: hipStreamSynchronize
  *   "timing"       1: kicp_stats.gpu_ms from HIP events; 2: also kicp_stats.pass_ms[]
  * Read only: "small_active" (path of the last call: 0 generic, 1 sub-lanes, 2 wave per query), "resident_passes", "batch_queue_passes",
- *   "batch_resident_passes", "batch_threads_active", "small_relaunches", "score_launches", "aql_active", "aql_kernarg", "comm_ranks".
+ *   "batch_resident_passes", "batch_threads_active", "small_relaunches", "score_launches", "search_nodes_scored", "search_launches", "aql_active", "aql_kernarg", "comm_ranks".
  * Test hooks (exercise fall-backs that this hardware does not reach by itself): "small_cmd" 0 - workgroup 0 relays the resident kernels'
  *   commands (platforms without a CPU-writable BAR); "debug_tag" - jump next to the 16-bit pass tag's wrap-around; "debug_stall_us" -
  *   be late with one command; "debug_p2p_one_row" - send this rank's total as one mailbox row, as launches of more than 32 groups
@@ -394,6 +396,80 @@ int kicp_relocalize_planar(kicp_reg *reg, kicp_map *map, const double *frame_xyz
  * Returns the number of poses of the grid and writes the first min(that, cap_poses) of them (out_poses_qt may be null: count only). */
 size_t kicp_planar_grid(const double center_qt[7], double half_x, double half_y, double half_yaw, double step_x, double step_y, double step_yaw,
                         double *out_poses_qt, size_t cap_poses);
+
+/* ---- whole-map relocalisation: an occupancy pyramid of the map and a branch-and-bound search over it ----
+ * A kicp_occ is a SNAPSHOT of a map as bits: one bit per cell of a world-aligned grid, set where a map point lies within `dilate` cells
+ * (Chebyshev) of it.  It owns its device memory and does NOT follow later updates of the map - the use case is the frozen map
+ * (build it again after the map changed).  Geometry, per axis, all in fp64 without contraction:
+ *     min  = (floor(lowest map coordinate / cell) - (dilate + 1)) * cell
+ *     dims = floor((highest map coordinate - min) / cell) + dilate + 2
+ *     cell index of a coordinate p: floor((p - min) / cell)
+ * (an empty map: min = 0, dims = 1, no bit set).  Level 0 is that grid.  Level h (1 .. levels) has the SAME resolution and is a sliding
+ * OR over x and y: occ_h(x, y, z) = OR of occ_0(x + a, y + b, z) over 0 <= a, b < 2^h, cells beyond the grid empty - so occ_h at a cell
+ * bounds occ_0 at every cell of the 2^h x 2^h block that starts there, which is what the search rests on.
+ * Layout of a level (what kicp_occ_level downloads): 32-bit words, cell (x, y, z) is bit (x & 31) - bit 0 the least significant - of
+ * word (z * dims[1] + y) * words_x + (x >> 5), words_x = (dims[0] + 31) / 32; the bits of a row's last word beyond dims[0] are zero.
+ * The build reads the map's HBM mirror (made current first; a pending deferred update is collected and its error returned), so a map
+ * whose newest state lives on the device needs no host round trip.  cell <= 0 or not finite, dilate outside 0 .. 4, levels outside
+ * 0 .. 10: KICP_ERR_ARG.  A pyramid (all levels) of more than 1 GiB, or an axis of 2^24 cells or more: KICP_ERR_CAPACITY, the message
+ * names the size. */
+typedef struct kicp_occ kicp_occ;
+int kicp_occ_build(kicp_map *map, int device, double cell, int dilate, int levels, kicp_occ **out);
+void kicp_occ_destroy(kicp_occ *occ);
+/* any output may be null; out_set_cells: the number of set bits of level 0 */
+int kicp_occ_info(const kicp_occ *occ, double out_min[3], int out_dims[3], double *out_cell, int *out_dilate, int *out_levels,
+                  unsigned long long *out_set_cells);
+/* one level as words (layout above): writes min(cap_words, total) words, *out_total_words = total (out_words may be null with cap 0) */
+int kicp_occ_level(const kicp_occ *occ, int level, unsigned int *out_words, size_t cap_words, size_t *out_total_words);
+
+/* The discretised pose space of a search.  Node (j, ix, iy) is the planar pose with translation (x0 + ix * cell, y0 + iy * cell, z) and
+ * rotation yaw0 + j * yaw_step about z (roll = pitch = 0); its index is (j * ny + iy) * nx + ix.  nx, ny <= 2^20, nyaw <= 2^16. */
+typedef struct kicp_search_window {
+    double x0, y0, z;        /* world position of node (ix = 0, iy = 0); z: the base frame's height */
+    unsigned int nx, ny;     /* nodes per axis, ONE CELL of the pyramid apart */
+    double yaw0, yaw_step;   /* yaw of j = 0, spacing */
+    unsigned int nyaw;
+} kicp_search_window;
+/* The rotation table the scores are computed from: out_cs[2 j] = std::cos(yaw0 + (double)j * yaw_step), out_cs[2 j + 1] = std::sin of
+ * the same angle, on the host; the device uses these doubles and no trigonometry of its own. */
+int kicp_search_yaws(const kicp_search_window *w, double *out_cs /* nyaw x 2 */);
+/* A window around center_xy: nodes at center + i * cell for |i * cell| <= half extent per axis (the extent rounded down to whole
+ * cells), the full circle of yaws from -pi in steps of 2 pi / ceil(2 pi / yaw_step) (yaw_step <= 0: one yaw, 0).  A half extent <= 0
+ * (center_xy may then be null): that axis covers the pyramid's whole footprint, nodes on the cell corners min + i * cell. */
+int kicp_search_window_around(const kicp_occ *occ, const double center_xy[2], double half_x, double half_y, double z, double yaw_step,
+                              kicp_search_window *out);
+/* Scores of nodes at one level of the pyramid.  Because the nodes are one cell apart, the cell of frame point p is computed once per
+ * yaw j, with (c, s) of kicp_search_yaws, each operation rounded on its own in this order:
+ *     cx = floor((((c * p.x - s * p.y) + x0) - min[0]) / cell)
+ *     cy = floor((((s * p.x + c * p.y) + y0) - min[1]) / cell)
+ *     cz = floor(((p.z + z) - min[2]) / cell)
+ * and the score of node (j, ix, iy) at level h is the number of frame points with occ_h set at (cx + ix, cy + iy, cz); a cell outside
+ * the grid - or not finite - counts as empty, with one exception that keeps the bound below valid: at level h > 0 an x (or y) in
+ * -2^h < x < 0 is read as 0 (the block that starts there reaches into the grid, and the block that starts at the edge covers all of
+ * that).  Scores are integers and exact.  At level h the score of (j, ix, iy) is an upper bound of the level-0 score of every node
+ * (j, ix + a, iy + b), 0 <= a, b < 2^h.
+ * `nodes`: count node indices (any order, repeats allowed), out_hits: count scores.  n == 0: zeros.  level outside 0 .. levels, an index
+ * beyond the window, a null argument, a handle on another device than the pyramid's, or a multi-GPU exchange attached: KICP_ERR_ARG. */
+int kicp_occ_score_nodes(kicp_reg *reg, const kicp_occ *occ, const double *frame_xyz, size_t n, const kicp_search_window *w, int level,
+                         const unsigned long long *nodes, size_t count, unsigned int *out_hits);
+/* The best nodes of the whole window: the first min(top_m, nx * ny * nyaw) of ALL its nodes sorted by (level-0 score descending, node
+ * index ascending) - exactly what scoring every node and a stable sort give - found by branch and bound: the window is tiled with
+ * blocks of 2^levels cells scored at the top level, a greedy dive of the best blocks yields a lower limit L (the top_m-th best leaf it
+ * meets), and level by level the four children of every block whose bound is >= L are scored in one go.  out_nodes / out_hits
+ * (top entries each), out_poses_qt (top x 7, nullable): the nodes' poses; *out_found = the number of entries written.
+ * Option "search_max_nodes" (default 2^26) limits the nodes a call may score: beyond it the call returns KICP_ERR_CAPACITY, never an
+ * inexact result.  "search_nodes_scored" and "search_launches" (read only) describe the last call (of
+ * kicp_occ_score_nodes too: its `count` and its launches).  top_m == 0: KICP_ERR_ARG; the
+ * other errors are those of kicp_occ_score_nodes; an empty frame gives zero scores (the first nodes by index). */
+int kicp_search_poses(kicp_reg *reg, const kicp_occ *occ, const double *frame_xyz, size_t n, const kicp_search_window *w, size_t top_m,
+                      unsigned long long *out_nodes, unsigned int *out_hits, double *out_poses_qt, size_t *out_found);
+/* Relocalisation without a candidate grid of the caller's: kicp_search_poses, then kicp_relocalize_planar with the found poses as the
+ * candidates and every one of them a finalist.  The score only selects the finalists; cost, ranking, ties, the refinement and the
+ * KICP_WARN_NO_CORRESPONDENCES fall-back are those of kicp_relocalize_planar on `map` (the map the pyramid was built from).
+ * *out_node (nullable): the node the returned pose started from. */
+int kicp_relocalize_search(kicp_reg *reg, kicp_map *map, const kicp_occ *occ, const double *frame_xyz, size_t n, const kicp_search_window *w,
+                           double max_correspondence_distance, size_t top_m, int max_iterations, double convergence, double out_pose_qt[7],
+                           unsigned long long *out_node, double *out_cost_before, double *out_cost_after);
 
 /* ---- pre-steps of the pipeline on the GPU (pipeline/KinematicICP.cpp:54-62) -----------
  * A kicp_pre owns KICP_PRE_BUFFERS device point buffers.  Results stay in HBM (feed kicp_register_device with

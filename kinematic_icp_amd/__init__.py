@@ -46,6 +46,17 @@ class Stats(C.Structure):
                 ("dx", (C.c_double * 2) * MAX_LOG_PASSES), ("gpu_ms", C.c_double), ("pass_ms", C.c_double * MAX_LOG_PASSES)]
 
 
+class SearchWindow(C.Structure):
+    """kicp_search_window: node (j, ix, iy) is the planar pose at (x0 + ix cell, y0 + iy cell, z) with yaw yaw0 + j yaw_step; its index
+    is (j * ny + iy) * nx + ix"""
+    _fields_ = [("x0", C.c_double), ("y0", C.c_double), ("z", C.c_double), ("nx", C.c_uint), ("ny", C.c_uint), ("yaw0", C.c_double),
+                ("yaw_step", C.c_double), ("nyaw", C.c_uint)]
+
+    @property
+    def nodes(self):
+        return int(self.nx) * int(self.ny) * int(self.nyaw)
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p)
 
 _dp = C.POINTER(C.c_double)
@@ -110,6 +121,18 @@ _SIGNATURES = {
                                                   C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "kicp_relocalize_planar": (C.c_int, [C.c_void_p, C.c_void_p, _dp, C.c_size_t, _dp, C.c_size_t, C.c_double, C.c_size_t, C.c_int, C.c_double, _dp,
                                          C.POINTER(C.c_size_t), _dp, _dp]),
+    "kicp_occ_build": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),
+    "kicp_occ_destroy": (None, [C.c_void_p]),
+    "kicp_occ_info": (C.c_int, [C.c_void_p, _dp, C.POINTER(C.c_int), _dp, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_ulonglong)]),
+    "kicp_occ_level": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_uint), C.c_size_t, C.POINTER(C.c_size_t)]),
+    "kicp_search_yaws": (C.c_int, [C.POINTER(SearchWindow), _dp]),
+    "kicp_search_window_around": (C.c_int, [C.c_void_p, _dp, C.c_double, C.c_double, C.c_double, C.c_double, C.POINTER(SearchWindow)]),
+    "kicp_occ_score_nodes": (C.c_int, [C.c_void_p, C.c_void_p, _dp, C.c_size_t, C.POINTER(SearchWindow), C.c_int, C.POINTER(C.c_ulonglong), C.c_size_t,
+                                       C.POINTER(C.c_uint)]),
+    "kicp_search_poses": (C.c_int, [C.c_void_p, C.c_void_p, _dp, C.c_size_t, C.POINTER(SearchWindow), C.c_size_t, C.POINTER(C.c_ulonglong),
+                                    C.POINTER(C.c_uint), _dp, C.POINTER(C.c_size_t)]),
+    "kicp_relocalize_search": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, _dp, C.c_size_t, C.POINTER(SearchWindow), C.c_double, C.c_size_t, C.c_int,
+                                         C.c_double, _dp, C.POINTER(C.c_ulonglong), _dp, _dp]),
     "kicp_planar_grid": (C.c_size_t, [_dp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _dp, C.c_size_t]),
     "kicp_map_save_pcd": (C.c_int, [C.c_void_p, C.c_char_p]),
     "kicp_map_load_pcd": (C.c_int, [C.c_char_p, C.c_double, C.c_double, C.c_uint, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
@@ -273,6 +296,60 @@ def planar_grid(center, half_x, half_y, half_yaw, step_x, step_y, step_yaw):
     out = np.empty((n, 7), dtype=np.float64)
     lib().kicp_planar_grid(c, *args, out.ctypes.data_as(_dp), n)
     return out
+
+
+def search_yaws(window):
+    """kicp_search_yaws: the (nyaw, 2) table of (cos, sin) the node scores are computed from - the very doubles the device uses"""
+    out = np.zeros((window.nyaw, 2), dtype=np.float64)
+    _check(lib().kicp_search_yaws(C.byref(window), out.ctypes.data_as(_dp)))
+    return out
+
+
+def search_window_around(occ, center_xy, half_x, half_y, z, yaw_step):
+    """kicp_search_window_around: the window of nodes within the half extents of center_xy (rounded down to whole cells of the pyramid)
+    over the full circle of yaws; half extents <= 0 (center_xy may be None): the pyramid's whole x-y footprint -> SearchWindow"""
+    w = SearchWindow()
+    center, c = (None, None) if center_xy is None else _d(np.asarray(center_xy, dtype=np.float64).reshape(2))  # (`center` keeps the array alive)
+    _check(lib().kicp_search_window_around(occ._h, c, float(half_x), float(half_y), float(z), float(yaw_step), C.byref(w)))
+    return w
+
+
+class OccupancyPyramid:
+    """kicp_occ: a SNAPSHOT of a map as an occupancy grid of `cell` metres (every point's cell and those within `dilate` of it) and
+    `levels` max-pooled levels above it (include/kicp.h).  It owns its device memory and does not follow later updates of the map."""
+
+    def __init__(self, voxel_map, cell, dilate=1, levels=4, device=0):
+        h = C.c_void_p()
+        self._h = None
+        _check(lib().kicp_occ_build(voxel_map._h, int(device), float(cell), int(dilate), int(levels), C.byref(h)))
+        self._h, self.device = h, device
+
+    @classmethod
+    def build(cls, voxel_map, cell, dilate=1, levels=4, device=0):
+        """kicp_occ_build, spelled as the C-ABI spells it: the same as calling the class"""
+        return cls(voxel_map, cell, dilate, levels, device)
+
+    def __del__(self):
+        if getattr(self, "_h", None) and _lib is not None:
+            _lib.kicp_occ_destroy(self._h)
+            self._h = None
+
+    def info(self):
+        """-> dict: min[3], dims[3], cell, dilate, levels, set_cells (level 0)"""
+        mn, dims = np.zeros(3, dtype=np.float64), (C.c_int * 3)()
+        cell, dilate, levels, set_cells = C.c_double(), C.c_int(), C.c_int(), C.c_ulonglong()
+        _check(lib().kicp_occ_info(self._h, mn.ctypes.data_as(_dp), dims, C.byref(cell), C.byref(dilate), C.byref(levels), C.byref(set_cells)))
+        return {"min": mn, "dims": np.array(list(dims), dtype=np.int64), "cell": cell.value, "dilate": dilate.value, "levels": levels.value,
+                "set_cells": set_cells.value}
+
+    def level(self, level):
+        """one level as uint32 words shaped (dims z, dims y, words per row): cell (x, y, z) is bit x & 31 of [z, y, x >> 5]"""
+        total = C.c_size_t()
+        _check(lib().kicp_occ_level(self._h, int(level), None, 0, C.byref(total)))
+        words = np.zeros(total.value, dtype=np.uint32)
+        _check(lib().kicp_occ_level(self._h, int(level), words.ctypes.data_as(C.POINTER(C.c_uint)), total.value, None))
+        dims = self.info()["dims"]
+        return words.reshape(int(dims[2]), int(dims[1]), -1)
 
 
 class VoxelHashMap:
@@ -657,6 +734,39 @@ class KinematicRegistration:
                                           int(max_iterations), float(convergence), pose.ctypes.data_as(_dp), C.byref(cand), C.byref(before), C.byref(after))
         self.last_status = rc if rc >= 0 else _check(rc)
         return pose, cand.value, before.value, after.value
+
+    def ScoreNodes(self, frame, occ, window, level, nodes):
+        """kicp_occ_score_nodes: per node index of `nodes` the number of frame points whose cell - at the node's yaw, shifted by the node's
+        (ix, iy) - is set in level `level` of the pyramid -> uint32[count]; exact integers"""
+        a, p = _d(frame)
+        q = np.ascontiguousarray(np.asarray(nodes, dtype=np.uint64).reshape(-1))
+        hits = np.zeros(q.size, dtype=np.uint32)
+        _check(lib().kicp_occ_score_nodes(self._h, occ._h, p, a.size // 3, C.byref(window), int(level), q.ctypes.data_as(C.POINTER(C.c_ulonglong)), q.size,
+                                          hits.ctypes.data_as(C.POINTER(C.c_uint))))
+        return hits
+
+    def SearchPoses(self, frame, occ, window, top_m=8):
+        """kicp_search_poses: the first min(top_m, all) nodes of the window by (level-0 score descending, node index ascending), found by
+        branch and bound over the pyramid -> (nodes uint64[k], hits uint32[k], poses[k, 7]).  Option "search_max_nodes" bounds the work
+        (KicpError with KICP_ERR_CAPACITY beyond it); "search_nodes_scored" / "search_launches" describe the last call."""
+        a, p = _d(frame)
+        k = min(int(top_m), window.nodes)
+        nodes, hits, poses = np.zeros(k, dtype=np.uint64), np.zeros(k, dtype=np.uint32), np.zeros((k, 7), dtype=np.float64)
+        found = C.c_size_t()
+        _check(lib().kicp_search_poses(self._h, occ._h, p, a.size // 3, C.byref(window), int(top_m), nodes.ctypes.data_as(C.POINTER(C.c_ulonglong)),
+                                       hits.ctypes.data_as(C.POINTER(C.c_uint)), poses.ctypes.data_as(_dp), C.byref(found)))
+        return nodes[:found.value], hits[:found.value], poses[:found.value]
+
+    def RelocalizeSearch(self, frame, voxel_map, occ, window, max_correspondence_distance, top_m=8, max_iterations=100, convergence=1e-4):
+        """kicp_relocalize_search: SearchPoses over the whole window, then RelocalizePlanar with the found poses as candidates and every one
+        of them a finalist -> (pose[7], node index, cost before, cost after).  `occ` must be a pyramid of `voxel_map`."""
+        a, p = _d(frame)
+        pose = np.zeros(7, dtype=np.float64)
+        node, before, after = C.c_ulonglong(), C.c_double(), C.c_double()
+        rc = lib().kicp_relocalize_search(self._h, voxel_map._h, occ._h, p, a.size // 3, C.byref(window), max_correspondence_distance, int(top_m),
+                                          int(max_iterations), float(convergence), pose.ctypes.data_as(_dp), C.byref(node), C.byref(before), C.byref(after))
+        self.last_status = rc if rc >= 0 else _check(rc)
+        return pose, node.value, before.value, after.value
 
     def pass_words(self, frame, voxel_map, pose, max_correspondence_distance):
         """The same pass as raw int64[24] limb words (the multi-GPU all-reduce payload; see sharding.py)."""

@@ -7,6 +7,7 @@
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
+#include <memory>
 #include <sophus/se3.hpp>
 #include <stdexcept>
 #include <string>
@@ -80,6 +81,21 @@ struct PointCloud2Xyz32 {
 inline int check(int rc, const char *what) {
     if (rc < 0) throw std::runtime_error(std::string(what) + ": " + kicp_last_error());
     return rc;  // (> 0: a warning code of include/kicp.h; the result still follows the reference's convention)
+}
+// The occupancy pyramid of a map for KinematicRegistration::RelocalizeSearch (kicp.h kicp_occ_build): a snapshot that owns its device
+// memory and does not follow later map updates; shared, because nothing changes it once it is built.
+inline std::shared_ptr<kicp_occ> build_occupancy(kicp_map *map, double cell, int dilate = 1, int levels = 4, int device = -1) {
+    kicp_occ *occ = nullptr;
+    check(kicp_occ_build(map, device < 0 ? default_device() : device, cell, dilate, levels, &occ), "kicp_bridge::build_occupancy");
+    return std::shared_ptr<kicp_occ>(occ, kicp_occ_destroy);
+}
+// The search window around a point of the map, or - with half extents <= 0 - over the pyramid's whole footprint (kicp.h
+// kicp_search_window_around); z: the base frame's height, yaw_step: the spacing of the full circle of yaws.
+inline kicp_search_window search_window_around(const kicp_occ *occ, const Eigen::Vector2d &center, double half_x, double half_y, double z, double yaw_step) {
+    const double c[2] = {center.x(), center.y()};
+    kicp_search_window w{};
+    check(kicp_search_window_around(occ, c, half_x, half_y, z, yaw_step, &w), "kicp_bridge::search_window_around");
+    return w;
 }
 // a warning the reference has no channel for: once per process on stderr
 inline void warn_once(const char *message) {

@@ -261,6 +261,22 @@ public:
         last_pose_ = found.pose;
         return found;
     }
+    // BuildOccupancy: the occupancy pyramid of the map as it is NOW (kicp.h kicp_occ_build; a snapshot - build it again after the map
+    // changed), `cell` about the map's point spacing voxel_size / sqrt(max_points_per_voxel).  RelocalizeSearch then needs no
+    // candidates: it searches a whole window (kicp_bridge::search_window_around(Occupancy(), ...); half extents <= 0: the whole map)
+    // for the top_m nodes that explain `keypoints` best and refines them in the plane (kicp.h kicp_relocalize_search).  The result
+    // becomes the pipeline's pose.
+    void BuildOccupancy(double cell, int dilate = 1, int levels = 4) { occupancy_ = kicp_bridge::build_occupancy(local_map_.handle(), cell, dilate, levels); }
+    const kicp_occ *Occupancy() const { return occupancy_.get(); }
+    KinematicRegistration::Relocalization RelocalizeSearch(const std::vector<Eigen::Vector3d> &keypoints, const kicp_search_window &window,
+                                                           size_t top_m = 8, int max_iterations = 100, double convergence = 1e-4) {
+        if (!occupancy_) throw std::runtime_error("KinematicICP::RelocalizeSearch: call BuildOccupancy first");
+        correspondence_threshold_.Reset();
+        const double tau = correspondence_threshold_.ComputeThreshold();
+        const auto found = registration_.RelocalizeSearch(keypoints, local_map_, occupancy_.get(), window, tau, top_m, max_iterations, convergence);
+        last_pose_ = found.pose;
+        return found;
+    }
 
     std::vector<Eigen::Vector3d> LocalMap() const { return local_map_.Pointcloud(); }
     const kiss_icp::VoxelHashMap &VoxelMap() const { return local_map_; }
@@ -353,6 +369,7 @@ protected:
     kiss_icp::Preprocessor preprocessor_;
     kiss_icp::VoxelHashMap local_map_;
     kicp_pre *pre_ = nullptr;  // device workspace of the pre-steps (backend detail)
+    std::shared_ptr<kicp_occ> occupancy_;  // BuildOccupancy's snapshot of the map (backend detail)
 };
 
 }  // namespace kinematic_icp::pipeline

@@ -170,6 +170,22 @@ struct KinematicRegistration {
         r.pose = kicp_bridge::from_params(out), r.refined = rc == KICP_OK;
         return r;
     }
+    // backend extension: relocalisation over a whole search window without a candidate grid (kicp.h kicp_relocalize_search): the top_m
+    // best nodes of the window by their hit count in the occupancy pyramid `occ` of voxel_map (kicp_bridge::build_occupancy), found by
+    // branch and bound, then RelocalizePlanar with every one of them a finalist.  `candidate` is the node index the pose started from.
+    Relocalization RelocalizeSearch(const std::vector<Eigen::Vector3d> &frame, const kiss_icp::VoxelHashMap &voxel_map, const kicp_occ *occ,
+                                    const kicp_search_window &window, const double max_correspondence_distance, const size_t top_m = 8,
+                                    const int max_iterations = 100, const double convergence = 1e-4) {
+        Relocalization r;
+        double out[7];
+        unsigned long long node = 0;
+        const int rc = kicp_bridge::check(kicp_relocalize_search(handle_, voxel_map.handle(), occ, kicp_bridge::xyz(frame), frame.size(), &window,
+                                                                 max_correspondence_distance, top_m, max_iterations, convergence, out, &node, &r.cost_before,
+                                                                 &r.cost_after),
+                                          "KinematicRegistration::RelocalizeSearch");
+        r.pose = kicp_bridge::from_params(out), r.candidate = static_cast<size_t>(node), r.refined = rc == KICP_OK;
+        return r;
+    }
 
     int max_num_iterations_;
     double convergence_criterion_;

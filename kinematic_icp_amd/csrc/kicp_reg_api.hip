@@ -176,6 +176,7 @@ int kicp_reg_set_option(kicp_reg *reg, const char *name, double value) {
     }
     else if (k == "small_timeout_us") reg->small_timeout_us = value;
     else if (k == "score_chunk") reg->score_chunk = value >= 1.0 ? std::min(value, 1.0e15) : 8388608.0;  // (0: back to the default)
+    else if (k == "search_max_nodes") reg->search_max_nodes = value >= 1.0 ? std::min(value, 1.0e15) : 67108864.0;  // (0: back to the default)
     else if (k == "debug_stall_us") reg->debug_stall_us = value;
     else if (k == "dbg") {
 #ifdef KICP_DBG_BUILD
@@ -231,6 +232,9 @@ double kicp_reg_get_option(const kicp_reg *reg, const char *name) {
     if (k == "small_timeout_us") return reg->small_timeout_us;
     if (k == "score_chunk") return reg->score_chunk;
     if (k == "score_launches") return reg->score_launches;
+    if (k == "search_max_nodes") return reg->search_max_nodes;
+    if (k == "search_nodes_scored") return static_cast<double>(reg->search_nodes_scored);
+    if (k == "search_launches") return reg->search_launches;
     if (k == "small_active") return reg->last_small;  // path of the last registration: 0 generic, 1 small (sub-lanes per query), 2 small (wave per query)
     if (k == "small_relaunches") return static_cast<double>(reg->small_relaunches);
     if (k == "aql_active") return (reg->aql.ready && reg->last_via_aql) ? 1.0 : 0.0;  // was the last pass dispatched through the AQL queue
@@ -415,6 +419,7 @@ int kicp_reg_clone(const kicp_reg *reg, kicp_reg **out) {
     c->wave_block = reg->wave_block, c->small_resident = reg->small_resident, c->small_timeout_us = reg->small_timeout_us, c->small_group_rows = reg->small_group_rows;
     c->resident_generic = reg->resident_generic, c->batch_resident = reg->batch_resident, c->batch_depth = reg->batch_depth, c->batch_rotate = reg->batch_rotate, c->batch_queues = reg->batch_queues, c->batch_threads = reg->batch_threads ;
     c->score_chunk = reg->score_chunk;
+    c->search_max_nodes = reg->search_max_nodes;
     *out = c;
     return KICP_OK;
 }

@@ -8,7 +8,8 @@
 //   kicp_reg_queues.hip   batches with several scans in flight on queues of their own (also sharded: shared segment / RCCL lanes)
 //   kicp_reg_comm.hip     the multi-GPU exchanges: RCCL communicator, host shared segment, peer mailboxes, caller-supplied all-reduce
 //   kicp_reg_api.hip      the C-ABI entry points of include/kicp.h: create / destroy / options / kicp_register* / kicp_pass_*
-// and kicp_score.hip (one frame scored at many poses, kicp_relocalize) works on the same handle.
+// and kicp_score.hip (one frame scored at many poses, kicp_relocalize) and kicp_search.hip (the occupancy pyramid and the search over
+// it) work on the same handle.
 #pragma once
 #include <dlfcn.h>
 #include <fcntl.h>
@@ -205,6 +206,15 @@ struct kicp_reg {
     DevBuf<unsigned long long> d_planar_acc; // kicp_planar_sums: kPlanarWords per pose, for as many poses as the two above hold
     double score_chunk = 8388608.0;   // option "score_chunk": queries (pose x point pairs) one launch of k_score_poses may serve
     int score_launches = 0;           // launches the last kicp_score_poses call used (get-only "score_launches")
+    // kicp_occ_score_nodes / kicp_search_poses (kicp_search.hip): the frame's cells per yaw, the rotation table, a piece of the node list
+    // and its scores
+    DevBuf<int32_t> d_search_cells;
+    DevBuf<double> d_search_cs;
+    DevBuf<unsigned long long> d_search_nodes;
+    DevBuf<uint32_t> d_search_hits;
+    double search_max_nodes = 67108864.0;          // option "search_max_nodes": nodes one kicp_search_poses call may score
+    unsigned long long search_nodes_scored = 0;    // nodes the last search scored (get-only "search_nodes_scored")
+    int search_launches = 0;                       // launches of k_search_score in the last call (get-only "search_launches")
     uint32_t trace_pass = 1;      // the pass of a launch the stamps are taken on (the option's value)
     DevBuf<long long> d_trace;    // option "small_trace": device buffer of the kernel's per-pass wall-clock stamps
     double trace_host_us = 0.0, trace_dev_us = 0.0, trace_first_us = 0.0;  // host: rows seen -> command sent; device: command sent -> rows seen; launch -> first rows
