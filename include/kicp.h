@@ -471,6 +471,76 @@ int kicp_relocalize_search(kicp_reg *reg, kicp_map *map, const kicp_occ *occ, co
                            double max_correspondence_distance, size_t top_m, int max_iterations, double convergence, double out_pose_qt[7],
                            unsigned long long *out_node, double *out_cost_before, double *out_cost_after);
 
+/* ---- a 2-D occupancy grid drawn while mapping: hits, and the free space the rays carve (kicp_grid.hip) ----------------------------
+ * What a planner reads (nav_msgs/OccupancyGrid, map.pgm + map.yaml) cannot be made from the saved point map afterwards: telling free
+ * from unknown needs the ray from the sensor to every return, and the rays exist only while the frames are being registered.
+ *
+ * The grid is world aligned: width x height cells of side `cell`, lower corner at (origin_x, origin_y), cell (ix, iy) is element
+ * iy * width + ix.  Each cell holds two 16-bit counters, hits and misses; both saturate at 65 535.  Everything below is exact and
+ * integer from the floor on.
+ *
+ * A frame is n points in the base frame, the pose and the sensor's origin in the base frame.  A point is USED when its three coordinates
+ * are finite, z_min <= p.z < z_max holds for its base-frame z (the band needs no transform), its world coordinates are finite and its
+ * endpoint cell passes the reach test.  With R, t of the pose (the registration's pose_to_rt, evaluated on the host):
+ *   wx = ((r00 p.x + r01 p.y) + r02 p.z) + t0,  wy likewise with row 1 (every operation rounded on its own),
+ *   cx = floor((wx - origin_x) / cell),  cy = floor((wy - origin_y) / cell);
+ * the sensor's origin goes through the same arithmetic to the sensor cell (sx, sy).  reach = ceil(max_ray / cell) cells, computed at
+ * creation: a point with max(|cx - sx|, |cy - sy|) > reach is skipped - no hit, no ray - so one frame touches at most the
+ * (2 reach + 1)^2 cells around the sensor cell.
+ * The ray of an endpoint cell (ex, ey), a = |ex - sx|, b = |ey - sy|, m = max(a, b), visits for k = 0 .. m - 1 the cell
+ *   (sx + sgn(ex - sx) ((2 k a + m) / (2 m)),  sy + sgn(ey - sy) ((2 k b + m) / (2 m)))      (integer divisions)
+ * - the sensor cell first, never the endpoint cell; m = 0 visits nothing.
+ * Once per cell per frame: a cell inside the grid is HIT when it is the endpoint cell of at least one used point, otherwise MISS when
+ * at least one used point's ray visits it, otherwise untouched; HIT cells get hits = min(hits + 1, 65535), MISS cells get misses =
+ * min(misses + 1, 65535).  Cells outside the grid are ignored, but a ray whose endpoint or sensor cell lies outside still marks the
+ * cells inside that it visits.  The result depends on the SET of endpoint cells only, not on the points' number or order.
+ *
+ * Limits: width * height <= 2^28 and reach <= 4095 (KICP_ERR_CAPACITY, the size in the message); cell and max_ray positive and finite,
+ * the origin finite, z_min < z_max, width and height >= 1, no null pointer (KICP_ERR_ARG). */
+typedef struct kicp_grid kicp_grid;
+typedef struct kicp_grid_config {
+    double cell, origin_x, origin_y; /* metres */
+    unsigned int width, height;      /* cells */
+    double z_min, z_max;             /* the band of base-frame heights whose points count: z_min <= p.z < z_max */
+    double max_ray;                  /* metres: returns whose cell is farther than ceil(max_ray / cell) cells from the sensor's are skipped */
+} kicp_grid_config;
+int kicp_grid_create(const kicp_grid_config *config, int device, kicp_grid **out);
+void kicp_grid_destroy(kicp_grid *grid);
+/* the configuration, reach, and the frames integrated since creation or the last kicp_grid_clear (each nullable) */
+int kicp_grid_info(const kicp_grid *grid, kicp_grid_config *out_config, int *out_reach, unsigned long long *out_frames);
+int kicp_grid_clear(kicp_grid *grid); /* every counter and the frame count back to zero */
+/* One frame.  kicp_grid_integrate takes the points from host memory (through the handle's pinned staging buffer);
+ * kicp_grid_integrate_device takes them where they already are in HBM, complete - e.g. kicp_pre_device_ptr(pre, 0, ..) after
+ * kicp_pre_frame has returned - and is what the drop-in pipeline calls.  Both return after their kernels have completed.
+ * out_stats (nullable): points used, points skipped, cells HIT, cells MISS of this frame.  n == 0 is legal: nothing changes, the frame
+ * is counted.  n > 0x7FFFFFF0 / 3: KICP_ERR_CAPACITY. */
+int kicp_grid_integrate(kicp_grid *grid, const double *frame_xyz, size_t n, const double pose_qt[7], const double sensor_xyz[3],
+                        unsigned long long out_stats[4]);
+int kicp_grid_integrate_device(kicp_grid *grid, const double *d_frame_xyz, size_t n, const double pose_qt[7], const double sensor_xyz[3],
+                               unsigned long long out_stats[4]);
+/* The counters, cells x 2: hits then misses of cell 0, of cell 1, ...  cap_cells / cells must be the grid's width * height
+ * (KICP_ERR_ARG otherwise).  kicp_grid_set_counts replaces them all: it resumes a mapping run from saved counters (the frame count is
+ * not part of them). */
+int kicp_grid_counts(const kicp_grid *grid, unsigned short *out, size_t cap_cells);
+int kicp_grid_set_counts(kicp_grid *grid, const unsigned short *in, size_t cells);
+/* The readout, the `data` of a nav_msgs/OccupancyGrid: width * height bytes, row-major from the origin,
+ *   -1 where hits + misses < min_observations (min_observations >= 1, KICP_ERR_ARG otherwise),
+ *   (100 hits + (hits + misses) / 2) / (hits + misses) otherwise, in integers: 0 .. 100.
+ * kicp_grid_occupancy computes it on the GPU, so one byte per cell crosses PCIe; kicp_grid_occupancy_from_counts is the same arithmetic
+ * as pure host code over counters in the layout of kicp_grid_counts and needs no GPU. */
+int kicp_grid_occupancy(const kicp_grid *grid, unsigned int min_observations, signed char *out, size_t cap_cells);
+int kicp_grid_occupancy_from_counts(const unsigned short *counts, size_t cells, unsigned int min_observations, signed char *out);
+/* The grid as the <prefix>.pgm + <prefix>.yaml pair map_server and Nav2 read.  The PGM: "P5\n<width> <height>\n255\n", then the rows
+ * from the highest iy down to 0; a pixel is 0 when (double)value > occupied_thresh * 100.0, 254 when value >= 0 and (double)value <
+ * free_thresh * 100.0, 205 otherwise (unknown cells too).  The YAML: image (the PGM's base name), mode: trinary, resolution, origin
+ * [x, y, 0], negate: 0, occupied_thresh, free_thresh, the numbers as %.17g.  map_server's defaults are occupied_thresh 0.65 and
+ * free_thresh 0.25; 0 <= free_thresh < occupied_thresh <= 1, KICP_ERR_ARG otherwise, and KICP_ERR_ARG with the system's reason when
+ * a file cannot be written (as kicp_map_save_pcd).  kicp_grid_write_map is pure host code and needs no GPU; kicp_grid_save_map is the
+ * readout followed by it. */
+int kicp_grid_save_map(const kicp_grid *grid, const char *prefix, unsigned int min_observations, double occupied_thresh, double free_thresh);
+int kicp_grid_write_map(const char *prefix, const signed char *occupancy, unsigned int width, unsigned int height, double cell, double origin_x,
+                        double origin_y, double occupied_thresh, double free_thresh);
+
 /* ---- pre-steps of the pipeline on the GPU (pipeline/KinematicICP.cpp:54-62) -----------
  * A kicp_pre owns KICP_PRE_BUFFERS device point buffers.  Results stay in HBM (feed kicp_register_device with
  * kicp_pre_device_ptr) and are downloaded only when the host needs them (map update, return values). */

@@ -57,6 +57,13 @@ class SearchWindow(C.Structure):
         return int(self.nx) * int(self.ny) * int(self.nyaw)
 
 
+class GridConfig(C.Structure):
+    """kicp_grid_config: width x height cells of side `cell` from (origin_x, origin_y); points with z_min <= z < z_max (base frame) whose
+    cell lies within ceil(max_ray / cell) cells of the sensor's count"""
+    _fields_ = [("cell", C.c_double), ("origin_x", C.c_double), ("origin_y", C.c_double), ("width", C.c_uint), ("height", C.c_uint),
+                ("z_min", C.c_double), ("z_max", C.c_double), ("max_ray", C.c_double)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p)
 
 _dp = C.POINTER(C.c_double)
@@ -133,6 +140,18 @@ _SIGNATURES = {
                                     C.POINTER(C.c_uint), _dp, C.POINTER(C.c_size_t)]),
     "kicp_relocalize_search": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, _dp, C.c_size_t, C.POINTER(SearchWindow), C.c_double, C.c_size_t, C.c_int,
                                          C.c_double, _dp, C.POINTER(C.c_ulonglong), _dp, _dp]),
+    "kicp_grid_create": (C.c_int, [C.POINTER(GridConfig), C.c_int, C.POINTER(C.c_void_p)]),
+    "kicp_grid_destroy": (None, [C.c_void_p]),
+    "kicp_grid_info": (C.c_int, [C.c_void_p, C.POINTER(GridConfig), C.POINTER(C.c_int), C.POINTER(C.c_ulonglong)]),
+    "kicp_grid_clear": (C.c_int, [C.c_void_p]),
+    "kicp_grid_integrate": (C.c_int, [C.c_void_p, _dp, C.c_size_t, _dp, _dp, C.POINTER(C.c_ulonglong)]),
+    "kicp_grid_integrate_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, _dp, _dp, C.POINTER(C.c_ulonglong)]),
+    "kicp_grid_counts": (C.c_int, [C.c_void_p, C.POINTER(C.c_ushort), C.c_size_t]),
+    "kicp_grid_set_counts": (C.c_int, [C.c_void_p, C.POINTER(C.c_ushort), C.c_size_t]),
+    "kicp_grid_occupancy": (C.c_int, [C.c_void_p, C.c_uint, C.POINTER(C.c_byte), C.c_size_t]),
+    "kicp_grid_occupancy_from_counts": (C.c_int, [C.POINTER(C.c_ushort), C.c_size_t, C.c_uint, C.POINTER(C.c_byte)]),
+    "kicp_grid_save_map": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint, C.c_double, C.c_double]),
+    "kicp_grid_write_map": (C.c_int, [C.c_char_p, C.POINTER(C.c_byte), C.c_uint, C.c_uint, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double]),
     "kicp_planar_grid": (C.c_size_t, [_dp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _dp, C.c_size_t]),
     "kicp_map_save_pcd": (C.c_int, [C.c_void_p, C.c_char_p]),
     "kicp_map_load_pcd": (C.c_int, [C.c_char_p, C.c_double, C.c_double, C.c_uint, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
@@ -350,6 +369,100 @@ class OccupancyPyramid:
         _check(lib().kicp_occ_level(self._h, int(level), words.ctypes.data_as(C.POINTER(C.c_uint)), total.value, None))
         dims = self.info()["dims"]
         return words.reshape(int(dims[2]), int(dims[1]), -1)
+
+
+def occupancy_from_counts(counts, min_observations=1):
+    """kicp_grid_occupancy_from_counts: the readout of counters shaped (..., 2) = (hits, misses) on the host -> int8 of the leading shape:
+    -1 below min_observations, else (100 hits + (hits + misses) / 2) / (hits + misses) in integers.  Needs no GPU."""
+    c = np.ascontiguousarray(counts, dtype=np.uint16)
+    if c.ndim < 1 or c.shape[-1] != 2:
+        raise KicpError(KICP_ERR_ARG, "counts must be shaped (..., 2): hits, misses")
+    out = np.empty(c.shape[:-1], dtype=np.int8)
+    _check(lib().kicp_grid_occupancy_from_counts(c.ctypes.data_as(C.POINTER(C.c_ushort)), out.size, int(min_observations),
+                                                 out.ctypes.data_as(C.POINTER(C.c_byte))))
+    return out
+
+
+def write_map(prefix, occupancy, cell, origin_x, origin_y, occupied_thresh=0.65, free_thresh=0.25):
+    """kicp_grid_write_map: `occupancy` (int8, shaped (height, width), row 0 at the origin) as <prefix>.pgm + <prefix>.yaml, the pair
+    map_server and Nav2 read.  Needs no GPU."""
+    occ = np.ascontiguousarray(occupancy, dtype=np.int8)
+    if occ.ndim != 2:
+        raise KicpError(KICP_ERR_ARG, "occupancy must be shaped (height, width)")
+    _check(lib().kicp_grid_write_map(os.fsencode(prefix), occ.ctypes.data_as(C.POINTER(C.c_byte)), occ.shape[1], occ.shape[0], float(cell), float(origin_x),
+                                     float(origin_y), float(occupied_thresh), float(free_thresh)))
+
+
+class OccupancyGrid:
+    """kicp_grid: a world-aligned 2-D grid of (hits, misses) counters a mapping run draws frame by frame - every used point's cell is
+    hit, the cells its ray from the sensor crosses are missed, once per cell per frame (include/kicp.h states the exact semantics).
+    It owns its device memory; the counters stay in HBM until they are asked for."""
+
+    def __init__(self, cell, origin_x, origin_y, width, height, z_min, z_max, max_ray, device=0):
+        self._h = None
+        cfg = GridConfig(float(cell), float(origin_x), float(origin_y), int(width), int(height), float(z_min), float(z_max), float(max_ray))
+        h = C.c_void_p()
+        _check(lib().kicp_grid_create(C.byref(cfg), int(device), C.byref(h)))
+        self._h, self.device, self.width, self.height = h, device, int(width), int(height)
+        self._last = np.zeros(4, dtype=np.uint64)
+
+    def __del__(self):
+        if getattr(self, "_h", None) and _lib is not None:
+            _lib.kicp_grid_destroy(self._h)
+            self._h = None
+
+    def info(self):
+        """-> dict: the configuration's fields, reach (cells) and frames (integrated since creation or clear)"""
+        cfg, reach, frames = GridConfig(), C.c_int(), C.c_ulonglong()
+        _check(lib().kicp_grid_info(self._h, C.byref(cfg), C.byref(reach), C.byref(frames)))
+        out = {name: getattr(cfg, name) for name, _ in GridConfig._fields_}
+        out.update(reach=reach.value, frames=frames.value)
+        return out
+
+    def clear(self):
+        _check(lib().kicp_grid_clear(self._h))
+
+    def integrate(self, frame, pose, sensor_xyz=(0.0, 0.0, 0.0)):
+        """kicp_grid_integrate: one frame of points in the base frame (host memory) at `pose`, the sensor at `sensor_xyz` in the base frame
+        -> (points used, points skipped, cells HIT, cells MISS)"""
+        a, p = _d(np.asarray(frame, dtype=np.float64).reshape(-1, 3))
+        s, sp = _d(np.asarray(sensor_xyz, dtype=np.float64).reshape(3))
+        _check(lib().kicp_grid_integrate(self._h, p if a.size else None, a.size // 3, _pose_ptr(pose), sp, self._last.ctypes.data_as(C.POINTER(C.c_ulonglong))))
+        return self.last_frame()
+
+    def integrate_device(self, device_frame, pose, sensor_xyz=(0.0, 0.0, 0.0), n=None):
+        """kicp_grid_integrate_device: the same for a DeviceFrame (or anything with .ptr and .n) already in HBM"""
+        s, sp = _d(np.asarray(sensor_xyz, dtype=np.float64).reshape(3))
+        count = device_frame.n if n is None else int(n)
+        _check(lib().kicp_grid_integrate_device(self._h, device_frame.ptr if count else None, count, _pose_ptr(pose), sp,
+                                                self._last.ctypes.data_as(C.POINTER(C.c_ulonglong))))
+        return self.last_frame()
+
+    def last_frame(self):
+        """(points used, points skipped, cells HIT, cells MISS) of the last integrated frame"""
+        return tuple(int(v) for v in self._last)
+
+    def counts(self):
+        """-> uint16 (height, width, 2): hits, misses"""
+        out = np.empty((self.height, self.width, 2), dtype=np.uint16)
+        _check(lib().kicp_grid_counts(self._h, out.ctypes.data_as(C.POINTER(C.c_ushort)), self.width * self.height))
+        return out
+
+    def set_counts(self, counts):
+        c = np.ascontiguousarray(counts, dtype=np.uint16)
+        if c.size % 2:
+            raise KicpError(KICP_ERR_ARG, "counts must hold (hits, misses) pairs")
+        _check(lib().kicp_grid_set_counts(self._h, c.ctypes.data_as(C.POINTER(C.c_ushort)), c.size // 2))
+
+    def occupancy(self, min_observations=1):
+        """kicp_grid_occupancy: the readout on the GPU -> int8 (height, width): -1 unknown, else 0 .. 100 - a nav_msgs/OccupancyGrid's data"""
+        out = np.empty((self.height, self.width), dtype=np.int8)
+        _check(lib().kicp_grid_occupancy(self._h, int(min_observations), out.ctypes.data_as(C.POINTER(C.c_byte)), out.size))
+        return out
+
+    def save_map(self, prefix, min_observations=1, occupied_thresh=0.65, free_thresh=0.25):
+        """kicp_grid_save_map: <prefix>.pgm + <prefix>.yaml of the readout"""
+        _check(lib().kicp_grid_save_map(self._h, os.fsencode(prefix), int(min_observations), float(occupied_thresh), float(free_thresh)))
 
 
 class VoxelHashMap:

@@ -97,6 +97,26 @@ inline kicp_search_window search_window_around(const kicp_occ *occ, const Eigen:
     check(kicp_search_window_around(occ, c, half_x, half_y, z, yaw_step, &w), "kicp_bridge::search_window_around");
     return w;
 }
+// The 2-D occupancy grid a mapping run draws for a planner (kicp.h kicp_grid_*): KinematicICP::EnableGrid takes a GridConfig and holds
+// the handle shared, so a node can keep KinematicICP::Grid() for its map publisher.  clone_grid is the deep copy a copied pipeline
+// gets: a grid of the same configuration with the same counters (its frame count starts again).
+using GridConfig = kicp_grid_config;
+inline std::shared_ptr<kicp_grid> make_grid(const GridConfig &config, int device = -1) {
+    kicp_grid *grid = nullptr;
+    check(kicp_grid_create(&config, device < 0 ? default_device() : device, &grid), "kicp_bridge::make_grid");
+    return std::shared_ptr<kicp_grid>(grid, kicp_grid_destroy);
+}
+inline std::shared_ptr<kicp_grid> clone_grid(const kicp_grid *grid, int device = -1) {
+    if (!grid) return nullptr;
+    GridConfig config{};
+    check(kicp_grid_info(grid, &config, nullptr, nullptr), "kicp_bridge::clone_grid");
+    const size_t cells = static_cast<size_t>(config.width) * config.height;
+    std::vector<unsigned short> counts(2 * cells);
+    check(kicp_grid_counts(grid, counts.data(), cells), "kicp_bridge::clone_grid");
+    auto copy = make_grid(config, device);
+    check(kicp_grid_set_counts(copy.get(), counts.data(), cells), "kicp_bridge::clone_grid");
+    return copy;
+}
 // a warning the reference has no channel for: once per process on stderr
 inline void warn_once(const char *message) {
     static bool said = false;

@@ -9,10 +9,12 @@
 #pragma once
 #include <Eigen/Core>
 #include <cmath>
+#include <cstdint>
 #include <cstdlib>
 #include <kiss_icp/core/Preprocessing.hpp>
 #include <kiss_icp/core/VoxelHashMap.hpp>
 #include <kiss_icp/core/VoxelUtils.hpp>
+#include <memory>
 #include <sophus/se3.hpp>
 #include <stdexcept>
 #include <string>
@@ -68,14 +70,16 @@ public:
     }
     ~KinematicICP() { kicp_pre_destroy(pre_); }
     // copyable and movable like the reference's class (every member is held by value there, KinematicICP.hpp:100-108): a copy owns
-    // a deep copy of the map, a registration handle of its own and its own pre-step workspace
+    // a deep copy of the map (and of the occupancy grid, when one is enabled), a registration handle of its own and its own pre-step workspace
     KinematicICP(const KinematicICP &o)
         : last_pose_(o.last_pose_),
           registration_(o.registration_),
           correspondence_threshold_(o.correspondence_threshold_),
           config_(o.config_),
           preprocessor_(o.preprocessor_),
-          local_map_(o.local_map_) {
+          local_map_(o.local_map_),
+          grid_(kicp_bridge::clone_grid(o.grid_.get())),
+          sensor_in_base_(o.sensor_in_base_) {
 #ifndef KICP_HOST_PRESTEPS
         kicp_bridge::check(kicp_pre_create(kicp_bridge::default_device(), &pre_), "KinematicICP");
 #endif
@@ -87,7 +91,9 @@ public:
           config_(o.config_),
           preprocessor_(o.preprocessor_),
           local_map_(std::move(o.local_map_)),
-          pre_(o.pre_) {
+          pre_(o.pre_),
+          grid_(std::move(o.grid_)),
+          sensor_in_base_(o.sensor_in_base_) {
         o.pre_ = nullptr;
     }
     KinematicICP &operator=(KinematicICP o) noexcept {  // copy / move and swap
@@ -96,12 +102,14 @@ public:
         std::swap(correspondence_threshold_, o.correspondence_threshold_), std::swap(config_, o.config_), std::swap(preprocessor_, o.preprocessor_);
         local_map_ = std::move(o.local_map_);
         std::swap(pre_, o.pre_);
+        std::swap(grid_, o.grid_), std::swap(sensor_in_base_, o.sensor_in_base_);
         return *this;
     }
 
     // pipeline/KinematicICP.cpp:48-85
     Vector3dVectorTuple RegisterFrame(const std::vector<Eigen::Vector3d> &frame, const std::vector<double> &timestamps,
                                       const Sophus::SE3d &lidar_to_base, const Sophus::SE3d &relative_odometry) {
+        sensor_in_base_ = lidar_to_base.translation();
         const Sophus::SE3d relative_odometry_in_lidar = lidar_to_base.inverse() * relative_odometry * lidar_to_base;
 #ifndef KICP_HOST_PRESTEPS
         double rel_lidar[7], ext[7];
@@ -132,6 +140,7 @@ public:
         correspondence_threshold_.UpdateOdometryError(odometry_error);
         if (config_.update_map) local_map_.Update(frame_downsample, new_pose);
         last_pose_ = new_pose;
+        if (grid_) IntegrateGrid(kicp_bridge::xyz(preprocessed_frame_in_base), preprocessed_frame_in_base.size(), false);
         return {preprocessed_frame_in_base, source};
 #endif
     }
@@ -163,6 +172,7 @@ public:
         kicp_bridge::check(kicp_pre_ingest_ahead(pre_, data, n_points, &layout, nullptr), "AnnounceNextCloud");
     }
     Vector3dVectorTuple RegisterIngestedFrame(const Sophus::SE3d &lidar_to_base, const Sophus::SE3d &relative_odometry) {
+        sensor_in_base_ = lidar_to_base.translation();
         const Sophus::SE3d relative_odometry_in_lidar = lidar_to_base.inverse() * relative_odometry * lidar_to_base;
         double rel_lidar[7], ext[7];
         kicp_bridge::to_params(relative_odometry_in_lidar, rel_lidar);
@@ -186,6 +196,7 @@ public:
     // pointer means the cloud is not produced at all (a topic without subscriber): the frame is then not even pushed.
     void RegisterFrameF32(const std::vector<Eigen::Vector3d> &frame, const std::vector<double> &timestamps, const Sophus::SE3d &lidar_to_base,
                           const Sophus::SE3d &relative_odometry, std::vector<uint8_t> *frame_data, std::vector<uint8_t> *keypoints_data) {
+        sensor_in_base_ = lidar_to_base.translation();
         const Sophus::SE3d relative_odometry_in_lidar = lidar_to_base.inverse() * relative_odometry * lidar_to_base;
         double rel_lidar[7], ext[7];
         kicp_bridge::to_params(relative_odometry_in_lidar, rel_lidar);
@@ -202,6 +213,7 @@ public:
     }
     void RegisterIngestedFrameF32(const Sophus::SE3d &lidar_to_base, const Sophus::SE3d &relative_odometry, std::vector<uint8_t> *frame_data,
                                   std::vector<uint8_t> *keypoints_data) {
+        sensor_in_base_ = lidar_to_base.translation();
         const Sophus::SE3d relative_odometry_in_lidar = lidar_to_base.inverse() * relative_odometry * lidar_to_base;
         double rel_lidar[7], ext[7];
         kicp_bridge::to_params(relative_odometry_in_lidar, rel_lidar);
@@ -278,6 +290,28 @@ public:
         return found;
     }
 
+    // ---- backend extension: an occupancy grid for the planner (INTEGRATION.md "An occupancy grid for the planner") ----
+    // With a grid enabled, RegisterFrame, RegisterIngestedFrame and their F32 variants integrate the frame they return - the deskewed,
+    // cropped frame in the base frame, all of it - into a 2-D grid after the registration and before they return: at the new pose, with
+    // the translation of lidar_to_base as the sensor's origin, every point in the band a hit and the cells its ray crosses free (kicp.h
+    // kicp_grid_*).  Poses, thresholds, returned clouds and the map are what they are without the grid.  Config::update_map = false
+    // does not stop it: localising in a saved map while drawing a grid of what is seen now is legitimate.  SetPose leaves it alone.
+    // Grid() is the shared handle (null without a grid): a node may keep it for the kicp_grid_* calls of its map publisher.
+    void EnableGrid(const kicp_bridge::GridConfig &config) { grid_ = kicp_bridge::make_grid(config); }
+    void DisableGrid() { grid_.reset(); }
+    std::shared_ptr<kicp_grid> Grid() const { return grid_; }
+    // the readout, a nav_msgs/OccupancyGrid's `data`: width * height bytes, row-major from the origin, -1 unknown, else 0 .. 100
+    void GridOccupancy(std::vector<int8_t> &data, unsigned int min_observations = 1) const {
+        kicp_grid_config config{};
+        kicp_bridge::check(kicp_grid_info(RequireGrid("GridOccupancy"), &config, nullptr, nullptr), "GridOccupancy");
+        data.resize(static_cast<size_t>(config.width) * config.height);
+        kicp_bridge::check(kicp_grid_occupancy(grid_.get(), min_observations, reinterpret_cast<signed char *>(data.data()), data.size()), "GridOccupancy");
+    }
+    // <prefix>.pgm + <prefix>.yaml, the pair map_server and Nav2 read
+    void SaveGrid(const std::string &prefix, unsigned int min_observations = 1, double occupied_thresh = 0.65, double free_thresh = 0.25) const {
+        kicp_bridge::check(kicp_grid_save_map(RequireGrid("SaveGrid"), prefix.c_str(), min_observations, occupied_thresh, free_thresh), "SaveGrid");
+    }
+
     std::vector<Eigen::Vector3d> LocalMap() const { return local_map_.Pointcloud(); }
     const kiss_icp::VoxelHashMap &VoxelMap() const { return local_map_; }
     kiss_icp::VoxelHashMap &VoxelMap() { return local_map_; }
@@ -285,6 +319,18 @@ public:
     Sophus::SE3d &pose() { return last_pose_; }
 
 protected:
+    const kicp_grid *RequireGrid(const char *who) const {
+        if (!grid_) throw std::runtime_error(std::string("KinematicICP::") + who + ": call EnableGrid first");
+        return grid_.get();
+    }
+    // one frame into the grid at last_pose_ (already the new pose), from HBM or from host memory
+    void IntegrateGrid(const double *xyz, size_t n, bool on_device) {
+        double pose[7];
+        kicp_bridge::to_params(last_pose_, pose);
+        const double sensor[3] = {sensor_in_base_.x(), sensor_in_base_.y(), sensor_in_base_.z()};
+        kicp_bridge::check(on_device ? kicp_grid_integrate_device(grid_.get(), xyz, n, pose, sensor, nullptr) : kicp_grid_integrate(grid_.get(), xyz, n, pose, sensor, nullptr),
+                           "occupancy grid");
+    }
 #ifndef KICP_HOST_PRESTEPS
     // From the moment the backend's helper thread holds a pointer into the result's frame vector: should any later step throw,
     // the download is collected (and dropped) before the vector is destroyed, so nothing is ever copied into freed memory.
@@ -309,6 +355,8 @@ protected:
         // (the map update's kernels run while this thread collects the two returned clouds: nothing below touches the map or buffer 1)
         if (config_.update_map) local_map_.UpdateDeviceBegin(kicp_pre_device_ptr(pre_, 1, nullptr), n_down, new_pose);
         last_pose_ = new_pose;
+        // the occupancy grid, when enabled: the whole preprocessed frame (buffer 0, complete since the pre-steps returned) at the new pose
+        if (grid_) IntegrateGrid(kicp_pre_device_ptr(pre_, 0, nullptr), counts[0], true);
     }
     Vector3dVectorTuple RegisterChained(Vector3dVectorTuple &result, DownloadGuard &guard, const size_t counts[3], const Sophus::SE3d &relative_odometry) {
         kicp_bridge::Trace trace("registration");
@@ -370,6 +418,8 @@ protected:
     kiss_icp::VoxelHashMap local_map_;
     kicp_pre *pre_ = nullptr;  // device workspace of the pre-steps (backend detail)
     std::shared_ptr<kicp_occ> occupancy_;  // BuildOccupancy's snapshot of the map (backend detail)
+    std::shared_ptr<kicp_grid> grid_;      // EnableGrid's occupancy grid (backend detail); null: no grid
+    Eigen::Vector3d sensor_in_base_ = Eigen::Vector3d(0.0, 0.0, 0.0);  // the translation of the last frame's lidar_to_base
 };
 
 }  // namespace kinematic_icp::pipeline

@@ -1,0 +1,234 @@
+// kicp_grid.hip -- the 2-D occupancy grid a mapping run draws beside its voxel map (kicp_grid_*; include/kicp.h states the semantics):
+// per frame the used points' endpoint cells are HIT and the cells their rays cross are MISS, once per cell per frame.  Kernels:
+// kicp_grid.hpp; the geometry they share with the host entries: kicp_grid_host.hpp.  A handle owns its stream, its staging buffer and
+// its device memory: the counters (cells x 2 x 16 bit) and the two frame-local planes over the window.
+#include <cerrno>
+#include <memory>
+
+#include "kicp_grid.hpp"
+#include "kicp_internal.hpp"
+
+using namespace kicp;
+using namespace kicp::host;
+
+struct kicp_grid {
+    int device = 0;
+    kicp_grid_config cfg{};
+    GridGeom geom{};
+    size_t cells = 0;
+    uint32_t plane_words = 0;  // ceil((2 reach + 1)^2 / 4)
+    unsigned long long frames = 0;
+    hipStream_t stream = nullptr;
+    DevBuf<uint16_t> d_counts;          // cells x 2: hits, misses
+    DevBuf<uint32_t> d_hit, d_miss;     // the planes, zero between frames
+    DevBuf<unsigned int> d_stats;       // used, cells HIT, cells MISS of the frame in flight, and the length of d_rays
+    DevBuf<uint32_t> d_rays;            // the frame's ray list: the window cells that became HIT (room for one per point)
+    PinnedBuf<unsigned int> h_stats;
+    DevBuf<double> d_frame;             // kicp_grid_integrate's upload
+    DevBuf<int8_t> d_occupancy;         // kicp_grid_occupancy's readout
+    HostStage stage;
+    ~kicp_grid() {
+        if (stream) (void)hipStreamSynchronize(stream), (void)hipStreamDestroy(stream);
+    }
+};
+
+namespace {
+constexpr size_t kGridMaxPoints = 0x7FFFFFF0ull / 3;
+
+int check_thresholds(double occupied_thresh, double free_thresh) {
+    if (!(0.0 <= free_thresh && free_thresh < occupied_thresh && occupied_thresh <= 1.0))
+        return fail(KICP_ERR_ARG, "thresholds must satisfy 0 <= free_thresh < occupied_thresh <= 1");
+    return KICP_OK;
+}
+// the frame at d_xyz (n points; arguments checked): three launches, the statistics back, the stream drained
+int integrate_on_device(kicp_grid *grid, const double *d_xyz, size_t n, const double pose_qt[7], const double sensor_xyz[3], unsigned long long out_stats[4]) {
+    unsigned long long stats[4] = {0, n, 0, 0};
+    if (n) {
+        const GridFrame f = grid_frame(grid->geom, pose_qt, sensor_xyz);
+        hipStream_t st = grid->stream;
+        if (n > grid->d_rays.capacity()) {
+            HIP_TRY(hipStreamSynchronize(st));
+            if (int rc = grid->d_rays.reserve(n + n / 2)) return rc;
+        }
+        HIP_TRY(hipMemsetAsync(grid->d_stats.get(), 0, 4 * sizeof(unsigned int), st));
+        const uint32_t blocks = static_cast<uint32_t>((n + kGridBlock - 1) / kGridBlock);
+        hipLaunchKernelGGL(k_grid_mark, dim3(blocks), dim3(kGridBlock), 0, st, d_xyz, static_cast<uint32_t>(n), grid->geom, f, grid->d_hit.get(), grid->d_rays.get(),
+                           grid->d_stats.get());
+        // one wave per ray, at most one ray per point; the waves of up to 2048 workgroups stride over the list, whose length is on the device
+        hipLaunchKernelGGL(k_grid_rays, dim3(std::min(blocks, 2048u)), dim3(kGridBlock), 0, st, grid->d_rays.get(), grid->d_stats.get() + 3, grid->geom.reach,
+                           reinterpret_cast<uint8_t *>(grid->d_miss.get()));
+        hipLaunchKernelGGL(k_grid_apply, dim3((grid->plane_words + kGridBlock - 1) / kGridBlock), dim3(kGridBlock), 0, st, grid->d_hit.get(), grid->d_miss.get(),
+                           grid->plane_words, grid->geom, f, grid->d_counts.get(), grid->d_stats.get());
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(grid->h_stats.get(), grid->d_stats.get(), 4 * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        const unsigned int *h = grid->h_stats.get();
+        stats[0] = h[0], stats[1] = n - h[0], stats[2] = h[1], stats[3] = h[2];
+    }
+    ++grid->frames;
+    if (out_stats)
+        for (int k = 0; k < 4; ++k) out_stats[k] = stats[k];
+    return KICP_OK;
+}
+int check_frame_args(const kicp_grid *grid, const double *xyz, size_t n, const double *pose_qt, const double *sensor_xyz) {
+    if (!grid || !pose_qt || !sensor_xyz || (!xyz && n)) return fail(KICP_ERR_ARG, "null argument");
+    if (n > kGridMaxPoints) return fail(KICP_ERR_CAPACITY, "frame too large");
+    return KICP_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int kicp_grid_create(const kicp_grid_config *cfg, int device, kicp_grid **out) {
+    KICP_TRACE_CALL();
+    if (!cfg || !out) return fail(KICP_ERR_ARG, "null argument");
+    *out = nullptr;
+    if (!(cfg->cell > 0.0) || !std::isfinite(cfg->cell)) return fail(KICP_ERR_ARG, "cell must be positive and finite");
+    if (!(cfg->max_ray > 0.0) || !std::isfinite(cfg->max_ray)) return fail(KICP_ERR_ARG, "max_ray must be positive and finite");
+    if (!std::isfinite(cfg->origin_x) || !std::isfinite(cfg->origin_y)) return fail(KICP_ERR_ARG, "the origin must be finite");
+    if (!(cfg->z_min < cfg->z_max)) return fail(KICP_ERR_ARG, "the band needs z_min < z_max");
+    if (cfg->width == 0 || cfg->height == 0) return fail(KICP_ERR_ARG, "width and height must be at least 1");
+    const unsigned long long cells = static_cast<unsigned long long>(cfg->width) * cfg->height;
+    if (cells > kGridMaxCells)
+        return fail(KICP_ERR_CAPACITY, "the grid would have " + std::to_string(cfg->width) + " x " + std::to_string(cfg->height) + " = " + std::to_string(cells) +
+                                           " cells (limit 2^28 = " + std::to_string(kGridMaxCells) + ")");
+    const double reach = std::ceil(cfg->max_ray / cfg->cell);
+    if (!(reach <= static_cast<double>(kGridMaxReach)))
+        return fail(KICP_ERR_CAPACITY, "max_ray / cell gives a reach of " + std::to_string(reach) + " cells (limit " + std::to_string(kGridMaxReach) + ")");
+    if (int rc = set_device(device)) return rc;
+    std::unique_ptr<kicp_grid> grid(new kicp_grid);
+    grid->device = device, grid->cfg = *cfg, grid->cells = static_cast<size_t>(cells);
+    grid->geom = GridGeom{cfg->cell, cfg->origin_x, cfg->origin_y, cfg->z_min, cfg->z_max, cfg->width, cfg->height, static_cast<int32_t>(reach)};
+    const unsigned long long side = 2ull * static_cast<unsigned long long>(grid->geom.reach) + 1ull;
+    grid->plane_words = static_cast<uint32_t>((side * side + 3ull) / 4ull);
+    HIP_TRY(hipStreamCreateWithFlags(&grid->stream, hipStreamNonBlocking));
+    if (int rc = grid->d_counts.reserve(2 * grid->cells)) return rc;
+    if (int rc = grid->d_hit.reserve(grid->plane_words)) return rc;
+    if (int rc = grid->d_miss.reserve(grid->plane_words)) return rc;
+    if (int rc = grid->d_stats.reserve(4)) return rc;
+    if (int rc = grid->h_stats.reserve(4, hipHostMallocDefault, false)) return rc;
+    HIP_TRY(hipMemsetAsync(grid->d_counts.get(), 0, 2 * grid->cells * sizeof(uint16_t), grid->stream));
+    HIP_TRY(hipMemsetAsync(grid->d_hit.get(), 0, grid->plane_words * sizeof(uint32_t), grid->stream));
+    HIP_TRY(hipMemsetAsync(grid->d_miss.get(), 0, grid->plane_words * sizeof(uint32_t), grid->stream));
+    HIP_TRY(hipStreamSynchronize(grid->stream));
+    *out = grid.release();
+    return KICP_OK;
+}
+void kicp_grid_destroy(kicp_grid *grid) {
+    if (!grid) return;
+    (void)hipSetDevice(grid->device);
+    delete grid;
+}
+int kicp_grid_info(const kicp_grid *grid, kicp_grid_config *out_config, int *out_reach, unsigned long long *out_frames) {
+    if (!grid) return fail(KICP_ERR_ARG, "null argument");
+    if (out_config) *out_config = grid->cfg;
+    if (out_reach) *out_reach = grid->geom.reach;
+    if (out_frames) *out_frames = grid->frames;
+    return KICP_OK;
+}
+int kicp_grid_clear(kicp_grid *grid) {
+    KICP_TRACE_CALL();
+    if (!grid) return fail(KICP_ERR_ARG, "null argument");
+    if (int rc = set_device(grid->device)) return rc;
+    HIP_TRY(hipMemsetAsync(grid->d_counts.get(), 0, 2 * grid->cells * sizeof(uint16_t), grid->stream));
+    HIP_TRY(hipStreamSynchronize(grid->stream));
+    grid->frames = 0;
+    return KICP_OK;
+}
+int kicp_grid_integrate(kicp_grid *grid, const double *frame_xyz, size_t n, const double pose_qt[7], const double sensor_xyz[3], unsigned long long out_stats[4]) {
+    KICP_TRACE_CALL();
+    if (int rc = check_frame_args(grid, frame_xyz, n, pose_qt, sensor_xyz)) return rc;
+    if (int rc = set_device(grid->device)) return rc;
+    if (n) {
+        if (3 * n > grid->d_frame.capacity()) {
+            HIP_TRY(hipStreamSynchronize(grid->stream));
+            if (int rc = grid->d_frame.reserve(3 * n + 3 * n / 2)) return rc;
+        }
+        if (int rc = staged_upload(grid->stage, 0, grid->d_frame.get(), frame_xyz, n * 24, grid->stream)) return rc;
+    }
+    return integrate_on_device(grid, grid->d_frame.get(), n, pose_qt, sensor_xyz, out_stats);
+}
+int kicp_grid_integrate_device(kicp_grid *grid, const double *d_frame_xyz, size_t n, const double pose_qt[7], const double sensor_xyz[3],
+                               unsigned long long out_stats[4]) {
+    KICP_TRACE_CALL();
+    if (int rc = check_frame_args(grid, d_frame_xyz, n, pose_qt, sensor_xyz)) return rc;
+    if (int rc = set_device(grid->device)) return rc;
+    return integrate_on_device(grid, d_frame_xyz, n, pose_qt, sensor_xyz, out_stats);
+}
+int kicp_grid_counts(const kicp_grid *grid, unsigned short *out, size_t cap_cells) {
+    KICP_TRACE_CALL();
+    if (!grid || !out) return fail(KICP_ERR_ARG, "null argument");
+    if (cap_cells != grid->cells) return fail(KICP_ERR_ARG, "cap_cells must be the grid's " + std::to_string(grid->cells) + " cells");
+    if (int rc = set_device(grid->device)) return rc;
+    HIP_TRY(hipMemcpyAsync(out, grid->d_counts.get(), 2 * grid->cells * sizeof(uint16_t), hipMemcpyDeviceToHost, grid->stream));
+    HIP_TRY(hipStreamSynchronize(grid->stream));
+    return KICP_OK;
+}
+int kicp_grid_set_counts(kicp_grid *grid, const unsigned short *in, size_t cells) {
+    KICP_TRACE_CALL();
+    if (!grid || !in) return fail(KICP_ERR_ARG, "null argument");
+    if (cells != grid->cells) return fail(KICP_ERR_ARG, "cells must be the grid's " + std::to_string(grid->cells) + " cells");
+    if (int rc = set_device(grid->device)) return rc;
+    HIP_TRY(hipMemcpyAsync(grid->d_counts.get(), in, 2 * grid->cells * sizeof(uint16_t), hipMemcpyHostToDevice, grid->stream));
+    HIP_TRY(hipStreamSynchronize(grid->stream));
+    return KICP_OK;
+}
+int kicp_grid_occupancy(const kicp_grid *cgrid, unsigned int min_observations, signed char *out, size_t cap_cells) {
+    KICP_TRACE_CALL();
+    if (!cgrid || !out) return fail(KICP_ERR_ARG, "null argument");
+    if (min_observations < 1u) return fail(KICP_ERR_ARG, "min_observations must be at least 1");
+    if (cap_cells != cgrid->cells) return fail(KICP_ERR_ARG, "cap_cells must be the grid's " + std::to_string(cgrid->cells) + " cells");
+    kicp_grid *grid = const_cast<kicp_grid *>(cgrid);  // logically const: the readout's buffer is scratch
+    if (int rc = set_device(grid->device)) return rc;
+    if (int rc = grid->d_occupancy.reserve(grid->cells)) return rc;
+    hipLaunchKernelGGL(k_grid_readout, dim3(static_cast<uint32_t>((grid->cells + kGridBlock - 1) / kGridBlock)), dim3(kGridBlock), 0, grid->stream,
+                       grid->d_counts.get(), grid->cells, min_observations, grid->d_occupancy.get());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, grid->d_occupancy.get(), grid->cells, hipMemcpyDeviceToHost, grid->stream));
+    HIP_TRY(hipStreamSynchronize(grid->stream));
+    return KICP_OK;
+}
+int kicp_grid_occupancy_from_counts(const unsigned short *counts, size_t cells, unsigned int min_observations, signed char *out) {
+    if ((!counts || !out) && cells) return fail(KICP_ERR_ARG, "null argument");
+    if (min_observations < 1u) return fail(KICP_ERR_ARG, "min_observations must be at least 1");
+    for (size_t i = 0; i < cells; ++i) out[i] = grid_readout(counts[2 * i], counts[2 * i + 1], min_observations);
+    return KICP_OK;
+}
+int kicp_grid_write_map(const char *prefix, const signed char *occupancy, unsigned int width, unsigned int height, double cell, double origin_x, double origin_y,
+                        double occupied_thresh, double free_thresh) {
+    if (!prefix || !occupancy) return fail(KICP_ERR_ARG, "null argument");
+    if (width == 0 || height == 0) return fail(KICP_ERR_ARG, "width and height must be at least 1");
+    if (!(cell > 0.0) || !std::isfinite(cell) || !std::isfinite(origin_x) || !std::isfinite(origin_y))
+        return fail(KICP_ERR_ARG, "cell must be positive and finite, the origin finite");
+    if (int rc = check_thresholds(occupied_thresh, free_thresh)) return rc;
+    const std::string pgm = std::string(prefix) + ".pgm", yaml = std::string(prefix) + ".yaml";
+    std::FILE *f = std::fopen(pgm.c_str(), "wb");
+    if (!f) return fail(KICP_ERR_ARG, "cannot write " + pgm + ": " + std::strerror(errno));
+    bool ok = std::fprintf(f, "P5\n%u %u\n255\n", width, height) > 0;
+    std::vector<unsigned char> row(width);
+    for (unsigned int iy = height; ok && iy-- > 0;) {  // the image's first row is the grid's highest iy
+        for (unsigned int ix = 0; ix < width; ++ix) row[ix] = grid_pixel(occupancy[static_cast<size_t>(iy) * width + ix], occupied_thresh, free_thresh);
+        ok = std::fwrite(row.data(), 1, row.size(), f) == row.size();
+    }
+    ok = (std::fclose(f) == 0) && ok;
+    if (!ok) return fail(KICP_ERR_ARG, "cannot write " + pgm + ": " + std::strerror(errno));
+    f = std::fopen(yaml.c_str(), "wb");
+    if (!f) return fail(KICP_ERR_ARG, "cannot write " + yaml + ": " + std::strerror(errno));
+    const size_t slash = pgm.find_last_of('/');
+    ok = std::fprintf(f, "image: %s\nmode: trinary\nresolution: %.17g\norigin: [%.17g, %.17g, 0]\nnegate: 0\noccupied_thresh: %.17g\nfree_thresh: %.17g\n",
+                      pgm.c_str() + (slash == std::string::npos ? 0 : slash + 1), cell, origin_x, origin_y, occupied_thresh, free_thresh) > 0;
+    ok = (std::fclose(f) == 0) && ok;
+    if (!ok) return fail(KICP_ERR_ARG, "cannot write " + yaml + ": " + std::strerror(errno));
+    return KICP_OK;
+}
+int kicp_grid_save_map(const kicp_grid *grid, const char *prefix, unsigned int min_observations, double occupied_thresh, double free_thresh) {
+    KICP_TRACE_CALL();
+    if (!grid || !prefix) return fail(KICP_ERR_ARG, "null argument");
+    if (int rc = check_thresholds(occupied_thresh, free_thresh)) return rc;
+    std::vector<signed char> occupancy(grid->cells);
+    if (int rc = kicp_grid_occupancy(grid, min_observations, occupancy.data(), grid->cells)) return rc;
+    return kicp_grid_write_map(prefix, occupancy.data(), grid->cfg.width, grid->cfg.height, grid->cfg.cell, grid->cfg.origin_x, grid->cfg.origin_y, occupied_thresh,
+                               free_thresh);
+}
+
+}  // extern "C"
