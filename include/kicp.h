@@ -201,7 +201,11 @@ int kicp_reg_set_config(kicp_reg *reg, const kicp_reg_config *config); /* the re
  *   "resident_generic" 1 (default): scans beyond the small-scan kernels and up to 131 072 points keep the generic kernel's latency build
  *                  resident for the later iterations of a call too; 0: one launch per iteration
  * Batches of independent scans (kicp_register_device_batch):
- *   "batch_queues"   (default 4, 0 .. 8) scans in flight at a time, each on a handle and HSA queue of its own; < 2: off
+ *   "batch_queues"   (default 8, 0 .. 16) scans in flight at a time, on batch_queues / batch_group handles with an HSA queue each; < 2: off
+ *   "batch_group"    (default 4, 1 .. 8) scans whose passes share ONE launch of the pass kernel on such a queue (a 2-D grid: a job per scan);
+ *                  1: a launch per scan and pass, each scan on a queue of its own.  That is also what sharded batches, batches too short to
+ *                  give every queue two groups and batches in which most scans take another kernel (the small-scan kernels, sub-lanes per
+ *                  query) run: on min("batch_queues", 8) queues once the caller has set "batch_queues", on four until then
  *   "batch_resident" 1 (default): batches "batch_queues" does not take keep ONE resident kernel across the batch's scans; 0: scan by scan
  *   "batch_depth"    (default 3, 1 .. 4) scans that kernel has in flight
  *   "batch_threads"  (default 8, 0 .. 9) batches of scans that leave most of the device empty: up to this many resident kernels side by
@@ -248,7 +252,7 @@ int kicp_register_device(kicp_reg *reg, kicp_map *map, const double *d_frame_xyz
  *     "batch_threads" (default 8) resident kernels side by side - as many as fit the device at once -, each with a contiguous part of
  *     the batch, "batch_depth" scans of it in flight, and a host thread of the library's pool;
  *   - otherwise, batches of at least two scans per queue that hold at least one scan for the generic pass kernel (more than 4 096 points by
- *     default): option "batch_queues" (default 4) scans at a time, each on a handle + HSA queue of its own (clones of `reg`,
+ *     default): option "batch_queues" (default 8) scans at a time, "batch_group" (default 4) per launch, on handles + HSA queues of their own (clones of `reg`,
  *     created on first use and kept until kicp_reg_destroy(reg); they follow reg's configuration and kernel-shape options at every
  *     call), every pass an ordinary launch (large scans: the four-waves-per-SIMD build; small scans in such a batch: their own
  *     kernels, one launch per pass); the thread goes round the scans in flight: rows complete -> solve -> next pass or next scan;

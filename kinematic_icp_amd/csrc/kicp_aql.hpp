@@ -23,6 +23,7 @@
 #include <hsa/hsa.h>
 #include <hsa/hsa_ext_amd.h>
 
+#include <algorithm>
 #include <chrono>
 #include <cstdint>
 #include <cstdio>
@@ -124,16 +125,21 @@ public:
         return kernels_.emplace(prefix, k).first->second;
     }
     size_t symbol_count() const { return symbols_.size(); }
+    static constexpr size_t max_kernarg_bytes() { return kSlotBytes; }
     const char *kernarg_place() const { return kernarg_in_hbm_ ? (hdp_flush_ ? "device memory + HDP flush" : "device memory") : "host memory"; }
 
-    // one 1-D dispatch: `grid` workgroups of `block` work-items; `args` = the kernel's explicit argument block
+    // one dispatch: `grid` workgroups of `block` work-items; `args` = the kernel's explicit argument block
     // acquire / release: HSA_FENCE_SCOPE_{NONE, AGENT, SYSTEM} of the packet's fences
+    // `grid_y` > 1: a 2-D grid of grid x grid_y workgroups (k_pass_gather32_jobs: blockIdx.y = the job).  `explicit_bytes` (0: args_bytes):
+    // the size of the kernel's whole explicit block where the caller fills only its first args_bytes - the tail of a list of jobs that
+    // is not full is never read and not written either.
     bool dispatch(const AqlKernel &k, uint32_t grid, uint32_t block_size, const void *args, size_t args_bytes, int acquire = HSA_FENCE_SCOPE_SYSTEM,
-                  int release = HSA_FENCE_SCOPE_SYSTEM) {
-        const size_t implicit = (args_bytes + 7) & ~size_t(7);  // code object v5: the implicit arguments follow, 8-byte aligned
+                  int release = HSA_FENCE_SCOPE_SYSTEM, uint32_t grid_y = 1u, size_t explicit_bytes = 0) {
+        if (explicit_bytes < args_bytes) explicit_bytes = args_bytes;
+        const size_t implicit = (explicit_bytes + 7) & ~size_t(7);  // code object v5: the implicit arguments follow, 8-byte aligned
         // (a kernel that reads no hidden argument has none: its kernarg segment ends with the explicit block)
         const bool has_implicit = implicit + 80 <= k.kernarg_size;
-        if (!ready || !k.usable || queue_error || args_bytes > k.kernarg_size) return false;
+        if (!ready || !k.usable || queue_error || explicit_bytes > k.kernarg_size || grid_y == 0u || grid_y > 0xFFFFu) return false;
         unsigned char *ka = kernarg_ + (slot_++ % kSlots) * kSlotBytes;
         // The whole kernarg segment is built in a local block (zeroed: every hidden argument this file does not set - hostcall /
         // printf buffer, heap, dynamic LDS size, queue pointer - reads as 0 instead of a stale byte of an earlier dispatch) and
@@ -142,13 +148,23 @@ public:
         // hidden_global_offset_{x,y,z} u64 @40, hidden_grid_dims u16 @64 (llvm AMDGPU usage, code object v5)
         alignas(64) unsigned char block[kSlotBytes];
         const size_t total = (static_cast<size_t>(k.kernarg_size) + 63) & ~size_t(63);
-        std::memset(block, 0, total);
-        std::memcpy(block, args, args_bytes);
-        unsigned char *ia = block + implicit;
-        const uint32_t counts[3] = {grid, 1u, 1u};
-        const uint16_t sizes[3] = {static_cast<uint16_t>(block_size), 1, 1}, dims = 1;
-        if (has_implicit) std::memcpy(ia, counts, 12), std::memcpy(ia + 12, sizes, 6), std::memcpy(ia + 64, &dims, 2);
-        std::memcpy(ka, block, total);
+        const uint32_t counts[3] = {grid, grid_y, 1u};
+        const uint16_t sizes[3] = {static_cast<uint16_t>(block_size), 1, 1}, dims = grid_y > 1u ? 2 : 1;
+        if (explicit_bytes == args_bytes) {
+            std::memset(block, 0, total);
+            std::memcpy(block, args, args_bytes);
+            unsigned char *ia = block + implicit;
+            if (has_implicit) std::memcpy(ia, counts, 12), std::memcpy(ia + 12, sizes, 6), std::memcpy(ia + 64, &dims, 2);
+            std::memcpy(ka, block, total);
+        } else {  // what the caller filled goes out as it is; the implicit arguments follow at their place behind the whole explicit block
+            std::memcpy(ka, args, args_bytes);
+            if (implicit < k.kernarg_size) {
+                const size_t hidden = k.kernarg_size - implicit;
+                std::memset(block, 0, hidden);
+                if (has_implicit) std::memcpy(block, counts, 12), std::memcpy(block + 12, sizes, 6), std::memcpy(block + 64, &dims, 2);
+                std::memcpy(ka + implicit, block, hidden);
+            }
+        }
         if (kernarg_in_hbm_) {
             // The ring lives in HBM and was written through the PCIe BAR (write-combining): drain the CPU's WC buffers, then
             // make the device's host data path hand the bytes on to memory.  Both the flush register and the doorbell below
@@ -163,7 +179,7 @@ public:
         auto *pkt = static_cast<hsa_kernel_dispatch_packet_t *>(queue_->base_address) + (index & (queue_->size - 1));
         pkt->workgroup_size_x = static_cast<uint16_t>(block_size), pkt->workgroup_size_y = 1, pkt->workgroup_size_z = 1;
         pkt->reserved0 = 0;
-        pkt->grid_size_x = grid * block_size, pkt->grid_size_y = 1, pkt->grid_size_z = 1;
+        pkt->grid_size_x = grid * block_size, pkt->grid_size_y = grid_y, pkt->grid_size_z = 1;
         pkt->private_segment_size = 0, pkt->group_segment_size = k.group_size;
         pkt->kernel_object = k.object;
         pkt->kernarg_address = ka;
@@ -172,7 +188,7 @@ public:
         const uint16_t header = static_cast<uint16_t>((HSA_PACKET_TYPE_KERNEL_DISPATCH << HSA_PACKET_HEADER_TYPE) | (1u << HSA_PACKET_HEADER_BARRIER) |
                                                       (acquire << HSA_PACKET_HEADER_SCACQUIRE_FENCE_SCOPE) |
                                                       (release << HSA_PACKET_HEADER_SCRELEASE_FENCE_SCOPE));
-        const uint16_t setup = 1u << HSA_KERNEL_DISPATCH_PACKET_SETUP_DIMENSIONS;
+        const uint16_t setup = static_cast<uint16_t>((grid_y > 1u ? 2u : 1u) << HSA_KERNEL_DISPATCH_PACKET_SETUP_DIMENSIONS);
         __atomic_store_n(reinterpret_cast<uint32_t *>(pkt), static_cast<uint32_t>(header) | (static_cast<uint32_t>(setup) << 16), __ATOMIC_RELEASE);
         hsa_signal_store_screlease(queue_->doorbell_signal, static_cast<hsa_signal_value_t>(index));
         ++dispatched_;
@@ -226,7 +242,7 @@ public:
     }
 
 private:
-    static constexpr size_t kSlots = 64, kSlotBytes = 1024;
+    static constexpr size_t kSlots = 64, kSlotBytes = 4096;  // (a slot holds the argument block of k_pass_gather32_jobs: eight jobs' PassParams)
     int off(const std::string &reason) {
         why = reason;
         ready = false;

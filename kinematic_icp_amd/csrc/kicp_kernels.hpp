@@ -659,9 +659,10 @@ constexpr long long kRowWaitTicks = 200000000ll;
 // for both; an ordinary launch: the tag's parity for the accumulators, row set 0).  Round 4: the resident generic kernel; round 5:
 // every launch whose group rows go to the host, and the small-scan kernels (kicp_small.hpp), whose every workgroup used to send a
 // row of its own across PCIe.
+// `nblocks`: the workgroups of the pass - the launch's (gridDim.x), or the job's where a launch serves several (k_pass_gather32_jobs).
 __device__ __forceinline__ void counting_hand_over(const I128 &t, int range_error, int gave_up, const PassParams &p, uint32_t row_tag, uint32_t acc_set,
-                                                   uint32_t row_set, int lane) {
-    const uint32_t nblocks = gridDim.x, b = blockIdx.x, g = b / kGroup, ngroups = (nblocks + kGroup - 1) / kGroup;
+                                                   uint32_t row_set, int lane, uint32_t nblocks = gridDim.x) {
+    const uint32_t b = blockIdx.x, g = b / kGroup, ngroups = (nblocks + kGroup - 1) / kGroup;
     long long l[3] = {0ll, 0ll, 0ll};
     if (lane < kNumSums) i128_to_limbs(t, l);
     const int from = min(lane, kNumLimbs - 1) / 3;
@@ -690,7 +691,7 @@ __device__ __forceinline__ void counting_hand_over(const I128 &t, int range_erro
 // that started pass k.
 template <int BLOCK, bool ROWS_ONLY = false>
 __device__ __forceinline__ void finish_pass(Acc &a, const PassParams &p, int (*s_red)[kWaveLimbs], int *s_flag, uint32_t row_tag, int gave_up = 0,
-                                            uint32_t parity = 0u) {
+                                            uint32_t parity = 0u, uint32_t nblocks = gridDim.x) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     IcpState *st = p.st;
     if (!ROWS_ONLY && dbg_is(p, 8)) {  // ablation (tools/gpu_dbg.py): no reduction at all, workgroup 0 hands over zeros
@@ -775,13 +776,13 @@ __device__ __forceinline__ void finish_pass(Acc &a, const PassParams &p, int (*s
         for (int w = 0; w < BLOCK / 64; ++w)
             i128_add_limb_sums(t, s_red[w][kTermLimbs * lane], s_red[w][kTermLimbs * lane + 1], s_red[w][kTermLimbs * lane + 2], s_red[w][kTermLimbs * lane + 3]);
     }
-    const uint32_t nblocks = gridDim.x, b = blockIdx.x, g = b / kGroup, ngroups = (nblocks + kGroup - 1) / kGroup;
+    const uint32_t b = blockIdx.x, g = b / kGroup, ngroups = (nblocks + kGroup - 1) / kGroup;
     // (an ordinary launch in mode 4 - round 5: the accumulators alternate with the pass tag's parity, the host's row of group g stays
     //  where it was; dbg 14: round 4's rows -> ticket -> reload, for the in-process A/B)
     const bool counting = ROWS_ONLY || (p.sol.mode == 4 && dbg_not(p, 14));
     if (!ROWS_ONLY && counting) parity = row_tag & 1u;
     if (counting) {
-        counting_hand_over(t, range_error, gave_up, p, row_tag, parity, ROWS_ONLY ? parity : 0u, lane);
+        counting_hand_over(t, range_error, gave_up, p, row_tag, parity, ROWS_ONLY ? parity : 0u, lane, nblocks);
         return;
     }
     unsigned long long *const rows0 = p.partials + (ROWS_ONLY ? static_cast<size_t>(parity) * nblocks * kReduceWords : 0u);
@@ -1245,6 +1246,26 @@ __device__ __forceinline__ const PassParams &args_at_point_of_use() {
     asm volatile("; kernel arguments, re-read at the point of use" : "+s"(q));
     return *(const PassParams *)q;
 }
+// k_pass_gather32_jobs: ONE launch serves the passes of up to kMaxJobs scans (the batch path, run_batch_groups) on a 2-D grid -
+// blockIdx.y is the job, blockIdx.x the workgroup inside that job's scan.  Every job brings its whole PassParams (scan, pose and
+// basis, pass, tag, its own accumulators and host rows; map, search numbers and tau are the same in all of them), read from the
+// kernarg segment with scalar loads where they are used, exactly as a single launch reads its one block; nblocks[j] = the
+// workgroups of job j (gridDim.x is the largest of them).
+constexpr int kMaxJobs = 8;
+struct JobsParams {
+    uint32_t nblocks[kMaxJobs];
+    PassParams job[kMaxJobs];
+};
+typedef const JobsParams __attribute__((address_space(4))) *JobsKernarg;
+__device__ __forceinline__ const PassParams &job_args(uint32_t job) {
+    JobsKernarg q = (JobsKernarg)__builtin_amdgcn_kernarg_segment_ptr();
+    return *(const PassParams *)&q->job[job];
+}
+__device__ __forceinline__ const PassParams &job_args_at_point_of_use(uint32_t job) {
+    JobsKernarg q = (JobsKernarg)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("; kernel arguments, re-read at the point of use" : "+s"(q));
+    return *(const PassParams *)&q->job[job];
+}
 // exact resolution of a finished search: the winner (and whatever lies within the margin of it) re-evaluated in fp64, the
 // reference's tie rule, the acceptance test and the per-correspondence terms (Registration.cpp:74-77, 86-93)
 // `host_pose`: T is the host's pose (the kernel arguments carry its basis); otherwise the basis is formed here, from T
@@ -1257,7 +1278,8 @@ __device__ __forceinline__ void export_correspondence(const PassParams &p, uint3
 // ACC = ScoreAcc (k_score_poses): the same search result, resolution, tie rule and acceptance test; only what is kept of an accepted
 // correspondence differs (its squared residual and the count - no basis, no Jacobian terms)
 // ACC = PlanarAcc (k_planar_poses): likewise; the basis is formed here from T, as for a pass whose pose is the device's
-template <bool EXPORT = false, class ACC = Acc>
+// JOBS: the kernel arguments are a list of jobs and this workgroup's are those of job blockIdx.y (k_pass_gather32_jobs)
+template <bool EXPORT = false, class ACC = Acc, bool JOBS = false>
 __device__ __forceinline__ void resolve_and_accumulate(ACC &acc, const PassParams &p, bool host_pose, const double *__restrict__ src, const Pose &T, uint32_t i,
                                                        const Best3 &t, const KeptQuery *kept = nullptr) {
     if (EXPORT && i != kNoIndex32) export_correspondence(p, i, kNoIndex32, 0.0, 0.0, 0.0, 0.0);  // (overwritten below when the query has a correspondence)
@@ -1315,7 +1337,7 @@ __device__ __forceinline__ void resolve_and_accumulate(ACC &acc, const PassParam
             int from_args = __builtin_amdgcn_readfirstlane(host_pose ? 1 : 0);
             asm volatile("; the basis is taken up here" : "+s"(from_args));
             PassBasis B;
-            if (from_args) B = args_at_point_of_use().sol.basis;
+            if (from_args) B = JOBS ? job_args_at_point_of_use(blockIdx.y).sol.basis : args_at_point_of_use().sol.basis;
             else B = basis_of(T);
             // the untransformed source point again (L1 / L2 hit) unless the build kept it: cheaper than registers kept live through the search
             accumulate(acc, B, kept ? kept->sx : src[3 * i], kept ? kept->sy : src[3 * i + 1], q.x, q.y, q.z, wx, wy, wz);
@@ -1340,7 +1362,7 @@ __device__ __forceinline__ void resolve_and_accumulate(ACC &acc, const PassParam
 constexpr int kParkWords = 5;
 // `host_pose`: T is the host's pose (kernel arguments) and p.sol.basis its basis; where the kernel got T from the device the basis
 // is formed right before the exact phase, not kept through the search.
-template <int BLOCK, int G, bool SPLIT, bool LAT, bool PARK = false, bool EXPORT = false, class ACC = Acc>
+template <int BLOCK, int G, bool SPLIT, bool LAT, bool PARK = false, bool EXPORT = false, class ACC = Acc, bool JOBS = false>
 __device__ __forceinline__ void gather32_pass(const PassParams &p, const Pose &T, bool host_pose, uint32_t tid, ACC &acc, const double *__restrict__ src, uint32_t n,
                                               uint32_t block, int *lend = nullptr, double *park = nullptr) {
     const MapView &m = p.map;
@@ -1473,7 +1495,7 @@ __device__ __forceinline__ void gather32_pass(const PassParams &p, const Pose &T
         kept.sx = park[3 * BLOCK + tid], kept.sy = park[4 * BLOCK + tid], kept.voxel = false;
     }
     if (sub == 0) {
-        resolve_and_accumulate<EXPORT, ACC>(acc, p, host_pose, src, T, L.i, L.t, (LAT || PARK) ? &kept : nullptr);
+        resolve_and_accumulate<EXPORT, ACC, JOBS>(acc, p, host_pose, src, T, L.i, L.t, (LAT || PARK) ? &kept : nullptr);
     }
     // dbg 10 (bench.py's latency model): no correspondences are formed; the "count" sum carries the number of visiting rounds
     // this WAVE ran - its chain of dependent bucket visits - from lane 0 (as rounds x 2^40: limb 1 holds bits 21..41, limb 2 the rest)
@@ -1495,6 +1517,25 @@ __global__ __launch_bounds__(BLOCK, OCC) void k_pass_gather32(const PassParams p
                                                 s_park);
     if (BLOCK > 64) __syncthreads();
     finish_pass<BLOCK>(acc, p, s_red, &s_flag, p.sol.tag);
+}
+// the four-waves build with one lane per query, for a list of jobs (JobsParams): every job's pose is its host's and its rows go to
+// that host in mode 4, group by group, through the job's own accumulators.  A launch's grid is as wide as its largest job: the
+// workgroups beyond a smaller job's end leave at once.
+template <int BLOCK, int G, int OCC>
+__global__ __launch_bounds__(BLOCK, OCC) void k_pass_gather32_jobs(const JobsParams) {
+    static_assert(G == 1, "the job list serves the one-lane-per-query build");
+    const uint32_t job = blockIdx.y;
+    const uint32_t nblocks = ((JobsKernarg)__builtin_amdgcn_kernarg_segment_ptr())->nblocks[job];
+    if (blockIdx.x >= nblocks) return;
+    const PassParams &p = job_args(job);
+    KICP_PASS_SHARED(BLOCK)
+    __shared__ int s_lend[BLOCK / 64][kLendWords];
+    __shared__ double s_park[BLOCK * kParkWords];
+    const Pose T = p.sol.pose0;
+    Acc acc{};
+    gather32_pass<BLOCK, G, false, false, true, false, Acc, true>(p, T, true, threadIdx.x, acc, p.src, p.n, blockIdx.x, &s_lend[threadIdx.x / 64][0], s_park);
+    __syncthreads();
+    finish_pass<BLOCK>(acc, p, s_red, &s_flag, p.sol.tag, 0, 0u, nblocks);
 }
 
 // multi-GPU with host-side solve: hand the all-reduced limb totals to the host

@@ -151,7 +151,8 @@ int kicp_reg_set_option(kicp_reg *reg, const char *name, double value) {
     else if (k == "lanes_per_query") reg->lanes_per_query = (value >= 4) ? 4 : (value >= 2 ? 2 : (value >= 1 ? 1 : 0));
     else if (k == "resident_generic") reg->resident_generic = value != 0.0;
     else if (k == "batch_resident") reg->batch_resident = value != 0.0;
-    else if (k == "batch_queues") reg->batch_queues = std::min<int>(std::max(static_cast<int>(value), 0), kMaxBatchQueues);
+    else if (k == "batch_queues") reg->batch_queues = std::min<int>(std::max(static_cast<int>(value), 0), kMaxBatchInFlight), reg->batch_queues_set = true;
+    else if (k == "batch_group") reg->batch_group = std::min<int>(std::max(static_cast<int>(value), 1), kMaxJobs);
     else if (k == "batch_rotate") reg->batch_rotate = value != 0.0;
     else if (k == "batch_threads") reg->batch_threads = std::min<int>(std::max(static_cast<int>(value), 0), kMaxBatchQueues + 1);
     else if (k == "batch_depth") reg->batch_depth = std::min<int>(std::max(static_cast<int>(value), 1), kPipeSlots);
@@ -202,6 +203,9 @@ double kicp_reg_get_option(const kicp_reg *reg, const char *name) {
     if (k == "batch_depth") return reg->batch_depth;
     if (k == "batch_rotate") return reg->batch_rotate;
     if (k == "batch_queues") return reg->batch_queues;
+    if (k == "batch_group") return reg->batch_group;
+    if (k == "batch_group_launches") return static_cast<double>(reg->batch_group_launches);
+    if (k == "batch_group_aql_launches") return static_cast<double>(reg->batch_group_aql_launches);
     if (k == "batch_queue_passes") return static_cast<double>(reg->batch_queue_passes);
     if (k == "batch_resident_passes") return static_cast<double>(reg->batch_resident_passes);
     if (k == "latency_kernel") return reg->latency_kernel;
@@ -417,7 +421,7 @@ int kicp_reg_clone(const kicp_reg *reg, kicp_reg **out) {
     c->p2p_rows = reg->p2p_rows, c->use_aql = reg->use_aql;
     c->small_cmd = reg->cmd_bar ? 1 : reg->small_cmd, c->use_small = reg->use_small, c->small_block = reg->small_block, c->small_wave = reg->small_wave;
     c->wave_block = reg->wave_block, c->small_resident = reg->small_resident, c->small_timeout_us = reg->small_timeout_us, c->small_group_rows = reg->small_group_rows;
-    c->resident_generic = reg->resident_generic, c->batch_resident = reg->batch_resident, c->batch_depth = reg->batch_depth, c->batch_rotate = reg->batch_rotate, c->batch_queues = reg->batch_queues, c->batch_threads = reg->batch_threads ;
+    c->resident_generic = reg->resident_generic, c->batch_resident = reg->batch_resident, c->batch_depth = reg->batch_depth, c->batch_rotate = reg->batch_rotate, c->batch_queues = reg->batch_queues, c->batch_queues_set = reg->batch_queues_set, c->batch_group = reg->batch_group, c->batch_threads = reg->batch_threads ;
     c->score_chunk = reg->score_chunk;
     c->search_max_nodes = reg->search_max_nodes;
     *out = c;
@@ -509,6 +513,7 @@ size_t kicp_aql_kernel_names(char *out, size_t cap) {
     char name[128];
     all += "void kicp::k_pass_gather32<256, 1, 2, false, true, false>(\n";
     all += "void kicp::k_pass_gather32<256, 1, 4, false, false, false>(\n";
+    all += "void kicp::k_pass_gather32_jobs<256, 1, 4>(\n";
     all += "void kicp::k_pass_gather32<256, 2, 4, true, false, false>(\n";
     all += "void kicp::k_pass_gather32<256, 4, 4, false, false, false>(\n";
     for (int g : {1, 2, 4}) {

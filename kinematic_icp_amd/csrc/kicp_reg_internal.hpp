@@ -184,7 +184,12 @@ struct kicp_reg {
     unsigned long long small_relaunches = 0;  // launches repeated because a resident kernel gave up waiting
     int last_small = 0;           // 1 when the last registration ran on the small path
     int resident_generic = 1;     // option "resident_generic": scans beyond the small-scan kernels keep the generic kernel resident for a call's later iterations
-    int batch_queues = 4;         // option "batch_queues": large scans of a batch in flight at a time, each on a queue of its own (run_batch_queues); < 2: off
+    int batch_queues = 8;         // option "batch_queues": large scans of a batch in flight at a time, batch_queues / batch_group queues (run_batch_queues); < 2: off
+    bool batch_queues_set = false;  // the caller has set it: until then batches that keep a launch per scan run on kDefaultScanQueues queues, as they always did
+    int batch_group = 4;          // option "batch_group": scans whose passes share ONE launch of the pass kernel on such a queue (run_batch_groups); the
+                                  // call then drives batch_queues / batch_group queues.  1: a launch per scan and pass
+    unsigned long long batch_group_aql_launches = 0;  // ... of them, through the lanes' AQL queues (get-only "batch_group_aql_launches")
+    unsigned long long batch_group_launches = 0;  // launches that served a list of jobs so far (get-only "batch_group_launches")
     std::vector<kicp_reg *> batch_lanes;  // the handles those queues belong to (clones of this one, made on first use)
     unsigned long long batch_queue_passes = 0;  // passes served that way so far (get-only "batch_queue_passes")
     int batch_rotate = 1;         // option "batch_rotate": the workgroups of that kernel take turns at the parts of a scan (k_pass_resident)
@@ -227,6 +232,8 @@ constexpr int kPassBlock = 256;  // workgroup size of every build of the generic
 constexpr size_t kLatencyMaxPoints = 131072;  // two waves per SIMD on 256 CUs
 constexpr uint32_t kBatchMaxPasses = 1024;  // passes (= tags) one launch may serve
 constexpr int kMaxBatchQueues = 8;
+constexpr int kMaxBatchInFlight = 16;  // scans in flight at a time when launches serve several ("batch_group"): two lanes of eight jobs, eight lanes of two
+constexpr int kDefaultScanQueues = 4;  // queues of a batch that keeps a launch per scan while "batch_queues" is at its default (measured best: profiles/history/ab_queues.txt)
 constexpr int kMaxGiveUps = 16;  // launches in a row that may end without a completed pass before the call fails
 constexpr size_t kThreadsMaxGenericPoints = 24576;  // (five and more such kernels fit the device)
 double wait_timeout_s();
@@ -293,6 +300,8 @@ const AqlKernel *aql_resident_kernel_for(kicp_reg *r, bool lat);
 const AqlKernel *aql_small_kernel_for(kicp_reg *r, int block, int g, bool wave);
 int aql_quiesce(kicp_reg *r);
 int launch_pass(kicp_reg *r, const PassParams &p, bool allow_aql = false);
+const AqlKernel *aql_jobs_kernel_for(kicp_reg *r);
+int launch_jobs(kicp_reg *r, const JobsParams &jp, uint32_t jobs, uint32_t grid_x);
 int ensure_partials(kicp_reg *r, size_t blocks);
 int ensure_frame(kicp_reg *r, size_t n);  // room for a host frame of n points in r->d_frame (kicp_reg_api.hip)
 int ensure_rows(kicp_reg *r, size_t groups);

@@ -138,6 +138,30 @@ int launch_pass(kicp_reg *r, const PassParams &p, bool allow_aql) {
     else hipLaunchKernelGGL((k_pass_gather32<kPassBlock, 4, 4, false>), dim3(grid), dim3(kPassBlock), 0, r->stream, p);
     return KICP_OK;
 }
+// One launch for the passes of `jobs` scans (k_pass_gather32_jobs; run_batch_groups): the same choice between the handle's AQL queue
+// and its HIP stream, the same fences as launch_pass.  `grid_x`: the largest of the jobs' workgroup counts.
+// (256: the hidden arguments of code object v5 that follow the explicit block wherever a kernel reads one; a segment larger than
+//  a slot would turn every dispatch of the job list into a HIP launch - tests/test_gpu_batch_group.py counts the AQL ones)
+static_assert(sizeof(JobsParams) + 256 <= AqlDispatcher::max_kernarg_bytes(), "the job list and the hidden arguments must fit a slot of the kernarg ring");
+const AqlKernel *aql_jobs_kernel_for(kicp_reg *r) { return aql_lookup(r, -8, "void kicp::k_pass_gather32_jobs<256, 1, 4>("); }
+int launch_jobs(kicp_reg *r, const JobsParams &jp, uint32_t jobs, uint32_t grid_x) {
+    if (jobs == 0u || jobs > static_cast<uint32_t>(kMaxJobs) || grid_x == 0u) return fail(KICP_ERR_ARG, "launch_jobs: an empty or oversized job list");
+    if (r->use_aql && !r->stream_dirty) {
+        if (const AqlKernel *k = aql_jobs_kernel_for(r)) {
+            const size_t filled = offsetof(JobsParams, job) + jobs * sizeof(PassParams);
+            if (r->aql.dispatch(*k, grid_x, static_cast<uint32_t>(kPassBlock), &jp, filled, HSA_FENCE_SCOPE_AGENT, HSA_FENCE_SCOPE_AGENT, jobs, sizeof jp)) {
+                r->last_via_aql = true;
+                return KICP_OK;
+            }
+        }
+    }
+    r->stream_dirty = false;  // the host waits for these passes: by then everything queued before them is done
+    if (int rc = aql_quiesce(r)) return rc;
+    r->last_via_aql = false;
+    hipLaunchKernelGGL((k_pass_gather32_jobs<kPassBlock, 1, 4>), dim3(grid_x, jobs), dim3(kPassBlock), 0, r->stream, jp);
+    HIP_TRY(hipGetLastError());
+    return KICP_OK;
+}
 int ensure_partials(kicp_reg *r, size_t blocks) {
     if (blocks <= r->partial_blocks) return KICP_OK;
     if (int rc = aql_quiesce(r)) return rc;

@@ -1,5 +1,6 @@
 // kicp_reg_queues.hip -- batches with several scans in flight on queues of their own, sharded or not (see kicp_reg_internal.hpp)
 #include "kicp_reg_internal.hpp"
+#include "kicp_batch_groups.hpp"
 
 using namespace kicp;
 using namespace kicp::host;
@@ -8,7 +9,9 @@ namespace kicp {
 namespace host {
 // kicp_register_device_batch, large scans: SEVERAL SCANS IN FLIGHT ON SEVERAL QUEUES, one host thread.  The scans of a batch do
 // not depend on each other - every one starts from its own pose, the map does not change - so the call keeps option
-// "batch_queues" (default 4) of them going at a time, each on a handle of its own (clones of the caller's, made on first use and
+// "batch_queues" of them going at a time (four while the option is at its default) - here, with a launch per scan and pass (what
+// sharded, short and mostly-small batches and "batch_group" 1 run; run_batch_groups below is the same with several scans per
+// launch) - each on a handle of its own (clones of the caller's, made on first use and
 // kept): own HSA queue, own reduction scratch and rows.  Every pass is an ordinary launch of the pass kernel in its
 // four-waves-per-SIMD build (the latency-oriented build fills the register file with ONE scan's waves and leaves no room for a
 // second scan's next to them); the device takes workgroups from all queues as wave slots fall free, so a pass's slow workgroups
@@ -167,10 +170,220 @@ int flight_launch(BatchFlight &f, const kicp_map *map, const double *d_frame, si
     }
     return launch_pass(h, pp, true);
 }
+// SEVERAL SCANS PER LAUNCH (option "batch_group" = G > 1; unsharded batches).  The first passes of a batch's scans depend on nothing
+// the host computes during the call, and a dispatch per scan pays for its own fill and drain of the device, its own packet, kernarg
+// slot and doorbell, and a turn-round of the host on its queue.  So a lane - a queue with this thread behind it, batch_queues / G of
+// them - launches GROUPS of up to G jobs in one dispatch of k_pass_gather32_jobs (2-D grid: blockIdx.y = the job), a job being the
+// next pass of one scan: its own PassParams, tag, accumulators and host rows (slot s of the lane's buffers).  The lane adds the
+// jobs' rows as they land and runs HostLoop::step per job; when the group is collected, the scans that go on and fresh ones from
+// the front of the batch (BatchGroups, kicp_batch_groups.hpp) make the next group.  Scans that take another kernel - the small-scan
+// kernels, sub-lanes per query - keep their launch per scan and pass (flight_launch) in between.  Bit-equal to one call per scan:
+// the same kernel body on the same arguments, exact integer sums.
+struct GroupJob {
+    size_t k = 0;  // the scan
+    HostLoop loop;
+    uint32_t tag = 0;
+    size_t rows = 0, row_next = 0;  // group rows of the pass in flight; how many are in
+    long long words[kReduceWords] = {};
+    bool collected = false, goes_on = false;
+};
+struct GroupLane {
+    BatchFlight solo;  // (also holds the lane's handle)
+    std::vector<GroupJob> jobs;
+    bool active = false, is_solo = false;
+    size_t pending = 0;  // jobs of the group whose rows are not all in yet
+    unsigned polls = 0;
+    Deadline since;
+    JobsParams jp;
+};
+static int group_launch(kicp_reg *r, GroupLane &L, int group, size_t slot_groups, const kicp_map *map, const double *const *d_frames, const size_t *n, double tau) {
+    kicp_reg *h = L.solo.h;
+    const size_t slots = static_cast<size_t>(group);
+    if (int rc = ensure_partials(h, slots * slot_groups * kGroup)) return rc;
+    if (int rc = ensure_rows(h, slots * slot_groups)) return rc;
+    if (int rc = clear_stale_tickets(h)) return rc;
+    uint32_t tag0 = 0, grid_x = 0;
+    if (int rc = next_tag_range(h, static_cast<uint32_t>(L.jobs.size()), &tag0)) return rc;
+    const SearchParams search = search_params(tau, map->mirror.view.voxel_size);
+    for (size_t s = 0; s < L.jobs.size(); ++s) {
+        GroupJob &j = L.jobs[s];
+        PassParams &pp = L.jp.job[s];
+        pp = PassParams{};
+        pp.src = d_frames[j.k], pp.n = static_cast<uint32_t>(n[j.k]), pp.map = map->mirror.view, pp.tau = tau, pp.st = h->d_state.get();
+        pp.search = search, pp.dbg = h->dbg;
+        // (mode 4 hands over through the job's counting accumulators only - the rows -> ticket -> reload hand-over, "dbg" 14, keeps a
+        //  launch per scan - so a job has no workgroup rows and no tickets: a slot's share of them would not hold grid + groups rows)
+        pp.partials = nullptr, pp.tickets = nullptr;
+        pp.group_acc = h->d_group_acc.get() + s * 2 * slot_groups * kAccStride;
+        SolveParams &sol = pp.sol;
+        set_pose(sol, j.loop.T);
+        sol.pass = j.loop.iter, sol.mode = 4, sol.max_iterations = h->cfg.max_num_iterations;
+        sol.convergence_criterion = h->cfg.convergence_criterion;
+        sol.call_id = ++h->call_id, sol.rec = h->rec.dev(), sol.pub_rows = h->rows.dev() + s * slot_groups * kReduceWords;
+        sol.tag = j.tag = tag0 + static_cast<uint32_t>(s);
+        const uint32_t grid = pass_grid(h, n[j.k]);
+        L.jp.nblocks[s] = grid, grid_x = std::max(grid_x, grid);
+        j.rows = (grid + kGroup - 1) / kGroup, j.row_next = 0, j.collected = false, j.goes_on = false;
+        for (auto &w : j.words) w = 0;
+    }
+    L.pending = L.jobs.size(), L.polls = 0, L.since = Deadline();
+    ++r->batch_group_launches;
+    if (int rc = launch_jobs(h, L.jp, static_cast<uint32_t>(L.jobs.size()), grid_x)) return rc;
+    if (h->last_via_aql) ++r->batch_group_aql_launches;
+    return KICP_OK;
+}
+// the rows of job `s` that have arrived since the last look: 1 all in (sums in j.words), 0 not yet
+static int group_job_rows(GroupLane &L, size_t s, size_t slot_groups) {
+    GroupJob &j = L.jobs[s];
+    const unsigned long long *base = L.solo.h->rows.get() + s * slot_groups * kReduceWords;
+    for (; j.row_next < j.rows; ++j.row_next) {
+        const unsigned long long *row = base + j.row_next * kReduceWords;
+        unsigned long long w[kReduceWords];
+        bool ok = true;
+        for (int i = 0; i < kReduceWords; ++i) {
+            w[i] = __atomic_load_n(row + i, __ATOMIC_RELAXED);
+            ok = ok && (static_cast<uint32_t>(w[i]) & 0xFFFFu) == j.tag;
+        }
+        if (!ok) return 0;
+        for (int i = 0; i < kReduceWords; ++i)
+            if (i != kNumLimbs) j.words[i] += static_cast<long long>(w[i]) >> 16;
+        j.words[kNumLimbs] |= row_flags(static_cast<long long>(w[kNumLimbs]) >> 16);
+    }
+    __atomic_thread_fence(__ATOMIC_ACQUIRE);
+    return 1;
+}
+static int run_batch_groups(kicp_reg *r, kicp_map *map, size_t count, const double *const *d_frames, const size_t *n, const double *last_poses_qt,
+                            const double *rel_odoms_qt, double tau, double *out_poses_qt, int *out_iterations, size_t *done, int *worst, int lanes, int group) {
+    std::vector<GroupLane> L(static_cast<size_t>(lanes));
+    std::vector<unsigned char> solo(count, 0);
+    size_t slot_groups = 1;
+    for (int j = 0; j < lanes; ++j) L[j].solo.h = r->batch_lanes[j];
+    kicp_reg *h0 = L[0].solo.h;
+    for (size_t k = 0; k < count; ++k) {
+        const SmallPlan pl = h0->use_small ? small_plan(h0, n[k]) : SmallPlan();
+        solo[k] = (pl.grid != 0 && !pl.generic) || lanes_for(h0, n[k]) != 1;
+        if (!solo[k]) slot_groups = std::max<size_t>(slot_groups, (pass_grid(h0, n[k]) + kGroup - 1) / kGroup);
+    }
+    BatchGroups sched(count, group, solo);
+    auto leave = [&](int rc) {  // nothing of this call may still be running when it returns: the caller owns the frames
+        for (int j = 0; j < lanes; ++j) {
+            kicp_reg *h = L[j].solo.h;
+            (void)aql_quiesce(h);
+            (void)hipStreamSynchronize(h->stream);
+            if (rc < 0 && L[j].active) h->acc_dirty = true;  // (a group that was not collected: every job's accumulators may be part full)
+        }
+        *done = sched.done();
+        return rc;
+    };
+    auto finish_scan = [&](const HostLoop &loop, size_t k) {
+        pose_to(loop.T, out_poses_qt + 7 * k);
+        if (out_iterations) out_iterations[k] = loop.iter;
+        sched.finish(k);
+        if (loop.nan_flag == 2) return fail(KICP_ERR_CAPACITY, "a per-point term exceeded the exact-accumulation range (|x| >= 2^43)");
+        if (loop.nan_flag) *worst = std::max(*worst, static_cast<int>(KICP_WARN_NO_CORRESPONDENCES));
+        return static_cast<int>(KICP_OK);
+    };
+    std::vector<size_t> carry, scans;
+    std::vector<GroupJob> next;
+    // the lane's next group: what goes on of the one it has just collected, then fresh scans
+    auto start_group = [&](GroupLane &g) {
+        carry.clear();
+        if (g.active && g.is_solo) carry.push_back(g.solo.k);  // (only ever called for a solo scan that goes on)
+        else if (g.active)
+            for (const GroupJob &j : g.jobs)
+                if (j.goes_on) carry.push_back(j.k);
+        const bool fresh_solo = carry.empty();
+        const bool is_solo = sched.next_group(carry, scans);
+        if (scans.empty()) {
+            g.active = false, g.jobs.clear();
+            return static_cast<int>(KICP_OK);
+        }
+        auto fresh = [&](size_t k) {
+            HostLoop loop;
+            loop.T = pose_mul(pose_from(last_poses_qt + 7 * k), pose_from(rel_odoms_qt + 7 * k));  // Registration.cpp:156
+            return loop;
+        };
+        if (is_solo) {
+            BatchFlight &f = g.solo;
+            if (!(g.active && g.is_solo && !fresh_solo)) f.k = scans[0], f.loop = fresh(f.k);
+            g.jobs.clear(), g.active = true, g.is_solo = true, f.active = true;
+            return flight_launch(f, map, d_frames[f.k], n[f.k], tau);
+        }
+        next.clear();
+        for (size_t k : scans) {
+            GroupJob nj;
+            nj.k = k;
+            bool found = false;
+            for (const GroupJob &j : g.jobs)
+                if (g.active && !g.is_solo && j.goes_on && j.k == k) nj.loop = j.loop, found = true;
+            if (!found) nj.loop = fresh(k);
+            next.push_back(nj);
+        }
+        g.jobs.swap(next);
+        g.active = true, g.is_solo = false, g.solo.active = false;
+        return group_launch(r, g, group, slot_groups, map, d_frames, n, tau);
+    };
+    while (!sched.all_finished()) {
+        bool any_active = false;
+        for (int jl = 0; jl < lanes; ++jl) {
+            GroupLane &g = L[jl];
+            if (!g.active) {
+                if (int rc = start_group(g)) return leave(rc);
+                any_active = any_active || g.active;
+                continue;
+            }
+            any_active = true;
+            if (g.is_solo) {
+                BatchFlight &f = g.solo;
+                long long words[kReduceWords];
+                const int ready = flight_rows(f, words);
+                if (ready < 0) return leave(ready);
+                if (ready == 0) continue;
+                if ((static_cast<unsigned long long>(words[kNumLimbs]) >> 8) != 0ull)
+                    return leave(fail(KICP_ERR_HIP, "a workgroup's row did not reach its group's reader in time (kRowWaitTicks)"));
+                ++r->batch_queue_passes;
+                if (!f.loop.step(f.h, words, nullptr)) {
+                    if (int rc = start_group(g)) return leave(rc);
+                    continue;
+                }
+                if (int rc = finish_scan(f.loop, f.k)) return leave(rc);
+                g.active = false, f.active = false;
+                continue;
+            }
+            for (size_t s = 0; s < g.jobs.size(); ++s) {
+                GroupJob &j = g.jobs[s];
+                if (j.collected || !group_job_rows(g, s, slot_groups)) continue;
+                j.collected = true, --g.pending;
+                if ((static_cast<unsigned long long>(j.words[kNumLimbs]) >> 8) != 0ull)
+                    return leave(fail(KICP_ERR_HIP, "a workgroup's row did not reach its group's reader in time (kRowWaitTicks)"));
+                ++r->batch_queue_passes;
+                j.goes_on = !j.loop.step(g.solo.h, j.words, nullptr);
+                if (!j.goes_on)
+                    if (int rc = finish_scan(j.loop, j.k)) return leave(rc);
+            }
+            if (g.pending != 0) {
+                if (++g.polls % 256u == 0u) {
+                    kicp_reg *h = g.solo.h;
+                    if (h->last_via_aql) {
+                        if (h->aql.queue_error) return leave(fail(KICP_ERR_HIP, "the AQL queue reported error " + std::to_string(h->aql.queue_error)));
+                    } else {  // (the query makes the runtime flush commands it may still hold back, and reports device faults)
+                        const hipError_t q = hipStreamQuery(h->stream);
+                        if (q != hipSuccess && q != hipErrorNotReady) return leave(fail(KICP_ERR_HIP, std::string("stream fault: ") + hipGetErrorString(q)));
+                    }
+                    if (g.since.passed()) return leave(fail(KICP_ERR_HIP, "timed out waiting for the pass kernel's rows (KICP_WAIT_TIMEOUT_S)"));
+                }
+                continue;
+            }
+            if (int rc = start_group(g)) return leave(rc);  // the group is collected: the next one goes out at once
+        }
+        if (!any_active && !sched.all_finished()) return leave(fail(KICP_ERR_ARG, "internal: scans left over without a lane to run them"));
+    }
+    *done = count;
+    return KICP_OK;
+}
 int run_batch_queues(kicp_reg *r, kicp_map *map, size_t count, const double *const *d_frames, const size_t *n, const double *last_poses_qt,
                      const double *rel_odoms_qt, double tau, double *out_poses_qt, int *out_iterations, size_t *done, int *worst) {
     *done = 0;
-    const int queues = std::min(r->batch_queues, kMaxBatchQueues);
     const int max_it = r->cfg.max_num_iterations;
     // SHARDED batches (the shared segment attached, kicp_reg_shm_init): every rank calls with ITS shard of every scan, the lanes'
     // exchanges go through the segment (below).  Every decision up to here and in the loop must then be the same on every rank - so
@@ -181,7 +394,31 @@ int run_batch_queues(kicp_reg *r, kicp_map *map, size_t count, const double *con
     // after scan while the shared segment kept four in flight)
     const bool over_rccl = r->comm != nullptr && !r->shm && g_comm.CommSplit != nullptr && !r->lane_comms_failed;
     const bool sharded = r->shm != nullptr || over_rccl;
-    if (queues < 2 || count < 2u * static_cast<size_t>(queues) || max_it <= 0 || kicp_map_empty(map)) return 1;
+    if (r->batch_queues < 2 || max_it <= 0 || kicp_map_empty(map)) return 1;
+    // Several scans per launch ("batch_group" = G): "batch_queues" is the number of scans in flight, on batch_queues / G lanes, each
+    // with a list of up to G jobs per launch (run_batch_groups).  A launch per scan and pass, each scan on a queue of its own, is
+    // what remains for G = 1, for sharded batches (their lanes exchange per scan and pass), for batches too short to give every lane
+    // two groups, and for batches in which most scans take another kernel than the one the job list serves.  That path is as it
+    // was: "batch_queues" queues where the caller has set the option, else the four it has always run on (the default of eight
+    // scans in flight is sized for two lanes of four jobs), and batches of fewer than two scans per queue go elsewhere.  (None of
+    // these decisions looks at a sharded batch's sizes.)
+    const int in_flight = std::min(r->batch_queues, kMaxBatchInFlight);
+    int group = (sharded || r->dbg == 14) ? 1 : std::min({r->batch_group, in_flight, static_cast<int>(kMaxJobs)});
+    int lanes = std::min(in_flight / group, kMaxBatchQueues);
+    if (group > 1 && count < 2u * static_cast<size_t>(lanes) * static_cast<size_t>(group)) group = 1;
+    if (group > 1) {
+        size_t shared = 0;
+        for (size_t k = 0; k < count; ++k) {
+            const SmallPlan pl = r->use_small ? small_plan(r, n[k]) : SmallPlan();
+            if ((pl.grid == 0 || pl.generic) && lanes_for(r, n[k]) == 1) ++shared;
+        }
+        if (2 * shared < count) group = 1;
+    }
+    if (group == 1) {
+        lanes = r->batch_queues_set ? std::min(r->batch_queues, kMaxBatchQueues) : kDefaultScanQueues;
+        if (lanes < 2 || count < 2u * static_cast<size_t>(lanes)) return 1;
+    }
+    const int queues = lanes;
     if (!(r->use_aql && (!r->comm || over_rccl) && !r->allreduce_fn && !r->d_p2p_table && r->timing == 0 &&
           r->wait_mode == 0 && (r->dbg == 0 || r->dbg == 11 || r->dbg == 12 || r->dbg == 14)))
         return 1;
@@ -203,13 +440,13 @@ int run_batch_queues(kicp_reg *r, kicp_map *map, size_t count, const double *con
     const uint64_t epoch_before = map->mirror.synced_epoch;
     if (int rc = map_sync(map, r->device, r->stream)) return rc;
     if (map->mirror.synced_epoch != epoch_before) HIP_TRY(hipStreamSynchronize(r->stream));  // (the lanes only read the copy)
-    while (static_cast<int>(r->batch_lanes.size()) < queues) {
+    while (static_cast<int>(r->batch_lanes.size()) < lanes) {
         kicp_reg *c = nullptr;
         if (int rc = kicp_reg_clone(r, &c)) return rc;
         r->batch_lanes.push_back(c);
     }
     BatchFlight flights[kMaxBatchQueues];
-    for (int j = 0; j < queues; ++j) {
+    for (int j = 0; j < lanes; ++j) {
         kicp_reg *h = r->batch_lanes[j];
         h->cfg = r->cfg, h->lanes_per_query = r->lanes_per_query;
         h->query_every = r->query_every, h->dbg = r->dbg, h->latency_kernel = 0, h->small_resident = 0, h->batch_queues = 0;
@@ -235,6 +472,8 @@ int run_batch_queues(kicp_reg *r, kicp_map *map, size_t count, const double *con
         const SmallPlan first = r->use_small ? small_plan(flights[0].h, n[0]) : SmallPlan();
         if (first.grid && !first.generic) r->last_small = first.wave ? 2 : 1;  // ("small_active": the path of the batch's first scan)
     }
+    if (group > 1)
+        return run_batch_groups(r, map, count, d_frames, n, last_poses_qt, rel_odoms_qt, tau, out_poses_qt, out_iterations, done, worst, lanes, group);
     std::vector<unsigned char> complete(count, 0);
     size_t next_scan = 0, front = 0, finished_scans = 0;
     auto leave = [&](int rc) {  // nothing of this call may still be running when it returns: the caller owns the frames
