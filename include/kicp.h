@@ -662,7 +662,22 @@ size_t kicp_pre_ingested_count(const kicp_pre *pre);
  *   "guess"  the survivor count from which the fused chain sizes its first table before it knows the real one (default: the
  *            previous frame's; the first frame: the input count).  A wrong power-of-two bracket costs the frame the unfused
  *            downsamples, never a different result.
- *   "fused_frames" / "guess_misses" (read only): frames the fused chain served / of those, frames whose guess was wrong. */
+ *   "fused_frames" / "guess_misses" (read only): frames the fused chain served / of those, frames whose guess was wrong.
+ * Which way the last decode went (read only, host-side bookkeeping; for tests that must prove the regime they ran in).
+ * "ingest_*": the last kicp_pre_ingest that decoded its message itself (not one that took a look-ahead slot, not an empty one);
+ * "ahead_*": the last look-ahead decode (kicp_pre_ingest_ahead + the chained pre-steps; read it after the kicp_pre_ingest call
+ * that collects the message).  All are 0 before the first such decode.
+ *   "ingest_launches"       launches of the decode kernel: one per piece of the message
+ *   "ingest_workgroups"     workgroups of the widest of these launches (a look-ahead launch has at most 48, KICP_PRE_AHEAD_WGS,
+ *                           and walks the piece's 256-record tiles with them)
+ *   "ingest_piece_records"  records per piece: max(256, P / point_step / 256 * 256) with integer divisions, P = 512 KiB
+ *                           (a look-ahead message: KICP_PRE_AHEAD_PIECE_KB, default 512 too)
+ *   "ingest_aligned"        1: every field sits at a multiple of its size - point_step and the offsets of x, y, z multiples of 4,
+ *                           the stamp's offset and point_step multiples of the stamp's size - and is read with plain loads;
+ *                           0: byte-wise loads
+ *   "ingest_wide"           1: point_step > 128, records read field by field from where they are; 0: staged through LDS
+ *   "ingest_direct"         1: the kernel read the pinned staging buffer itself; 0: the bytes were copied into device memory first
+ * Unknown names return -1. */
 int kicp_pre_set_option(kicp_pre *pre, const char *name, double value);
 double kicp_pre_get_option(const kicp_pre *pre, const char *name);
 int kicp_pre_upload(kicp_pre *pre, int buffer, const double *xyz, size_t n);

@@ -10,6 +10,7 @@
 #include <cmath>
 #include "kicp_common.hpp"
 #include "kicp_se3.hpp"
+#include "kicp_ordered_key.hpp"
 #include "kicp_table_order.hpp"
 
 namespace kicp {
@@ -695,18 +696,7 @@ __device__ __forceinline__ T load_unaligned(const unsigned char *p) {
     __builtin_memcpy(&v, p, sizeof(T));
     return v;
 }
-// order-preserving map double -> uint64 (and back), so the block extrema can be merged as integers
-__device__ __forceinline__ unsigned long long ordered_key(double v) {
-    const unsigned long long b = static_cast<unsigned long long>(__double_as_longlong(v));
-    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
-}
-KICP_HD double ordered_value(unsigned long long k) {
-    const unsigned long long b = (k >> 63) ? (k & 0x7FFFFFFFFFFFFFFFull) : ~k;
-    double v;
-    __builtin_memcpy(&v, &b, 8);
-    return v;
-}
-
+// (ordered_key / ordered_value, the order-preserving map double <-> uint64 the block extrema are merged through: kicp_ordered_key.hpp)
 template <typename T>
 __device__ __forceinline__ T load_field(const unsigned char *p, bool aligned) {
     return aligned ? *reinterpret_cast<const T *>(p) : load_unaligned<T>(p);

@@ -86,6 +86,14 @@ struct kicp_pre {
     DevBuf<unsigned long long> d_block_minmax;
     size_t ingested_n = 0;
     bool ingested = false, ingested_stamps = false;
+    // which way the last ingest_run of either slot went ([0] this call's message, [1] the look-ahead's; kicp_pre_get_option "ingest_*" /
+    // "ahead_*", include/kicp.h): host-side bookkeeping only, written once the launches are queued - the look-ahead's by its thread,
+    // which every kicp_pre_ingest call joins first
+    struct IngestCounts {
+        unsigned launches = 0, workgroups = 0;  // k_ingest launches / workgroups of the widest of them
+        int aligned = 0, wide = 0, direct = 0;
+        size_t piece_records = 0;
+    } ingest_counts[2];
     // LOOK-AHEAD ingest (kicp_pre_ingest_ahead, round 5): the NEXT message is uploaded and decoded into a second slot (d_in2 / d_ts2) on
     // a stream of its own by the kicp_pre_frame_ingested call of the CURRENT one - while that call's kernels run and its thread would
     // only wait -, and the kicp_pre_ingest call for the same message then just swaps the slots.
@@ -343,6 +351,7 @@ int ingest_run(kicp_pre *p, const void *data, size_t n_points, const kicp_cloud_
         lanes[1] = p->ingest_stream2;
     }
     unsigned piece_index = 0;
+    uint32_t widest = 0;
     for (size_t first = 0; first < n_points; first += piece_records)  // (one ticket per workgroup of every launch)
         p->ticket_drawn[slot] += std::min<uint32_t>(wgs_cap, static_cast<uint32_t>((std::min(piece_records, n_points - first) + 255) / 256));
     ip.ticket_done = p->ticket_drawn[slot];
@@ -356,11 +365,16 @@ int ingest_run(kicp_pre *p, const void *data, size_t n_points, const kicp_cloud_
             ip.raw = p->d_raw.get() + off;
         }
         ip.first = static_cast<uint32_t>(first), ip.n = static_cast<uint32_t>(count);
-        hipLaunchKernelGGL(k_ingest, dim3(std::min<uint32_t>(wgs_cap, static_cast<uint32_t>((count + 255) / 256))), dim3(256), 0, lanes[piece_index & 1u], ip);
+        const uint32_t wgs = std::min<uint32_t>(wgs_cap, static_cast<uint32_t>((count + 255) / 256));
+        hipLaunchKernelGGL(k_ingest, dim3(wgs), dim3(256), 0, lanes[piece_index & 1u], ip);
+        widest = std::max(widest, wgs);
         ++piece_index;
         if (slot == 0) trace_lap("piece copied, its decode launched");
     }
     HIP_TRY(hipGetLastError());
+    kicp_pre::IngestCounts &ic = p->ingest_counts[slot];
+    ic.launches = piece_index, ic.workgroups = widest, ic.aligned = ip.aligned, ic.wide = L.point_step > 128u ? 1 : 0, ic.direct = direct ? 1 : 0;
+    ic.piece_records = piece_records;
     if (int rc = wait_word(rec + 2, ip.seq, ~0ull, stream, 2.0, kPreLost)) return rc;  // (`data` and the staging buffer are free again behind this)
     if (slot == 0) trace_lap("the decoded cloud's record at the host");
     *out_lo = *out_hi = 0.0;
@@ -885,6 +899,18 @@ double kicp_pre_get_option(const kicp_pre *p, const char *name) {
     if (n == "guess") return static_cast<double>(p->spec_n0);
     if (n == "fused_frames") return static_cast<double>(p->fused_frames);
     if (n == "guess_misses") return static_cast<double>(p->spec_misses);
+    for (int slot = 0; slot < 2; ++slot) {  // "ingest_<counter>" / "ahead_<counter>": the last ingest_run of the slot
+        const std::string prefix = slot ? "ahead_" : "ingest_";
+        if (n.compare(0, prefix.size(), prefix) != 0) continue;
+        const std::string c = n.substr(prefix.size());
+        const kicp_pre::IngestCounts &ic = p->ingest_counts[slot];
+        if (c == "launches") return static_cast<double>(ic.launches);
+        if (c == "workgroups") return static_cast<double>(ic.workgroups);
+        if (c == "aligned") return static_cast<double>(ic.aligned);
+        if (c == "wide") return static_cast<double>(ic.wide);
+        if (c == "piece_records") return static_cast<double>(ic.piece_records);
+        if (c == "direct") return static_cast<double>(ic.direct);
+    }
     return -1.0;
 }
 size_t kicp_pre_ingested_count(const kicp_pre *p) { return (p && p->ingested) ? p->ingested_n : 0; }

@@ -217,8 +217,8 @@ def test_gpu_look_ahead_ingest_equals_the_plain_ingest(stamp, layout):
 
 def test_ordered_integer_keys_of_doubles_are_monotone():
     """k_ingest merges the stamps' extrema with integer atomics on an order-preserving map double -> uint64
-    (kicp_pre.hpp ordered_key / ordered_value); re-enacted here: monotone over negatives, zeros, subnormals and infinities,
-    and invertible."""
+    (kicp_ordered_key.hpp ordered_key / ordered_value; the functions themselves: tests/test_ordered_key.py); re-enacted
+    here: monotone over negatives, zeros, subnormals and infinities, and invertible."""
     def ordered_key(v):
         b = np.asarray(v, dtype=np.float64).view(np.uint64)
         return np.where(b >> np.uint64(63), ~b, b | np.uint64(1 << 63))
