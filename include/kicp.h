@@ -545,6 +545,66 @@ int kicp_grid_save_map(const kicp_grid *grid, const char *prefix, unsigned int m
 int kicp_grid_write_map(const char *prefix, const signed char *occupancy, unsigned int width, unsigned int height, double cell, double origin_x,
                         double origin_y, double occupied_thresh, double free_thresh);
 
+/* ---- map points the new frame sees through: a cube-map depth test (kicp_view.hip) ----------------------------------------------------
+ * The local map loses points by distance only (RemovePointsFarFromLocation); whatever stood in view for one frame - a person crossing,
+ * a forklift, a door leaf - stays until the robot is max_range away.  A kicp_view holds a depth image of ONE frame, and
+ * kicp_map_remove_seen_through removes the map points that frame looks past.  Everything below is exact: subtractions, divisions,
+ * floor and comparisons in fp64, every operation rounded on its own - no atan2, no sqrt.
+ *
+ * The image is a cube map of depths around the sensor, 6 faces of res x res pixels, the faces aligned to the WORLD axes.  Per frame:
+ *   c = pose * sensor_xyz,   w = pose * p per point (quaternion rotation + translation, the very transform of kicp_map_update_pose: a
+ *   point lands where Update(points, pose) files it),   v = w - c per component,   m = max(|v.x|, |v.y|, |v.z|)  - the depth (Chebyshev).
+ * A point is USED iff p, w and m are finite and 0 < m <= max_ray; every other point is skipped.  A pose or sensor that is not finite
+ * uses no point.  Face: the first axis in the order x, y, z whose |v| equals m, with that component's sign: 2 axis + (negative ? 1 : 0).
+ * The other two components (a, b) are (y, z) for an x face, (x, z) for a y face, (x, y) for a z face.  Pixel:
+ *   u  = min(res - 1, (int)floor((a / m + 1.0) * (res / 2.0))),   w_ = min(res - 1, (int)floor((b / m + 1.0) * (res / 2.0))),
+ * element (face * res + w_) * res + u of the image.  A pixel holds the minimum over the frame's used points in it of (float)m (round to
+ * nearest even), +inf when there is none: a minimum over the SET of points, whatever their order.
+ *
+ * The verdict for a world point q: v, m, face and pixel as above from q - c.  q is IN RANGE iff m is finite and 0 < m <= max_ray.  Of
+ * the pixels (u + du, w_ + dw), |du|, |dw| <= window, that lie inside the SAME face (the window is clipped at the face's edges), N is
+ * the number that are not empty and D the smallest value.  q is SEEN THROUGH iff it is in range, N >= min_rays and
+ *   m + (margin + margin_per_metre * m) < (double)D        (fp64 as written, strict).
+ * The window is what keeps a surface seen at a grazing angle: it then also holds nearer returns of the same surface.  (2 window + 1)
+ * pixels must span the sensor's vertical beam spacing.
+ *
+ * kicp_map_remove_seen_through gives every point of every occupied voxel the verdict.  Seen-through points leave their bucket, the
+ * survivors keep their relative order (a voxel's first point is then its first survivor), and a voxel that loses all its points is
+ * erased as RemovePointsFarFromLocation erases one.  It collects a pending kicp_map_update_pose_device_begin first (and returns its
+ * error), brings the map to the view's device if need be, runs there and leaves the HBM copy the current one; a map whose updates stay
+ * on the host (a voxel beyond +-2^20) is swept on the host with the same verdict over the downloaded image.  An empty map or a view
+ * that never rendered a frame: nothing is removed, KICP_OK.  out_stats (nullable): points in range, points removed, voxels that lost at
+ * least one point, voxels erased.
+ *
+ * Limits: res even and 8 .. 1024, window 0 .. 4 (larger: KICP_ERR_CAPACITY), 1 <= min_rays <= (2 window + 1)^2, max_ray positive and
+ * finite, both margins finite and not negative, no null pointer (KICP_ERR_ARG); n > 0x7FFFFFF0 / 3 points: KICP_ERR_CAPACITY. */
+typedef struct kicp_view kicp_view;
+typedef struct kicp_view_config {
+    unsigned int res;        /* pixels per face edge */
+    int window;              /* the verdict looks at (2 window + 1)^2 pixels */
+    unsigned int min_rays;   /* of them at least this many must hold a return */
+    double max_ray;          /* metres (Chebyshev): farther frame points are skipped, farther map points kept */
+    double margin, margin_per_metre; /* metres, and metres per metre of depth */
+} kicp_view_config;
+int kicp_view_create(const kicp_view_config *config, int device, kicp_view **out);
+void kicp_view_destroy(kicp_view *view);
+/* the configuration, the sensor's world position c of the last frame (NaN before the first, or when that frame's pose or sensor was not
+ * finite) and the frames rendered since creation (each nullable) */
+int kicp_view_info(const kicp_view *view, kicp_view_config *out_config, double out_sensor_world[3], unsigned long long *out_frames);
+/* One frame REPLACES the image.  kicp_view_render takes the points from host memory, kicp_view_render_device where they already are in
+ * HBM, complete (kicp_pre_device_ptr(pre, 0, ..) after kicp_pre_frame has returned: what the drop-in pipeline calls).  Both return
+ * after their kernel has completed.  out_stats (nullable): points used, points skipped.  n == 0 is legal: the image is empty then. */
+int kicp_view_render(kicp_view *view, const double *frame_xyz, size_t n, const double pose_qt[7], const double sensor_xyz[3],
+                     unsigned long long out_stats[2]);
+int kicp_view_render_device(kicp_view *view, const double *d_frame_xyz, size_t n, const double pose_qt[7], const double sensor_xyz[3],
+                            unsigned long long out_stats[2]);
+/* the image: 6 res^2 floats, face-major; cap must be that number (KICP_ERR_ARG otherwise) */
+int kicp_view_depth(const kicp_view *view, float *out, size_t cap);
+/* The verdict for n world points in host memory, one byte each: bit 0 (value 1) seen through, bit 1 (value 2) in range - so 0, 2 or 3.
+ * Useful on its own, e.g. to filter a cloud before it is published. */
+int kicp_view_classify(kicp_view *view, const double *points_xyz, size_t n, unsigned char *out);
+int kicp_map_remove_seen_through(kicp_map *map, kicp_view *view, unsigned long long out_stats[4]);
+
 /* ---- pre-steps of the pipeline on the GPU (pipeline/KinematicICP.cpp:54-62) -----------
  * A kicp_pre owns KICP_PRE_BUFFERS device point buffers.  Results stay in HBM (feed kicp_register_device with
  * kicp_pre_device_ptr) and are downloaded only when the host needs them (map update, return values). */

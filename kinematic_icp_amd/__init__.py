@@ -64,6 +64,13 @@ class GridConfig(C.Structure):
                 ("z_min", C.c_double), ("z_max", C.c_double), ("max_ray", C.c_double)]
 
 
+class ViewConfig(C.Structure):
+    """kicp_view_config: a cube map of res x res pixels per face; the verdict looks at (2 window + 1)^2 pixels, needs min_rays returns
+    among them and a gap of more than margin + margin_per_metre * depth; max_ray bounds the (Chebyshev) depth on both sides"""
+    _fields_ = [("res", C.c_uint), ("window", C.c_int), ("min_rays", C.c_uint), ("max_ray", C.c_double), ("margin", C.c_double),
+                ("margin_per_metre", C.c_double)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p)
 
 _dp = C.POINTER(C.c_double)
@@ -99,6 +106,14 @@ _SIGNATURES = {
     "kicp_map_check": (C.c_size_t, [C.c_void_p]),
     "kicp_map_sync": (C.c_int, [C.c_void_p, C.c_int]),
     "kicp_map_last_upload": (C.c_int, [C.c_void_p, C.POINTER(C.c_size_t), C.POINTER(C.c_int)]),
+    "kicp_view_create": (C.c_int, [C.POINTER(ViewConfig), C.c_int, C.POINTER(C.c_void_p)]),
+    "kicp_view_destroy": (None, [C.c_void_p]),
+    "kicp_view_info": (C.c_int, [C.c_void_p, C.POINTER(ViewConfig), _dp, C.POINTER(C.c_ulonglong)]),
+    "kicp_view_render": (C.c_int, [C.c_void_p, _dp, C.c_size_t, _dp, _dp, C.POINTER(C.c_ulonglong)]),
+    "kicp_view_render_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, _dp, _dp, C.POINTER(C.c_ulonglong)]),
+    "kicp_view_depth": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.c_size_t]),
+    "kicp_view_classify": (C.c_int, [C.c_void_p, _dp, C.c_size_t, C.POINTER(C.c_ubyte)]),
+    "kicp_map_remove_seen_through": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_ulonglong)]),
     "kicp_reg_create": (C.c_int, [C.POINTER(RegConfig), C.c_int, C.POINTER(C.c_void_p)]),
     "kicp_reg_destroy": (None, [C.c_void_p]),
     "kicp_reg_clone": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
@@ -465,6 +480,68 @@ class OccupancyGrid:
         _check(lib().kicp_grid_save_map(self._h, os.fsencode(prefix), int(min_observations), float(occupied_thresh), float(free_thresh)))
 
 
+class DepthView:
+    """kicp_view: a cube map of depths around the sensor, rendered from ONE frame, that tells which world points that frame sees
+    through (include/kicp.h states the exact semantics); VoxelHashMap.RemoveSeenThrough(view) removes them from a map.  It owns its
+    device memory; the image stays in HBM until it is asked for."""
+
+    SEEN_THROUGH, IN_RANGE = 1, 2  # bits of a verdict
+
+    def __init__(self, res, window, min_rays, max_ray, margin, margin_per_metre, device=0):
+        self._h = None
+        cfg = ViewConfig(int(res), int(window), int(min_rays), float(max_ray), float(margin), float(margin_per_metre))
+        h = C.c_void_p()
+        _check(lib().kicp_view_create(C.byref(cfg), int(device), C.byref(h)))
+        self._h, self.device, self.res = h, device, int(res)
+        self._last = np.zeros(2, dtype=np.uint64)
+
+    def __del__(self):
+        if getattr(self, "_h", None) and _lib is not None:
+            _lib.kicp_view_destroy(self._h)
+            self._h = None
+
+    def info(self):
+        """-> dict: the configuration's fields, sensor_world (c of the last frame, NaN before the first) and frames (rendered so far)"""
+        cfg, c, frames = ViewConfig(), np.zeros(3), C.c_ulonglong()
+        _check(lib().kicp_view_info(self._h, C.byref(cfg), c.ctypes.data_as(_dp), C.byref(frames)))
+        out = {name: getattr(cfg, name) for name, _ in ViewConfig._fields_}
+        out.update(sensor_world=c, frames=frames.value)
+        return out
+
+    def render(self, frame, pose, sensor_xyz=(0.0, 0.0, 0.0)):
+        """kicp_view_render: the image of one frame of points in the base frame (host memory) at `pose`, the sensor at `sensor_xyz` in the
+        base frame -> (points used, points skipped)"""
+        a, p = _d(np.asarray(frame, dtype=np.float64).reshape(-1, 3))
+        s, sp = _d(np.asarray(sensor_xyz, dtype=np.float64).reshape(3))
+        _check(lib().kicp_view_render(self._h, p if a.size else None, a.size // 3, _pose_ptr(pose), sp, self._last.ctypes.data_as(C.POINTER(C.c_ulonglong))))
+        return self.last_frame()
+
+    def render_device(self, device_frame, pose, sensor_xyz=(0.0, 0.0, 0.0), n=None):
+        """kicp_view_render_device: the same for a DeviceFrame (or anything with .ptr and .n) already in HBM"""
+        s, sp = _d(np.asarray(sensor_xyz, dtype=np.float64).reshape(3))
+        count = device_frame.n if n is None else int(n)
+        _check(lib().kicp_view_render_device(self._h, device_frame.ptr if count else None, count, _pose_ptr(pose), sp,
+                                             self._last.ctypes.data_as(C.POINTER(C.c_ulonglong))))
+        return self.last_frame()
+
+    def last_frame(self):
+        """(points used, points skipped) of the last rendered frame"""
+        return tuple(int(v) for v in self._last)
+
+    def depth(self):
+        """kicp_view_depth -> float32 (6, res, res): [face, w_, u], +inf where no used point fell"""
+        out = np.empty((6, self.res, self.res), dtype=np.float32)
+        _check(lib().kicp_view_depth(self._h, out.ctypes.data_as(C.POINTER(C.c_float)), out.size))
+        return out
+
+    def classify(self, points):
+        """kicp_view_classify: the verdict for world points -> uint8 per point: bit 0 (SEEN_THROUGH), bit 1 (IN_RANGE)"""
+        a, p = _d(np.asarray(points, dtype=np.float64).reshape(-1, 3))
+        out = np.zeros(a.size // 3, dtype=np.uint8)
+        _check(lib().kicp_view_classify(self._h, p if a.size else None, a.size // 3, out.ctypes.data_as(C.POINTER(C.c_ubyte))))
+        return out
+
+
 class VoxelHashMap:
     """kiss_icp::VoxelHashMap: host-authoritative voxel map with an HBM mirror (SURVEY.md App. A.2)."""
 
@@ -557,6 +634,13 @@ class VoxelHashMap:
     def UpdateFinish(self):
         _check(lib().kicp_map_update_finish(self._h))
         return bool(lib().kicp_map_last_update_on_device(self._h))
+
+    def RemoveSeenThrough(self, view):
+        """kicp_map_remove_seen_through: remove every map point the frame in `view` (a DepthView) sees through -> (points in range, points
+        removed, voxels that lost at least one point, voxels erased).  A pending map update is collected first."""
+        out = (C.c_ulonglong * 4)()
+        _check(lib().kicp_map_remove_seen_through(self._h, view._h, out))
+        return tuple(int(v) for v in out)
 
     def device_updates(self):
         """Updates that ran on the GPU and have been collected (kicp_map_device_updates); a pending one stays pending."""

@@ -117,6 +117,21 @@ inline std::shared_ptr<kicp_grid> clone_grid(const kicp_grid *grid, int device =
     check(kicp_grid_set_counts(copy.get(), counts.data(), cells), "kicp_bridge::clone_grid");
     return copy;
 }
+// The depth view behind KinematicICP::EnableSeeThroughRemoval (kicp.h kicp_view_*): the image of the frame just registered, against
+// which the map is swept.  clone_view is what a copied pipeline gets: a view of the same configuration (the image is per frame: the
+// copy renders its own).
+using ViewConfig = kicp_view_config;
+inline std::shared_ptr<kicp_view> make_view(const ViewConfig &config, int device = -1) {
+    kicp_view *view = nullptr;
+    check(kicp_view_create(&config, device < 0 ? default_device() : device, &view), "kicp_bridge::make_view");
+    return std::shared_ptr<kicp_view>(view, kicp_view_destroy);
+}
+inline std::shared_ptr<kicp_view> clone_view(const kicp_view *view, int device = -1) {
+    if (!view) return nullptr;
+    ViewConfig config{};
+    check(kicp_view_info(view, &config, nullptr, nullptr), "kicp_bridge::clone_view");
+    return make_view(config, device);
+}
 // a warning the reference has no channel for: once per process on stderr
 inline void warn_once(const char *message) {
     static bool said = false;

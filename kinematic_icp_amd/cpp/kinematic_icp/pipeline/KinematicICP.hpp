@@ -8,6 +8,7 @@
 // (SURVEY.md section 8f rows 1, 2 and 4).
 #pragma once
 #include <Eigen/Core>
+#include <array>
 #include <cmath>
 #include <cstdint>
 #include <cstdlib>
@@ -70,7 +71,8 @@ public:
     }
     ~KinematicICP() { kicp_pre_destroy(pre_); }
     // copyable and movable like the reference's class (every member is held by value there, KinematicICP.hpp:100-108): a copy owns
-    // a deep copy of the map (and of the occupancy grid, when one is enabled), a registration handle of its own and its own pre-step workspace
+    // a deep copy of the map (and of the occupancy grid, when one is enabled, and a depth view of the same configuration), a registration
+    // handle of its own and its own pre-step workspace
     KinematicICP(const KinematicICP &o)
         : last_pose_(o.last_pose_),
           registration_(o.registration_),
@@ -79,6 +81,8 @@ public:
           preprocessor_(o.preprocessor_),
           local_map_(o.local_map_),
           grid_(kicp_bridge::clone_grid(o.grid_.get())),
+          view_(kicp_bridge::clone_view(o.view_.get())),
+          last_removal_(o.last_removal_),
           sensor_in_base_(o.sensor_in_base_) {
 #ifndef KICP_HOST_PRESTEPS
         kicp_bridge::check(kicp_pre_create(kicp_bridge::default_device(), &pre_), "KinematicICP");
@@ -93,6 +97,8 @@ public:
           local_map_(std::move(o.local_map_)),
           pre_(o.pre_),
           grid_(std::move(o.grid_)),
+          view_(std::move(o.view_)),
+          last_removal_(o.last_removal_),
           sensor_in_base_(o.sensor_in_base_) {
         o.pre_ = nullptr;
     }
@@ -102,7 +108,7 @@ public:
         std::swap(correspondence_threshold_, o.correspondence_threshold_), std::swap(config_, o.config_), std::swap(preprocessor_, o.preprocessor_);
         local_map_ = std::move(o.local_map_);
         std::swap(pre_, o.pre_);
-        std::swap(grid_, o.grid_), std::swap(sensor_in_base_, o.sensor_in_base_);
+        std::swap(grid_, o.grid_), std::swap(view_, o.view_), std::swap(last_removal_, o.last_removal_), std::swap(sensor_in_base_, o.sensor_in_base_);
         return *this;
     }
 
@@ -138,6 +144,7 @@ public:
         const auto new_pose = registration_.ComputeRobotMotion(source, local_map_, last_pose_, relative_odometry, tau);
         const auto odometry_error = (last_pose_ * relative_odometry).inverse() * new_pose;
         correspondence_threshold_.UpdateOdometryError(odometry_error);
+        if (view_ && config_.update_map) RemoveSeenThrough(kicp_bridge::xyz(preprocessed_frame_in_base), preprocessed_frame_in_base.size(), false, new_pose);
         if (config_.update_map) local_map_.Update(frame_downsample, new_pose);
         last_pose_ = new_pose;
         if (grid_) IntegrateGrid(kicp_bridge::xyz(preprocessed_frame_in_base), preprocessed_frame_in_base.size(), false);
@@ -312,6 +319,19 @@ public:
         kicp_bridge::check(kicp_grid_save_map(RequireGrid("SaveGrid"), prefix.c_str(), min_observations, occupied_thresh, free_thresh), "SaveGrid");
     }
 
+    // ---- backend extension: keeping moving things out of the map (INTEGRATION.md "Keeping moving things out of the map") ----
+    // With see-through removal enabled, RegisterFrame, RegisterIngestedFrame and their F32 variants render the frame they return - the
+    // deskewed, cropped frame in the base frame, all of it - into a depth view at the new pose, with the translation of lidar_to_base
+    // as the sensor, and remove the map points that frame sees through (kicp.h kicp_view_*, kicp_map_remove_seen_through) - after the
+    // pose is known and BEFORE the frame's own points go into the map.  The pose of THIS frame and the returned clouds are what they
+    // are without it; the map, and with it later poses, differ by the removed points.  With Config::update_map == false the map is a
+    // prior and nothing is removed.  LastRemoval(): points in range, points removed, voxels that lost at least one point, voxels
+    // erased of the last frame (zeros before the first, and when the removal was skipped).
+    void EnableSeeThroughRemoval(const kicp_bridge::ViewConfig &config) { view_ = kicp_bridge::make_view(config), last_removal_ = {}; }
+    void DisableSeeThroughRemoval() { view_.reset(), last_removal_ = {}; }
+    std::shared_ptr<kicp_view> View() const { return view_; }
+    const std::array<unsigned long long, 4> &LastRemoval() const { return last_removal_; }
+
     std::vector<Eigen::Vector3d> LocalMap() const { return local_map_.Pointcloud(); }
     const kiss_icp::VoxelHashMap &VoxelMap() const { return local_map_; }
     kiss_icp::VoxelHashMap &VoxelMap() { return local_map_; }
@@ -330,6 +350,15 @@ protected:
         const double sensor[3] = {sensor_in_base_.x(), sensor_in_base_.y(), sensor_in_base_.z()};
         kicp_bridge::check(on_device ? kicp_grid_integrate_device(grid_.get(), xyz, n, pose, sensor, nullptr) : kicp_grid_integrate(grid_.get(), xyz, n, pose, sensor, nullptr),
                            "occupancy grid");
+    }
+    // the frame into the depth view at the new pose, from HBM or from host memory; then the sweep of the map
+    void RemoveSeenThrough(const double *xyz, size_t n, bool on_device, const Sophus::SE3d &new_pose) {
+        double pose[7];
+        kicp_bridge::to_params(new_pose, pose);
+        const double sensor[3] = {sensor_in_base_.x(), sensor_in_base_.y(), sensor_in_base_.z()};
+        kicp_bridge::check(on_device ? kicp_view_render_device(view_.get(), xyz, n, pose, sensor, nullptr) : kicp_view_render(view_.get(), xyz, n, pose, sensor, nullptr),
+                           "depth view");
+        last_removal_ = local_map_.RemoveSeenThrough(view_.get());
     }
 #ifndef KICP_HOST_PRESTEPS
     // From the moment the backend's helper thread holds a pointer into the result's frame vector: should any later step throw,
@@ -352,6 +381,9 @@ protected:
                                                                      relative_odometry, tau);
         trace.lap("threshold + map update");
         correspondence_threshold_.UpdateOdometryError((last_pose_ * relative_odometry).inverse() * new_pose);
+        // see-through removal, when enabled: the whole preprocessed frame (buffer 0, complete since the pre-steps returned) is rendered at
+        // the new pose and the map swept against it, before the frame's own points go in
+        if (view_ && config_.update_map) RemoveSeenThrough(kicp_pre_device_ptr(pre_, 0, nullptr), counts[0], true, new_pose);
         // (the map update's kernels run while this thread collects the two returned clouds: nothing below touches the map or buffer 1)
         if (config_.update_map) local_map_.UpdateDeviceBegin(kicp_pre_device_ptr(pre_, 1, nullptr), n_down, new_pose);
         last_pose_ = new_pose;
@@ -419,6 +451,8 @@ protected:
     kicp_pre *pre_ = nullptr;  // device workspace of the pre-steps (backend detail)
     std::shared_ptr<kicp_occ> occupancy_;  // BuildOccupancy's snapshot of the map (backend detail)
     std::shared_ptr<kicp_grid> grid_;      // EnableGrid's occupancy grid (backend detail); null: no grid
+    std::shared_ptr<kicp_view> view_;      // EnableSeeThroughRemoval's depth view (backend detail); null: nothing is removed
+    std::array<unsigned long long, 4> last_removal_{};  // the last frame's sweep statistics
     Eigen::Vector3d sensor_in_base_ = Eigen::Vector3d(0.0, 0.0, 0.0);  // the translation of the last frame's lidar_to_base
 };
 

@@ -10,6 +10,7 @@
 // compile - clear / erase / insert / emplace / operator[] ... end in a static_assert that names the way out: the map is
 // changed through AddPoints / Update / RemovePointsFarFromLocation / Clear, as every caller in the reference does.
 #pragma once
+#include <array>
 #include <Eigen/Core>
 #include <cmath>
 #include <cstdint>
@@ -169,6 +170,14 @@ struct VoxelHashMap {
         kicp_bridge::check(kicp_map_add_points(handle_, kicp_bridge::xyz(points), points.size()), "VoxelHashMap::AddPoints");
     }
     void RemovePointsFarFromLocation(const Eigen::Vector3d &origin) { kicp_map_remove_far(handle_, origin.data()), ++version_; }
+    // backend extension: remove the points the frame in `view` sees through (kicp.h kicp_map_remove_seen_through)
+    // -> points in range, points removed, voxels that lost at least one point, voxels erased
+    std::array<unsigned long long, 4> RemoveSeenThrough(kicp_view *view) {
+        std::array<unsigned long long, 4> stats{};
+        ++version_;
+        kicp_bridge::check(kicp_map_remove_seen_through(handle_, view, stats.data()), "VoxelHashMap::RemoveSeenThrough");
+        return stats;
+    }
     std::vector<Eigen::Vector3d> Pointcloud() const {
         std::vector<Eigen::Vector3d> points(kicp_map_num_points(handle_));
         if (!points.empty()) kicp_map_pointcloud(handle_, points.front().data(), points.size());

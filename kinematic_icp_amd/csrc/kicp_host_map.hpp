@@ -157,6 +157,41 @@ public:
         ++epoch_;
     }
 
+    // Remove every point p (three doubles) for which remove(p) holds; each point of each occupied voxel is asked once.  The survivors of
+    // a bucket keep their relative order (the voxel's FIRST point is then its first survivor), the fp64 pool and the 16-bit mirror move
+    // alike and the mirror's freed tail is marked empty; a voxel that loses all its points is erased as RemovePointsFarFromLocation
+    // erases one.  out (nullable): points removed, voxels that lost at least one point, voxels erased.
+    template <typename F>
+    void RemovePointsIf(F remove, unsigned long long out[3]) {
+        unsigned long long n_removed = 0, n_touched = 0, n_erased = 0;
+        for (size_t i = 0; i < table_.size(); ++i) {  // no entry moves during the sweep (erase leaves a halo/dead entry)
+            Slot &slot = table_[i];
+            if (slot.val == kEmptyVal || val_count(slot.val, cb_) == 0) continue;
+            const uint32_t count = val_count(slot.val, cb_), bucket = val_bucket(slot.val, cb_);
+            double *b = &pool_[static_cast<size_t>(bucket) * cap_ * 3];
+            MirrorPoint *b16 = &pool16_[static_cast<size_t>(bucket) * cap16_];
+            uint32_t kept = 0;
+            for (uint32_t k = 0; k < count; ++k) {
+                if (remove(static_cast<const double *>(b + 3 * k))) continue;
+                if (kept != k) std::memmove(b + 3 * kept, b + 3 * k, 24), b16[kept] = b16[k];
+                ++kept;
+            }
+            if (kept == count) continue;
+            n_removed += count - kept, ++n_touched;
+            if (kept == 0) {
+                erase_voxel(i), ++n_erased;
+                continue;
+            }
+            for (uint32_t k = kept; k < count; ++k) b16[k] = mirror_empty();
+            slot.val = make_val(bucket, kept, cb_);
+            n_points_ -= count - kept;
+            touch_slot(i), touch_bucket(bucket);
+        }
+        if (n_dead_ * 4 > n_entries_) rebuild(table_.size());
+        ++epoch_;
+        if (out) out[0] = n_removed, out[1] = n_touched, out[2] = n_erased;
+    }
+
     // Update(points, origin) / Update(points, pose) -- App. A.5
     bool Update(const double *xyz, size_t n, const double origin[3]) {
         const bool ok = AddPoints(xyz, n);
