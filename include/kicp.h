@@ -545,6 +545,58 @@ int kicp_grid_save_map(const kicp_grid *grid, const char *prefix, unsigned int m
 int kicp_grid_write_map(const char *prefix, const signed char *occupancy, unsigned int width, unsigned int height, double cell, double origin_x,
                         double origin_y, double occupied_thresh, double free_thresh);
 
+/* ---- what a planner plans on: the clearance of every cell and a Nav2-style costmap of the grid (kicp_grid.hip) -------------------------
+ * Everything below is exact and integer: squared cell distances, and a lookup table for the cost.
+ *
+ * CLASSES.  With v the readout of a cell at `min_observations` (above), a cell is a SOURCE when (double)v > occupied_thresh * 100.0 -
+ * exactly the cells whose pixel in the map image is 0 - UNKNOWN when v < 0, and CLEAR otherwise.  With unknown_is_obstacle != 0 the
+ * unknown cells are sources too.  Cells outside the grid are nothing: neither sources nor anything else.
+ *
+ * CLEARANCE.  With a radius of R = radius_cells, 1 <= R <= 254, the clearance of cell (x, y) is
+ *   c(x, y) = min of dx^2 + dy^2 over the sources at (x + dx, y + dy) with dx^2 + dy^2 <= R^2,   R^2 + 1 ("far") when there is none
+ * - a squared distance in cells, 0 on a source, as 16 bits: R <= 254 keeps a column distance inside a byte and R^2 + 1 = 64 517 inside
+ * 16 bits.  R < 1: KICP_ERR_ARG; R > 254: KICP_ERR_CAPACITY, the limit in the message.
+ *
+ * RECTANGLE.  Every entry takes x0, y0, w, h: a rectangle of grid cells, inside the grid, w and h >= 1 (KICP_ERR_ARG otherwise), and
+ * writes h * w values, row-major from (x0, y0); cap must be w * h (KICP_ERR_ARG otherwise).  Sources within R of the rectangle count
+ * whether they lie inside it or not, so the result for a rectangle EQUALS the result for the full grid - the rectangle (0, 0, width,
+ * height) - restricted to it.  As the transform is local, a frame can change the result only within R cells of its window:
+ * kicp_grid_last_window gives the window of the last integrated frame clipped to the grid, w = h = 0 (and x0 = y0 = 0) when no cell of
+ * it lies inside the grid, before any frame and after kicp_grid_clear.  That rectangle grown by R and clipped is all a node has to
+ * refresh after a frame.
+ *
+ * COSTMAP.  One byte per cell with nav2_costmap_2d's constants: 254 lethal, 253 inscribed, 255 no information, 0 free.  The caller
+ * passes table[0 .. R^2 + 1], the cost of every clearance (table_len must be R^2 + 2, KICP_ERR_ARG otherwise); t = table[c(x, y)].
+ * The cell's base cost is 254 for a source, 255 for an unknown cell that is not a source, 0 for a clear cell.  For a base of 255 the
+ * result is t when (inflate_unknown ? t > 0 : t >= 253) and 255 otherwise; for any other base it is max(base, t) - the rule of Nav2's
+ * inflation layer over a master grid that holds the base costs.
+ * kicp_grid_cost_table_nav2 fills the table Nav2's inflation layer uses (pure host code; cap must be R^2 + 2): table[0] = 254,
+ * table[R^2 + 1] = 0, and for 1 <= d2 <= R^2 with d = sqrt((double)d2) * cell: 253 when d <= inscribed_radius, otherwise
+ * (unsigned char)(252.0 * exp(-cost_scaling_factor * (d - inscribed_radius))).  cell positive and finite, inscribed_radius and
+ * cost_scaling_factor finite and >= 0 (KICP_ERR_ARG otherwise).
+ *
+ * kicp_grid_clearance and kicp_grid_costmap work on the counters where they are, in HBM, and return after their kernels have completed
+ * and the h * w values have arrived; the *_from_occupancy entries are the same arithmetic as pure host code over a readout (width x
+ * height values as kicp_grid_occupancy writes them) and need no GPU.  For every entry: a null pointer, min_observations < 1 or an
+ * occupied_thresh outside [0, 1] is KICP_ERR_ARG. */
+typedef struct kicp_grid_clearance_config {
+    unsigned int min_observations; /* of the readout the classes are taken from (the *_from_occupancy entries only check it) */
+    double occupied_thresh;        /* a cell is a source when (double)v > occupied_thresh * 100.0 */
+    int unknown_is_obstacle;       /* != 0: unknown cells are sources too */
+    int radius_cells;              /* R: 1 .. 254 */
+} kicp_grid_clearance_config;
+int kicp_grid_clearance(const kicp_grid *grid, const kicp_grid_clearance_config *config, unsigned int x0, unsigned int y0, unsigned int w, unsigned int h,
+                        unsigned short *out, size_t cap);
+int kicp_grid_costmap(const kicp_grid *grid, const kicp_grid_clearance_config *config, const unsigned char *table, size_t table_len, int inflate_unknown,
+                      unsigned int x0, unsigned int y0, unsigned int w, unsigned int h, unsigned char *out, size_t cap);
+int kicp_grid_clearance_from_occupancy(const signed char *occupancy, unsigned int width, unsigned int height, const kicp_grid_clearance_config *config,
+                                       unsigned int x0, unsigned int y0, unsigned int w, unsigned int h, unsigned short *out, size_t cap);
+int kicp_grid_costmap_from_occupancy(const signed char *occupancy, unsigned int width, unsigned int height, const kicp_grid_clearance_config *config,
+                                     const unsigned char *table, size_t table_len, int inflate_unknown, unsigned int x0, unsigned int y0, unsigned int w,
+                                     unsigned int h, unsigned char *out, size_t cap);
+int kicp_grid_cost_table_nav2(double cell, int radius_cells, double inscribed_radius, double cost_scaling_factor, unsigned char *table, size_t cap);
+int kicp_grid_last_window(const kicp_grid *grid, unsigned int *x0, unsigned int *y0, unsigned int *w, unsigned int *h);
+
 /* ---- map points the new frame sees through: a cube-map depth test (kicp_view.hip) ----------------------------------------------------
  * The local map loses points by distance only (RemovePointsFarFromLocation); whatever stood in view for one frame - a person crossing,
  * a forklift, a door leaf - stays until the robot is max_range away.  A kicp_view holds a depth image of ONE frame, and

@@ -13,6 +13,7 @@ There is NO CPU fallback: importing works anywhere, but creating a KinematicRegi
 device operation) without the built extension or without a visible gfx950 device raises KicpError.
 """
 import ctypes as C
+import math
 import os
 
 import numpy as np
@@ -62,6 +63,12 @@ class GridConfig(C.Structure):
     cell lies within ceil(max_ray / cell) cells of the sensor's count"""
     _fields_ = [("cell", C.c_double), ("origin_x", C.c_double), ("origin_y", C.c_double), ("width", C.c_uint), ("height", C.c_uint),
                 ("z_min", C.c_double), ("z_max", C.c_double), ("max_ray", C.c_double)]
+
+
+class GridClearanceConfig(C.Structure):
+    """kicp_grid_clearance_config: the readout's min_observations, the threshold above which a cell is a source, whether unknown cells
+    are sources too, and the radius R in cells (1 .. 254)"""
+    _fields_ = [("min_observations", C.c_uint), ("occupied_thresh", C.c_double), ("unknown_is_obstacle", C.c_int), ("radius_cells", C.c_int)]
 
 
 class ViewConfig(C.Structure):
@@ -167,6 +174,15 @@ _SIGNATURES = {
     "kicp_grid_occupancy_from_counts": (C.c_int, [C.POINTER(C.c_ushort), C.c_size_t, C.c_uint, C.POINTER(C.c_byte)]),
     "kicp_grid_save_map": (C.c_int, [C.c_void_p, C.c_char_p, C.c_uint, C.c_double, C.c_double]),
     "kicp_grid_write_map": (C.c_int, [C.c_char_p, C.POINTER(C.c_byte), C.c_uint, C.c_uint, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double]),
+    "kicp_grid_clearance": (C.c_int, [C.c_void_p, C.POINTER(GridClearanceConfig), C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.POINTER(C.c_ushort), C.c_size_t]),
+    "kicp_grid_costmap": (C.c_int, [C.c_void_p, C.POINTER(GridClearanceConfig), C.POINTER(C.c_ubyte), C.c_size_t, C.c_int, C.c_uint, C.c_uint, C.c_uint, C.c_uint,
+                                    C.POINTER(C.c_ubyte), C.c_size_t]),
+    "kicp_grid_clearance_from_occupancy": (C.c_int, [C.POINTER(C.c_byte), C.c_uint, C.c_uint, C.POINTER(GridClearanceConfig), C.c_uint, C.c_uint, C.c_uint, C.c_uint,
+                                                     C.POINTER(C.c_ushort), C.c_size_t]),
+    "kicp_grid_costmap_from_occupancy": (C.c_int, [C.POINTER(C.c_byte), C.c_uint, C.c_uint, C.POINTER(GridClearanceConfig), C.POINTER(C.c_ubyte), C.c_size_t, C.c_int,
+                                                   C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.POINTER(C.c_ubyte), C.c_size_t]),
+    "kicp_grid_cost_table_nav2": (C.c_int, [C.c_double, C.c_int, C.c_double, C.c_double, C.POINTER(C.c_ubyte), C.c_size_t]),
+    "kicp_grid_last_window": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_uint)]),
     "kicp_planar_grid": (C.c_size_t, [_dp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _dp, C.c_size_t]),
     "kicp_map_save_pcd": (C.c_int, [C.c_void_p, C.c_char_p]),
     "kicp_map_load_pcd": (C.c_int, [C.c_char_p, C.c_double, C.c_double, C.c_uint, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
@@ -408,6 +424,75 @@ def write_map(prefix, occupancy, cell, origin_x, origin_y, occupied_thresh=0.65,
                                      float(origin_y), float(occupied_thresh), float(free_thresh)))
 
 
+def _clearance_config(radius_cells, min_observations, occupied_thresh, unknown_is_obstacle):
+    return GridClearanceConfig(int(min_observations), float(occupied_thresh), 1 if unknown_is_obstacle else 0, int(radius_cells))
+
+
+def _rect(rect, width, height):
+    """(x0, y0, w, h) of `rect`, the full grid for None; negative numbers are passed as something the library refuses"""
+    x0, y0, w, h = (0, 0, width, height) if rect is None else (int(v) for v in rect)
+    if min(x0, y0, w, h) < 0:
+        raise KicpError(KICP_ERR_ARG, "the rectangle (x0, y0, w, h) must not be negative")
+    return x0, y0, w, h
+
+
+def _cost_table(table):
+    t = np.ascontiguousarray(table, dtype=np.uint8)
+    if t.ndim != 1:
+        raise KicpError(KICP_ERR_ARG, "the cost table must be one-dimensional: table[0 .. R^2 + 1]")
+    return t
+
+
+def _occupancy_2d(occupancy):
+    occ = np.ascontiguousarray(occupancy, dtype=np.int8)
+    if occ.ndim != 2 or occ.size == 0:
+        raise KicpError(KICP_ERR_ARG, "occupancy must be shaped (height, width), both at least 1")
+    return occ
+
+
+def clearance_from_occupancy(occupancy, radius_cells, min_observations=1, occupied_thresh=0.65, unknown_is_obstacle=False, rect=None):
+    """kicp_grid_clearance_from_occupancy: the squared distance in cells from every cell of `rect` = (x0, y0, w, h) (None: the full grid)
+    to the nearest source within radius_cells of it, radius_cells^2 + 1 where there is none, over a readout shaped (height, width) ->
+    uint16 (h, w).  Pure host code: needs no GPU."""
+    occ = _occupancy_2d(occupancy)
+    x0, y0, w, h = _rect(rect, occ.shape[1], occ.shape[0])
+    cfg = _clearance_config(radius_cells, min_observations, occupied_thresh, unknown_is_obstacle)
+    out = np.empty((h, w), dtype=np.uint16)
+    _check(lib().kicp_grid_clearance_from_occupancy(occ.ctypes.data_as(C.POINTER(C.c_byte)), occ.shape[1], occ.shape[0], C.byref(cfg), x0, y0, w, h,
+                                                    out.ctypes.data_as(C.POINTER(C.c_ushort)), out.size))
+    return out
+
+
+def costmap_from_occupancy(occupancy, table, min_observations=1, occupied_thresh=0.65, unknown_is_obstacle=False, inflate_unknown=False, rect=None):
+    """kicp_grid_costmap_from_occupancy: Nav2's costs (254 lethal, 253 inscribed, 255 no information, 0 free) of the cells of `rect` from
+    `table`[clearance] (length R^2 + 2, which gives R) over a readout shaped (height, width) -> uint8 (h, w).  Pure host code."""
+    occ, t = _occupancy_2d(occupancy), _cost_table(table)
+    x0, y0, w, h = _rect(rect, occ.shape[1], occ.shape[0])
+    cfg = _clearance_config(_table_radius(t), min_observations, occupied_thresh, unknown_is_obstacle)
+    out = np.empty((h, w), dtype=np.uint8)
+    _check(lib().kicp_grid_costmap_from_occupancy(occ.ctypes.data_as(C.POINTER(C.c_byte)), occ.shape[1], occ.shape[0], C.byref(cfg),
+                                                  t.ctypes.data_as(C.POINTER(C.c_ubyte)), t.size, 1 if inflate_unknown else 0, x0, y0, w, h,
+                                                  out.ctypes.data_as(C.POINTER(C.c_ubyte)), out.size))
+    return out
+
+
+def _table_radius(table):
+    """R of a table of R^2 + 2 entries (any other length: KICP_ERR_ARG)"""
+    r = math.isqrt(max(int(table.size) - 2, 0))
+    if r * r + 2 != table.size:
+        raise KicpError(KICP_ERR_ARG, "the cost table must have R^2 + 2 entries, table[0 .. R^2 + 1]")
+    return r
+
+
+def nav2_cost_table(cell, radius_cells, inscribed_radius, cost_scaling_factor):
+    """kicp_grid_cost_table_nav2: the table of Nav2's inflation layer for a radius of radius_cells cells of `cell` metres -> uint8
+    [radius_cells^2 + 2]: 254 at 0, 253 up to inscribed_radius, 252 exp(-cost_scaling_factor (d - inscribed_radius)) beyond, 0 for far"""
+    r = int(radius_cells)
+    out = np.empty(r * r + 2 if 1 <= r <= 254 else 2, dtype=np.uint8)
+    _check(lib().kicp_grid_cost_table_nav2(float(cell), r, float(inscribed_radius), float(cost_scaling_factor), out.ctypes.data_as(C.POINTER(C.c_ubyte)), out.size))
+    return out
+
+
 class OccupancyGrid:
     """kicp_grid: a world-aligned 2-D grid of (hits, misses) counters a mapping run draws frame by frame - every used point's cell is
     hit, the cells its ray from the sensor crosses are missed, once per cell per frame (include/kicp.h states the exact semantics).
@@ -474,6 +559,34 @@ class OccupancyGrid:
         out = np.empty((self.height, self.width), dtype=np.int8)
         _check(lib().kicp_grid_occupancy(self._h, int(min_observations), out.ctypes.data_as(C.POINTER(C.c_byte)), out.size))
         return out
+
+    def clearance(self, radius_cells, min_observations=1, occupied_thresh=0.65, unknown_is_obstacle=False, rect=None):
+        """kicp_grid_clearance: on the GPU, the squared distance in cells from every cell of `rect` = (x0, y0, w, h) (None: the full grid)
+        to the nearest source within radius_cells of it - inside the rectangle or not - radius_cells^2 + 1 where there is none
+        -> uint16 (h, w)"""
+        x0, y0, w, h = _rect(rect, self.width, self.height)
+        cfg = _clearance_config(radius_cells, min_observations, occupied_thresh, unknown_is_obstacle)
+        out = np.empty((h, w), dtype=np.uint16)
+        _check(lib().kicp_grid_clearance(self._h, C.byref(cfg), x0, y0, w, h, out.ctypes.data_as(C.POINTER(C.c_ushort)), out.size))
+        return out
+
+    def costmap(self, table, min_observations=1, occupied_thresh=0.65, unknown_is_obstacle=False, inflate_unknown=False, rect=None):
+        """kicp_grid_costmap: on the GPU, Nav2's costs of the cells of `rect` from `table`[clearance] (nav2_cost_table builds one; its
+        length R^2 + 2 gives R) -> uint8 (h, w): a nav2_msgs/Costmap's data"""
+        t = _cost_table(table)
+        x0, y0, w, h = _rect(rect, self.width, self.height)
+        cfg = _clearance_config(_table_radius(t), min_observations, occupied_thresh, unknown_is_obstacle)
+        out = np.empty((h, w), dtype=np.uint8)
+        _check(lib().kicp_grid_costmap(self._h, C.byref(cfg), t.ctypes.data_as(C.POINTER(C.c_ubyte)), t.size, 1 if inflate_unknown else 0, x0, y0, w, h,
+                                       out.ctypes.data_as(C.POINTER(C.c_ubyte)), out.size))
+        return out
+
+    def last_window(self):
+        """kicp_grid_last_window: (x0, y0, w, h) of the last integrated frame's window clipped to the grid; w = h = 0 when it lies
+        outside and before any frame.  Grown by R and clipped it is all a costmap has to refresh after that frame."""
+        v = [C.c_uint() for _ in range(4)]
+        _check(lib().kicp_grid_last_window(self._h, *[C.byref(x) for x in v]))
+        return tuple(int(x.value) for x in v)
 
     def save_map(self, prefix, min_observations=1, occupied_thresh=0.65, free_thresh=0.25):
         """kicp_grid_save_map: <prefix>.pgm + <prefix>.yaml of the readout"""

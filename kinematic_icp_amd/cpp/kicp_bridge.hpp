@@ -99,8 +99,22 @@ inline kicp_search_window search_window_around(const kicp_occ *occ, const Eigen:
 }
 // The 2-D occupancy grid a mapping run draws for a planner (kicp.h kicp_grid_*): KinematicICP::EnableGrid takes a GridConfig and holds
 // the handle shared, so a node can keep KinematicICP::Grid() for its map publisher.  clone_grid is the deep copy a copied pipeline
-// gets: a grid of the same configuration with the same counters (its frame count starts again).
+// gets: a grid of the same configuration with the same counters (its frame count and its last window start again).
+// GridClearanceConfig and GridRect are what KinematicICP::GridClearance / GridCostmap take: the classes and the radius, and a rectangle
+// of cells (x0, y0, w, h) - GridLastWindow returns one, grown() is that rectangle R cells larger on every side and clipped.
 using GridConfig = kicp_grid_config;
+using GridClearanceConfig = kicp_grid_clearance_config;
+struct GridRect {
+    unsigned int x0 = 0, y0 = 0, w = 0, h = 0;
+    bool empty() const { return w == 0 || h == 0; }
+    GridRect grown(unsigned int cells, unsigned int width, unsigned int height) const {
+        GridRect g;
+        g.x0 = x0 > cells ? x0 - cells : 0u, g.y0 = y0 > cells ? y0 - cells : 0u;
+        const unsigned long long x1 = static_cast<unsigned long long>(x0) + w + cells, y1 = static_cast<unsigned long long>(y0) + h + cells;
+        g.w = static_cast<unsigned int>(x1 < width ? x1 : width) - g.x0, g.h = static_cast<unsigned int>(y1 < height ? y1 : height) - g.y0;
+        return g;
+    }
+};
 inline std::shared_ptr<kicp_grid> make_grid(const GridConfig &config, int device = -1) {
     kicp_grid *grid = nullptr;
     check(kicp_grid_create(&config, device < 0 ? default_device() : device, &grid), "kicp_bridge::make_grid");

@@ -314,6 +314,30 @@ public:
         data.resize(static_cast<size_t>(config.width) * config.height);
         kicp_bridge::check(kicp_grid_occupancy(grid_.get(), min_observations, reinterpret_cast<signed char *>(data.data()), data.size()), "GridOccupancy");
     }
+    // What a planner plans on (kicp.h kicp_grid_clearance .. kicp_grid_last_window), computed on the GPU from the counters where they
+    // are.  GridClearance: per cell of `rect` (null: the full grid) the squared distance in cells to the nearest source within
+    // config.radius_cells, radius_cells^2 + 1 where there is none.  GridCostmap: a nav2_msgs/Costmap's data, Nav2's inflation rule over
+    // `table` (radius_cells^2 + 2 entries; kicp_grid_cost_table_nav2 fills Nav2's own).  The result for a rectangle equals the full
+    // grid's restricted to it, and a frame changes nothing beyond GridLastWindow().grown(radius_cells, width, height): that is all a
+    // node has to refresh after RegisterFrame.
+    void GridClearance(std::vector<uint16_t> &data, const kicp_bridge::GridClearanceConfig &config, const kicp_bridge::GridRect *rect = nullptr) const {
+        const kicp_bridge::GridRect r = GridRectOrAll(rect, "GridClearance");
+        data.resize(static_cast<size_t>(r.w) * r.h);
+        kicp_bridge::check(kicp_grid_clearance(grid_.get(), &config, r.x0, r.y0, r.w, r.h, data.data(), data.size()), "GridClearance");
+    }
+    void GridCostmap(std::vector<uint8_t> &data, const kicp_bridge::GridClearanceConfig &config, const std::vector<uint8_t> &table, bool inflate_unknown = false,
+                     const kicp_bridge::GridRect *rect = nullptr) const {
+        const kicp_bridge::GridRect r = GridRectOrAll(rect, "GridCostmap");
+        data.resize(static_cast<size_t>(r.w) * r.h);
+        kicp_bridge::check(kicp_grid_costmap(grid_.get(), &config, table.data(), table.size(), inflate_unknown ? 1 : 0, r.x0, r.y0, r.w, r.h, data.data(), data.size()),
+                           "GridCostmap");
+    }
+    // the window of the last integrated frame clipped to the grid; empty() when it lies outside, and before any frame
+    kicp_bridge::GridRect GridLastWindow() const {
+        kicp_bridge::GridRect r;
+        kicp_bridge::check(kicp_grid_last_window(RequireGrid("GridLastWindow"), &r.x0, &r.y0, &r.w, &r.h), "GridLastWindow");
+        return r;
+    }
     // <prefix>.pgm + <prefix>.yaml, the pair map_server and Nav2 read
     void SaveGrid(const std::string &prefix, unsigned int min_observations = 1, double occupied_thresh = 0.65, double free_thresh = 0.25) const {
         kicp_bridge::check(kicp_grid_save_map(RequireGrid("SaveGrid"), prefix.c_str(), min_observations, occupied_thresh, free_thresh), "SaveGrid");
@@ -342,6 +366,14 @@ protected:
     const kicp_grid *RequireGrid(const char *who) const {
         if (!grid_) throw std::runtime_error(std::string("KinematicICP::") + who + ": call EnableGrid first");
         return grid_.get();
+    }
+    kicp_bridge::GridRect GridRectOrAll(const kicp_bridge::GridRect *rect, const char *who) const {
+        if (rect) return RequireGrid(who), *rect;
+        kicp_grid_config config{};
+        kicp_bridge::check(kicp_grid_info(RequireGrid(who), &config, nullptr, nullptr), who);
+        kicp_bridge::GridRect all;
+        all.w = config.width, all.h = config.height;
+        return all;
     }
     // one frame into the grid at last_pose_ (already the new pose), from HBM or from host memory
     void IntegrateGrid(const double *xyz, size_t n, bool on_device) {

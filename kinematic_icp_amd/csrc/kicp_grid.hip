@@ -1,10 +1,13 @@
 // kicp_grid.hip -- the 2-D occupancy grid a mapping run draws beside its voxel map (kicp_grid_*; include/kicp.h states the semantics):
 // per frame the used points' endpoint cells are HIT and the cells their rays cross are MISS, once per cell per frame.  Kernels:
 // kicp_grid.hpp; the geometry they share with the host entries: kicp_grid_host.hpp.  A handle owns its stream, its staging buffer and
-// its device memory: the counters (cells x 2 x 16 bit) and the two frame-local planes over the window.
+// its device memory: the counters (cells x 2 x 16 bit) and the two frame-local planes over the window.  The clearance and the costmap
+// a planner reads off the counters (kicp_grid_clearance, kicp_grid_costmap; kernels: kicp_clear.hpp, arithmetic: kicp_clear_host.hpp)
+// are entries of the same handle.
 #include <cerrno>
 #include <memory>
 
+#include "kicp_clear.hpp"
 #include "kicp_grid.hpp"
 #include "kicp_internal.hpp"
 
@@ -18,6 +21,8 @@ struct kicp_grid {
     size_t cells = 0;
     uint32_t plane_words = 0;  // ceil((2 reach + 1)^2 / 4)
     unsigned long long frames = 0;
+    bool has_window = false;  // a frame has been integrated since creation or the last clear: (win_x0, win_y0) is its window's lower corner
+    int32_t win_x0 = 0, win_y0 = 0;
     hipStream_t stream = nullptr;
     DevBuf<uint16_t> d_counts;          // cells x 2: hits, misses
     DevBuf<uint32_t> d_hit, d_miss;     // the planes, zero between frames
@@ -26,6 +31,9 @@ struct kicp_grid {
     PinnedBuf<unsigned int> h_stats;
     DevBuf<double> d_frame;             // kicp_grid_integrate's upload
     DevBuf<int8_t> d_occupancy;         // kicp_grid_occupancy's readout
+    DevBuf<uint8_t> d_coldist;          // kicp_grid_clearance / kicp_grid_costmap: the column distances, the caller's table and the result
+    DevBuf<uint8_t> d_cost_table, d_cost;
+    DevBuf<uint16_t> d_clearance;
     HostStage stage;
     ~kicp_grid() {
         if (stream) (void)hipStreamSynchronize(stream), (void)hipStreamDestroy(stream);
@@ -43,8 +51,9 @@ int check_thresholds(double occupied_thresh, double free_thresh) {
 // the frame at d_xyz (n points; arguments checked): three launches, the statistics back, the stream drained
 int integrate_on_device(kicp_grid *grid, const double *d_xyz, size_t n, const double pose_qt[7], const double sensor_xyz[3], unsigned long long out_stats[4]) {
     unsigned long long stats[4] = {0, n, 0, 0};
+    const GridFrame f = grid_frame(grid->geom, pose_qt, sensor_xyz);
+    grid->has_window = true, grid->win_x0 = f.gx0, grid->win_y0 = f.gy0;
     if (n) {
-        const GridFrame f = grid_frame(grid->geom, pose_qt, sensor_xyz);
         hipStream_t st = grid->stream;
         if (n > grid->d_rays.capacity()) {
             HIP_TRY(hipStreamSynchronize(st));
@@ -73,6 +82,63 @@ int integrate_on_device(kicp_grid *grid, const double *d_xyz, size_t n, const do
 int check_frame_args(const kicp_grid *grid, const double *xyz, size_t n, const double *pose_qt, const double *sensor_xyz) {
     if (!grid || !pose_qt || !sensor_xyz || (!xyz && n)) return fail(KICP_ERR_ARG, "null argument");
     if (n > kGridMaxPoints) return fail(KICP_ERR_CAPACITY, "frame too large");
+    return KICP_OK;
+}
+// the configuration of a clearance call as the kernels take it
+int check_clear_config(const kicp_grid_clearance_config *cfg, ClearParams &p) {
+    if (cfg->min_observations < 1u) return fail(KICP_ERR_ARG, "min_observations must be at least 1");
+    if (!(0.0 <= cfg->occupied_thresh && cfg->occupied_thresh <= 1.0)) return fail(KICP_ERR_ARG, "occupied_thresh must lie in [0, 1]");
+    if (cfg->radius_cells < 1) return fail(KICP_ERR_ARG, "radius_cells must be at least 1");
+    if (cfg->radius_cells > kClearMaxRadius)
+        return fail(KICP_ERR_CAPACITY, "radius_cells = " + std::to_string(cfg->radius_cells) + " (limit " + std::to_string(kClearMaxRadius) + ")");
+    p = ClearParams{cfg->min_observations, clear_source_min(cfg->occupied_thresh), cfg->unknown_is_obstacle ? 1u : 0u, static_cast<uint32_t>(cfg->radius_cells)};
+    return KICP_OK;
+}
+int check_clear_rect(unsigned int width, unsigned int height, const ClearRect &r, size_t cap) {
+    if (r.w < 1u || r.h < 1u || r.x0 >= width || r.y0 >= height || r.w > width - r.x0 || r.h > height - r.y0)
+        return fail(KICP_ERR_ARG, "the rectangle must lie inside the grid of " + std::to_string(width) + " x " + std::to_string(height) + " cells, w and h at least 1");
+    if (cap != static_cast<size_t>(r.w) * r.h) return fail(KICP_ERR_ARG, "cap must be w * h = " + std::to_string(static_cast<size_t>(r.w) * r.h));
+    return KICP_OK;
+}
+int check_cost_table(const ClearParams &p, size_t table_len) {
+    if (table_len != static_cast<size_t>(clear_far(p.radius)) + 1u)
+        return fail(KICP_ERR_ARG, "the table must have radius_cells^2 + 2 = " + std::to_string(clear_far(p.radius) + 1u) + " entries");
+    return KICP_OK;
+}
+// The clearance (table == nullptr: 16 bits per cell into `out`) or the costmap (a byte per cell) of a rectangle; arguments checked.
+// Two launches, one copy, the stream drained.  The buffers grow while the stream is idle: every entry of the handle drains it.
+int clear_on_device(kicp_grid *grid, const ClearParams &p, const ClearRect &r, const unsigned char *table, uint32_t inflate_unknown, void *out) {
+    if (int rc = set_device(grid->device)) return rc;
+    const size_t cells = static_cast<size_t>(r.w) * r.h;
+    uint32_t cx0, cx1;
+    clear_host::column_range(grid->cfg.width, r, p.radius, cx0, cx1);
+    const uint32_t cw = cx1 - cx0;
+    hipStream_t st = grid->stream;
+    if (int rc = grid->d_coldist.reserve(static_cast<size_t>(cw) * r.h)) return rc;
+    if (table) {
+        if (int rc = grid->d_cost.reserve(cells)) return rc;
+        if (int rc = grid->d_cost_table.reserve(static_cast<size_t>(clear_far(kClearMaxRadius)) + 1u)) return rc;
+        HIP_TRY(hipMemcpyAsync(grid->d_cost_table.get(), table, static_cast<size_t>(clear_far(p.radius)) + 1u, hipMemcpyHostToDevice, st));
+    } else if (int rc = grid->d_clearance.reserve(cells)) {
+        return rc;
+    }
+    // a strip of at least R rows keeps the rows a workgroup reads beside its own at or below twice its own
+    const uint32_t strip = std::max(32u, p.radius), strips = (r.h + strip - 1u) / strip, col_blocks = (cw + kClearBlock - 1u) / kClearBlock;
+    const uint32_t segments = (r.w + kClearSegment - 1u) / kClearSegment;  // (both products stay below 2^29: cells <= 2^28)
+    hipLaunchKernelGGL(k_clear_columns, dim3(strips * col_blocks), dim3(kClearBlock), 0, st, grid->d_counts.get(), grid->cfg.width, grid->cfg.height, p, r, cx0, cw, strip,
+                       col_blocks, grid->d_coldist.get());
+    if (table)
+        hipLaunchKernelGGL(k_clear_rows<true>, dim3(r.h * segments), dim3(kClearBlock), 0, st, grid->d_coldist.get(), cx0, cw, grid->d_counts.get(), grid->cfg.width, p, r,
+                           segments, grid->d_cost_table.get(), inflate_unknown, static_cast<void *>(grid->d_cost.get()));
+    else
+        hipLaunchKernelGGL(k_clear_rows<false>, dim3(r.h * segments), dim3(kClearBlock), 0, st, grid->d_coldist.get(), cx0, cw, grid->d_counts.get(), grid->cfg.width, p, r,
+                           segments, static_cast<const uint8_t *>(nullptr), 0u, static_cast<void *>(grid->d_clearance.get()));
+    HIP_TRY(hipGetLastError());
+    if (table)
+        HIP_TRY(hipMemcpyAsync(out, grid->d_cost.get(), cells, hipMemcpyDeviceToHost, st));
+    else
+        HIP_TRY(hipMemcpyAsync(out, grid->d_clearance.get(), cells * sizeof(uint16_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     return KICP_OK;
 }
 }  // namespace
@@ -132,7 +198,7 @@ int kicp_grid_clear(kicp_grid *grid) {
     if (int rc = set_device(grid->device)) return rc;
     HIP_TRY(hipMemsetAsync(grid->d_counts.get(), 0, 2 * grid->cells * sizeof(uint16_t), grid->stream));
     HIP_TRY(hipStreamSynchronize(grid->stream));
-    grid->frames = 0;
+    grid->frames = 0, grid->has_window = false;
     return KICP_OK;
 }
 int kicp_grid_integrate(kicp_grid *grid, const double *frame_xyz, size_t n, const double pose_qt[7], const double sensor_xyz[3], unsigned long long out_stats[4]) {
@@ -192,6 +258,73 @@ int kicp_grid_occupancy_from_counts(const unsigned short *counts, size_t cells, 
     if ((!counts || !out) && cells) return fail(KICP_ERR_ARG, "null argument");
     if (min_observations < 1u) return fail(KICP_ERR_ARG, "min_observations must be at least 1");
     for (size_t i = 0; i < cells; ++i) out[i] = grid_readout(counts[2 * i], counts[2 * i + 1], min_observations);
+    return KICP_OK;
+}
+int kicp_grid_clearance(const kicp_grid *cgrid, const kicp_grid_clearance_config *cfg, unsigned int x0, unsigned int y0, unsigned int w, unsigned int h,
+                        unsigned short *out, size_t cap) {
+    KICP_TRACE_CALL();
+    if (!cgrid || !cfg || !out) return fail(KICP_ERR_ARG, "null argument");
+    ClearParams p;
+    const ClearRect r{x0, y0, w, h};
+    if (int rc = check_clear_config(cfg, p)) return rc;
+    if (int rc = check_clear_rect(cgrid->cfg.width, cgrid->cfg.height, r, cap)) return rc;
+    return clear_on_device(const_cast<kicp_grid *>(cgrid), p, r, nullptr, 0u, out);  // logically const: the buffers are scratch
+}
+int kicp_grid_costmap(const kicp_grid *cgrid, const kicp_grid_clearance_config *cfg, const unsigned char *table, size_t table_len, int inflate_unknown, unsigned int x0,
+                      unsigned int y0, unsigned int w, unsigned int h, unsigned char *out, size_t cap) {
+    KICP_TRACE_CALL();
+    if (!cgrid || !cfg || !table || !out) return fail(KICP_ERR_ARG, "null argument");
+    ClearParams p;
+    const ClearRect r{x0, y0, w, h};
+    if (int rc = check_clear_config(cfg, p)) return rc;
+    if (int rc = check_cost_table(p, table_len)) return rc;
+    if (int rc = check_clear_rect(cgrid->cfg.width, cgrid->cfg.height, r, cap)) return rc;
+    return clear_on_device(const_cast<kicp_grid *>(cgrid), p, r, table, inflate_unknown ? 1u : 0u, out);
+}
+int kicp_grid_clearance_from_occupancy(const signed char *occupancy, unsigned int width, unsigned int height, const kicp_grid_clearance_config *cfg, unsigned int x0,
+                                       unsigned int y0, unsigned int w, unsigned int h, unsigned short *out, size_t cap) {
+    if (!occupancy || !cfg || !out) return fail(KICP_ERR_ARG, "null argument");
+    ClearParams p;
+    const ClearRect r{x0, y0, w, h};
+    if (int rc = check_clear_config(cfg, p)) return rc;
+    if (int rc = check_clear_rect(width, height, r, cap)) return rc;
+    clear_host::clearance(reinterpret_cast<const int8_t *>(occupancy), width, height, p, r, out);
+    return KICP_OK;
+}
+int kicp_grid_costmap_from_occupancy(const signed char *occupancy, unsigned int width, unsigned int height, const kicp_grid_clearance_config *cfg,
+                                     const unsigned char *table, size_t table_len, int inflate_unknown, unsigned int x0, unsigned int y0, unsigned int w, unsigned int h,
+                                     unsigned char *out, size_t cap) {
+    if (!occupancy || !cfg || !table || !out) return fail(KICP_ERR_ARG, "null argument");
+    ClearParams p;
+    const ClearRect r{x0, y0, w, h};
+    if (int rc = check_clear_config(cfg, p)) return rc;
+    if (int rc = check_cost_table(p, table_len)) return rc;
+    if (int rc = check_clear_rect(width, height, r, cap)) return rc;
+    clear_host::costmap(reinterpret_cast<const int8_t *>(occupancy), width, height, p, table, inflate_unknown ? 1u : 0u, r, out);
+    return KICP_OK;
+}
+int kicp_grid_cost_table_nav2(double cell, int radius_cells, double inscribed_radius, double cost_scaling_factor, unsigned char *table, size_t cap) {
+    if (!table) return fail(KICP_ERR_ARG, "null argument");
+    if (radius_cells < 1) return fail(KICP_ERR_ARG, "radius_cells must be at least 1");
+    if (radius_cells > kClearMaxRadius)
+        return fail(KICP_ERR_CAPACITY, "radius_cells = " + std::to_string(radius_cells) + " (limit " + std::to_string(kClearMaxRadius) + ")");
+    if (!(cell > 0.0) || !std::isfinite(cell)) return fail(KICP_ERR_ARG, "cell must be positive and finite");
+    if (!(inscribed_radius >= 0.0) || !std::isfinite(inscribed_radius) || !(cost_scaling_factor >= 0.0) || !std::isfinite(cost_scaling_factor))
+        return fail(KICP_ERR_ARG, "inscribed_radius and cost_scaling_factor must be finite and not negative");
+    const ClearParams p{1u, 0, 0u, static_cast<uint32_t>(radius_cells)};
+    if (int rc = check_cost_table(p, cap)) return rc;
+    clear_host::cost_table_nav2(cell, p.radius, inscribed_radius, cost_scaling_factor, table);
+    return KICP_OK;
+}
+int kicp_grid_last_window(const kicp_grid *grid, unsigned int *x0, unsigned int *y0, unsigned int *w, unsigned int *h) {
+    if (!grid || !x0 || !y0 || !w || !h) return fail(KICP_ERR_ARG, "null argument");
+    *x0 = *y0 = *w = *h = 0u;
+    if (!grid->has_window) return KICP_OK;
+    const int64_t side = 2 * static_cast<int64_t>(grid->geom.reach) + 1;
+    const int64_t ax = std::max<int64_t>(grid->win_x0, 0), bx = std::min<int64_t>(grid->win_x0 + side, grid->cfg.width);
+    const int64_t ay = std::max<int64_t>(grid->win_y0, 0), by = std::min<int64_t>(grid->win_y0 + side, grid->cfg.height);
+    if (ax >= bx || ay >= by) return KICP_OK;
+    *x0 = static_cast<unsigned int>(ax), *y0 = static_cast<unsigned int>(ay), *w = static_cast<unsigned int>(bx - ax), *h = static_cast<unsigned int>(by - ay);
     return KICP_OK;
 }
 int kicp_grid_write_map(const char *prefix, const signed char *occupancy, unsigned int width, unsigned int height, double cell, double origin_x, double origin_y,
