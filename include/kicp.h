@@ -44,7 +44,8 @@ enum {
                                          index addresses - 2^24-2 at <= 255 points per voxel -, a per-point term of the normal
                                          equations >= 2^43: source points ~2 900 km from the base frame, a voxel coordinate beyond
                                          +-2^20 in kicp_pre_voxel_downsample) */
-    KICP_ERR_COMM = -4                /* a multi-GPU exchange failed (RCCL, peer mailboxes, shared segment): a peer did not show up in time */
+    KICP_ERR_COMM = -4,               /* a multi-GPU exchange failed (RCCL, peer mailboxes, shared segment): a peer did not show up in time */
+    KICP_ERR_INTERNAL = -5            /* a bound the library proves for itself did not hold (kicp_grid_potential's round limit): a bug, please report */
 };
 
 typedef struct kicp_map kicp_map; /* twin of kiss_icp::VoxelHashMap: host-authoritative voxel map + HBM mirror */
@@ -596,6 +597,69 @@ int kicp_grid_costmap_from_occupancy(const signed char *occupancy, unsigned int 
                                      unsigned int h, unsigned char *out, size_t cap);
 int kicp_grid_cost_table_nav2(double cell, int radius_cells, double inscribed_radius, double cost_scaling_factor, unsigned char *table, size_t cap);
 int kicp_grid_last_window(const kicp_grid *grid, unsigned int *x0, unsigned int *y0, unsigned int *w, unsigned int *h);
+
+/* ---- from the costmap to a path: the cost-to-go field a planner spreads from its goal, and the path down it (kicp_grid.hip) -------------
+ * What Nav2's NavFn calls the potential.  Everything below is exact and integer; the field is the unique least fixed point of its
+ * recurrence, so the host and the device entries return equal arrays.
+ *
+ * INPUTS.  A costmap of width x height bytes, cell (x, y) at y * width + x, as kicp_grid_costmap writes it (any byte array will do).
+ * A weight table weight[256] of bytes: q(c) = weight[costmap[c]]; q = 0 means the cell is IMPASSABLE, otherwise 1 <= q <= 255.  A goal
+ * list of n_goals >= 1 cells as (x, y) pairs, goals_xy[2 g] = x, goals_xy[2 g + 1] = y: a goal outside the grid is KICP_ERR_ARG, a
+ * goal on an impassable cell is ignored (out_stats counts the others; a cell listed twice counts twice).  max_potential with
+ * 1 <= max_potential <= 0xFFFFFFFE.
+ *
+ * EDGES.  A passable cell is joined to each of its eight neighbours that is passable.  There is NO corner rule: a diagonal step
+ * between two passable cells is allowed whatever the two cells beside it are - the costmap's inflation is what keeps a path off
+ * corners, so plan on an inflated costmap.  With s = q(u) + q(v) an orthogonal step weighs s and a diagonal step (181 * s + 64) >> 7
+ * (181 / 128 = 1.4140625).  Edges are symmetric and weigh at least 2 (at most 721).
+ *
+ * POTENTIAL.  32 bits per cell.  A passable goal has potential 0; every other passable cell min(D, max_potential), where D is the least
+ * sum of edge weights over the paths from it to a passable goal; cells without such a path, and impassable cells, read 0xFFFFFFFF.
+ * The clamp is part of the definition, not an overflow escape: pot(c) = min over neighbours n of sat(pot(n) + edge(c, n)) with sat
+ * saturating at max_potential is monotone, so its least fixed point is exactly min(D, max_potential).  The clamp doubles as a planning
+ * horizon: beyond it the field is flat and yields no path.
+ *
+ * PATH.  From a potential array and a start cell: from the current cell take the FIRST neighbour n, in the order +x, -x, +y, -y,
+ * (+x, +y), (-x, +y), (+x, -y), (-x, -y), that is passable (q(n) > 0 and its potential below 0xFFFFFFFF) and has
+ * pot[cur] == pot[n] + edge(cur, n); stop at potential 0.  The costmap and the weights must be those the potential was made from:
+ * they give `edge`.  The output is the cell list as (x, y) pairs of unsigned int, start and goal included; *out_n is its length.  A
+ * start outside the grid, or one whose potential is 0xFFFFFFFF ("unreachable"), is KICP_ERR_ARG.  A walk that reaches a cell above 0
+ * where no neighbour satisfies the equality - a start at or inside the zone max_potential clamped - is KICP_ERR_CAPACITY, max_potential
+ * named in the message, *out_n = 0.  cap_cells too small is KICP_ERR_CAPACITY as well, with the needed length in *out_n (> cap_cells)
+ * and the first cap_cells cells stored; out_xy may be NULL only with cap_cells == 0.  Every step lowers the potential by at least 2,
+ * so the walk ends.
+ *
+ * WEIGHTS.  kicp_plan_weights fills the table NavFn's rule gives (pure host code): for b < lethal_from
+ *   weight[b] = min(255, neutral + b * factor_num / factor_den)     (integers; the product in 64 bits)
+ * for lethal_from <= b <= 254 it is 0, and weight[255] = unknown_weight - 0 keeps the planner out of unknown space.  Checked
+ * (KICP_ERR_ARG): out not null, 1 <= neutral <= 255, factor_den >= 1, lethal_from <= 255, unknown_weight <= 255.  NavFn's own numbers
+ * are neutral 50, factor 4 / 5 and lethal_from 253.
+ *
+ * ENTRIES.  kicp_potential_from_costmap (Dijkstra with 64-bit sums, clamped at the end) and kicp_potential_path are pure host code and
+ * need no GPU.  kicp_grid_potential_of_costmap takes a costmap of the grid's width x height from host memory to the GPU;
+ * kicp_grid_potential computes the full grid's costmap as kicp_grid_costmap does (same arguments, same bytes) and spreads the field
+ * over it where it is: the costmap never leaves HBM.  Both return after their kernels have completed and the width * height values
+ * have arrived.  cap must be width * height.  out_stats (nullable): goals used, cells with a potential below max_potential, cells equal
+ * to max_potential, relaxation rounds - the last is 0 for the host entry and implementation-defined on the device (it depends on how
+ * the work is tiled and batched; do not compare it).  Errors: a null pointer, width or height 0, cap != width * height, n_goals == 0
+ * or max_potential out of range are KICP_ERR_ARG; width * height or n_goals above 2^28 is KICP_ERR_CAPACITY; kicp_grid_potential also
+ * has the argument errors of kicp_grid_costmap.  The device entries bound their rounds by the number of cells plus one, which a
+ * correct build cannot reach: KICP_ERR_INTERNAL. */
+typedef struct kicp_plan_config {
+    unsigned int max_potential; /* 1 .. 0xFFFFFFFE: potentials are clamped here */
+} kicp_plan_config;
+int kicp_plan_weights(unsigned int neutral, unsigned int factor_num, unsigned int factor_den, unsigned int lethal_from, unsigned int unknown_weight,
+                      unsigned char out[256]);
+int kicp_potential_from_costmap(const unsigned char *costmap, unsigned int width, unsigned int height, const unsigned char weight[256],
+                                const kicp_plan_config *config, const unsigned int *goals_xy, size_t n_goals, unsigned int *out, size_t cap,
+                                unsigned long long out_stats[4]);
+int kicp_potential_path(const unsigned int *potential, const unsigned char *costmap, unsigned int width, unsigned int height, const unsigned char weight[256],
+                        unsigned int start_x, unsigned int start_y, unsigned int *out_xy, size_t cap_cells, size_t *out_n);
+int kicp_grid_potential_of_costmap(const kicp_grid *grid, const unsigned char *costmap, const unsigned char weight[256], const kicp_plan_config *config,
+                                   const unsigned int *goals_xy, size_t n_goals, unsigned int *out, size_t cap, unsigned long long out_stats[4]);
+int kicp_grid_potential(const kicp_grid *grid, const kicp_grid_clearance_config *clearance, const unsigned char *table, size_t table_len, int inflate_unknown,
+                        const unsigned char weight[256], const kicp_plan_config *config, const unsigned int *goals_xy, size_t n_goals, unsigned int *out,
+                        size_t cap, unsigned long long out_stats[4]);
 
 /* ---- map points the new frame sees through: a cube-map depth test (kicp_view.hip) ----------------------------------------------------
  * The local map loses points by distance only (RemovePointsFarFromLocation); whatever stood in view for one frame - a person crossing,

@@ -27,7 +27,7 @@ COMM_ID_BYTES = 128
 KICP_OK = 0
 KICP_WARN_NO_CORRESPONDENCES = 1
 KICP_WARN_TABLE_ORDER = 2
-KICP_ERR_HIP, KICP_ERR_ARG, KICP_ERR_CAPACITY, KICP_ERR_COMM = -1, -2, -3, -4
+KICP_ERR_HIP, KICP_ERR_ARG, KICP_ERR_CAPACITY, KICP_ERR_COMM, KICP_ERR_INTERNAL = -1, -2, -3, -4, -5
 
 
 class KicpError(RuntimeError):
@@ -69,6 +69,11 @@ class GridClearanceConfig(C.Structure):
     """kicp_grid_clearance_config: the readout's min_observations, the threshold above which a cell is a source, whether unknown cells
     are sources too, and the radius R in cells (1 .. 254)"""
     _fields_ = [("min_observations", C.c_uint), ("occupied_thresh", C.c_double), ("unknown_is_obstacle", C.c_int), ("radius_cells", C.c_int)]
+
+
+class PlanConfig(C.Structure):
+    """kicp_plan_config: potentials are clamped at max_potential (1 .. 0xFFFFFFFE), which doubles as a planning horizon"""
+    _fields_ = [("max_potential", C.c_uint)]
 
 
 class ViewConfig(C.Structure):
@@ -183,6 +188,15 @@ _SIGNATURES = {
                                                    C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.POINTER(C.c_ubyte), C.c_size_t]),
     "kicp_grid_cost_table_nav2": (C.c_int, [C.c_double, C.c_int, C.c_double, C.c_double, C.POINTER(C.c_ubyte), C.c_size_t]),
     "kicp_grid_last_window": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_uint)]),
+    "kicp_plan_weights": (C.c_int, [C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.POINTER(C.c_ubyte)]),
+    "kicp_potential_from_costmap": (C.c_int, [C.POINTER(C.c_ubyte), C.c_uint, C.c_uint, C.POINTER(C.c_ubyte), C.POINTER(PlanConfig), C.POINTER(C.c_uint), C.c_size_t,
+                                              C.POINTER(C.c_uint), C.c_size_t, C.POINTER(C.c_ulonglong)]),
+    "kicp_potential_path": (C.c_int, [C.POINTER(C.c_uint), C.POINTER(C.c_ubyte), C.c_uint, C.c_uint, C.POINTER(C.c_ubyte), C.c_uint, C.c_uint, C.POINTER(C.c_uint),
+                                      C.c_size_t, C.POINTER(C.c_size_t)]),
+    "kicp_grid_potential_of_costmap": (C.c_int, [C.c_void_p, C.POINTER(C.c_ubyte), C.POINTER(C.c_ubyte), C.POINTER(PlanConfig), C.POINTER(C.c_uint), C.c_size_t,
+                                                 C.POINTER(C.c_uint), C.c_size_t, C.POINTER(C.c_ulonglong)]),
+    "kicp_grid_potential": (C.c_int, [C.c_void_p, C.POINTER(GridClearanceConfig), C.POINTER(C.c_ubyte), C.c_size_t, C.c_int, C.POINTER(C.c_ubyte), C.POINTER(PlanConfig),
+                                      C.POINTER(C.c_uint), C.c_size_t, C.POINTER(C.c_uint), C.c_size_t, C.POINTER(C.c_ulonglong)]),
     "kicp_planar_grid": (C.c_size_t, [_dp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _dp, C.c_size_t]),
     "kicp_map_save_pcd": (C.c_int, [C.c_void_p, C.c_char_p]),
     "kicp_map_load_pcd": (C.c_int, [C.c_char_p, C.c_double, C.c_double, C.c_uint, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
@@ -493,6 +507,92 @@ def nav2_cost_table(cell, radius_cells, inscribed_radius, cost_scaling_factor):
     return out
 
 
+MAX_POTENTIAL = 0xFFFFFFFE
+UNREACHED = 0xFFFFFFFF
+
+
+def plan_weights(neutral=50, factor_num=4, factor_den=5, lethal_from=253, unknown_weight=0):
+    """kicp_plan_weights: weight[256] for the potential, uint8: min(255, neutral + b * factor_num / factor_den) for a cost b < lethal_from,
+    0 (impassable) from lethal_from to 254, unknown_weight for 255 (0 keeps the planner out of unknown space).  The defaults are NavFn's."""
+    args = [int(v) for v in (neutral, factor_num, factor_den, lethal_from, unknown_weight)]
+    if min(args) < 0 or max(args) > 0xFFFFFFFF:
+        raise KicpError(KICP_ERR_ARG, "the arguments of plan_weights are unsigned 32-bit integers")
+    out = np.empty(256, dtype=np.uint8)
+    _check(lib().kicp_plan_weights(*args, out.ctypes.data_as(C.POINTER(C.c_ubyte))))
+    return out
+
+
+def _plan_args(costmap, weight, goals, max_potential):
+    """-> (costmap uint8 (H, W), weight uint8 [256], goals uint32 (n, 2), PlanConfig); what the library cannot be handed is refused here"""
+    cm, wt = np.ascontiguousarray(costmap, dtype=np.uint8), np.ascontiguousarray(weight, dtype=np.uint8)
+    if cm.ndim != 2 or cm.size == 0:
+        raise KicpError(KICP_ERR_ARG, "the costmap must be shaped (height, width), both at least 1")
+    if wt.shape != (256,):
+        raise KicpError(KICP_ERR_ARG, "the weight table must have 256 entries")
+    g = np.asarray(goals, dtype=np.int64).reshape(-1, 2)
+    if g.size and (g.min() < 0 or g.max() > 0xFFFFFFFF):
+        raise KicpError(KICP_ERR_ARG, "a goal (x, y) must not be negative")
+    if not 0 <= int(max_potential) <= 0xFFFFFFFF:
+        raise KicpError(KICP_ERR_ARG, "max_potential must lie in 1 .. 0xFFFFFFFE")
+    return cm, wt, np.ascontiguousarray(g, dtype=np.uint32), PlanConfig(int(max_potential))
+
+
+def _u8(a):
+    return a.ctypes.data_as(C.POINTER(C.c_ubyte))
+
+
+def _u32(a):
+    return a.ctypes.data_as(C.POINTER(C.c_uint))
+
+
+def _potential_out(out, shape):
+    """the array a potential is written into: `out` (uint32, C-contiguous, of `shape`) or a new one"""
+    if out is None:
+        return np.empty(shape, dtype=np.uint32)
+    if not isinstance(out, np.ndarray) or out.dtype != np.uint32 or out.shape != tuple(shape) or not out.flags.c_contiguous or not out.flags.writeable:
+        raise KicpError(KICP_ERR_ARG, "out must be a writeable C-contiguous uint32 array shaped (height, width)")
+    return out
+
+
+def _potential_result(out, stats, return_stats):
+    return (out, tuple(int(v) for v in stats)) if return_stats else out
+
+
+def potential_from_costmap(costmap, weight, goals, max_potential=MAX_POTENTIAL, return_stats=False, out=None):
+    """kicp_potential_from_costmap: the cost-to-go field over a costmap shaped (height, width) with q = weight[costmap] (0: impassable)
+    from `goals` = [(x, y), ...] -> uint32 (height, width): 0 on a passable goal, min(least sum of edge weights, max_potential) on every
+    cell a path reaches, 0xFFFFFFFF elsewhere.  return_stats: also (goals used, cells below max_potential, cells at it, 0).  out: a uint32
+    array of that shape to write into instead of a new one.  Pure host code: needs no GPU."""
+    cm, wt, g, cfg = _plan_args(costmap, weight, goals, max_potential)
+    out, stats = _potential_out(out, cm.shape), np.zeros(4, dtype=np.uint64)
+    _check(lib().kicp_potential_from_costmap(_u8(cm), cm.shape[1], cm.shape[0], _u8(wt), C.byref(cfg), _u32(g), len(g), _u32(out), out.size,
+                                             stats.ctypes.data_as(C.POINTER(C.c_ulonglong))))
+    return _potential_result(out, stats, return_stats)
+
+
+def potential_path(potential, costmap, weight, start):
+    """kicp_potential_path: the path from `start` = (x, y) down `potential` (made from this costmap and these weights) -> uint32 (n, 2):
+    the cells as (x, y), start and goal included.  Each step takes the first neighbour - +x, -x, +y, -y, then the diagonals - whose
+    potential plus the edge's weight is the current cell's.  KICP_ERR_ARG for an unreachable start, KICP_ERR_CAPACITY for one at or
+    inside the zone max_potential clamped.  Needs no GPU."""
+    cm, wt, _, _ = _plan_args(costmap, weight, np.zeros((0, 2)), 1)
+    pot = np.ascontiguousarray(potential, dtype=np.uint32)
+    if pot.shape != cm.shape:
+        raise KicpError(KICP_ERR_ARG, "the potential must have the costmap's shape")
+    x, y = (int(v) for v in start)
+    if min(x, y) < 0 or max(x, y) > 0xFFFFFFFF:
+        raise KicpError(KICP_ERR_ARG, "the start (x, y) must not be negative")
+    cap, n = cm.shape[0] + cm.shape[1], C.c_size_t()
+    while True:
+        out = np.empty((cap, 2), dtype=np.uint32)
+        rc = lib().kicp_potential_path(_u32(pot), _u8(cm), cm.shape[1], cm.shape[0], _u8(wt), x, y, _u32(out), cap, C.byref(n))
+        if rc == KICP_ERR_CAPACITY and n.value > cap:  # the path is longer: its length came back
+            cap = n.value
+            continue
+        _check(rc)
+        return out[:n.value].copy()
+
+
 class OccupancyGrid:
     """kicp_grid: a world-aligned 2-D grid of (hits, misses) counters a mapping run draws frame by frame - every used point's cell is
     hit, the cells its ray from the sensor crosses are missed, once per cell per frame (include/kicp.h states the exact semantics).
@@ -580,6 +680,31 @@ class OccupancyGrid:
         _check(lib().kicp_grid_costmap(self._h, C.byref(cfg), t.ctypes.data_as(C.POINTER(C.c_ubyte)), t.size, 1 if inflate_unknown else 0, x0, y0, w, h,
                                        out.ctypes.data_as(C.POINTER(C.c_ubyte)), out.size))
         return out
+
+    def potential_of_costmap(self, costmap, weight, goals, max_potential=MAX_POTENTIAL, return_stats=False, out=None):
+        """kicp_grid_potential_of_costmap: on the GPU, the cost-to-go field of potential_from_costmap over `costmap` (uint8, the grid's
+        (height, width)) -> uint32 (height, width).  return_stats: also (goals used, cells below max_potential, cells at it, relaxation
+        rounds - the last depends on the implementation); out: as potential_from_costmap's."""
+        cm, wt, g, cfg = _plan_args(costmap, weight, goals, max_potential)
+        if cm.shape != (self.height, self.width):
+            raise KicpError(KICP_ERR_ARG, "the costmap must have the grid's shape (height, width)")
+        out, stats = _potential_out(out, cm.shape), np.zeros(4, dtype=np.uint64)
+        _check(lib().kicp_grid_potential_of_costmap(self._h, _u8(cm), _u8(wt), C.byref(cfg), _u32(g), len(g), _u32(out), out.size,
+                                                    stats.ctypes.data_as(C.POINTER(C.c_ulonglong))))
+        return _potential_result(out, stats, return_stats)
+
+    def potential(self, table, weight, goals, max_potential=MAX_POTENTIAL, min_observations=1, occupied_thresh=0.65, unknown_is_obstacle=False, inflate_unknown=False,
+                  return_stats=False, out=None):
+        """kicp_grid_potential: on the GPU, the full grid's costmap (the arguments and bytes of costmap()) and the cost-to-go field over
+        it from `goals` = [(x, y), ...] - the costmap never leaves HBM -> uint32 (height, width); return_stats and out as
+        potential_of_costmap's"""
+        t = _cost_table(table)
+        cfg = _clearance_config(_table_radius(t), min_observations, occupied_thresh, unknown_is_obstacle)
+        _, wt, g, plan = _plan_args(np.zeros((1, 1), dtype=np.uint8), weight, goals, max_potential)
+        out, stats = _potential_out(out, (self.height, self.width)), np.zeros(4, dtype=np.uint64)
+        _check(lib().kicp_grid_potential(self._h, C.byref(cfg), _u8(t), t.size, 1 if inflate_unknown else 0, _u8(wt), C.byref(plan), _u32(g), len(g), _u32(out), out.size,
+                                         stats.ctypes.data_as(C.POINTER(C.c_ulonglong))))
+        return _potential_result(out, stats, return_stats)
 
     def last_window(self):
         """kicp_grid_last_window: (x0, y0, w, h) of the last integrated frame's window clipped to the grid; w = h = 0 when it lies

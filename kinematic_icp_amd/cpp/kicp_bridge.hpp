@@ -3,6 +3,7 @@
 #pragma once
 #include <Eigen/Core>
 #include <Eigen/Geometry>
+#include <array>
 #include <chrono>
 #include <cstdint>
 #include <cstdio>
@@ -115,6 +116,30 @@ struct GridRect {
         return g;
     }
 };
+// PlanConfig, plan_weights and potential_path go with KinematicICP::GridPotential / GridPotentialOfCostmap / PotentialPath (kicp.h
+// kicp_plan_weights .. kicp_grid_potential): the clamp of the cost-to-go field, NavFn's weight per cost, and the walk down a potential.
+using PlanConfig = kicp_plan_config;
+inline std::array<uint8_t, 256> plan_weights(unsigned int neutral = 50, unsigned int factor_num = 4, unsigned int factor_den = 5, unsigned int lethal_from = 253,
+                                             unsigned int unknown_weight = 0) {
+    std::array<uint8_t, 256> weight{};
+    check(kicp_plan_weights(neutral, factor_num, factor_den, lethal_from, unknown_weight, weight.data()), "kicp_bridge::plan_weights");
+    return weight;
+}
+inline std::vector<std::array<unsigned int, 2>> potential_path(const std::vector<uint32_t> &potential, const std::vector<uint8_t> &costmap, unsigned int width,
+                                                               unsigned int height, const std::array<uint8_t, 256> &weight, const std::array<unsigned int, 2> &start) {
+    if (potential.size() != static_cast<size_t>(width) * height || costmap.size() != potential.size())
+        throw std::runtime_error("kicp_bridge::potential_path: the potential and the costmap must have width * height cells");
+    std::vector<std::array<unsigned int, 2>> cells(static_cast<size_t>(width) + height);
+    size_t n = 0;
+    int rc = kicp_potential_path(potential.data(), costmap.data(), width, height, weight.data(), start[0], start[1], cells.front().data(), cells.size(), &n);
+    if (rc == KICP_ERR_CAPACITY && n > cells.size()) {  // the path is longer: its length came back
+        cells.resize(n);
+        rc = kicp_potential_path(potential.data(), costmap.data(), width, height, weight.data(), start[0], start[1], cells.front().data(), cells.size(), &n);
+    }
+    check(rc, "kicp_bridge::potential_path");
+    cells.resize(n);
+    return cells;
+}
 inline std::shared_ptr<kicp_grid> make_grid(const GridConfig &config, int device = -1) {
     kicp_grid *grid = nullptr;
     check(kicp_grid_create(&config, device < 0 ? default_device() : device, &grid), "kicp_bridge::make_grid");

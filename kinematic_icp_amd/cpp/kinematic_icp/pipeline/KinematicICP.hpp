@@ -332,6 +332,44 @@ public:
         kicp_bridge::check(kicp_grid_costmap(grid_.get(), &config, table.data(), table.size(), inflate_unknown ? 1 : 0, r.x0, r.y0, r.w, r.h, data.data(), data.size()),
                            "GridCostmap");
     }
+    // From the costmap to a path (kicp.h kicp_plan_weights .. kicp_grid_potential): the cost-to-go field a planner spreads from its goals
+    // - 0 on a passable goal, min(least sum of step weights, plan.max_potential) where a path reaches, 0xFFFFFFFF elsewhere - with
+    // q = weight[cost] per cell, 0 for impassable (kicp_plan_weights fills NavFn's table).  GridPotential computes the full grid's
+    // costmap as GridCostmap does and spreads the field over it on the GPU: the costmap never leaves HBM.  GridPotentialOfCostmap takes
+    // a costmap the node holds (width * height bytes, e.g. the master grid after other layers wrote into it).  goals: (x, y) cells.
+    // Returns goals used, cells below max_potential, cells at it, relaxation rounds.  PotentialPath walks down a potential from
+    // `start` to a goal (host code; throws for an unreachable start and for one in the zone max_potential clamped) -> the cells as
+    // (x, y), start and goal included; it needs the costmap the potential was made from, so a node that plans with GridPotential keeps
+    // its costmap current as above.
+    using GridCell = std::array<unsigned int, 2>;
+    std::array<unsigned long long, 4> GridPotential(std::vector<uint32_t> &data, const kicp_bridge::GridClearanceConfig &config, const std::vector<uint8_t> &table,
+                                                    bool inflate_unknown, const std::array<uint8_t, 256> &weight, const std::vector<GridCell> &goals,
+                                                    const kicp_bridge::PlanConfig &plan = kicp_bridge::PlanConfig{0xFFFFFFFEu}) const {
+        const kicp_bridge::GridRect r = GridRectOrAll(nullptr, "GridPotential");
+        data.resize(static_cast<size_t>(r.w) * r.h);
+        std::array<unsigned long long, 4> stats{};
+        kicp_bridge::check(kicp_grid_potential(grid_.get(), &config, table.data(), table.size(), inflate_unknown ? 1 : 0, weight.data(), &plan,
+                                               goals.empty() ? nullptr : goals.front().data(), goals.size(), data.data(), data.size(), stats.data()),
+                           "GridPotential");
+        return stats;
+    }
+    std::array<unsigned long long, 4> GridPotentialOfCostmap(std::vector<uint32_t> &data, const std::vector<uint8_t> &costmap, const std::array<uint8_t, 256> &weight,
+                                                             const std::vector<GridCell> &goals,
+                                                             const kicp_bridge::PlanConfig &plan = kicp_bridge::PlanConfig{0xFFFFFFFEu}) const {
+        const kicp_bridge::GridRect r = GridRectOrAll(nullptr, "GridPotentialOfCostmap");
+        if (costmap.size() != static_cast<size_t>(r.w) * r.h) throw std::runtime_error("KinematicICP::GridPotentialOfCostmap: the costmap must have the grid's width * height bytes");
+        data.resize(costmap.size());
+        std::array<unsigned long long, 4> stats{};
+        kicp_bridge::check(kicp_grid_potential_of_costmap(grid_.get(), costmap.data(), weight.data(), &plan, goals.empty() ? nullptr : goals.front().data(), goals.size(),
+                                                          data.data(), data.size(), stats.data()),
+                           "GridPotentialOfCostmap");
+        return stats;
+    }
+    std::vector<GridCell> PotentialPath(const std::vector<uint32_t> &potential, const std::vector<uint8_t> &costmap, const std::array<uint8_t, 256> &weight,
+                                        const GridCell &start) const {
+        const kicp_bridge::GridRect r = GridRectOrAll(nullptr, "PotentialPath");
+        return kicp_bridge::potential_path(potential, costmap, r.w, r.h, weight, start);
+    }
     // the window of the last integrated frame clipped to the grid; empty() when it lies outside, and before any frame
     kicp_bridge::GridRect GridLastWindow() const {
         kicp_bridge::GridRect r;

@@ -3,13 +3,16 @@
 // kicp_grid.hpp; the geometry they share with the host entries: kicp_grid_host.hpp.  A handle owns its stream, its staging buffer and
 // its device memory: the counters (cells x 2 x 16 bit) and the two frame-local planes over the window.  The clearance and the costmap
 // a planner reads off the counters (kicp_grid_clearance, kicp_grid_costmap; kernels: kicp_clear.hpp, arithmetic: kicp_clear_host.hpp)
-// are entries of the same handle.
+// are entries of the same handle, and so is the cost-to-go field a planner spreads over that costmap (kicp_grid_potential,
+// kicp_grid_potential_of_costmap; kernels: kicp_nav.hpp, arithmetic: kicp_nav_host.hpp; the pure-host kicp_plan_weights,
+// kicp_potential_from_costmap and kicp_potential_path live here too).
 #include <cerrno>
 #include <memory>
 
 #include "kicp_clear.hpp"
 #include "kicp_grid.hpp"
 #include "kicp_internal.hpp"
+#include "kicp_nav.hpp"
 
 using namespace kicp;
 using namespace kicp::host;
@@ -34,6 +37,11 @@ struct kicp_grid {
     DevBuf<uint8_t> d_coldist;          // kicp_grid_clearance / kicp_grid_costmap: the column distances, the caller's table and the result
     DevBuf<uint8_t> d_cost_table, d_cost;
     DevBuf<uint16_t> d_clearance;
+    DevBuf<uint32_t> d_pot, d_goals;    // kicp_grid_potential*: the potential, the goal list, q = weight[costmap], the weight table,
+    DevBuf<uint8_t> d_q, d_weight;      // the tiles' activity flags (two planes) and the counters: raised flags of each round of a
+    DevBuf<uint8_t> d_nav_flags;        // batch, then the cells below and at max_potential
+    DevBuf<uint32_t> d_nav_ctr;
+    PinnedBuf<uint32_t> h_nav;
     HostStage stage;
     ~kicp_grid() {
         if (stream) (void)hipStreamSynchronize(stream), (void)hipStreamDestroy(stream);
@@ -107,6 +115,7 @@ int check_cost_table(const ClearParams &p, size_t table_len) {
 }
 // The clearance (table == nullptr: 16 bits per cell into `out`) or the costmap (a byte per cell) of a rectangle; arguments checked.
 // Two launches, one copy, the stream drained.  The buffers grow while the stream is idle: every entry of the handle drains it.
+// out == nullptr: the costmap stays in d_cost for the launches the caller queues behind these; nothing is copied or waited for.
 int clear_on_device(kicp_grid *grid, const ClearParams &p, const ClearRect &r, const unsigned char *table, uint32_t inflate_unknown, void *out) {
     if (int rc = set_device(grid->device)) return rc;
     const size_t cells = static_cast<size_t>(r.w) * r.h;
@@ -134,11 +143,81 @@ int clear_on_device(kicp_grid *grid, const ClearParams &p, const ClearRect &r, c
         hipLaunchKernelGGL(k_clear_rows<false>, dim3(r.h * segments), dim3(kClearBlock), 0, st, grid->d_coldist.get(), cx0, cw, grid->d_counts.get(), grid->cfg.width, p, r,
                            segments, static_cast<const uint8_t *>(nullptr), 0u, static_cast<void *>(grid->d_clearance.get()));
     HIP_TRY(hipGetLastError());
+    if (!out) return KICP_OK;
     if (table)
         HIP_TRY(hipMemcpyAsync(out, grid->d_cost.get(), cells, hipMemcpyDeviceToHost, st));
     else
         HIP_TRY(hipMemcpyAsync(out, grid->d_clearance.get(), cells * sizeof(uint16_t), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
+    return KICP_OK;
+}
+// what the potential entries share: the configuration, the output's size and the goal list
+int check_plan_args(const kicp_plan_config *cfg, unsigned int width, unsigned int height, const unsigned int *goals, size_t n_goals, size_t cap) {
+    if (cfg->max_potential < 1u || cfg->max_potential > kNavMaxPotential) return fail(KICP_ERR_ARG, "max_potential must lie in 1 .. 0xFFFFFFFE");
+    if (cap != static_cast<size_t>(width) * height) return fail(KICP_ERR_ARG, "cap must be width * height = " + std::to_string(static_cast<size_t>(width) * height));
+    if (n_goals < 1u) return fail(KICP_ERR_ARG, "at least one goal is needed");
+    if (n_goals > kGridMaxCells) return fail(KICP_ERR_CAPACITY, "n_goals = " + std::to_string(n_goals) + " (limit 2^28 = " + std::to_string(kGridMaxCells) + ")");
+    for (size_t g = 0; g < n_goals; ++g)
+        if (goals[2 * g] >= width || goals[2 * g + 1] >= height)
+            return fail(KICP_ERR_ARG, "goal " + std::to_string(g) + " = (" + std::to_string(goals[2 * g]) + ", " + std::to_string(goals[2 * g + 1]) + ") lies outside the grid of " +
+                                          std::to_string(width) + " x " + std::to_string(height) + " cells");
+    return KICP_OK;
+}
+// The potential over the costmap at d_costmap (the grid's width x height bytes, written by work already queued on the stream);
+// arguments checked.  Two launches, rounds of k_nav_relax in batches of kNavBatch with a look at their counters after each batch, the
+// count, one copy of the result, the stream drained.
+int potential_on_device(kicp_grid *grid, const uint8_t *d_costmap, const unsigned char *weight, uint32_t max_potential, const unsigned int *goals, size_t n_goals,
+                        unsigned int *out, unsigned long long out_stats[4]) {
+    const uint32_t width = grid->cfg.width, height = grid->cfg.height, cells = static_cast<uint32_t>(grid->cells);
+    const uint32_t tiles_x = (width + kNavTile - 1u) / kNavTile, tiles_y = (height + kNavTile - 1u) / kNavTile, tiles = tiles_x * tiles_y;
+    hipStream_t st = grid->stream;
+    if (int rc = grid->d_pot.reserve(cells)) return rc;
+    if (int rc = grid->d_q.reserve(cells)) return rc;
+    if (int rc = grid->d_nav_flags.reserve(2 * static_cast<size_t>(tiles))) return rc;
+    if (int rc = grid->d_weight.reserve(256)) return rc;
+    if (int rc = grid->d_goals.reserve(2 * n_goals)) return rc;
+    if (int rc = grid->d_nav_ctr.reserve(kNavBatch + 2u)) return rc;
+    if (int rc = grid->h_nav.reserve(kNavBatch + 2u, hipHostMallocDefault, false)) return rc;
+    uint8_t *flags = grid->d_nav_flags.get();
+    uint32_t *ctr = grid->d_nav_ctr.get(), *h = grid->h_nav.get();
+    HIP_TRY(hipMemcpyAsync(grid->d_weight.get(), weight, 256, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(grid->d_goals.get(), goals, 2 * n_goals * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(flags, 0, 2 * static_cast<size_t>(tiles), st));
+    HIP_TRY(hipMemsetAsync(ctr, 0, (kNavBatch + 2u) * sizeof(uint32_t), st));
+    hipLaunchKernelGGL(k_nav_init, dim3((cells + kNavBlock - 1u) / kNavBlock), dim3(kNavBlock), 0, st, d_costmap, grid->d_weight.get(), cells, grid->d_q.get(),
+                       grid->d_pot.get());
+    hipLaunchKernelGGL(k_nav_goals, dim3(static_cast<uint32_t>((n_goals + kNavBlock - 1u) / kNavBlock)), dim3(kNavBlock), 0, st, grid->d_goals.get(),
+                       static_cast<uint32_t>(n_goals), width, tiles_x, grid->d_q.get(), grid->d_pot.get(), flags);
+    // A round holds a full sweep of every active tile, so the rounds end within the number of cells; never loop without that limit.
+    const unsigned long long limit = static_cast<unsigned long long>(cells) + 1ull;
+    unsigned long long rounds = 0;
+    for (bool done = false; !done;) {
+        if (rounds >= limit) return fail(KICP_ERR_INTERNAL, "the potential did not settle within " + std::to_string(limit) + " rounds");
+        const uint32_t batch = static_cast<uint32_t>(std::min<unsigned long long>(kNavBatch, limit - rounds));
+        for (uint32_t i = 0; i < batch; ++i) {
+            const uint32_t parity = static_cast<uint32_t>((rounds + i) & 1ull);
+            hipLaunchKernelGGL(k_nav_relax, dim3(tiles), dim3(kNavBlock), 0, st, grid->d_pot.get(), grid->d_q.get(), width, height, tiles_x, tiles_y, max_potential,
+                               flags + static_cast<size_t>(parity) * tiles, flags + static_cast<size_t>(parity ^ 1u) * tiles, ctr + i);
+        }
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(h, ctr, kNavBatch * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipMemsetAsync(ctr, 0, kNavBatch * sizeof(uint32_t), st));
+        HIP_TRY(hipStreamSynchronize(st));
+        uint32_t i = 0;
+        while (i < batch && h[i] != 0u) ++i;  // the first round that raised no flag: every later one found no tile active
+        done = i < batch;
+        rounds += done ? i + 1u : batch;
+    }
+    hipLaunchKernelGGL(k_nav_count, dim3(std::min((cells + kNavBlock - 1u) / kNavBlock, 1024u)), dim3(kNavBlock), 0, st, grid->d_pot.get(), cells, max_potential,
+                       ctr + kNavBatch);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, grid->d_pot.get(), static_cast<size_t>(cells) * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(h + kNavBatch, ctr + kNavBatch, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (out_stats) {
+        out_stats[0] = 0ull, out_stats[1] = h[kNavBatch], out_stats[2] = h[kNavBatch + 1u], out_stats[3] = rounds;
+        for (size_t g = 0; g < n_goals; ++g) out_stats[0] += out[static_cast<size_t>(goals[2 * g + 1]) * width + goals[2 * g]] == 0u ? 1ull : 0ull;  // 0 only on a passable goal
+    }
     return KICP_OK;
 }
 }  // namespace
@@ -315,6 +394,65 @@ int kicp_grid_cost_table_nav2(double cell, int radius_cells, double inscribed_ra
     if (int rc = check_cost_table(p, cap)) return rc;
     clear_host::cost_table_nav2(cell, p.radius, inscribed_radius, cost_scaling_factor, table);
     return KICP_OK;
+}
+int kicp_plan_weights(unsigned int neutral, unsigned int factor_num, unsigned int factor_den, unsigned int lethal_from, unsigned int unknown_weight,
+                      unsigned char out[256]) {
+    if (!out) return fail(KICP_ERR_ARG, "null argument");
+    if (neutral < 1u || neutral > 255u) return fail(KICP_ERR_ARG, "neutral must lie in 1 .. 255");
+    if (factor_den < 1u) return fail(KICP_ERR_ARG, "factor_den must be at least 1");
+    if (lethal_from > 255u) return fail(KICP_ERR_ARG, "lethal_from must lie in 0 .. 255");
+    if (unknown_weight > 255u) return fail(KICP_ERR_ARG, "unknown_weight must lie in 0 .. 255");
+    nav_host::weights(neutral, factor_num, factor_den, lethal_from, unknown_weight, out);
+    return KICP_OK;
+}
+int kicp_potential_from_costmap(const unsigned char *costmap, unsigned int width, unsigned int height, const unsigned char weight[256], const kicp_plan_config *cfg,
+                                const unsigned int *goals_xy, size_t n_goals, unsigned int *out, size_t cap, unsigned long long out_stats[4]) {
+    if (!costmap || !weight || !cfg || !goals_xy || !out) return fail(KICP_ERR_ARG, "null argument");
+    if (width == 0 || height == 0) return fail(KICP_ERR_ARG, "width and height must be at least 1");
+    if (static_cast<unsigned long long>(width) * height > kGridMaxCells) return fail(KICP_ERR_CAPACITY, "width * height exceeds 2^28 = " + std::to_string(kGridMaxCells));
+    if (int rc = check_plan_args(cfg, width, height, goals_xy, n_goals, cap)) return rc;
+    unsigned long long stats[4];
+    nav_host::potential(costmap, width, height, weight, cfg->max_potential, goals_xy, n_goals, out, stats);
+    if (out_stats)
+        for (int k = 0; k < 4; ++k) out_stats[k] = stats[k];
+    return KICP_OK;
+}
+int kicp_potential_path(const unsigned int *potential, const unsigned char *costmap, unsigned int width, unsigned int height, const unsigned char weight[256],
+                        unsigned int start_x, unsigned int start_y, unsigned int *out_xy, size_t cap_cells, size_t *out_n) {
+    if (!potential || !costmap || !weight || !out_n || (!out_xy && cap_cells)) return fail(KICP_ERR_ARG, "null argument");
+    *out_n = 0;
+    if (width == 0 || height == 0) return fail(KICP_ERR_ARG, "width and height must be at least 1");
+    if (start_x >= width || start_y >= height) return fail(KICP_ERR_ARG, "the start lies outside the grid of " + std::to_string(width) + " x " + std::to_string(height) + " cells");
+    const int rc = nav_host::path(potential, costmap, width, height, weight, start_x, start_y, out_xy, cap_cells, out_n);
+    if (rc == 1) return fail(KICP_ERR_ARG, "the start is unreachable: its potential is 0xFFFFFFFF");
+    if (rc == 2) return fail(KICP_ERR_CAPACITY, "the path enters the zone that max_potential clamped: no neighbour continues it; raise max_potential");
+    if (*out_n > cap_cells) return fail(KICP_ERR_CAPACITY, "the path has " + std::to_string(*out_n) + " cells, cap_cells is " + std::to_string(cap_cells));
+    return KICP_OK;
+}
+int kicp_grid_potential_of_costmap(const kicp_grid *cgrid, const unsigned char *costmap, const unsigned char weight[256], const kicp_plan_config *cfg,
+                                   const unsigned int *goals_xy, size_t n_goals, unsigned int *out, size_t cap, unsigned long long out_stats[4]) {
+    KICP_TRACE_CALL();
+    if (!cgrid || !costmap || !weight || !cfg || !goals_xy || !out) return fail(KICP_ERR_ARG, "null argument");
+    if (int rc = check_plan_args(cfg, cgrid->cfg.width, cgrid->cfg.height, goals_xy, n_goals, cap)) return rc;
+    kicp_grid *grid = const_cast<kicp_grid *>(cgrid);  // logically const: the buffers are scratch
+    if (int rc = set_device(grid->device)) return rc;
+    if (int rc = grid->d_cost.reserve(grid->cells)) return rc;
+    HIP_TRY(hipMemcpyAsync(grid->d_cost.get(), costmap, grid->cells, hipMemcpyHostToDevice, grid->stream));
+    return potential_on_device(grid, grid->d_cost.get(), weight, cfg->max_potential, goals_xy, n_goals, out, out_stats);
+}
+int kicp_grid_potential(const kicp_grid *cgrid, const kicp_grid_clearance_config *clearance, const unsigned char *table, size_t table_len, int inflate_unknown,
+                        const unsigned char weight[256], const kicp_plan_config *cfg, const unsigned int *goals_xy, size_t n_goals, unsigned int *out, size_t cap,
+                        unsigned long long out_stats[4]) {
+    KICP_TRACE_CALL();
+    if (!cgrid || !clearance || !table || !weight || !cfg || !goals_xy || !out) return fail(KICP_ERR_ARG, "null argument");
+    ClearParams p;
+    const ClearRect r{0u, 0u, cgrid->cfg.width, cgrid->cfg.height};
+    if (int rc = check_clear_config(clearance, p)) return rc;
+    if (int rc = check_cost_table(p, table_len)) return rc;
+    if (int rc = check_plan_args(cfg, r.w, r.h, goals_xy, n_goals, cap)) return rc;
+    kicp_grid *grid = const_cast<kicp_grid *>(cgrid);
+    if (int rc = clear_on_device(grid, p, r, table, inflate_unknown ? 1u : 0u, nullptr)) return rc;  // the costmap stays in d_cost
+    return potential_on_device(grid, grid->d_cost.get(), weight, cfg->max_potential, goals_xy, n_goals, out, out_stats);
 }
 int kicp_grid_last_window(const kicp_grid *grid, unsigned int *x0, unsigned int *y0, unsigned int *w, unsigned int *h) {
     if (!grid || !x0 || !y0 || !w || !h) return fail(KICP_ERR_ARG, "null argument");
