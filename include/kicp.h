@@ -661,6 +661,79 @@ int kicp_grid_potential(const kicp_grid *grid, const kicp_grid_clearance_config 
                         const unsigned char weight[256], const kicp_plan_config *config, const unsigned int *goals_xy, size_t n_goals, unsigned int *out,
                         size_t cap, unsigned long long out_stats[4]);
 
+/* ---- from the field to a command: a fan of arc trajectories scored on the costmap and the potential (kicp_grid.hip) ------------------
+ * What a local planner (DWA / DWB, MPPI) does each control cycle: roll candidate commands forward as arcs, lay the robot's footprint on
+ * the costmap at every pose, drop the arcs that collide, rank the rest by how far down the cost-to-go field they end.  Everything below
+ * is exact: the only floating-point operations are fp64 + - * / and floor, every operation rounded on its own (the library is built
+ * with -ffp-contract=off), and no transcendental is evaluated inside a scoring entry.  The host and the device entry return equal arrays.
+ *
+ * PLAN.  A successful kicp_grid_potential or kicp_grid_potential_of_costmap leaves a plan in the handle: q = weight[costmap] per cell
+ * (1 .. 255, 0 impassable) and the potential, for the grid's width x height, where they lie in HBM.  The plan stays valid until the next
+ * call of either entry; a call of theirs that fails - on its arguments too - invalidates it.  Integrating frames does not: the plan is
+ * a snapshot.  kicp_grid_clearance and kicp_grid_costmap do not write the plan's buffers and do not invalidate it.  Scoring on a handle
+ * without a valid plan is KICP_ERR_ARG.
+ *
+ * START.  start[4] = x, y, c, s: the base frame's origin in world metres and its heading as a unit vector (cosine, sine; the caller
+ * evaluates them).  All four must be finite (KICP_ERR_ARG).
+ *
+ * ARCS.  arcs holds n_arcs x 4 doubles (dx, dy, dc, ds): ONE step of the arc, expressed in the robot's frame - the reference's motion
+ * model, a displacement and a yaw.  The rollout of arc k starts with pose_0 = start; for t = 1 .. n_steps
+ *   x_t = x_{t-1} + (c_{t-1} * dx - s_{t-1} * dy)        c_t = c_{t-1} * dc - s_{t-1} * ds
+ *   y_t = y_{t-1} + (s_{t-1} * dx + c_{t-1} * dy)        s_t = s_{t-1} * dc + c_{t-1} * ds
+ *
+ * FOOTPRINT.  n_samples points (fx, fy) in the base frame, footprint_xy[2 p] = fx, footprint_xy[2 p + 1] = fy.  Sample p at pose t lies at
+ *   wx = x_t + (c_t * fx - s_t * fy),   wy = y_t + (s_t * fx + c_t * fy)
+ * in the cell cx = floor((wx - origin_x) / cell), cy = floor((wy - origin_y) / cell) - the grid's own arithmetic.  Its weight is
+ * q(cx, cy) when 0 <= cx < width and 0 <= cy < height, and 0 when the cell is outside the grid or wx or wy is not finite.  Values that
+ * are not finite inside arcs or footprint_xy are legal input: they collide.  Pose t COLLIDES when a sample's weight is 0; otherwise
+ * its cost m_t is the largest of the samples' weights.  The start pose is not checked: the robot is where it is.
+ *
+ * RESULT.  Four unsigned int per arc, out[4 k .. 4 k + 3]:
+ *   free_steps     the largest f <= n_steps such that the poses 1 .. f do not collide
+ *   cost_sum       the sum of m_t over t = 1 .. f
+ *   cost_max       the largest of those m_t, 0 when f = 0
+ *   end_potential  the plan's potential at the cell of (x_f, y_f) - the base origin at the last free pose, the start when f = 0 -
+ *                  and 0xFFFFFFFF when that cell is outside the grid (an impassable or unreached cell reads 0xFFFFFFFF as well)
+ *
+ * LIMITS.  1 <= n_arcs <= 2^20, 1 <= n_steps <= 1024, 1 <= n_samples <= 4096: above is KICP_ERR_CAPACITY with the limit in the message,
+ * 0 or a null pointer KICP_ERR_ARG.  cap must be 4 * n_arcs (KICP_ERR_ARG).
+ *
+ * ENTRIES.  kicp_grid_score_arcs scores on the handle's plan where it lies in HBM - one launch, a wave per arc - and returns after the
+ * n_arcs x 4 words have arrived.  kicp_score_arcs_from_plan is the same arithmetic as pure host code over the caller's arrays (q and
+ * potential of width x height, cell (x, y) at y * width + x, with the grid's cell, origin_x, origin_y) and needs no GPU; cell not
+ * positive or not finite, an origin that is not finite, width or height 0 are KICP_ERR_ARG, width * height above 2^28
+ * KICP_ERR_CAPACITY.  kicp_plan_q makes its q from a costmap: out[c] = weight[costmap[c]] for `cells` cells (pure host code).
+ *
+ * kicp_arc_steps fills n_arcs x 4 doubles from commands (v, omega) held for dt with the reference's arc (pure host code; sin and cos are
+ * the C library's sin() and cos(), each called on its own - not its sincos(), which differs from them in the last bit now and then): d = v[k] * dt, theta = omega[k] * dt,
+ *   (dx, dy) = (d, 0)                                                       when |theta| < 1e-9
+ *   dx = (d * sin(theta)) / theta,   dy = (d * (1 - cos(theta))) / theta    otherwise
+ *   dc = cos(theta),   ds = sin(theta).
+ * The branch stands where the reference adds an epsilon to theta, which divides by zero at theta = -epsilon.  n_arcs as above.
+ *
+ * kicp_footprint_box makes a lattice over a box that includes its boundary (pure host code): nx = ceil((x_max - x_min) / spacing) + 1
+ * points x_i = x_min + ((x_max - x_min) * i) / (nx - 1) - x_min alone when nx = 1 - and y likewise; sample j * nx + i is (x_i, y_j).
+ * *out_n is nx * ny; cap counts samples (out_xy has room for 2 * cap doubles).  A cap that is too small is KICP_ERR_CAPACITY with the needed count in *out_n (> cap) and the first cap samples
+ * stored; out_xy may be NULL only with cap == 0.  A box that is not finite, x_min > x_max, y_min > y_max, spacing not positive or not
+ * finite: KICP_ERR_ARG; nx * ny above 4096, a footprint's limit: KICP_ERR_CAPACITY with *out_n = 0.
+ *
+ * kicp_arcs_best ranks results as the scoring entries write them (pure host code - ranking n_arcs rows is microseconds, so there is no
+ * device argmin).  Arc k is ADMISSIBLE when free_steps >= min_free_steps and end_potential != 0xFFFFFFFF.  Its score is
+ *   w_potential * end_potential + w_cost * cost_sum + w_blocked * (n_steps - free_steps)
+ * each product and the sum in unsigned 64 bits (the sum wraps; n_steps - free_steps counts as 0 when free_steps > n_steps).
+ * *out_index is the admissible arc of least score, the lowest index on a tie, and n_arcs when none is admissible.  n_arcs as above. */
+int kicp_plan_q(const unsigned char *costmap, size_t cells, const unsigned char weight[256], unsigned char *out);
+int kicp_arc_steps(const double *v, const double *omega, double dt, size_t n_arcs, double *out /* n_arcs x 4 */);
+int kicp_footprint_box(double x_min, double x_max, double y_min, double y_max, double spacing, double *out_xy, size_t cap, size_t *out_n);
+int kicp_arcs_best(const unsigned int *results /* n_arcs x 4 */, size_t n_arcs, unsigned int w_potential, unsigned int w_cost, unsigned int w_blocked,
+                   unsigned int n_steps, unsigned int min_free_steps, size_t *out_index);
+int kicp_score_arcs_from_plan(const unsigned char *q, const unsigned int *potential, double cell, double origin_x, double origin_y, unsigned int width,
+                              unsigned int height, const double start[4], const double *arcs, size_t n_arcs, unsigned int n_steps, const double *footprint_xy,
+                              size_t n_samples, unsigned int *out, size_t cap);
+int kicp_grid_has_plan(const kicp_grid *grid); /* 1 when the handle holds a valid plan, else 0 (a null handle too) */
+int kicp_grid_score_arcs(const kicp_grid *grid, const double start[4], const double *arcs, size_t n_arcs, unsigned int n_steps, const double *footprint_xy,
+                         size_t n_samples, unsigned int *out, size_t cap);
+
 /* ---- map points the new frame sees through: a cube-map depth test (kicp_view.hip) ----------------------------------------------------
  * The local map loses points by distance only (RemovePointsFarFromLocation); whatever stood in view for one frame - a person crossing,
  * a forklift, a door leaf - stays until the robot is max_range away.  A kicp_view holds a depth image of ONE frame, and

@@ -197,6 +197,14 @@ _SIGNATURES = {
                                                  C.POINTER(C.c_uint), C.c_size_t, C.POINTER(C.c_ulonglong)]),
     "kicp_grid_potential": (C.c_int, [C.c_void_p, C.POINTER(GridClearanceConfig), C.POINTER(C.c_ubyte), C.c_size_t, C.c_int, C.POINTER(C.c_ubyte), C.POINTER(PlanConfig),
                                       C.POINTER(C.c_uint), C.c_size_t, C.POINTER(C.c_uint), C.c_size_t, C.POINTER(C.c_ulonglong)]),
+    "kicp_plan_q": (C.c_int, [C.POINTER(C.c_ubyte), C.c_size_t, C.POINTER(C.c_ubyte), C.POINTER(C.c_ubyte)]),
+    "kicp_arc_steps": (C.c_int, [_dp, _dp, C.c_double, C.c_size_t, _dp]),
+    "kicp_footprint_box": (C.c_int, [C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _dp, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "kicp_arcs_best": (C.c_int, [C.POINTER(C.c_uint), C.c_size_t, C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.POINTER(C.c_size_t)]),
+    "kicp_score_arcs_from_plan": (C.c_int, [C.POINTER(C.c_ubyte), C.POINTER(C.c_uint), C.c_double, C.c_double, C.c_double, C.c_uint, C.c_uint, _dp, _dp, C.c_size_t, C.c_uint,
+                                            _dp, C.c_size_t, C.POINTER(C.c_uint), C.c_size_t]),
+    "kicp_grid_has_plan": (C.c_int, [C.c_void_p]),
+    "kicp_grid_score_arcs": (C.c_int, [C.c_void_p, _dp, _dp, C.c_size_t, C.c_uint, _dp, C.c_size_t, C.POINTER(C.c_uint), C.c_size_t]),
     "kicp_planar_grid": (C.c_size_t, [_dp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _dp, C.c_size_t]),
     "kicp_map_save_pcd": (C.c_int, [C.c_void_p, C.c_char_p]),
     "kicp_map_load_pcd": (C.c_int, [C.c_char_p, C.c_double, C.c_double, C.c_uint, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
@@ -547,11 +555,7 @@ def _u32(a):
 
 def _potential_out(out, shape):
     """the array a potential is written into: `out` (uint32, C-contiguous, of `shape`) or a new one"""
-    if out is None:
-        return np.empty(shape, dtype=np.uint32)
-    if not isinstance(out, np.ndarray) or out.dtype != np.uint32 or out.shape != tuple(shape) or not out.flags.c_contiguous or not out.flags.writeable:
-        raise KicpError(KICP_ERR_ARG, "out must be a writeable C-contiguous uint32 array shaped (height, width)")
-    return out
+    return _out_array(out, shape, np.uint32, "(height, width)")
 
 
 def _potential_result(out, stats, return_stats):
@@ -591,6 +595,104 @@ def potential_path(potential, costmap, weight, start):
             continue
         _check(rc)
         return out[:n.value].copy()
+
+
+ARCS_MAX_K, ARCS_MAX_T, ARCS_MAX_P = 1 << 20, 1024, 4096
+
+
+def _out_array(out, shape, dtype, what):
+    """the array a result is written into: `out` (of `dtype`, C-contiguous, of `shape`) or a new one"""
+    if out is None:
+        return np.empty(shape, dtype=dtype)
+    if not isinstance(out, np.ndarray) or out.dtype != dtype or out.shape != tuple(shape) or not out.flags.c_contiguous or not out.flags.writeable:
+        raise KicpError(KICP_ERR_ARG, "out must be a writeable C-contiguous %s array shaped %s" % (np.dtype(dtype).name, what))
+    return out
+
+
+def plan_q(costmap, weight, out=None):
+    """kicp_plan_q: q = weight[costmap], uint8 of the costmap's shape (0: impassable) - half of the plan score_arcs_from_plan takes.
+    Pure host code."""
+    cm, wt = np.ascontiguousarray(costmap, dtype=np.uint8), np.ascontiguousarray(weight, dtype=np.uint8)
+    if wt.shape != (256,):
+        raise KicpError(KICP_ERR_ARG, "the weight table must have 256 entries")
+    out = _out_array(out, cm.shape, np.uint8, "like the costmap")
+    _check(lib().kicp_plan_q(_u8(cm), cm.size, _u8(wt), _u8(out)))
+    return out
+
+
+def arc_start(x, y, yaw):
+    """the start of score_arcs from a planar pose: (x, y, cos(yaw), sin(yaw))"""
+    return np.array([float(x), float(y), math.cos(yaw), math.sin(yaw)], dtype=np.float64)
+
+
+def arc_steps(v, omega, dt, out=None):
+    """kicp_arc_steps: one step (dx, dy, dc, ds) of the arc each command (v[k], omega[k]) drives in dt, the reference's motion model
+    -> float64 (K, 4).  Pure host code."""
+    va, vp = _d(np.asarray(v, dtype=np.float64).reshape(-1))
+    wa, wp = _d(np.asarray(omega, dtype=np.float64).reshape(-1))
+    if va.size != wa.size:
+        raise KicpError(KICP_ERR_ARG, "v and omega must have the same length")
+    out = _out_array(out, (va.size, 4), np.float64, "(K, 4)")
+    _check(lib().kicp_arc_steps(vp, wp, float(dt), va.size, C.cast(out.ctypes.data, _dp)))
+    return out
+
+
+def footprint_box(x_min, x_max, y_min, y_max, spacing, out=None):
+    """kicp_footprint_box: a lattice over the box [x_min, x_max] x [y_min, y_max] (base frame) that includes its boundary, at most
+    `spacing` apart -> float64 (nx * ny, 2), x running fastest.  out: a float64 array of exactly that shape.  Pure host code."""
+    box = [float(v) for v in (x_min, x_max, y_min, y_max, spacing)]
+    n = C.c_size_t()
+    rc = lib().kicp_footprint_box(*box, None, 0, C.byref(n))
+    if rc != KICP_ERR_CAPACITY or n.value == 0:  # the count came back with KICP_ERR_CAPACITY; anything else is the error itself
+        _check(rc)
+    out = _out_array(out, (n.value, 2), np.float64, "(nx * ny, 2) = (%d, 2)" % n.value)
+    _check(lib().kicp_footprint_box(*box, C.cast(out.ctypes.data, _dp), n.value, C.byref(n)))
+    return out
+
+
+def _arcs_args(start, arcs, n_steps, footprint):
+    """-> (start [4], arcs (K, 4), footprint (P, 2), all float64, and n_steps); what the library cannot be handed is refused here"""
+    s = np.ascontiguousarray(start, dtype=np.float64).reshape(-1)
+    a, f = np.ascontiguousarray(arcs, dtype=np.float64), np.ascontiguousarray(footprint, dtype=np.float64)
+    if s.size != 4:
+        raise KicpError(KICP_ERR_ARG, "the start must be (x, y, cosine, sine)")
+    if a.ndim != 2 or a.shape[1] != 4:
+        raise KicpError(KICP_ERR_ARG, "the arcs must be shaped (K, 4): dx, dy, dc, ds")
+    if f.ndim != 2 or f.shape[1] != 2:
+        raise KicpError(KICP_ERR_ARG, "the footprint must be shaped (P, 2)")
+    if not 0 <= int(n_steps) <= 0xFFFFFFFF:
+        raise KicpError(KICP_ERR_ARG, "n_steps must lie in 1 .. %d" % ARCS_MAX_T)
+    return s, a, f, int(n_steps)
+
+
+def score_arcs_from_plan(q, potential, cell, origin_x, origin_y, start, arcs, n_steps, footprint, out=None):
+    """kicp_score_arcs_from_plan: every arc of `arcs` (K, 4) rolled n_steps poses forward from `start` = (x, y, cosine, sine) with the
+    footprint's samples (P, 2) laid on q (uint8 (height, width), 0 impassable: plan_q makes it) at every pose -> uint32 (K, 4):
+    free_steps, cost_sum, cost_max, end_potential (the potential at the last free pose; 0xFFFFFFFF outside the grid).  out: a uint32
+    (K, 4) array to write into.  Pure host code: needs no GPU."""
+    qa, pot = np.ascontiguousarray(q, dtype=np.uint8), np.ascontiguousarray(potential, dtype=np.uint32)
+    if qa.ndim != 2 or qa.size == 0 or pot.shape != qa.shape:
+        raise KicpError(KICP_ERR_ARG, "q and the potential must be shaped (height, width), both at least 1")
+    s, a, f, n_steps = _arcs_args(start, arcs, n_steps, footprint)
+    out = _out_array(out, (len(a), 4), np.uint32, "(K, 4)")
+    _check(lib().kicp_score_arcs_from_plan(_u8(qa), _u32(pot), float(cell), float(origin_x), float(origin_y), qa.shape[1], qa.shape[0], C.cast(s.ctypes.data, _dp),
+                                           C.cast(a.ctypes.data, _dp), len(a), n_steps, C.cast(f.ctypes.data, _dp), len(f), _u32(out), out.size))
+    return out
+
+
+def arcs_best(results, n_steps, w_potential=1, w_cost=0, w_blocked=0, min_free_steps=1):
+    """kicp_arcs_best: the index of the admissible arc (free_steps >= min_free_steps, end_potential != 0xFFFFFFFF) of least
+    w_potential * end_potential + w_cost * cost_sum + w_blocked * (n_steps - free_steps), the lowest on a tie; None when no arc is
+    admissible.  Pure host code."""
+    r = np.ascontiguousarray(results, dtype=np.uint32)
+    if r.ndim != 2 or r.shape[1] != 4:
+        raise KicpError(KICP_ERR_ARG, "the results must be shaped (K, 4)")
+    args = [int(v) for v in (w_potential, w_cost, w_blocked, n_steps, min_free_steps)]
+    if min(args) < 0 or max(args) > 0xFFFFFFFF:
+        raise KicpError(KICP_ERR_ARG, "the weights, n_steps and min_free_steps are unsigned 32-bit integers")
+    index = C.c_size_t()
+    _check(lib().kicp_arcs_best(_u32(r), len(r), *args, C.byref(index)))
+    return None if index.value == len(r) else int(index.value)
 
 
 class OccupancyGrid:
@@ -705,6 +807,20 @@ class OccupancyGrid:
         _check(lib().kicp_grid_potential(self._h, C.byref(cfg), _u8(t), t.size, 1 if inflate_unknown else 0, _u8(wt), C.byref(plan), _u32(g), len(g), _u32(out), out.size,
                                          stats.ctypes.data_as(C.POINTER(C.c_ulonglong))))
         return _potential_result(out, stats, return_stats)
+
+    def has_plan(self):
+        """kicp_grid_has_plan: does the handle hold the plan of a potential call that succeeded?"""
+        return bool(lib().kicp_grid_has_plan(self._h))
+
+    def score_arcs(self, start, arcs, n_steps, footprint, out=None):
+        """kicp_grid_score_arcs: on the GPU, score_arcs_from_plan's result on the plan the last potential() or potential_of_costmap()
+        left in the handle (KICP_ERR_ARG when there is none) -> uint32 (K, 4); the plan never leaves HBM.  out: as
+        score_arcs_from_plan's."""
+        s, a, f, n_steps = _arcs_args(start, arcs, n_steps, footprint)
+        out = _out_array(out, (len(a), 4), np.uint32, "(K, 4)")
+        _check(lib().kicp_grid_score_arcs(self._h, C.cast(s.ctypes.data, _dp), C.cast(a.ctypes.data, _dp), len(a), n_steps, C.cast(f.ctypes.data, _dp), len(f), _u32(out),
+                                          out.size))
+        return out
 
     def last_window(self):
         """kicp_grid_last_window: (x0, y0, w, h) of the last integrated frame's window clipped to the grid; w = h = 0 when it lies

@@ -5,6 +5,7 @@
 #include <Eigen/Geometry>
 #include <array>
 #include <chrono>
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -139,6 +140,42 @@ inline std::vector<std::array<unsigned int, 2>> potential_path(const std::vector
     check(rc, "kicp_bridge::potential_path");
     cells.resize(n);
     return cells;
+}
+// ArcStart, ArcStep, ArcResult, arc_start, arc_steps, footprint_box and best_arc go with KinematicICP::ScoreArcs (kicp.h kicp_plan_q ..
+// kicp_grid_score_arcs): where the rollout starts (x, y, cosine, sine), one step of an arc (dx, dy, dc, ds), what an arc scores
+// (free_steps, cost_sum, cost_max, end_potential), the arcs of a list of commands, a box footprint's samples and the ranking.
+using ArcStart = std::array<double, 4>;
+using ArcStep = std::array<double, 4>;
+using ArcResult = std::array<uint32_t, 4>;
+using FootprintSample = std::array<double, 2>;
+// the start of a pose: its translation's x and y, and the base frame's x axis projected into the world's plane as a unit vector
+inline ArcStart arc_start(const Sophus::SE3d &pose) {
+    const auto &q = pose.unit_quaternion();
+    const double c = 1.0 - 2.0 * (q.y() * q.y() + q.z() * q.z()), s = 2.0 * (q.x() * q.y() + q.z() * q.w()), n = std::sqrt(c * c + s * s);
+    if (!(n > 0.0)) throw std::runtime_error("kicp_bridge::arc_start: the pose's x axis has no heading in the plane");
+    return {pose.translation().x(), pose.translation().y(), c / n, s / n};
+}
+inline std::vector<ArcStep> arc_steps(const std::vector<double> &v, const std::vector<double> &omega, double dt) {
+    if (v.size() != omega.size()) throw std::runtime_error("kicp_bridge::arc_steps: v and omega must have the same length");
+    std::vector<ArcStep> arcs(v.size());
+    check(kicp_arc_steps(v.data(), omega.data(), dt, v.size(), arcs.empty() ? nullptr : arcs.front().data()), "kicp_bridge::arc_steps");
+    return arcs;
+}
+inline std::vector<FootprintSample> footprint_box(double x_min, double x_max, double y_min, double y_max, double spacing) {
+    size_t n = 0;
+    const int rc = kicp_footprint_box(x_min, x_max, y_min, y_max, spacing, nullptr, 0, &n);
+    if (rc != KICP_ERR_CAPACITY || n == 0) check(rc, "kicp_bridge::footprint_box");  // the count came back with KICP_ERR_CAPACITY
+    std::vector<FootprintSample> samples(n);
+    check(kicp_footprint_box(x_min, x_max, y_min, y_max, spacing, samples.front().data(), samples.size(), &n), "kicp_bridge::footprint_box");
+    return samples;
+}
+// the index of the best arc, results.size() when none is admissible
+inline size_t best_arc(const std::vector<ArcResult> &results, unsigned int n_steps, unsigned int w_potential = 1, unsigned int w_cost = 0, unsigned int w_blocked = 0,
+                       unsigned int min_free_steps = 1) {
+    size_t index = results.size();
+    check(kicp_arcs_best(results.empty() ? nullptr : results.front().data(), results.size(), w_potential, w_cost, w_blocked, n_steps, min_free_steps, &index),
+          "kicp_bridge::best_arc");
+    return index;
 }
 inline std::shared_ptr<kicp_grid> make_grid(const GridConfig &config, int device = -1) {
     kicp_grid *grid = nullptr;

@@ -370,6 +370,38 @@ public:
         const kicp_bridge::GridRect r = GridRectOrAll(nullptr, "PotentialPath");
         return kicp_bridge::potential_path(potential, costmap, r.w, r.h, weight, start);
     }
+    // From the field to a command (kicp.h kicp_plan_q .. kicp_grid_score_arcs): a fan of arcs - one step (dx, dy, dc, ds) each, in the
+    // robot's frame; ArcSteps makes them from commands (v, omega) held for dt with the odometry's own motion model - rolled n_steps
+    // poses forward from `start` with the footprint's samples (base frame; FootprintBox makes a box's) laid on the plan at every pose.
+    // The plan is what the last GridPotential or GridPotentialOfCostmap left on the GPU - q per cell and the potential - and is scored
+    // there: nothing but the arcs and the results crosses PCIe.  Per arc: free_steps (poses before the first collision), cost_sum
+    // and cost_max of the weights under the footprint along them, end_potential at the last free pose (0xFFFFFFFF outside the grid).
+    // Throws without a grid and without a plan ("call GridPotential first").  BestArc ranks the results on the host: the admissible
+    // arc (free_steps >= min_free_steps, end_potential != 0xFFFFFFFF) of least w_potential * end_potential + w_cost * cost_sum +
+    // w_blocked * (n_steps - free_steps), the lowest index on a tie, results.size() when there is none.
+    void ScoreArcs(std::vector<kicp_bridge::ArcResult> &results, const kicp_bridge::ArcStart &start, const std::vector<kicp_bridge::ArcStep> &arcs, unsigned int n_steps,
+                   const std::vector<kicp_bridge::FootprintSample> &footprint) const {
+        const kicp_grid *grid = RequireGrid("ScoreArcs");
+        if (!kicp_grid_has_plan(grid)) throw std::runtime_error("KinematicICP::ScoreArcs: call GridPotential first (or GridPotentialOfCostmap): the grid holds no plan");
+        results.resize(arcs.size());
+        kicp_bridge::check(kicp_grid_score_arcs(grid, start.data(), arcs.empty() ? nullptr : arcs.front().data(), arcs.size(), n_steps,
+                                                footprint.empty() ? nullptr : footprint.front().data(), footprint.size(), results.empty() ? nullptr : results.front().data(),
+                                                4 * results.size()),
+                           "ScoreArcs");
+    }
+    // the same from a pose - pose() for the robot as it stands: its x, y and the heading of its x axis in the plane
+    void ScoreArcs(std::vector<kicp_bridge::ArcResult> &results, const Sophus::SE3d &pose, const std::vector<kicp_bridge::ArcStep> &arcs, unsigned int n_steps,
+                   const std::vector<kicp_bridge::FootprintSample> &footprint) const {
+        ScoreArcs(results, kicp_bridge::arc_start(pose), arcs, n_steps, footprint);
+    }
+    std::vector<kicp_bridge::ArcStep> ArcSteps(const std::vector<double> &v, const std::vector<double> &omega, double dt) const { return kicp_bridge::arc_steps(v, omega, dt); }
+    std::vector<kicp_bridge::FootprintSample> FootprintBox(double x_min, double x_max, double y_min, double y_max, double spacing) const {
+        return kicp_bridge::footprint_box(x_min, x_max, y_min, y_max, spacing);
+    }
+    size_t BestArc(const std::vector<kicp_bridge::ArcResult> &results, unsigned int n_steps, unsigned int w_potential = 1, unsigned int w_cost = 0, unsigned int w_blocked = 0,
+                   unsigned int min_free_steps = 1) const {
+        return kicp_bridge::best_arc(results, n_steps, w_potential, w_cost, w_blocked, min_free_steps);
+    }
     // the window of the last integrated frame clipped to the grid; empty() when it lies outside, and before any frame
     kicp_bridge::GridRect GridLastWindow() const {
         kicp_bridge::GridRect r;

@@ -5,10 +5,14 @@
 // a planner reads off the counters (kicp_grid_clearance, kicp_grid_costmap; kernels: kicp_clear.hpp, arithmetic: kicp_clear_host.hpp)
 // are entries of the same handle, and so is the cost-to-go field a planner spreads over that costmap (kicp_grid_potential,
 // kicp_grid_potential_of_costmap; kernels: kicp_nav.hpp, arithmetic: kicp_nav_host.hpp; the pure-host kicp_plan_weights,
-// kicp_potential_from_costmap and kicp_potential_path live here too).
+// kicp_potential_from_costmap and kicp_potential_path live here too).  A successful potential call leaves a PLAN in the handle - q and
+// the potential, where they lie in HBM - on which kicp_grid_score_arcs scores a fan of arc trajectories (kernel: kicp_arcs.hpp,
+// arithmetic: kicp_arcs_host.hpp; its host twin kicp_score_arcs_from_plan and the helpers kicp_plan_q, kicp_arc_steps,
+// kicp_footprint_box and kicp_arcs_best are here as well).
 #include <cerrno>
 #include <memory>
 
+#include "kicp_arcs.hpp"
 #include "kicp_clear.hpp"
 #include "kicp_grid.hpp"
 #include "kicp_internal.hpp"
@@ -42,6 +46,10 @@ struct kicp_grid {
     DevBuf<uint8_t> d_nav_flags;        // batch, then the cells below and at max_potential
     DevBuf<uint32_t> d_nav_ctr;
     PinnedBuf<uint32_t> h_nav;
+    bool plan_valid = false;             // d_q and d_pot hold the plan of the last potential call, and it succeeded (kicp_grid_score_arcs)
+    DevBuf<double> d_arcs, d_footprint;  // kicp_grid_score_arcs: its uploads, its results and the pinned buffer they come back through
+    DevBuf<uint32_t> d_arc_out;
+    PinnedBuf<uint32_t> h_arc_out;
     HostStage stage;
     ~kicp_grid() {
         if (stream) (void)hipStreamSynchronize(stream), (void)hipStreamDestroy(stream);
@@ -171,6 +179,7 @@ int potential_on_device(kicp_grid *grid, const uint8_t *d_costmap, const unsigne
     const uint32_t width = grid->cfg.width, height = grid->cfg.height, cells = static_cast<uint32_t>(grid->cells);
     const uint32_t tiles_x = (width + kNavTile - 1u) / kNavTile, tiles_y = (height + kNavTile - 1u) / kNavTile, tiles = tiles_x * tiles_y;
     hipStream_t st = grid->stream;
+    grid->plan_valid = false;  // until this call has succeeded
     if (int rc = grid->d_pot.reserve(cells)) return rc;
     if (int rc = grid->d_q.reserve(cells)) return rc;
     if (int rc = grid->d_nav_flags.reserve(2 * static_cast<size_t>(tiles))) return rc;
@@ -218,6 +227,27 @@ int potential_on_device(kicp_grid *grid, const uint8_t *d_costmap, const unsigne
         out_stats[0] = 0ull, out_stats[1] = h[kNavBatch], out_stats[2] = h[kNavBatch + 1u], out_stats[3] = rounds;
         for (size_t g = 0; g < n_goals; ++g) out_stats[0] += out[static_cast<size_t>(goals[2 * g + 1]) * width + goals[2 * g]] == 0u ? 1ull : 0ull;  // 0 only on a passable goal
     }
+    grid->plan_valid = true;
+    return KICP_OK;
+}
+// what the entries that take a list of arcs share
+int check_arc_count(size_t n_arcs) {
+    if (n_arcs < 1u) return fail(KICP_ERR_ARG, "at least one arc is needed");
+    if (n_arcs > kArcsMaxK) return fail(KICP_ERR_CAPACITY, "n_arcs = " + std::to_string(n_arcs) + " (limit 2^20 = " + std::to_string(kArcsMaxK) + ")");
+    return KICP_OK;
+}
+// what the two scoring entries share
+int check_arcs_args(const double *start, const double *arcs, size_t n_arcs, unsigned int n_steps, const double *footprint_xy, size_t n_samples, const unsigned int *out,
+                    size_t cap) {
+    if (!start || !arcs || !footprint_xy || !out) return fail(KICP_ERR_ARG, "null argument");
+    if (int rc = check_arc_count(n_arcs)) return rc;
+    if (n_steps < 1u) return fail(KICP_ERR_ARG, "at least one step is needed");
+    if (n_steps > kArcsMaxT) return fail(KICP_ERR_CAPACITY, "n_steps = " + std::to_string(n_steps) + " (limit " + std::to_string(kArcsMaxT) + ")");
+    if (n_samples < 1u) return fail(KICP_ERR_ARG, "at least one footprint sample is needed");
+    if (n_samples > kArcsMaxP) return fail(KICP_ERR_CAPACITY, "n_samples = " + std::to_string(n_samples) + " (limit " + std::to_string(kArcsMaxP) + ")");
+    if (cap != 4 * n_arcs) return fail(KICP_ERR_ARG, "cap must be 4 * n_arcs = " + std::to_string(4 * n_arcs));
+    for (int i = 0; i < 4; ++i)
+        if (!std::isfinite(start[i])) return fail(KICP_ERR_ARG, "the start (x, y, cosine, sine) must be finite");
     return KICP_OK;
 }
 }  // namespace
@@ -432,6 +462,7 @@ int kicp_potential_path(const unsigned int *potential, const unsigned char *cost
 int kicp_grid_potential_of_costmap(const kicp_grid *cgrid, const unsigned char *costmap, const unsigned char weight[256], const kicp_plan_config *cfg,
                                    const unsigned int *goals_xy, size_t n_goals, unsigned int *out, size_t cap, unsigned long long out_stats[4]) {
     KICP_TRACE_CALL();
+    if (cgrid) const_cast<kicp_grid *>(cgrid)->plan_valid = false;  // a call that fails, on its arguments too, leaves no plan
     if (!cgrid || !costmap || !weight || !cfg || !goals_xy || !out) return fail(KICP_ERR_ARG, "null argument");
     if (int rc = check_plan_args(cfg, cgrid->cfg.width, cgrid->cfg.height, goals_xy, n_goals, cap)) return rc;
     kicp_grid *grid = const_cast<kicp_grid *>(cgrid);  // logically const: the buffers are scratch
@@ -444,6 +475,7 @@ int kicp_grid_potential(const kicp_grid *cgrid, const kicp_grid_clearance_config
                         const unsigned char weight[256], const kicp_plan_config *cfg, const unsigned int *goals_xy, size_t n_goals, unsigned int *out, size_t cap,
                         unsigned long long out_stats[4]) {
     KICP_TRACE_CALL();
+    if (cgrid) const_cast<kicp_grid *>(cgrid)->plan_valid = false;
     if (!cgrid || !clearance || !table || !weight || !cfg || !goals_xy || !out) return fail(KICP_ERR_ARG, "null argument");
     ClearParams p;
     const ClearRect r{0u, 0u, cgrid->cfg.width, cgrid->cfg.height};
@@ -453,6 +485,78 @@ int kicp_grid_potential(const kicp_grid *cgrid, const kicp_grid_clearance_config
     kicp_grid *grid = const_cast<kicp_grid *>(cgrid);
     if (int rc = clear_on_device(grid, p, r, table, inflate_unknown ? 1u : 0u, nullptr)) return rc;  // the costmap stays in d_cost
     return potential_on_device(grid, grid->d_cost.get(), weight, cfg->max_potential, goals_xy, n_goals, out, out_stats);
+}
+int kicp_plan_q(const unsigned char *costmap, size_t cells, const unsigned char weight[256], unsigned char *out) {
+    if (!weight || ((!costmap || !out) && cells)) return fail(KICP_ERR_ARG, "null argument");
+    for (size_t c = 0; c < cells; ++c) out[c] = weight[costmap[c]];
+    return KICP_OK;
+}
+int kicp_arc_steps(const double *v, const double *omega, double dt, size_t n_arcs, double *out) {
+    if (!v || !omega || !out) return fail(KICP_ERR_ARG, "null argument");
+    if (int rc = check_arc_count(n_arcs)) return rc;
+    arcs_host::steps(v, omega, dt, n_arcs, out);
+    return KICP_OK;
+}
+int kicp_footprint_box(double x_min, double x_max, double y_min, double y_max, double spacing, double *out_xy, size_t cap, size_t *out_n) {
+    if (!out_n || (!out_xy && cap)) return fail(KICP_ERR_ARG, "null argument");
+    *out_n = 0;
+    if (!std::isfinite(x_min) || !std::isfinite(x_max) || !std::isfinite(y_min) || !std::isfinite(y_max) || !(x_min <= x_max) || !(y_min <= y_max))
+        return fail(KICP_ERR_ARG, "the box must be finite with x_min <= x_max and y_min <= y_max");
+    if (!(spacing > 0.0) || !std::isfinite(spacing)) return fail(KICP_ERR_ARG, "spacing must be positive and finite");
+    const double nx = arcs_host::box_count(x_min, x_max, spacing), ny = arcs_host::box_count(y_min, y_max, spacing);
+    if (!(nx * ny <= static_cast<double>(kArcsMaxP)))
+        return fail(KICP_ERR_CAPACITY, "the lattice would have more samples than a footprint may (limit " + std::to_string(kArcsMaxP) + ")");
+    *out_n = static_cast<size_t>(nx) * static_cast<size_t>(ny);
+    arcs_host::box(x_min, x_max, y_min, y_max, static_cast<size_t>(nx), static_cast<size_t>(ny), out_xy, cap);
+    if (*out_n > cap) return fail(KICP_ERR_CAPACITY, "the lattice has " + std::to_string(*out_n) + " samples, cap is " + std::to_string(cap));
+    return KICP_OK;
+}
+int kicp_arcs_best(const unsigned int *results, size_t n_arcs, unsigned int w_potential, unsigned int w_cost, unsigned int w_blocked, unsigned int n_steps,
+                   unsigned int min_free_steps, size_t *out_index) {
+    if (!results || !out_index) return fail(KICP_ERR_ARG, "null argument");
+    *out_index = n_arcs;
+    if (int rc = check_arc_count(n_arcs)) return rc;
+    *out_index = arcs_host::best(results, n_arcs, w_potential, w_cost, w_blocked, n_steps, min_free_steps);
+    return KICP_OK;
+}
+int kicp_score_arcs_from_plan(const unsigned char *q, const unsigned int *potential, double cell, double origin_x, double origin_y, unsigned int width,
+                              unsigned int height, const double start[4], const double *arcs, size_t n_arcs, unsigned int n_steps, const double *footprint_xy,
+                              size_t n_samples, unsigned int *out, size_t cap) {
+    if (!q || !potential) return fail(KICP_ERR_ARG, "null argument");
+    if (!(cell > 0.0) || !std::isfinite(cell) || !std::isfinite(origin_x) || !std::isfinite(origin_y)) return fail(KICP_ERR_ARG, "cell must be positive and finite, the origin finite");
+    if (width == 0 || height == 0) return fail(KICP_ERR_ARG, "width and height must be at least 1");
+    if (static_cast<unsigned long long>(width) * height > kGridMaxCells) return fail(KICP_ERR_CAPACITY, "width * height exceeds 2^28 = " + std::to_string(kGridMaxCells));
+    if (int rc = check_arcs_args(start, arcs, n_arcs, n_steps, footprint_xy, n_samples, out, cap)) return rc;
+    arcs_host::score(ArcGeom{cell, origin_x, origin_y, width, height}, q, potential, start, arcs, n_arcs, n_steps, footprint_xy, static_cast<uint32_t>(n_samples), out);
+    return KICP_OK;
+}
+int kicp_grid_has_plan(const kicp_grid *grid) { return grid && grid->plan_valid ? 1 : 0; }
+int kicp_grid_score_arcs(const kicp_grid *cgrid, const double start[4], const double *arcs, size_t n_arcs, unsigned int n_steps, const double *footprint_xy,
+                         size_t n_samples, unsigned int *out, size_t cap) {
+    KICP_TRACE_CALL();
+    if (!cgrid) return fail(KICP_ERR_ARG, "null argument");
+    if (int rc = check_arcs_args(start, arcs, n_arcs, n_steps, footprint_xy, n_samples, out, cap)) return rc;
+    if (!cgrid->plan_valid)
+        return fail(KICP_ERR_ARG, "the handle holds no plan: call kicp_grid_potential or kicp_grid_potential_of_costmap first (a call of theirs that failed left none)");
+    kicp_grid *grid = const_cast<kicp_grid *>(cgrid);  // logically const: the buffers are scratch, the plan is only read
+    if (int rc = set_device(grid->device)) return rc;
+    hipStream_t st = grid->stream;
+    // the buffers grow while the stream is idle: every entry of the handle drains it
+    if (int rc = grid->d_arcs.reserve(4 * n_arcs)) return rc;
+    if (int rc = grid->d_footprint.reserve(2 * n_samples)) return rc;
+    if (int rc = grid->d_arc_out.reserve(4 * n_arcs)) return rc;
+    if (int rc = grid->h_arc_out.reserve(4 * n_arcs, hipHostMallocDefault, false)) return rc;
+    HIP_TRY(hipMemcpyAsync(grid->d_arcs.get(), arcs, 4 * n_arcs * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(grid->d_footprint.get(), footprint_xy, 2 * n_samples * sizeof(double), hipMemcpyHostToDevice, st));
+    const uint32_t blocks = static_cast<uint32_t>((n_arcs + kArcsPerBlock - 1u) / kArcsPerBlock);
+    hipLaunchKernelGGL(k_arcs_score, dim3(blocks), dim3(kArcsBlock), 0, st, grid->d_q.get(), grid->d_pot.get(),
+                       ArcGeom{grid->cfg.cell, grid->cfg.origin_x, grid->cfg.origin_y, grid->cfg.width, grid->cfg.height}, ArcPose{start[0], start[1], start[2], start[3]},
+                       grid->d_arcs.get(), static_cast<uint32_t>(n_arcs), n_steps, grid->d_footprint.get(), static_cast<uint32_t>(n_samples), grid->d_arc_out.get());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(grid->h_arc_out.get(), grid->d_arc_out.get(), 4 * n_arcs * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    std::memcpy(out, grid->h_arc_out.get(), 4 * n_arcs * sizeof(uint32_t));
+    return KICP_OK;
 }
 int kicp_grid_last_window(const kicp_grid *grid, unsigned int *x0, unsigned int *y0, unsigned int *w, unsigned int *h) {
     if (!grid || !x0 || !y0 || !w || !h) return fail(KICP_ERR_ARG, "null argument");

@@ -45,9 +45,12 @@ def grown(rect, radius, width, height):
     return (ax, ay, min(x0 + w + radius, width) - ax, min(y0 + h + radius, height) - ay)
 
 
-def cases(n_frames):
+def cases(n_frames, only=None):
+    """only: (scene, cell) pairs to build instead of all four"""
     out = []
     for name in GEOMETRY:
+        if only is not None and not any(scene == name for scene, _ in only):
+            continue
         cfg, scene, dirs, rng = scene_and_beams(name)
         sensor = np.array([0.0, 0.0, cfg.sensor_height])
         poses = [syn.planar_pose(1.2, -0.7, 0.9)]
@@ -55,6 +58,8 @@ def cases(n_frames):
             poses.append(syn.pose_mul(poses[-1], syn.planar_pose(0.2, 0.0, np.deg2rad(1.0 + 0.1 * k))))
         frames = [np.ascontiguousarray(syn.make_scan(scene, pose, dirs, cfg.sensor_height, rng)) for pose in poses]
         for cell in CELLS:
+            if only is not None and (name, cell) not in only:
+                continue
             gcfg = grid_config(name, cell)
             grid = make_grid(gcfg)
             for pose, frame in zip(poses, frames):
@@ -62,7 +67,7 @@ def cases(n_frames):
             radius = int(round(1.0 / cell))
             window = grid.last_window()
             out.append(dict(name=name, cell=cell, cfg=gcfg, grid=grid, radius=radius, table=K.nav2_cost_table(cell, radius, 0.35, 3.0), points=len(frames[0]),
-                            rects={"full": None, "window": grown(window, radius, gcfg["width"], gcfg["height"])}, window=window,
+                            rects={"full": None, "window": grown(window, radius, gcfg["width"], gcfg["height"])}, window=window, pose=poses[-1],
                             t={(where, which): [] for where in ("device", "host") for which in ("full", "window")}))
     return out
 
