@@ -734,6 +734,65 @@ int kicp_grid_has_plan(const kicp_grid *grid); /* 1 when the handle holds a vali
 int kicp_grid_score_arcs(const kicp_grid *grid, const double start[4], const double *arcs, size_t n_arcs, unsigned int n_steps, const double *footprint_xy,
                          size_t n_samples, unsigned int *out, size_t cap);
 
+/* ---- where to go while mapping: the exploration frontiers of the grid, ranked by the plan (kicp_grid.hip) ------------------------------
+ * A robot that is still mapping has no goal from outside: its goal is the edge of what it has seen.  These entries find the free cells
+ * that border unknown space, group them into frontiers and sum ten words per frontier - what explore_lite or a Nav2 exploration node
+ * does on a copy of the map.  Everything below is integer and the result is unique: the host and the device entry return equal arrays.
+ *
+ * CLASSES.  Those of the clearance section above, with unknown_is_obstacle = 0: with v the readout of a cell at `min_observations`, the
+ * cell is OCCUPIED (a source) when (double)v > occupied_thresh * 100.0, UNKNOWN when v < 0, and CLEAR otherwise.  Cells outside the
+ * grid are nothing: in particular they are not unknown.
+ *
+ * FRONTIER CELL.  A CLEAR cell is a frontier cell when at least one of its four edge neighbours inside the grid is UNKNOWN.
+ *
+ * FRONTIER.  Frontier cells are joined to each of their eight neighbours that is a frontier cell.  There is NO corner rule: two
+ * frontier cells that touch at a corner are joined whatever the two cells beside them are.  A frontier is a connected component of
+ * that graph.
+ *
+ * LABEL.  The label of a frontier is the least cell index y * width + x among its cells.  The label plane is width * height words of
+ * unsigned int: a frontier cell holds its frontier's label, every other cell 0xFFFFFFFF.  width * height <= 2^28, so labels fit.
+ *
+ * ROW.  Per frontier KICP_FRONTIER_WORDS = 10 words of unsigned long long:
+ *   0           the label
+ *   1           the size in cells
+ *   2, 3        the sum of x and the sum of y over its cells (the centroid is the caller's division: none enters the contract)
+ *   4, 5, 6, 7  min x, max x, min y, max y
+ *   8           best_potential: the least pot(c) over its cells
+ *   9           best_cell: the least cell index among the cells that attain it
+ * pot(c) is the potential of the PLAN the handle holds (the section above) when use_plan != 0 - for the host entry: potential[c] when
+ * `potential` is not null - and 0xFFFFFFFF for every cell otherwise; then word 8 is 0xFFFFFFFF and word 9 equals the label.  Words 8
+ * and 9 together are the minimum of the 64-bit key pot(c) * 2^32 + c.  With the robot's cell as the plan's one goal, word 8 is the cost
+ * of driving to the frontier and word 9 the cell to drive to; a frontier that lies wholly in unreached space reads 0xFFFFFFFF.
+ *
+ * OUTPUT.  Frontiers with size < min_size are dropped (min_size >= 1; anything else is KICP_ERR_ARG); the others are written in
+ * ascending label order.  The label plane is NOT filtered by min_size.
+ *
+ * CAPACITY.  *out_n is the number of frontiers that pass the filter.  When it exceeds cap_rows, the first cap_rows rows are stored and
+ * the call returns KICP_ERR_CAPACITY with the needed number in *out_n - kicp_potential_path's convention.  out_rows may be NULL only
+ * with cap_rows == 0.  out_labels is nullable: cap_labels must be width * height with a label plane and 0 without one.
+ *
+ * ENTRIES.  kicp_frontiers_from_occupancy is pure host code over a readout (width x height values as kicp_grid_occupancy writes them;
+ * min_observations is only checked) and needs no GPU; width or height 0 is KICP_ERR_ARG, width * height above 2^28 KICP_ERR_CAPACITY.
+ * kicp_grid_frontiers works on the counters where they are, in HBM, and returns after its kernels have completed and the rows - and
+ * the label plane, if one was asked for - have arrived.  THE PLAN IS A SNAPSHOT, THE FRONTIERS COME FROM THE CURRENT COUNTERS: frames
+ * integrated since the potential call move the frontiers and not the potentials they are ranked by.  That is intended - a node plans
+ * at a lower rate than it maps - and a caller who wants both of one moment calls kicp_grid_potential first.  The call reads the plan
+ * and never writes it: a plan stays valid, its q and potential unchanged, and the counters are untouched too.  use_plan != 0 on a
+ * handle without a valid plan (kicp_grid_has_plan) is KICP_ERR_ARG; the message says to call kicp_grid_potential first.
+ * For both entries a null handle / occupancy, config or out_n, min_observations < 1, an occupied_thresh outside [0, 1], min_size < 1
+ * and a cap_labels that is neither 0 nor width * height are KICP_ERR_ARG; *out_n is 0 after any of them. */
+typedef struct kicp_frontier_config {
+    unsigned int min_observations; /* >= 1 */
+    double occupied_thresh;        /* in [0, 1] */
+    unsigned int min_size;         /* >= 1: frontiers of fewer cells are not output */
+} kicp_frontier_config;
+#define KICP_FRONTIER_WORDS 10
+int kicp_frontiers_from_occupancy(const signed char *occupancy, unsigned int width, unsigned int height, const kicp_frontier_config *config,
+                                  const unsigned int *potential, unsigned long long *out_rows, size_t cap_rows, size_t *out_n,
+                                  unsigned int *out_labels, size_t cap_labels);
+int kicp_grid_frontiers(const kicp_grid *grid, const kicp_frontier_config *config, int use_plan, unsigned long long *out_rows, size_t cap_rows,
+                        size_t *out_n, unsigned int *out_labels, size_t cap_labels);
+
 /* ---- map points the new frame sees through: a cube-map depth test (kicp_view.hip) ----------------------------------------------------
  * The local map loses points by distance only (RemovePointsFarFromLocation); whatever stood in view for one frame - a person crossing,
  * a forklift, a door leaf - stays until the robot is max_range away.  A kicp_view holds a depth image of ONE frame, and

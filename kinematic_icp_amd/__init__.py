@@ -76,6 +76,12 @@ class PlanConfig(C.Structure):
     _fields_ = [("max_potential", C.c_uint)]
 
 
+class FrontierConfig(C.Structure):
+    """kicp_frontier_config: the readout's min_observations, the threshold above which a cell is occupied, and the least size in cells
+    of a frontier that is output"""
+    _fields_ = [("min_observations", C.c_uint), ("occupied_thresh", C.c_double), ("min_size", C.c_uint)]
+
+
 class ViewConfig(C.Structure):
     """kicp_view_config: a cube map of res x res pixels per face; the verdict looks at (2 window + 1)^2 pixels, needs min_rays returns
     among them and a gap of more than margin + margin_per_metre * depth; max_ray bounds the (Chebyshev) depth on both sides"""
@@ -205,7 +211,11 @@ _SIGNATURES = {
                                             _dp, C.c_size_t, C.POINTER(C.c_uint), C.c_size_t]),
     "kicp_grid_has_plan": (C.c_int, [C.c_void_p]),
     "kicp_grid_score_arcs": (C.c_int, [C.c_void_p, _dp, _dp, C.c_size_t, C.c_uint, _dp, C.c_size_t, C.POINTER(C.c_uint), C.c_size_t]),
-    "kicp_planar_grid": (C.c_size_t, [_dp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _dp, C.c_size_t]),
+    "kicp_frontiers_from_occupancy": (C.c_int, [C.POINTER(C.c_byte), C.c_uint, C.c_uint, C.POINTER(FrontierConfig), C.POINTER(C.c_uint), C.POINTER(C.c_ulonglong), C.c_size_t,
+                                                C.POINTER(C.c_size_t), C.POINTER(C.c_uint), C.c_size_t]),
+    "kicp_grid_frontiers": (C.c_int, [C.c_void_p, C.POINTER(FrontierConfig), C.c_int, C.POINTER(C.c_ulonglong), C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint),
+                                      C.c_size_t]),
+    "kicp_planar_grid": (C.c_size_t,[_dp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _dp, C.c_size_t]),
     "kicp_map_save_pcd": (C.c_int, [C.c_void_p, C.c_char_p]),
     "kicp_map_load_pcd": (C.c_int, [C.c_char_p, C.c_double, C.c_double, C.c_uint, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
     "kicp_map_params": (C.c_int, [C.c_void_p, _dp, _dp, C.POINTER(C.c_uint)]),
@@ -695,6 +705,52 @@ def arcs_best(results, n_steps, w_potential=1, w_cost=0, w_blocked=0, min_free_s
     return None if index.value == len(r) else int(index.value)
 
 
+FRONTIER_WORDS = 10
+
+
+def _frontier_config(min_observations, occupied_thresh, min_size):
+    args = [int(min_observations), int(min_size)]
+    if min(args) < 0 or max(args) > 0xFFFFFFFF:
+        raise KicpError(KICP_ERR_ARG, "min_observations and min_size are unsigned 32-bit integers, at least 1")
+    return FrontierConfig(args[0], float(occupied_thresh), args[1])
+
+
+def _frontier_call(call, shape, return_labels):
+    """call(rows pointer, cap, byref(n), labels pointer, cap_labels) -> rc, with a modest capacity first and, when more frontiers pass the
+    filter than that, once more with the number that came back -> uint64 (F, 10), or that and uint32 labels of `shape`"""
+    labels = np.empty(shape, dtype=np.uint32) if return_labels else None
+    lp, lcap = (_u32(labels), labels.size) if return_labels else (None, 0)
+    cap, n = 256, C.c_size_t()
+    rows = np.empty((cap, FRONTIER_WORDS), dtype=np.uint64)
+    rc = call(rows.ctypes.data_as(C.POINTER(C.c_ulonglong)), cap, C.byref(n), lp, lcap)
+    if rc == KICP_ERR_CAPACITY and n.value > cap:  # more frontiers than that: their number came back
+        cap = n.value
+        rows = np.empty((cap, FRONTIER_WORDS), dtype=np.uint64)
+        rc = call(rows.ctypes.data_as(C.POINTER(C.c_ulonglong)), cap, C.byref(n), lp, lcap)
+    _check(rc)
+    rows = rows[:n.value].copy()
+    return (rows, labels) if return_labels else rows
+
+
+def frontiers_from_occupancy(occupancy, min_observations=1, occupied_thresh=0.65, min_size=1, potential=None, return_labels=False):
+    """kicp_frontiers_from_occupancy: the exploration frontiers of a readout shaped (height, width) - the clear cells with an unknown edge
+    neighbour, joined over their eight neighbours - of at least min_size cells, in ascending label order -> uint64 (F, 10): label (the
+    least cell index y * width + x), size, sum of x, sum of y, min x, max x, min y, max y, best_potential (the least of `potential`,
+    uint32 (height, width), over the cells; 0xFFFFFFFF without one) and best_cell (the least index that attains it).  return_labels:
+    also uint32 (height, width), the label on every frontier cell - of the small frontiers too - and 0xFFFFFFFF elsewhere.  Pure host
+    code: needs no GPU."""
+    occ = _occupancy_2d(occupancy)
+    cfg = _frontier_config(min_observations, occupied_thresh, min_size)
+    pot = None
+    if potential is not None:
+        pot = np.ascontiguousarray(potential, dtype=np.uint32)
+        if pot.shape != occ.shape:
+            raise KicpError(KICP_ERR_ARG, "the potential must have the occupancy's shape")
+    return _frontier_call(lambda rp, cap, n, lp, lcap: lib().kicp_frontiers_from_occupancy(occ.ctypes.data_as(C.POINTER(C.c_byte)), occ.shape[1], occ.shape[0], C.byref(cfg),
+                                                                                           None if pot is None else _u32(pot), rp, cap, n, lp, lcap),
+                          occ.shape, return_labels)
+
+
 class OccupancyGrid:
     """kicp_grid: a world-aligned 2-D grid of (hits, misses) counters a mapping run draws frame by frame - every used point's cell is
     hit, the cells its ray from the sensor crosses are missed, once per cell per frame (include/kicp.h states the exact semantics).
@@ -821,6 +877,16 @@ class OccupancyGrid:
         _check(lib().kicp_grid_score_arcs(self._h, C.cast(s.ctypes.data, _dp), C.cast(a.ctypes.data, _dp), len(a), n_steps, C.cast(f.ctypes.data, _dp), len(f), _u32(out),
                                           out.size))
         return out
+
+    def frontiers(self, min_observations=1, occupied_thresh=0.65, min_size=1, use_plan=False, return_labels=False):
+        """kicp_grid_frontiers: on the GPU, frontiers_from_occupancy's result on the counters where they are -> uint64 (F, 10), and uint32
+        (height, width) labels with return_labels.  use_plan: best_potential and best_cell come from the plan the last potential() or
+        potential_of_costmap() left in the handle (KICP_ERR_ARG when there is none) - with the robot's cell as that call's one goal,
+        the cost of driving to each frontier and the cell to drive to.  The plan is a snapshot, the frontiers are the current counters';
+        neither is changed."""
+        cfg = _frontier_config(min_observations, occupied_thresh, min_size)
+        return _frontier_call(lambda rp, cap, n, lp, lcap: lib().kicp_grid_frontiers(self._h, C.byref(cfg), 1 if use_plan else 0, rp, cap, n, lp, lcap),
+                              (self.height, self.width), return_labels)
 
     def last_window(self):
         """kicp_grid_last_window: (x0, y0, w, h) of the last integrated frame's window clipped to the grid; w = h = 0 when it lies

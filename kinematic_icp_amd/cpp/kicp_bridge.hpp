@@ -177,6 +177,25 @@ inline size_t best_arc(const std::vector<ArcResult> &results, unsigned int n_ste
           "kicp_bridge::best_arc");
     return index;
 }
+// FrontierConfig and Frontier go with KinematicICP::GridFrontiers (kicp.h kicp_grid_frontiers): the classes' thresholds and the least
+// size of a frontier that is output, and one frontier - the ten words of its row by name.  The centroid is in cells, as doubles: the
+// middle of cell (x, y) lies at origin + (x + 0.5, y + 0.5) * cell in the world.
+using FrontierConfig = kicp_frontier_config;
+struct Frontier {
+    uint32_t label = 0;  // the least cell index y * width + x of its cells
+    uint64_t size = 0, sum_x = 0, sum_y = 0;
+    uint32_t min_x = 0, max_x = 0, min_y = 0, max_y = 0;
+    uint32_t best_potential = 0xFFFFFFFFu, best_cell = 0;  // the least potential of the plan over its cells (0xFFFFFFFF: none reached, or no plan asked for) and where
+    double centroid_x() const { return static_cast<double>(sum_x) / static_cast<double>(size); }
+    double centroid_y() const { return static_cast<double>(sum_y) / static_cast<double>(size); }
+};
+inline Frontier frontier_of_row(const unsigned long long *row) {
+    Frontier f;
+    f.label = static_cast<uint32_t>(row[0]), f.size = row[1], f.sum_x = row[2], f.sum_y = row[3];
+    f.min_x = static_cast<uint32_t>(row[4]), f.max_x = static_cast<uint32_t>(row[5]), f.min_y = static_cast<uint32_t>(row[6]), f.max_y = static_cast<uint32_t>(row[7]);
+    f.best_potential = static_cast<uint32_t>(row[8]), f.best_cell = static_cast<uint32_t>(row[9]);
+    return f;
+}
 inline std::shared_ptr<kicp_grid> make_grid(const GridConfig &config, int device = -1) {
     kicp_grid *grid = nullptr;
     check(kicp_grid_create(&config, device < 0 ? default_device() : device, &grid), "kicp_bridge::make_grid");

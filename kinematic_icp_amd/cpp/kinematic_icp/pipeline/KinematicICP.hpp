@@ -402,6 +402,34 @@ public:
                    unsigned int min_free_steps = 1) const {
         return kicp_bridge::best_arc(results, n_steps, w_potential, w_cost, w_blocked, min_free_steps);
     }
+    // Where to go while mapping (kicp.h kicp_grid_frontiers): the frontiers of the grid as it stands - the clear cells with an unknown
+    // edge neighbour, joined over their eight neighbours - found on the GPU from the counters, those of at least config.min_size cells
+    // in ascending label order.  With use_plan, best_potential and best_cell come from the plan the last GridPotential or
+    // GridPotentialOfCostmap left on the GPU: with the robot's cell as that call's one goal they are the cost of driving to the frontier
+    // and the cell to drive to - PotentialPath from best_cell leads down to the robot; reverse it.  The plan is a snapshot, the
+    // frontiers are the current counters'; neither is changed.  labels (nullable): width * height words, the label on every frontier
+    // cell and 0xFFFFFFFF elsewhere.  Throws without a grid, and with use_plan without a plan ("call GridPotential first").
+    void GridFrontiers(std::vector<kicp_bridge::Frontier> &frontiers, const kicp_bridge::FrontierConfig &config, bool use_plan = false,
+                       std::vector<uint32_t> *labels = nullptr) const {
+        const kicp_bridge::GridRect r = GridRectOrAll(nullptr, "GridFrontiers");
+        if (use_plan && !kicp_grid_has_plan(grid_.get()))
+            throw std::runtime_error("KinematicICP::GridFrontiers: call GridPotential first (or GridPotentialOfCostmap): the grid holds no plan");
+        if (labels) labels->resize(static_cast<size_t>(r.w) * r.h);
+        std::vector<unsigned long long> rows(256 * static_cast<size_t>(KICP_FRONTIER_WORDS));
+        size_t n = 0;
+        auto call = [&] {
+            return kicp_grid_frontiers(grid_.get(), &config, use_plan ? 1 : 0, rows.data(), rows.size() / KICP_FRONTIER_WORDS, &n, labels ? labels->data() : nullptr,
+                                       labels ? labels->size() : 0);
+        };
+        int rc = call();
+        if (rc == KICP_ERR_CAPACITY && n > rows.size() / KICP_FRONTIER_WORDS) {  // more frontiers than that: their number came back
+            rows.resize(n * KICP_FRONTIER_WORDS);
+            rc = call();
+        }
+        kicp_bridge::check(rc, "GridFrontiers");
+        frontiers.resize(n);
+        for (size_t i = 0; i < n; ++i) frontiers[i] = kicp_bridge::frontier_of_row(rows.data() + i * KICP_FRONTIER_WORDS);
+    }
     // the window of the last integrated frame clipped to the grid; empty() when it lies outside, and before any frame
     kicp_bridge::GridRect GridLastWindow() const {
         kicp_bridge::GridRect r;

@@ -8,12 +8,15 @@
 // kicp_potential_from_costmap and kicp_potential_path live here too).  A successful potential call leaves a PLAN in the handle - q and
 // the potential, where they lie in HBM - on which kicp_grid_score_arcs scores a fan of arc trajectories (kernel: kicp_arcs.hpp,
 // arithmetic: kicp_arcs_host.hpp; its host twin kicp_score_arcs_from_plan and the helpers kicp_plan_q, kicp_arc_steps,
-// kicp_footprint_box and kicp_arcs_best are here as well).
+// kicp_footprint_box and kicp_arcs_best are here as well).  The exploration frontiers of the counters - the free cells that border
+// unknown space, grouped and ranked by that plan - are kicp_grid_frontiers (kernels: kicp_front.hpp, arithmetic: kicp_front_host.hpp;
+// host twin: kicp_frontiers_from_occupancy).
 #include <cerrno>
 #include <memory>
 
 #include "kicp_arcs.hpp"
 #include "kicp_clear.hpp"
+#include "kicp_front.hpp"
 #include "kicp_grid.hpp"
 #include "kicp_internal.hpp"
 #include "kicp_nav.hpp"
@@ -50,6 +53,11 @@ struct kicp_grid {
     DevBuf<double> d_arcs, d_footprint;  // kicp_grid_score_arcs: its uploads, its results and the pinned buffer they come back through
     DevBuf<uint32_t> d_arc_out;
     PinnedBuf<uint32_t> h_arc_out;
+    DevBuf<uint8_t> d_front_flags;       // kicp_grid_frontiers: a byte per cell, the parent plane that becomes the label plane, the roots'
+    DevBuf<uint32_t> d_front_parent, d_front_row_of, d_front_ctr;  // row numbers, the count of roots, the rows and where they and the
+    DevBuf<unsigned long long> d_front_rows;                       // count land
+    PinnedBuf<uint32_t> h_front_ctr;
+    std::vector<unsigned long long> h_front_rows;
     HostStage stage;
     ~kicp_grid() {
         if (stream) (void)hipStreamSynchronize(stream), (void)hipStreamDestroy(stream);
@@ -248,6 +256,23 @@ int check_arcs_args(const double *start, const double *arcs, size_t n_arcs, unsi
     if (cap != 4 * n_arcs) return fail(KICP_ERR_ARG, "cap must be 4 * n_arcs = " + std::to_string(4 * n_arcs));
     for (int i = 0; i < 4; ++i)
         if (!std::isfinite(start[i])) return fail(KICP_ERR_ARG, "the start (x, y, cosine, sine) must be finite");
+    return KICP_OK;
+}
+// what the two frontier entries share: the configuration, and the two outputs with their capacities
+int check_front_args(const kicp_frontier_config *cfg, size_t cells, const unsigned long long *out_rows, size_t cap_rows, const unsigned int *out_labels, size_t cap_labels,
+                     FrontParams &p) {
+    if (cfg->min_observations < 1u) return fail(KICP_ERR_ARG, "min_observations must be at least 1");
+    if (!(0.0 <= cfg->occupied_thresh && cfg->occupied_thresh <= 1.0)) return fail(KICP_ERR_ARG, "occupied_thresh must lie in [0, 1]");
+    if (cfg->min_size < 1u) return fail(KICP_ERR_ARG, "min_size must be at least 1");
+    if (!out_rows && cap_rows) return fail(KICP_ERR_ARG, "out_rows may be null only when cap_rows is 0");
+    if (cap_labels != 0u && cap_labels != cells) return fail(KICP_ERR_ARG, "cap_labels must be 0 or width * height = " + std::to_string(cells));
+    if ((out_labels == nullptr) != (cap_labels == 0u)) return fail(KICP_ERR_ARG, "out_labels must be null exactly when cap_labels is 0");
+    p = FrontParams{cfg->min_observations, clear_source_min(cfg->occupied_thresh)};
+    return KICP_OK;
+}
+int front_result(size_t n, size_t cap_rows, size_t *out_n) {
+    *out_n = n;
+    if (n > cap_rows) return fail(KICP_ERR_CAPACITY, std::to_string(n) + " frontiers pass the filter, cap_rows is " + std::to_string(cap_rows));
     return KICP_OK;
 }
 }  // namespace
@@ -557,6 +582,63 @@ int kicp_grid_score_arcs(const kicp_grid *cgrid, const double start[4], const do
     HIP_TRY(hipStreamSynchronize(st));
     std::memcpy(out, grid->h_arc_out.get(), 4 * n_arcs * sizeof(uint32_t));
     return KICP_OK;
+}
+int kicp_frontiers_from_occupancy(const signed char *occupancy, unsigned int width, unsigned int height, const kicp_frontier_config *cfg, const unsigned int *potential,
+                                  unsigned long long *out_rows, size_t cap_rows, size_t *out_n, unsigned int *out_labels, size_t cap_labels) {
+    if (out_n) *out_n = 0;
+    if (!occupancy || !cfg || !out_n) return fail(KICP_ERR_ARG, "null argument");
+    if (width == 0 || height == 0) return fail(KICP_ERR_ARG, "width and height must be at least 1");
+    if (static_cast<unsigned long long>(width) * height > kGridMaxCells) return fail(KICP_ERR_CAPACITY, "width * height exceeds 2^28 = " + std::to_string(kGridMaxCells));
+    FrontParams p;
+    if (int rc = check_front_args(cfg, static_cast<size_t>(width) * height, out_rows, cap_rows, out_labels, cap_labels, p)) return rc;
+    return front_result(front_host::frontiers(reinterpret_cast<const int8_t *>(occupancy), width, height, p.source_min, cfg->min_size, potential, out_rows, cap_rows, out_labels),
+                        cap_rows, out_n);
+}
+int kicp_grid_frontiers(const kicp_grid *cgrid, const kicp_frontier_config *cfg, int use_plan, unsigned long long *out_rows, size_t cap_rows, size_t *out_n,
+                        unsigned int *out_labels, size_t cap_labels) {
+    KICP_TRACE_CALL();
+    if (out_n) *out_n = 0;
+    if (!cgrid || !cfg || !out_n) return fail(KICP_ERR_ARG, "null argument");
+    FrontParams p;
+    if (int rc = check_front_args(cfg, cgrid->cells, out_rows, cap_rows, out_labels, cap_labels, p)) return rc;
+    if (use_plan && !cgrid->plan_valid)
+        return fail(KICP_ERR_ARG, "the handle holds no plan: call kicp_grid_potential or kicp_grid_potential_of_costmap first (a call of theirs that failed left none)");
+    kicp_grid *grid = const_cast<kicp_grid *>(cgrid);  // logically const: the buffers are scratch, the counters and the plan are only read
+    if (int rc = set_device(grid->device)) return rc;
+    hipStream_t st = grid->stream;
+    const uint32_t width = grid->cfg.width, height = grid->cfg.height, cells = static_cast<uint32_t>(grid->cells);
+    const uint32_t tiles_x = (width + kFrontTile - 1u) / kFrontTile, tiles_y = (height + kFrontTile - 1u) / kFrontTile;
+    // the buffers grow while the stream is idle: every entry of the handle drains it
+    if (int rc = grid->d_front_flags.reserve(cells)) return rc;
+    if (int rc = grid->d_front_parent.reserve(cells)) return rc;
+    if (int rc = grid->d_front_row_of.reserve(cells)) return rc;
+    if (int rc = grid->d_front_ctr.reserve(1)) return rc;
+    if (int rc = grid->h_front_ctr.reserve(1, hipHostMallocDefault, false)) return rc;
+    const uint32_t cell_blocks = (cells + kFrontBlock - 1u) / kFrontBlock;
+    HIP_TRY(hipMemsetAsync(grid->d_front_ctr.get(), 0, sizeof(uint32_t), st));
+    hipLaunchKernelGGL(k_front_mark, dim3(cell_blocks), dim3(kFrontBlock), 0, st, grid->d_counts.get(), width, height, cells, p, grid->d_front_flags.get());
+    hipLaunchKernelGGL(k_front_local, dim3(tiles_x * tiles_y), dim3(kFrontBlock), 0, st, grid->d_front_flags.get(), width, height, tiles_x, grid->d_front_parent.get());
+    const uint32_t row_lanes = (tiles_y - 1u) * width, lanes = row_lanes + (tiles_x - 1u) * height;  // (both below cells / 16)
+    if (lanes)
+        hipLaunchKernelGGL(k_front_border, dim3((lanes + kFrontBlock - 1u) / kFrontBlock), dim3(kFrontBlock), 0, st, grid->d_front_flags.get(), width, height, row_lanes, lanes,
+                           grid->d_front_parent.get());
+    hipLaunchKernelGGL(k_front_flatten, dim3(cell_blocks), dim3(kFrontBlock), 0, st, grid->d_front_flags.get(), cells, grid->d_front_parent.get(), grid->d_front_row_of.get(),
+                       grid->d_front_ctr.get());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(grid->h_front_ctr.get(), grid->d_front_ctr.get(), sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    if (out_labels) HIP_TRY(hipMemcpyAsync(out_labels, grid->d_front_parent.get(), static_cast<size_t>(cells) * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));  // the number of frontiers sizes the rows
+    const uint32_t n_rows = grid->h_front_ctr.get()[0];
+    if (n_rows == 0u) return KICP_OK;
+    if (int rc = grid->d_front_rows.reserve(static_cast<size_t>(n_rows) * kFrontWords)) return rc;
+    grid->h_front_rows.resize(static_cast<size_t>(n_rows) * kFrontWords);
+    hipLaunchKernelGGL(k_front_rows, dim3((n_rows + kFrontBlock - 1u) / kFrontBlock), dim3(kFrontBlock), 0, st, grid->d_front_rows.get(), n_rows);
+    hipLaunchKernelGGL(k_front_sum, dim3(cell_blocks), dim3(kFrontBlock), 0, st, grid->d_front_flags.get(), grid->d_front_parent.get(), grid->d_front_row_of.get(),
+                       use_plan ? grid->d_pot.get() : static_cast<const uint32_t *>(nullptr), width, cells, n_rows, grid->d_front_rows.get());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(grid->h_front_rows.data(), grid->d_front_rows.get(), grid->h_front_rows.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return front_result(front_emit(grid->h_front_rows.data(), n_rows, cfg->min_size, out_rows, cap_rows), cap_rows, out_n);
 }
 int kicp_grid_last_window(const kicp_grid *grid, unsigned int *x0, unsigned int *y0, unsigned int *w, unsigned int *h) {
     if (!grid || !x0 || !y0 || !w || !h) return fail(KICP_ERR_ARG, "null argument");
