@@ -920,7 +920,8 @@ int kicp_pre_ingested(const kicp_pre *pre, double *out_xyz, double *out_stamps, 
 /* kiss_icp::VoxelDownsample(buffer src, voxel_size) -> buffer dst: the first point (lowest index) of every voxel, in the
  * ITERATION ORDER of the reference's tsl::robin_map after reserve(frame.size()) - the order the second downsample and the map
  * update of the pipeline depend on (kiss-icp v1.2.0 core/VoxelUtils.cpp; call sites pipeline/KinematicICP.cpp:40,42).
- * KICP_ERR_CAPACITY when a voxel coordinate leaves +-2^20 (the handle stays usable). */
+ * KICP_ERR_CAPACITY when a voxel coordinate leaves +-2^20 (the handle stays usable).  A coordinate that is not finite counts as
+ * out of range: NaN and +-inf give KICP_ERR_CAPACITY too (the reference's float-to-int conversion of such a value is undefined). */
 int kicp_pre_voxel_downsample(kicp_pre *pre, int src_buffer, double voxel_size, int dst_buffer, size_t *out_n);
 /* Largest robin-hood displacement (in buckets) the last kicp_pre_voxel_downsample saw while replaying the reference's table
  * (0 when every probe stayed below 32).  tsl::robin_map grows its table when an insertion's probe exceeds the container's
@@ -971,6 +972,11 @@ size_t kicp_pre_ingested_count(const kicp_pre *pre);
  *            previous frame's; the first frame: the input count).  A wrong power-of-two bracket costs the frame the unfused
  *            downsamples, never a different result.
  *   "fused_frames" / "guess_misses" (read only): frames the fused chain served / of those, frames whose guess was wrong.
+ *   "point_tiles" / "l1_tiles" / "l2_workgroups" / "l2_tiles" (read only, host-side bookkeeping; 0 before the first fused frame):
+ *            the last fused frame's 256-point tiles, 256-bucket tiles of its guessed first table, workgroups of its second-level
+ *            launches and 256-bucket tiles of its second table (from the returned count; 0 when the guess was wrong).
+ *   "scan_launches" (read only): launches of the separate block-count scan this handle has made so far - one per compaction
+ *            or gather whose grid exceeds 4 096 workgroups.
  * Which way the last decode went (read only, host-side bookkeeping; for tests that must prove the regime they ran in).
  * "ingest_*": the last kicp_pre_ingest that decoded its message itself (not one that took a look-ahead slot, not an empty one);
  * "ahead_*": the last look-ahead decode (kicp_pre_ingest_ahead + the chained pre-steps; read it after the kicp_pre_ingest call

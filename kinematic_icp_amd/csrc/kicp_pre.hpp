@@ -190,6 +190,15 @@ __device__ __forceinline__ unsigned long long pack_voxel21(int32_t x, int32_t y,
            (static_cast<unsigned long long>(static_cast<uint32_t>(y + lim) & 0x1FFFFFu) << 21) |
            static_cast<unsigned long long>(static_cast<uint32_t>(x + lim) & 0x1FFFFFu);
 }
+// the voxel of a point and its key.  +-inf saturates in the conversion and fails the range test; a NaN coordinate converts to 0 and
+// would pass for a point of voxel 0: it is out of range too (the reference puts it at INT_MIN, which no table here can hold)
+__device__ __forceinline__ unsigned long long voxel_key_of(double x, double y, double z, double vs, bool &ok, int32_t &vx, int32_t &vy, int32_t &vz) {
+    const double fx = floor(x / vs), fy = floor(y / vs), fz = floor(z / vs);
+    vx = static_cast<int32_t>(fx), vy = static_cast<int32_t>(fy), vz = static_cast<int32_t>(fz);
+    const unsigned long long key = pack_voxel21(vx, vy, vz, ok);
+    if (fx != fx || fy != fy || fz != fz) ok = false;
+    return key;
+}
 // One point's claim: `key` (kEmptyVoxelKey: this lane has no point) finds / takes its voxel's slot by linear probing from the
 // reference's ideal bucket and lowers the slot's winner to `index`.  The lanes of a wave hold CONSECUTIVE, ASCENDING indices.
 // `overflow` / `overflow_tag` (the fused chain's first level, whose table size is a guess): a probe longer than kClaimProbeLimit
@@ -201,11 +210,12 @@ __device__ __forceinline__ void claim_voxel(unsigned long long *keys, uint32_t *
     // and every one of them would hammer the same two words with atomics - the kernel's tail, up to 0.6 ms on some frames.  Only
     // the FIRST lane of a run inside a wave goes on: it has the lowest index of the run, which is all atomicMin would keep.
     const unsigned long long prev = __shfl_up(key, 1, 64);
-    if (key == kEmptyVoxelKey || ((threadIdx.x & 63) != 0 && prev == key)) return;
-    if (!ok) {
+    if (key == kEmptyVoxelKey) return;
+    if (!ok) {  // (before the run test: pack_voxel21 masks, so a voxel 2^21 beyond an in-range one carries that one's key)
         *error = 1u;
         return;
     }
+    if ((threadIdx.x & 63) != 0 && prev == key) return;
     uint32_t slot = reference_voxel_hash(vx, vy, vz) & mask;
     for (uint32_t probes = 0;; ++probes) {
         const unsigned long long seen = atomicCAS(keys + slot, kEmptyVoxelKey, key);
@@ -225,12 +235,9 @@ static __global__ __launch_bounds__(256) void k_downsample_claim(const Downsampl
     if (i == 0 && !p.probe_max_sticky) *p.probe_max = 0u;  // (the replay kernel, which raises it, runs after this one: no separate memset per call)
     const uint32_t n = ds_count(p), mask = ds_mask(p, n);
     const bool in_range = i < n;
-    const double vs = p.voxel_size;
     int32_t vx = 0, vy = 0, vz = 0;
-    if (in_range)
-        vx = static_cast<int32_t>(floor(p.in[3 * i] / vs)), vy = static_cast<int32_t>(floor(p.in[3 * i + 1] / vs)), vz = static_cast<int32_t>(floor(p.in[3 * i + 2] / vs));
     bool ok = true;
-    const unsigned long long key = in_range ? pack_voxel21(vx, vy, vz, ok) : kEmptyVoxelKey;
+    const unsigned long long key = in_range ? voxel_key_of(p.in[3 * i], p.in[3 * i + 1], p.in[3 * i + 2], p.voxel_size, ok, vx, vy, vz) : kEmptyVoxelKey;
     claim_voxel(p.keys, p.min_index, mask, key, ok, vx, vy, vz, i, p.error);
 }
 
@@ -349,10 +356,6 @@ __device__ __forceinline__ uint32_t tile_position(bool flagged, uint32_t offset)
     uint32_t pos = offset + static_cast<uint32_t>(__popcll(ballot & ((1ull << lane) - 1ull)));
     for (int w = 0; w < wave; ++w) pos += s_wave[w];
     return pos;
-}
-__device__ __forceinline__ unsigned long long voxel_key_of(double x, double y, double z, double vs, bool &ok, int32_t &vx, int32_t &vy, int32_t &vz) {
-    vx = static_cast<int32_t>(floor(x / vs)), vy = static_cast<int32_t>(floor(y / vs)), vz = static_cast<int32_t>(floor(z / vs));
-    return pack_voxel21(vx, vy, vz, ok);
 }
 
 static __global__ __launch_bounds__(256) void k_frame_pre(const FrameParams f) {

@@ -50,6 +50,10 @@ struct kicp_pre {
     uint32_t chain_seq = 0;
     unsigned long long ingest_seq = 0;
     unsigned long long spec_misses = 0, fused_frames = 0;
+    // how the last fused frame was laid out and how often this handle launched k_scan_blocks (kicp_pre_get_option "point_tiles" ..
+    // "scan_launches", include/kicp.h): host-side bookkeeping only
+    uint32_t last_point_tiles = 0, last_l1_tiles = 0, last_l2_workgroups = 0, last_l2_tiles = 0;
+    unsigned long long scan_launches = 0;
     bool fused = [] {
         const char *e = std::getenv("KICP_PRE_FUSED");
         return !(e && *e == '0');
@@ -174,12 +178,17 @@ int pre_finish(kicp_pre *p, int dst, size_t *out_n) {
     if (out_n) *out_n = misc[0];
     return KICP_OK;
 }
+// exclusive scan of the first `nblocks` block counts in place, their sum to *total (grids beyond kFusedScanBlocks workgroups)
+void scan_blocks(kicp_pre *p, uint32_t nblocks, uint32_t *total) {
+    hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(1024), 0, p->stream, p->d_block_counts.get(), nblocks, total);
+    ++p->scan_launches;
+}
 // flags + block counts are in place: scan, compact staged -> buffer dst, return the survivor count
 int pre_compact(kicp_pre *p, const double *staged, size_t n, int dst, size_t *out_n) {
     const uint32_t grid = static_cast<uint32_t>((n + 255) / 256);
     if (int rc = pre_ensure_buf(p, dst, n)) return rc;
     const int raw = grid <= kFusedScanBlocks ? 1 : 0;  // (frame-sized grids: every workgroup adds up the counts before it itself)
-    if (!raw) hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(1024), 0, p->stream, p->d_block_counts.get(), grid, p->d_misc.get());
+    if (!raw) scan_blocks(p, grid, p->d_misc.get());
     hipLaunchKernelGGL(k_compact, dim3(grid), dim3(256), 0, p->stream, staged, static_cast<const uint32_t *>(p->d_flags.get()), static_cast<const uint32_t *>(p->d_block_counts.get()), raw,
                        p->d_misc.get(), static_cast<uint32_t>(n), p->buf[dst].get());
     HIP_TRY(hipGetLastError());
@@ -595,7 +604,7 @@ int kicp_pre_voxel_downsample(kicp_pre *p, int src, double voxel_size, int dst, 
     hipLaunchKernelGGL(k_downsample_claim, dim3(grid), dim3(256), 0, p->stream, dp);
     hipLaunchKernelGGL(k_downsample_replay, dim3(sgrid), dim3(256), 0, p->stream, dp);
     const int raw = sgrid <= kFusedScanBlocks ? 1 : 0;
-    if (!raw) hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(1024), 0, p->stream, p->d_block_counts.get(), sgrid, p->d_misc.get());
+    if (!raw) scan_blocks(p, sgrid, p->d_misc.get());
     hipLaunchKernelGGL(k_downsample_gather, dim3(sgrid), dim3(256), 0, p->stream, dp, static_cast<const uint32_t *>(p->d_block_counts.get()), raw, p->d_misc.get(), p->buf[dst].get());
     HIP_TRY(hipGetLastError());
     const int rc = pre_finish(p, dst, out_n);
@@ -776,6 +785,8 @@ static int pre_frame_chain(kicp_pre *p, size_t n_in, bool do_deskew, const doubl
         p->src_f32 = f32;
         p->src_seq = f.seq;
         p->spec_tiles_b = misc[5] ? static_cast<uint32_t>(reference_bucket_count(misc[5]) + 255) / 256u : 1u;
+        p->last_point_tiles = grid, p->last_l1_tiles = f.tiles_spec, p->last_l2_workgroups = grid_b;
+        p->last_l2_tiles = misc[5] ? ((reference_bucket_count_u32(misc[5]) - 1u) >> 8) + 1u : 0u;  // (the kernels' `tiles`, from the returned n1)
         if (unfused_tail) {  // a guess was wrong: the tables hold claims made under the wrong size; buffer 0 and its count are in place
             ++p->spec_misses;
             HIP_TRY(hipMemsetAsync(p->d_table.get(), 0xFF, p->table_slots * 20, p->stream));
@@ -784,7 +795,7 @@ static int pre_frame_chain(kicp_pre *p, size_t n_in, bool do_deskew, const doubl
     } else {
         hipLaunchKernelGGL(k_preprocess, dim3(grid), dim3(256), 0, p->stream, pp);
         const int raw_c = grid <= kFusedScanBlocks ? 1 : 0;
-        if (!raw_c) hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(1024), 0, p->stream, p->d_block_counts.get(), grid, cnt + 0);
+        if (!raw_c) scan_blocks(p, grid, cnt + 0);
         hipLaunchKernelGGL(k_compact, dim3(grid), dim3(256), 0, p->stream, static_cast<const double *>(p->d_staged.get()), static_cast<const uint32_t *>(p->d_flags.get()),
                            static_cast<const uint32_t *>(p->d_block_counts.get()), raw_c, cnt + 0, static_cast<uint32_t>(n_in), p->buf[0].get());
         if (int rc = mark_frame_ready()) return rc;
@@ -802,7 +813,7 @@ static int pre_frame_chain(kicp_pre *p, size_t n_in, bool do_deskew, const doubl
             dp.probe_max_sticky = stage == 0 ? nullptr : dp.probe_max;
             hipLaunchKernelGGL(k_downsample_claim, dim3(grid), dim3(256), 0, p->stream, dp);
             hipLaunchKernelGGL(k_downsample_replay, dim3(sgrid), dim3(256), 0, p->stream, dp);
-            if (!raw_g) hipLaunchKernelGGL(k_scan_blocks, dim3(1), dim3(1024), 0, p->stream, p->d_block_counts.get(), sgrid, cnt + stage + 1);
+            if (!raw_g) scan_blocks(p, sgrid, cnt + stage + 1);
             hipLaunchKernelGGL(k_downsample_gather, dim3(sgrid), dim3(256), 0, p->stream, dp, static_cast<const uint32_t *>(p->d_block_counts.get()), raw_g, cnt + stage + 1,
                                p->buf[stage + 1].get());
         }
@@ -899,6 +910,11 @@ double kicp_pre_get_option(const kicp_pre *p, const char *name) {
     if (n == "guess") return static_cast<double>(p->spec_n0);
     if (n == "fused_frames") return static_cast<double>(p->fused_frames);
     if (n == "guess_misses") return static_cast<double>(p->spec_misses);
+    if (n == "point_tiles") return static_cast<double>(p->last_point_tiles);
+    if (n == "l1_tiles") return static_cast<double>(p->last_l1_tiles);
+    if (n == "l2_workgroups") return static_cast<double>(p->last_l2_workgroups);
+    if (n == "l2_tiles") return static_cast<double>(p->last_l2_tiles);
+    if (n == "scan_launches") return static_cast<double>(p->scan_launches);
     for (int slot = 0; slot < 2; ++slot) {  // "ingest_<counter>" / "ahead_<counter>": the last ingest_run of the slot
         const std::string prefix = slot ? "ahead_" : "ingest_";
         if (n.compare(0, prefix.size(), prefix) != 0) continue;
