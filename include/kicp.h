@@ -793,6 +793,67 @@ int kicp_frontiers_from_occupancy(const signed char *occupancy, unsigned int wid
 int kicp_grid_frontiers(const kicp_grid *grid, const kicp_frontier_config *config, int use_plan, unsigned long long *out_rows, size_t cap_rows,
                         size_t *out_n, unsigned int *out_labels, size_t cap_labels);
 
+/* ---- what the robot would see from there: the unknown cells a sensor reveals from candidate viewpoints (kicp_grid.hip) ------------------
+ * The frontiers above say how far each frontier is; these entries say what lies behind it.  An exploration planner that goes past
+ * "nearest frontier" scores candidate viewpoints by information gain: it casts the sensor's rays from the candidate over the map, stops
+ * them at obstacles and counts the unknown cells they cross.  Everything below is integer and the result is unique: the host and the
+ * device entry return equal arrays.
+ *
+ * CLASSES.  Those of the frontier section: with v the readout of a cell at `min_observations`, the cell is OCCUPIED when
+ * (double)v > occupied_thresh * 100.0, UNKNOWN when v < 0, and CLEAR otherwise.  Cells outside the grid are nothing.
+ *
+ * VIEWPOINT.  A cell index y * width + x, an unsigned int below width * height: word 9 (best_cell) of a frontier's row can be passed
+ * as it is.
+ *
+ * RAYS.  Let R = range_cells, 1 <= R <= 361.  From a viewpoint (vx, vy) whose cell is CLEAR, 8 R rays are walked, one to each offset
+ * (dx, dy) with max(|dx|, |dy|) == R.  Ray (dx, dy) visits the offsets (ox, oy) of steps k = 1, 2, .., R in that order, by the
+ * integrator's own walk with m = R:  ox = sign(dx) * ((2 k |dx| + R) / (2 R)),  oy = sign(dy) * ((2 k |dy| + R) / (2 R)),  integer
+ * divisions.  k = 0, the viewpoint's own cell, is not visited.  At each step these tests apply IN THIS ORDER:
+ *   1. ox * ox + oy * oy > R * R: the ray ends and nothing is counted - the range is a disc;
+ *   2. the cell (vx + ox, vy + oy) lies outside the grid: the ray ends and counts as LEFT;
+ *   3. the cell is OCCUPIED: the ray ends and counts as BLOCKED; the cell is not seen;
+ *   4. the cell is UNKNOWN: it is SEEN and the ray goes on - unknown space does not stop a ray, the optimistic sensor model that
+ *      exploration planners use;
+ *   5. the cell is CLEAR: the ray goes on.
+ * A ray that completes step k = R ends and counts as neither LEFT nor BLOCKED.  On an empty plane the rays visit every offset of the
+ * disc except (0, 0), about 2.2 visits per cell of it (70 096 at R = 100).
+ *
+ * ROW.  Per viewpoint KICP_GAIN_WORDS = 4 words of unsigned int, in the order of the viewpoints (duplicates give duplicate rows):
+ *   0  the number of DISTINCT cells SEEN: a cell that several rays cross counts once
+ *   1  rays BLOCKED
+ *   2  rays LEFT
+ *   3  the class of the viewpoint's own cell: 0 clear, 1 unknown, 2 occupied
+ * When word 3 is not 0 no ray is walked and words 0 to 2 are 0.
+ *
+ * EXAMPLE.  Rows top down with y = 0 first, x left to right; 0 clear, 1 unknown, 2 occupied:
+ *      111111111        viewpoint (x, y)   R = 1     R = 2     R = 3      R = 4
+ *      100000211        (3, 3)             0,0,0,0   0,3,0,0   3,5,0,0    15,7,3,0
+ *      100020111        (1, 1)             2,0,0,0   5,0,2,0   7,1,13,0   9,2,21,0
+ *      100000011        (7, 5)             2,0,0,0   6,0,2,0   9,0,13,0   13,0,21,0
+ *      120000001        (4, 2)             0,0,0,2   0,0,0,2   0,0,0,2    0,0,0,2
+ *      100000001        (0, 0)             0,0,0,1   0,0,0,1   0,0,0,1    0,0,0,1
+ *      111111111
+ *
+ * ENTRIES.  kicp_gain_from_occupancy is pure host code over a readout (width x height values as kicp_grid_occupancy writes them;
+ * min_observations is only checked) and needs no GPU; width or height 0 is KICP_ERR_ARG, width * height above 2^28 KICP_ERR_CAPACITY.
+ * kicp_grid_gain works on the counters where they are, in HBM, on the grid's stream (one workgroup per viewpoint, the window's bit
+ * plane in LDS: that is where the limit of 361 cells comes from) and returns after the rows have arrived.  It writes neither the
+ * counters nor the plan: kicp_grid_has_plan, the plan's words and kicp_grid_counts read the same afterwards.
+ * n_views == 0 is KICP_OK and writes nothing.  cap_out is the number of words `out` holds and must be 4 * n_views -
+ * kicp_grid_score_arcs's convention.  For both entries a null handle / occupancy or config, null views or out with n_views > 0,
+ * min_observations < 1, an occupied_thresh outside [0, 1], range_cells outside 1 .. 361, a cap_out other than 4 * n_views and a
+ * viewpoint >= width * height - checked on the host before anything is launched; the message names the first bad one - are
+ * KICP_ERR_ARG with nothing written; more than 2^24 viewpoints in one call are KICP_ERR_CAPACITY. */
+typedef struct kicp_gain_config {
+    unsigned int min_observations; /* >= 1 */
+    double occupied_thresh;        /* in [0, 1] */
+    unsigned int range_cells;      /* R, 1 .. 361 */
+} kicp_gain_config;
+#define KICP_GAIN_WORDS 4
+int kicp_gain_from_occupancy(const signed char *occupancy, unsigned int width, unsigned int height, const kicp_gain_config *config, const unsigned int *views,
+                             size_t n_views, unsigned int *out /* n_views x 4 */, size_t cap_out);
+int kicp_grid_gain(const kicp_grid *grid, const kicp_gain_config *config, const unsigned int *views, size_t n_views, unsigned int *out, size_t cap_out);
+
 /* ---- map points the new frame sees through: a cube-map depth test (kicp_view.hip) ----------------------------------------------------
  * The local map loses points by distance only (RemovePointsFarFromLocation); whatever stood in view for one frame - a person crossing,
  * a forklift, a door leaf - stays until the robot is max_range away.  A kicp_view holds a depth image of ONE frame, and

@@ -82,6 +82,12 @@ class FrontierConfig(C.Structure):
     _fields_ = [("min_observations", C.c_uint), ("occupied_thresh", C.c_double), ("min_size", C.c_uint)]
 
 
+class GainConfig(C.Structure):
+    """kicp_gain_config: the readout's min_observations, the threshold above which a cell is occupied, and the sensor's range R in cells
+    (1 .. 361)"""
+    _fields_ = [("min_observations", C.c_uint), ("occupied_thresh", C.c_double), ("range_cells", C.c_uint)]
+
+
 class ViewConfig(C.Structure):
     """kicp_view_config: a cube map of res x res pixels per face; the verdict looks at (2 window + 1)^2 pixels, needs min_rays returns
     among them and a gap of more than margin + margin_per_metre * depth; max_ray bounds the (Chebyshev) depth on both sides"""
@@ -215,6 +221,8 @@ _SIGNATURES = {
                                                 C.POINTER(C.c_size_t), C.POINTER(C.c_uint), C.c_size_t]),
     "kicp_grid_frontiers": (C.c_int, [C.c_void_p, C.POINTER(FrontierConfig), C.c_int, C.POINTER(C.c_ulonglong), C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint),
                                       C.c_size_t]),
+    "kicp_gain_from_occupancy": (C.c_int, [C.POINTER(C.c_byte), C.c_uint, C.c_uint, C.POINTER(GainConfig), C.POINTER(C.c_uint), C.c_size_t, C.POINTER(C.c_uint), C.c_size_t]),
+    "kicp_grid_gain": (C.c_int, [C.c_void_p, C.POINTER(GainConfig), C.POINTER(C.c_uint), C.c_size_t, C.POINTER(C.c_uint), C.c_size_t]),
     "kicp_planar_grid": (C.c_size_t,[_dp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _dp, C.c_size_t]),
     "kicp_map_save_pcd": (C.c_int, [C.c_void_p, C.c_char_p]),
     "kicp_map_load_pcd": (C.c_int, [C.c_char_p, C.c_double, C.c_double, C.c_uint, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
@@ -751,6 +759,48 @@ def frontiers_from_occupancy(occupancy, min_observations=1, occupied_thresh=0.65
                           occ.shape, return_labels)
 
 
+GAIN_WORDS = 4
+
+
+def _gain_config(range_cells, min_observations, occupied_thresh):
+    args = [int(min_observations), int(range_cells)]
+    if min(args) < 0 or max(args) > 0xFFFFFFFF:
+        raise KicpError(KICP_ERR_ARG, "min_observations and range_cells are unsigned 32-bit integers, at least 1")
+    return GainConfig(args[0], float(occupied_thresh), args[1])
+
+
+def _gain_views(views, width, height):
+    """viewpoints as cell indices y * width + x (any shape but (N, 2): flattened) or as an (N, 2) array of (x, y) -> uint32 (N,)"""
+    v = np.asarray(views)
+    if v.size and v.dtype.kind not in "iu":
+        raise KicpError(KICP_ERR_ARG, "viewpoints are integers: cell indices, or an (N, 2) array of (x, y)")
+    v = v.astype(np.int64)
+    if v.ndim == 2 and v.shape[1] == 2:
+        if v.size and not ((v >= 0).all() and (v[:, 0] < width).all() and (v[:, 1] < height).all()):
+            bad = int(np.flatnonzero((v < 0).any(axis=1) | (v[:, 0] >= width) | (v[:, 1] >= height))[0])
+            raise KicpError(KICP_ERR_ARG, "viewpoint %d is (%d, %d), outside the grid of %d x %d cells" % (bad, v[bad, 0], v[bad, 1], width, height))
+        v = v[:, 1] * width + v[:, 0]
+    v = v.reshape(-1)
+    if v.size and (v.min() < 0 or v.max() > 0xFFFFFFFF):
+        raise KicpError(KICP_ERR_ARG, "viewpoints are cell indices, unsigned 32-bit integers")
+    return np.ascontiguousarray(v, dtype=np.uint32)
+
+
+def gain_from_occupancy(occupancy, views, range_cells, min_observations=1, occupied_thresh=0.65):
+    """kicp_gain_from_occupancy: what a sensor of range_cells' range (1 .. 361) would see from each viewpoint of a readout shaped
+    (height, width): from a clear viewpoint 8 R rays are walked to the cells at Chebyshev distance R, cut to the disc of radius R; a ray
+    ends where it leaves the grid or at an occupied cell and passes through unknown cells, which it thereby sees (include/kicp.h states
+    the walk).  views: cell indices y * width + x - word 9 of a frontier's row - or an (N, 2) array of (x, y) -> uint32 (N, 4): the
+    distinct unknown cells seen, the rays blocked, the rays that left the grid, and the class of the viewpoint's own cell (0 clear,
+    1 unknown, 2 occupied: then the other three are 0).  Pure host code: needs no GPU."""
+    occ = _occupancy_2d(occupancy)
+    cfg = _gain_config(range_cells, min_observations, occupied_thresh)
+    v = _gain_views(views, occ.shape[1], occ.shape[0])
+    out = np.empty((len(v), GAIN_WORDS), dtype=np.uint32)
+    _check(lib().kicp_gain_from_occupancy(occ.ctypes.data_as(C.POINTER(C.c_byte)), occ.shape[1], occ.shape[0], C.byref(cfg), _u32(v), len(v), _u32(out), out.size))
+    return out
+
+
 class OccupancyGrid:
     """kicp_grid: a world-aligned 2-D grid of (hits, misses) counters a mapping run draws frame by frame - every used point's cell is
     hit, the cells its ray from the sensor crosses are missed, once per cell per frame (include/kicp.h states the exact semantics).
@@ -887,6 +937,16 @@ class OccupancyGrid:
         cfg = _frontier_config(min_observations, occupied_thresh, min_size)
         return _frontier_call(lambda rp, cap, n, lp, lcap: lib().kicp_grid_frontiers(self._h, C.byref(cfg), 1 if use_plan else 0, rp, cap, n, lp, lcap),
                               (self.height, self.width), return_labels)
+
+    def gain(self, views, range_cells, min_observations=1, occupied_thresh=0.65):
+        """kicp_grid_gain: on the GPU, gain_from_occupancy's result on the counters where they are -> uint32 (N, 4): per viewpoint (a cell
+        index, such as frontiers(use_plan=True)[:, 9], or (x, y)) the distinct unknown cells a sensor of range_cells' range would see, the
+        rays blocked, the rays that left the grid and the class of the viewpoint's cell.  Neither the counters nor the plan are changed."""
+        cfg = _gain_config(range_cells, min_observations, occupied_thresh)
+        v = _gain_views(views, self.width, self.height)
+        out = np.empty((len(v), GAIN_WORDS), dtype=np.uint32)
+        _check(lib().kicp_grid_gain(self._h, C.byref(cfg), _u32(v), len(v), _u32(out), out.size))
+        return out
 
     def last_window(self):
         """kicp_grid_last_window: (x0, y0, w, h) of the last integrated frame's window clipped to the grid; w = h = 0 when it lies

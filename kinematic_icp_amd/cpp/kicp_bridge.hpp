@@ -196,6 +196,16 @@ inline Frontier frontier_of_row(const unsigned long long *row) {
     f.best_potential = static_cast<uint32_t>(row[8]), f.best_cell = static_cast<uint32_t>(row[9]);
     return f;
 }
+// GainConfig and Gain go with KinematicICP::GridGain (kicp.h kicp_grid_gain): the classes' thresholds and the sensor's range in cells,
+// and what one candidate viewpoint would see - the four words of its row by name.
+using GainConfig = kicp_gain_config;
+struct Gain {
+    uint32_t seen = 0;        // distinct unknown cells the rays cross
+    uint32_t blocked = 0;     // rays that end at an occupied cell
+    uint32_t left = 0;        // rays that leave the grid
+    uint32_t view_class = 0;  // the viewpoint's own cell: 0 clear, 1 unknown, 2 occupied - then no ray was walked
+};
+inline Gain gain_of_row(const unsigned int *row) { return Gain{row[0], row[1], row[2], row[3]}; }
 inline std::shared_ptr<kicp_grid> make_grid(const GridConfig &config, int device = -1) {
     kicp_grid *grid = nullptr;
     check(kicp_grid_create(&config, device < 0 ? default_device() : device, &grid), "kicp_bridge::make_grid");

@@ -430,6 +430,19 @@ public:
         frontiers.resize(n);
         for (size_t i = 0; i < n; ++i) frontiers[i] = kicp_bridge::frontier_of_row(rows.data() + i * KICP_FRONTIER_WORDS);
     }
+    // What the robot would see from there (kicp.h kicp_grid_gain): per candidate viewpoint - a cell index y * width + x, such as the
+    // best_cell of GridFrontiers' frontiers under a plan - the distinct unknown cells a sensor of config.range_cells' range (1 .. 361)
+    // would see, on the GPU from the counters: 8 R rays per viewpoint, cut to the disc, stopped by occupied cells and by the grid's
+    // edge, not by unknown ones.  An exploration node ranks its frontiers by out[i].seen against best_potential, the cost of driving
+    // there; the weighting is the caller's.  Neither the counters nor the plan are changed.  Throws without a grid, and for a cell
+    // index outside it.
+    void GridGain(const std::vector<unsigned int> &cells, const kicp_bridge::GainConfig &config, std::vector<kicp_bridge::Gain> &out) const {
+        const kicp_grid *grid = RequireGrid("GridGain");
+        std::vector<unsigned int> rows(cells.size() * static_cast<size_t>(KICP_GAIN_WORDS));
+        kicp_bridge::check(kicp_grid_gain(grid, &config, cells.data(), cells.size(), rows.data(), rows.size()), "GridGain");
+        out.resize(cells.size());
+        for (size_t i = 0; i < cells.size(); ++i) out[i] = kicp_bridge::gain_of_row(rows.data() + i * KICP_GAIN_WORDS);
+    }
     // the window of the last integrated frame clipped to the grid; empty() when it lies outside, and before any frame
     kicp_bridge::GridRect GridLastWindow() const {
         kicp_bridge::GridRect r;

@@ -10,13 +10,16 @@
 // arithmetic: kicp_arcs_host.hpp; its host twin kicp_score_arcs_from_plan and the helpers kicp_plan_q, kicp_arc_steps,
 // kicp_footprint_box and kicp_arcs_best are here as well).  The exploration frontiers of the counters - the free cells that border
 // unknown space, grouped and ranked by that plan - are kicp_grid_frontiers (kernels: kicp_front.hpp, arithmetic: kicp_front_host.hpp;
-// host twin: kicp_frontiers_from_occupancy).
+// host twin: kicp_frontiers_from_occupancy).  What a sensor would see of the unknown cells from candidate viewpoints - such as those
+// frontiers' best cells - is kicp_grid_gain (kernels: kicp_gain.hpp, arithmetic: kicp_gain_host.hpp; host twin:
+// kicp_gain_from_occupancy).
 #include <cerrno>
 #include <memory>
 
 #include "kicp_arcs.hpp"
 #include "kicp_clear.hpp"
 #include "kicp_front.hpp"
+#include "kicp_gain.hpp"
 #include "kicp_grid.hpp"
 #include "kicp_internal.hpp"
 #include "kicp_nav.hpp"
@@ -58,6 +61,9 @@ struct kicp_grid {
     DevBuf<unsigned long long> d_front_rows;                       // count land
     PinnedBuf<uint32_t> h_front_ctr;
     std::vector<unsigned long long> h_front_rows;
+    DevBuf<uint8_t> d_gain_classes;      // kicp_grid_gain: a byte per cell, the viewpoints' upload, their rows and the pinned buffer the
+    DevBuf<uint32_t> d_gain_views, d_gain_out;  // rows come back through
+    PinnedBuf<uint32_t> h_gain_out;
     HostStage stage;
     ~kicp_grid() {
         if (stream) (void)hipStreamSynchronize(stream), (void)hipStreamDestroy(stream);
@@ -273,6 +279,21 @@ int check_front_args(const kicp_frontier_config *cfg, size_t cells, const unsign
 int front_result(size_t n, size_t cap_rows, size_t *out_n) {
     *out_n = n;
     if (n > cap_rows) return fail(KICP_ERR_CAPACITY, std::to_string(n) + " frontiers pass the filter, cap_rows is " + std::to_string(cap_rows));
+    return KICP_OK;
+}
+constexpr size_t kGainMaxViews = 1u << 24;  // viewpoints per call: one workgroup each
+// what the two gain entries share: the configuration, the viewpoints - each a cell index below `cells` - and the output
+int check_gain_args(const kicp_gain_config *cfg, size_t cells, const unsigned int *views, size_t n_views, const unsigned int *out, size_t cap_out, GainParams &p) {
+    if (cfg->min_observations < 1u) return fail(KICP_ERR_ARG, "min_observations must be at least 1");
+    if (!(0.0 <= cfg->occupied_thresh && cfg->occupied_thresh <= 1.0)) return fail(KICP_ERR_ARG, "occupied_thresh must lie in [0, 1]");
+    if (cfg->range_cells < 1u || cfg->range_cells > kGainMaxRange) return fail(KICP_ERR_ARG, "range_cells must lie in 1 .. " + std::to_string(kGainMaxRange));
+    if (n_views > kGainMaxViews) return fail(KICP_ERR_CAPACITY, "n_views = " + std::to_string(n_views) + " (limit 2^24 = " + std::to_string(kGainMaxViews) + ")");
+    if (n_views && (!views || !out)) return fail(KICP_ERR_ARG, "views and out may be null only when n_views is 0");
+    if (cap_out != kGainWords * n_views) return fail(KICP_ERR_ARG, "cap_out must be 4 * n_views = " + std::to_string(kGainWords * n_views));
+    for (size_t i = 0; i < n_views; ++i)
+        if (views[i] >= cells)
+            return fail(KICP_ERR_ARG, "viewpoint " + std::to_string(i) + " is cell " + std::to_string(views[i]) + ", outside the grid's " + std::to_string(cells) + " cells");
+    p = GainParams{cfg->min_observations, clear_source_min(cfg->occupied_thresh), cfg->range_cells};
     return KICP_OK;
 }
 }  // namespace
@@ -639,6 +660,42 @@ int kicp_grid_frontiers(const kicp_grid *cgrid, const kicp_frontier_config *cfg,
     HIP_TRY(hipMemcpyAsync(grid->h_front_rows.data(), grid->d_front_rows.get(), grid->h_front_rows.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return front_result(front_emit(grid->h_front_rows.data(), n_rows, cfg->min_size, out_rows, cap_rows), cap_rows, out_n);
+}
+int kicp_gain_from_occupancy(const signed char *occupancy, unsigned int width, unsigned int height, const kicp_gain_config *cfg, const unsigned int *views, size_t n_views,
+                             unsigned int *out, size_t cap_out) {
+    if (!occupancy || !cfg) return fail(KICP_ERR_ARG, "null argument");
+    if (width == 0 || height == 0) return fail(KICP_ERR_ARG, "width and height must be at least 1");
+    if (static_cast<unsigned long long>(width) * height > kGridMaxCells) return fail(KICP_ERR_CAPACITY, "width * height exceeds 2^28 = " + std::to_string(kGridMaxCells));
+    GainParams p;
+    if (int rc = check_gain_args(cfg, static_cast<size_t>(width) * height, views, n_views, out, cap_out, p)) return rc;
+    if (n_views) gain_host::gain(reinterpret_cast<const int8_t *>(occupancy), width, height, p.source_min, p.range, views, n_views, out);
+    return KICP_OK;
+}
+int kicp_grid_gain(const kicp_grid *cgrid, const kicp_gain_config *cfg, const unsigned int *views, size_t n_views, unsigned int *out, size_t cap_out) {
+    KICP_TRACE_CALL();
+    if (!cgrid || !cfg) return fail(KICP_ERR_ARG, "null argument");
+    GainParams p;
+    if (int rc = check_gain_args(cfg, cgrid->cells, views, n_views, out, cap_out, p)) return rc;
+    if (n_views == 0u) return KICP_OK;
+    kicp_grid *grid = const_cast<kicp_grid *>(cgrid);  // logically const: the buffers are scratch, the counters and the plan are only read
+    if (int rc = set_device(grid->device)) return rc;
+    hipStream_t st = grid->stream;
+    const uint32_t cells = static_cast<uint32_t>(grid->cells), n = static_cast<uint32_t>(n_views);
+    // the buffers grow while the stream is idle: every entry of the handle drains it
+    if (int rc = grid->d_gain_classes.reserve(cells)) return rc;
+    if (int rc = grid->d_gain_views.reserve(n_views)) return rc;
+    if (int rc = grid->d_gain_out.reserve(kGainWords * n_views)) return rc;
+    if (int rc = grid->h_gain_out.reserve(kGainWords * n_views, hipHostMallocDefault, false)) return rc;
+    HIP_TRY(hipMemcpyAsync(grid->d_gain_views.get(), views, n_views * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_gain_classes, dim3((cells + kGainBlock - 1u) / kGainBlock), dim3(kGainBlock), 0, st, grid->d_counts.get(), cells, p.min_observations, p.source_min,
+                       grid->d_gain_classes.get());
+    hipLaunchKernelGGL(k_gain_rays, dim3(n), dim3(kGainBlock), gain_lds_bytes(p.range), st, grid->d_gain_classes.get(), grid->cfg.width, grid->cfg.height, p.range,
+                       grid->d_gain_views.get(), grid->d_gain_out.get());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(grid->h_gain_out.get(), grid->d_gain_out.get(), kGainWords * n_views * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    std::memcpy(out, grid->h_gain_out.get(), kGainWords * n_views * sizeof(uint32_t));
+    return KICP_OK;
 }
 int kicp_grid_last_window(const kicp_grid *grid, unsigned int *x0, unsigned int *y0, unsigned int *w, unsigned int *h) {
     if (!grid || !x0 || !y0 || !w || !h) return fail(KICP_ERR_ARG, "null argument");
