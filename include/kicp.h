@@ -546,7 +546,7 @@ int kicp_grid_save_map(const kicp_grid *grid, const char *prefix, unsigned int m
 int kicp_grid_write_map(const char *prefix, const signed char *occupancy, unsigned int width, unsigned int height, double cell, double origin_x,
                         double origin_y, double occupied_thresh, double free_thresh);
 
-/* ---- what a planner plans on: the clearance of every cell and a Nav2-style costmap of the grid (kicp_grid.hip) -------------------------
+/* ---- what a planner plans on: the clearance of every cell and a Nav2-style costmap of the grid (kicp_grid_plan.hip) --------------------
  * Everything below is exact and integer: squared cell distances, and a lookup table for the cost.
  *
  * CLASSES.  With v the readout of a cell at `min_observations` (above), a cell is a SOURCE when (double)v > occupied_thresh * 100.0 -
@@ -598,7 +598,7 @@ int kicp_grid_costmap_from_occupancy(const signed char *occupancy, unsigned int 
 int kicp_grid_cost_table_nav2(double cell, int radius_cells, double inscribed_radius, double cost_scaling_factor, unsigned char *table, size_t cap);
 int kicp_grid_last_window(const kicp_grid *grid, unsigned int *x0, unsigned int *y0, unsigned int *w, unsigned int *h);
 
-/* ---- from the costmap to a path: the cost-to-go field a planner spreads from its goal, and the path down it (kicp_grid.hip) -------------
+/* ---- from the costmap to a path: the cost-to-go field a planner spreads from its goal, and the path down it (kicp_grid_plan.hip) --------
  * What Nav2's NavFn calls the potential.  Everything below is exact and integer; the field is the unique least fixed point of its
  * recurrence, so the host and the device entries return equal arrays.
  *
@@ -661,7 +661,7 @@ int kicp_grid_potential(const kicp_grid *grid, const kicp_grid_clearance_config 
                         const unsigned char weight[256], const kicp_plan_config *config, const unsigned int *goals_xy, size_t n_goals, unsigned int *out,
                         size_t cap, unsigned long long out_stats[4]);
 
-/* ---- from the field to a command: a fan of arc trajectories scored on the costmap and the potential (kicp_grid.hip) ------------------
+/* ---- from the field to a command: a fan of arc trajectories scored on the costmap and the potential (kicp_grid_arcs.hip) -------------
  * What a local planner (DWA / DWB, MPPI) does each control cycle: roll candidate commands forward as arcs, lay the robot's footprint on
  * the costmap at every pose, drop the arcs that collide, rank the rest by how far down the cost-to-go field they end.  Everything below
  * is exact: the only floating-point operations are fp64 + - * / and floor, every operation rounded on its own (the library is built
@@ -734,7 +734,7 @@ int kicp_grid_has_plan(const kicp_grid *grid); /* 1 when the handle holds a vali
 int kicp_grid_score_arcs(const kicp_grid *grid, const double start[4], const double *arcs, size_t n_arcs, unsigned int n_steps, const double *footprint_xy,
                          size_t n_samples, unsigned int *out, size_t cap);
 
-/* ---- where to go while mapping: the exploration frontiers of the grid, ranked by the plan (kicp_grid.hip) ------------------------------
+/* ---- where to go while mapping: the exploration frontiers of the grid, ranked by the plan (kicp_grid_explore.hip) ----------------------
  * A robot that is still mapping has no goal from outside: its goal is the edge of what it has seen.  These entries find the free cells
  * that border unknown space, group them into frontiers and sum ten words per frontier - what explore_lite or a Nav2 exploration node
  * does on a copy of the map.  Everything below is integer and the result is unique: the host and the device entry return equal arrays.
@@ -793,7 +793,7 @@ int kicp_frontiers_from_occupancy(const signed char *occupancy, unsigned int wid
 int kicp_grid_frontiers(const kicp_grid *grid, const kicp_frontier_config *config, int use_plan, unsigned long long *out_rows, size_t cap_rows,
                         size_t *out_n, unsigned int *out_labels, size_t cap_labels);
 
-/* ---- what the robot would see from there: the unknown cells a sensor reveals from candidate viewpoints (kicp_grid.hip) ------------------
+/* ---- what the robot would see from there: the unknown cells a sensor reveals from candidate viewpoints (kicp_grid_explore.hip) ----------
  * The frontiers above say how far each frontier is; these entries say what lies behind it.  An exploration planner that goes past
  * "nearest frontier" scores candidate viewpoints by information gain: it casts the sensor's rays from the candidate over the map, stops
  * them at obstacles and counts the unknown cells they cross.  Everything below is integer and the result is unique: the host and the

@@ -1,4 +1,4 @@
-// kicp_arcs.hpp -- the kernel that scores a fan of arc trajectories on the grid's plan (kicp_grid_score_arcs; C-ABI: kicp_grid.hip,
+// kicp_arcs.hpp -- the kernel that scores a fan of arc trajectories on the grid's plan (kicp_grid_score_arcs; C-ABI: kicp_grid_arcs.hip,
 // arithmetic: kicp_arcs_host.hpp).  One launch on the grid's stream:
 //   k_arcs_score  one wave per arc, four arcs per 256-lane workgroup.  Every lane rolls the arc's poses forward by the same recurrence
 //                 (wave-uniform: a dozen fp64 operations a step, no lane waits for another), the lanes stride over the footprint's

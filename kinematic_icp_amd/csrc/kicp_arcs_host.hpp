@@ -1,7 +1,7 @@
 // kicp_arcs_host.hpp -- the arithmetic of scoring a fan of arc trajectories on a plan (kicp_grid_score_arcs,
 // kicp_score_arcs_from_plan; include/kicp.h states the semantics): one step of the rollout, the cell of a footprint sample, a pose's
 // weight and the loop over one arc's poses; and of the pure-host helpers around it (kicp_arc_steps, kicp_footprint_box,
-// kicp_arcs_best).  ONE text for the kernel (kicp_arcs.hpp), for the host entries (kicp_grid.hip) and for the stand-alone program that
+// kicp_arcs_best).  ONE text for the kernel (kicp_arcs.hpp), for the host entries (kicp_grid_arcs.hip) and for the stand-alone program that
 // runs arcs_host:: under sanitizers (tests/cpp/arcs_host_test.cpp).  fp64 + - * / floor only, every operation rounded on its own
 // (-ffp-contract=off); no transcendental except in arcs_host::steps, which fills the arcs on the host.
 //

@@ -1,4 +1,4 @@
-// kicp_clear.hpp -- the kernels of the grid's clearance and costmap (kicp_grid_clearance, kicp_grid_costmap; C-ABI: kicp_grid.hip,
+// kicp_clear.hpp -- the kernels of the grid's clearance and costmap (kicp_grid_clearance, kicp_grid_costmap; C-ABI: kicp_grid_plan.hip,
 // arithmetic: kicp_clear_host.hpp).  The squared distance to the nearest source within R cells is separable, so two launches on the
 // grid's stream make a result for a rectangle of cells:
 //   k_clear_columns  over the rectangle grown by R in x and clipped: one lane per column, so a wave reads 64 consecutive counter pairs

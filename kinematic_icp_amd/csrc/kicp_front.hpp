@@ -1,4 +1,4 @@
-// kicp_front.hpp -- the kernels of the grid's exploration frontiers (kicp_grid_frontiers; C-ABI: kicp_grid.hip, arithmetic:
+// kicp_front.hpp -- the kernels of the grid's exploration frontiers (kicp_grid_frontiers; C-ABI: kicp_grid_explore.hip, arithmetic:
 // kicp_front_host.hpp).  A frontier is a connected component of the frontier cells, its label the least cell index in it.  The
 // components are found by UNION-FIND, which needs no rounds and no look from the host; the launches on the grid's stream are
 //   k_front_mark     one lane per cell: the classes of the cell and of its four edge neighbours straight from the counters

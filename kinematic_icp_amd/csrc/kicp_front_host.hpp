@@ -1,7 +1,7 @@
 // kicp_front_host.hpp -- the arithmetic of the grid's exploration frontiers (kicp_grid_frontiers, kicp_frontiers_from_occupancy;
 // include/kicp.h states the semantics): the frontier-cell predicate from five classes, the update of one frontier's row by one of its
 // cells, the order and the filter of the output, and the host entry's labelling.  ONE text for the kernels (kicp_front.hpp), for the
-// entries (kicp_grid.hip) and for the stand-alone program that runs front_host:: under sanitizers (tests/cpp/front_host_test.cpp).
+// entries (kicp_grid_explore.hip) and for the stand-alone program that runs front_host:: under sanitizers (tests/cpp/front_host_test.cpp).
 // The class of a readout is kicp_clear_host.hpp's clear_class: the classes are the clearance's.  Everything is integer.
 //
 // A ROW while it is being summed has nine live words: 0 the label, 1 the size, 2 and 3 the sums of x and y, 4 .. 7 the box (min x,

@@ -1,4 +1,4 @@
-// kicp_gain.hpp -- the kernels of the grid's information gain (kicp_grid_gain; C-ABI: kicp_grid.hip, arithmetic: kicp_gain_host.hpp):
+// kicp_gain.hpp -- the kernels of the grid's information gain (kicp_grid_gain; C-ABI: kicp_grid_explore.hip, arithmetic: kicp_gain_host.hpp):
 // what a sensor of R cells' range would see of the unknown cells from each candidate viewpoint.  Two launches on the grid's stream:
 //   k_gain_classes  one lane per cell: the class of the cell from its counters (grid_readout, clear_class), one byte.  Once per call:
 //                   the ray kernel then pays one byte load per visit instead of a readout's division, and neighbouring viewpoints

@@ -1,7 +1,7 @@
 // kicp_gain_host.hpp -- the arithmetic of the grid's information gain (kicp_grid_gain, kicp_gain_from_occupancy; include/kicp.h states
 // the semantics): the 8 R perimeter offsets by a ray index, the decision at one step of one ray - the four tests in their order, on
 // top of kicp_grid_host.hpp's grid_step and kicp_clear_host.hpp's clear_class - the row of one viewpoint and the host entry's walk.
-// ONE text for the kernels (kicp_gain.hpp), for the entries (kicp_grid.hip) and for the stand-alone program that runs gain_host::
+// ONE text for the kernels (kicp_gain.hpp), for the entries (kicp_grid_explore.hip) and for the stand-alone program that runs gain_host::
 // under sanitizers (tests/cpp/gain_host_test.cpp).  Everything is integer.
 //
 // THE WINDOW of a viewpoint is the (2 R + 1)^2 square of offsets around it; offset (ox, oy) has the bit (oy + R) (2 R + 1) + ox + R of
@@ -16,6 +16,7 @@ namespace kicp {
 
 constexpr uint32_t kGainWords = 4;       // KICP_GAIN_WORDS
 constexpr uint32_t kGainMaxRange = 361;  // cells: the bit plane of the window stays within 64 KiB of LDS (65 344 bytes)
+constexpr size_t kGainMaxViews = 1u << 24;  // viewpoints per call: one workgroup each
 
 // what one step of a ray comes to: the ray goes on (over a clear cell, or over an unknown one that is thereby SEEN) or ends
 enum : uint32_t { kGainOn = 0u, kGainSeen = 1u, kGainEndDisc = 2u, kGainEndLeft = 3u, kGainEndBlocked = 4u };

@@ -256,6 +256,28 @@ int stage_begin(HostStage &hs, size_t bytes, hipStream_t stream);
 int stage_end(HostStage &hs, hipStream_t stream);
 int staged_upload(HostStage &hs, size_t offset, void *dst, const void *src, size_t bytes, hipStream_t stream);
 int staged_download(HostStage &hs, void *dst, const void *src, size_t bytes, hipStream_t stream);
+// The upload of a frame of n points (3 doubles each) from caller memory, for the handles that take frames on a stream of their own
+// (kicp_grid, kicp_view): the HBM buffer, the staging buffer in front of it, how the buffer grows and how many points it may hold.
+struct FrameUpload {
+    static constexpr size_t kMaxPoints = 0x7FFFFFF0ull / 3;  // 3 n stays below 2^31
+    DevBuf<double> d_xyz;
+    HostStage stage;
+    // what an entry that takes n points checks first; `pointers`: none of those it needs is null
+    static int check(bool pointers, size_t n, const char *too_many) {
+        if (!pointers) return fail(KICP_ERR_ARG, "null argument");
+        if (n > kMaxPoints) return fail(KICP_ERR_CAPACITY, too_many);
+        return KICP_OK;
+    }
+    // n points into d_xyz; the buffer grows by half as much again, behind a synchronisation that keeps queued work off the old memory
+    int put(const double *xyz, size_t n, hipStream_t stream) {
+        if (!n) return KICP_OK;
+        if (3 * n > d_xyz.capacity()) {
+            HIP_TRY(hipStreamSynchronize(stream));
+            if (int rc = d_xyz.reserve(3 * n + 3 * n / 2)) return rc;
+        }
+        return staged_upload(stage, 0, d_xyz.get(), xyz, n * 24, stream);
+    }
+};
 
 struct DeviceMirror {
     int device = -1;

@@ -1,5 +1,5 @@
 // kicp_nav.hpp -- the kernels of the cost-to-go field over the grid's costmap (kicp_grid_potential, kicp_grid_potential_of_costmap;
-// C-ABI: kicp_grid.hip, arithmetic: kicp_nav_host.hpp).  The field is the least fixed point of a min-plus recurrence over integers, so
+// C-ABI: kicp_grid_plan.hip, arithmetic: kicp_nav_host.hpp).  The field is the least fixed point of a min-plus recurrence over integers, so
 // any order of relaxation reaches the same values; the launches on the grid's stream are
 //   k_nav_init   one lane per cell: q = weight[costmap] (a byte) and the potential "unreached".
 //   k_nav_goals  one lane per goal: potential 0 on a passable goal, and the activity flag of its tile up.
@@ -11,7 +11,7 @@
 //                counter with one atomic add per workgroup, the only atomic here.
 //   k_nav_count  the cells below max_potential and equal to it, for the statistics.
 // Rounds are separate launches; the host reads the counters after a batch of them and stops at the first round that raised nothing
-// (kicp_grid.hip).  The flags are bytes in two planes, used by round parity: round r reads plane r & 1 and writes plane (r + 1) & 1,
+// (kicp_grid_plan.hip).  The flags are bytes in two planes, used by round parity: round r reads plane r & 1 and writes plane (r + 1) & 1,
 // which round r - 1 read and lowered.  No workgroup waits for another, no floating point.
 //
 // Why races do not matter.  Inside a sweep a lane reads LDS words that other lanes are storing to, and while a tile loads its halo the

@@ -2,7 +2,7 @@
 // states the semantics): a cube map of Chebyshev depths around the sensor, faces aligned to the world axes, rendered from the frame the
 // pipeline has just registered; a map point that the frame looks past - it lies in front of what the frame returned around its pixel,
 // by more than a margin - leaves the map.  Kernels: kicp_view.hpp; geometry and verdict, shared with the host: kicp_view_host.hpp.
-// A handle owns its stream, its staging buffer and its device memory: the image, the sweep's voxel list and the statistics.
+// A handle owns its stream, its frame upload (kicp_internal.hpp) and its device memory: the image, the sweep's voxel list and the statistics.
 #include <memory>
 
 #include "kicp_internal.hpp"
@@ -22,17 +22,15 @@ struct kicp_view {
     DevBuf<uint32_t> d_depth;      // the image as float bit patterns
     DevBuf<unsigned int> d_stats;  // [0] points used by the render; [3] the length of d_list, [4 ..) the sweep's statistics, kSweepShards sets of four
     PinnedBuf<unsigned int> h_stats;
-    DevBuf<double> d_frame;        // kicp_view_render's and kicp_view_classify's upload
+    FrameUpload upload;            // kicp_view_render's and kicp_view_classify's points; its staging buffer also serves the verdicts' download
     DevBuf<uint8_t> d_verdicts;    // kicp_view_classify's result
     DevBuf<uint32_t> d_list;       // the sweep's voxel list (slots)
-    HostStage stage;
     ~kicp_view() {
         if (stream) (void)hipStreamSynchronize(stream), (void)hipStreamDestroy(stream);
     }
 };
 
 namespace {
-constexpr size_t kViewMaxPoints = 0x7FFFFFF0ull / 3;
 constexpr size_t kStatWords = 4 + 4 * kSweepShards;  // kicp_view::d_stats
 
 // the frame at d_xyz (n points; arguments checked): the image emptied, one launch, the statistics back, the stream drained
@@ -55,18 +53,7 @@ int render_on_device(kicp_view *view, const double *d_xyz, size_t n, const doubl
     return KICP_OK;
 }
 int check_frame_args(const kicp_view *view, const double *xyz, size_t n, const double *pose_qt, const double *sensor_xyz) {
-    if (!view || !pose_qt || !sensor_xyz || (!xyz && n)) return fail(KICP_ERR_ARG, "null argument");
-    if (n > kViewMaxPoints) return fail(KICP_ERR_CAPACITY, "frame too large");
-    return KICP_OK;
-}
-// n points from host memory into the handle's upload buffer
-int upload_points(kicp_view *view, const double *xyz, size_t n) {
-    if (!n) return KICP_OK;
-    if (3 * n > view->d_frame.capacity()) {
-        HIP_TRY(hipStreamSynchronize(view->stream));
-        if (int rc = view->d_frame.reserve(3 * n + 3 * n / 2)) return rc;
-    }
-    return staged_upload(view->stage, 0, view->d_frame.get(), xyz, n * 24, view->stream);
+    return FrameUpload::check(view && pose_qt && sensor_xyz && (xyz || !n), n, "frame too large");
 }
 int download_depth(const kicp_view *view, uint32_t *out) {
     HIP_TRY(hipMemcpyAsync(out, view->d_depth.get(), view->pixels * sizeof(uint32_t), hipMemcpyDeviceToHost, view->stream));
@@ -114,8 +101,8 @@ int kicp_view_render(kicp_view *view, const double *frame_xyz, size_t n, const d
     KICP_TRACE_CALL();
     if (int rc = check_frame_args(view, frame_xyz, n, pose_qt, sensor_xyz)) return rc;
     if (int rc = set_device(view->device)) return rc;
-    if (int rc = upload_points(view, frame_xyz, n)) return rc;
-    return render_on_device(view, view->d_frame.get(), n, pose_qt, sensor_xyz, out_stats);
+    if (int rc = view->upload.put(frame_xyz, n, view->stream)) return rc;
+    return render_on_device(view, view->upload.d_xyz.get(), n, pose_qt, sensor_xyz, out_stats);
 }
 int kicp_view_render_device(kicp_view *view, const double *d_frame_xyz, size_t n, const double pose_qt[7], const double sensor_xyz[3],
                             unsigned long long out_stats[2]) {
@@ -133,19 +120,18 @@ int kicp_view_depth(const kicp_view *view, float *out, size_t cap) {
 }
 int kicp_view_classify(kicp_view *view, const double *points_xyz, size_t n, unsigned char *out) {
     KICP_TRACE_CALL();
-    if (!view || ((!points_xyz || !out) && n)) return fail(KICP_ERR_ARG, "null argument");
-    if (n > kViewMaxPoints) return fail(KICP_ERR_CAPACITY, "too many points");
+    if (int rc = FrameUpload::check(view && ((points_xyz && out) || !n), n, "too many points")) return rc;
     if (!n) return KICP_OK;
     if (int rc = set_device(view->device)) return rc;
-    if (int rc = upload_points(view, points_xyz, n)) return rc;
+    if (int rc = view->upload.put(points_xyz, n, view->stream)) return rc;
     if (n > view->d_verdicts.capacity()) {
         HIP_TRY(hipStreamSynchronize(view->stream));
         if (int rc = view->d_verdicts.reserve(n + n / 2)) return rc;
     }
-    hipLaunchKernelGGL(k_view_classify, dim3(static_cast<uint32_t>((n + kViewBlock - 1) / kViewBlock)), dim3(kViewBlock), 0, view->stream, view->d_frame.get(),
+    hipLaunchKernelGGL(k_view_classify, dim3(static_cast<uint32_t>((n + kViewBlock - 1) / kViewBlock)), dim3(kViewBlock), 0, view->stream, view->upload.d_xyz.get(),
                        static_cast<uint32_t>(n), view->geom, view->frame, view->d_depth.get(), view->d_verdicts.get());
     HIP_TRY(hipGetLastError());
-    return staged_download(view->stage, out, view->d_verdicts.get(), n, view->stream);
+    return staged_download(view->upload.stage, out, view->d_verdicts.get(), n, view->stream);
 }
 
 int kicp_map_remove_seen_through(kicp_map *map, kicp_view *view, unsigned long long out_stats[4]) {
