@@ -223,7 +223,9 @@ int kicp_reg_set_config(kicp_reg *reg, const kicp_reg_config *config); /* the re
  *   "wait"         0 (default): poll the tagged rows in host memory; 1: hipStreamSynchronize
  *   "timing"       1: kicp_stats.gpu_ms from HIP events; 2: also kicp_stats.pass_ms[]
  * Read only: "small_active" (path of the last call: 0 generic, 1 sub-lanes, 2 wave per query), "resident_passes", "batch_queue_passes",
- *   "batch_resident_passes", "batch_threads_active", "small_relaunches", "score_launches", "search_nodes_scored", "search_launches", "aql_active", "aql_kernarg", "comm_ranks".
+ *   "batch_resident_passes", "batch_threads_active", "small_relaunches", "score_launches", "score_items_per_workgroup" (the most tile x pose items one
+ *   workgroup served in a launch of the last scoring call), "search_nodes_scored", "search_launches", "search_yaw_trips" (yaws one workgroup of
+ *   the last call's cell kernel served), "aql_active", "aql_kernarg", "comm_ranks".
  * Test hooks (exercise fall-backs that this hardware does not reach by itself): "small_cmd" 0 - workgroup 0 relays the resident kernels'
  *   commands (platforms without a CPU-writable BAR); "debug_tag" - jump next to the 16-bit pass tag's wrap-around; "debug_stall_us" -
  *   be late with one command; "debug_p2p_one_row" - send this rank's total as one mailbox row, as launches of more than 32 groups

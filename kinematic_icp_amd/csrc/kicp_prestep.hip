@@ -384,7 +384,10 @@ int ingest_run(kicp_pre *p, const void *data, size_t n_points, const kicp_cloud_
     kicp_pre::IngestCounts &ic = p->ingest_counts[slot];
     ic.launches = piece_index, ic.workgroups = widest, ic.aligned = ip.aligned, ic.wide = L.point_step > 128u ? 1 : 0, ic.direct = direct ? 1 : 0;
     ic.piece_records = piece_records;
-    if (int rc = wait_word(rec + 2, ip.seq, ~0ull, stream, 2.0, kPreLost)) return rc;  // (`data` and the staging buffer are free again behind this)
+    // (`data` and the staging buffer are free again behind this.)  The record is written by the workgroup that finishes last, on either
+    // lane: once the limit has run out wait_word drains `stream` alone, so the other lane is drained too before the call gives up
+    if (wait_word(rec + 2, ip.seq, ~0ull, stream, 2.0, kPreLost) != KICP_OK)
+        if (int rc = wait_word(rec + 2, ip.seq, ~0ull, lanes[1], 0.0, kPreLost)) return rc;
     if (slot == 0) trace_lap("the decoded cloud's record at the host");
     *out_lo = *out_hi = 0.0;
     if (st != 0) *out_lo = ordered_value(rec[0]), *out_hi = ordered_value(rec[1]);

@@ -236,9 +236,11 @@ double kicp_reg_get_option(const kicp_reg *reg, const char *name) {
     if (k == "small_timeout_us") return reg->small_timeout_us;
     if (k == "score_chunk") return reg->score_chunk;
     if (k == "score_launches") return reg->score_launches;
+    if (k == "score_items_per_workgroup") return static_cast<double>(reg->score_items_per_workgroup);
     if (k == "search_max_nodes") return reg->search_max_nodes;
     if (k == "search_nodes_scored") return static_cast<double>(reg->search_nodes_scored);
     if (k == "search_launches") return reg->search_launches;
+    if (k == "search_yaw_trips") return reg->search_yaw_trips;
     if (k == "small_active") return reg->last_small;  // path of the last registration: 0 generic, 1 small (sub-lanes per query), 2 small (wave per query)
     if (k == "small_relaunches") return static_cast<double>(reg->small_relaunches);
     if (k == "aql_active") return (reg->aql.ready && reg->last_via_aql) ? 1.0 : 0.0;  // was the last pass dispatched through the AQL queue

@@ -211,6 +211,7 @@ struct kicp_reg {
     DevBuf<unsigned long long> d_planar_acc; // kicp_planar_sums: kPlanarWords per pose, for as many poses as the two above hold
     double score_chunk = 8388608.0;   // option "score_chunk": queries (pose x point pairs) one launch of k_score_poses may serve
     int score_launches = 0;           // launches the last kicp_score_poses call used (get-only "score_launches")
+    unsigned long long score_items_per_workgroup = 0;  // most (tile, pose) items one workgroup served in a launch of it (get-only "score_items_per_workgroup")
     // kicp_occ_score_nodes / kicp_search_poses (kicp_search.hip): the frame's cells per yaw, the rotation table, a piece of the node list
     // and its scores
     DevBuf<int32_t> d_search_cells;
@@ -220,6 +221,7 @@ struct kicp_reg {
     double search_max_nodes = 67108864.0;          // option "search_max_nodes": nodes one kicp_search_poses call may score
     unsigned long long search_nodes_scored = 0;    // nodes the last search scored (get-only "search_nodes_scored")
     int search_launches = 0;                       // launches of k_search_score in the last call (get-only "search_launches")
+    unsigned int search_yaw_trips = 0;             // yaws one workgroup of the last k_search_cells launch served (get-only "search_yaw_trips")
     uint32_t trace_pass = 1;      // the pass of a launch the stamps are taken on (the option's value)
     DevBuf<long long> d_trace;    // option "small_trace": device buffer of the kernel's per-pass wall-clock stamps
     double trace_host_us = 0.0, trace_dev_us = 0.0, trace_first_us = 0.0;  // host: rows seen -> command sent; device: command sent -> rows seen; launch -> first rows

@@ -72,7 +72,7 @@ int check_score_args(const kicp_reg *reg, const kicp_map *map, const void *frame
 template <bool PLANAR, class OnRow>
 int rows_device(kicp_reg *reg, kicp_map *map, const double *d_frame, size_t n, const double *poses_qt, size_t count, double tau, OnRow on_row) {
     constexpr int kRowWords = PLANAR ? kPlanarWords : kScoreWords;
-    reg->score_launches = 0;
+    reg->score_launches = 0, reg->score_items_per_workgroup = 0;
     if (int rc = map_finish_pending(map)) return rc;  // (a deferred update's error is this call's: the map it would score against is not the updated one)
     if (kicp_map_empty(map) || n == 0 || count == 0) return KICP_OK;
     if (int rc = set_device(reg->device)) return rc;
@@ -97,6 +97,7 @@ int rows_device(kicp_reg *reg, kicp_map *map, const double *d_frame, size_t n, c
         for (unsigned long long item0 = 0; item0 < total; item0 += per_launch) {
             sp.item0 = item0, sp.items = std::min(per_launch, total - item0);
             const uint32_t grid = static_cast<uint32_t>(std::min<unsigned long long>(sp.items, kScoreMaxGrid));
+            reg->score_items_per_workgroup = std::max(reg->score_items_per_workgroup, (sp.items + grid - 1) / grid);
             if (PLANAR) hipLaunchKernelGGL(k_planar_poses, dim3(grid), dim3(kScoreBlock), 0, reg->stream, sp);
             else hipLaunchKernelGGL(k_score_poses, dim3(grid), dim3(kScoreBlock), 0, reg->stream, sp);
             ++reg->score_launches;
@@ -138,18 +139,19 @@ int refine_planar_device(kicp_reg *reg, kicp_map *map, const double *d_frame, si
                          double convergence, double *out_poses_qt, int *iterations, int *status) {
     if (count) std::memmove(out_poses_qt, poses_qt, count * 7 * sizeof(double));
     for (size_t k = 0; k < count; ++k) iterations[k] = 0, status[k] = kPlanarDegenerate;
-    reg->score_launches = 0;
+    reg->score_launches = 0, reg->score_items_per_workgroup = 0;
     if (int rc = map_finish_pending(map)) return rc;
     if (kicp_map_empty(map) || n == 0 || count == 0) return KICP_OK;
     std::vector<size_t> active(count), next;
     for (size_t k = 0; k < count; ++k) active[k] = k;
     std::vector<double> poses, sums;
     int launches = 0;
+    unsigned long long items_per_workgroup = 0;
     while (!active.empty()) {
         poses.resize(7 * active.size()), sums.resize(kPlanarSums * active.size());
         for (size_t j = 0; j < active.size(); ++j) std::memcpy(&poses[7 * j], out_poses_qt + 7 * active[j], 7 * sizeof(double));
         if (int rc = planar_sums_device(reg, map, d_frame, n, poses.data(), active.size(), tau, sums.data())) return rc;
-        launches += reg->score_launches;
+        launches += reg->score_launches, items_per_workgroup = std::max(items_per_workgroup, reg->score_items_per_workgroup);
         next.clear();
         for (size_t j = 0; j < active.size(); ++j) {
             const size_t k = active[j];
@@ -162,7 +164,7 @@ int refine_planar_device(kicp_reg *reg, kicp_map *map, const double *d_frame, si
         }
         active.swap(next);
     }
-    reg->score_launches = launches;
+    reg->score_launches = launches, reg->score_items_per_workgroup = items_per_workgroup;
     return KICP_OK;
 }
 int check_refine_args(int max_iterations, double convergence) {

@@ -83,7 +83,9 @@ int prepare_cells(kicp_reg *reg, const kicp_occ *occ, const double *frame_xyz, s
     yaw_table(w, cs.data());
     if (int rc = staged_upload(reg->stage, 0, reg->d_search_cs.get(), cs.data(), cs.size() * sizeof(double), reg->stream)) return rc;
     const SearchWindowDev wd{w->x0, w->y0, w->z, w->nx, w->ny, w->nyaw};
-    hipLaunchKernelGGL(k_search_cells, dim3(static_cast<uint32_t>((n + 255) / 256), std::min(w->nyaw, 1024u)), dim3(256), 0, reg->stream, reg->d_frame.get(),
+    const uint32_t yaw_grid = std::min(w->nyaw, 1024u);
+    reg->search_yaw_trips = (w->nyaw + yaw_grid - 1) / yaw_grid;
+    hipLaunchKernelGGL(k_search_cells, dim3(static_cast<uint32_t>((n + 255) / 256), yaw_grid), dim3(256), 0, reg->stream, reg->d_frame.get(),
                        static_cast<uint32_t>(n), reg->d_search_cs.get(), wd, occ->grid, reg->d_search_cells.get());
     HIP_TRY(hipGetLastError());
     return KICP_OK;
