@@ -182,7 +182,7 @@ void kicp_reg_destroy(kicp_reg *reg);
 int kicp_reg_clone(const kicp_reg *reg, kicp_reg **out);
 int kicp_reg_get_config(const kicp_reg *reg, kicp_reg_config *out);
 int kicp_reg_set_config(kicp_reg *reg, const kicp_reg_config *config); /* the reference's fields are public & mutable */
-/* Backend tuning knobs (not part of the reference API).  Nineteen settable options; everything that lost its A/B over five rounds
+/* Backend tuning knobs (not part of the reference API).  Twenty settable options; everything that lost its A/B over five rounds
  * (other workgroup sizes and register budgets, the plain fp64 gather, the device-side solve, single-record hand-offs, ...) was deleted
  * in round 6, and the pass kernels' ablation switches ("dbg") exist in libkicp_amd_dbg.so only (make -C kinematic_icp_amd/csrc dbg).
  * Which kernel runs:
@@ -191,6 +191,10 @@ int kicp_reg_set_config(kicp_reg *reg, const kicp_reg_config *config); /* the re
  *   "latency_kernel" one lane per query: 1 (default) scans of at most 131 072 points - which leave the device two waves per SIMD
  *                  anyway - run the build that has TWO neighbour voxels in flight per round; 2: every such scan; 0: never (the
  *                  four-waves-per-SIMD build)
+ *   "pass_tiles"   blocks of 256 queries a workgroup of the one-lane-per-query four-waves build serves before its one epilogue:
+ *                  0 (default) by scan size and scans in flight - more than one only while the passes in flight keep at least 1.5
+ *                  workgroups per workgroup slot of the device (cfg2 in a batch: 2) -, or 1 | 2 | 4 (other values are clamped to the next of these below).  Changes no bit of a
+ *                  result: the sums are exact.  The other builds serve one block per workgroup whatever the value.
  *   "small"        1 (default): scans of at most 16 384 lanes (points x sub-lanes) take the small-scan path - the kernel stays resident for
  *                  the iterations of a call, polling for the next pose; 0: always the generic pass kernel
  *   "small_wave"   1 (default): scans of at most 4 096 points run ONE WAVE PER QUERY (k_pass_wave); 0: sub-lanes per query (k_pass_small)

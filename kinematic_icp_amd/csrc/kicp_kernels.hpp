@@ -27,6 +27,7 @@
 #include <climits>
 
 #include "kicp_common.hpp"
+#include "kicp_pass_tiles.hpp"
 #include "kicp_se3.hpp"
 
 namespace kicp {
@@ -159,6 +160,9 @@ struct PassParams {
     unsigned long long *group_acc; // resident kernels: the groups' counting accumulators (finish_pass, ROWS_ONLY), zero between passes
     SolveParams sol;
     int32_t dbg;          // ablation switches for tools/dbg_census.py (0 = normal operation); read by the DBG build only (dbg_is)
+    // blocks of 256 queries a workgroup of the one-lane-per-query four-waves build serves before its ONE epilogue (0 and 1: one block;
+    // at most kMaxPassTiles; the grid is then ceil(blocks / tiles) workgroups).  Read by that build only (pass_tiles_loop).
+    uint32_t tiles;
     // kicp_pass_correspondences (the EXPORT instantiations of the pass kernels only; nullptr otherwise): what DataAssociation appends
     // for query i (Registration.cpp:73-77) - the chosen map point's index in the pool (-1: no correspondence), its squared distance
     // to T * source[i] and its coordinates
@@ -211,9 +215,10 @@ __device__ __forceinline__ double limbs_to_double(const long long l[3]) {
     return (neg ? -mag : mag) / kFixScale;
 }
 
-// A lane's contribution to the seven sums of one pass: every lane serves at most ONE correspondence per pass, so each sum is
-// a single fixed-point term x * 2^40 with |x| < 2^43, held as four 21-bit limbs (the top one signed) - a wave's 64 values of
-// a limb then add up in int32 (finish_pass).  The term is formed without leaving the integers' range: x = ip + fr with
+// A lane's contribution to the seven sums of one pass: every lane serves at most ONE correspondence per block of queries (tile),
+// so per tile each sum is a single fixed-point term x * 2^40 with |x| < 2^43, held as four 21-bit limbs (the top one signed).  A
+// lane adds its limbs over the at most kMaxPassTiles tiles of its workgroup (pass_tiles_loop), and a wave's 64 values of a limb
+// then add up in int32 (finish_pass): 4 * 64 * 2^21 = 2^29.  The term is formed without leaving the integers' range: x = ip + fr with
 // ip = rint(x) (exact in int64) and fr = x - ip (exact, |fr| <= 1/2), so round(x * 2^40) = ip * 2^40 + round(fr * 2^40)
 // - the same integer the single conversion gives wherever that one fits (ties included: ip * 2^40 is even).
 constexpr int kTermLimbs = 4;
@@ -280,6 +285,7 @@ __device__ __forceinline__ void i128_add_limb_sums(I128 &t, long long s0, long l
     i128_add(t, I128{static_cast<unsigned long long>(s2) << 42, s2 >> 22});
     i128_add(t, I128{static_cast<unsigned long long>(s3) << 63, s3 >> 1});
 }
+// (kMaxPassTiles and limb_sums_to_words - a workgroup's limb sums as row words - live in kicp_pass_tiles.hpp, which a host program can include)
 
 // ------------------------------------------------------------------------------------------------------------
 // nearest-neighbour search helpers
@@ -649,8 +655,8 @@ constexpr unsigned long long kGaveUpUnit = 1ull << 16;
 // the host repeats the pass (resident kernel) or fails the call - instead of a wave spinning on the device for ever.
 constexpr unsigned long long kLostRowUnit = 1ull << 8;
 constexpr long long kRowWaitTicks = 200000000ll;
-// The hand-over of a workgroup's exact sums through its group's COUNTING ACCUMULATORS (wave 0; lanes 0..6 hold the seven 128-bit
-// totals `t`): ONE round trip to the L2 and no reader.  Lane w < kReduceWords adds word w of the workgroup's row - biased to be
+// The hand-over of a workgroup's exact sums through its group's COUNTING ACCUMULATORS (wave 0; lanes 0..6 hold the row words
+// of the seven sums): ONE round trip to the L2 and no reader.  Lane w < kReduceWords adds word w of the workgroup's row - biased to be
 // non-negative, with a 1 in the count field above it - to word w of the group's accumulator.  The addition that finds the count at
 // group size - 1 is the last one for that word: old value + own = the group's sum, which that lane hands to the host (and clears
 // the word for the set's next turn).  Every word is completed by whichever workgroup happened to add to it last - not necessarily
@@ -660,11 +666,11 @@ constexpr long long kRowWaitTicks = 200000000ll;
 // every launch whose group rows go to the host, and the small-scan kernels (kicp_small.hpp), whose every workgroup used to send a
 // row of its own across PCIe.
 // `nblocks`: the workgroups of the pass - the launch's (gridDim.x), or the job's where a launch serves several (k_pass_gather32_jobs).
-__device__ __forceinline__ void counting_hand_over(const I128 &t, int range_error, int gave_up, const PassParams &p, uint32_t row_tag, uint32_t acc_set,
+// `l` (lanes 0..6): the three row words of the lane's sum - the canonical limbs of its 128-bit total (i128_to_limbs) or any other
+// three words of magnitude below 2^40 with the same weighted sum (limb_sums_to_words).
+__device__ __forceinline__ void counting_hand_over(const long long (&l)[3], int range_error, int gave_up, const PassParams &p, uint32_t row_tag, uint32_t acc_set,
                                                    uint32_t row_set, int lane, uint32_t nblocks = gridDim.x) {
     const uint32_t b = blockIdx.x, g = b / kGroup, ngroups = (nblocks + kGroup - 1) / kGroup;
-    long long l[3] = {0ll, 0ll, 0ll};
-    if (lane < kNumSums) i128_to_limbs(t, l);
     const int from = min(lane, kNumLimbs - 1) / 3;
     const long long a0 = __shfl(l[0], from, 64), a1 = __shfl(l[1], from, 64), a2 = __shfl(l[2], from, 64);
     long long word = lane % 3 == 0 ? a0 : (lane % 3 == 1 ? a1 : a2);
@@ -682,6 +688,28 @@ __device__ __forceinline__ void counting_hand_over(const I128 &t, int range_erro
         }
     }
 }
+// the same for a caller that holds 128-bit totals (k_pass_wave: its lanes convert whole terms, there are no limb sums)
+__device__ __forceinline__ void counting_hand_over(const I128 &t, int range_error, int gave_up, const PassParams &p, uint32_t row_tag, uint32_t acc_set,
+                                                   uint32_t row_set, int lane, uint32_t nblocks = gridDim.x) {
+    long long l[3] = {0ll, 0ll, 0ll};
+    if (lane < kNumSums) i128_to_limbs(t, l);
+    counting_hand_over(l, range_error, gave_up, p, row_tag, acc_set, row_set, lane, nblocks);
+}
+// Wave 0 after the workgroup's barrier: lane i < 7 adds the waves' sums of the four limbs of sum i (64-bit additions of int32
+// values) and cuts them into the three row words (limb_sums_to_words).  No 128-bit arithmetic: the chain every workgroup's last
+// wave runs alone is a dozen 64-bit operations.
+template <int WAVES>
+__device__ __forceinline__ void workgroup_row_words(const int (*s_red)[kWaveLimbs], int lane, long long (&l)[3]) {
+    l[0] = l[1] = l[2] = 0ll;
+    if (lane < kNumSums) {
+        long long s[kTermLimbs] = {0ll, 0ll, 0ll, 0ll};
+#pragma unroll
+        for (int w = 0; w < WAVES; ++w)
+#pragma unroll
+            for (int k = 0; k < kTermLimbs; ++k) s[k] += s_red[w][kTermLimbs * lane + k];
+        limb_sums_to_words(s[0], s[1], s[2], s[3], l);
+    }
+}
 
 // ROWS_ONLY: the caller only ever runs mode 4 (the resident kernel): none of the other hand-offs is compiled in.
 // `parity` (resident kernel: pass & 1): workgroup rows, tickets and the groups' host rows are double-buffered by pass parity, so
@@ -689,9 +717,12 @@ __device__ __forceinline__ void counting_hand_over(const I128 &t, int range_erro
 // command of pass k + 1 - can never land on a row of pass k that its reader (the group's last workgroup, the host) has not
 // consumed yet.  The buffer of parity (k + 1) & 1 last held pass k - 1, whose rows the host had added before it sent the command
 // that started pass k.
-template <int BLOCK, bool ROWS_ONLY = false>
+// TILED (the kernels whose workgroups serve several tiles, pass_tiles_loop): `a` holds the lane's limb sums over its tiles,
+// `holders` the number of correspondences the WAVE found in all of them (wave-uniform) and `jtj` the four limbs of |R UnitX|^2
+// (PassBasis::jtj00, wave-uniform) - a lane may hold several correspondences, so the two shortcuts below take these instead of a ballot.
+template <int BLOCK, bool ROWS_ONLY = false, bool TILED = false>
 __device__ __forceinline__ void finish_pass(Acc &a, const PassParams &p, int (*s_red)[kWaveLimbs], int *s_flag, uint32_t row_tag, int gave_up = 0,
-                                            uint32_t parity = 0u, uint32_t nblocks = gridDim.x) {
+                                            uint32_t parity = 0u, uint32_t nblocks = gridDim.x, int holders = 0, const int *jtj = nullptr) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     IcpState *st = p.st;
     if (!ROWS_ONLY && dbg_is(p, 8)) {  // ablation (tools/gpu_dbg.py): no reduction at all, workgroup 0 hands over zeros
@@ -705,8 +736,8 @@ __device__ __forceinline__ void finish_pass(Acc &a, const PassParams &p, int (*s
         }
         return;
     }
-    // Every lane contributes at most ONE correspondence per pass, so its seven sums are single terms (to_fixed): four limbs
-    // of 21 bits each, and a wave's 64 values of a limb add up in int32.
+    // Every lane contributes at most ONE correspondence per tile and serves at most kMaxPassTiles of them, so each of its seven
+    // sums is at most four terms (to_fixed): limbs of 21 bits each, below 2^23 per lane, and a wave's 64 values of a limb add up in int32.
     int range_error = a.range_error;
     int limb[kWaveLimbs];
     if (dbg_is(p, 10) || dbg_is(p, 12)) {  // (10, the census: the count's limbs carry something else; 12: the in-process A/B switch of what follows)
@@ -716,12 +747,19 @@ __device__ __forceinline__ void finish_pass(Acc &a, const PassParams &p, int (*s
         // Two of the seven sums need no reduction.  The count: every correspondence adds 2^40 = limb 1 at 2^19, so the wave's sum is
         // the number of lanes that hold one.  |J.col(0)|^2 = |R UnitX|^2 depends on the pose alone: every correspondence adds the SAME
         // four limbs, so the wave's sum is that number times the limbs of any lane that holds one.  (Sums of identical integers:
-        // exactly what the additions would give.)
-        const unsigned long long holders = __ballot(a.limb[6 * kTermLimbs + 1] != 0);
-        const int n_holders = __popcll(holders);
-        const int some = holders ? static_cast<int>(__ffsll(static_cast<long long>(holders))) - 1 : 0;
+        // exactly what the additions would give.)  TILED: the number is the caller's count over the wave's tiles, the limbs the basis'.
+        int n_holders;
+        if constexpr (TILED) {
+            n_holders = holders;
 #pragma unroll
-        for (int k = 0; k < kTermLimbs; ++k) limb[k] = n_holders * __builtin_amdgcn_readlane(a.limb[k], some);
+            for (int k = 0; k < kTermLimbs; ++k) limb[k] = n_holders * jtj[k];
+        } else {
+            const unsigned long long held = __ballot(a.limb[6 * kTermLimbs + 1] != 0);
+            n_holders = __popcll(held);
+            const int some = held ? static_cast<int>(__ffsll(static_cast<long long>(held))) - 1 : 0;
+#pragma unroll
+            for (int k = 0; k < kTermLimbs; ++k) limb[k] = n_holders * __builtin_amdgcn_readlane(a.limb[k], some);
+        }
         limb[6 * kTermLimbs] = 0, limb[6 * kTermLimbs + 1] = n_holders << 19, limb[6 * kTermLimbs + 2] = 0, limb[6 * kTermLimbs + 3] = 0;
         // The other twenty limbs: a reduction that HALVES the number of values a lane carries with every step it can - the lanes of a
         // pair keep one half each and take the partner's share of it (quad_perm), twice; then the quads of a row (row_shr 4, 8) and the
@@ -769,21 +807,23 @@ __device__ __forceinline__ void finish_pass(Acc &a, const PassParams &p, int (*s
     __syncthreads();
     if (wave != 0) return;
     range_error = (*s_flag & 2) ? 1 : 0;
-    // wave 0 only from here.  Lane i < 7 takes the workgroup total of sum i (as a 128-bit integer) and publishes its three
-    // 40-bit limbs.
-    I128 t{0ull, 0ll};
-    if (lane < kNumSums) {
-        for (int w = 0; w < BLOCK / 64; ++w)
-            i128_add_limb_sums(t, s_red[w][kTermLimbs * lane], s_red[w][kTermLimbs * lane + 1], s_red[w][kTermLimbs * lane + 2], s_red[w][kTermLimbs * lane + 3]);
-    }
+    // wave 0 only from here.
     const uint32_t b = blockIdx.x, g = b / kGroup, ngroups = (nblocks + kGroup - 1) / kGroup;
     // (an ordinary launch in mode 4 - round 5: the accumulators alternate with the pass tag's parity, the host's row of group g stays
     //  where it was; dbg 14: round 4's rows -> ticket -> reload, for the in-process A/B)
     const bool counting = ROWS_ONLY || (p.sol.mode == 4 && dbg_not(p, 14));
     if (!ROWS_ONLY && counting) parity = row_tag & 1u;
-    if (counting) {
-        counting_hand_over(t, range_error, gave_up, p, row_tag, parity, ROWS_ONLY ? parity : 0u, lane, nblocks);
+    if (counting) {  // lane i < 7: the three row words of sum i straight from the waves' limb sums
+        long long l[3];
+        workgroup_row_words<BLOCK / 64>(s_red, lane, l);
+        counting_hand_over(l, range_error, gave_up, p, row_tag, parity, ROWS_ONLY ? parity : 0u, lane, nblocks);
         return;
+    }
+    // The other hand-offs: lane i < 7 takes the workgroup total of sum i (as a 128-bit integer) and publishes its three 40-bit limbs.
+    I128 t{0ull, 0ll};
+    if (lane < kNumSums) {
+        for (int w = 0; w < BLOCK / 64; ++w)
+            i128_add_limb_sums(t, s_red[w][kTermLimbs * lane], s_red[w][kTermLimbs * lane + 1], s_red[w][kTermLimbs * lane + 2], s_red[w][kTermLimbs * lane + 3]);
     }
     unsigned long long *const rows0 = p.partials + (ROWS_ONLY ? static_cast<size_t>(parity) * nblocks * kReduceWords : 0u);
     unsigned int *const tickets0 = p.tickets + (ROWS_ONLY ? static_cast<size_t>(parity) * ngroups * kTicketStride : 0u);
@@ -1502,6 +1542,76 @@ __device__ __forceinline__ void gather32_pass(const PassParams &p, const Pose &T
     if constexpr (ACC::kKind == AccKind::Pass)
         if (dbg_is(p, 10) && (tid & 63u) == 0u) acc.limb[6 * kTermLimbs + 1] = static_cast<int>(rounds & 3u) << 19, acc.limb[6 * kTermLimbs + 2] = static_cast<int>(rounds >> 2);
 }
+// SEVERAL TILES PER WORKGROUP (the one-lane-per-query four-waves build: k_pass_gather32<256, 1, 4, false, false>, its EXPORT twin,
+// k_pass_gather32_jobs).  The epilogue - the wave reduction of twenty limbs, the barrier, wave 0's section alone on its SIMD, 24
+// atomics and a share of a group row the host collects - costs a workgroup the same however many queries it served, and the sums
+// are exact integers: any dealing of the queries to workgroups gives the same 24 words.  So a workgroup searches p.tiles blocks of
+// BLOCK queries, one after the other, and finishes ONCE.  Workgroup b of `nwg` takes blocks b, b + nwg, b + 2 nwg, ...: strided by
+// the grid, so that (workgroups being dealt round-robin to the XCDs) a block stays on the XCD it ran on with one tile wherever nwg
+// is a multiple of 8, and every workgroup's first tile is a full one.  The waves of a workgroup pass from tile to tile on their
+// own: what a tile uses of the LDS is private to a wave (s_lend) or a lane (s_park, s_tile), so no barrier separates the tiles.
+// Between tiles a lane's terms wait in LDS, `tile` = [20][BLOCK] ints: the limbs of the five sums that need a reduction are added
+// there by ds_add_u32 (column `tid`: no bank conflict, no VALU instruction, no register held through the next search) and read back
+// once for the single reduction.  The two other sums travel as the wave's number of correspondences (`holders`).  With one tile the
+// terms stay in registers and the LDS array is not touched.
+// Returns the wave's number of correspondences; `acc` holds the lane's limb sums (limbs 4 .. 23) and its range flag, OR-ed over the tiles.
+constexpr int kTileLimbs = kWaveLimbs - 2 * kTermLimbs;  // (|R UnitX|^2 and the count need no per-lane sums: finish_pass, TILED)
+template <int BLOCK, bool EXPORT, bool JOBS>
+__device__ __forceinline__ int pass_tiles_loop(Acc &acc, int (*lend)[kLendWords], double *park, int (*tile)[BLOCK]) {
+    const uint32_t tid = threadIdx.x;
+    // (the wave's count and the lane's range flag wait in vector registers: the search leaves a few of those free and no scalar one)
+    int holders = 0, range_error = 0;
+    uint32_t block = blockIdx.x;
+    for (;;) {
+        asm volatile("; kept in vector registers through the tile" : "+v"(holders), "+v"(range_error));
+        // Nothing of a tile's set-up may be carried from tile to tile in registers (the build has none to spare, scalar ones
+        // included): the arguments and the pose are re-read from the kernarg segment and the lane index is taken up afresh, so
+        // that the compiler cannot hoist what depends on them out of the loop and hold it through the search.
+        const PassParams &pt = JOBS ? job_args_at_point_of_use(blockIdx.y) : args_at_point_of_use();
+        const Pose T = JOBS ? pt.sol.pose0 : load_pose(pt);
+        const bool host_pose = JOBS || pt.sol.pass == 0 || pt.sol.mode >= 2;  // (load_pose)
+        uint32_t lane_id = tid;
+        asm volatile("; a tile starts here" : "+v"(lane_id));
+        Acc one{};
+        gather32_pass<BLOCK, 1, false, false, true, EXPORT, Acc, JOBS>(pt, T, host_pose, lane_id, one, pt.src, pt.n, block, &lend[lane_id / 64u][0], park);
+        holders += __popcll(__ballot(one.limb[6 * kTermLimbs + 1] != 0));
+        range_error |= one.range_error;
+        // (all wave-uniform from here, and read where they are used: the job's or the launch's workgroups, the tiles of each, the scan's blocks)
+        const PassParams &pe = JOBS ? job_args_at_point_of_use(blockIdx.y) : args_at_point_of_use();
+        const uint32_t tiles = min(pe.tiles, static_cast<uint32_t>(kMaxPassTiles));
+        if (tiles <= 1u) {  // the terms never leave the registers
+            acc = one;
+            break;
+        }
+        if (block == blockIdx.x) {
+#pragma unroll
+            for (int k = 0; k < kTileLimbs; ++k) tile[k][tid] = one.limb[kTermLimbs + k];
+        } else {
+#pragma unroll
+            for (int k = 0; k < kTileLimbs; ++k) (void)__hip_atomic_fetch_add(&tile[k][tid], one.limb[kTermLimbs + k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WAVEFRONT);
+        }
+        const uint32_t nwg = JOBS ? ((JobsKernarg)__builtin_amdgcn_kernarg_segment_ptr())->nblocks[blockIdx.y] : gridDim.x;
+        const uint32_t end = min((pe.n + BLOCK - 1) / BLOCK, blockIdx.x + tiles * nwg);
+        block += nwg;
+        if (block >= end) {  // (a lane reads back what it wrote itself: no barrier)
+#pragma unroll
+            for (int k = 0; k < kTileLimbs; ++k) acc.limb[kTermLimbs + k] = tile[k][tid];
+            break;
+        }
+    }
+    acc.range_error = range_error;
+    return __builtin_amdgcn_readfirstlane(holders);
+}
+// the limbs of |R UnitX|^2 every correspondence of the pass adds (accumulate takes them from the same place)
+template <bool JOBS>
+__device__ __forceinline__ void pass_jtj00(int (&jtj)[kTermLimbs]) {
+    const PassParams &p = JOBS ? job_args_at_point_of_use(blockIdx.y) : args_at_point_of_use();
+    PassBasis B;
+    if (JOBS || p.sol.pass == 0 || p.sol.mode >= 2) B = p.sol.basis;  // (load_pose: the host's pose and its basis)
+    else B = basis_of(load_pose(p));
+#pragma unroll
+    for (int k = 0; k < kTermLimbs; ++k) jtj[k] = B.jtj00[k];
+}
 template <int BLOCK, int G, int OCC, bool SPLIT, bool LAT = false, bool EXPORT = false>
 __global__ __launch_bounds__(BLOCK, OCC) void k_pass_gather32(const PassParams p) {
     static_assert(!SPLIT || G == 2, "bucket sharing is written for pairs of lanes");
@@ -1510,13 +1620,22 @@ __global__ __launch_bounds__(BLOCK, OCC) void k_pass_gather32(const PassParams p
     constexpr bool kLends = G == 1 && !SPLIT && !LAT;  // idle lanes take over voxels of loaded queries (gather32_pass)
     __shared__ int s_lend[kLends ? BLOCK / 64 : 1][kLendWords];
     __shared__ double s_park[kLends ? BLOCK * kParkWords : 1];
-    const Pose T = load_pose(p);
-    const bool host_pose = p.sol.pass == 0 || p.sol.mode >= 2;  // (load_pose)
     Acc acc{};
-    gather32_pass<BLOCK, G, SPLIT, LAT, kLends, EXPORT>(p, T, host_pose, threadIdx.x, acc, p.src, p.n, blockIdx.x, kLends ? &s_lend[kLends ? threadIdx.x / 64 : 0][0] : nullptr,
-                                                s_park);
-    if (BLOCK > 64) __syncthreads();
-    finish_pass<BLOCK>(acc, p, s_red, &s_flag, p.sol.tag);
+    if constexpr (kLends) {  // the four-waves build: p.tiles blocks per workgroup
+        __shared__ int s_tile[kTileLimbs][BLOCK];
+        const int holders = pass_tiles_loop<BLOCK, EXPORT, false>(acc, s_lend, s_park, s_tile);
+        int jtj[kTermLimbs];
+        pass_jtj00<false>(jtj);
+        __syncthreads();
+        const PassParams &pf = args_at_point_of_use();  // (not `p`: its loads would be issued ahead of the loop and held through it)
+        finish_pass<BLOCK, false, true>(acc, pf, s_red, &s_flag, pf.sol.tag, 0, 0u, gridDim.x, holders, jtj);
+    } else {
+        const Pose T = load_pose(p);
+        const bool host_pose = p.sol.pass == 0 || p.sol.mode >= 2;  // (load_pose)
+        gather32_pass<BLOCK, G, SPLIT, LAT, kLends, EXPORT>(p, T, host_pose, threadIdx.x, acc, p.src, p.n, blockIdx.x, nullptr, s_park);
+        if (BLOCK > 64) __syncthreads();
+        finish_pass<BLOCK>(acc, p, s_red, &s_flag, p.sol.tag);
+    }
 }
 // the four-waves build with one lane per query, for a list of jobs (JobsParams): every job's pose is its host's and its rows go to
 // that host in mode 4, group by group, through the job's own accumulators.  A launch's grid is as wide as its largest job: the
@@ -1531,11 +1650,14 @@ __global__ __launch_bounds__(BLOCK, OCC) void k_pass_gather32_jobs(const JobsPar
     KICP_PASS_SHARED(BLOCK)
     __shared__ int s_lend[BLOCK / 64][kLendWords];
     __shared__ double s_park[BLOCK * kParkWords];
-    const Pose T = p.sol.pose0;
+    __shared__ int s_tile[kTileLimbs][BLOCK];
     Acc acc{};
-    gather32_pass<BLOCK, G, false, false, true, false, Acc, true>(p, T, true, threadIdx.x, acc, p.src, p.n, blockIdx.x, &s_lend[threadIdx.x / 64][0], s_park);
+    // (`nblocks`: the job's workgroups, each of p.tiles blocks - a job list may mix tile counts)
+    const int holders = pass_tiles_loop<BLOCK, false, true>(acc, s_lend, s_park, s_tile);
+    int jtj[kTermLimbs];
+    pass_jtj00<true>(jtj);
     __syncthreads();
-    finish_pass<BLOCK>(acc, p, s_red, &s_flag, p.sol.tag, 0, 0u, nblocks);
+    finish_pass<BLOCK, false, true>(acc, p, s_red, &s_flag, p.sol.tag, 0, 0u, nblocks, holders, jtj);
 }
 
 // multi-GPU with host-side solve: hand the all-reduced limb totals to the host

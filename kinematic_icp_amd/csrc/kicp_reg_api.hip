@@ -157,6 +157,7 @@ int kicp_reg_set_option(kicp_reg *reg, const char *name, double value) {
     else if (k == "batch_threads") reg->batch_threads = std::min<int>(std::max(static_cast<int>(value), 0), kMaxBatchQueues + 1);
     else if (k == "batch_depth") reg->batch_depth = std::min<int>(std::max(static_cast<int>(value), 1), kPipeSlots);
     else if (k == "latency_kernel") reg->latency_kernel = value == 2.0 ? 2 : (value == 1.0 ? 1 : 0);
+    else if (k == "pass_tiles") reg->pass_tiles = clamp_pass_tiles(value);  // 0 automatic (default) | 1, 2, 4 blocks of 256 queries per workgroup
     else if (k == "aql") reg->use_aql = value != 0.0 ? 1 : 0;
     else if (k == "bar_frame") reg->use_bar_frame = value != 0.0 ? 1 : 0;
     else if (k == "fetch_upload") reg->fetch_frames = value != 0.0 ? 1 : 0;
@@ -209,6 +210,7 @@ double kicp_reg_get_option(const kicp_reg *reg, const char *name) {
     if (k == "batch_queue_passes") return static_cast<double>(reg->batch_queue_passes);
     if (k == "batch_resident_passes") return static_cast<double>(reg->batch_resident_passes);
     if (k == "latency_kernel") return reg->latency_kernel;
+    if (k == "pass_tiles") return reg->pass_tiles;
     if (k == "timing") return reg->timing;
     if (k == "aql") return reg->use_aql;
     if (k == "aql_kernarg") return !reg->aql.ready ? -1.0 : (std::strcmp(reg->aql.kernarg_place(), "host memory") == 0 ? 0.0 : (std::strcmp(reg->aql.kernarg_place(), "device memory") == 0 ? 1.0 : 2.0));
@@ -420,6 +422,7 @@ int kicp_reg_clone(const kicp_reg *reg, kicp_reg **out) {
     c->use_bar_frame = reg->use_bar_frame, c->fetch_frames = reg->fetch_frames;
     c->wait_mode = reg->wait_mode, c->timing = reg->timing;
     c->query_every = reg->query_every, c->lanes_per_query = reg->lanes_per_query, c->latency_kernel = reg->latency_kernel;
+    c->pass_tiles = reg->pass_tiles;
     c->p2p_rows = reg->p2p_rows, c->use_aql = reg->use_aql;
     c->small_cmd = reg->cmd_bar ? 1 : reg->small_cmd, c->use_small = reg->use_small, c->small_block = reg->small_block, c->small_wave = reg->small_wave;
     c->wave_block = reg->wave_block, c->small_resident = reg->small_resident, c->small_timeout_us = reg->small_timeout_us, c->small_group_rows = reg->small_group_rows;

@@ -336,6 +336,7 @@ int run_batch_resident_threads(kicp_reg *r, kicp_map *map, size_t count, const d
     for (int t = 1; t < threads; ++t) {
         kicp_reg *h = r->batch_lanes[t - 1];
         h->cfg = r->cfg, h->query_every = r->query_every, h->dbg = 0, h->latency_kernel = r->latency_kernel, h->batch_queues = 0, h->batch_threads = 0;
+        h->pass_tiles = r->pass_tiles, h->scans_in_flight = 1;
         h->use_small = r->use_small, h->small_wave = r->small_wave, h->wave_block = r->wave_block, h->small_block = r->small_block, h->small_resident = r->small_resident;
         h->small_group_rows = r->small_group_rows, h->small_timeout_us = r->small_timeout_us, h->batch_depth = r->batch_depth, h->batch_rotate = r->batch_rotate;
         h->batch_resident = 1, h->resident_generic = 1, h->small_cmd = r->cmd_bar ? 1 : r->small_cmd;

@@ -118,6 +118,8 @@ struct kicp_reg {
     int query_every = 512; // polls between hipStreamQuery calls while waiting (a call costs ~1 us of host time)
     int lanes_per_query = 0;  // variant 3: sub-lanes sharing one query (1, 2 or 4); 0 = by scan size
     int latency_kernel = 1;   // variant 3, one lane per query: the two-voxels-per-round build (0 never | 1 scans <= kLatencyMaxPoints | 2 always)
+    int pass_tiles = 0;       // option "pass_tiles": blocks of 256 queries per workgroup of the four-waves build (0 by scan size: auto_pass_tiles | 1, 2, 4)
+    int scans_in_flight = 1;  // a batch lane's handle: the scans the batch keeps on the device at once (auto_pass_tiles; set per batch call)
     // multi-GPU
     // RCCL: the communicator of single calls; a sharded batch call (run_batch_queues) gives every lane a communicator of its own, split off
     // this one on first use, so that each lane issues ITS collectives in its own fixed order on its own stream (lane_comms: owned here,
@@ -294,7 +296,9 @@ struct HostLoop {
 };
 double wait_timeout_s();
 int lanes_for(const kicp_reg *r, size_t n);
-uint32_t pass_grid(const kicp_reg *r, size_t n);
+// `jobs`: the pass goes out in a job list (k_pass_gather32_jobs: the four-waves build whatever the scan's size)
+uint32_t pass_tiles(const kicp_reg *r, size_t n, bool jobs = false);
+uint32_t pass_grid(const kicp_reg *r, size_t n, bool jobs = false);
 bool aql_up(kicp_reg *r);
 const AqlKernel *aql_lookup(kicp_reg *r, int key, const char *demangled_prefix);
 const AqlKernel *aql_kernel_for(kicp_reg *r, int b, int g, int occ, bool split, bool lat);

@@ -38,9 +38,26 @@ int lanes_for(const kicp_reg *r, size_t n) {
     if (r->lanes_per_query > 0) return r->lanes_per_query;
     return n <= 4096 ? 4 : (n <= 32768 ? 2 : 1);
 }
-uint32_t pass_grid(const kicp_reg *r, size_t n) {
+// the latency-oriented build (two neighbour voxels per round, two waves per SIMD): scans of one lane per query that
+// leave the machine at most two waves per SIMD anyway
+static bool latency_build_for(const kicp_reg *r, size_t n) {
+    return lanes_for(r, n) == 1 && (r->latency_kernel == 2 || (r->latency_kernel == 1 && n <= kLatencyMaxPoints));
+}
+static size_t pass_blocks(const kicp_reg *r, size_t n) {
     const size_t threads = n * static_cast<size_t>(lanes_for(r, n));
-    return static_cast<uint32_t>(std::max<size_t>(1, (threads + kPassBlock - 1) / kPassBlock));
+    return std::max<size_t>(1, (threads + kPassBlock - 1) / kPassBlock);
+}
+// Blocks of 256 queries per workgroup (PassParams::tiles): more than one in the one-lane-per-query four-waves build only - the
+// build of every job list and of launch_pass' larger scans.  The ablation switches ("dbg") count per block: one tile.
+uint32_t pass_tiles(const kicp_reg *r, size_t n, bool jobs) {
+    if (r->dbg != 0 || lanes_for(r, n) != 1 || (!jobs && latency_build_for(r, n))) return 1u;
+    if (r->pass_tiles > 0) return static_cast<uint32_t>(std::min(r->pass_tiles, kMaxPassTiles));
+    return auto_pass_tiles(pass_blocks(r, n), r->scans_in_flight, r->num_cus);
+}
+// the workgroups of a pass
+uint32_t pass_grid(const kicp_reg *r, size_t n, bool jobs) {
+    const size_t tiles = pass_tiles(r, n, jobs);
+    return static_cast<uint32_t>((pass_blocks(r, n) + tiles - 1) / tiles);
 }
 // AQL kernel objects, looked up once per template instantiation by DEMANGLED name (kicp_aql.hpp), or nullptr
 bool aql_up(kicp_reg *r) {
@@ -95,12 +112,12 @@ int aql_quiesce(kicp_reg *r) {
 //   one lane per query, two waves per SIMD, two neighbour voxels per round (LAT)   scans of up to 131 072 points, one call at a time
 //   one lane per query, four waves per SIMD                                        larger scans; several scans in flight
 //   two lanes per query sharing every bucket / four lanes per query               scans of up to 32 768 / 4 096 points
-int launch_pass(kicp_reg *r, const PassParams &p, bool allow_aql) {
+int launch_pass(kicp_reg *r, const PassParams &args, bool allow_aql) {
+    PassParams p = args;
+    p.tiles = pass_tiles(r, p.n);  // (the callers size rows and buffers by pass_grid, which divides by the same number)
     const uint32_t grid = pass_grid(r, p.n);
     const int g = lanes_for(r, p.n);
-    // the latency-oriented build (two neighbour voxels per round, two waves per SIMD): scans of one lane per query that
-    // leave the machine at most two waves per SIMD anyway
-    const bool lat = g == 1 && (r->latency_kernel == 2 || (r->latency_kernel == 1 && p.n <= kLatencyMaxPoints));
+    const bool lat = latency_build_for(r, p.n);
     const int occ = lat ? 2 : 4;
     const bool split = g == 2;
     // While HIP work may be pending on the handle's stream (a frame upload, a mirror refresh, a clear) the kernel goes

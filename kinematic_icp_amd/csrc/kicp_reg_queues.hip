@@ -221,7 +221,8 @@ static int group_launch(kicp_reg *r, GroupLane &L, int group, size_t slot_groups
         sol.convergence_criterion = h->cfg.convergence_criterion;
         sol.call_id = ++h->call_id, sol.rec = h->rec.dev(), sol.pub_rows = h->rows.dev() + s * slot_groups * kReduceWords;
         sol.tag = j.tag = tag0 + static_cast<uint32_t>(s);
-        const uint32_t grid = pass_grid(h, n[j.k]);
+        pp.tiles = pass_tiles(h, n[j.k], true);  // (per job: a list may mix tile counts)
+        const uint32_t grid = pass_grid(h, n[j.k], true);
         L.jp.nblocks[s] = grid, grid_x = std::max(grid_x, grid);
         j.rows = (grid + kGroup - 1) / kGroup, j.row_next = 0, j.collected = false, j.goes_on = false;
         for (auto &w : j.words) w = 0;
@@ -262,7 +263,7 @@ static int run_batch_groups(kicp_reg *r, kicp_map *map, size_t count, const doub
     for (size_t k = 0; k < count; ++k) {
         const SmallPlan pl = h0->use_small ? small_plan(h0, n[k]) : SmallPlan();
         solo[k] = (pl.grid != 0 && !pl.generic) || lanes_for(h0, n[k]) != 1;
-        if (!solo[k]) slot_groups = std::max<size_t>(slot_groups, (pass_grid(h0, n[k]) + kGroup - 1) / kGroup);
+        if (!solo[k]) slot_groups = std::max<size_t>(slot_groups, (pass_grid(h0, n[k], true) + kGroup - 1) / kGroup);
     }
     BatchGroups sched(count, group, solo);
     auto leave = [&](int rc) {  // nothing of this call may still be running when it returns: the caller owns the frames
@@ -450,6 +451,7 @@ int run_batch_queues(kicp_reg *r, kicp_map *map, size_t count, const double *con
         kicp_reg *h = r->batch_lanes[j];
         h->cfg = r->cfg, h->lanes_per_query = r->lanes_per_query;
         h->query_every = r->query_every, h->dbg = r->dbg, h->latency_kernel = 0, h->small_resident = 0, h->batch_queues = 0;
+        h->pass_tiles = r->pass_tiles, h->scans_in_flight = group > 1 ? lanes * group : lanes;
         h->small_group_rows = r->small_group_rows;
         h->use_small = sharded ? 0 : r->use_small, h->small_block = r->small_block, h->small_wave = r->small_wave, h->wave_block = r->wave_block;
         flights[j].h = h;

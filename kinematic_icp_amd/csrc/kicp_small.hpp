@@ -167,14 +167,16 @@ __device__ __forceinline__ void small_publish(const Acc &a, const SmallParams &s
     }
     __syncthreads();
     if (wave != 0) return;
+    if (sp.group_rows) {  // one row per group of 32 workgroups reaches the host (kicp_kernels.hpp::counting_hand_over)
+        long long l[3];
+        workgroup_row_words<BLOCK / 64>(s_red, lane, l);
+        counting_hand_over(l, (*s_flag & 2) ? 1 : 0, gave_up, sp.p, tag, pass % kPipeSlots, pass % kPipeSlots, lane);
+        return;
+    }
     I128 t{0ull, 0ll};
     if (lane < kNumSums)
         for (int w = 0; w < BLOCK / 64; ++w)
             i128_add_limb_sums(t, s_red[w][kTermLimbs * lane], s_red[w][kTermLimbs * lane + 1], s_red[w][kTermLimbs * lane + 2], s_red[w][kTermLimbs * lane + 3]);
-    if (sp.group_rows) {  // one row per group of 32 workgroups reaches the host (kicp_kernels.hpp::counting_hand_over)
-        counting_hand_over(t, (*s_flag & 2) ? 1 : 0, gave_up, sp.p, tag, pass % kPipeSlots, pass % kPipeSlots, lane);
-        return;
-    }
     // |workgroup sum| < 2^83 * BLOCK: bits 0..47 and 48..95 (the upper half carries the sign)
     const unsigned long long m48 = (1ull << 48) - 1;
     const unsigned long long h0 = t.lo & m48, h1 = ((t.lo >> 48) | (static_cast<unsigned long long>(t.hi) << 16)) & m48;

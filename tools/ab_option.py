@@ -26,6 +26,7 @@ ap.add_argument("--fixed", action="append", default=[], help="name=value options
 ap.add_argument("--multi", action="store_true")
 ap.add_argument("--blocks", type=int, default=40)
 ap.add_argument("--calls", type=int, default=250)
+ap.add_argument("--points", type=int, default=0, help="thin every scan to this many points (evenly over its rings; 0: the whole scan)")
 ap.add_argument("--batch", action="store_true", help="a block is ONE kicp_register_device_batch call of --calls scans (what bench.py times)")
 args = ap.parse_args()
 
@@ -35,7 +36,13 @@ ident = np.array([0, 0, 0, 1.0, 0, 0, 0])
 syn.build_map_points(scene, cfg, lambda pts: gmap.UpdateDevice(K.DeviceFrame(pts), ident), gmap.num_points, rng)
 gmap.sync(0)
 tau = cfg.first_frame_tau()
-frames = [K.DeviceFrame(s["frame"]) for s in scans]
+def thinned(frame):
+    if args.points <= 0 or args.points >= len(frame):
+        return frame
+    return np.ascontiguousarray(frame[np.linspace(0, len(frame) - 1, args.points).astype(np.int64)])
+
+
+frames = [K.DeviceFrame(thinned(s["frame"])) for s in scans]
 extra = syn.planar_pose(0.2, 0.0, np.deg2rad(1.5)) if args.multi else syn.planar_pose(0.0, 0.0, 0.0)
 rels = [syn.pose_mul(s["rel_odom"], extra) for s in scans]
 regs, labels = [], []
@@ -66,7 +73,7 @@ for b in range(args.blocks):
         us[j].append((time.perf_counter() - t0) / args.calls * 1e6)
 if args.batch:
     poses = [b.out.copy() for b in batches]
-out = {"workload": args.workload, "multi": args.multi, "iterations": regs[0].last_stats.iterations,
+out = {"workload": args.workload, "points": len(thinned(scans[0]["frame"])), "multi": args.multi, "iterations": regs[0].last_stats.iterations,
        "same_pose": bool(all(np.array_equal(p, poses[0]) for p in poses))}
 for v, u in zip(labels, us):
     out[v] = {"median_us": round(float(np.median(u)), 2), "p10_us": round(float(np.percentile(u, 10)), 2), "min_us": round(float(np.min(u)), 2)}
