@@ -334,18 +334,25 @@ __device__ __forceinline__ uint32_t table_lookup(const MapView &m, int32_t x, in
 // the whole entry: bucket value and the 27-bit neighbour-occupancy mask (0 when the voxel has no entry at all,
 // i.e. none of its 27 neighbours holds a point)
 // slot index of the entry (for its nb[] record) and the 27-bit neighbour-occupancy mask; nbr == 0 when the voxel has
-// no entry at all, i.e. none of its 27 neighbours holds a point
-__device__ __forceinline__ void table_lookup_entry(const MapView &m, int32_t x, int32_t y, int32_t z, uint32_t &slot, uint32_t &nbr) {
+// no entry at all, i.e. none of its 27 neighbours holds a point.  `val`: the entry's own bucket value (a halo entry's where the voxel
+// itself holds no points: bit 0 of nbr is clear then), for the caller that visits the own voxel without reading nb[0]
+template <bool WITH_VAL>
+__device__ __forceinline__ void table_lookup_entry(const MapView &m, int32_t x, int32_t y, int32_t z, uint32_t &slot, uint32_t &nbr, uint32_t &val) {
     uint32_t h = voxel_hash(x, y, z) & m.mask;
     for (;;) {
-        const int4 e = *reinterpret_cast<const int4 *>(m.table + h);
-        const uint32_t n = m.table[h].nbr;  // same cache line: issued together with the key
+        int4 e = *reinterpret_cast<const int4 *>(m.table + h);
+        uint32_t n = m.table[h].nbr;  // same cache line: issued together with the key
+        // (all five words are wanted HERE: left to itself the compiler loads val, tests it, then loads the key, then nbr - three
+        // round trips to one cache line in every wave's chain.  Only the build that asks for val is made to: the five registers
+        // this holds at once are not free in every kernel that probes.)
+        if (WITH_VAL) asm volatile("; the entry's key, val and nbr" : "+v"(e.x), "+v"(e.y), "+v"(e.z), "+v"(e.w), "+v"(n));
         if (static_cast<uint32_t>(e.w) == kEmptyVal) {
             slot = 0u, nbr = 0u;
             return;
         }
         if (e.x == x && e.y == y && e.z == z) {
             slot = h, nbr = n;
+            if (WITH_VAL) val = static_cast<uint32_t>(e.w);
             return;
         }
         h = (h + 1) & m.mask;
@@ -1052,6 +1059,18 @@ __device__ __forceinline__ void best3_merge(Best3 &t, const Best3 &o) {
     t.b3 = fminf(t.b3, o.b3);  // o.b3 can never undercut the runner-up of a set that already holds o.b1 <= o.b2
 }
 
+// best3_merge(t, o) for a `t` that holds nothing yet, t = {B, B, B, none, none, 0, 0}, and o.b1 <= o.b2 <= o.b3 as a trip's
+// tournament leaves them - compare for compare: the first update takes o's winner iff o.b1 < B and leaves the rest at B; the second
+// finds o.b2 >= the new t.b1 (o.b1, or B <= o.b1) and takes the runner-up's place iff o.b2 < B; t.b3 stays B but for o.b3.
+// Three compares and six selects where the merge into an unknown record takes ~40 instructions.
+__device__ __forceinline__ void best3_assign_fresh(Best3 &t, const Best3 &o) {
+    const float B = t.b1;
+    const bool lt1 = o.b1 < B, lt2 = o.b2 < B;
+    t.b1 = lt1 ? o.b1 : B, t.i1 = lt1 ? o.i1 : kNoIndex32, t.o1 = lt1 ? o.o1 : 0u;
+    t.b2 = lt2 ? o.b2 : B, t.i2 = lt2 ? o.i2 : kNoIndex32, t.o2 = lt2 ? o.o2 : 0u;
+    t.b3 = fminf(B, o.b3);
+}
+
 // PointToVoxel component: static_cast<int>(floor(c / vs)) as the reference evaluates it (kiss-icp v1.2.0 core/VoxelUtils.hpp),
 // without paying an fp64 division for every coordinate: t = c * (1 / vs) agrees with fl(c / vs) to a few ulps, so the two
 // floors can only differ when t lies within that distance of an integer - and only then is the division carried out.
@@ -1102,7 +1121,9 @@ __device__ __forceinline__ void make_query_of(Query &q, const PassParams &p, con
 // plus 4.2e-6 D for the fp32 squares / sums and the 5 mantissa bits dropped for the integer tournament.  sp.margin_u covers
 // the errors of BOTH candidates of a decision with 10 % to spare, for D up to the acceptance bound (and never farther than
 // the 27-voxel neighbourhood reaches, D <= 12 voxel sizes^2): computed on the host (search_params()).
-__device__ __forceinline__ void start_lane(Lane &L, const PassParams &p, const double *__restrict__ src, const Pose &T, uint32_t i, bool valid, KeptQuery *kept = nullptr) {
+template <bool OWN_VAL>
+__device__ __forceinline__ void start_lane(Lane &L, const PassParams &p, const double *__restrict__ src, const Pose &T, uint32_t i, bool valid, uint32_t &own_val,
+                                           KeptQuery *kept = nullptr) {  // OWN_VAL: the caller wants the probe's `own_val`
     const SearchParams &sp = p.search;
     L.i = valid ? i : kNoIndex32;
     L.q.slot0 = 0u, L.todo = 0u;
@@ -1115,10 +1136,16 @@ __device__ __forceinline__ void start_lane(Lane &L, const PassParams &p, const d
     L.q.lz = static_cast<float>((q.z - q.vz * vs) * sp.upm);
     // ONE probe at the own voxel: the occupancy mask of the 27 neighbours (bit s = shift s of the reference's order) and
     // the record of their buckets.  Only voxels that hold points are ever visited; empty space costs nothing.
-    if (valid && dbg_not(p, 2)) table_lookup_entry(p.map, q.vx, q.vy, q.vz, L.q.slot0, L.todo);
+    // (`own_val`: the entry's own bucket value, for a first round that visits the own voxel straight from the probe - visit_first)
+    own_val = 0u;
+    if (valid && dbg_not(p, 2)) table_lookup_entry<OWN_VAL>(p.map, q.vx, q.vy, q.vz, L.q.slot0, L.todo, own_val);
     if (dbg_is(p, 3)) L.todo &= 1u;     // experiments: own voxel only
     if (dbg_is(p, 5)) L.todo &= 0x7Fu;  // own + faces
     if (dbg_is(p, 4)) L.todo = 0u;      // probe only, no bucket visit
+}
+__device__ __forceinline__ void start_lane(Lane &L, const PassParams &p, const double *__restrict__ src, const Pose &T, uint32_t i, bool valid, KeptQuery *kept = nullptr) {
+    uint32_t own_val;  // (not wanted)
+    start_lane<false>(L, p, src, T, i, valid, own_val, kept);
 }
 // drop the neighbour voxels that cannot hold anything within the margin of `best` (units^2).  A voxel's lower bound is the sum of
 // the squared distances to the faces crossed on the way to it (one term for the six face neighbours, two for the twelve edge
@@ -1163,7 +1190,9 @@ __device__ __forceinline__ void load_trip(const uint4 *bt, uint4 (&c)[N / 2]) {
 #pragma unroll
     for (int u = 0; u < N / 2; ++u) c[u] = bt[u];
 }
-template <int N, int PARTS>
+// FRESH: `t` is known to be the record a search starts from, {B, B, B, none, none, 0, 0} with B = the acceptance bound (start_lane),
+// and this is a bucket's first trip: what the trip found is ASSIGNED (best3_assign_fresh), not merged.
+template <int N, int PARTS, bool FRESH = false>
 __device__ __forceinline__ bool process_trip(const uint4 (&c)[N / 2], uint32_t pos0, uint32_t base, int s, const v2f qx, const v2f qy, const v2f qz, Best3 &t,
                                              float margin) {
     // All distances first (independent), then the minimum as a tournament over integer keys: a non-negative
@@ -1206,7 +1235,8 @@ __device__ __forceinline__ bool process_trip(const uint4 (&c)[N / 2], uint32_t p
         // with fewer than three points the far key stands in (finite, beyond every real distance)
         Best3 o{m1, __uint_as_float(min(key2, kFarKey) & ~31u), __uint_as_float(min(key3, kFarKey) & ~31u), base + k1,
                 base + k2, static_cast<uint32_t>(s) * kOrdStride + k1, static_cast<uint32_t>(s) * kOrdStride + k2};
-        best3_merge(t, o);
+        if (FRESH) best3_assign_fresh(t, o);
+        else best3_merge(t, o);
     }
     return more;
 }
@@ -1236,6 +1266,26 @@ __device__ __forceinline__ void visit_bucket(const Probe &P, Best3 &t, const Map
         uint4 c[kMine / 2];
         load_trip<kMine>(b + (k0 + first) / 2, c);
         if (!process_trip<kMine, PARTS>(c, k0 + first, base, s, q.x, q.y, q.z, t, margin)) break;
+    }
+}
+// The FIRST visit of a query, with the record start_lane left.  Where it goes to the own voxel (s == 0: two queries of three on a
+// 64-beam scan) the bucket is the one the probe's entry names (`val`: no load of nb[0] behind the probe); a query whose own voxel
+// holds no points reads its first neighbour's bucket from the entry's record as every later visit does.  The first trip's findings
+// are assigned to the fresh record (process_trip FRESH); a bucket deeper than one trip (max_points_per_voxel > kTrip) goes on with
+// the generic trip.
+__device__ __forceinline__ void visit_first(const Probe &P, Best3 &t, const MapView &m, int s, uint32_t val, float margin) {
+    uint32_t bucket = val_bucket(val, m.cbits);
+    if (s != 0) bucket = m.table[P.slot0].nb[s];
+    const uint32_t base = bucket * m.cap;
+    const uint32_t stride16 = m.cap16;
+    const uint4 *b = reinterpret_cast<const uint4 *>(m.pool16 + static_cast<size_t>(bucket) * stride16);
+    const QueryFrom q = query_from(P, s);
+    uint4 c[kTrip / 2];
+    load_trip<kTrip>(b, c);
+    bool more = process_trip<kTrip, 1, true>(c, 0u, base, s, q.x, q.y, q.z, t, margin);
+    for (uint32_t k0 = kTrip; more && k0 < stride16; k0 += kTrip) {
+        load_trip<kTrip>(b + k0 / 2, c);
+        more = process_trip<kTrip, 1>(c, k0, base, s, q.x, q.y, q.z, t, margin);
     }
 }
 // Latency-oriented round (scans that leave the machine two waves per SIMD: every dependent memory access is ~0.9 us of a wave's
@@ -1414,7 +1464,12 @@ __device__ __forceinline__ void gather32_pass(const PassParams &p, const Pose &T
     Lane L;
     KeptQuery kept;
     static_assert(!(LAT && PARK), "the latency-oriented build keeps the query in registers");
-    start_lane(L, p, src, T, i, valid, (LAT || PARK) ? &kept : nullptr);
+    // (the pass kernels' one-lane-per-query build whose idle lanes take over voxels has a first round of its own, see below; the
+    // kernels that score poses through ACC share that build's register budget and have none to spare for it)
+    constexpr bool kFirstRound = G == 1 && !LAT && PARK && ACC::kKind == AccKind::Pass;
+    const bool first_round = kFirstRound && lend != nullptr && dbg_not(p, 11) && dbg_not(p, 15);
+    uint32_t own_val = 0u;
+    start_lane<kFirstRound>(L, p, src, T, i, valid, own_val, (LAT || PARK) ? &kept : nullptr);
     if (PARK) {
         park[0 * BLOCK + tid] = kept.q.x, park[1 * BLOCK + tid] = kept.q.y, park[2 * BLOCK + tid] = kept.q.z;
         park[3 * BLOCK + tid] = kept.sx, park[4 * BLOCK + tid] = kept.sy;
@@ -1430,6 +1485,26 @@ __device__ __forceinline__ void gather32_pass(const PassParams &p, const Pose &T
     }
     float cull = L.t.b1;  // running minimum shared by the G sub-lanes (culling only)
     uint32_t rounds = 0u;  // (wave-uniform; read by the dbg 10 census only)
+    // THE FIRST ROUND of the lending build.  Every lane that visits anything in it does so with the record start_lane left, most
+    // of them at their own voxel (bit 0: the first shift of the order), and nobody lends before round 2 - so the round is written
+    // out for that case (visit_first) and skips what the generic round pays for nothing: cull_todo, the load of nb[0] behind the
+    // probe, the merge into a record that holds nothing, and the lending round's copies of record and probe.
+    // Without the cull a lane takes the first OCCUPIED voxel of the order: its own wherever that holds points (bit 0 is always
+    // alive), else - a third of a 64-beam scan's queries: the own voxel empty, a halo entry - the first occupied neighbour, even
+    // one that lies beyond the acceptance bound and that the cull would have dropped.  Such a visit is wasted but harmless: a culled
+    // voxel can never hold the winner, a voxel visited needlessly cannot change the outcome, and the visiting order travels with
+    // every candidate.  Every other bit is culled at the top of round 2 against a minimum that can only be sharper than the bound.
+    // (Letting those lanes sit the round out instead costs a round for a third of the lanes: +14 % instructions, measured.)
+    // (dbg 15: the in-process A/B switch of this round.)
+    if (first_round && __any(L.todo != 0u)) {
+        ++rounds;
+        if (L.todo) {
+            const int s = __ffs(L.todo) - 1;
+            L.todo &= L.todo - 1u;
+            visit_first(L.q, L.t, m, s, own_val, margin);
+        }
+        cull = L.t.b1;
+    }
     while (__any(L.todo != 0u)) {
         ++rounds;
         // which of the 27 neighbours could still hold something within the margin of the current minimum
