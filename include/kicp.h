@@ -860,6 +860,99 @@ int kicp_gain_from_occupancy(const signed char *occupancy, unsigned int width, u
                              size_t n_views, unsigned int *out /* n_views x 4 */, size_t cap_out);
 int kicp_grid_gain(const kicp_grid *grid, const kicp_gain_config *config, const unsigned int *views, size_t n_views, unsigned int *out, size_t cap_out);
 
+/* ---- uneven ground: a column of heights per cell, and traversability by height over the local ground (kicp_elev.hip) -----------------
+ * The grid above calls a return an obstacle when its BASE-FRAME z lies in a fixed band.  Where the floor is not one plane that is
+ * wrong: a ramp ahead rises into the band and becomes a wall, a kerb or a drop below the band is invisible, a ceiling or a table top is
+ * an obstacle or not by where z_max was put.  What decides is height over the LOCAL GROUND, so this layer keeps which world heights have
+ * ever returned in every cell, and reads three classes off that.  Everything below is exact and integer from the floor on.
+ *
+ * THE LAYER is world aligned with the grid's geometry - width x height cells of side `cell` from (origin_x, origin_y), cell (ix, iy) at
+ * iy * width + ix, max_ray - so its arrays overlay a kicp_grid of equal geometry, and a vertical one: z_origin and slab, in metres.
+ * Each cell holds one 64-bit COLUMN: bit b is set when some used return ever had a world height in [z_origin + b slab, z_origin +
+ * (b + 1) slab).  Bits are only ever set.
+ *
+ * A FRAME is n points in the base frame, the pose and the sensor's origin in the base frame, exactly as for kicp_grid_integrate.  With R,
+ * t of the pose (pose_to_rt, evaluated once on the host):
+ *   wx = ((r00 p.x + r01 p.y) + r02 p.z) + t0,  wy with row 1 and wz with row 2 likewise (every operation rounded on its own),
+ *   cx = floor((wx - origin_x) / cell),  cy = floor((wy - origin_y) / cell),  s = floor((wz - z_origin) / slab);
+ * the sensor's origin goes through the same arithmetic to the sensor cell (sx, sy); reach = ceil(max_ray / cell).  Each point falls into
+ * exactly one of four classes, tested in this order, every comparison on doubles before any conversion:
+ *   1 SKIPPED         p.x, p.y or p.z not finite, or wx, wy or wz not finite, or max(|cx - sx|, |cy - sy|) > reach (a comparison with
+ *                     a NaN is false: a sensor cell that is not finite skips every point);
+ *   2 OUTSIDE_GRID    not (0 <= cx < width and 0 <= cy < height);
+ *   3 OUTSIDE_COLUMN  not (0 <= s <= 63);
+ *   4 USED            bit s of the column of cell (cx, cy) is set.
+ * There is no height band: every return counts.  The frame's statistics are six words: used, skipped, outside_grid, outside_column,
+ * new_bits - bits that were clear before this frame - and new_cells - columns that were zero before this frame.  The first four sum to
+ * n; all six depend only on the SET of (cell, slab) pairs of the frame and on the columns before it, not on the points' number or
+ * order.  n == 0 is legal: nothing changes, the frame is counted.  n > 0x7FFFFFF0 / 3: KICP_ERR_CAPACITY.
+ *
+ * TRAVERSABILITY.  With step_slabs = S, 0 <= S <= 62, and robot_slabs = H, S < H <= 64 (KICP_ERR_ARG otherwise), a cell with column c is
+ *   -1 (unknown) when c == 0; otherwise, with g the index of the lowest set bit of c - the GROUND -,
+ *   BODY  when some bit b of c has g + S < b <= g + H: something between step height and robot height over the ground; bits above
+ *         g + H are overhead and ignored;
+ *   STEP  when some 8-neighbour inside the grid has a column that is not zero whose ground g_n satisfies g - g_n > S: the HIGHER cell
+ *         of an edge is marked, which keeps the robot off a kerb it would hit and off a ledge it would fall from;
+ *   100 when BODY or STEP, else 0.  Neighbours outside the grid and unknown neighbours say nothing.
+ * The entries take a rectangle x0, y0, w, h by the clearance entries' rule above: inside the grid, w and h >= 1, cap == w * h
+ * (KICP_ERR_ARG otherwise), h * w values row-major from (x0, y0), and the result for a rectangle EQUALS the full grid's restricted to
+ * it.  They write `out`, signed char classes in kicp_grid_occupancy's convention; out_ground (nullable), one unsigned char per cell: g,
+ * 255 for an unknown cell; out_counts (nullable), four words: unknown, traversable, BODY, STEP only.  A frame changes classes only
+ * inside its window grown by one cell; kicp_elev_last_window gives that window by kicp_grid_last_window's rules.
+ * kicp_elev_traversability works on the columns where they are, in HBM, and returns after its kernel has completed and the values
+ * have arrived; kicp_elev_traversability_from_columns is the same arithmetic as pure host code over columns in kicp_elev_columns'
+ * layout (width * height <= 2^28, KICP_ERR_CAPACITY otherwise) and needs no GPU.
+ *
+ * INTO THE PLANNER'S CHAIN.  kicp_elev_to_grid writes the class of every cell into the counters of a kicp_grid whose cell, origin_x,
+ * origin_y, width and height are bit-equal to the layer's, on the same device (KICP_ERR_ARG otherwise): an obstacle becomes (hits 1,
+ * misses 0), a traversable cell (0, 1), an unknown cell (0, 0).  It replaces ALL counters, with the consequences kicp_grid_set_counts
+ * has; the caller dedicates a grid handle to it.  At min_observations = 1 every GPU entry of that grid - kicp_grid_costmap,
+ * kicp_grid_potential, kicp_grid_score_arcs, kicp_grid_frontiers, kicp_grid_gain - then runs on traversability, without a byte
+ * crossing PCIe.
+ *
+ * KNOWN LIMITATIONS.  Bits never clear: a passer-by leaves a BODY cell until kicp_elev_clear or kicp_elev_set_columns.  One spurious
+ * low return lowers a cell's ground for good.  A cell that has only ever returned an overhang, its ground unseen, reads as a high ground
+ * and is marked STEP until a ground return arrives - conservative by choice.  There is no slope limit over a baseline longer than one
+ * cell, and no merge with the free space the grid's rays carve.
+ *
+ * Limits: width * height <= 2^28 and reach <= 4095 (KICP_ERR_CAPACITY, the size in the message); cell, max_ray and slab positive and
+ * finite, the origin and z_origin finite, width and height >= 1, no null pointer but the nullable outputs (KICP_ERR_ARG).  Every
+ * entry returns after its work on the GPU has completed. */
+typedef struct kicp_elev kicp_elev;
+typedef struct kicp_elev_config {
+    double cell, origin_x, origin_y; /* metres */
+    unsigned int width, height;      /* cells */
+    double z_origin, slab;           /* metres: bit b of a column is the world heights [z_origin + b slab, z_origin + (b + 1) slab) */
+    double max_ray;                  /* metres: returns whose cell is farther than ceil(max_ray / cell) cells from the sensor's are skipped */
+} kicp_elev_config;
+typedef struct kicp_elev_traversability_config {
+    unsigned int step_slabs;  /* S: the highest step the robot takes, in slabs: 0 .. 62 */
+    unsigned int robot_slabs; /* H: the robot's height in slabs: S < H <= 64 */
+} kicp_elev_traversability_config;
+#define KICP_ELEV_STATS 6
+int kicp_elev_create(const kicp_elev_config *config, int device, kicp_elev **out);
+void kicp_elev_destroy(kicp_elev *elev);
+/* the configuration, reach, and the frames integrated since creation or the last kicp_elev_clear (each nullable) */
+int kicp_elev_info(const kicp_elev *elev, kicp_elev_config *out_config, int *out_reach, unsigned long long *out_frames);
+int kicp_elev_clear(kicp_elev *elev); /* every column and the frame count back to zero */
+/* One frame: from host memory (through the handle's pinned staging buffer), or where the points already are in HBM, complete - what
+ * the drop-in pipeline calls.  out_stats (nullable): the six words above. */
+int kicp_elev_integrate(kicp_elev *elev, const double *frame_xyz, size_t n, const double pose_qt[7], const double sensor_xyz[3],
+                        unsigned long long out_stats[6]);
+int kicp_elev_integrate_device(kicp_elev *elev, const double *d_frame_xyz, size_t n, const double pose_qt[7], const double sensor_xyz[3],
+                               unsigned long long out_stats[6]);
+/* The columns, one 64-bit word per cell; cap_cells / cells must be the layer's width * height (KICP_ERR_ARG otherwise).
+ * kicp_elev_set_columns replaces them all (the frame count is not part of them). */
+int kicp_elev_columns(const kicp_elev *elev, unsigned long long *out, size_t cap_cells);
+int kicp_elev_set_columns(kicp_elev *elev, const unsigned long long *in, size_t cells);
+int kicp_elev_last_window(const kicp_elev *elev, unsigned int *x0, unsigned int *y0, unsigned int *w, unsigned int *h);
+int kicp_elev_traversability(const kicp_elev *elev, const kicp_elev_traversability_config *config, unsigned int x0, unsigned int y0, unsigned int w,
+                             unsigned int h, signed char *out, unsigned char *out_ground, unsigned long long out_counts[4], size_t cap);
+int kicp_elev_traversability_from_columns(const unsigned long long *columns, unsigned int width, unsigned int height,
+                                          const kicp_elev_traversability_config *config, unsigned int x0, unsigned int y0, unsigned int w, unsigned int h,
+                                          signed char *out, unsigned char *out_ground, unsigned long long out_counts[4], size_t cap);
+int kicp_elev_to_grid(const kicp_elev *elev, const kicp_elev_traversability_config *config, kicp_grid *grid);
+
 /* ---- map points the new frame sees through: a cube-map depth test (kicp_view.hip) ----------------------------------------------------
  * The local map loses points by distance only (RemovePointsFarFromLocation); whatever stood in view for one frame - a person crossing,
  * a forklift, a door leaf - stays until the robot is max_range away.  A kicp_view holds a depth image of ONE frame, and

@@ -88,6 +88,18 @@ class GainConfig(C.Structure):
     _fields_ = [("min_observations", C.c_uint), ("occupied_thresh", C.c_double), ("range_cells", C.c_uint)]
 
 
+class ElevationConfig(C.Structure):
+    """kicp_elev_config: the grid's geometry - width x height cells of side `cell` from (origin_x, origin_y), max_ray - and a vertical
+    one: bit b of a cell's 64-bit column is the world heights [z_origin + b slab, z_origin + (b + 1) slab)"""
+    _fields_ = [("cell", C.c_double), ("origin_x", C.c_double), ("origin_y", C.c_double), ("width", C.c_uint), ("height", C.c_uint),
+                ("z_origin", C.c_double), ("slab", C.c_double), ("max_ray", C.c_double)]
+
+
+class ElevationTraversabilityConfig(C.Structure):
+    """kicp_elev_traversability_config: the highest step the robot takes (0 .. 62) and its height (step_slabs < robot_slabs <= 64), in slabs"""
+    _fields_ = [("step_slabs", C.c_uint), ("robot_slabs", C.c_uint)]
+
+
 class ViewConfig(C.Structure):
     """kicp_view_config: a cube map of res x res pixels per face; the verdict looks at (2 window + 1)^2 pixels, needs min_rays returns
     among them and a gap of more than margin + margin_per_metre * depth; max_ray bounds the (Chebyshev) depth on both sides"""
@@ -223,6 +235,20 @@ _SIGNATURES = {
                                       C.c_size_t]),
     "kicp_gain_from_occupancy": (C.c_int, [C.POINTER(C.c_byte), C.c_uint, C.c_uint, C.POINTER(GainConfig), C.POINTER(C.c_uint), C.c_size_t, C.POINTER(C.c_uint), C.c_size_t]),
     "kicp_grid_gain": (C.c_int, [C.c_void_p, C.POINTER(GainConfig), C.POINTER(C.c_uint), C.c_size_t, C.POINTER(C.c_uint), C.c_size_t]),
+    "kicp_elev_create": (C.c_int, [C.POINTER(ElevationConfig), C.c_int, C.POINTER(C.c_void_p)]),
+    "kicp_elev_destroy": (None, [C.c_void_p]),
+    "kicp_elev_info": (C.c_int, [C.c_void_p, C.POINTER(ElevationConfig), C.POINTER(C.c_int), C.POINTER(C.c_ulonglong)]),
+    "kicp_elev_clear": (C.c_int, [C.c_void_p]),
+    "kicp_elev_integrate": (C.c_int, [C.c_void_p, _dp, C.c_size_t, _dp, _dp, C.POINTER(C.c_ulonglong)]),
+    "kicp_elev_integrate_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, _dp, _dp, C.POINTER(C.c_ulonglong)]),
+    "kicp_elev_columns": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong), C.c_size_t]),
+    "kicp_elev_set_columns": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong), C.c_size_t]),
+    "kicp_elev_last_window": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_uint)]),
+    "kicp_elev_traversability": (C.c_int, [C.c_void_p, C.POINTER(ElevationTraversabilityConfig), C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.POINTER(C.c_byte),
+                                           C.POINTER(C.c_ubyte), C.POINTER(C.c_ulonglong), C.c_size_t]),
+    "kicp_elev_traversability_from_columns": (C.c_int, [C.POINTER(C.c_ulonglong), C.c_uint, C.c_uint, C.POINTER(ElevationTraversabilityConfig), C.c_uint, C.c_uint, C.c_uint,
+                                                        C.c_uint, C.POINTER(C.c_byte), C.POINTER(C.c_ubyte), C.POINTER(C.c_ulonglong), C.c_size_t]),
+    "kicp_elev_to_grid": (C.c_int, [C.c_void_p, C.POINTER(ElevationTraversabilityConfig), C.c_void_p]),
     "kicp_planar_grid": (C.c_size_t,[_dp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _dp, C.c_size_t]),
     "kicp_map_save_pcd": (C.c_int, [C.c_void_p, C.c_char_p]),
     "kicp_map_load_pcd": (C.c_int, [C.c_char_p, C.c_double, C.c_double, C.c_uint, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
@@ -801,6 +827,33 @@ def gain_from_occupancy(occupancy, views, range_cells, min_observations=1, occup
     return out
 
 
+def _traversability_call(call, w, h, return_ground, return_counts):
+    """what the two traversability entries share: the outputs, the call, and what is returned - the classes alone, or a tuple with the
+    ground bytes and / or the four counts behind them"""
+    out = np.empty((h, w), dtype=np.int8)
+    ground = np.empty((h, w), dtype=np.uint8) if return_ground else None
+    counts = np.zeros(4, dtype=np.uint64)
+    _check(call(out.ctypes.data_as(C.POINTER(C.c_byte)), ground.ctypes.data_as(C.POINTER(C.c_ubyte)) if return_ground else None,
+                counts.ctypes.data_as(C.POINTER(C.c_ulonglong)) if return_counts else None, out.size))
+    if not (return_ground or return_counts):
+        return out
+    return (out,) + ((ground,) if return_ground else ()) + ((tuple(int(v) for v in counts),) if return_counts else ())
+
+
+def traversability_from_columns(columns, step_slabs, robot_slabs, rect=None, return_ground=False, return_counts=False):
+    """kicp_elev_traversability_from_columns: the classes of the cells of `rect` = (x0, y0, w, h) (None: the full layer) from columns
+    shaped (height, width), uint64 -> int8 (h, w): -1 unknown, 0 traversable, 100 obstacle (BODY: something between step_slabs and
+    robot_slabs over the cell's ground; STEP: an 8-neighbour's ground more than step_slabs below).  return_ground adds uint8 (h, w), the
+    ground's slab, 255 unknown; return_counts adds (unknown, traversable, BODY, STEP only).  Pure host code: needs no GPU."""
+    c = np.ascontiguousarray(columns, dtype=np.uint64)
+    if c.ndim != 2 or c.size == 0:
+        raise KicpError(KICP_ERR_ARG, "columns must be shaped (height, width), both at least 1")
+    x0, y0, w, h = _rect(rect, c.shape[1], c.shape[0])
+    cfg = ElevationTraversabilityConfig(int(step_slabs), int(robot_slabs))
+    return _traversability_call(lambda o, g, n, cap: lib().kicp_elev_traversability_from_columns(c.ctypes.data_as(C.POINTER(C.c_ulonglong)), c.shape[1], c.shape[0],
+                                                                                                  C.byref(cfg), x0, y0, w, h, o, g, n, cap), w, h, return_ground, return_counts)
+
+
 class OccupancyGrid:
     """kicp_grid: a world-aligned 2-D grid of (hits, misses) counters a mapping run draws frame by frame - every used point's cell is
     hit, the cells its ray from the sensor crosses are missed, once per cell per frame (include/kicp.h states the exact semantics).
@@ -958,6 +1011,87 @@ class OccupancyGrid:
     def save_map(self, prefix, min_observations=1, occupied_thresh=0.65, free_thresh=0.25):
         """kicp_grid_save_map: <prefix>.pgm + <prefix>.yaml of the readout"""
         _check(lib().kicp_grid_save_map(self._h, os.fsencode(prefix), int(min_observations), float(occupied_thresh), float(free_thresh)))
+
+
+class ElevationLayer:
+    """kicp_elev: a world-aligned layer over a grid's geometry that keeps, per cell, one 64-bit column of the world heights that ever
+    returned there, and reads traversability off it by height over the local ground (include/kicp.h states the exact semantics and the
+    known limitations).  It owns its device memory; the columns stay in HBM until they are asked for."""
+
+    def __init__(self, cell, origin_x, origin_y, width, height, z_origin, slab, max_ray, device=0):
+        self._h = None
+        cfg = ElevationConfig(float(cell), float(origin_x), float(origin_y), int(width), int(height), float(z_origin), float(slab), float(max_ray))
+        h = C.c_void_p()
+        _check(lib().kicp_elev_create(C.byref(cfg), int(device), C.byref(h)))
+        self._h, self.device, self.width, self.height = h, device, int(width), int(height)
+        self._last = np.zeros(6, dtype=np.uint64)
+
+    def __del__(self):
+        if getattr(self, "_h", None) and _lib is not None:
+            _lib.kicp_elev_destroy(self._h)
+            self._h = None
+
+    def info(self):
+        """-> dict: the configuration's fields, reach (cells) and frames (integrated since creation or clear)"""
+        cfg, reach, frames = ElevationConfig(), C.c_int(), C.c_ulonglong()
+        _check(lib().kicp_elev_info(self._h, C.byref(cfg), C.byref(reach), C.byref(frames)))
+        out = {name: getattr(cfg, name) for name, _ in ElevationConfig._fields_}
+        out.update(reach=reach.value, frames=frames.value)
+        return out
+
+    def clear(self):
+        _check(lib().kicp_elev_clear(self._h))
+
+    def integrate(self, frame, pose, sensor_xyz=(0.0, 0.0, 0.0)):
+        """kicp_elev_integrate: one frame of points in the base frame (host memory) at `pose`, the sensor at `sensor_xyz` in the base frame
+        -> (used, skipped, outside_grid, outside_column, new_bits, new_cells)"""
+        a, p = _d(np.asarray(frame, dtype=np.float64).reshape(-1, 3))
+        s, sp = _d(np.asarray(sensor_xyz, dtype=np.float64).reshape(3))
+        _check(lib().kicp_elev_integrate(self._h, p if a.size else None, a.size // 3, _pose_ptr(pose), sp, self._last.ctypes.data_as(C.POINTER(C.c_ulonglong))))
+        return self.last_frame()
+
+    def integrate_device(self, device_frame, pose, sensor_xyz=(0.0, 0.0, 0.0), n=None):
+        """kicp_elev_integrate_device: the same for a DeviceFrame (or anything with .ptr and .n) already in HBM"""
+        s, sp = _d(np.asarray(sensor_xyz, dtype=np.float64).reshape(3))
+        count = device_frame.n if n is None else int(n)
+        _check(lib().kicp_elev_integrate_device(self._h, device_frame.ptr if count else None, count, _pose_ptr(pose), sp,
+                                                self._last.ctypes.data_as(C.POINTER(C.c_ulonglong))))
+        return self.last_frame()
+
+    def last_frame(self):
+        """(used, skipped, outside_grid, outside_column, new_bits, new_cells) of the last integrated frame"""
+        return tuple(int(v) for v in self._last)
+
+    def columns(self):
+        """-> uint64 (height, width): bit b of a column is set when a return ever had a world height in slab b"""
+        out = np.empty((self.height, self.width), dtype=np.uint64)
+        _check(lib().kicp_elev_columns(self._h, out.ctypes.data_as(C.POINTER(C.c_ulonglong)), out.size))
+        return out
+
+    def set_columns(self, columns):
+        c = np.ascontiguousarray(columns, dtype=np.uint64)
+        _check(lib().kicp_elev_set_columns(self._h, c.ctypes.data_as(C.POINTER(C.c_ulonglong)), c.size))
+
+    def last_window(self):
+        """kicp_elev_last_window: (x0, y0, w, h) of the last integrated frame's window clipped to the layer, by OccupancyGrid.last_window's
+        rules; that rectangle grown by one cell is all a frame can change of the traversability"""
+        v = [C.c_uint() for _ in range(4)]
+        _check(lib().kicp_elev_last_window(self._h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
+
+    def traversability(self, step_slabs, robot_slabs, rect=None, return_ground=False, return_counts=False):
+        """kicp_elev_traversability: on the GPU, traversability_from_columns' result on the columns where they are"""
+        x0, y0, w, h = _rect(rect, self.width, self.height)
+        cfg = ElevationTraversabilityConfig(int(step_slabs), int(robot_slabs))
+        return _traversability_call(lambda o, g, n, cap: lib().kicp_elev_traversability(self._h, C.byref(cfg), x0, y0, w, h, o, g, n, cap), w, h, return_ground,
+                                    return_counts)
+
+    def to_grid(self, grid, step_slabs, robot_slabs):
+        """kicp_elev_to_grid: on the GPU, the classes of every cell into the counters of `grid`, an OccupancyGrid of equal cell, origin,
+        width and height on the same device that the caller dedicates to it: obstacle (1, 0), traversable (0, 1), unknown (0, 0).  At
+        min_observations = 1 grid.costmap, .potential, .score_arcs, .frontiers and .gain then run on traversability."""
+        cfg = ElevationTraversabilityConfig(int(step_slabs), int(robot_slabs))
+        _check(lib().kicp_elev_to_grid(self._h, C.byref(cfg), grid._h))
 
 
 class DepthView:

@@ -222,6 +222,30 @@ inline std::shared_ptr<kicp_grid> clone_grid(const kicp_grid *grid, int device =
     check(kicp_grid_set_counts(copy.get(), counts.data(), cells), "kicp_bridge::clone_grid");
     return copy;
 }
+// The height columns a mapping run keeps for uneven ground (kicp.h kicp_elev_*): KinematicICP::EnableElevation takes an ElevationConfig
+// and holds the handle shared, so a node can keep KinematicICP::Elevation() - for kicp_elev_to_grid into its planner's grid, say.
+// clone_elevation is the deep copy a copied pipeline gets: a layer of the same configuration with the same columns (its frame count
+// and its last window start again).  ElevationTraversabilityConfig is what KinematicICP::ElevationTraversability takes: the highest
+// step and the robot's height, in slabs.  ElevationStats: the six words of a frame.
+using ElevationConfig = kicp_elev_config;
+using ElevationTraversabilityConfig = kicp_elev_traversability_config;
+using ElevationStats = std::array<unsigned long long, KICP_ELEV_STATS>;  // used, skipped, outside_grid, outside_column, new_bits, new_cells
+inline std::shared_ptr<kicp_elev> make_elevation(const ElevationConfig &config, int device = -1) {
+    kicp_elev *elev = nullptr;
+    check(kicp_elev_create(&config, device < 0 ? default_device() : device, &elev), "kicp_bridge::make_elevation");
+    return std::shared_ptr<kicp_elev>(elev, kicp_elev_destroy);
+}
+inline std::shared_ptr<kicp_elev> clone_elevation(const kicp_elev *elev, int device = -1) {
+    if (!elev) return nullptr;
+    ElevationConfig config{};
+    check(kicp_elev_info(elev, &config, nullptr, nullptr), "kicp_bridge::clone_elevation");
+    const size_t cells = static_cast<size_t>(config.width) * config.height;
+    std::vector<unsigned long long> columns(cells);
+    check(kicp_elev_columns(elev, columns.data(), cells), "kicp_bridge::clone_elevation");
+    auto copy = make_elevation(config, device);
+    check(kicp_elev_set_columns(copy.get(), columns.data(), cells), "kicp_bridge::clone_elevation");
+    return copy;
+}
 // The depth view behind KinematicICP::EnableSeeThroughRemoval (kicp.h kicp_view_*): the image of the frame just registered, against
 // which the map is swept.  clone_view is what a copied pipeline gets: a view of the same configuration (the image is per frame: the
 // copy renders its own).

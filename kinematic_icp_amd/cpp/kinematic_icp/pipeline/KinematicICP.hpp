@@ -71,7 +71,7 @@ public:
     }
     ~KinematicICP() { kicp_pre_destroy(pre_); }
     // copyable and movable like the reference's class (every member is held by value there, KinematicICP.hpp:100-108): a copy owns
-    // a deep copy of the map (and of the occupancy grid, when one is enabled, and a depth view of the same configuration), a registration
+    // a deep copy of the map (and of the occupancy grid and the height columns, when enabled, and a depth view of the same configuration), a registration
     // handle of its own and its own pre-step workspace
     KinematicICP(const KinematicICP &o)
         : last_pose_(o.last_pose_),
@@ -81,6 +81,8 @@ public:
           preprocessor_(o.preprocessor_),
           local_map_(o.local_map_),
           grid_(kicp_bridge::clone_grid(o.grid_.get())),
+          elev_(kicp_bridge::clone_elevation(o.elev_.get())),
+          last_elev_stats_(o.last_elev_stats_),
           view_(kicp_bridge::clone_view(o.view_.get())),
           last_removal_(o.last_removal_),
           sensor_in_base_(o.sensor_in_base_) {
@@ -97,6 +99,8 @@ public:
           local_map_(std::move(o.local_map_)),
           pre_(o.pre_),
           grid_(std::move(o.grid_)),
+          elev_(std::move(o.elev_)),
+          last_elev_stats_(o.last_elev_stats_),
           view_(std::move(o.view_)),
           last_removal_(o.last_removal_),
           sensor_in_base_(o.sensor_in_base_) {
@@ -108,7 +112,7 @@ public:
         std::swap(correspondence_threshold_, o.correspondence_threshold_), std::swap(config_, o.config_), std::swap(preprocessor_, o.preprocessor_);
         local_map_ = std::move(o.local_map_);
         std::swap(pre_, o.pre_);
-        std::swap(grid_, o.grid_), std::swap(view_, o.view_), std::swap(last_removal_, o.last_removal_), std::swap(sensor_in_base_, o.sensor_in_base_);
+        std::swap(grid_, o.grid_), std::swap(elev_, o.elev_), std::swap(last_elev_stats_, o.last_elev_stats_), std::swap(view_, o.view_), std::swap(last_removal_, o.last_removal_), std::swap(sensor_in_base_, o.sensor_in_base_);
         return *this;
     }
 
@@ -148,6 +152,7 @@ public:
         if (config_.update_map) local_map_.Update(frame_downsample, new_pose);
         last_pose_ = new_pose;
         if (grid_) IntegrateGrid(kicp_bridge::xyz(preprocessed_frame_in_base), preprocessed_frame_in_base.size(), false);
+        if (elev_) IntegrateElevation(kicp_bridge::xyz(preprocessed_frame_in_base), preprocessed_frame_in_base.size(), false);
         return {preprocessed_frame_in_base, source};
 #endif
     }
@@ -454,6 +459,44 @@ public:
         kicp_bridge::check(kicp_grid_save_map(RequireGrid("SaveGrid"), prefix.c_str(), min_observations, occupied_thresh, free_thresh), "SaveGrid");
     }
 
+    // ---- backend extension: uneven ground (INTEGRATION.md "Uneven ground: height columns") ----
+    // With the height columns enabled, RegisterFrame, RegisterIngestedFrame and their F32 variants integrate the frame they return into a
+    // layer of one 64-bit column per cell - which world heights ever returned there - exactly where and as the occupancy grid gets it:
+    // after the registration, at the new pose, with the translation of lidar_to_base as the sensor (kicp.h kicp_elev_*, which also states
+    // the layer's known limitations).  Poses, thresholds, returned clouds, the map and the grid are what they are without it.
+    // Elevation() is the shared handle (null without a layer): kicp_elev_to_grid(Elevation().get(), &config, planner_grid.get()) puts the
+    // traversability into a grid a node dedicates to its planner.  LastElevationStats(): used, skipped, outside_grid, outside_column,
+    // new_bits, new_cells of the last frame (zeros before the first).
+    void EnableElevation(const kicp_bridge::ElevationConfig &config) { elev_ = kicp_bridge::make_elevation(config), last_elev_stats_ = {}; }
+    void DisableElevation() { elev_.reset(), last_elev_stats_ = {}; }
+    std::shared_ptr<kicp_elev> Elevation() const { return elev_; }
+    const kicp_bridge::ElevationStats &LastElevationStats() const { return last_elev_stats_; }
+    // -1 unknown, 0 traversable, 100 obstacle per cell of `rect` (nullptr: the full layer), row-major; ground (nullable): the ground's
+    // slab per cell, 255 unknown; counts (nullable): unknown, traversable, BODY, STEP only.  The result for a rectangle equals the full
+    // layer's restricted to it; a frame changes it only inside ElevationLastWindow() grown by one cell.
+    void ElevationTraversability(const kicp_bridge::ElevationTraversabilityConfig &config, std::vector<int8_t> &data, const kicp_bridge::GridRect *rect = nullptr,
+                                 std::vector<uint8_t> *ground = nullptr, std::array<unsigned long long, 4> *counts = nullptr) const {
+        kicp_bridge::GridRect r;
+        if (rect) {
+            r = *rect;
+        } else {
+            kicp_elev_config layer{};
+            kicp_bridge::check(kicp_elev_info(RequireElevation("ElevationTraversability"), &layer, nullptr, nullptr), "ElevationTraversability");
+            r.w = layer.width, r.h = layer.height;
+        }
+        data.resize(static_cast<size_t>(r.w) * r.h);
+        if (ground) ground->resize(data.size());
+        kicp_bridge::check(kicp_elev_traversability(RequireElevation("ElevationTraversability"), &config, r.x0, r.y0, r.w, r.h, reinterpret_cast<signed char *>(data.data()),
+                                                    ground ? ground->data() : nullptr, counts ? counts->data() : nullptr, data.size()),
+                           "ElevationTraversability");
+    }
+    // the window of the last integrated frame clipped to the layer; empty() when it lies outside, and before any frame
+    kicp_bridge::GridRect ElevationLastWindow() const {
+        kicp_bridge::GridRect r;
+        kicp_bridge::check(kicp_elev_last_window(RequireElevation("ElevationLastWindow"), &r.x0, &r.y0, &r.w, &r.h), "ElevationLastWindow");
+        return r;
+    }
+
     // ---- backend extension: keeping moving things out of the map (INTEGRATION.md "Keeping moving things out of the map") ----
     // With see-through removal enabled, RegisterFrame, RegisterIngestedFrame and their F32 variants render the frame they return - the
     // deskewed, cropped frame in the base frame, all of it - into a depth view at the new pose, with the translation of lidar_to_base
@@ -478,6 +521,10 @@ protected:
         if (!grid_) throw std::runtime_error(std::string("KinematicICP::") + who + ": call EnableGrid first");
         return grid_.get();
     }
+    const kicp_elev *RequireElevation(const char *who) const {
+        if (!elev_) throw std::runtime_error(std::string("KinematicICP::") + who + ": call EnableElevation first");
+        return elev_.get();
+    }
     kicp_bridge::GridRect GridRectOrAll(const kicp_bridge::GridRect *rect, const char *who) const {
         if (rect) return RequireGrid(who), *rect;
         kicp_grid_config config{};
@@ -493,6 +540,15 @@ protected:
         const double sensor[3] = {sensor_in_base_.x(), sensor_in_base_.y(), sensor_in_base_.z()};
         kicp_bridge::check(on_device ? kicp_grid_integrate_device(grid_.get(), xyz, n, pose, sensor, nullptr) : kicp_grid_integrate(grid_.get(), xyz, n, pose, sensor, nullptr),
                            "occupancy grid");
+    }
+    // one frame into the height columns at last_pose_ (already the new pose), from HBM or from host memory
+    void IntegrateElevation(const double *xyz, size_t n, bool on_device) {
+        double pose[7];
+        kicp_bridge::to_params(last_pose_, pose);
+        const double sensor[3] = {sensor_in_base_.x(), sensor_in_base_.y(), sensor_in_base_.z()};
+        unsigned long long *stats = last_elev_stats_.data();
+        kicp_bridge::check(on_device ? kicp_elev_integrate_device(elev_.get(), xyz, n, pose, sensor, stats) : kicp_elev_integrate(elev_.get(), xyz, n, pose, sensor, stats),
+                           "height columns");
     }
     // the frame into the depth view at the new pose, from HBM or from host memory; then the sweep of the map
     void RemoveSeenThrough(const double *xyz, size_t n, bool on_device, const Sophus::SE3d &new_pose) {
@@ -532,6 +588,8 @@ protected:
         last_pose_ = new_pose;
         // the occupancy grid, when enabled: the whole preprocessed frame (buffer 0, complete since the pre-steps returned) at the new pose
         if (grid_) IntegrateGrid(kicp_pre_device_ptr(pre_, 0, nullptr), counts[0], true);
+        // the height columns, when enabled: the same frame at the same pose
+        if (elev_) IntegrateElevation(kicp_pre_device_ptr(pre_, 0, nullptr), counts[0], true);
     }
     Vector3dVectorTuple RegisterChained(Vector3dVectorTuple &result, DownloadGuard &guard, const size_t counts[3], const Sophus::SE3d &relative_odometry) {
         kicp_bridge::Trace trace("registration");
@@ -594,6 +652,8 @@ protected:
     kicp_pre *pre_ = nullptr;  // device workspace of the pre-steps (backend detail)
     std::shared_ptr<kicp_occ> occupancy_;  // BuildOccupancy's snapshot of the map (backend detail)
     std::shared_ptr<kicp_grid> grid_;      // EnableGrid's occupancy grid (backend detail); null: no grid
+    std::shared_ptr<kicp_elev> elev_;      // EnableElevation's height columns (backend detail); null: no layer
+    kicp_bridge::ElevationStats last_elev_stats_{};  // the last frame's statistics of that layer
     std::shared_ptr<kicp_view> view_;      // EnableSeeThroughRemoval's depth view (backend detail); null: nothing is removed
     std::array<unsigned long long, 4> last_removal_{};  // the last frame's sweep statistics
     Eigen::Vector3d sensor_in_base_ = Eigen::Vector3d(0.0, 0.0, 0.0);  // the translation of the last frame's lidar_to_base

@@ -1,0 +1,255 @@
+// kicp_elev.hip -- the height columns a mapping run keeps beside its occupancy grid (kicp_elev_*; include/kicp.h states the semantics):
+// per cell one 64-bit column of the world heights that ever returned, and the traversability read off it - unknown, traversable,
+// obstacle by height over the local ground.  Kernels: kicp_elev.hpp; the arithmetic they share with the host entries:
+// kicp_elev_host.hpp.  kicp_elev_to_grid writes the classes into a kicp_grid's counters, so this file sees that handle too.
+#include <cstring>
+#include <memory>
+
+#include "kicp_elev.hpp"
+#include "kicp_grid_internal.hpp"
+
+// The handle keeps the grid's rules (kicp_grid_internal.hpp): const entries write only the `mutable` group, and every entry returns
+// with the stream drained.
+struct kicp_elev {
+    int device = 0;
+    kicp_elev_config cfg{};
+    ElevGeom geom{};
+    size_t cells = 0;
+    DevBuf<unsigned long long> d_columns;  // the layer: one column per cell
+    hipStream_t stream = nullptr;
+    unsigned long long frames = 0;
+    bool has_window = false;  // as kicp_grid's
+    int32_t win_x0 = 0, win_y0 = 0;
+    // kicp_elev_integrate*: skipped, outside_grid, outside_column, new_bits, new_cells of the frame in flight, in their shards
+    struct {
+        DevBuf<unsigned int> d_stats;
+        PinnedBuf<unsigned int> h_stats;
+        FrameUpload upload;  // kicp_elev_integrate's points
+    } frame;
+    // kicp_elev_traversability: the classes, the ground bytes and the four counts in their shards
+    mutable struct {
+        DevBuf<int8_t> d_classes;
+        DevBuf<uint8_t> d_ground;
+        DevBuf<unsigned int> d_counts;
+        PinnedBuf<unsigned int> h_counts;
+    } readout;
+    ~kicp_elev() {
+        if (stream) (void)hipStreamSynchronize(stream), (void)hipStreamDestroy(stream);
+    }
+};
+
+namespace {
+constexpr int kElevStats = 5;  // words of a shard the mark kernel adds to
+constexpr size_t kElevCountWords = static_cast<size_t>(kElevCountShards) * kElevCountStride;  // a sharded counter block (kicp_elev.hpp)
+// word k of such a block as it came back, summed over the shards
+unsigned long long shard_sum(const unsigned int *h, int k) {
+    unsigned long long sum = 0;
+    for (uint32_t shard = 0; shard < kElevCountShards; ++shard) sum += h[shard * kElevCountStride + k];
+    return sum;
+}
+
+int check_elev_params(const kicp_elev_traversability_config *cfg, ElevParams &p) {
+    p = ElevParams{cfg->step_slabs, cfg->robot_slabs};
+    if (cfg->step_slabs > kElevMaxStep) return fail(KICP_ERR_ARG, "step_slabs must lie in 0 .. 62");
+    if (!(cfg->step_slabs < cfg->robot_slabs && cfg->robot_slabs <= kElevSlabs)) return fail(KICP_ERR_ARG, "robot_slabs must satisfy step_slabs < robot_slabs <= 64");
+    return KICP_OK;
+}
+int check_elev_rect(unsigned int width, unsigned int height, const ElevRect &r, size_t cap) {
+    if (r.w < 1u || r.h < 1u || r.x0 >= width || r.y0 >= height || r.w > width - r.x0 || r.h > height - r.y0)
+        return fail(KICP_ERR_ARG, "the rectangle must lie inside the layer of " + std::to_string(width) + " x " + std::to_string(height) + " cells, w and h at least 1");
+    if (cap != static_cast<size_t>(r.w) * r.h) return fail(KICP_ERR_ARG, "cap must be w * h = " + std::to_string(static_cast<size_t>(r.w) * r.h));
+    return KICP_OK;
+}
+// the frame at d_xyz (n points; arguments checked): one launch, the statistics back, the stream drained
+int integrate_on_device(kicp_elev *elev, const double *d_xyz, size_t n, const double pose_qt[7], const double sensor_xyz[3], unsigned long long out_stats[6]) {
+    unsigned long long stats[6] = {0, 0, 0, 0, 0, 0};
+    const ElevFrame f = elev_frame(elev->geom, pose_qt, sensor_xyz);
+    elev->has_window = true, elev->win_x0 = f.plane.gx0, elev->win_y0 = f.plane.gy0;
+    if (n) {
+        hipStream_t st = elev->stream;
+        auto &fr = elev->frame;
+        HIP_TRY(hipMemsetAsync(fr.d_stats.get(), 0, kElevCountWords * sizeof(unsigned int), st));
+        hipLaunchKernelGGL(k_elev_mark, dim3(static_cast<uint32_t>((n + kElevBlock - 1) / kElevBlock)), dim3(kElevBlock), 0, st, d_xyz, static_cast<uint32_t>(n), elev->geom,
+                           f, elev->d_columns.get(), fr.d_stats.get());
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(fr.h_stats.get(), fr.d_stats.get(), kElevCountWords * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        for (int k = 0; k < kElevStats; ++k) stats[1 + k] = shard_sum(fr.h_stats.get(), k);
+        stats[0] = n - (stats[1] + stats[2] + stats[3]);
+    }
+    ++elev->frames;
+    if (out_stats)
+        for (int k = 0; k < 6; ++k) out_stats[k] = stats[k];
+    return KICP_OK;
+}
+int check_frame_args(const kicp_elev *elev, const double *xyz, size_t n, const double *pose_qt, const double *sensor_xyz) {
+    return FrameUpload::check(elev && pose_qt && sensor_xyz && (xyz || !n), n, "frame too large");
+}
+uint32_t elev_tiles(uint32_t cells_side) { return (cells_side + kElevTile - 1u) / kElevTile; }
+}  // namespace
+
+extern "C" {
+
+int kicp_elev_create(const kicp_elev_config *cfg, int device, kicp_elev **out) {
+    KICP_TRACE_CALL();
+    if (!cfg || !out) return fail(KICP_ERR_ARG, "null argument");
+    *out = nullptr;
+    if (!(cfg->cell > 0.0) || !std::isfinite(cfg->cell)) return fail(KICP_ERR_ARG, "cell must be positive and finite");
+    if (!(cfg->max_ray > 0.0) || !std::isfinite(cfg->max_ray)) return fail(KICP_ERR_ARG, "max_ray must be positive and finite");
+    if (!(cfg->slab > 0.0) || !std::isfinite(cfg->slab)) return fail(KICP_ERR_ARG, "slab must be positive and finite");
+    if (!std::isfinite(cfg->origin_x) || !std::isfinite(cfg->origin_y) || !std::isfinite(cfg->z_origin)) return fail(KICP_ERR_ARG, "the origin and z_origin must be finite");
+    if (cfg->width == 0 || cfg->height == 0) return fail(KICP_ERR_ARG, "width and height must be at least 1");
+    const unsigned long long cells = static_cast<unsigned long long>(cfg->width) * cfg->height;
+    if (cells > kGridMaxCells)
+        return fail(KICP_ERR_CAPACITY, "the layer would have " + std::to_string(cfg->width) + " x " + std::to_string(cfg->height) + " = " + std::to_string(cells) +
+                                           " cells (limit 2^28 = " + std::to_string(kGridMaxCells) + ")");
+    const double reach = std::ceil(cfg->max_ray / cfg->cell);
+    if (!(reach <= static_cast<double>(kGridMaxReach)))
+        return fail(KICP_ERR_CAPACITY, "max_ray / cell gives a reach of " + std::to_string(reach) + " cells (limit " + std::to_string(kGridMaxReach) + ")");
+    if (int rc = set_device(device)) return rc;
+    std::unique_ptr<kicp_elev> elev(new kicp_elev);
+    elev->device = device, elev->cfg = *cfg, elev->cells = static_cast<size_t>(cells);
+    const double inf = std::numeric_limits<double>::infinity();
+    elev->geom = ElevGeom{GridGeom{cfg->cell, cfg->origin_x, cfg->origin_y, -inf, inf, cfg->width, cfg->height, static_cast<int32_t>(reach)}, cfg->z_origin, cfg->slab};
+    HIP_TRY(hipStreamCreateWithFlags(&elev->stream, hipStreamNonBlocking));
+    if (int rc = elev->d_columns.reserve(elev->cells)) return rc;
+    if (int rc = elev->frame.d_stats.reserve(kElevCountWords)) return rc;
+    if (int rc = elev->frame.h_stats.reserve(kElevCountWords, hipHostMallocDefault, false)) return rc;
+    HIP_TRY(hipMemsetAsync(elev->d_columns.get(), 0, elev->cells * sizeof(unsigned long long), elev->stream));
+    HIP_TRY(hipStreamSynchronize(elev->stream));
+    *out = elev.release();
+    return KICP_OK;
+}
+void kicp_elev_destroy(kicp_elev *elev) {
+    if (!elev) return;
+    (void)hipSetDevice(elev->device);
+    delete elev;
+}
+int kicp_elev_info(const kicp_elev *elev, kicp_elev_config *out_config, int *out_reach, unsigned long long *out_frames) {
+    if (!elev) return fail(KICP_ERR_ARG, "null argument");
+    if (out_config) *out_config = elev->cfg;
+    if (out_reach) *out_reach = elev->geom.plane.reach;
+    if (out_frames) *out_frames = elev->frames;
+    return KICP_OK;
+}
+int kicp_elev_clear(kicp_elev *elev) {
+    KICP_TRACE_CALL();
+    if (!elev) return fail(KICP_ERR_ARG, "null argument");
+    if (int rc = set_device(elev->device)) return rc;
+    HIP_TRY(hipMemsetAsync(elev->d_columns.get(), 0, elev->cells * sizeof(unsigned long long), elev->stream));
+    HIP_TRY(hipStreamSynchronize(elev->stream));
+    elev->frames = 0, elev->has_window = false;
+    return KICP_OK;
+}
+int kicp_elev_integrate(kicp_elev *elev, const double *frame_xyz, size_t n, const double pose_qt[7], const double sensor_xyz[3], unsigned long long out_stats[6]) {
+    KICP_TRACE_CALL();
+    if (int rc = check_frame_args(elev, frame_xyz, n, pose_qt, sensor_xyz)) return rc;
+    if (int rc = set_device(elev->device)) return rc;
+    if (int rc = elev->frame.upload.put(frame_xyz, n, elev->stream)) return rc;
+    return integrate_on_device(elev, elev->frame.upload.d_xyz.get(), n, pose_qt, sensor_xyz, out_stats);
+}
+int kicp_elev_integrate_device(kicp_elev *elev, const double *d_frame_xyz, size_t n, const double pose_qt[7], const double sensor_xyz[3],
+                               unsigned long long out_stats[6]) {
+    KICP_TRACE_CALL();
+    if (int rc = check_frame_args(elev, d_frame_xyz, n, pose_qt, sensor_xyz)) return rc;
+    if (int rc = set_device(elev->device)) return rc;
+    return integrate_on_device(elev, d_frame_xyz, n, pose_qt, sensor_xyz, out_stats);
+}
+int kicp_elev_columns(const kicp_elev *elev, unsigned long long *out, size_t cap_cells) {
+    KICP_TRACE_CALL();
+    if (!elev || !out) return fail(KICP_ERR_ARG, "null argument");
+    if (cap_cells != elev->cells) return fail(KICP_ERR_ARG, "cap_cells must be the layer's " + std::to_string(elev->cells) + " cells");
+    if (int rc = set_device(elev->device)) return rc;
+    HIP_TRY(hipMemcpyAsync(out, elev->d_columns.get(), elev->cells * sizeof(unsigned long long), hipMemcpyDeviceToHost, elev->stream));
+    HIP_TRY(hipStreamSynchronize(elev->stream));
+    return KICP_OK;
+}
+int kicp_elev_set_columns(kicp_elev *elev, const unsigned long long *in, size_t cells) {
+    KICP_TRACE_CALL();
+    if (!elev || !in) return fail(KICP_ERR_ARG, "null argument");
+    if (cells != elev->cells) return fail(KICP_ERR_ARG, "cells must be the layer's " + std::to_string(elev->cells) + " cells");
+    if (int rc = set_device(elev->device)) return rc;
+    HIP_TRY(hipMemcpyAsync(elev->d_columns.get(), in, elev->cells * sizeof(unsigned long long), hipMemcpyHostToDevice, elev->stream));
+    HIP_TRY(hipStreamSynchronize(elev->stream));
+    return KICP_OK;
+}
+int kicp_elev_last_window(const kicp_elev *elev, unsigned int *x0, unsigned int *y0, unsigned int *w, unsigned int *h) {
+    if (!elev || !x0 || !y0 || !w || !h) return fail(KICP_ERR_ARG, "null argument");
+    *x0 = *y0 = *w = *h = 0u;
+    if (!elev->has_window) return KICP_OK;
+    const int64_t side = 2 * static_cast<int64_t>(elev->geom.plane.reach) + 1;
+    const int64_t ax = std::max<int64_t>(elev->win_x0, 0), bx = std::min<int64_t>(elev->win_x0 + side, elev->cfg.width);
+    const int64_t ay = std::max<int64_t>(elev->win_y0, 0), by = std::min<int64_t>(elev->win_y0 + side, elev->cfg.height);
+    if (ax >= bx || ay >= by) return KICP_OK;
+    *x0 = static_cast<unsigned int>(ax), *y0 = static_cast<unsigned int>(ay), *w = static_cast<unsigned int>(bx - ax), *h = static_cast<unsigned int>(by - ay);
+    return KICP_OK;
+}
+int kicp_elev_traversability(const kicp_elev *elev, const kicp_elev_traversability_config *cfg, unsigned int x0, unsigned int y0, unsigned int w, unsigned int h,
+                             signed char *out, unsigned char *out_ground, unsigned long long out_counts[4], size_t cap) {
+    KICP_TRACE_CALL();
+    if (!elev || !cfg || !out) return fail(KICP_ERR_ARG, "null argument");
+    ElevParams p;
+    const ElevRect r{x0, y0, w, h};
+    if (int rc = check_elev_params(cfg, p)) return rc;
+    if (int rc = check_elev_rect(elev->cfg.width, elev->cfg.height, r, cap)) return rc;
+    if (int rc = set_device(elev->device)) return rc;
+    auto &ro = elev->readout;
+    if (int rc = ro.d_classes.reserve(cap)) return rc;
+    if (out_ground)
+        if (int rc = ro.d_ground.reserve(cap)) return rc;
+    if (out_counts) {
+        if (int rc = ro.d_counts.reserve(kElevCountWords)) return rc;
+        if (int rc = ro.h_counts.reserve(kElevCountWords, hipHostMallocDefault, false)) return rc;
+    }
+    hipStream_t st = elev->stream;
+    if (out_counts) HIP_TRY(hipMemsetAsync(ro.d_counts.get(), 0, kElevCountWords * sizeof(unsigned int), st));
+    const uint32_t tiles_x = elev_tiles(w), tiles_y = elev_tiles(h);  // (their product stays below 2^25: cells <= 2^28)
+    hipLaunchKernelGGL(k_elev_classify, dim3(tiles_x * tiles_y), dim3(kElevBlock), 0, st, elev->d_columns.get(), elev->cfg.width, elev->cfg.height, p, r, tiles_x,
+                       ro.d_classes.get(), out_ground ? ro.d_ground.get() : static_cast<uint8_t *>(nullptr),
+                       out_counts ? ro.d_counts.get() : static_cast<unsigned int *>(nullptr));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, ro.d_classes.get(), cap, hipMemcpyDeviceToHost, st));
+    if (out_ground) HIP_TRY(hipMemcpyAsync(out_ground, ro.d_ground.get(), cap, hipMemcpyDeviceToHost, st));
+    if (out_counts) HIP_TRY(hipMemcpyAsync(ro.h_counts.get(), ro.d_counts.get(), kElevCountWords * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (out_counts)
+        for (int k = 0; k < 4; ++k) out_counts[k] = shard_sum(ro.h_counts.get(), k);
+    return KICP_OK;
+}
+int kicp_elev_traversability_from_columns(const unsigned long long *columns, unsigned int width, unsigned int height, const kicp_elev_traversability_config *cfg,
+                                          unsigned int x0, unsigned int y0, unsigned int w, unsigned int h, signed char *out, unsigned char *out_ground,
+                                          unsigned long long out_counts[4], size_t cap) {
+    if (!columns || !cfg || !out) return fail(KICP_ERR_ARG, "null argument");
+    ElevParams p;
+    const ElevRect r{x0, y0, w, h};
+    if (int rc = check_elev_params(cfg, p)) return rc;
+    if (int rc = check_grid_dims(width, height)) return rc;
+    if (int rc = check_elev_rect(width, height, r, cap)) return rc;
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "a column is 64 bits");
+    elev_host::classify(reinterpret_cast<const uint64_t *>(columns), width, height, p, r, reinterpret_cast<int8_t *>(out), out_ground, out_counts);
+    return KICP_OK;
+}
+int kicp_elev_to_grid(const kicp_elev *elev, const kicp_elev_traversability_config *cfg, kicp_grid *grid) {
+    KICP_TRACE_CALL();
+    if (!elev || !cfg || !grid) return fail(KICP_ERR_ARG, "null argument");
+    ElevParams p;
+    if (int rc = check_elev_params(cfg, p)) return rc;
+    const kicp_grid_config &gc = grid->cfg;
+    const kicp_elev_config &ec = elev->cfg;
+    auto same_bits = [](double a, double b) { return std::memcmp(&a, &b, sizeof a) == 0; };
+    if (!(same_bits(gc.cell, ec.cell) && same_bits(gc.origin_x, ec.origin_x) && same_bits(gc.origin_y, ec.origin_y) && gc.width == ec.width && gc.height == ec.height))
+        return fail(KICP_ERR_ARG, "the grid's cell, origin, width and height must equal the layer's");
+    if (grid->device != elev->device)
+        return fail(KICP_ERR_ARG, "the grid lives on device " + std::to_string(grid->device) + ", the layer on device " + std::to_string(elev->device));
+    if (int rc = set_device(elev->device)) return rc;
+    // Both handles' streams are idle (the stream rule); the launch runs on the layer's and is waited for, so the grid's next entry
+    // finds its counters written.
+    const uint32_t tiles_x = elev_tiles(ec.width), tiles_y = elev_tiles(ec.height);
+    hipLaunchKernelGGL(k_elev_to_grid, dim3(tiles_x * tiles_y), dim3(kElevBlock), 0, elev->stream, elev->d_columns.get(), ec.width, ec.height, p,
+                       ElevRect{0u, 0u, ec.width, ec.height}, tiles_x, grid->d_counts.get());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(elev->stream));
+    return KICP_OK;
+}
+
+}  // extern "C"

@@ -1,0 +1,141 @@
+// kicp_elev.hpp -- the kernels of the height columns (kicp_elev_*; C-ABI: kicp_elev.hip, arithmetic: kicp_elev_host.hpp).
+//
+//   k_elev_mark      one lane per point: the transform, the cell, the reach and range tests and the slab, then the point's bit is set in
+//                    its cell's 64-bit column - ONE launch per frame.  No frame-local planes: OR is idempotent, so the columns
+//                    deduplicate the points themselves.  TEST BEFORE SET: the lane loads the column and issues the atomic OR only
+//                    when it finds the bit clear.  A robot re-observes what it has seen, so in steady state nearly every lane finds its
+//                    bit set, and a plain load is served by L2 while an atomic executes beyond it and drops the line from it
+//   k_elev_classify  a tile of 16 x 16 cells per workgroup: each lane reduces its column to a ground byte, the tile's grounds and a
+//                    one-cell halo go through LDS, BODY comes from the lane's own column by shifts and STEP from the eight
+//                    neighbours in LDS; the classes, the optional ground bytes and per-wave sums of the four counts are written
+//   k_elev_to_grid   the same classification (elev_classify_cell, one device function for both) written as the two 16-bit counters
+//                    of a kicp_grid
+// The atomics besides the OR are the statistics: one add per wave per statistic that has something to add.  No kernel uses scratch.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "kicp_elev_host.hpp"
+
+namespace kicp {
+
+constexpr uint32_t kElevBlock = 256;
+constexpr uint32_t kElevTile = 16;              // cells per side of a classification tile: kElevTile^2 lanes
+constexpr uint32_t kElevHalo = kElevTile + 2u;  // its side with the halo
+// A frame's statistics and the four counts of a classification are kept in kElevCountShards copies, each on a 128-byte line of its own,
+// and summed on the host: one word takes an atomic add every 11 ns or so, whoever adds, and nearly every wave has something to add
+// to the same few words - a frame that explores sets new bits in every wave, and most cells of a large layer are unknown
+constexpr uint32_t kElevCountShards = 64, kElevCountStride = 32;
+// this wave's shard of such a counter block
+static __device__ __forceinline__ unsigned int *elev_shard(unsigned int *counters) {
+    return counters + ((blockIdx.x * (kElevBlock / 64u) + threadIdx.x / 64u) % kElevCountShards) * kElevCountStride;
+}
+
+static __device__ __forceinline__ void elev_wave_add(unsigned int *counter, bool flag) {
+    const unsigned long long b = __ballot(flag);
+    if ((threadIdx.x & 63u) == 0u && b) atomicAdd(counter, static_cast<unsigned int>(__popcll(b)));
+}
+
+// stats: kElevCountShards x kElevCountStride words; a wave adds skipped, outside_grid, outside_column, new_bits, new_cells to words
+// 0 .. 4 of its shard.  The used points are what the host derives: in steady state nearly every point is used and nothing is new, and
+// a wave with nothing to add issues no atomic at all.
+static __global__ __launch_bounds__(kElevBlock) void k_elev_mark(const double *__restrict__ xyz, uint32_t n, ElevGeom g, ElevFrame f, unsigned long long *columns,
+                                                                 unsigned int *__restrict__ stats) {
+    const uint32_t i = blockIdx.x * kElevBlock + threadIdx.x;
+    int cls = kElevUsed;  // (a lane beyond the frame counts as nothing: the used points are the ones that are not counted)
+    bool new_bit = false, new_cell = false;
+    size_t cell = 0;
+    uint32_t slab = 0;
+    const bool point = i < n;
+    if (point) cls = elev_point(g, f, xyz[3 * static_cast<size_t>(i)], xyz[3 * static_cast<size_t>(i) + 1], xyz[3 * static_cast<size_t>(i) + 2], cell, slab);
+    if (point && cls == kElevUsed) {  // cell < width * height: elev_point compared both coordinates with the grid's extent
+        const unsigned long long bit = 1ull << slab;
+        // A STALE VALUE IS SAFE HERE.  Within a launch a bit only ever goes from clear to set, so a load that misses another lane's OR
+        // can only read the bit as clear, and that costs a redundant atomic, never a lost bit; a load can never read a bit as set
+        // that is not.  Between entries the handle's stream is drained (the grid's stream rule), so a launch sees all that earlier
+        // calls wrote.  The statistics do not rest on this load: they come from the atomic's returned value - exactly one atomic
+        // sees each bit clear, and exactly one sees each column zero.
+        if (!(columns[cell] & bit)) {
+            const unsigned long long old = atomicOr(&columns[cell], bit);
+            new_bit = !(old & bit), new_cell = old == 0ull;
+        }
+    }
+    unsigned int *shard = elev_shard(stats);
+    elev_wave_add(&shard[0], cls == kElevSkipped);
+    elev_wave_add(&shard[1], cls == kElevOutsideGrid);
+    elev_wave_add(&shard[2], cls == kElevOutsideColumn);
+    elev_wave_add(&shard[3], new_bit);
+    elev_wave_add(&shard[4], new_cell);
+}
+
+// The class of this lane's cell, (r.x0 + tile_x kElevTile + tx, r.y0 + tile_y kElevTile + ty) with tx = threadIdx.x % kElevTile: every
+// lane of the workgroup calls it (it holds the barrier).  grounds: kElevHalo^2 bytes of LDS.  -> inside: the cell lies in the
+// rectangle; value, ground and which (elev_value) are its results.  Halo cells outside the rectangle but inside the grid are read
+// like any other, so a rectangle's result is the full grid's restricted to it; cells outside the grid read as unknown.
+static __device__ __forceinline__ bool elev_classify_cell(const unsigned long long *__restrict__ columns, uint32_t width, uint32_t height, const ElevParams &p,
+                                                          const ElevRect &r, uint32_t tiles_x, uint8_t *grounds, int8_t &value, uint8_t &ground, uint32_t &which) {
+    const uint32_t tx = threadIdx.x % kElevTile, ty = threadIdx.x / kElevTile;
+    const uint32_t bx = r.x0 + (blockIdx.x % tiles_x) * kElevTile, by = r.y0 + (blockIdx.x / tiles_x) * kElevTile;  // the tile's corner: inside the rectangle
+    const uint32_t x = bx + tx, y = by + ty;
+    const bool in_grid = x < width && y < height;
+    const bool inside = x - r.x0 < r.w && y - r.y0 < r.h;  // (inside the rectangle implies inside the grid)
+    const unsigned long long c = in_grid ? columns[static_cast<size_t>(y) * width + x] : 0ull;
+    ground = elev_ground(c);
+    grounds[(ty + 1u) * kElevHalo + (tx + 1u)] = ground;
+    if (threadIdx.x < 4u * kElevTile + 4u) {  // the halo's 68 cells: two rows of kElevHalo, two columns of kElevTile
+        const uint32_t k = threadIdx.x;
+        const uint32_t hx = k < kElevHalo ? k : k < 2u * kElevHalo ? k - kElevHalo : k < 2u * kElevHalo + kElevTile ? 0u : kElevHalo - 1u;
+        const uint32_t hy = k < kElevHalo ? 0u : k < 2u * kElevHalo ? kElevHalo - 1u : k < 2u * kElevHalo + kElevTile ? k - 2u * kElevHalo + 1u : k - 2u * kElevHalo - kElevTile + 1u;
+        const int64_t gx = static_cast<int64_t>(bx) + hx - 1, gy = static_cast<int64_t>(by) + hy - 1;
+        const bool ok = gx >= 0 && gy >= 0 && gx < static_cast<int64_t>(width) && gy < static_cast<int64_t>(height);
+        grounds[hy * kElevHalo + hx] = ok ? elev_ground(columns[static_cast<size_t>(gy) * width + static_cast<size_t>(gx)]) : kElevNoGround;
+    }
+    __syncthreads();
+    bool body = false, step = false;
+    if (c) {
+        body = elev_body(c, ground, p);
+#pragma unroll
+        for (uint32_t dy = 0; dy < 3u; ++dy)
+#pragma unroll
+            for (uint32_t dx = 0; dx < 3u; ++dx)
+                if (dx != 1u || dy != 1u) step = step || elev_step(ground, grounds[(ty + dy) * kElevHalo + (tx + dx)], p);
+    }
+    value = elev_value(c != 0ull, body, step, which);
+    return inside;
+}
+
+// out / out_ground (nullable): r.h * r.w values; counts (nullable): kElevCountShards x kElevCountStride words, a wave adds unknown,
+// traversable, BODY, STEP only to words 0 .. 3 of its shard
+static __global__ __launch_bounds__(kElevBlock) void k_elev_classify(const unsigned long long *__restrict__ columns, uint32_t width, uint32_t height, ElevParams p, ElevRect r,
+                                                                     uint32_t tiles_x, int8_t *__restrict__ out, uint8_t *__restrict__ out_ground,
+                                                                     unsigned int *__restrict__ counts) {
+    __shared__ uint8_t grounds[kElevHalo * kElevHalo];
+    int8_t value;
+    uint8_t ground;
+    uint32_t which;
+    const bool inside = elev_classify_cell(columns, width, height, p, r, tiles_x, grounds, value, ground, which);
+    if (inside) {
+        const uint32_t rx = (blockIdx.x % tiles_x) * kElevTile + threadIdx.x % kElevTile, ry = (blockIdx.x / tiles_x) * kElevTile + threadIdx.x / kElevTile;
+        const size_t o = static_cast<size_t>(ry) * r.w + rx;
+        out[o] = value;
+        if (out_ground) out_ground[o] = ground;
+    }
+    if (counts) {
+        unsigned int *shard = elev_shard(counts);
+        for (uint32_t k = 0; k < 4u; ++k) elev_wave_add(&shard[k], inside && which == k);
+    }
+}
+
+// grid_counts: the (hits, misses) pairs of a kicp_grid of width x height cells, written whole: obstacle (1, 0), traversable (0, 1),
+// unknown (0, 0).  The rectangle is the full grid.
+static __global__ __launch_bounds__(kElevBlock) void k_elev_to_grid(const unsigned long long *__restrict__ columns, uint32_t width, uint32_t height, ElevParams p, ElevRect r,
+                                                                    uint32_t tiles_x, uint16_t *__restrict__ grid_counts) {
+    __shared__ uint8_t grounds[kElevHalo * kElevHalo];
+    int8_t value;
+    uint8_t ground;
+    uint32_t which;
+    if (!elev_classify_cell(columns, width, height, p, r, tiles_x, grounds, value, ground, which)) return;  // (behind the barrier)
+    const uint32_t x = (blockIdx.x % tiles_x) * kElevTile + threadIdx.x % kElevTile, y = (blockIdx.x / tiles_x) * kElevTile + threadIdx.x / kElevTile;
+    reinterpret_cast<uint32_t *>(grid_counts)[static_cast<size_t>(y) * width + x] = value < 0 ? 0u : value ? 1u : 0x10000u;
+}
+
+}  // namespace kicp

@@ -1,0 +1,219 @@
+"""What the height columns cost (kicp_elev_*), one process, the caller bound as tools/bench_pipeline.py binds it.
+
+Cases: tools/bench_grid.py's - a 131 072-point frame (64 beams x 2048 azimuths) in cfg1's scene and a 1 080-beam scan in cfg4's, each at
+0.05 m and 0.25 m cells; slabs of 0.125 m from 1 m below the floor.  The host clock around each call, which returns after its kernels
+have completed.  Warm; everything that is compared alternates in the same process `rounds` times; median, p10 / p90, min .. max.
+  - integrate: kicp_elev_integrate_device of the frame onto an EMPTY layer (cleared before, untimed: every bit is new, all atomics) and
+    of the SAME frame again (steady state: no new bit), and kicp_grid_integrate_device on a grid of the same geometry as the yardstick;
+    with --ab NAME=LIBRARY (repeatable) the same two calls through another build of the library loaded beside this one - how a kernel
+    variant is compared before the loser is deleted;
+  - traversability: kicp_elev_traversability of a full 1 600 x 1 600 layer and of its last window grown by one cell (max_ray 12 m there,
+    so that the window is not the whole layer), the full layer once more with the ground bytes and the four counts, and
+    kicp_grid_occupancy of an equal grid as the yardstick; kicp_elev_to_grid too;
+  - with --pipeline: KinematicICP::RegisterFrame on a short drive in the case's scene (tests/cpp/elev_facade_test, mode `timed`; the
+    frames as vectors, the clock around the call), a process with the layer and a process without, alternating `pipeline-rounds`
+    times; with --contender NAME=EXECUTABLE:LIBDIR (repeatable) also a process of another build's `<facade test> timed .. off` - the
+    parent commit's, to show that a disabled layer costs nothing: the median of the drive's second half per process, then median and
+    min .. max over the processes.
+Prints one JSON line.
+
+    python tools/bench_elev.py [--rounds 30] [--ab NAME=LIB] [--pipeline] [--pipeline-rounds 3] [--pipeline-frames 16] [--contender NAME=EXE:LIBDIR]
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import subprocess
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import kinematic_icp_amd as K  # noqa: E402
+from kinematic_icp_amd import synthetic as syn  # noqa: E402
+from bench_pipeline import placement  # noqa: E402
+from bench_relocalize import spread  # noqa: E402
+from bench_grid import CELLS, GEOMETRY, grid_config, make_grid, scene_and_beams  # noqa: E402
+
+Z_ORIGIN, SLAB = -1.0, 0.125
+STEP_SLABS, ROBOT_SLABS = 2, 12
+
+
+class RawLayer:
+    """a layer of another build of the library (an --ab contender), through its C-ABI"""
+
+    def __init__(self, lib, cfg):
+        self.lib, self._h = lib, C.c_void_p()
+        c = K.ElevationConfig(cfg["cell"], cfg["origin_x"], cfg["origin_y"], cfg["width"], cfg["height"], Z_ORIGIN, SLAB, cfg["max_ray"])
+        assert lib.kicp_elev_create(C.byref(c), 0, C.byref(self._h)) == 0
+        self._last = np.zeros(6, dtype=np.uint64)
+
+    def clear(self):
+        assert self.lib.kicp_elev_clear(self._h) == 0
+
+    def integrate_device(self, dev, pose, sensor):
+        rc = self.lib.kicp_elev_integrate_device(self._h, dev.ptr, dev.n, pose.ctypes.data_as(K._dp), sensor.ctypes.data_as(K._dp), self._last.ctypes.data_as(C.POINTER(C.c_ulonglong)))
+        assert rc == 0
+        return tuple(int(v) for v in self._last)
+
+    def __del__(self):
+        self.lib.kicp_elev_destroy(self._h)
+
+
+def load_contender(path):
+    lib = C.CDLL(os.path.abspath(path))
+    for name, (res, args) in K._SIGNATURES.items():
+        if name.startswith("kicp_elev_"):
+            fn = getattr(lib, name)
+            fn.restype, fn.argtypes = res, args
+    return lib
+
+
+def make_layer(cfg):
+    return K.ElevationLayer(cfg["cell"], cfg["origin_x"], cfg["origin_y"], cfg["width"], cfg["height"], Z_ORIGIN, SLAB, cfg["max_ray"])
+
+
+def timed(call):
+    t0 = time.perf_counter()
+    out = call()
+    return (time.perf_counter() - t0) * 1e3, out
+
+
+def integrate_rows(rounds, contenders):
+    cases = []
+    for name in GEOMETRY:
+        cfg, scene, dirs, rng = scene_and_beams(name)
+        pose = syn.planar_pose(1.2, -0.7, 0.9)
+        frame = np.ascontiguousarray(syn.make_scan(scene, pose, dirs, cfg.sensor_height, rng))
+        sensor = np.array([0.0, 0.0, cfg.sensor_height])
+        for cell in CELLS:
+            gcfg = grid_config(name, cell)
+            layers = {"this": make_layer(gcfg)}
+            layers.update({who: RawLayer(lib, gcfg) for who, lib in contenders.items()})
+            cases.append(dict(name=name, cell=cell, cfg=gcfg, layers=layers, grid=make_grid(gcfg), frame=frame, dev=K.DeviceFrame(frame), pose=pose, sensor=sensor,
+                              t_grid=[], t_first={w: [] for w in layers}, t_again={w: [] for w in layers}, stats={}))
+    for r in range(rounds + 3):  # (the first three rounds warm)
+        for c in cases:
+            t_grid, _ = timed(lambda: c["grid"].integrate_device(c["dev"], c["pose"], c["sensor"]))
+            if r >= 3:
+                c["t_grid"].append(t_grid)
+            for who, layer in c["layers"].items():
+                layer.clear()
+                t_first, first = timed(lambda: layer.integrate_device(c["dev"], c["pose"], c["sensor"]))
+                t_again, again = timed(lambda: layer.integrate_device(c["dev"], c["pose"], c["sensor"]))
+                assert again[:4] == first[:4] and again[4:] == (0, 0) and c["stats"].setdefault("first", first) == first  # every build computes the same
+                if r >= 3:
+                    c["t_first"][who].append(t_first), c["t_again"][who].append(t_again)
+    rows = []
+    for c in cases:
+        first = c["stats"]["first"]
+        row = {"scene": c["name"], "points": len(c["frame"]), "cell_m": c["cell"], "layer_cells": [c["cfg"]["width"], c["cfg"]["height"]], "reach_cells": c["cfg"]["reach"],
+               "used": first[0], "skipped": first[1], "outside_grid": first[2], "outside_column": first[3], "bits_of_the_frame": first[4], "cells_of_the_frame": first[5],
+               "grid_integrate_device_ms": spread(c["t_grid"])}
+        for who in c["layers"]:
+            row["elev_first_frame_ms_" + who] = spread(c["t_first"][who])
+            row["elev_same_frame_again_ms_" + who] = spread(c["t_again"][who])
+        rows.append(row)
+    return rows
+
+
+def traversability_rows(rounds):
+    name = "cfg1"
+    cfg, scene, dirs, rng = scene_and_beams(name)
+    pose = syn.planar_pose(1.2, -0.7, 0.9)
+    frame = np.ascontiguousarray(syn.make_scan(scene, pose, dirs, cfg.sensor_height, rng))
+    sensor = np.array([0.0, 0.0, cfg.sensor_height])
+    gcfg = dict(grid_config(name, 0.05), max_ray=12.0, reach=240)
+    layer, grid, other = make_layer(gcfg), make_grid(gcfg), make_grid(gcfg)
+    layer.integrate(frame, pose, sensor), grid.integrate(frame, pose, sensor)
+    x0, y0, w, h = layer.last_window()
+    ax, ay = max(x0 - 1, 0), max(y0 - 1, 0)
+    rect = (ax, ay, min(x0 + w + 1, gcfg["width"]) - ax, min(y0 + h + 1, gcfg["height"]) - ay)
+    t = {"full": [], "counted": [], "window": [], "occupancy": [], "to_grid": []}
+    for r in range(rounds + 3):
+        a, full = timed(lambda: layer.traversability(STEP_SLABS, ROBOT_SLABS))
+        b, part = timed(lambda: layer.traversability(STEP_SLABS, ROBOT_SLABS, rect=rect))
+        c, _ = timed(lambda: grid.occupancy(1))
+        d, _ = timed(lambda: layer.to_grid(other, STEP_SLABS, ROBOT_SLABS))
+        e, _ = timed(lambda: layer.traversability(STEP_SLABS, ROBOT_SLABS, return_ground=True, return_counts=True))
+        if r >= 3:
+            t["full"].append(a), t["window"].append(b), t["occupancy"].append(c), t["to_grid"].append(d), t["counted"].append(e)
+    assert np.array_equal(part, full[rect[1]:rect[1] + rect[3], rect[0]:rect[0] + rect[2]]) and np.array_equal(other.occupancy(1), full)
+    counts = layer.traversability(STEP_SLABS, ROBOT_SLABS, return_counts=True)[1]
+    return [{"scene": name, "points": len(frame), "cell_m": 0.05, "layer_cells": [gcfg["width"], gcfg["height"]], "window_grown_by_one": list(rect),
+             "step_slabs": STEP_SLABS, "robot_slabs": ROBOT_SLABS, "unknown_traversable_body_step": list(counts), "traversability_full_ms": spread(t["full"]), "traversability_full_with_ground_and_counts_ms": spread(t["counted"]),
+             "traversability_window_ms": spread(t["window"]), "grid_occupancy_full_ms": spread(t["occupancy"]), "to_grid_ms": spread(t["to_grid"])}]
+
+
+def pipeline_rows(rounds, n_frames, contenders):
+    import test_elev_facade
+    exe = test_elev_facade.build_binary()
+    bind, _ = placement()
+    rows = []
+    with tempfile.TemporaryDirectory() as td:
+        for name in GEOMETRY:
+            cfg, scene, dirs, rng = scene_and_beams(name)
+            ext = np.concatenate([[0, 0, np.sin(0.05), np.cos(0.05)], [0.3, 0.0, cfg.sensor_height]])
+            poses, drive = [syn.planar_pose(0.0, 0.0, 0.1)], os.path.join(td, name + ".bin")
+            with open(drive, "wb") as fh:
+                np.array([n_frames, cfg.voxel_size, cfg.max_range, 1.0]).tofile(fh)
+                ext.tofile(fh)
+                for k in range(n_frames):
+                    delta_true = syn.planar_pose(0.2, 0.0, np.deg2rad(1.0 + 0.1 * k))
+                    poses.append(syn.pose_mul(poses[-1], delta_true))
+                    wl = syn.pose_mul(poses[-1], ext)
+                    t = scene.raycast(wl[4:], dirs @ syn.quat_to_matrix(wl[:4]).T) + rng.normal(0, 0.01, len(dirs))
+                    np.array([float(len(dirs))]).tofile(fh)
+                    np.ascontiguousarray((dirs * t[:, None]).astype(np.float32).astype(np.float64)).tofile(fh)
+                    np.linspace(0.0, 1.0, len(dirs)).astype(np.float32).astype(np.float64).tofile(fh)
+                    syn.pose_mul(delta_true, syn.planar_pose(0.01 * (-1) ** k, 0.0, np.deg2rad(0.1))).tofile(fh)
+            for cell in CELLS:
+                gcfg = grid_config(name, cell)
+                lfile = os.path.join(td, "layer.bin")
+                np.array([gcfg[k] for k in ("cell", "origin_x", "origin_y", "width", "height")] + [Z_ORIGIN, SLAB, gcfg["max_ray"], STEP_SLABS, ROBOT_SLABS],
+                         dtype=np.float64).tofile(lfile)
+                runs = {"off": ([exe, "timed", drive, lfile, "off"], None, 0), "on": ([exe, "timed", drive, lfile, "on"], None, n_frames)}
+                for who, (other_exe, libdir) in contenders.items():
+                    runs[who] = ([other_exe, "timed", drive, lfile, "off"], dict(os.environ, LD_LIBRARY_PATH=libdir + ":" + os.environ.get("LD_LIBRARY_PATH", "")), 0)
+                per = {which: [] for which in runs}
+                for r in range(rounds + 1):  # (the first round warms the file cache and the driver)
+                    for which, (cmd, env, integrated) in runs.items():
+                        out = subprocess.check_output(cmd, text=True, preexec_fn=bind, env=env).splitlines()
+                        ms = np.array([float(ln.split()[3]) for ln in out if ln.startswith("frame ")])
+                        assert ("frames_integrated %d" % integrated) in out
+                        if r:
+                            per[which].append(float(np.median(ms[len(ms) // 2:])))
+                row = {"scene": name, "points": len(dirs), "cell_m": cell, "frames": n_frames,
+                       "what": "median RegisterFrame wall time of the drive's second half per process; spread over %d alternating processes each" % rounds}
+                row.update({"register_frame_ms_" + ("layer_" + which if which in ("on", "off") else which): spread(v) for which, v in per.items()})
+                rows.append(row)
+    return rows
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=30)
+    ap.add_argument("--ab", action="append", default=[], metavar="NAME=LIB")
+    ap.add_argument("--pipeline", action="store_true")
+    ap.add_argument("--pipeline-rounds", type=int, default=3)
+    ap.add_argument("--pipeline-frames", type=int, default=16)
+    ap.add_argument("--contender", action="append", default=[], metavar="NAME=EXE:LIBDIR")
+    a = ap.parse_args()
+    bind, where = placement()
+    if bind:
+        bind()
+    libs = {spec.split("=", 1)[0]: load_contender(spec.split("=", 1)[1]) for spec in a.ab}
+    res = {"caller_process": where, "rounds": a.rounds, "integrate": integrate_rows(a.rounds, libs), "traversability": traversability_rows(a.rounds)}
+    if a.pipeline:
+        others = {spec.split("=", 1)[0]: tuple(os.path.abspath(p) for p in spec.split("=", 1)[1].split(":", 1)) for spec in a.contender}
+        res["pipeline"] = pipeline_rows(a.pipeline_rounds, a.pipeline_frames, others)
+    print(json.dumps(res))
+
+
+if __name__ == "__main__":
+    main()
