@@ -1,6 +1,7 @@
 """The grid's clearance and costmap on the GPU (kicp_grid_clearance, kicp_grid_costmap, kicp_grid_last_window: K.OccupancyGrid.clearance,
 .costmap, .last_window) against the numpy restatement of include/kicp.h's text (tests/clearance_ref.py).  Everything is exact:
-np.array_equal, no tolerance anywhere.  The counters are set with set_counts, so only the last test drives frames."""
+np.array_equal, no tolerance anywhere.  The counters are set with set_counts, so only the last test drives frames.  Column distances
+of 253 .. 255 and scans to k = 254 (R = 253 and 254 on grids 520 cells long): tests/test_gpu_plan_regimes.py."""
 import ctypes as C
 
 import numpy as np

@@ -1,6 +1,8 @@
 """The height columns on the GPU (kicp_elev_*: K.ElevationLayer) against the numpy restatement of include/kicp.h's semantics
 (tests/elev_ref.py).  Everything is exact: after EVERY frame the columns and the six frame statistics must be np.array_equal to the
-restatement's, and every class, ground byte and count of the traversability likewise - no tolerance anywhere."""
+restatement's, and every class, ground byte and count of the traversability likewise - no tolerance anywhere.  Layer sides around
+one and two tiles, counts where waves share a shard (300 x 300) and frames around a wave's and a workgroup's size:
+tests/test_gpu_plan_regimes.py."""
 import ctypes as C
 
 import numpy as np

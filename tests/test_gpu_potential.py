@@ -1,7 +1,8 @@
 """The cost-to-go field on the GPU (kicp_grid_potential, kicp_grid_potential_of_costmap: K.OccupancyGrid.potential,
 .potential_of_costmap) against the restatement of include/kicp.h's text (tests/potential_ref.py).  The field is a unique fixed point
 over integers, so everything is exact: np.array_equal, no tolerance anywhere.  The round count is implementation-defined and is not
-compared; one test asserts that it took more than two batches where the field has to cross about a hundred tile borders."""
+compared; one test asserts that it took more than two batches where the field has to cross about a hundred tile borders.  More than
+one workgroup of goals and grids beyond the counting launch's first trip: tests/test_gpu_plan_regimes.py."""
 import ctypes as C
 
 import numpy as np
