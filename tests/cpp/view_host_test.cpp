@@ -55,7 +55,8 @@ int main(int argc, char **argv) {
 
     FILE *out = fopen(argv[2], "wb");
     if (!out) return 1;
-    const bool ok = fwrite(depth.data(), 4, depth.size(), out) == depth.size() && fwrite(verdicts.data(), 1, n_query, out) == n_query &&
-                    fwrite(cloud.data(), 8, cloud.size(), out) == cloud.size();
+    // (an empty vector's data() may be null, which fwrite must not be given: a map swept empty, or no queries)
+    const bool ok = fwrite(depth.data(), 4, depth.size(), out) == depth.size() && (n_query == 0 || fwrite(verdicts.data(), 1, n_query, out) == n_query) &&
+                    (cloud.empty() || fwrite(cloud.data(), 8, cloud.size(), out) == cloud.size());
     return (fclose(out) == 0 && ok) ? 0 : 1;
 }
