@@ -869,7 +869,7 @@ int kicp_grid_gain(const kicp_grid *grid, const kicp_gain_config *config, const 
  * THE LAYER is world aligned with the grid's geometry - width x height cells of side `cell` from (origin_x, origin_y), cell (ix, iy) at
  * iy * width + ix, max_ray - so its arrays overlay a kicp_grid of equal geometry, and a vertical one: z_origin and slab, in metres.
  * Each cell holds one 64-bit COLUMN: bit b is set when some used return ever had a world height in [z_origin + b slab, z_origin +
- * (b + 1) slab).  Bits are only ever set.
+ * (b + 1) slab).  kicp_elev_integrate only ever sets bits; kicp_elev_update (CARVING, below) also clears them.
  *
  * A FRAME is n points in the base frame, the pose and the sensor's origin in the base frame, exactly as for kicp_grid_integrate.  With R,
  * t of the pose (pose_to_rt, evaluated once on the host):
@@ -910,10 +910,40 @@ int kicp_grid_gain(const kicp_grid *grid, const kicp_gain_config *config, const 
  * kicp_grid_potential, kicp_grid_score_arcs, kicp_grid_frontiers, kicp_grid_gain - then runs on traversability, without a byte
  * crossing PCIe.
  *
- * KNOWN LIMITATIONS.  Bits never clear: a passer-by leaves a BODY cell until kicp_elev_clear or kicp_elev_set_columns.  One spurious
- * low return lowers a cell's ground for good.  A cell that has only ever returned an overhang, its ground unseen, reads as a high ground
- * and is marked STEP until a ground return arrives - conservative by choice.  There is no slope limit over a baseline longer than one
- * cell, and no merge with the free space the grid's rays carve.
+ * CARVING ALONG THE FRAME'S RAYS.  kicp_elev_integrate only ever sets bits.  An UPDATE of a frame (kicp_elev_update*) is a CARVE - bits
+ * that the frame's rays pass through are cleared - and then the mark that kicp_elev_integrate does, so a frame's own returns always
+ * survive it.  With the carve configuration G = margin_steps, W = widen_slabs (0 .. 64) and keep_ground (0 or 1; KICP_ERR_ARG
+ * otherwise):
+ *   the sensor's slab is ss = floor((wz_sensor - z_origin) / slab), wz_sensor from row 2 of the pose exactly as a point's wz; when ss
+ *   does not satisfy -32768 <= ss <= 32767 (a NaN fails it) the frame carves nothing.
+ *   A point is ELIGIBLE when its class (the four above, unchanged) is not SKIPPED and its s satisfies -32768 <= s <= 32767, compared
+ *   on doubles; s of an OUTSIDE_GRID point is computed as for any other.  OUTSIDE_GRID and OUTSIDE_COLUMN points do carve - without
+ *   the rays of ceiling returns nothing above the sensor would ever clear -; points skipped for reach do not, as in the grid.
+ *   THE RAY of a distinct triple (ex, ey, es) of an eligible point, with dx = ex - sx, dy = ey - sy, d = es - ss, m = max(|dx|, |dy|),
+ *   takes the steps k = 0 .. m - 1 - G: none when m <= G, and m = 0 never carves.  The cell of step k is the grid's walk's (step k
+ *   visits (sx + sgn(dx) ((2 k |dx| + m) / (2 m)), sy + sgn(dy) ((2 k |dy| + m) / (2 m))), integer divisions): it starts at the
+ *   sensor's cell and never reaches the endpoint cell.  The slab of the ray at parameter j / (2 m) is
+ *     u(j) = ss + sgn(d) ((j |d| + m) / (2 m))   (integer division; u(0) = ss, u(2 m) = es; j <= 8191, |d| <= 65535: below 2^29).
+ *   Step k spans a = u(max(2 k - 1, 0)) to b = u(2 k + 1); lo = min(a, b) - W, hi = max(a, b) + W; its MASK is the bits max(lo, 0) ..
+ *   min(hi, 63), empty when hi < 0 or lo > 63.
+ *   THE COLUMNS.  For a cell inside the grid with column c before the frame, let M be the OR of the masks of all steps of all rays that
+ *   visit it.  The carved column is c & ~(M & ~keep), keep = c & -c - the column's lowest set bit, which is then never cleared - with
+ *   keep_ground, else 0.  The mark then ORs in the frame's USED bits as above.  Cells outside the grid are ignored; a ray whose sensor
+ *   cell or endpoint cell lies outside still carves the cells inside that it visits.
+ * The statistics are nine words (KICP_ELEV_UPDATE_STATS): the six above, new_bits and new_cells counted relative to the CARVED columns;
+ * carve_points, the eligible points (0 when ss is out of range); bits_cleared; cells_emptied, the columns that were not zero before and
+ * are zero after the carve (always 0 with keep_ground).  The columns, bits_cleared and cells_emptied depend only on the SET of triples
+ * and on the columns before the frame.  Every visited cell lies within reach of the sensor's cell, so kicp_elev_last_window and
+ * "classes change only inside the window grown by one cell" hold for an update as for an integrate.  kicp_elev_update and
+ * kicp_elev_update_device mirror the two integrate entries in arguments, errors, frame count, last window and n == 0;
+ * kicp_elev_update_columns is the same arithmetic as pure host code over columns in kicp_elev_columns' layout (`cells` must be the
+ * configuration's width * height; the configuration is checked as kicp_elev_create checks it) and needs no GPU.
+ *
+ * KNOWN LIMITATIONS.  Bits clear only under kicp_elev_update*: kicp_elev_integrate never clears one.  Returns beyond reach do not
+ * carve.  With keep_ground, a cell whose floor was never seen keeps a passer-by's lowest bit until a floor return arrives; without it
+ * grazing rays erode the floor.  One spurious low return lowers a cell's ground for good: keep_ground keeps exactly that bit.  A cell that has only
+ * ever returned an overhang, its ground unseen, reads as a high ground and is marked STEP until a ground return arrives - conservative
+ * by choice.  There is no slope limit over a baseline longer than one cell, and no merge with the free space the grid's rays carve.
  *
  * Limits: width * height <= 2^28 and reach <= 4095 (KICP_ERR_CAPACITY, the size in the message); cell, max_ray and slab positive and
  * finite, the origin and z_origin finite, width and height >= 1, no null pointer but the nullable outputs (KICP_ERR_ARG).  Every
@@ -929,7 +959,13 @@ typedef struct kicp_elev_traversability_config {
     unsigned int step_slabs;  /* S: the highest step the robot takes, in slabs: 0 .. 62 */
     unsigned int robot_slabs; /* H: the robot's height in slabs: S < H <= 64 */
 } kicp_elev_traversability_config;
+typedef struct kicp_elev_carve_config {
+    unsigned int margin_steps; /* G: the last G steps of every ray before its endpoint cell are not carved */
+    unsigned int widen_slabs;  /* W: 0 .. 64, each step's span of slabs is widened by W on both sides */
+    unsigned int keep_ground;  /* 0 or 1: the lowest set bit of a column is never cleared */
+} kicp_elev_carve_config;
 #define KICP_ELEV_STATS 6
+#define KICP_ELEV_UPDATE_STATS 9
 int kicp_elev_create(const kicp_elev_config *config, int device, kicp_elev **out);
 void kicp_elev_destroy(kicp_elev *elev);
 /* the configuration, reach, and the frames integrated since creation or the last kicp_elev_clear (each nullable) */
@@ -941,6 +977,14 @@ int kicp_elev_integrate(kicp_elev *elev, const double *frame_xyz, size_t n, cons
                         unsigned long long out_stats[6]);
 int kicp_elev_integrate_device(kicp_elev *elev, const double *d_frame_xyz, size_t n, const double pose_qt[7], const double sensor_xyz[3],
                                unsigned long long out_stats[6]);
+/* One frame as an UPDATE: the carve along its rays, then the mark.  out_stats (nullable): the nine words above. */
+int kicp_elev_update(kicp_elev *elev, const double *frame_xyz, size_t n, const double pose_qt[7], const double sensor_xyz[3],
+                     const kicp_elev_carve_config *carve_config, unsigned long long out_stats[9]);
+int kicp_elev_update_device(kicp_elev *elev, const double *d_frame_xyz, size_t n, const double pose_qt[7], const double sensor_xyz[3],
+                            const kicp_elev_carve_config *carve_config, unsigned long long out_stats[9]);
+int kicp_elev_update_columns(const kicp_elev_config *config, unsigned long long *columns, size_t cells, const double *frame_xyz, size_t n,
+                             const double pose_qt[7], const double sensor_xyz[3], const kicp_elev_carve_config *carve_config,
+                             unsigned long long out_stats[9]);
 /* The columns, one 64-bit word per cell; cap_cells / cells must be the layer's width * height (KICP_ERR_ARG otherwise).
  * kicp_elev_set_columns replaces them all (the frame count is not part of them). */
 int kicp_elev_columns(const kicp_elev *elev, unsigned long long *out, size_t cap_cells);

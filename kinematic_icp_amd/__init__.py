@@ -100,6 +100,12 @@ class ElevationTraversabilityConfig(C.Structure):
     _fields_ = [("step_slabs", C.c_uint), ("robot_slabs", C.c_uint)]
 
 
+class ElevationCarveConfig(C.Structure):
+    """kicp_elev_carve_config: the last margin_steps steps of every ray before its endpoint cell are not carved, each step's span of slabs
+    is widened by widen_slabs (0 .. 64) on both sides, and with keep_ground (0 or 1) the lowest set bit of a column is never cleared"""
+    _fields_ = [("margin_steps", C.c_uint), ("widen_slabs", C.c_uint), ("keep_ground", C.c_uint)]
+
+
 class ViewConfig(C.Structure):
     """kicp_view_config: a cube map of res x res pixels per face; the verdict looks at (2 window + 1)^2 pixels, needs min_rays returns
     among them and a gap of more than margin + margin_per_metre * depth; max_ray bounds the (Chebyshev) depth on both sides"""
@@ -241,6 +247,10 @@ _SIGNATURES = {
     "kicp_elev_clear": (C.c_int, [C.c_void_p]),
     "kicp_elev_integrate": (C.c_int, [C.c_void_p, _dp, C.c_size_t, _dp, _dp, C.POINTER(C.c_ulonglong)]),
     "kicp_elev_integrate_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, _dp, _dp, C.POINTER(C.c_ulonglong)]),
+    "kicp_elev_update": (C.c_int, [C.c_void_p, _dp, C.c_size_t, _dp, _dp, C.POINTER(ElevationCarveConfig), C.POINTER(C.c_ulonglong)]),
+    "kicp_elev_update_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, _dp, _dp, C.POINTER(ElevationCarveConfig), C.POINTER(C.c_ulonglong)]),
+    "kicp_elev_update_columns": (C.c_int, [C.POINTER(ElevationConfig), C.POINTER(C.c_ulonglong), C.c_size_t, _dp, C.c_size_t, _dp, _dp, C.POINTER(ElevationCarveConfig),
+                                           C.POINTER(C.c_ulonglong)]),
     "kicp_elev_columns": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong), C.c_size_t]),
     "kicp_elev_set_columns": (C.c_int, [C.c_void_p, C.POINTER(C.c_ulonglong), C.c_size_t]),
     "kicp_elev_last_window": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_uint)]),
@@ -854,6 +864,20 @@ def traversability_from_columns(columns, step_slabs, robot_slabs, rect=None, ret
                                                                                                   C.byref(cfg), x0, y0, w, h, o, g, n, cap), w, h, return_ground, return_counts)
 
 
+def elev_update_columns(config, columns, frame, pose, sensor_xyz=(0.0, 0.0, 0.0), margin_steps=2, widen_slabs=1, keep_ground=1):
+    """kicp_elev_update_columns: ElevationLayer.update as pure host code.  config: an ElevationConfig, or a dict with its fields;
+    columns: uint64 (height, width), contiguous, CHANGED IN PLACE -> the nine words of the update.  Needs no GPU."""
+    cfg = config if isinstance(config, ElevationConfig) else ElevationConfig(*[config[name] for name, _ in ElevationConfig._fields_])
+    if not (isinstance(columns, np.ndarray) and columns.dtype == np.uint64 and columns.flags.c_contiguous and columns.flags.writeable):
+        raise KicpError(KICP_ERR_ARG, "columns must be a writeable contiguous uint64 array")
+    a, p = _d(np.asarray(frame, dtype=np.float64).reshape(-1, 3))
+    s, sp = _d(np.asarray(sensor_xyz, dtype=np.float64).reshape(3))
+    carve, out = ElevationCarveConfig(int(margin_steps), int(widen_slabs), int(keep_ground)), np.zeros(9, dtype=np.uint64)
+    _check(lib().kicp_elev_update_columns(C.byref(cfg), columns.ctypes.data_as(C.POINTER(C.c_ulonglong)), columns.size, p if a.size else None, a.size // 3, _pose_ptr(pose), sp,
+                                          C.byref(carve), out.ctypes.data_as(C.POINTER(C.c_ulonglong))))
+    return tuple(int(v) for v in out)
+
+
 class OccupancyGrid:
     """kicp_grid: a world-aligned 2-D grid of (hits, misses) counters a mapping run draws frame by frame - every used point's cell is
     hit, the cells its ray from the sensor crosses are missed, once per cell per frame (include/kicp.h states the exact semantics).
@@ -1016,7 +1040,8 @@ class OccupancyGrid:
 class ElevationLayer:
     """kicp_elev: a world-aligned layer over a grid's geometry that keeps, per cell, one 64-bit column of the world heights that ever
     returned there, and reads traversability off it by height over the local ground (include/kicp.h states the exact semantics and the
-    known limitations).  It owns its device memory; the columns stay in HBM until they are asked for."""
+    known limitations).  integrate only ever sets bits; update also clears the bits a frame's rays pass through, so what has left is
+    forgotten.  It owns its device memory; the columns stay in HBM until they are asked for."""
 
     def __init__(self, cell, origin_x, origin_y, width, height, z_origin, slab, max_ray, device=0):
         self._h = None
@@ -1024,7 +1049,7 @@ class ElevationLayer:
         h = C.c_void_p()
         _check(lib().kicp_elev_create(C.byref(cfg), int(device), C.byref(h)))
         self._h, self.device, self.width, self.height = h, device, int(width), int(height)
-        self._last = np.zeros(6, dtype=np.uint64)
+        self._last, self._last_update = np.zeros(6, dtype=np.uint64), np.zeros(9, dtype=np.uint64)
 
     def __del__(self):
         if getattr(self, "_h", None) and _lib is not None:
@@ -1058,9 +1083,35 @@ class ElevationLayer:
                                                 self._last.ctypes.data_as(C.POINTER(C.c_ulonglong))))
         return self.last_frame()
 
+    def update(self, frame, pose, sensor_xyz=(0.0, 0.0, 0.0), margin_steps=2, widen_slabs=1, keep_ground=1):
+        """kicp_elev_update: the frame as an UPDATE - the bits its rays pass through are cleared (the last margin_steps steps of a ray
+        left alone, each step's slabs widened by widen_slabs, a column's lowest bit kept with keep_ground), then the frame is marked as
+        integrate marks it -> integrate's six words, counted on the carved columns, then (carve_points, bits_cleared, cells_emptied)"""
+        a, p = _d(np.asarray(frame, dtype=np.float64).reshape(-1, 3))
+        s, sp = _d(np.asarray(sensor_xyz, dtype=np.float64).reshape(3))
+        cfg, out = ElevationCarveConfig(int(margin_steps), int(widen_slabs), int(keep_ground)), np.zeros(9, dtype=np.uint64)
+        _check(lib().kicp_elev_update(self._h, p if a.size else None, a.size // 3, _pose_ptr(pose), sp, C.byref(cfg), out.ctypes.data_as(C.POINTER(C.c_ulonglong))))
+        self._last[:], self._last_update = out[:6], out
+        return self.last_update()
+
+    def update_device(self, device_frame, pose, sensor_xyz=(0.0, 0.0, 0.0), margin_steps=2, widen_slabs=1, keep_ground=1, n=None):
+        """kicp_elev_update_device: the same for a DeviceFrame (or anything with .ptr and .n) already in HBM"""
+        s, sp = _d(np.asarray(sensor_xyz, dtype=np.float64).reshape(3))
+        count = device_frame.n if n is None else int(n)
+        cfg, out = ElevationCarveConfig(int(margin_steps), int(widen_slabs), int(keep_ground)), np.zeros(9, dtype=np.uint64)
+        _check(lib().kicp_elev_update_device(self._h, device_frame.ptr if count else None, count, _pose_ptr(pose), sp, C.byref(cfg),
+                                             out.ctypes.data_as(C.POINTER(C.c_ulonglong))))
+        self._last[:], self._last_update = out[:6], out
+        return self.last_update()
+
     def last_frame(self):
-        """(used, skipped, outside_grid, outside_column, new_bits, new_cells) of the last integrated frame"""
+        """(used, skipped, outside_grid, outside_column, new_bits, new_cells) of the last integrated or updated frame"""
         return tuple(int(v) for v in self._last)
+
+    def last_update(self):
+        """the nine words of the last update (zeros before the first one): last_frame()'s six, then carve_points, bits_cleared,
+        cells_emptied"""
+        return tuple(int(v) for v in self._last_update)
 
     def columns(self):
         """-> uint64 (height, width): bit b of a column is set when a return ever had a world height in slab b"""

@@ -230,6 +230,10 @@ inline std::shared_ptr<kicp_grid> clone_grid(const kicp_grid *grid, int device =
 using ElevationConfig = kicp_elev_config;
 using ElevationTraversabilityConfig = kicp_elev_traversability_config;
 using ElevationStats = std::array<unsigned long long, KICP_ELEV_STATS>;  // used, skipped, outside_grid, outside_column, new_bits, new_cells
+// what KinematicICP::EnableElevationCarving takes - margin_steps, widen_slabs, keep_ground - and the nine words of an update: the six
+// above, then carve_points, bits_cleared, cells_emptied
+using ElevationCarveConfig = kicp_elev_carve_config;
+using ElevationCarveStats = std::array<unsigned long long, KICP_ELEV_UPDATE_STATS>;
 inline std::shared_ptr<kicp_elev> make_elevation(const ElevationConfig &config, int device = -1) {
     kicp_elev *elev = nullptr;
     check(kicp_elev_create(&config, device < 0 ? default_device() : device, &elev), "kicp_bridge::make_elevation");

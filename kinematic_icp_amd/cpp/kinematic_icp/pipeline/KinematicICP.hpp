@@ -8,6 +8,7 @@
 // (SURVEY.md section 8f rows 1, 2 and 4).
 #pragma once
 #include <Eigen/Core>
+#include <algorithm>
 #include <array>
 #include <cmath>
 #include <cstdint>
@@ -83,6 +84,9 @@ public:
           grid_(kicp_bridge::clone_grid(o.grid_.get())),
           elev_(kicp_bridge::clone_elevation(o.elev_.get())),
           last_elev_stats_(o.last_elev_stats_),
+          elev_carving_(o.elev_carving_),
+          elev_carve_(o.elev_carve_),
+          last_elev_carve_stats_(o.last_elev_carve_stats_),
           view_(kicp_bridge::clone_view(o.view_.get())),
           last_removal_(o.last_removal_),
           sensor_in_base_(o.sensor_in_base_) {
@@ -101,6 +105,9 @@ public:
           grid_(std::move(o.grid_)),
           elev_(std::move(o.elev_)),
           last_elev_stats_(o.last_elev_stats_),
+          elev_carving_(o.elev_carving_),
+          elev_carve_(o.elev_carve_),
+          last_elev_carve_stats_(o.last_elev_carve_stats_),
           view_(std::move(o.view_)),
           last_removal_(o.last_removal_),
           sensor_in_base_(o.sensor_in_base_) {
@@ -112,6 +119,7 @@ public:
         std::swap(correspondence_threshold_, o.correspondence_threshold_), std::swap(config_, o.config_), std::swap(preprocessor_, o.preprocessor_);
         local_map_ = std::move(o.local_map_);
         std::swap(pre_, o.pre_);
+        std::swap(elev_carving_, o.elev_carving_), std::swap(elev_carve_, o.elev_carve_), std::swap(last_elev_carve_stats_, o.last_elev_carve_stats_);
         std::swap(grid_, o.grid_), std::swap(elev_, o.elev_), std::swap(last_elev_stats_, o.last_elev_stats_), std::swap(view_, o.view_), std::swap(last_removal_, o.last_removal_), std::swap(sensor_in_base_, o.sensor_in_base_);
         return *this;
     }
@@ -467,10 +475,24 @@ public:
     // Elevation() is the shared handle (null without a layer): kicp_elev_to_grid(Elevation().get(), &config, planner_grid.get()) puts the
     // traversability into a grid a node dedicates to its planner.  LastElevationStats(): used, skipped, outside_grid, outside_column,
     // new_bits, new_cells of the last frame (zeros before the first).
-    void EnableElevation(const kicp_bridge::ElevationConfig &config) { elev_ = kicp_bridge::make_elevation(config), last_elev_stats_ = {}; }
-    void DisableElevation() { elev_.reset(), last_elev_stats_ = {}; }
+    void EnableElevation(const kicp_bridge::ElevationConfig &config) { elev_ = kicp_bridge::make_elevation(config), last_elev_stats_ = {}, DisableElevationCarving(); }
+    void DisableElevation() { elev_.reset(), last_elev_stats_ = {}, DisableElevationCarving(); }
     std::shared_ptr<kicp_elev> Elevation() const { return elev_; }
     const kicp_bridge::ElevationStats &LastElevationStats() const { return last_elev_stats_; }
+    // CARVING (off by default; a new layer starts with it off).  With it on, a frame goes into the layer as an UPDATE (kicp.h
+    // kicp_elev_update): the bits its rays pass through are cleared, then the frame is marked, so what has left - a passer-by - leaves
+    // the traversability too.  The configuration is checked here (std::invalid_argument).  LastElevationCarveStats(): the nine words of
+    // the last update - LastElevationStats()'s six, counted on the carved columns, then carve_points, bits_cleared, cells_emptied
+    // (zeros before the first, and while carving is off).
+    void EnableElevationCarving(const kicp_bridge::ElevationCarveConfig &config) {
+        RequireElevation("EnableElevationCarving");
+        if (config.widen_slabs > 64u || config.keep_ground > 1u)
+            throw std::invalid_argument("KinematicICP::EnableElevationCarving: widen_slabs must lie in 0 .. 64 and keep_ground must be 0 or 1");
+        elev_carving_ = true, elev_carve_ = config, last_elev_carve_stats_ = {};
+    }
+    void DisableElevationCarving() { elev_carving_ = false, elev_carve_ = {}, last_elev_carve_stats_ = {}; }
+    bool ElevationCarving() const { return elev_carving_; }
+    const kicp_bridge::ElevationCarveStats &LastElevationCarveStats() const { return last_elev_carve_stats_; }
     // -1 unknown, 0 traversable, 100 obstacle per cell of `rect` (nullptr: the full layer), row-major; ground (nullable): the ground's
     // slab per cell, 255 unknown; counts (nullable): unknown, traversable, BODY, STEP only.  The result for a rectangle equals the full
     // layer's restricted to it; a frame changes it only inside ElevationLastWindow() grown by one cell.
@@ -546,6 +568,14 @@ protected:
         double pose[7];
         kicp_bridge::to_params(last_pose_, pose);
         const double sensor[3] = {sensor_in_base_.x(), sensor_in_base_.y(), sensor_in_base_.z()};
+        if (elev_carving_) {
+            unsigned long long *stats = last_elev_carve_stats_.data();
+            kicp_bridge::check(on_device ? kicp_elev_update_device(elev_.get(), xyz, n, pose, sensor, &elev_carve_, stats)
+                                         : kicp_elev_update(elev_.get(), xyz, n, pose, sensor, &elev_carve_, stats),
+                               "height columns");
+            std::copy(stats, stats + KICP_ELEV_STATS, last_elev_stats_.begin());
+            return;
+        }
         unsigned long long *stats = last_elev_stats_.data();
         kicp_bridge::check(on_device ? kicp_elev_integrate_device(elev_.get(), xyz, n, pose, sensor, stats) : kicp_elev_integrate(elev_.get(), xyz, n, pose, sensor, stats),
                            "height columns");
@@ -654,6 +684,9 @@ protected:
     std::shared_ptr<kicp_grid> grid_;      // EnableGrid's occupancy grid (backend detail); null: no grid
     std::shared_ptr<kicp_elev> elev_;      // EnableElevation's height columns (backend detail); null: no layer
     kicp_bridge::ElevationStats last_elev_stats_{};  // the last frame's statistics of that layer
+    bool elev_carving_ = false;                      // EnableElevationCarving: frames go into the layer as updates
+    kicp_bridge::ElevationCarveConfig elev_carve_{};
+    kicp_bridge::ElevationCarveStats last_elev_carve_stats_{};  // the last update's nine words
     std::shared_ptr<kicp_view> view_;      // EnableSeeThroughRemoval's depth view (backend detail); null: nothing is removed
     std::array<unsigned long long, 4> last_removal_{};  // the last frame's sweep statistics
     Eigen::Vector3d sensor_in_base_ = Eigen::Vector3d(0.0, 0.0, 0.0);  // the translation of the last frame's lidar_to_base

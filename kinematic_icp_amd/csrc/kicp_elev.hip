@@ -1,6 +1,6 @@
 // kicp_elev.hip -- the height columns a mapping run keeps beside its occupancy grid (kicp_elev_*; include/kicp.h states the semantics):
 // per cell one 64-bit column of the world heights that ever returned, and the traversability read off it - unknown, traversable,
-// obstacle by height over the local ground.  Kernels: kicp_elev.hpp; the arithmetic they share with the host entries:
+// obstacle by height over the local ground; kicp_elev_update* also clear what a frame's rays pass through.  Kernels: kicp_elev.hpp; the arithmetic they share with the host entries:
 // kicp_elev_host.hpp.  kicp_elev_to_grid writes the classes into a kicp_grid's counters, so this file sees that handle too.
 #include <cstring>
 #include <memory>
@@ -25,6 +25,7 @@ struct kicp_elev {
         DevBuf<unsigned int> d_stats;
         PinnedBuf<unsigned int> h_stats;
         FrameUpload upload;  // kicp_elev_integrate's points
+        DevBuf<unsigned long long> d_rays;  // kicp_elev_update*: the carve list, room for one record per point
     } frame;
     // kicp_elev_traversability: the classes, the ground bytes and the four counts in their shards
     mutable struct {
@@ -60,15 +61,56 @@ int check_elev_rect(unsigned int width, unsigned int height, const ElevRect &r, 
     if (cap != static_cast<size_t>(r.w) * r.h) return fail(KICP_ERR_ARG, "cap must be w * h = " + std::to_string(static_cast<size_t>(r.w) * r.h));
     return KICP_OK;
 }
-// the frame at d_xyz (n points; arguments checked): one launch, the statistics back, the stream drained
-int integrate_on_device(kicp_elev *elev, const double *d_xyz, size_t n, const double pose_qt[7], const double sensor_xyz[3], unsigned long long out_stats[6]) {
-    unsigned long long stats[6] = {0, 0, 0, 0, 0, 0};
+// the layer's configuration as kicp_elev_create and the pure-host update take it -> the geometry and the number of cells
+int check_elev_config(const kicp_elev_config *cfg, ElevGeom &geom, unsigned long long &cells) {
+    if (!(cfg->cell > 0.0) || !std::isfinite(cfg->cell)) return fail(KICP_ERR_ARG, "cell must be positive and finite");
+    if (!(cfg->max_ray > 0.0) || !std::isfinite(cfg->max_ray)) return fail(KICP_ERR_ARG, "max_ray must be positive and finite");
+    if (!(cfg->slab > 0.0) || !std::isfinite(cfg->slab)) return fail(KICP_ERR_ARG, "slab must be positive and finite");
+    if (!std::isfinite(cfg->origin_x) || !std::isfinite(cfg->origin_y) || !std::isfinite(cfg->z_origin)) return fail(KICP_ERR_ARG, "the origin and z_origin must be finite");
+    if (cfg->width == 0 || cfg->height == 0) return fail(KICP_ERR_ARG, "width and height must be at least 1");
+    cells = static_cast<unsigned long long>(cfg->width) * cfg->height;
+    if (cells > kGridMaxCells)
+        return fail(KICP_ERR_CAPACITY, "the layer would have " + std::to_string(cfg->width) + " x " + std::to_string(cfg->height) + " = " + std::to_string(cells) +
+                                           " cells (limit 2^28 = " + std::to_string(kGridMaxCells) + ")");
+    const double reach = std::ceil(cfg->max_ray / cfg->cell);
+    if (!(reach <= static_cast<double>(kGridMaxReach)))
+        return fail(KICP_ERR_CAPACITY, "max_ray / cell gives a reach of " + std::to_string(reach) + " cells (limit " + std::to_string(kGridMaxReach) + ")");
+    const double inf = std::numeric_limits<double>::infinity();
+    geom = ElevGeom{GridGeom{cfg->cell, cfg->origin_x, cfg->origin_y, -inf, inf, cfg->width, cfg->height, static_cast<int32_t>(reach)}, cfg->z_origin, cfg->slab};
+    return KICP_OK;
+}
+int check_carve_config(const kicp_elev_carve_config *cfg, ElevCarveParams &p) {
+    p = ElevCarveParams{cfg->margin_steps, cfg->widen_slabs, cfg->keep_ground};
+    if (cfg->widen_slabs > kElevMaxWiden) return fail(KICP_ERR_ARG, "widen_slabs must lie in 0 .. 64");
+    if (cfg->keep_ground > 1u) return fail(KICP_ERR_ARG, "keep_ground must be 0 or 1");
+    return KICP_OK;
+}
+// The frame at d_xyz (n points; arguments checked): the launches, the statistics back, the stream drained.  carve (nullable): an UPDATE -
+// the list and the carve are launched in front of the mark, and out_stats has nine words, else six.
+int integrate_on_device(kicp_elev *elev, const double *d_xyz, size_t n, const double pose_qt[7], const double sensor_xyz[3], unsigned long long *out_stats,
+                        const ElevCarveParams *carve = nullptr) {
+    unsigned long long stats[KICP_ELEV_UPDATE_STATS] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     const ElevFrame f = elev_frame(elev->geom, pose_qt, sensor_xyz);
     elev->has_window = true, elev->win_x0 = f.plane.gx0, elev->win_y0 = f.plane.gy0;
     if (n) {
         hipStream_t st = elev->stream;
         auto &fr = elev->frame;
+        const ElevCarveFrame cf = carve ? elev_carve_frame(elev->geom, f, sensor_xyz) : ElevCarveFrame{0, false};
+        if (cf.carves && n > fr.d_rays.capacity()) {
+            HIP_TRY(hipStreamSynchronize(st));
+            if (int rc = fr.d_rays.reserve(n + n / 2)) return rc;
+        }
         HIP_TRY(hipMemsetAsync(fr.d_stats.get(), 0, kElevCountWords * sizeof(unsigned int), st));
+        if (cf.carves) {
+            const uint32_t list_blocks = static_cast<uint32_t>((n + kElevBlock * kElevListPoints - 1) / (kElevBlock * kElevListPoints));
+            hipLaunchKernelGGL(k_elev_list, dim3(list_blocks), dim3(kElevBlock), 0, st, d_xyz, static_cast<uint32_t>(n), elev->geom, f, fr.d_rays.get(), fr.d_stats.get());
+            // One wave per ray, at most one ray per point: a wave for each of n rays, in up to 2048 workgroups whose waves stride over the
+            // list - its length is on the device.  (Sized by points per workgroup, as k_grid_rays is, a 1 080-beam scan got 5 workgroups
+            // for 1 080 rays of up to 500 steps: DESIGN 5i.)
+            const uint32_t ray_blocks = static_cast<uint32_t>((n + kElevBlock / 64u - 1) / (kElevBlock / 64u));
+            hipLaunchKernelGGL(k_elev_carve, dim3(std::min(ray_blocks, 2048u)), dim3(kElevBlock), 0, st, fr.d_rays.get(), fr.d_stats.get() + kElevListWord, elev->geom, f, cf.ss,
+                               *carve, elev->d_columns.get(), fr.d_stats.get());
+        }
         hipLaunchKernelGGL(k_elev_mark, dim3(static_cast<uint32_t>((n + kElevBlock - 1) / kElevBlock)), dim3(kElevBlock), 0, st, d_xyz, static_cast<uint32_t>(n), elev->geom,
                            f, elev->d_columns.get(), fr.d_stats.get());
         HIP_TRY(hipGetLastError());
@@ -76,10 +118,11 @@ int integrate_on_device(kicp_elev *elev, const double *d_xyz, size_t n, const do
         HIP_TRY(hipStreamSynchronize(st));
         for (int k = 0; k < kElevStats; ++k) stats[1 + k] = shard_sum(fr.h_stats.get(), k);
         stats[0] = n - (stats[1] + stats[2] + stats[3]);
+        if (cf.carves) stats[6] = fr.h_stats.get()[kElevListWord], stats[7] = shard_sum(fr.h_stats.get(), 5), stats[8] = shard_sum(fr.h_stats.get(), 6);
     }
     ++elev->frames;
     if (out_stats)
-        for (int k = 0; k < 6; ++k) out_stats[k] = stats[k];
+        for (int k = 0; k < (carve ? KICP_ELEV_UPDATE_STATS : KICP_ELEV_STATS); ++k) out_stats[k] = stats[k];
     return KICP_OK;
 }
 int check_frame_args(const kicp_elev *elev, const double *xyz, size_t n, const double *pose_qt, const double *sensor_xyz) {
@@ -94,23 +137,12 @@ int kicp_elev_create(const kicp_elev_config *cfg, int device, kicp_elev **out) {
     KICP_TRACE_CALL();
     if (!cfg || !out) return fail(KICP_ERR_ARG, "null argument");
     *out = nullptr;
-    if (!(cfg->cell > 0.0) || !std::isfinite(cfg->cell)) return fail(KICP_ERR_ARG, "cell must be positive and finite");
-    if (!(cfg->max_ray > 0.0) || !std::isfinite(cfg->max_ray)) return fail(KICP_ERR_ARG, "max_ray must be positive and finite");
-    if (!(cfg->slab > 0.0) || !std::isfinite(cfg->slab)) return fail(KICP_ERR_ARG, "slab must be positive and finite");
-    if (!std::isfinite(cfg->origin_x) || !std::isfinite(cfg->origin_y) || !std::isfinite(cfg->z_origin)) return fail(KICP_ERR_ARG, "the origin and z_origin must be finite");
-    if (cfg->width == 0 || cfg->height == 0) return fail(KICP_ERR_ARG, "width and height must be at least 1");
-    const unsigned long long cells = static_cast<unsigned long long>(cfg->width) * cfg->height;
-    if (cells > kGridMaxCells)
-        return fail(KICP_ERR_CAPACITY, "the layer would have " + std::to_string(cfg->width) + " x " + std::to_string(cfg->height) + " = " + std::to_string(cells) +
-                                           " cells (limit 2^28 = " + std::to_string(kGridMaxCells) + ")");
-    const double reach = std::ceil(cfg->max_ray / cfg->cell);
-    if (!(reach <= static_cast<double>(kGridMaxReach)))
-        return fail(KICP_ERR_CAPACITY, "max_ray / cell gives a reach of " + std::to_string(reach) + " cells (limit " + std::to_string(kGridMaxReach) + ")");
+    ElevGeom geom;
+    unsigned long long cells;
+    if (int rc = check_elev_config(cfg, geom, cells)) return rc;
     if (int rc = set_device(device)) return rc;
     std::unique_ptr<kicp_elev> elev(new kicp_elev);
-    elev->device = device, elev->cfg = *cfg, elev->cells = static_cast<size_t>(cells);
-    const double inf = std::numeric_limits<double>::infinity();
-    elev->geom = ElevGeom{GridGeom{cfg->cell, cfg->origin_x, cfg->origin_y, -inf, inf, cfg->width, cfg->height, static_cast<int32_t>(reach)}, cfg->z_origin, cfg->slab};
+    elev->device = device, elev->cfg = *cfg, elev->cells = static_cast<size_t>(cells), elev->geom = geom;
     HIP_TRY(hipStreamCreateWithFlags(&elev->stream, hipStreamNonBlocking));
     if (int rc = elev->d_columns.reserve(elev->cells)) return rc;
     if (int rc = elev->frame.d_stats.reserve(kElevCountWords)) return rc;
@@ -154,6 +186,43 @@ int kicp_elev_integrate_device(kicp_elev *elev, const double *d_frame_xyz, size_
     if (int rc = check_frame_args(elev, d_frame_xyz, n, pose_qt, sensor_xyz)) return rc;
     if (int rc = set_device(elev->device)) return rc;
     return integrate_on_device(elev, d_frame_xyz, n, pose_qt, sensor_xyz, out_stats);
+}
+int kicp_elev_update(kicp_elev *elev, const double *frame_xyz, size_t n, const double pose_qt[7], const double sensor_xyz[3], const kicp_elev_carve_config *carve_config,
+                     unsigned long long out_stats[9]) {
+    KICP_TRACE_CALL();
+    if (int rc = check_frame_args(elev, frame_xyz, n, pose_qt, sensor_xyz)) return rc;
+    if (!carve_config) return fail(KICP_ERR_ARG, "null argument");
+    ElevCarveParams p;
+    if (int rc = check_carve_config(carve_config, p)) return rc;
+    if (int rc = set_device(elev->device)) return rc;
+    if (int rc = elev->frame.upload.put(frame_xyz, n, elev->stream)) return rc;
+    return integrate_on_device(elev, elev->frame.upload.d_xyz.get(), n, pose_qt, sensor_xyz, out_stats, &p);
+}
+int kicp_elev_update_device(kicp_elev *elev, const double *d_frame_xyz, size_t n, const double pose_qt[7], const double sensor_xyz[3],
+                            const kicp_elev_carve_config *carve_config, unsigned long long out_stats[9]) {
+    KICP_TRACE_CALL();
+    if (int rc = check_frame_args(elev, d_frame_xyz, n, pose_qt, sensor_xyz)) return rc;
+    if (!carve_config) return fail(KICP_ERR_ARG, "null argument");
+    ElevCarveParams p;
+    if (int rc = check_carve_config(carve_config, p)) return rc;
+    if (int rc = set_device(elev->device)) return rc;
+    return integrate_on_device(elev, d_frame_xyz, n, pose_qt, sensor_xyz, out_stats, &p);
+}
+int kicp_elev_update_columns(const kicp_elev_config *config, unsigned long long *columns, size_t cells, const double *frame_xyz, size_t n, const double pose_qt[7],
+                             const double sensor_xyz[3], const kicp_elev_carve_config *carve_config, unsigned long long out_stats[9]) {
+    if (int rc = FrameUpload::check(config && columns && carve_config && pose_qt && sensor_xyz && (frame_xyz || !n), n, "frame too large")) return rc;
+    ElevGeom geom;
+    unsigned long long layer_cells;
+    ElevCarveParams p;
+    if (int rc = check_elev_config(config, geom, layer_cells)) return rc;
+    if (int rc = check_carve_config(carve_config, p)) return rc;
+    if (cells != layer_cells) return fail(KICP_ERR_ARG, "cells must be the layer's " + std::to_string(layer_cells) + " cells");
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "a column is 64 bits");
+    unsigned long long stats[KICP_ELEV_UPDATE_STATS];
+    elev_host::update(geom, reinterpret_cast<uint64_t *>(columns), frame_xyz, n, pose_qt, sensor_xyz, p, stats);
+    if (out_stats)
+        for (int k = 0; k < KICP_ELEV_UPDATE_STATS; ++k) out_stats[k] = stats[k];
+    return KICP_OK;
 }
 int kicp_elev_columns(const kicp_elev *elev, unsigned long long *out, size_t cap_cells) {
     KICP_TRACE_CALL();

@@ -5,12 +5,18 @@
 //                    deduplicate the points themselves.  TEST BEFORE SET: the lane loads the column and issues the atomic OR only
 //                    when it finds the bit clear.  A robot re-observes what it has seen, so in steady state nearly every lane finds its
 //                    bit set, and a plain load is served by L2 while an atomic executes beyond it and drops the line from it
+//   k_elev_list      (an UPDATE only, before the mark) one lane per point: the points whose rays carve are appended to a list
+//   k_elev_carve     (an UPDATE only, before the mark) one wave per entry of that list, its lanes striding over the ray's steps as
+//                    k_grid_rays' do: each step clears a span of slabs in the column of the cell it visits - TEST BEFORE CLEAR, a 64-bit
+//                    atomic AND only where the loaded column has something to clear.  No frame-local plane: AND is idempotent too, so
+//                    rays that share a triple repeat loads, not atomics
 //   k_elev_classify  a tile of 16 x 16 cells per workgroup: each lane reduces its column to a ground byte, the tile's grounds and a
 //                    one-cell halo go through LDS, BODY comes from the lane's own column by shifts and STEP from the eight
 //                    neighbours in LDS; the classes, the optional ground bytes and per-wave sums of the four counts are written
 //   k_elev_to_grid   the same classification (elev_classify_cell, one device function for both) written as the two 16-bit counters
 //                    of a kicp_grid
-// The atomics besides the OR are the statistics: one add per wave per statistic that has something to add.  No kernel uses scratch.
+// The atomics besides the OR and the AND are the statistics and the list's length: one add per wave per word that has something to add.
+// No kernel uses scratch; the mark, list and carve kernels use no LDS.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -65,6 +71,89 @@ static __global__ __launch_bounds__(kElevBlock) void k_elev_mark(const double *_
     elev_wave_add(&shard[2], cls == kElevOutsideColumn);
     elev_wave_add(&shard[3], new_bit);
     elev_wave_add(&shard[4], new_cell);
+}
+
+// ---- carving (kicp_elev_update*): two launches in front of k_elev_mark ---------------------------------------------------------------
+// A record of the carve list: the endpoint cell relative to the sensor's, each offset by reach (13 bits each: reach <= 4095), and the
+// endpoint's slab offset by 32768 (16 bits).
+static __device__ __forceinline__ unsigned long long elev_ray_pack(int32_t dx, int32_t dy, int32_t es, int32_t reach) {
+    return static_cast<unsigned long long>(static_cast<uint32_t>(dx + reach) | static_cast<uint32_t>(dy + reach) << 13) |
+           static_cast<unsigned long long>(static_cast<uint32_t>(es + 32768)) << 26;
+}
+static __device__ __forceinline__ uint32_t elev_wave_sum(uint32_t v) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+constexpr uint32_t kElevListWord = 7;  // word of shard 0 that holds the carve list's length; words 5 and 6 of a shard: bits_cleared, cells_emptied
+
+// The eligible points append (dx, dy, es) to `rays` (room for n entries) by ballot compaction; stats[kElevListWord] becomes the list's
+// length, the frame's carve_points.  A lane takes kElevListPoints points, 64 apart, so that a wave has ONE add to the list's length for
+// 256 points: that word takes an add about every 11 ns, and with an add per 64 points a 131 072-point frame spent 23 of this
+// kernel's 26 us queueing for it.
+constexpr uint32_t kElevListPoints = 4;
+static __global__ __launch_bounds__(kElevBlock) void k_elev_list(const double *__restrict__ xyz, uint32_t n, ElevGeom g, ElevFrame f, unsigned long long *__restrict__ rays,
+                                                                 unsigned int *__restrict__ stats) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t first = (blockIdx.x * (kElevBlock / 64u) + threadIdx.x / 64u) * (64u * kElevListPoints) + lane;  // (n <= 0x7FFFFFF0 / 3: no overflow)
+    unsigned long long record[kElevListPoints], ballots[kElevListPoints];
+    uint32_t total = 0;
+#pragma unroll
+    for (uint32_t t = 0; t < kElevListPoints; ++t) {
+        const uint32_t i = first + 64u * t;
+        bool eligible = false;
+        int32_t dx = 0, dy = 0, es = 0;
+        if (i < n) eligible = elev_carve_point(g, f, xyz[3 * static_cast<size_t>(i)], xyz[3 * static_cast<size_t>(i) + 1], xyz[3 * static_cast<size_t>(i) + 2], dx, dy, es);
+        record[t] = elev_ray_pack(dx, dy, es, g.plane.reach);
+        ballots[t] = __ballot(eligible);
+        total += static_cast<uint32_t>(__popcll(ballots[t]));
+    }
+    uint32_t base = 0;
+    if (lane == 0u && total) base = atomicAdd(&stats[kElevListWord], total);
+    base = __shfl(base, 0, 64);
+#pragma unroll
+    for (uint32_t t = 0; t < kElevListPoints; ++t) {
+        if ((ballots[t] >> lane) & 1ull) rays[base + static_cast<uint32_t>(__popcll(ballots[t] & ((1ull << lane) - 1ull)))] = record[t];  // < n: one per eligible point
+        base += static_cast<uint32_t>(__popcll(ballots[t]));
+    }
+}
+
+// rays[0 .. *n_rays): one wave per entry, striding; the lanes take the steps k = lane, lane + 64, .. of that ray, each its cell and its
+// mask.  TEST BEFORE CLEAR: a lane loads the column and issues the atomic AND only when it finds something to clear.
+// A STALE VALUE IS SAFE HERE.  Within this launch bits only go from set to clear, and with keep_ground the lowest set bit of a column
+// never changes (no lane clears it, whichever value it computed it from), so a load that misses another lane's AND can only cost a
+// redundant atomic: never a lost clear, never another `keep`.  The statistics come from the atomics' returned values - exactly one
+// atomic sees each bit set, and exactly one takes a column to zero - summed per wave into words 5 and 6 of its shard.
+static __global__ __launch_bounds__(kElevBlock) void k_elev_carve(const unsigned long long *__restrict__ rays, const unsigned int *__restrict__ n_rays, ElevGeom g, ElevFrame f,
+                                                                  int32_t ss, ElevCarveParams p, unsigned long long *columns, unsigned int *__restrict__ stats) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const int32_t reach = g.plane.reach;
+    const uint32_t waves = gridDim.x * (kElevBlock / 64u), count = *n_rays;
+    uint32_t cleared = 0, emptied = 0;
+    for (uint32_t r = blockIdx.x * (kElevBlock / 64u) + threadIdx.x / 64u; r < count; r += waves) {
+        const unsigned long long rec = rays[r];
+        const int32_t dx = static_cast<int32_t>(static_cast<uint32_t>(rec) & 0x1FFFu) - reach, dy = static_cast<int32_t>(static_cast<uint32_t>(rec >> 13) & 0x1FFFu) - reach;
+        const int32_t es = static_cast<int32_t>(static_cast<uint32_t>(rec >> 26) & 0xFFFFu) - 32768;
+        const uint32_t m = grid_walk_length(dx, dy), steps = elev_carve_steps(m, p.margin_steps);  // steps <= m <= reach
+        for (uint32_t k = lane; k < steps; k += 64u) {
+            int32_t ox, oy;
+            grid_step(dx, dy, m, k, ox, oy);
+            size_t cell;
+            if (!grid_inside(g.plane, f.plane, static_cast<uint32_t>(ox + reach), static_cast<uint32_t>(oy + reach), cell)) continue;  // every access is behind this test
+            const unsigned long long mask = elev_step_mask(ss, es, m, k, p.widen_slabs);
+            const unsigned long long c = columns[cell];
+            const unsigned long long clear = elev_clear_mask(c, mask, p.keep_ground);
+            if (!(c & clear)) continue;
+            const unsigned long long old = atomicAnd(&columns[cell], ~clear);
+            cleared += static_cast<uint32_t>(__popcll(old & clear));
+            emptied += (old != 0ull && (old & ~clear) == 0ull) ? 1u : 0u;
+        }
+    }
+    cleared = elev_wave_sum(cleared), emptied = elev_wave_sum(emptied);
+    if (lane == 0u) {
+        unsigned int *shard = elev_shard(stats);
+        if (cleared) atomicAdd(&shard[5], cleared);
+        if (emptied) atomicAdd(&shard[6], emptied);
+    }
 }
 
 // The class of this lane's cell, (r.x0 + tile_x kElevTile + tx, r.y0 + tile_y kElevTile + ty) with tx = threadIdx.x % kElevTile: every

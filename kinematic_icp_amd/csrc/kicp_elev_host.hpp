@@ -1,7 +1,9 @@
 // kicp_elev_host.hpp -- the arithmetic of the height columns (kicp_elev_*, include/kicp.h): the class of one point, the ground of one
-// column, BODY and STEP of one cell.  ONE text for the kernels (kicp_elev.hpp), for the pure-host entry
-// (kicp_elev_traversability_from_columns) and for elev_host::integrate / elev_host::classify, the host restatements that a
-// stand-alone program runs under sanitizers (tests/cpp/elev_host_test.cpp).  Everything is exact and integer from the floor on.
+// column, BODY and STEP of one cell, and the carve along a frame's rays: which points carve, the slab of a ray at a step, a step's mask
+// and what it clears of a column.  ONE text for the kernels (kicp_elev.hpp), for the pure-host entries
+// (kicp_elev_traversability_from_columns, kicp_elev_update_columns) and for elev_host::integrate / carve / update / classify, the host
+// restatements that stand-alone programs run under sanitizers (tests/cpp/elev_host_test.cpp, tests/cpp/elev_carve_host_test.cpp).
+// Everything is exact and integer from the floor on.
 #pragma once
 #include "kicp_grid_host.hpp"
 
@@ -30,16 +32,22 @@ struct ElevRect {
 
 enum ElevClass : int { kElevSkipped = 0, kElevOutsideGrid = 1, kElevOutsideColumn = 2, kElevUsed = 3 };
 
-// The class of one point, tested in the header's order; for a used point the cell's index and the slab.  Every comparison is made on
-// doubles before any conversion, and a comparison with a NaN is false: a sensor cell that is not finite skips everything.
-KICP_HD ElevClass elev_point(const ElevGeom &g, const ElevFrame &f, double px, double py, double pz, size_t &cell_index, uint32_t &slab) {
-    if (!(fabs(px) <= DBL_MAX && fabs(py) <= DBL_MAX && fabs(pz) <= DBL_MAX)) return kElevSkipped;
+// What the class of a point and its ray share: is the point SKIPPED (-> false), and if not, its cell (integer valued doubles) and its
+// world height.  Every comparison is made on doubles before any conversion, and a comparison with a NaN is false: a sensor cell that
+// is not finite skips everything.
+KICP_HD bool elev_locate(const ElevGeom &g, const ElevFrame &f, double px, double py, double pz, double &cx, double &cy, double &wz) {
+    if (!(fabs(px) <= DBL_MAX && fabs(py) <= DBL_MAX && fabs(pz) <= DBL_MAX)) return false;
     const double wx = grid_world(f.plane.r, f.plane.t[0], px, py, pz), wy = grid_world(f.plane.r + 3, f.plane.t[1], px, py, pz);
-    const double wz = grid_world(f.r2, f.t2, px, py, pz);
-    if (!(fabs(wx) <= DBL_MAX && fabs(wy) <= DBL_MAX && fabs(wz) <= DBL_MAX)) return kElevSkipped;
-    const double cx = grid_cell(wx, g.plane.origin_x, g.plane.cell), cy = grid_cell(wy, g.plane.origin_y, g.plane.cell);
+    wz = grid_world(f.r2, f.t2, px, py, pz);
+    if (!(fabs(wx) <= DBL_MAX && fabs(wy) <= DBL_MAX && fabs(wz) <= DBL_MAX)) return false;
+    cx = grid_cell(wx, g.plane.origin_x, g.plane.cell), cy = grid_cell(wy, g.plane.origin_y, g.plane.cell);
     const double reach = static_cast<double>(g.plane.reach);
-    if (!(fabs(cx - f.plane.sx) <= reach && fabs(cy - f.plane.sy) <= reach)) return kElevSkipped;
+    return fabs(cx - f.plane.sx) <= reach && fabs(cy - f.plane.sy) <= reach;
+}
+// The class of one point, tested in the header's order; for a used point the cell's index and the slab.
+KICP_HD ElevClass elev_point(const ElevGeom &g, const ElevFrame &f, double px, double py, double pz, size_t &cell_index, uint32_t &slab) {
+    double cx, cy, wz;
+    if (!elev_locate(g, f, px, py, pz, cx, cy, wz)) return kElevSkipped;
     if (!(cx >= 0.0 && cx < static_cast<double>(g.plane.width) && cy >= 0.0 && cy < static_cast<double>(g.plane.height))) return kElevOutsideGrid;
     const double s = floor((wz - g.z_origin) / g.slab);
     if (!(s >= 0.0 && s <= 63.0)) return kElevOutsideColumn;
@@ -76,7 +84,88 @@ KICP_HD int8_t elev_value(bool known, bool body, bool step, uint32_t &which) {
     return !known ? static_cast<int8_t>(-1) : static_cast<int8_t>((body || step) ? 100 : 0);
 }
 
+// ---- carving along the frame's rays (kicp_elev_update*) --------------------------------------------------------------------------
+constexpr uint32_t kElevMaxWiden = 64;                      // widen_slabs
+constexpr double kElevSlabMin = -32768.0, kElevSlabMax = 32767.0;  // the slabs a ray may start or end in
+
+struct ElevCarveParams {
+    uint32_t margin_steps, widen_slabs, keep_ground;  // G, W (0 .. 64), 0 or 1
+};
+// The carve's constants of a frame: the sensor's slab, and whether it lies in range - out of range (a NaN too) carves nothing.
+struct ElevCarveFrame {
+    int32_t ss;
+    bool carves;
+};
+inline ElevCarveFrame elev_carve_frame(const ElevGeom &g, const ElevFrame &f, const double sensor_xyz[3]) {
+    const double s = floor((grid_world(f.r2, f.t2, sensor_xyz[0], sensor_xyz[1], sensor_xyz[2]) - g.z_origin) / g.slab);
+    const bool ok = s >= kElevSlabMin && s <= kElevSlabMax;
+    return ElevCarveFrame{ok ? static_cast<int32_t>(s) : 0, ok};
+}
+// Is the point ELIGIBLE - its class not SKIPPED and -32768 <= s <= 32767, on doubles - and if so where does its ray end: the endpoint
+// cell relative to the sensor's (|dx|, |dy| <= reach) and the endpoint's slab.
+KICP_HD bool elev_carve_point(const ElevGeom &g, const ElevFrame &f, double px, double py, double pz, int32_t &dx, int32_t &dy, int32_t &es) {
+    double cx, cy, wz;
+    if (!elev_locate(g, f, px, py, pz, cx, cy, wz)) return false;
+    const double s = floor((wz - g.z_origin) / g.slab);
+    if (!(s >= kElevSlabMin && s <= kElevSlabMax)) return false;
+    dx = static_cast<int32_t>(cx - f.plane.sx), dy = static_cast<int32_t>(cy - f.plane.sy), es = static_cast<int32_t>(s);
+    return true;
+}
+// the steps a ray of length m takes: k = 0 .. m - 1 - G
+KICP_HD uint32_t elev_carve_steps(uint32_t m, uint32_t margin_steps) { return m > margin_steps ? m - margin_steps : 0u; }
+// The slab of the ray at parameter j / (2 m), 0 <= j <= 2 m, m >= 1: u(0) = ss, u(2 m) = es.  An integer division of non-negative
+// numbers; j |d| + m < 2^29 for j <= 8191 and |d| <= 65535.
+KICP_HD int32_t elev_ray_slab(int32_t ss, int32_t es, uint32_t m, uint32_t j) {
+    const int32_t d = es - ss;
+    const uint32_t a = static_cast<uint32_t>(d < 0 ? -d : d);
+    const int32_t q = static_cast<int32_t>((j * a + m) / (2u * m));
+    return d < 0 ? ss - q : ss + q;
+}
+// bits max(lo, 0) .. min(hi, 63) of a column, lo <= hi; empty when the span lies wholly outside it.  No shift reaches 64.
+KICP_HD uint64_t elev_span_mask(int32_t lo, int32_t hi) {
+    if (hi < 0 || lo > 63) return 0ull;
+    const uint32_t first = lo < 0 ? 0u : static_cast<uint32_t>(lo), past = hi >= 63 ? kElevSlabs : static_cast<uint32_t>(hi) + 1u;
+    return elev_bits_from(first) & ~elev_bits_from(past);
+}
+// the mask of step k of that ray: the slabs between parameters (2 k - 1) / (2 m) and (2 k + 1) / (2 m), widened by W on both sides
+KICP_HD uint64_t elev_step_mask(int32_t ss, int32_t es, uint32_t m, uint32_t k, uint32_t widen_slabs) {
+    const int32_t a = elev_ray_slab(ss, es, m, k ? 2u * k - 1u : 0u), b = elev_ray_slab(ss, es, m, 2u * k + 1u);
+    const int32_t w = static_cast<int32_t>(widen_slabs);
+    return elev_span_mask((a < b ? a : b) - w, (a < b ? b : a) + w);
+}
+// what a mask clears of a column: with keep_ground everything but the column's lowest set bit
+KICP_HD uint64_t elev_clear_mask(uint64_t column, uint64_t mask, uint32_t keep_ground) {
+    return keep_ground ? mask & ~(column & (~column + 1ull)) : mask;
+}
+
 namespace elev_host {
+// The carve of one frame on the host, as k_elev_list and k_elev_carve do it.  Masks are applied one by one: with keep_ground the lowest
+// set bit of a column never changes, so that equals clearing the OR of all masks at once.  stats[0 .. 3): carve_points, bits_cleared,
+// cells_emptied.
+inline void carve(const ElevGeom &g, uint64_t *columns, const double *xyz, size_t n, const double pose_qt[7], const double sensor_xyz[3],
+                  const ElevCarveParams &p, unsigned long long stats[3]) {
+    const ElevFrame f = elev_frame(g, pose_qt, sensor_xyz);
+    const ElevCarveFrame cf = elev_carve_frame(g, f, sensor_xyz);
+    stats[0] = stats[1] = stats[2] = 0;
+    if (!cf.carves) return;
+    for (size_t i = 0; i < n; ++i) {
+        int32_t dx, dy, es;
+        if (!elev_carve_point(g, f, xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2], dx, dy, es)) continue;
+        ++stats[0];
+        const uint32_t m = grid_walk_length(dx, dy), steps = elev_carve_steps(m, p.margin_steps);
+        for (uint32_t k = 0; k < steps; ++k) {
+            int32_t ox, oy;
+            grid_step(dx, dy, m, k, ox, oy);
+            size_t c;
+            if (!grid_inside(g.plane, f.plane, static_cast<uint32_t>(ox + g.plane.reach), static_cast<uint32_t>(oy + g.plane.reach), c)) continue;
+            const uint64_t clear = columns[c] & elev_clear_mask(columns[c], elev_step_mask(cf.ss, es, m, k, p.widen_slabs), p.keep_ground);
+            if (!clear) continue;
+            stats[1] += static_cast<unsigned long long>(__builtin_popcountll(clear));
+            columns[c] &= ~clear;
+            if (!columns[c]) ++stats[2];
+        }
+    }
+}
 // One frame on the host, as k_elev_mark does it.  columns: one 64-bit word per cell.  stats: used, skipped, outside_grid,
 // outside_column, new_bits, new_cells.
 inline void integrate(const ElevGeom &g, uint64_t *columns, const double *xyz, size_t n, const double pose_qt[7], const double sensor_xyz[3],
@@ -99,6 +188,13 @@ inline void integrate(const ElevGeom &g, uint64_t *columns, const double *xyz, s
             }
         }
     }
+}
+// An UPDATE: the carve, then the mark - a frame's own returns survive it.  stats: integrate's six, counted relative to the carved
+// columns, then carve's three.
+inline void update(const ElevGeom &g, uint64_t *columns, const double *xyz, size_t n, const double pose_qt[7], const double sensor_xyz[3],
+                   const ElevCarveParams &p, unsigned long long stats[9]) {
+    carve(g, columns, xyz, n, pose_qt, sensor_xyz, p, stats + 6);
+    integrate(g, columns, xyz, n, pose_qt, sensor_xyz, stats);
 }
 // The classes of a rectangle (inside the grid; checked by the caller), as k_elev_classify computes them: out and ground (nullable) are
 // h * w values, row-major from (x0, y0); counts (nullable): unknown, traversable, BODY, STEP only.

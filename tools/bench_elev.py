@@ -15,9 +15,16 @@ have completed.  Warm; everything that is compared alternates in the same proces
     times; with --contender NAME=EXECUTABLE:LIBDIR (repeatable) also a process of another build's `<facade test> timed .. off` - the
     parent commit's, to show that a disabled layer costs nothing: the median of the drive's second half per process, then median and
     min .. max over the processes.
+  - with --carve INSTEAD of the above: kicp_elev_update_device (margin_steps 2, widen_slabs 1, keep_ground set) of the frame onto an
+    EMPTY layer (nothing to clear: the rays are walked, every lane loads and no atomic AND is issued) and of the SAME frame again
+    (steady state), beside kicp_elev_integrate_device of the same frame again and kicp_grid_integrate_device - the yardsticks, the
+    grid walks the same rays once per HIT cell - from the same process, alternating; --ab compares another build's update; with
+    --pipeline the drive through tests/cpp/elev_carve_facade_test, mode `timed`: a process without a layer, one with a layer and one
+    with a layer that carves, and per --contender a process of another build's tests/cpp/elev_facade_test `timed .. on` - the parent
+    commit's pipeline with its layer, which is what this build's frame must cost while carving is off.
 Prints one JSON line.
 
-    python tools/bench_elev.py [--rounds 30] [--ab NAME=LIB] [--pipeline] [--pipeline-rounds 3] [--pipeline-frames 16] [--contender NAME=EXE:LIBDIR]
+    python tools/bench_elev.py [--rounds 30] [--carve] [--ab NAME=LIB] [--pipeline] [--pipeline-rounds 3] [--pipeline-frames 16] [--contender NAME=EXE:LIBDIR]
 """
 import argparse
 import ctypes as C
@@ -42,6 +49,7 @@ from bench_grid import CELLS, GEOMETRY, grid_config, make_grid, scene_and_beams 
 
 Z_ORIGIN, SLAB = -1.0, 0.125
 STEP_SLABS, ROBOT_SLABS = 2, 12
+CARVE = (2, 1, 1)  # margin_steps, widen_slabs, keep_ground
 
 
 class RawLayer:
@@ -60,6 +68,12 @@ class RawLayer:
         rc = self.lib.kicp_elev_integrate_device(self._h, dev.ptr, dev.n, pose.ctypes.data_as(K._dp), sensor.ctypes.data_as(K._dp), self._last.ctypes.data_as(C.POINTER(C.c_ulonglong)))
         assert rc == 0
         return tuple(int(v) for v in self._last)
+
+    def update_device(self, dev, pose, sensor, margin_steps, widen_slabs, keep_ground):
+        carve, out = K.ElevationCarveConfig(margin_steps, widen_slabs, keep_ground), np.zeros(9, dtype=np.uint64)
+        rc = self.lib.kicp_elev_update_device(self._h, dev.ptr, dev.n, pose.ctypes.data_as(K._dp), sensor.ctypes.data_as(K._dp), C.byref(carve), out.ctypes.data_as(C.POINTER(C.c_ulonglong)))
+        assert rc == 0
+        return tuple(int(v) for v in out)
 
     def __del__(self):
         self.lib.kicp_elev_destroy(self._h)
@@ -122,6 +136,48 @@ def integrate_rows(rounds, contenders):
     return rows
 
 
+def carve_rows(rounds, contenders):
+    """the update beside the two yardsticks, on integrate_rows' frames and cells"""
+    cases = []
+    for name in GEOMETRY:
+        cfg, scene, dirs, rng = scene_and_beams(name)
+        pose = syn.planar_pose(1.2, -0.7, 0.9)
+        frame = np.ascontiguousarray(syn.make_scan(scene, pose, dirs, cfg.sensor_height, rng))
+        sensor = np.array([0.0, 0.0, cfg.sensor_height])
+        for cell in CELLS:
+            gcfg = grid_config(name, cell)
+            layers = {"this": make_layer(gcfg)}
+            layers.update({who: RawLayer(lib, gcfg) for who, lib in contenders.items()})
+            cases.append(dict(name=name, cell=cell, cfg=gcfg, layers=layers, grid=make_grid(gcfg), frame=frame, dev=K.DeviceFrame(frame), pose=pose, sensor=sensor,
+                              t_grid=[], t_integrate=[], t_first={w: [] for w in layers}, t_again={w: [] for w in layers}, stats={}))
+    for r in range(rounds + 3):  # (the first three rounds warm)
+        for c in cases:
+            t_grid, _ = timed(lambda: c["grid"].integrate_device(c["dev"], c["pose"], c["sensor"]))
+            for who, layer in c["layers"].items():
+                layer.clear()
+                t_first, first = timed(lambda: layer.update_device(c["dev"], c["pose"], c["sensor"], *CARVE))
+                t_again, again = timed(lambda: layer.update_device(c["dev"], c["pose"], c["sensor"], *CARVE))
+                assert first[7:] == (0, 0) and again[:4] == first[:4] and again[6] == first[6]
+                assert c["stats"].setdefault("first", first) == first and c["stats"].setdefault("again", again) == again  # every build computes the same
+                if r >= 3:
+                    c["t_first"][who].append(t_first), c["t_again"][who].append(t_again)
+            t_integrate, _ = timed(lambda: c["layers"]["this"].integrate_device(c["dev"], c["pose"], c["sensor"]))
+            if r >= 3:
+                c["t_grid"].append(t_grid), c["t_integrate"].append(t_integrate)
+    rows = []
+    for c in cases:
+        first, again = c["stats"]["first"], c["stats"]["again"]
+        row = {"scene": c["name"], "points": len(c["frame"]), "cell_m": c["cell"], "layer_cells": [c["cfg"]["width"], c["cfg"]["height"]], "reach_cells": c["cfg"]["reach"],
+               "margin_steps": CARVE[0], "widen_slabs": CARVE[1], "keep_ground": CARVE[2], "used": first[0], "carve_points": first[6],
+               "bits_cleared_same_frame_again": again[7], "new_bits_same_frame_again": again[4],
+               "grid_integrate_device_ms": spread(c["t_grid"]), "elev_integrate_device_same_frame_again_ms": spread(c["t_integrate"])}
+        for who in c["layers"]:
+            row["elev_update_first_frame_ms_" + who] = spread(c["t_first"][who])
+            row["elev_update_same_frame_again_ms_" + who] = spread(c["t_again"][who])
+        rows.append(row)
+    return rows
+
+
 def traversability_rows(rounds):
     name = "cfg1"
     cfg, scene, dirs, rng = scene_and_beams(name)
@@ -150,9 +206,10 @@ def traversability_rows(rounds):
              "traversability_window_ms": spread(t["window"]), "grid_occupancy_full_ms": spread(t["occupancy"]), "to_grid_ms": spread(t["to_grid"])}]
 
 
-def pipeline_rows(rounds, n_frames, contenders):
+def pipeline_rows(rounds, n_frames, contenders, carve=False):
     import test_elev_facade
-    exe = test_elev_facade.build_binary()
+    import test_elev_carve_facade
+    exe = test_elev_carve_facade.build_binary() if carve else test_elev_facade.build_binary()
     bind, _ = placement()
     rows = []
     with tempfile.TemporaryDirectory() as td:
@@ -175,22 +232,28 @@ def pipeline_rows(rounds, n_frames, contenders):
             for cell in CELLS:
                 gcfg = grid_config(name, cell)
                 lfile = os.path.join(td, "layer.bin")
-                np.array([gcfg[k] for k in ("cell", "origin_x", "origin_y", "width", "height")] + [Z_ORIGIN, SLAB, gcfg["max_ray"], STEP_SLABS, ROBOT_SLABS],
-                         dtype=np.float64).tofile(lfile)
-                runs = {"off": ([exe, "timed", drive, lfile, "off"], None, 0), "on": ([exe, "timed", drive, lfile, "on"], None, n_frames)}
+                # (the carve's program reads G, W, keep_ground behind the eight doubles and one more; the layer's S, H and ignores them when timed)
+                np.array([gcfg[k] for k in ("cell", "origin_x", "origin_y", "width", "height")] + [Z_ORIGIN, SLAB, gcfg["max_ray"]] +
+                         (list(CARVE) if carve else [STEP_SLABS, ROBOT_SLABS]), dtype=np.float64).tofile(lfile)
+                if carve:
+                    runs = {"none": ([exe, "timed", drive, lfile, "none"], None, None), "carving_off": ([exe, "timed", drive, lfile, "off"], None, None),
+                            "carving_on": ([exe, "timed", drive, lfile, "on"], None, None)}
+                else:
+                    runs = {"off": ([exe, "timed", drive, lfile, "off"], None, 0), "on": ([exe, "timed", drive, lfile, "on"], None, n_frames)}
                 for who, (other_exe, libdir) in contenders.items():
-                    runs[who] = ([other_exe, "timed", drive, lfile, "off"], dict(os.environ, LD_LIBRARY_PATH=libdir + ":" + os.environ.get("LD_LIBRARY_PATH", "")), 0)
+                    runs[who] = ([other_exe, "timed", drive, lfile, "on" if carve else "off"], dict(os.environ, LD_LIBRARY_PATH=libdir + ":" + os.environ.get("LD_LIBRARY_PATH", "")),
+                                 n_frames if carve else 0)
                 per = {which: [] for which in runs}
                 for r in range(rounds + 1):  # (the first round warms the file cache and the driver)
                     for which, (cmd, env, integrated) in runs.items():
                         out = subprocess.check_output(cmd, text=True, preexec_fn=bind, env=env).splitlines()
                         ms = np.array([float(ln.split()[3]) for ln in out if ln.startswith("frame ")])
-                        assert ("frames_integrated %d" % integrated) in out
+                        assert integrated is None or ("frames_integrated %d" % integrated) in out
                         if r:
                             per[which].append(float(np.median(ms[len(ms) // 2:])))
                 row = {"scene": name, "points": len(dirs), "cell_m": cell, "frames": n_frames,
                        "what": "median RegisterFrame wall time of the drive's second half per process; spread over %d alternating processes each" % rounds}
-                row.update({"register_frame_ms_" + ("layer_" + which if which in ("on", "off") else which): spread(v) for which, v in per.items()})
+                row.update({"register_frame_ms_" + ("layer_" + which if which in ("on", "off", "none", "carving_on", "carving_off") else which): spread(v) for which, v in per.items()})
                 rows.append(row)
     return rows
 
@@ -198,6 +261,7 @@ def pipeline_rows(rounds, n_frames, contenders):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=30)
+    ap.add_argument("--carve", action="store_true")
     ap.add_argument("--ab", action="append", default=[], metavar="NAME=LIB")
     ap.add_argument("--pipeline", action="store_true")
     ap.add_argument("--pipeline-rounds", type=int, default=3)
@@ -208,10 +272,13 @@ def main():
     if bind:
         bind()
     libs = {spec.split("=", 1)[0]: load_contender(spec.split("=", 1)[1]) for spec in a.ab}
-    res = {"caller_process": where, "rounds": a.rounds, "integrate": integrate_rows(a.rounds, libs), "traversability": traversability_rows(a.rounds)}
+    if a.carve:
+        res = {"caller_process": where, "rounds": a.rounds, "carve": carve_rows(a.rounds, libs)}
+    else:
+        res = {"caller_process": where, "rounds": a.rounds, "integrate": integrate_rows(a.rounds, libs), "traversability": traversability_rows(a.rounds)}
     if a.pipeline:
         others = {spec.split("=", 1)[0]: tuple(os.path.abspath(p) for p in spec.split("=", 1)[1].split(":", 1)) for spec in a.contender}
-        res["pipeline"] = pipeline_rows(a.pipeline_rounds, a.pipeline_frames, others)
+        res["pipeline"] = pipeline_rows(a.pipeline_rounds, a.pipeline_frames, others, carve=a.carve)
     print(json.dumps(res))
 
 
