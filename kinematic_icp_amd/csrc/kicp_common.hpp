@@ -52,15 +52,21 @@ KICP_HD uint32_t voxel_hash(int32_t x, int32_t y, int32_t z) {
 
 // One point of the compact mirror the pre-selection pass reads: the offset from the voxel corner, per axis, in units of
 // voxel_size / 65536 (so the quantisation error is <= 1 unit = 1.5e-5 voxel sizes wherever the map is), 8 bytes:
-//   x = qx | qy << 16,  y = qz | aux << 16;  aux = 0 for a point, 0xFFFF for an empty slot of the bucket.
-// The pass kernel converts the whole second word to float: a point yields its z offset exactly, an empty slot 4.3e9 units -
-// farther than anything real, so empty slots lose every comparison without being tested for.  A bucket's mirror is reset to
-// empty slots (mirror_empty) when the bucket receives its first point.
+//   x = qx | qy << 16   (two 16-bit integers),
+//   y = the bit pattern of the FLOAT qz (0 .. 65 535, exact in fp32) for a point, of kMirrorEmptyZ for an empty slot of the bucket.
+// The name stays "16-bit mirror" - every coordinate is a 16-bit quantity - but z travels as the float the pass kernel subtracts
+// the query from: the kernel reinterprets the word and spends no conversion on it.  An empty slot reads 4 294 901 760 units
+// (what the integer word 0xFFFF0000 of the earlier format converted to) - farther than anything real, so empty slots lose every
+// comparison without being tested for.  A point's word is at most the bits of 65 535.0f, so "this slot holds a point" is one
+// unsigned compare of the word against the empty pattern.  A bucket's mirror is reset to empty slots (mirror_empty) when the
+// bucket receives its first point.
 // It only PRE-SELECTS: the winner, and anything within the error margin of it, is re-evaluated from the fp64 pool.
 using MirrorPoint = uint2;
+constexpr float kMirrorEmptyZ = 4294901760.0f;       // 2^32 - 2^16, exact in fp32
+constexpr uint32_t kMirrorEmptyWord = 0x4F7FFF00u;   // its bit pattern
 KICP_HD MirrorPoint mirror_empty() {
     MirrorPoint m;
-    m.x = 0u, m.y = 0xFFFF0000u;
+    m.x = 0u, m.y = kMirrorEmptyWord;
     return m;
 }
 KICP_HD uint32_t mirror_quant(double offset, double units_per_metre) {  // round to nearest unit, clamped into 16 bits
@@ -70,9 +76,15 @@ KICP_HD uint32_t mirror_quant(double offset, double units_per_metre) {  // round
 KICP_HD MirrorPoint mirror_point(double ox, double oy, double oz, double units_per_metre) {
     MirrorPoint m;
     m.x = mirror_quant(ox, units_per_metre) | (mirror_quant(oy, units_per_metre) << 16);
-    m.y = mirror_quant(oz, units_per_metre);
+    m.y = __builtin_bit_cast(uint32_t, static_cast<float>(mirror_quant(oz, units_per_metre)));
     return m;
 }
+// the second word of a slot, as the readers see it
+KICP_HD float mirror_word_z(uint32_t word) { return __builtin_bit_cast(float, word); }  // z in units, kMirrorEmptyZ for an empty slot
+KICP_HD bool mirror_word_is_point(uint32_t word) { return word < kMirrorEmptyWord; }
+KICP_HD float mirror_z(MirrorPoint m) { return mirror_word_z(m.y); }
+KICP_HD uint32_t mirror_qz(MirrorPoint m) { return static_cast<uint32_t>(mirror_word_z(m.y)); }  // the quantised integer (of a point)
+KICP_HD bool mirror_is_point(MirrorPoint m) { return mirror_word_is_point(m.y); }
 KICP_HD double mirror_units_per_metre(double voxel_size) { return 65536.0 / voxel_size; }
 
 // Device view of a voxel map mirror (all pointers in HBM).

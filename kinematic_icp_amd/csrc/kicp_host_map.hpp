@@ -239,8 +239,10 @@ public:
                 ++occupied, points += count;
                 const uint32_t b = val_bucket(e.val, cb_);
                 if (b >= n_buckets_hi_ || count > cap_) ++bad;
-                for (uint32_t k = count; k < cap16_; ++k)  // empty slots are marked (what lets the kernel skip testing for them)
-                    if ((pool16_[static_cast<size_t>(b) * cap16_ + k].y >> 16) != 0xFFFFu) ++bad;
+                for (uint32_t k = count; k < cap16_; ++k) {  // empty slots are marked (what lets the kernel skip testing for them):
+                    const MirrorPoint f = pool16_[static_cast<size_t>(b) * cap16_ + k];  // exactly the empty pattern, 4 294 901 760.0f
+                    if (f.y != mirror_empty().y || mirror_is_point(f) || mirror_z(f) != kMirrorEmptyZ) ++bad;
+                }
                 const double upm = mirror_units_per_metre(voxel_size_);
                 for (uint32_t k = 0; k < count; ++k) {
                     const double *p = &pool_[(static_cast<size_t>(b) * cap_ + k) * 3];
@@ -248,9 +250,12 @@ public:
                     if (to_voxel(p[0]) != e.x || to_voxel(p[1]) != e.y || to_voxel(p[2]) != e.z) ++bad;
                     const MirrorPoint want = mirror_point(p[0] - e.x * voxel_size_, p[1] - e.y * voxel_size_, p[2] - e.z * voxel_size_, upm);
                     if (f.x != want.x || f.y != want.y) ++bad;
+                    // the z word holds the float bits of the quantised z (what the kernel reads without converting), and says "a point"
+                    const uint32_t qz = mirror_quant(p[2] - e.z * voxel_size_, upm);
+                    if (!mirror_is_point(f) || mirror_z(f) != static_cast<float>(qz) || mirror_qz(f) != qz) ++bad;
                     // the decoded offset is within one unit of the true one on every axis (what the kernel's margin assumes)
                     const double o[3] = {p[0] - e.x * voxel_size_, p[1] - e.y * voxel_size_, p[2] - e.z * voxel_size_};
-                    const uint32_t q[3] = {f.x & 0xffffu, f.x >> 16, f.y & 0xffffu};
+                    const uint32_t q[3] = {f.x & 0xffffu, f.x >> 16, mirror_qz(f)};
                     for (int a = 0; a < 3; ++a)
                         if (std::fabs(q[a] / upm - o[a]) > 1.0 / upm) ++bad;
                 }

@@ -1199,13 +1199,15 @@ __device__ __forceinline__ bool process_trip(const uint4 (&c)[N / 2], uint32_t p
     // float orders like its bit pattern, so (bits & ~31) | position is one v_min3_u32 per three candidates
     // and yields value and position at once (unique keys: the lower position wins a tie, like the
     // reference's first minimum).  The 5 dropped mantissa bits are part of the margin's error model.
-    // Empty slots need no test: their second word converts to 4.3e9 units (kicp_common.hpp).
+    // Empty slots need no test: their second word reads 4.3e9 units (kicp_common.hpp).  x and y are converted from their 16-bit
+    // halves; z is stored as the float itself: no conversion, only a register copy per pair of points to bring the two z words of a
+    // load into one register pair (profiles/mirror_z_ab.txt).
     uint32_t key[N];
 #pragma unroll
     for (int u = 0; u < N / 2; ++u) {
         const v2f px = {static_cast<float>(c[u].x & 0xffffu), static_cast<float>(c[u].z & 0xffffu)};
         const v2f py = {static_cast<float>(c[u].x >> 16), static_cast<float>(c[u].z >> 16)};
-        const v2f pz = {static_cast<float>(c[u].y), static_cast<float>(c[u].w)};  // (the whole word: z, or far away for an empty slot)
+        const v2f pz = {mirror_word_z(c[u].y), mirror_word_z(c[u].w)};  // (the word IS the float: z, or far away for an empty slot)
         const v2f ddx = px - qx, ddy = py - qy, ddz = pz - qz;
         const v2f d = __builtin_elementwise_fma(ddz, ddz, __builtin_elementwise_fma(ddy, ddy, ddx * ddx));
         key[2 * u] = (__float_as_uint(d.x) & ~31u) | static_cast<uint32_t>(2 * u);
@@ -1215,7 +1217,7 @@ __device__ __forceinline__ bool process_trip(const uint4 (&c)[N / 2], uint32_t p
     // holds that slot - quad_perm [1, 1, 3, 3])
     uint32_t last_word = c[N / 2 - 1].w;
     if (PARTS == 2) last_word = static_cast<uint32_t>(__builtin_amdgcn_update_dpp(0, static_cast<int>(last_word), 0xF5, 0xf, 0xf, false));
-    const bool more = (last_word >> 16) == 0u;
+    const bool more = mirror_word_is_point(last_word);
     // winner and runner-up in one tournament (the keys are unique, so the runner-up is a different candidate)
     uint32_t key1, key2;
     tree_min2_u32<N>(key, key1, key2);

@@ -231,9 +231,14 @@ int kicp_pre_create(int device, kicp_pre **out) {
     if (e == hipSuccess && !rc) rc = p->d_push_tickets.reserve(kPushPieces);
     if (e == hipSuccess && !rc) {
         std::memset(p->h_rec.get(), 0, 32 * sizeof(unsigned long long));
-        e = hipMemset(p->d_misc.get(), 0, 64);
-        if (e == hipSuccess) e = hipMemset(p->d_ticket.get(), 0, 16);
-        if (e == hipSuccess) e = hipMemset(p->d_push_tickets.get(), 0, kPushPieces * 8);
+        // The counters must read zero before the first kernel draws a ticket.  hipMemset of device memory may return before it has run,
+        // and the handle's streams are non-blocking - nothing orders them behind the null stream: a first ingest that draws its ticket
+        // ahead of the memset passes, the memset then wipes the count, and every later call of the handle waits for a last workgroup
+        // that never comes ("finished without handing their result over").  So: on the handle's stream, and waited for here.
+        e = hipMemsetAsync(p->d_misc.get(), 0, 64, p->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(p->d_ticket.get(), 0, 16, p->stream);
+        if (e == hipSuccess) e = hipMemsetAsync(p->d_push_tickets.get(), 0, kPushPieces * 8, p->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
         if (e == hipSuccess) e = hipEventCreateWithFlags(&p->chain_ready, hipEventDisableTiming);
     }
     if (e != hipSuccess || rc) {

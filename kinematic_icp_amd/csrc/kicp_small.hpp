@@ -540,7 +540,7 @@ __global__ __launch_bounds__(BLOCK) void k_pass_wave(const SmallParams /* read t
                     double cx = 0.0, cy = 0.0, cz = 0.0;
 #pragma unroll
                     for (int u = 0; u < 2; ++u) {
-                        const bool have = active[u] && k < m.cap && (mp[u].y >> 16) == 0u;
+                        const bool have = active[u] && k < m.cap && mirror_is_point(mp[u]);
                         const double dx = px[u] - q.x, dy = py[u] - q.y, dz = pz[u] - q.z;
                         const double e = dx * dx + dy * dy + dz * dz;
                         const uint32_t o = static_cast<uint32_t>(svl[u]) * kOrdStride + k;
@@ -565,7 +565,7 @@ __global__ __launch_bounds__(BLOCK) void k_pass_wave(const SmallParams /* read t
                         cur_u = fminf(cur_u, static_cast<float>(best.d2 * sq.upm * sq.upm) * 1.00001f + 1.0f);
                     }
                     // a bucket goes on where the last slot of this trip holds a point (any of the round's buckets)
-                    more = __ballot((active[0] && kk == kTripPoints - 1 && (mp[0].y >> 16) == 0u) || (active[1] && kk == kTripPoints - 1 && (mp[1].y >> 16) == 0u)) != 0ull;
+                    more = __ballot((active[0] && kk == kTripPoints - 1 && mirror_is_point(mp[0])) || (active[1] && kk == kTripPoints - 1 && mirror_is_point(mp[1]))) != 0ull;
                 }
             }
             const bool take = best.idx != kNoIndex32 && sqrt(best.d2) < p.tau;  // `distance < max_correspondance_distance`, Registration.cpp:75
