@@ -910,6 +910,35 @@ int kicp_grid_gain(const kicp_grid *grid, const kicp_gain_config *config, const 
  * kicp_grid_potential, kicp_grid_score_arcs, kicp_grid_frontiers, kicp_grid_gain - then runs on traversability, without a byte
  * crossing PCIe.
  *
+ * THE SLOPE LIMIT.  BODY looks at one column and STEP at neighbours one cell away, so neither sees a gradient: at 0.1 m cells, 0.0625 m
+ * slabs and S = 2, STEP fires only above 2 slabs per cell, 51 degrees.  Grounds are quantised to a slab and most ground cells between a
+ * lidar's rings are unknown, so a slope comes from a least-squares plane through the known grounds of a window, in exact integers.
+ * With the slope configuration L = radius_cells (1 .. 8), K = gate_slabs (0 .. 63), min_cells (3 .. 289), rise_slabs (0 .. 65535) and
+ * run_cells (1 .. 65535) (KICP_ERR_ARG otherwise; the traversability configuration is checked as above), the FIT SET of a known cell
+ * (x, y) with ground g is the cells (x + dx, y + dy) with |dx|, |dy| <= L that lie inside the grid, whose column is not zero and whose
+ * ground g_n satisfies |g_n - g| <= K; the cell itself always belongs.  With z = g_n - g, nine integer sums are taken over the set:
+ * n, Sx = sum dx, Sy, Sxx, Sxy, Syy, Sz, Sxz, Syz.  The normal equations of z ~ a dx + b dy + c give by Cramer's rule
+ *   D  = Sxx (Syy n - Sy Sy) - Sxy (Sxy n - Sy Sx) + Sx (Sxy Sy - Syy Sx)
+ *   Da = Sxz (Syy n - Sy Sy) - Sxy (Syz n - Sy Sz) + Sx (Syz Sy - Syy Sz)
+ *   Db = Sxx (Syz n - Sz Sy) - Sxz (Sxy n - Sy Sx) + Sx (Sxy Sz - Syz Sx)
+ * The cell HAS A FIT when n >= min_cells and D > 0 (D is a Gram determinant: 0 when the set lies on one line); the gradient is then
+ * (Da / D, Db / D) slabs per cell, and the cell is
+ *   SLOPE when it has a fit and (Da^2 + Db^2) run_cells^2 > rise_slabs^2 D^2 - strictly, on exact integers, without a division.
+ * A cell without a fit is not SLOPE: like an unknown neighbour, it says nothing.  The value of a cell is -1 when it is unknown, 100 when
+ * BODY, STEP or SLOPE, else 0; BODY and STEP are exactly as above, so wherever a cell is not "SLOPE only" its value equals
+ * kicp_elev_traversability's.  out_counts (nullable) is five words (KICP_ELEV_SLOPE_COUNTS): unknown, traversable, BODY, STEP only,
+ * SLOPE only - SLOPE without BODY or STEP.  out_fit (nullable): w * h triples D, Da, Db, row-major as `out`; 0, 0, 0 where the cell has
+ * no fit.  The widths: at L = 8, n <= 289, Sxx <= 6 936, |Sxy| <= 5 184, |Sz| <= 18 207 and |Sxz| <= 77 112, so the sums fit 32-bit
+ * integers; D < 2^34 and |Da|, |Db| < 2^41, so the determinants fit 64-bit ones; the two sides of the comparison stay below 2^115 and
+ * 2^100 and are formed as 128-bit products - never in fp64.  The rectangle rules are the ones above: a rectangle's result EQUALS the
+ * full layer's restricted to it - window cells outside the rectangle but inside the grid count, cells outside the grid do not - and
+ * a frame changes the result only inside kicp_elev_last_window grown by max(1, L) cells.  ADVICE: choose K >= (S + 1) L; whatever STEP
+ * does not catch then stays in the fit set.  kicp_elev_traversability_slope_from_columns is the same arithmetic as pure host code
+ * and needs no GPU; kicp_elev_to_grid_slope follows kicp_elev_to_grid's rules - the same checks, the same counters written.
+ * kicp_elev_slope_limit turns a tangent into a limit for a layer's cell and slab: run_cells = 1024 and rise_slabs =
+ * floor(((max_tangent cell) / slab) 1024), each operation rounded on its own; KICP_ERR_ARG when that is not finite, is negative or
+ * exceeds 65 535 (of the configuration only cell and slab are read: positive and finite).
+ *
  * CARVING ALONG THE FRAME'S RAYS.  kicp_elev_integrate only ever sets bits.  An UPDATE of a frame (kicp_elev_update*) is a CARVE - bits
  * that the frame's rays pass through are cleared - and then the mark that kicp_elev_integrate does, so a frame's own returns always
  * survive it.  With the carve configuration G = margin_steps, W = widen_slabs (0 .. 64) and keep_ground (0 or 1; KICP_ERR_ARG
@@ -943,7 +972,8 @@ int kicp_grid_gain(const kicp_grid *grid, const kicp_gain_config *config, const 
  * carve.  With keep_ground, a cell whose floor was never seen keeps a passer-by's lowest bit until a floor return arrives; without it
  * grazing rays erode the floor.  One spurious low return lowers a cell's ground for good: keep_ground keeps exactly that bit.  A cell that has only
  * ever returned an overhang, its ground unseen, reads as a high ground and is marked STEP until a ground return arrives - conservative
- * by choice.  There is no slope limit over a baseline longer than one cell, and no merge with the free space the grid's rays carve.
+ * by choice.  The slope limit is a class, not a cost, and it has no roughness measure - the residual to the fitted plane is not looked
+ * at - and no robustness to outliers beyond the gate; there is no merge with the free space the grid's rays carve.
  *
  * Limits: width * height <= 2^28 and reach <= 4095 (KICP_ERR_CAPACITY, the size in the message); cell, max_ray and slab positive and
  * finite, the origin and z_origin finite, width and height >= 1, no null pointer but the nullable outputs (KICP_ERR_ARG).  Every
@@ -996,6 +1026,25 @@ int kicp_elev_traversability_from_columns(const unsigned long long *columns, uns
                                           const kicp_elev_traversability_config *config, unsigned int x0, unsigned int y0, unsigned int w, unsigned int h,
                                           signed char *out, unsigned char *out_ground, unsigned long long out_counts[4], size_t cap);
 int kicp_elev_to_grid(const kicp_elev *elev, const kicp_elev_traversability_config *config, kicp_grid *grid);
+/* The slope limit (THE SLOPE LIMIT above): the traversability with the class SLOPE from a plane fit over each cell's window. */
+typedef struct kicp_elev_slope_config {
+    unsigned int radius_cells; /* L: 1 .. 8, the window is (2L+1) x (2L+1) cells around the cell */
+    unsigned int gate_slabs;   /* K: 0 .. 63, a window cell counts only when its ground differs from the cell's by at most K */
+    unsigned int min_cells;    /* 3 .. 289: fewer cells in the fit say nothing */
+    unsigned int rise_slabs;   /* 0 .. 65535 */
+    unsigned int run_cells;    /* 1 .. 65535: the limit is rise_slabs slabs of height per run_cells cells of distance */
+} kicp_elev_slope_config;
+#define KICP_ELEV_SLOPE_COUNTS 5
+int kicp_elev_traversability_slope(const kicp_elev *elev, const kicp_elev_traversability_config *config, const kicp_elev_slope_config *slope_config,
+                                   unsigned int x0, unsigned int y0, unsigned int w, unsigned int h, signed char *out, unsigned char *out_ground,
+                                   long long *out_fit, unsigned long long out_counts[5], size_t cap);
+int kicp_elev_traversability_slope_from_columns(const unsigned long long *columns, unsigned int width, unsigned int height,
+                                                const kicp_elev_traversability_config *config, const kicp_elev_slope_config *slope_config,
+                                                unsigned int x0, unsigned int y0, unsigned int w, unsigned int h, signed char *out,
+                                                unsigned char *out_ground, long long *out_fit, unsigned long long out_counts[5], size_t cap);
+int kicp_elev_to_grid_slope(const kicp_elev *elev, const kicp_elev_traversability_config *config, const kicp_elev_slope_config *slope_config,
+                            kicp_grid *grid);
+int kicp_elev_slope_limit(const kicp_elev_config *config, double max_tangent, unsigned int *rise_slabs, unsigned int *run_cells);
 
 /* ---- map points the new frame sees through: a cube-map depth test (kicp_view.hip) ----------------------------------------------------
  * The local map loses points by distance only (RemovePointsFarFromLocation); whatever stood in view for one frame - a person crossing,

@@ -106,6 +106,13 @@ class ElevationCarveConfig(C.Structure):
     _fields_ = [("margin_steps", C.c_uint), ("widen_slabs", C.c_uint), ("keep_ground", C.c_uint)]
 
 
+class ElevationSlopeConfig(C.Structure):
+    """kicp_elev_slope_config: the plane fit of the slope limit - a window of radius_cells (1 .. 8) around each cell, of which the cells
+    count whose ground differs from the cell's by at most gate_slabs (0 .. 63); at least min_cells (3 .. 289) of them; the limit is
+    rise_slabs (0 .. 65535) slabs of height per run_cells (1 .. 65535) cells of distance"""
+    _fields_ = [("radius_cells", C.c_uint), ("gate_slabs", C.c_uint), ("min_cells", C.c_uint), ("rise_slabs", C.c_uint), ("run_cells", C.c_uint)]
+
+
 class ViewConfig(C.Structure):
     """kicp_view_config: a cube map of res x res pixels per face; the verdict looks at (2 window + 1)^2 pixels, needs min_rays returns
     among them and a gap of more than margin + margin_per_metre * depth; max_ray bounds the (Chebyshev) depth on both sides"""
@@ -259,6 +266,13 @@ _SIGNATURES = {
     "kicp_elev_traversability_from_columns": (C.c_int, [C.POINTER(C.c_ulonglong), C.c_uint, C.c_uint, C.POINTER(ElevationTraversabilityConfig), C.c_uint, C.c_uint, C.c_uint,
                                                         C.c_uint, C.POINTER(C.c_byte), C.POINTER(C.c_ubyte), C.POINTER(C.c_ulonglong), C.c_size_t]),
     "kicp_elev_to_grid": (C.c_int, [C.c_void_p, C.POINTER(ElevationTraversabilityConfig), C.c_void_p]),
+    "kicp_elev_traversability_slope": (C.c_int, [C.c_void_p, C.POINTER(ElevationTraversabilityConfig), C.POINTER(ElevationSlopeConfig), C.c_uint, C.c_uint, C.c_uint, C.c_uint,
+                                                 C.POINTER(C.c_byte), C.POINTER(C.c_ubyte), C.POINTER(C.c_longlong), C.POINTER(C.c_ulonglong), C.c_size_t]),
+    "kicp_elev_traversability_slope_from_columns": (C.c_int, [C.POINTER(C.c_ulonglong), C.c_uint, C.c_uint, C.POINTER(ElevationTraversabilityConfig),
+                                                              C.POINTER(ElevationSlopeConfig), C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.POINTER(C.c_byte), C.POINTER(C.c_ubyte),
+                                                              C.POINTER(C.c_longlong), C.POINTER(C.c_ulonglong), C.c_size_t]),
+    "kicp_elev_to_grid_slope": (C.c_int, [C.c_void_p, C.POINTER(ElevationTraversabilityConfig), C.POINTER(ElevationSlopeConfig), C.c_void_p]),
+    "kicp_elev_slope_limit": (C.c_int, [C.POINTER(ElevationConfig), C.c_double, C.POINTER(C.c_uint), C.POINTER(C.c_uint)]),
     "kicp_planar_grid": (C.c_size_t,[_dp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _dp, C.c_size_t]),
     "kicp_map_save_pcd": (C.c_int, [C.c_void_p, C.c_char_p]),
     "kicp_map_load_pcd": (C.c_int, [C.c_char_p, C.c_double, C.c_double, C.c_uint, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
@@ -864,6 +878,52 @@ def traversability_from_columns(columns, step_slabs, robot_slabs, rect=None, ret
                                                                                                   C.byref(cfg), x0, y0, w, h, o, g, n, cap), w, h, return_ground, return_counts)
 
 
+def _slope_config(slope):
+    """an ElevationSlopeConfig, or (radius_cells, gate_slabs, min_cells, rise_slabs, run_cells), or a dict with those fields"""
+    if isinstance(slope, ElevationSlopeConfig):
+        return slope
+    if isinstance(slope, dict):
+        slope = [slope[name] for name, _ in ElevationSlopeConfig._fields_]
+    return ElevationSlopeConfig(*[int(v) for v in slope])
+
+
+def _traversability_slope_call(call, w, h, return_ground, return_fit, return_counts):
+    """_traversability_call for the two entries with the slope limit: the fit is int64 (h, w, 3) - D, Da, Db - and the counts are five"""
+    out = np.empty((h, w), dtype=np.int8)
+    ground = np.empty((h, w), dtype=np.uint8) if return_ground else None
+    fit = np.empty((h, w, 3), dtype=np.int64) if return_fit else None
+    counts = np.zeros(5, dtype=np.uint64)
+    _check(call(out.ctypes.data_as(C.POINTER(C.c_byte)), ground.ctypes.data_as(C.POINTER(C.c_ubyte)) if return_ground else None,
+                fit.ctypes.data_as(C.POINTER(C.c_longlong)) if return_fit else None, counts.ctypes.data_as(C.POINTER(C.c_ulonglong)) if return_counts else None, out.size))
+    if not (return_ground or return_fit or return_counts):
+        return out
+    return (out,) + ((ground,) if return_ground else ()) + ((fit,) if return_fit else ()) + ((tuple(int(v) for v in counts),) if return_counts else ())
+
+
+def traversability_slope_from_columns(columns, step_slabs, robot_slabs, slope, rect=None, return_ground=False, return_fit=False, return_counts=False):
+    """kicp_elev_traversability_slope_from_columns: traversability_from_columns with the slope limit - a cell is also an obstacle when a
+    least-squares plane through the known grounds of its window (include/kicp.h states the fit) is steeper than slope.rise_slabs slabs
+    per slope.run_cells cells.  slope: an ElevationSlopeConfig, or its five fields as a tuple or a dict.  return_fit adds int64
+    (h, w, 3): the determinants D, Da, Db of the fit - the gradient is (Da / D, Db / D) slabs per cell -, zeros where a cell has no fit;
+    return_counts adds (unknown, traversable, BODY, STEP only, SLOPE only).  Pure host code: needs no GPU."""
+    c = np.ascontiguousarray(columns, dtype=np.uint64)
+    if c.ndim != 2 or c.size == 0:
+        raise KicpError(KICP_ERR_ARG, "columns must be shaped (height, width), both at least 1")
+    x0, y0, w, h = _rect(rect, c.shape[1], c.shape[0])
+    cfg, scfg = ElevationTraversabilityConfig(int(step_slabs), int(robot_slabs)), _slope_config(slope)
+    return _traversability_slope_call(lambda o, g, f, n, cap: lib().kicp_elev_traversability_slope_from_columns(
+        c.ctypes.data_as(C.POINTER(C.c_ulonglong)), c.shape[1], c.shape[0], C.byref(cfg), C.byref(scfg), x0, y0, w, h, o, g, f, n, cap), w, h, return_ground, return_fit,
+        return_counts)
+
+
+def elev_slope_limit(cell, slab, max_tangent):
+    """kicp_elev_slope_limit: -> (rise_slabs, run_cells) of the slope limit whose tangent is max_tangent on cells of side `cell` and
+    slabs of `slab` metres: run_cells = 1024, rise_slabs = floor(max_tangent * cell / slab * 1024)"""
+    cfg, rise, run = ElevationConfig(float(cell), 0.0, 0.0, 0, 0, 0.0, float(slab), 0.0), C.c_uint(), C.c_uint()
+    _check(lib().kicp_elev_slope_limit(C.byref(cfg), float(max_tangent), C.byref(rise), C.byref(run)))
+    return rise.value, run.value
+
+
 def elev_update_columns(config, columns, frame, pose, sensor_xyz=(0.0, 0.0, 0.0), margin_steps=2, widen_slabs=1, keep_ground=1):
     """kicp_elev_update_columns: ElevationLayer.update as pure host code.  config: an ElevationConfig, or a dict with its fields;
     columns: uint64 (height, width), contiguous, CHANGED IN PLACE -> the nine words of the update.  Needs no GPU."""
@@ -1143,6 +1203,24 @@ class ElevationLayer:
         min_observations = 1 grid.costmap, .potential, .score_arcs, .frontiers and .gain then run on traversability."""
         cfg = ElevationTraversabilityConfig(int(step_slabs), int(robot_slabs))
         _check(lib().kicp_elev_to_grid(self._h, C.byref(cfg), grid._h))
+
+    def traversability_slope(self, step_slabs, robot_slabs, slope, rect=None, return_ground=False, return_fit=False, return_counts=False):
+        """kicp_elev_traversability_slope: on the GPU, traversability_slope_from_columns' result on the columns where they are; a frame
+        changes it only inside last_window() grown by max(1, slope.radius_cells) cells"""
+        x0, y0, w, h = _rect(rect, self.width, self.height)
+        cfg, scfg = ElevationTraversabilityConfig(int(step_slabs), int(robot_slabs)), _slope_config(slope)
+        return _traversability_slope_call(lambda o, g, f, n, cap: lib().kicp_elev_traversability_slope(self._h, C.byref(cfg), C.byref(scfg), x0, y0, w, h, o, g, f, n, cap),
+                                          w, h, return_ground, return_fit, return_counts)
+
+    def to_grid_slope(self, grid, step_slabs, robot_slabs, slope):
+        """kicp_elev_to_grid_slope: to_grid with the slope limit - a SLOPE cell is an obstacle (1, 0) like a BODY or STEP one"""
+        cfg, scfg = ElevationTraversabilityConfig(int(step_slabs), int(robot_slabs)), _slope_config(slope)
+        _check(lib().kicp_elev_to_grid_slope(self._h, C.byref(cfg), C.byref(scfg), grid._h))
+
+    def slope_limit(self, max_tangent):
+        """elev_slope_limit for this layer's cell and slab -> (rise_slabs, run_cells)"""
+        info = self.info()
+        return elev_slope_limit(info["cell"], info["slab"], max_tangent)
 
 
 class DepthView:

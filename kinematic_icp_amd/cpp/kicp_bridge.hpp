@@ -234,6 +234,9 @@ using ElevationStats = std::array<unsigned long long, KICP_ELEV_STATS>;  // used
 // above, then carve_points, bits_cleared, cells_emptied
 using ElevationCarveConfig = kicp_elev_carve_config;
 using ElevationCarveStats = std::array<unsigned long long, KICP_ELEV_UPDATE_STATS>;
+// what KinematicICP::ElevationTraversabilitySlope takes beside the traversability configuration: radius_cells, gate_slabs, min_cells,
+// rise_slabs, run_cells of the plane fit (kicp.h THE SLOPE LIMIT); KinematicICP::ElevationSlopeLimit fills the last two from a tangent
+using ElevationSlopeConfig = kicp_elev_slope_config;
 inline std::shared_ptr<kicp_elev> make_elevation(const ElevationConfig &config, int device = -1) {
     kicp_elev *elev = nullptr;
     check(kicp_elev_create(&config, device < 0 ? default_device() : device, &elev), "kicp_bridge::make_elevation");

@@ -473,7 +473,8 @@ public:
     // after the registration, at the new pose, with the translation of lidar_to_base as the sensor (kicp.h kicp_elev_*, which also states
     // the layer's known limitations).  Poses, thresholds, returned clouds, the map and the grid are what they are without it.
     // Elevation() is the shared handle (null without a layer): kicp_elev_to_grid(Elevation().get(), &config, planner_grid.get()) puts the
-    // traversability into a grid a node dedicates to its planner.  LastElevationStats(): used, skipped, outside_grid, outside_column,
+    // traversability into a grid a node dedicates to its planner, and kicp_elev_to_grid_slope(Elevation().get(), &config, &slope,
+    // planner_grid.get()) the traversability with the slope limit.  LastElevationStats(): used, skipped, outside_grid, outside_column,
     // new_bits, new_cells of the last frame (zeros before the first).
     void EnableElevation(const kicp_bridge::ElevationConfig &config) { elev_ = kicp_bridge::make_elevation(config), last_elev_stats_ = {}, DisableElevationCarving(); }
     void DisableElevation() { elev_.reset(), last_elev_stats_ = {}, DisableElevationCarving(); }
@@ -511,6 +512,36 @@ public:
         kicp_bridge::check(kicp_elev_traversability(RequireElevation("ElevationTraversability"), &config, r.x0, r.y0, r.w, r.h, reinterpret_cast<signed char *>(data.data()),
                                                     ground ? ground->data() : nullptr, counts ? counts->data() : nullptr, data.size()),
                            "ElevationTraversability");
+    }
+    // The same with the slope limit (kicp.h THE SLOPE LIMIT): a cell is also an obstacle when a least-squares plane through the known
+    // grounds of its window is steeper than slope.rise_slabs slabs per slope.run_cells cells.  counts (nullable): unknown, traversable,
+    // BODY, STEP only, SLOPE only; fit (nullable): D, Da, Db per cell, zeros without a fit.  A frame changes the result only inside
+    // ElevationLastWindow() grown by max(1, slope.radius_cells) cells.  A bad configuration: std::runtime_error from the library's check.
+    void ElevationTraversabilitySlope(const kicp_bridge::ElevationTraversabilityConfig &config, const kicp_bridge::ElevationSlopeConfig &slope, std::vector<int8_t> &data,
+                                      const kicp_bridge::GridRect *rect = nullptr, std::vector<uint8_t> *ground = nullptr,
+                                      std::array<unsigned long long, KICP_ELEV_SLOPE_COUNTS> *counts = nullptr, std::vector<long long> *fit = nullptr) const {
+        const kicp_elev *elev = RequireElevation("ElevationTraversabilitySlope");
+        kicp_bridge::GridRect r;
+        if (rect) {
+            r = *rect;
+        } else {
+            kicp_elev_config layer{};
+            kicp_bridge::check(kicp_elev_info(elev, &layer, nullptr, nullptr), "ElevationTraversabilitySlope");
+            r.w = layer.width, r.h = layer.height;
+        }
+        data.resize(static_cast<size_t>(r.w) * r.h);
+        if (ground) ground->resize(data.size());
+        if (fit) fit->resize(3 * data.size());
+        kicp_bridge::check(kicp_elev_traversability_slope(elev, &config, &slope, r.x0, r.y0, r.w, r.h, reinterpret_cast<signed char *>(data.data()),
+                                                          ground ? ground->data() : nullptr, fit ? fit->data() : nullptr, counts ? counts->data() : nullptr, data.size()),
+                           "ElevationTraversabilitySlope");
+    }
+    // the slope limit of a tangent on this layer's cell and slab (kicp_elev_slope_limit): rise_slabs and run_cells of `slope` are set
+    kicp_bridge::ElevationSlopeConfig ElevationSlopeLimit(double max_tangent, kicp_bridge::ElevationSlopeConfig slope = {4u, 6u, 12u, 0u, 1u}) const {
+        kicp_elev_config layer{};
+        kicp_bridge::check(kicp_elev_info(RequireElevation("ElevationSlopeLimit"), &layer, nullptr, nullptr), "ElevationSlopeLimit");
+        kicp_bridge::check(kicp_elev_slope_limit(&layer, max_tangent, &slope.rise_slabs, &slope.run_cells), "ElevationSlopeLimit");
+        return slope;
     }
     // the window of the last integrated frame clipped to the layer; empty() when it lies outside, and before any frame
     kicp_bridge::GridRect ElevationLastWindow() const {

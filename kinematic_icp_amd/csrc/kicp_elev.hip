@@ -33,6 +33,7 @@ struct kicp_elev {
         DevBuf<uint8_t> d_ground;
         DevBuf<unsigned int> d_counts;
         PinnedBuf<unsigned int> h_counts;
+        DevBuf<long long> d_fit;  // kicp_elev_traversability_slope: D, Da, Db per cell
     } readout;
     ~kicp_elev() {
         if (stream) (void)hipStreamSynchronize(stream), (void)hipStreamDestroy(stream);
@@ -53,6 +54,15 @@ int check_elev_params(const kicp_elev_traversability_config *cfg, ElevParams &p)
     p = ElevParams{cfg->step_slabs, cfg->robot_slabs};
     if (cfg->step_slabs > kElevMaxStep) return fail(KICP_ERR_ARG, "step_slabs must lie in 0 .. 62");
     if (!(cfg->step_slabs < cfg->robot_slabs && cfg->robot_slabs <= kElevSlabs)) return fail(KICP_ERR_ARG, "robot_slabs must satisfy step_slabs < robot_slabs <= 64");
+    return KICP_OK;
+}
+int check_slope_config(const kicp_elev_slope_config *cfg, ElevSlopeParams &p) {
+    p = ElevSlopeParams{cfg->radius_cells, cfg->gate_slabs, cfg->min_cells, cfg->rise_slabs, cfg->run_cells};
+    if (cfg->radius_cells < 1u || cfg->radius_cells > kElevSlopeMaxRadius) return fail(KICP_ERR_ARG, "radius_cells must lie in 1 .. 8");
+    if (cfg->gate_slabs > kElevSlopeMaxGate) return fail(KICP_ERR_ARG, "gate_slabs must lie in 0 .. 63");
+    if (cfg->min_cells < kElevSlopeMinCells || cfg->min_cells > 289u) return fail(KICP_ERR_ARG, "min_cells must lie in 3 .. 289");
+    if (cfg->rise_slabs > kElevSlopeMaxRatio) return fail(KICP_ERR_ARG, "rise_slabs must lie in 0 .. 65535");
+    if (cfg->run_cells < 1u || cfg->run_cells > kElevSlopeMaxRatio) return fail(KICP_ERR_ARG, "run_cells must lie in 1 .. 65535");
     return KICP_OK;
 }
 int check_elev_rect(unsigned int width, unsigned int height, const ElevRect &r, size_t cap) {
@@ -129,6 +139,29 @@ int check_frame_args(const kicp_elev *elev, const double *xyz, size_t n, const d
     return FrameUpload::check(elev && pose_qt && sensor_xyz && (xyz || !n), n, "frame too large");
 }
 uint32_t elev_tiles(uint32_t cells_side) { return (cells_side + kElevTile - 1u) / kElevTile; }
+// the slope kernels' instantiation for L = radius (1 .. 8: check_slope_config)
+using SlopeKernel = void (*)(const unsigned long long *, uint32_t, uint32_t, ElevParams, ElevSlopeParams, ElevRect, uint32_t, int8_t *, uint8_t *, long long *, unsigned int *);
+using SlopeToGridKernel = void (*)(const unsigned long long *, uint32_t, uint32_t, ElevParams, ElevSlopeParams, ElevRect, uint32_t, uint16_t *);
+SlopeKernel slope_kernel(uint32_t radius) {
+    static const SlopeKernel k[kElevSlopeMaxRadius] = {k_elev_slope<1>, k_elev_slope<2>, k_elev_slope<3>, k_elev_slope<4>, k_elev_slope<5>, k_elev_slope<6>, k_elev_slope<7>, k_elev_slope<8>};
+    return k[radius - 1u];
+}
+SlopeToGridKernel slope_to_grid_kernel(uint32_t radius) {
+    static const SlopeToGridKernel k[kElevSlopeMaxRadius] = {k_elev_slope_to_grid<1>, k_elev_slope_to_grid<2>, k_elev_slope_to_grid<3>, k_elev_slope_to_grid<4>,
+                                                             k_elev_slope_to_grid<5>, k_elev_slope_to_grid<6>, k_elev_slope_to_grid<7>, k_elev_slope_to_grid<8>};
+    return k[radius - 1u];
+}
+// what kicp_elev_to_grid and kicp_elev_to_grid_slope ask of the grid: the layer's plane, on the layer's device
+int check_to_grid(const kicp_elev *elev, const kicp_grid *grid) {
+    const kicp_grid_config &gc = grid->cfg;
+    const kicp_elev_config &ec = elev->cfg;
+    auto same_bits = [](double a, double b) { return std::memcmp(&a, &b, sizeof a) == 0; };
+    if (!(same_bits(gc.cell, ec.cell) && same_bits(gc.origin_x, ec.origin_x) && same_bits(gc.origin_y, ec.origin_y) && gc.width == ec.width && gc.height == ec.height))
+        return fail(KICP_ERR_ARG, "the grid's cell, origin, width and height must equal the layer's");
+    if (grid->device != elev->device)
+        return fail(KICP_ERR_ARG, "the grid lives on device " + std::to_string(grid->device) + ", the layer on device " + std::to_string(elev->device));
+    return KICP_OK;
+}
 }  // namespace
 
 extern "C" {
@@ -303,13 +336,8 @@ int kicp_elev_to_grid(const kicp_elev *elev, const kicp_elev_traversability_conf
     if (!elev || !cfg || !grid) return fail(KICP_ERR_ARG, "null argument");
     ElevParams p;
     if (int rc = check_elev_params(cfg, p)) return rc;
-    const kicp_grid_config &gc = grid->cfg;
     const kicp_elev_config &ec = elev->cfg;
-    auto same_bits = [](double a, double b) { return std::memcmp(&a, &b, sizeof a) == 0; };
-    if (!(same_bits(gc.cell, ec.cell) && same_bits(gc.origin_x, ec.origin_x) && same_bits(gc.origin_y, ec.origin_y) && gc.width == ec.width && gc.height == ec.height))
-        return fail(KICP_ERR_ARG, "the grid's cell, origin, width and height must equal the layer's");
-    if (grid->device != elev->device)
-        return fail(KICP_ERR_ARG, "the grid lives on device " + std::to_string(grid->device) + ", the layer on device " + std::to_string(elev->device));
+    if (int rc = check_to_grid(elev, grid)) return rc;
     if (int rc = set_device(elev->device)) return rc;
     // Both handles' streams are idle (the stream rule); the launch runs on the layer's and is waited for, so the grid's next entry
     // finds its counters written.
@@ -318,6 +346,85 @@ int kicp_elev_to_grid(const kicp_elev *elev, const kicp_elev_traversability_conf
                        ElevRect{0u, 0u, ec.width, ec.height}, tiles_x, grid->d_counts.get());
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(elev->stream));
+    return KICP_OK;
+}
+int kicp_elev_traversability_slope(const kicp_elev *elev, const kicp_elev_traversability_config *cfg, const kicp_elev_slope_config *slope, unsigned int x0,
+                                   unsigned int y0, unsigned int w, unsigned int h, signed char *out, unsigned char *out_ground, long long *out_fit,
+                                   unsigned long long out_counts[5], size_t cap) {
+    KICP_TRACE_CALL();
+    if (!elev || !cfg || !slope || !out) return fail(KICP_ERR_ARG, "null argument");
+    ElevParams p;
+    ElevSlopeParams sp;
+    const ElevRect r{x0, y0, w, h};
+    if (int rc = check_elev_params(cfg, p)) return rc;
+    if (int rc = check_slope_config(slope, sp)) return rc;
+    if (int rc = check_elev_rect(elev->cfg.width, elev->cfg.height, r, cap)) return rc;
+    if (int rc = set_device(elev->device)) return rc;
+    auto &ro = elev->readout;
+    if (int rc = ro.d_classes.reserve(cap)) return rc;
+    if (out_ground)
+        if (int rc = ro.d_ground.reserve(cap)) return rc;
+    if (out_fit)
+        if (int rc = ro.d_fit.reserve(3 * cap)) return rc;
+    if (out_counts) {
+        if (int rc = ro.d_counts.reserve(kElevCountWords)) return rc;
+        if (int rc = ro.h_counts.reserve(kElevCountWords, hipHostMallocDefault, false)) return rc;
+    }
+    hipStream_t st = elev->stream;
+    if (out_counts) HIP_TRY(hipMemsetAsync(ro.d_counts.get(), 0, kElevCountWords * sizeof(unsigned int), st));
+    const uint32_t tiles_x = elev_tiles(w), tiles_y = elev_tiles(h);  // (their product stays below 2^25: cells <= 2^28)
+    hipLaunchKernelGGL(slope_kernel(sp.radius), dim3(tiles_x * tiles_y), dim3(kElevBlock), 0, st, elev->d_columns.get(), elev->cfg.width, elev->cfg.height, p, sp, r, tiles_x,
+                       ro.d_classes.get(), out_ground ? ro.d_ground.get() : static_cast<uint8_t *>(nullptr), out_fit ? ro.d_fit.get() : static_cast<long long *>(nullptr),
+                       out_counts ? ro.d_counts.get() : static_cast<unsigned int *>(nullptr));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, ro.d_classes.get(), cap, hipMemcpyDeviceToHost, st));
+    if (out_ground) HIP_TRY(hipMemcpyAsync(out_ground, ro.d_ground.get(), cap, hipMemcpyDeviceToHost, st));
+    if (out_fit) HIP_TRY(hipMemcpyAsync(out_fit, ro.d_fit.get(), 3 * cap * sizeof(long long), hipMemcpyDeviceToHost, st));
+    if (out_counts) HIP_TRY(hipMemcpyAsync(ro.h_counts.get(), ro.d_counts.get(), kElevCountWords * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (out_counts)
+        for (int k = 0; k < KICP_ELEV_SLOPE_COUNTS; ++k) out_counts[k] = shard_sum(ro.h_counts.get(), k);
+    return KICP_OK;
+}
+int kicp_elev_traversability_slope_from_columns(const unsigned long long *columns, unsigned int width, unsigned int height, const kicp_elev_traversability_config *cfg,
+                                                const kicp_elev_slope_config *slope, unsigned int x0, unsigned int y0, unsigned int w, unsigned int h, signed char *out,
+                                                unsigned char *out_ground, long long *out_fit, unsigned long long out_counts[5], size_t cap) {
+    if (!columns || !cfg || !slope || !out) return fail(KICP_ERR_ARG, "null argument");
+    ElevParams p;
+    ElevSlopeParams sp;
+    const ElevRect r{x0, y0, w, h};
+    if (int rc = check_elev_params(cfg, p)) return rc;
+    if (int rc = check_slope_config(slope, sp)) return rc;
+    if (int rc = check_grid_dims(width, height)) return rc;
+    if (int rc = check_elev_rect(width, height, r, cap)) return rc;
+    elev_host::classify_slope(reinterpret_cast<const uint64_t *>(columns), width, height, p, sp, r, reinterpret_cast<int8_t *>(out), out_ground, out_fit, out_counts);
+    return KICP_OK;
+}
+int kicp_elev_to_grid_slope(const kicp_elev *elev, const kicp_elev_traversability_config *cfg, const kicp_elev_slope_config *slope, kicp_grid *grid) {
+    KICP_TRACE_CALL();
+    if (!elev || !cfg || !slope || !grid) return fail(KICP_ERR_ARG, "null argument");
+    ElevParams p;
+    ElevSlopeParams sp;
+    if (int rc = check_elev_params(cfg, p)) return rc;
+    if (int rc = check_slope_config(slope, sp)) return rc;
+    if (int rc = check_to_grid(elev, grid)) return rc;
+    if (int rc = set_device(elev->device)) return rc;
+    const kicp_elev_config &ec = elev->cfg;
+    const uint32_t tiles_x = elev_tiles(ec.width), tiles_y = elev_tiles(ec.height);  // (the streams: as kicp_elev_to_grid)
+    hipLaunchKernelGGL(slope_to_grid_kernel(sp.radius), dim3(tiles_x * tiles_y), dim3(kElevBlock), 0, elev->stream, elev->d_columns.get(), ec.width, ec.height, p, sp,
+                       ElevRect{0u, 0u, ec.width, ec.height}, tiles_x, grid->d_counts.get());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(elev->stream));
+    return KICP_OK;
+}
+int kicp_elev_slope_limit(const kicp_elev_config *config, double max_tangent, unsigned int *rise_slabs, unsigned int *run_cells) {
+    if (!config || !rise_slabs || !run_cells) return fail(KICP_ERR_ARG, "null argument");
+    if (!(config->cell > 0.0) || !std::isfinite(config->cell) || !(config->slab > 0.0) || !std::isfinite(config->slab))
+        return fail(KICP_ERR_ARG, "cell and slab must be positive and finite");
+    const double rise = std::floor(((max_tangent * config->cell) / config->slab) * 1024.0);
+    if (!(rise >= 0.0 && rise <= static_cast<double>(kElevSlopeMaxRatio)))  // (a NaN fails both)
+        return fail(KICP_ERR_ARG, "max_tangent gives a rise of " + std::to_string(rise) + " slabs per 1024 cells: it must be finite and lie in 0 .. 65535");
+    *rise_slabs = static_cast<unsigned int>(rise), *run_cells = 1024u;
     return KICP_OK;
 }
 

@@ -15,6 +15,11 @@
 //                    neighbours in LDS; the classes, the optional ground bytes and per-wave sums of the four counts are written
 //   k_elev_to_grid   the same classification (elev_classify_cell, one device function for both) written as the two 16-bit counters
 //                    of a kicp_grid
+//   k_elev_slope<L>  the same tile with a halo of L <= 8 cells in LDS: a lane whose cell is known also walks its (2 L + 1)^2 window of
+//                    grounds into nine integer sums, and a least-squares plane through them - three 64-bit determinants, compared
+//                    in 128-bit integers - adds the class SLOPE; the optional determinants and five counts are written.  One
+//                    instantiation per L, so that the walk unrolls
+//   k_elev_slope_to_grid<L>  that classification (elev_slope_cell, one device function for both) as a kicp_grid's counters
 // The atomics besides the OR and the AND are the statistics and the list's length: one add per wave per word that has something to add.
 // No kernel uses scratch; the mark, list and carve kernels use no LDS.
 #pragma once
@@ -223,6 +228,104 @@ static __global__ __launch_bounds__(kElevBlock) void k_elev_to_grid(const unsign
     uint8_t ground;
     uint32_t which;
     if (!elev_classify_cell(columns, width, height, p, r, tiles_x, grounds, value, ground, which)) return;  // (behind the barrier)
+    const uint32_t x = (blockIdx.x % tiles_x) * kElevTile + threadIdx.x % kElevTile, y = (blockIdx.x / tiles_x) * kElevTile + threadIdx.x / kElevTile;
+    reinterpret_cast<uint32_t *>(grid_counts)[static_cast<size_t>(y) * width + x] = value < 0 ? 0u : value ? 1u : 0x10000u;
+}
+
+// ---- the slope limit (kicp_elev_traversability_slope, kicp_elev_to_grid_slope) ------------------------------------------------------
+// The window of a known cell out of LDS into the nine sums.  L IS A TEMPLATE ARGUMENT: both loops unroll, dx, dy, their products and
+// the byte offsets become constants, and the walk of a fully known 1 600 x 1 600 layer at L = 8 takes 0.29 ms where the same loops
+// bounded by a kernel argument took 0.70.
+template <int L>
+static __device__ __forceinline__ void elev_slope_walk(const uint8_t *centre, uint32_t ground, uint32_t gate, ElevSlopeSums &s) {
+    constexpr int32_t side = static_cast<int32_t>(kElevTile) + 2 * L;
+#pragma unroll
+    for (int32_t dy = -L; dy <= L; ++dy)
+#pragma unroll
+        for (int32_t dx = -L; dx <= L; ++dx) elev_slope_add(s, ground, centre[dy * side + dx], dx, dy, gate);
+}
+// The class of this lane's cell with the slope limit, the lane's cell as in elev_classify_cell: every lane of the workgroup calls it
+// (it holds the barrier).  L = sp.radius (the host picks the instantiation).  grounds: side^2 bytes of LDS, side = kElevTile + 2 L:
+// the tile's grounds and a halo of L cells, loaded by all lanes in a strided loop along rows, EVERY LOAD BEHIND THE INSIDE-THE-GRID
+// TEST; a cell outside the grid reads 255 like an unknown one.  After the barrier a lane whose cell is known walks its (2 L + 1)^2
+// window out of LDS into the nine sums; a lane whose cell is unknown skips the walk - most of a real layer is unknown, and a wave with
+// no known cell branches over it.  STEP comes from the same bytes, BODY from the lane's own column.  Every loop is bounded by L <= 8.
+// -> inside: the cell lies in the rectangle; value, ground, which (elev_slope_value) and d, da, db (zeros without a fit) are its results.
+template <int L>
+static __device__ __forceinline__ bool elev_slope_cell(const unsigned long long *__restrict__ columns, uint32_t width, uint32_t height, const ElevParams &p,
+                                                       const ElevSlopeParams &sp, const ElevRect &r, uint32_t tiles_x, uint8_t *grounds, int8_t &value, uint8_t &ground,
+                                                       uint32_t &which, int64_t &d, int64_t &da, int64_t &db) {
+    static_assert(L >= 1 && L <= static_cast<int>(kElevSlopeMaxRadius), "the halo is 1 .. 8 cells");
+    constexpr uint32_t side = kElevTile + 2u * L;
+    const uint32_t tx = threadIdx.x % kElevTile, ty = threadIdx.x / kElevTile;
+    const uint32_t bx = r.x0 + (blockIdx.x % tiles_x) * kElevTile, by = r.y0 + (blockIdx.x / tiles_x) * kElevTile;  // the tile's corner: inside the rectangle
+    const uint32_t x = bx + tx, y = by + ty;
+    const bool inside = x - r.x0 < r.w && y - r.y0 < r.h;  // (inside the rectangle implies inside the grid)
+#pragma unroll
+    for (uint32_t k = threadIdx.x; k < side * side; k += kElevBlock) {  // at most four trips
+        const uint32_t hx = k % side, hy = k / side;
+        const int64_t gx = static_cast<int64_t>(bx) + hx - L, gy = static_cast<int64_t>(by) + hy - L;
+        const bool ok = gx >= 0 && gy >= 0 && gx < static_cast<int64_t>(width) && gy < static_cast<int64_t>(height);
+        grounds[k] = ok ? elev_ground(columns[static_cast<size_t>(gy) * width + static_cast<size_t>(gx)]) : kElevNoGround;
+    }
+    __syncthreads();
+    const uint8_t *centre = grounds + (ty + L) * side + (tx + L);
+    ground = *centre;
+    const bool known = ground != kElevNoGround;
+    bool body = false, step = false, slope = false;
+    d = da = db = 0;
+    if (known) {  // (a known cell lies inside the grid: the load is behind that test)
+        body = elev_body(columns[static_cast<size_t>(y) * width + x], ground, p);
+#pragma unroll
+        for (int32_t dy = -1; dy <= 1; ++dy)
+#pragma unroll
+            for (int32_t dx = -1; dx <= 1; ++dx)
+                if (dx || dy) step = step || elev_step(ground, centre[dy * static_cast<int32_t>(side) + dx], p);
+        ElevSlopeSums s{};
+        elev_slope_walk<L>(centre, ground, sp.gate, s);
+        elev_slope_determinants(s, d, da, db);
+        if (elev_slope_has_fit(s, d, sp)) slope = elev_slope_exceeds(d, da, db, sp);
+        else d = da = db = 0;
+    }
+    value = elev_slope_value(known, body, step, slope, which);
+    return inside;
+}
+
+// out / out_ground (nullable) / out_fit (nullable: triples D, Da, Db): r.h * r.w entries; counts (nullable): kElevCountShards x
+// kElevCountStride words, a wave adds unknown, traversable, BODY, STEP only, SLOPE only to words 0 .. 4 of its shard
+template <int L>
+static __global__ __launch_bounds__(kElevBlock) void k_elev_slope(const unsigned long long *__restrict__ columns, uint32_t width, uint32_t height, ElevParams p,
+                                                                  ElevSlopeParams sp, ElevRect r, uint32_t tiles_x, int8_t *__restrict__ out,
+                                                                  uint8_t *__restrict__ out_ground, long long *__restrict__ out_fit, unsigned int *__restrict__ counts) {
+    __shared__ uint8_t grounds[(kElevTile + 2u * L) * (kElevTile + 2u * L)];
+    int8_t value;
+    uint8_t ground;
+    uint32_t which;
+    int64_t d, da, db;
+    const bool inside = elev_slope_cell<L>(columns, width, height, p, sp, r, tiles_x, grounds, value, ground, which, d, da, db);
+    if (inside) {
+        const uint32_t rx = (blockIdx.x % tiles_x) * kElevTile + threadIdx.x % kElevTile, ry = (blockIdx.x / tiles_x) * kElevTile + threadIdx.x / kElevTile;
+        const size_t o = static_cast<size_t>(ry) * r.w + rx;
+        out[o] = value;
+        if (out_ground) out_ground[o] = ground;
+        if (out_fit) out_fit[3 * o] = d, out_fit[3 * o + 1] = da, out_fit[3 * o + 2] = db;
+    }
+    if (counts) {
+        unsigned int *shard = elev_shard(counts);
+        for (uint32_t k = 0; k < 5u; ++k) elev_wave_add(&shard[k], inside && which == k);
+    }
+}
+
+// k_elev_to_grid with the slope limit: the rectangle is the full grid
+template <int L>
+static __global__ __launch_bounds__(kElevBlock) void k_elev_slope_to_grid(const unsigned long long *__restrict__ columns, uint32_t width, uint32_t height, ElevParams p,
+                                                                          ElevSlopeParams sp, ElevRect r, uint32_t tiles_x, uint16_t *__restrict__ grid_counts) {
+    __shared__ uint8_t grounds[(kElevTile + 2u * L) * (kElevTile + 2u * L)];
+    int8_t value;
+    uint8_t ground;
+    uint32_t which;
+    int64_t d, da, db;
+    if (!elev_slope_cell<L>(columns, width, height, p, sp, r, tiles_x, grounds, value, ground, which, d, da, db)) return;  // (behind the barrier)
     const uint32_t x = (blockIdx.x % tiles_x) * kElevTile + threadIdx.x % kElevTile, y = (blockIdx.x / tiles_x) * kElevTile + threadIdx.x / kElevTile;
     reinterpret_cast<uint32_t *>(grid_counts)[static_cast<size_t>(y) * width + x] = value < 0 ? 0u : value ? 1u : 0x10000u;
 }

@@ -1,8 +1,10 @@
 // kicp_elev_host.hpp -- the arithmetic of the height columns (kicp_elev_*, include/kicp.h): the class of one point, the ground of one
-// column, BODY and STEP of one cell, and the carve along a frame's rays: which points carve, the slab of a ray at a step, a step's mask
+// column, BODY and STEP of one cell, the slope limit - one window cell into the nine sums of a plane fit, its determinants and the
+// 128-bit comparison -, and the carve along a frame's rays: which points carve, the slab of a ray at a step, a step's mask
 // and what it clears of a column.  ONE text for the kernels (kicp_elev.hpp), for the pure-host entries
-// (kicp_elev_traversability_from_columns, kicp_elev_update_columns) and for elev_host::integrate / carve / update / classify, the host
-// restatements that stand-alone programs run under sanitizers (tests/cpp/elev_host_test.cpp, tests/cpp/elev_carve_host_test.cpp).
+// (kicp_elev_traversability_from_columns, kicp_elev_traversability_slope_from_columns, kicp_elev_update_columns) and for
+// elev_host::integrate / carve / update / classify / classify_slope, the host restatements that stand-alone programs run under
+// sanitizers (tests/cpp/elev_host_test.cpp, tests/cpp/elev_carve_host_test.cpp, tests/cpp/elev_slope_host_test.cpp).
 // Everything is exact and integer from the floor on.
 #pragma once
 #include "kicp_grid_host.hpp"
@@ -82,6 +84,49 @@ KICP_HD bool elev_step(uint32_t ground, uint8_t neighbour_ground, const ElevPara
 KICP_HD int8_t elev_value(bool known, bool body, bool step, uint32_t &which) {
     which = !known ? 0u : body ? 2u : step ? 3u : 1u;
     return !known ? static_cast<int8_t>(-1) : static_cast<int8_t>((body || step) ? 100 : 0);
+}
+
+// ---- the slope limit: a least-squares plane through the known grounds of a window (kicp_elev_traversability_slope*) ---------------
+constexpr uint32_t kElevSlopeMaxRadius = 8, kElevSlopeMaxGate = 63, kElevSlopeMinCells = 3, kElevSlopeMaxRatio = 65535;
+
+struct ElevSlopeParams {
+    uint32_t radius, gate, min_cells, rise, run;  // L, K, the fewest cells of a fit, and the limit: rise slabs per run cells
+};
+// The nine sums over a cell's FIT SET, z = g_n - g.  At L = 8: n <= 289, Sxx, Syy <= 6 936, |Sxy| <= 5 184, |Sz| <= 18 207, |Sxz|, |Syz| <=
+// 77 112 - 32 bits with room.
+struct ElevSlopeSums {
+    int32_t n, sx, sy, sxx, sxy, syy, sz, sxz, syz;
+};
+// One window cell (dx, dy) with ground byte neighbour_ground into the sums of a cell with ground g, when it belongs: known and
+// |g_n - g| <= K.  ONE unsigned comparison does both: K <= 63 and g <= 63, so the 255 of an unknown cell (or of one outside the grid)
+// gives 255 - g + K >= 192 + K > 2 K.
+KICP_HD void elev_slope_add(ElevSlopeSums &s, uint32_t ground, uint8_t neighbour_ground, int32_t dx, int32_t dy, uint32_t gate) {
+    if (static_cast<uint32_t>(neighbour_ground) - ground + gate > 2u * gate) return;
+    const int32_t z = static_cast<int32_t>(neighbour_ground) - static_cast<int32_t>(ground);
+    s.n += 1, s.sx += dx, s.sy += dy, s.sxx += dx * dx, s.sxy += dx * dy, s.syy += dy * dy, s.sz += z, s.sxz += dx * z, s.syz += dy * z;
+}
+// Cramer's rule on the normal equations of z ~ a dx + b dy + c: the gradient is (Da / D, Db / D) slabs per cell.  D is a Gram
+// determinant: >= 0, and 0 when the set lies on one line.  D < 2^34, |Da|, |Db| < 2^41, every product below 2^42: 64 bits.
+KICP_HD void elev_slope_determinants(const ElevSlopeSums &s, int64_t &d, int64_t &da, int64_t &db) {
+    const int64_t n = s.n, sx = s.sx, sy = s.sy, sxx = s.sxx, sxy = s.sxy, syy = s.syy, sz = s.sz, sxz = s.sxz, syz = s.syz;
+    d = sxx * (syy * n - sy * sy) - sxy * (sxy * n - sy * sx) + sx * (sxy * sy - syy * sx);
+    da = sxz * (syy * n - sy * sy) - sxy * (syz * n - sy * sz) + sx * (syz * sy - syy * sz);
+    db = sxx * (syz * n - sz * sy) - sxz * (sxy * n - sy * sx) + sx * (sxy * sz - syz * sx);
+}
+// the cell HAS A FIT
+KICP_HD bool elev_slope_has_fit(const ElevSlopeSums &s, int64_t d, const ElevSlopeParams &p) { return static_cast<uint32_t>(s.n) >= p.min_cells && d > 0; }
+// SLOPE of a cell that has a fit: (Da^2 + Db^2) run^2 > rise^2 D^2, strictly, on exact integers: the left side stays below 2^115, the
+// right below 2^100 - 128-bit products, no division, no floating point.
+KICP_HD bool elev_slope_exceeds(int64_t d, int64_t da, int64_t db, const ElevSlopeParams &p) {
+    typedef unsigned __int128 u128;
+    const u128 a = static_cast<uint64_t>(da < 0 ? -da : da), b = static_cast<uint64_t>(db < 0 ? -db : db), dd = static_cast<uint64_t>(d);
+    const uint64_t run2 = static_cast<uint64_t>(p.run) * p.run, rise2 = static_cast<uint64_t>(p.rise) * p.rise;
+    return (a * a + b * b) * run2 > dd * dd * rise2;
+}
+// the value of a cell and the count it adds to: 0 unknown, 1 traversable, 2 BODY, 3 STEP only, 4 SLOPE only
+KICP_HD int8_t elev_slope_value(bool known, bool body, bool step, bool slope, uint32_t &which) {
+    which = !known ? 0u : body ? 2u : step ? 3u : slope ? 4u : 1u;
+    return !known ? static_cast<int8_t>(-1) : static_cast<int8_t>((body || step || slope) ? 100 : 0);
 }
 
 // ---- carving along the frame's rays (kicp_elev_update*) --------------------------------------------------------------------------
@@ -224,6 +269,44 @@ inline void classify(const uint64_t *columns, uint32_t width, uint32_t height, c
         }
     if (counts)
         for (int k = 0; k < 4; ++k) counts[k] = sums[k];
+}
+// The same with the slope limit, as k_elev_slope computes it: fit (nullable) takes D, Da, Db per cell, zeros where the cell has no fit;
+// counts (nullable): unknown, traversable, BODY, STEP only, SLOPE only.
+inline void classify_slope(const uint64_t *columns, uint32_t width, uint32_t height, const ElevParams &p, const ElevSlopeParams &sp, const ElevRect &r, int8_t *out,
+                           uint8_t *ground, long long *fit, unsigned long long counts[5]) {
+    unsigned long long sums[5] = {0, 0, 0, 0, 0};
+    const int32_t L = static_cast<int32_t>(sp.radius);
+    for (uint32_t ry = 0; ry < r.h; ++ry)
+        for (uint32_t rx = 0; rx < r.w; ++rx) {
+            const uint32_t x = r.x0 + rx, y = r.y0 + ry;
+            const uint64_t c = columns[static_cast<size_t>(y) * width + x];
+            const uint8_t gr = elev_ground(c);
+            bool body = false, step = false, slope = false;
+            int64_t d = 0, da = 0, db = 0;
+            if (c) {
+                body = elev_body(c, gr, p);
+                ElevSlopeSums s{};
+                for (int32_t dy = -L; dy <= L; ++dy)
+                    for (int32_t dx = -L; dx <= L; ++dx) {
+                        const int64_t nx = static_cast<int64_t>(x) + dx, ny = static_cast<int64_t>(y) + dy;
+                        if (nx < 0 || ny < 0 || nx >= static_cast<int64_t>(width) || ny >= static_cast<int64_t>(height)) continue;
+                        const uint8_t gn = elev_ground(columns[static_cast<size_t>(ny) * width + static_cast<size_t>(nx)]);
+                        elev_slope_add(s, gr, gn, dx, dy, sp.gate);
+                        if ((dx || dy) && dx >= -1 && dx <= 1 && dy >= -1 && dy <= 1) step = step || elev_step(gr, gn, p);
+                    }
+                elev_slope_determinants(s, d, da, db);
+                if (elev_slope_has_fit(s, d, sp)) slope = elev_slope_exceeds(d, da, db, sp);
+                else d = da = db = 0;
+            }
+            uint32_t which;
+            const size_t o = static_cast<size_t>(ry) * r.w + rx;
+            out[o] = elev_slope_value(c != 0ull, body, step, slope, which);
+            if (ground) ground[o] = gr;
+            if (fit) fit[3 * o] = d, fit[3 * o + 1] = da, fit[3 * o + 2] = db;
+            ++sums[which];
+        }
+    if (counts)
+        for (int k = 0; k < 5; ++k) counts[k] = sums[k];
 }
 }  // namespace elev_host
 

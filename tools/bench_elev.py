@@ -22,9 +22,13 @@ have completed.  Warm; everything that is compared alternates in the same proces
     --pipeline the drive through tests/cpp/elev_carve_facade_test, mode `timed`: a process without a layer, one with a layer and one
     with a layer that carves, and per --contender a process of another build's tests/cpp/elev_facade_test `timed .. on` - the parent
     commit's pipeline with its layer, which is what this build's frame must cost while carving is off.
+  - with --slope INSTEAD of the above: the slope limit (kicp_elev_traversability_slope, kicp_elev_to_grid_slope) on the traversability
+    case's 1 600 x 1 600 layer at L = 2, 4 and 8 - the full layer, the last window grown by L, the full layer with every optional
+    output, and into a grid - beside kicp_elev_traversability and kicp_elev_to_grid of this build and, with --ab parent=LIBRARY, of
+    the parent commit's library on the same columns, alternating (raw output kept as profiles/elev_slope_bench.json).
 Prints one JSON line.
 
-    python tools/bench_elev.py [--rounds 30] [--carve] [--ab NAME=LIB] [--pipeline] [--pipeline-rounds 3] [--pipeline-frames 16] [--contender NAME=EXE:LIBDIR]
+    python tools/bench_elev.py [--rounds 30] [--carve | --slope] [--ab NAME=LIB] [--pipeline] [--pipeline-rounds 3] [--pipeline-frames 16] [--contender NAME=EXE:LIBDIR]
 """
 import argparse
 import ctypes as C
@@ -82,10 +86,43 @@ class RawLayer:
 def load_contender(path):
     lib = C.CDLL(os.path.abspath(path))
     for name, (res, args) in K._SIGNATURES.items():
-        if name.startswith("kicp_elev_"):
-            fn = getattr(lib, name)
-            fn.restype, fn.argtypes = res, args
+        if name.startswith("kicp_elev_") or name in ("kicp_grid_create", "kicp_grid_destroy"):
+            fn = getattr(lib, name, None)  # (an older build lacks the newer entries)
+            if fn is not None:
+                fn.restype, fn.argtypes = res, args
     return lib
+
+
+class RawClasses:
+    """kicp_elev_traversability and kicp_elev_to_grid of another build (an --ab contender) on given columns: a layer and a grid of that
+    build, through its C-ABI"""
+
+    def __init__(self, lib, cfg, columns):
+        self.lib, self._h, self._g = lib, C.c_void_p(), C.c_void_p()
+        c = K.ElevationConfig(cfg["cell"], cfg["origin_x"], cfg["origin_y"], cfg["width"], cfg["height"], Z_ORIGIN, SLAB, cfg["max_ray"])
+        g = K.GridConfig(cfg["cell"], cfg["origin_x"], cfg["origin_y"], cfg["width"], cfg["height"], cfg["z_min"], cfg["z_max"], cfg["max_ray"])
+        assert lib.kicp_elev_create(C.byref(c), 0, C.byref(self._h)) == 0 and lib.kicp_grid_create(C.byref(g), 0, C.byref(self._g)) == 0
+        assert lib.kicp_elev_set_columns(self._h, columns.ctypes.data_as(C.POINTER(C.c_ulonglong)), columns.size) == 0
+        self.cfg, self.out = K.ElevationTraversabilityConfig(STEP_SLABS, ROBOT_SLABS), np.empty((cfg["height"], cfg["width"]), dtype=np.int8)
+
+    def traversability(self):
+        h, w = self.out.shape
+        assert self.lib.kicp_elev_traversability(self._h, C.byref(self.cfg), 0, 0, w, h, self.out.ctypes.data_as(C.POINTER(C.c_byte)), None, None, self.out.size) == 0
+        return self.out
+
+    def to_grid(self):
+        assert self.lib.kicp_elev_to_grid(self._h, C.byref(self.cfg), self._g) == 0
+
+    def __del__(self):
+        lib = getattr(self, "lib", None)
+        if lib is None:
+            return
+        if getattr(self, "_h", None):
+            lib.kicp_elev_destroy(self._h)
+            self._h = None
+        if getattr(self, "_g", None):
+            lib.kicp_grid_destroy(self._g)
+            self._g = None
 
 
 def make_layer(cfg):
@@ -206,6 +243,63 @@ def traversability_rows(rounds):
              "traversability_window_ms": spread(t["window"]), "grid_occupancy_full_ms": spread(t["occupancy"]), "to_grid_ms": spread(t["to_grid"])}]
 
 
+SLOPE_RADII = (2, 4, 8)
+
+
+def slope_rows(rounds, contenders):
+    """the slope limit on traversability_rows' 1 600 x 1 600 layer, at L = 2, 4 and 8 (K = (S + 1) L, min_cells 12, 20 degrees): the full
+    layer, the last window grown by L, the full layer with ground bytes, determinants and counts, and kicp_elev_to_grid_slope - beside
+    kicp_elev_traversability and kicp_elev_to_grid of this build and of every --ab contender (the parent commit's library), on the
+    same columns, alternating"""
+    name = "cfg1"
+    cfg, scene, dirs, rng = scene_and_beams(name)
+    pose = syn.planar_pose(1.2, -0.7, 0.9)
+    frame = np.ascontiguousarray(syn.make_scan(scene, pose, dirs, cfg.sensor_height, rng))
+    sensor = np.array([0.0, 0.0, cfg.sensor_height])
+    gcfg = dict(grid_config(name, 0.05), max_ray=12.0, reach=240)
+    layer, other = make_layer(gcfg), make_grid(gcfg)
+    layer.integrate(frame, pose, sensor)
+    columns = layer.columns()
+    raws = {who: RawClasses(lib, gcfg, columns) for who, lib in contenders.items()}
+    x0, y0, w, h = layer.last_window()
+    rise, run = layer.slope_limit(np.tan(np.deg2rad(20.0)))
+    slopes = {L: (L, (STEP_SLABS + 1) * L, 12, rise, run) for L in SLOPE_RADII}
+    rects = {L: (max(x0 - L, 0), max(y0 - L, 0), min(x0 + w + L, gcfg["width"]) - max(x0 - L, 0), min(y0 + h + L, gcfg["height"]) - max(y0 - L, 0)) for L in SLOPE_RADII}
+    t = {"traversability_full_ms_this": [], "to_grid_ms_this": []}
+    for who in raws:
+        t["traversability_full_ms_" + who], t["to_grid_ms_" + who] = [], []
+    for L in SLOPE_RADII:
+        for what in ("slope_full", "slope_window", "slope_full_with_ground_fit_and_counts", "to_grid_slope"):
+            t["%s_ms_L%d" % (what, L)] = []
+    results = {}
+    for r in range(rounds + 3):  # (the first three rounds warm)
+        now = {}
+        now["traversability_full_ms_this"], plain = timed(lambda: layer.traversability(STEP_SLABS, ROBOT_SLABS))
+        now["to_grid_ms_this"], _ = timed(lambda: layer.to_grid(other, STEP_SLABS, ROBOT_SLABS))
+        for who, raw in raws.items():
+            now["traversability_full_ms_" + who], theirs = timed(raw.traversability)
+            now["to_grid_ms_" + who], _ = timed(raw.to_grid)
+            assert np.array_equal(theirs, plain)  # every build computes the same
+        for L in SLOPE_RADII:
+            now["slope_full_ms_L%d" % L], full = timed(lambda: layer.traversability_slope(STEP_SLABS, ROBOT_SLABS, slopes[L]))
+            now["slope_window_ms_L%d" % L], part = timed(lambda: layer.traversability_slope(STEP_SLABS, ROBOT_SLABS, slopes[L], rect=rects[L]))
+            now["slope_full_with_ground_fit_and_counts_ms_L%d" % L], counted = timed(
+                lambda: layer.traversability_slope(STEP_SLABS, ROBOT_SLABS, slopes[L], return_ground=True, return_fit=True, return_counts=True))
+            now["to_grid_slope_ms_L%d" % L], _ = timed(lambda: layer.to_grid_slope(other, STEP_SLABS, ROBOT_SLABS, slopes[L]))
+            rx, ry, rw, rh = rects[L]
+            assert np.array_equal(part, full[ry:ry + rh, rx:rx + rw]) and np.array_equal(counted[0], full) and np.array_equal(other.occupancy(1), full)
+            assert np.array_equal(full[full != plain], np.full(int((full != plain).sum()), 100, dtype=np.int8)) and counted[3][4] == int((full != plain).sum())
+            results[L] = counted[3]
+        if r >= 3:
+            for key, ms in now.items():
+                t[key].append(ms)
+    row = {"scene": name, "points": len(frame), "cell_m": 0.05, "slab_m": SLAB, "layer_cells": [gcfg["width"], gcfg["height"]], "step_slabs": STEP_SLABS, "robot_slabs": ROBOT_SLABS,
+           "slope_configs_L_K_min_rise_run": [list(slopes[L]) for L in SLOPE_RADII], "windows_grown_by_L": [list(rects[L]) for L in SLOPE_RADII],
+           "unknown_traversable_body_step_slope": {"L%d" % L: list(results[L]) for L in SLOPE_RADII}}
+    row.update({key: spread(v) for key, v in t.items()})
+    return [row]
+
+
 def pipeline_rows(rounds, n_frames, contenders, carve=False):
     import test_elev_facade
     import test_elev_carve_facade
@@ -262,6 +356,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rounds", type=int, default=30)
     ap.add_argument("--carve", action="store_true")
+    ap.add_argument("--slope", action="store_true")
     ap.add_argument("--ab", action="append", default=[], metavar="NAME=LIB")
     ap.add_argument("--pipeline", action="store_true")
     ap.add_argument("--pipeline-rounds", type=int, default=3)
@@ -272,7 +367,9 @@ def main():
     if bind:
         bind()
     libs = {spec.split("=", 1)[0]: load_contender(spec.split("=", 1)[1]) for spec in a.ab}
-    if a.carve:
+    if a.slope:
+        res = {"caller_process": where, "rounds": a.rounds, "slope": slope_rows(a.rounds, libs)}
+    elif a.carve:
         res = {"caller_process": where, "rounds": a.rounds, "carve": carve_rows(a.rounds, libs)}
     else:
         res = {"caller_process": where, "rounds": a.rounds, "integrate": integrate_rows(a.rounds, libs), "traversability": traversability_rows(a.rounds)}
