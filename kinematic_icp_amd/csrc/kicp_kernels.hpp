@@ -1074,13 +1074,36 @@ __device__ __forceinline__ void best3_assign_fresh(Best3 &t, const Best3 &o) {
 // PointToVoxel component: static_cast<int>(floor(c / vs)) as the reference evaluates it (kiss-icp v1.2.0 core/VoxelUtils.hpp),
 // without paying an fp64 division for every coordinate: t = c * (1 / vs) agrees with fl(c / vs) to a few ulps, so the two
 // floors can only differ when t lies within that distance of an integer - and only then is the division carried out.
-__device__ __forceinline__ int32_t voxel_coord(double c, double vs, double inv_vs) {
+// "A few ulps" of t is below 4e-16 |t|, which is below 8.6e-7 for every |t| < 2^31 (beyond that the conversion to int32 is out of
+// range on either path), so ONE constant guard serves all of them: the fast path is trusted while frac = t - floor(t) lies in
+// [G, 1 - G], G = 1e-6 - an addition and a compare with |.| where a guard relative to |t| took five fp64 instructions per axis.  The
+// division runs for 2e-6 of the coordinates instead of 1e-10 and yields the same integer wherever both paths are valid.
+// voxel_coord_offset also hands back the query's offset inside that voxel in mirror units (Probe::lx ..), in [0, 65536).  On the fast
+// path frac IS the offset in voxel sizes: one conversion and one fp32 product (frac <= 1 - 1e-6 keeps it below 65536) where
+// (c - v vs) upm took five fp64 instructions.  Where the division decided, the offset is formed from the division's voxel, as before,
+// and held to the range: that voxel is the reference's, and a coordinate within an ulp of a face can lie 1e-10 units outside it.
+constexpr double kVoxelGuard = 1.0e-6;
+constexpr float kCell = 65536.f;  // one voxel in mirror units
+KICP_HD bool voxel_frac_is_safe(double frac) { return !(fabs(frac - 0.5) > 0.5 - kVoxelGuard); }
+KICP_HD int32_t voxel_coord(double c, double vs, double inv_vs) {
+    const double t = c * inv_vs;
+    const double f = floor(t);
+    if (__builtin_expect(!voxel_frac_is_safe(t - f), 0)) return static_cast<int32_t>(floor(c / vs));
+    return static_cast<int32_t>(f);
+}
+struct VoxelCoord {
+    int32_t v;
+    float off;
+};
+KICP_HD VoxelCoord voxel_coord_offset(double c, double vs, double inv_vs, double upm) {
     const double t = c * inv_vs;
     const double f = floor(t);
     const double frac = t - f;
-    const double guard = 4.0e-16 * fabs(t) + 1.0e-300;
-    if (__builtin_expect(frac < guard || 1.0 - frac < guard, 0)) return static_cast<int32_t>(floor(c / vs));
-    return static_cast<int32_t>(f);
+    if (__builtin_expect(!voxel_frac_is_safe(frac), 0)) {
+        const int32_t v = static_cast<int32_t>(floor(c / vs));
+        return VoxelCoord{v, fminf(fmaxf(static_cast<float>((c - v * vs) * upm), 0.f), 65535.99609375f)};
+    }
+    return VoxelCoord{static_cast<int32_t>(f), static_cast<float>(frac) * kCell};
 }
 
 // What a bucket visit needs to know about the query it serves (a lane may visit on behalf of another lane's query).
@@ -1095,7 +1118,6 @@ struct Lane {
     uint32_t todo;  // neighbour voxels still to visit (bit s = shift s of the reference's order)
     Best3 t;
 };
-constexpr float kCell = 65536.f;  // one voxel in mirror units
 
 // the transformed point T * source[i] and its voxel (PointToVoxel); recomputed where needed rather than kept in registers
 // (`kept`: the latency-oriented build has the registers to keep the query and the two source coordinates the Jacobian needs
@@ -1106,14 +1128,23 @@ struct KeptQuery {
     bool voxel;  // q.vx .. q.vz are valid (a query parked in LDS comes back without them: only the rare exact search needs them)
 };
 // (`src`: the scan's points - p.src, or the scan a resident kernel was told to take up next, kicp_small.hpp)
-__device__ __forceinline__ void make_query_of(Query &q, const PassParams &p, const double *__restrict__ src, const Pose &T, uint32_t i, KeptQuery *kept = nullptr) {
+// (`probe`: a search starts here - the offsets inside the voxel come with the voxel, voxel_coord_offset)
+__device__ __forceinline__ void make_query_of(Query &q, const PassParams &p, const double *__restrict__ src, const Pose &T, uint32_t i, KeptQuery *kept = nullptr,
+                                              Probe *probe = nullptr) {
     const double sx = src[3 * i], sy = src[3 * i + 1], sz = src[3 * i + 2];
     if (kept) kept->sx = sx, kept->sy = sy;
     double rx, ry, rz;
     quat_rotate(T, sx, sy, sz, rx, ry, rz);
     q.x = rx + T.tx, q.y = ry + T.ty, q.z = rz + T.tz;
     const double vs = p.map.voxel_size;
-    q.vx = voxel_coord(q.x, vs, p.search.inv_vs), q.vy = voxel_coord(q.y, vs, p.search.inv_vs), q.vz = voxel_coord(q.z, vs, p.search.inv_vs);
+    if (probe) {
+        const VoxelCoord x = voxel_coord_offset(q.x, vs, p.search.inv_vs, p.search.upm), y = voxel_coord_offset(q.y, vs, p.search.inv_vs, p.search.upm),
+                         z = voxel_coord_offset(q.z, vs, p.search.inv_vs, p.search.upm);
+        q.vx = x.v, q.vy = y.v, q.vz = z.v;
+        probe->lx = x.off, probe->ly = y.off, probe->lz = z.off;
+    } else {
+        q.vx = voxel_coord(q.x, vs, p.search.inv_vs), q.vy = voxel_coord(q.y, vs, p.search.inv_vs), q.vz = voxel_coord(q.z, vs, p.search.inv_vs);
+    }
 }
 // Everything the search does is in MIRROR UNITS (voxel_size / 65536) until the exact phase.  Error model (units): a mirror
 // coordinate is within 1.0 of the true offset (rounding 0.5; 1.0 where the top of the range is clamped), the query offset and
@@ -1121,6 +1152,9 @@ __device__ __forceinline__ void make_query_of(Query &q, const PassParams &p, con
 // plus 4.2e-6 D for the fp32 squares / sums and the 5 mantissa bits dropped for the integer tournament.  sp.margin_u covers
 // the errors of BOTH candidates of a decision with 10 % to spare, for D up to the acceptance bound (and never farther than
 // the 27-voxel neighbourhood reaches, D <= 12 voxel sizes^2): computed on the host (search_params()).
+// The query offset is frac = t - floor(t) of t = c (1 / vs), times 65536 (voxel_coord_offset): t carries two roundings, 2.2e-16 |t|,
+// which is <= 1.5e-5 units for |t| <= 2^20 (the subtraction is exact), and the conversion to fp32 with its product <= 0.004 (half
+// an ulp of a number < 2^16; so is the clamp of the division's branch) - together well inside the 0.05 above.
 template <bool OWN_VAL>
 __device__ __forceinline__ void start_lane(Lane &L, const PassParams &p, const double *__restrict__ src, const Pose &T, uint32_t i, bool valid, uint32_t &own_val,
                                            KeptQuery *kept = nullptr) {  // OWN_VAL: the caller wants the probe's `own_val`
@@ -1129,11 +1163,8 @@ __device__ __forceinline__ void start_lane(Lane &L, const PassParams &p, const d
     L.q.slot0 = 0u, L.todo = 0u;
     L.t = Best3{sp.bound_u, sp.bound_u, sp.bound_u, kNoIndex32, kNoIndex32, 0u, 0u};
     Query q;
-    make_query_of(q, p, src, T, valid ? i : 0u, kept);
+    make_query_of(q, p, src, T, valid ? i : 0u, kept, &L.q);
     if (kept) kept->q = q, kept->voxel = true;
-    const double vs = p.map.voxel_size;
-    L.q.lx = static_cast<float>((q.x - q.vx * vs) * sp.upm), L.q.ly = static_cast<float>((q.y - q.vy * vs) * sp.upm),
-    L.q.lz = static_cast<float>((q.z - q.vz * vs) * sp.upm);
     // ONE probe at the own voxel: the occupancy mask of the 27 neighbours (bit s = shift s of the reference's order) and
     // the record of their buckets.  Only voxels that hold points are ever visited; empty space costs nothing.
     // (`own_val`: the entry's own bucket value, for a first round that visits the own voxel straight from the probe - visit_first)
@@ -1243,6 +1274,8 @@ __device__ __forceinline__ bool process_trip(const uint4 (&c)[N / 2], uint32_t p
     return more;
 }
 // the query as seen from the corner of neighbour voxel `s`, both lanes of the packed arithmetic
+// (Reading the 27 triples shift x 65536 from a table in device memory - one 16-byte load per lane beside the load of nb[s] - takes 31
+// VALU instructions per wave and block out of this and was SLOWER by the clock, cfg5 + 2.3 %: profiles/lane_start_ab.txt.  Not kept.)
 struct QueryFrom {
     v2f x, y, z;
 };
@@ -1535,13 +1568,14 @@ __device__ __forceinline__ void gather32_pass(const PassParams &p, const Pose &T
             bool helps = false;
             int jobs = 0, job0 = 0, slot = 0;
             if (rounds > 1u) {
-                const int spare = min(2, __popc(L.todo));
+                // (every minimum of this round between operands cast to `int`: mixed int / unsigned arguments pick min(double, double))
+                const int spare = min(2, static_cast<int>(__popc(L.todo)));
                 const unsigned long long give1 = __ballot(spare >= 1), give2 = __ballot(spare >= 2), idle = __ballot(!busy);
                 if (give1 != 0ull && idle != 0ull) {  // (wave-uniform)
                     const int lane = static_cast<int>(tid & 63u);
                     const unsigned long long below = (1ull << lane) - 1ull;
                     job0 = __popcll(give1 & below) + __popcll(give2 & below);
-                    const int pairs = min(min(__popcll(give1) + __popcll(give2), __popcll(idle)), kLendJobs);
+                    const int pairs = min(min(static_cast<int>(__popcll(give1) + __popcll(give2)), static_cast<int>(__popcll(idle))), kLendJobs);
                     slot = __popcll(idle & below);
                     helps = !busy && slot < pairs;
                     jobs = max(0, min(spare, pairs - job0));
