@@ -1147,7 +1147,7 @@ int kicp_pre_ingest(kicp_pre *pre, const void *data, size_t n_points, const kicp
  *                                                          handle -, the range cutoff, x y z and the per-beam field "stamps")
  *   then, on that cloud, what kicp_pre_ingest replaces: TimeStampHandler.cpp:42-52,57-106,121-128 (the FLOAT32 stamp branch, min /
  *   max, normalisation - including its 0/0 when every kept stamp is equal) and RosUtils.cpp:30-39 (float x y z widened to double).
- * laser_geometry is not part of the reference tree: its rules are RECALLED, all in one place (kicp_pre.hpp, laser_rules).
+ * laser_geometry is not part of the reference tree: its rules are RECALLED, all in one place (kicp_pre_ingest.hpp, laser_rules).
  * range_cutoff < 0 (what the node passes) means range_max.  Afterwards kicp_pre_ingested_count is the number of kept beams,
  * kicp_pre_ingested returns the projected cloud (has_stamps = 1 when a beam was kept), and kicp_pre_preprocess_ingested /
  * kicp_pre_frame_ingested work on it.  out_min/max_stamp: the kept beams' stamps in seconds (0 when none was kept).  A pending
@@ -1206,7 +1206,7 @@ int kicp_pre_frame_ingested(kicp_pre *pre, const double relative_motion_qt[7], c
 /* kicp_pre_frame / kicp_pre_frame_ingested with the returned frame as the PointCloud2 `data` the node publishes for it
  * (RosUtils.cpp:40-63 EigenToPointCloud2 of the frame, LidarOdometryServer.cpp:240-263 PublishClouds): out_frame_xyz receives
  * x y z FLOAT32 records, static_cast<float> of the fp64 frame's doubles - the GPU narrows them on the way out, so 12 bytes per
- * point cross PCIe (kicp_pre.hpp k_push_frame_f32).  out_frame_xyz may be NULL: then nothing is pushed at all (the node's "no
+ * point cross PCIe (kicp_pre_egress.hpp k_push_frame_f32).  out_frame_xyz may be NULL: then nothing is pushed at all (the node's "no
  * subscriber" case).  Otherwise collect it with kicp_pre_download_finish(pre, 0, NULL, 0, &n), as the fp64 entries' frame; the
  * first out_counts[0] records are the frame.  Buffer 2's host copy then holds records too: kicp_pre_download_f32(pre, 2, ...)
  * reads it; kicp_pre_download(pre, 2, ...) still returns the doubles (from HBM).  Everything else as the fp64 entries. */

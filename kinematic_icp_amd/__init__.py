@@ -1865,24 +1865,23 @@ class PreSteps:
         _check(lib().kicp_pre_ingested(self._h, xyz.ctypes.data_as(_dp), st.ctypes.data_as(_dp), n.value, C.byref(n), C.byref(has)))
         return xyz, (st if has.value else None)
 
-    def Frame(self, frame, timestamps, relative_motion, lidar_to_base, max_range, min_range, deskew, voxel_a, voxel_b, want_frame=True):
-        """kicp_pre_frame / kicp_pre_frame_ingested (frame=None: the ingested cloud): Preprocess + the two downsamples behind one
-        synchronisation.  Returns (counts, preprocessed frame or None)."""
+    def _frame(self, dtype, entry, entry_ingested, frame, timestamps, relative_motion, lidar_to_base, max_range, min_range, deskew, voxel_a, voxel_b, want_frame):
+        """Frame / FrameF32: the chained pre-steps through `entry` (or `entry_ingested`, frame=None), the preprocessed frame landing in
+        an (n, 3) array of `dtype`."""
         _, r = _d(relative_motion)
         _, e = _d(lidar_to_base)
         counts = (C.c_size_t * 3)()
+        f64 = dtype is np.float64
         if frame is None:
             n_in = lib().kicp_pre_ingested_count(self._h)
-            out = np.empty((n_in, 3), dtype=np.float64) if want_frame else None
-            rc = lib().kicp_pre_frame_ingested(self._h, r, e, max_range, min_range, int(deskew), voxel_a, voxel_b,
-                                               out.ctypes.data_as(_dp) if want_frame and n_in else None, n_in, counts)
         else:
             a, p = _d(frame)
             t, tp = _d(timestamps if timestamps is not None else np.zeros(0))
             n_in = a.size // 3
-            out = np.empty((n_in, 3), dtype=np.float64) if want_frame else None
-            rc = lib().kicp_pre_frame(self._h, p, n_in, tp, t.size, r, e, max_range, min_range, int(deskew), voxel_a, voxel_b,
-                                      out.ctypes.data_as(_dp) if want_frame and n_in else None, n_in, counts)
+        out = np.empty((n_in, 3), dtype=dtype) if want_frame else None
+        landing = (out.ctypes.data_as(_dp) if f64 else out.ctypes.data) if want_frame and n_in else None
+        tail = (r, e, max_range, min_range, int(deskew), voxel_a, voxel_b, landing, n_in, counts)
+        rc = entry_ingested(self._h, *tail) if frame is None else entry(self._h, p, n_in, tp, t.size, *tail)
         if rc < 0:
             message = lib().kicp_last_error().decode(errors="replace")
             if want_frame and n_in:  # the backend's helper thread may hold a pointer into `out`: collect (and drop) the download before the array can go
@@ -1890,41 +1889,23 @@ class PreSteps:
             raise KicpError(rc, message)
         self.last_status = rc
         if want_frame and n_in:
-            n = C.c_size_t()
-            _check(lib().kicp_pre_download_finish(self._h, 0, out.ctypes.data_as(_dp), n_in, C.byref(n)))
+            n = C.c_size_t()  # (FLOAT32 records land in `out` only: collected with NULL)
+            _check(lib().kicp_pre_download_finish(self._h, 0, landing if f64 else None, n_in if f64 else 0, C.byref(n)))
             out = out[:counts[0]]
         return [int(c) for c in counts], out
+
+    def Frame(self, frame, timestamps, relative_motion, lidar_to_base, max_range, min_range, deskew, voxel_a, voxel_b, want_frame=True):
+        """kicp_pre_frame / kicp_pre_frame_ingested (frame=None: the ingested cloud): Preprocess + the two downsamples behind one
+        synchronisation.  Returns (counts, preprocessed frame or None)."""
+        return self._frame(np.float64, lib().kicp_pre_frame, lib().kicp_pre_frame_ingested, frame, timestamps, relative_motion, lidar_to_base, max_range, min_range,
+                           deskew, voxel_a, voxel_b, want_frame)
 
     def FrameF32(self, frame, timestamps, relative_motion, lidar_to_base, max_range, min_range, deskew, voxel_a, voxel_b, want_frame=True):
         """kicp_pre_frame_f32 / kicp_pre_frame_ingested_f32: Frame() with the preprocessed frame returned as PointCloud2 records, (n, 3)
         float32 narrowed on the GPU (want_frame=False: nothing is pushed).  Returns (counts, records or None); download_f32(2) then
         reads the keypoints' records."""
-        _, r = _d(relative_motion)
-        _, e = _d(lidar_to_base)
-        counts = (C.c_size_t * 3)()
-        if frame is None:
-            n_in = lib().kicp_pre_ingested_count(self._h)
-            out = np.empty((n_in, 3), dtype=np.float32) if want_frame else None
-            rc = lib().kicp_pre_frame_ingested_f32(self._h, r, e, max_range, min_range, int(deskew), voxel_a, voxel_b,
-                                                   out.ctypes.data if want_frame and n_in else None, n_in, counts)
-        else:
-            a, p = _d(frame)
-            t, tp = _d(timestamps if timestamps is not None else np.zeros(0))
-            n_in = a.size // 3
-            out = np.empty((n_in, 3), dtype=np.float32) if want_frame else None
-            rc = lib().kicp_pre_frame_f32(self._h, p, n_in, tp, t.size, r, e, max_range, min_range, int(deskew), voxel_a, voxel_b,
-                                          out.ctypes.data if want_frame and n_in else None, n_in, counts)
-        if rc < 0:
-            message = lib().kicp_last_error().decode(errors="replace")
-            if want_frame and n_in:  # (as Frame: the helper thread may hold a pointer into `out`)
-                lib().kicp_pre_download_finish(self._h, 0, None, 0, None)
-            raise KicpError(rc, message)
-        self.last_status = rc
-        if want_frame and n_in:
-            n = C.c_size_t()
-            _check(lib().kicp_pre_download_finish(self._h, 0, None, 0, C.byref(n)))
-            out = out[:counts[0]]
-        return [int(c) for c in counts], out
+        return self._frame(np.float32, lib().kicp_pre_frame_f32, lib().kicp_pre_frame_ingested_f32, frame, timestamps, relative_motion, lidar_to_base, max_range,
+                           min_range, deskew, voxel_a, voxel_b, want_frame)
 
     def download_f32(self, buffer):
         """kicp_pre_download_f32: a buffer as PointCloud2 records, (n, 3) float32"""

@@ -15,9 +15,13 @@ namespace host {
 
 // (plain function on purpose: hipcc gave two namespace-scope initialiser lambdas of this shape the same closure symbol and
 // ran the first one's body for both)
-bool env_flag(const char *name) {
+bool env_flag(const char *name, bool fallback) {
     const char *e = std::getenv(name);
-    return e && *e && *e != '0';
+    return e && *e ? *e != '0' : fallback;
+}
+long env_int(const char *name, long fallback) {
+    const char *e = std::getenv(name);
+    return e && *e ? std::strtol(e, nullptr, 10) : fallback;
 }
 const bool g_trace = env_flag("KICP_TRACE");
 thread_local std::chrono::steady_clock::time_point g_trace_t0;

@@ -1,6 +1,6 @@
 // kicp_internal.hpp -- what the translation units behind include/kicp.h share: error handling, tracing, the staging
 // policy for caller memory, the HBM mirror of the voxel map and the handle behind kicp_map.  Host code only; the kernels
-// live in kicp_kernels.hpp (registration passes), kicp_mapdev.hpp (map maintenance) and kicp_pre.hpp (pre-steps), all with
+// live in kicp_kernels.hpp (registration passes), kicp_mapdev.hpp (map maintenance) and kicp_pre*.hpp (pre-steps), all with
 // internal linkage so that every translation unit may include what it launches.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -29,7 +29,9 @@ namespace kicp {
 namespace host {
 
 // KICP_TRACE=1 in the environment: every traced C-ABI call reports its wall time on stderr (debugging aid)
-bool env_flag(const char *name);
+// (`fallback`: what an unset or empty variable means; a set one is off when it begins with '0')
+bool env_flag(const char *name, bool fallback = false);
+long env_int(const char *name, long fallback);  // a tuning knob read as a decimal integer; unset or empty: `fallback`
 extern const bool g_trace;
 // KICP_ROCTX=1: the same calls open a roctx range (libroctx64, bound at run time), so that a rocprofv3 --marker-trace run shows
 // pre-steps, registration passes and map updates as named spans around their kernels

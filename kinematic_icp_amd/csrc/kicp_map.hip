@@ -4,7 +4,7 @@
 #include "kicp_internal.hpp"
 #include "kicp_kernels.hpp"
 #include "kicp_mapdev.hpp"
-#include "kicp_pre.hpp"  // k_scan_blocks
+#include "kicp_scan_blocks.hpp"  // k_scan_blocks
 
 using namespace kicp;
 using namespace kicp::host;

@@ -1,5 +1,5 @@
 // kicp_ordered_key.hpp -- the order-preserving map double -> uint64 (and back) through which the ingest kernels merge the stamps'
-// extrema as integers (kicp_pre.hpp k_ingest, k_ingest_scan; the host reads the result back with ordered_value, kicp_prestep.hip).
+// extrema as integers (kicp_pre_ingest.hpp k_ingest, k_ingest_scan; the host reads the result back with ordered_value, kicp_pre_ingest.hip).
 // -0.0 sorts below +0.0, the infinities sit at the ends, NaNs beyond them.  No HIP in here beyond the device's own bit cast, so
 // tests/cpp/ordered_key_test.cpp compiles this very file with g++ and checks both functions on the CPU.
 #pragma once

@@ -34,7 +34,7 @@ static void print_pose(const char *tag, const Sophus::SE3d &T) {
     printf("%s %.17g %.17g %.17g %.17g %.17g %.17g %.17g\n", tag, p[0], p[1], p[2], p[3], p[4], p[5], p[6]);
 }
 
-// laser_geometry's projector on the host, by the rules kicp_pre.hpp (laser_rules) states [RECALLED]: the cosine table cached while
+// laser_geometry's projector on the host, by the rules kicp_pre_ingest.hpp (laser_rules) states [RECALLED]: the cosine table cached while
 // n, angle_min and angle_max stay the same; the kept beams as x y z stamps FLOAT32 records
 struct HostProjector {
     std::vector<double> table;

@@ -2,7 +2,7 @@
 
 laser_geometry's LaserProjection::projectLaser_ (2.x), as the 2-D mode of the node calls it (online_node.cpp:44-58:
 projectLaser(*msg, cloud, -1.0, channel_option::Timestamp)).  laser_geometry is not part of the reference tree: the rules below
-are RECALLED, the same ones kicp_pre.hpp (laser_rules) states for the device:
+are RECALLED, the same ones kicp_pre_ingest.hpp (laser_rules) states for the device:
   - a cosine table C[i] = (cos a_i, sin a_i), libm double on a_i = angle_min + (float)i * angle_increment computed in float, cached
     per projector and rebuilt only when n, angle_min or angle_max changes (angle_increment is not part of the key);
   - range_cutoff < 0 -> (double)range_max; beam i kept iff r < range_cutoff (r widened to double) and r >= range_min (float);

@@ -1,6 +1,6 @@
 """The case table of the chained pre-steps' regime tests, shared by tests/test_prestep_cases.py (CPU: the premises of every case,
 from the oracle alone) and tests/test_gpu_presteps_regimes.py (GPU: kicp_pre.hpp k_frame_* / k_downsample_* / k_scan_blocks and
-kicp_prestep.hip pre_frame_chain).
+kicp_pre.hip pre_frame_chain).
 
 A frame case is an input cloud whose survivor counts are pinned by construction (the crop's and the first level's always, the
 second level's where a regime depends on it), so that the branch it is named after - a
@@ -9,7 +9,7 @@ deskew; survivors sit in the middle third of 0.5 m voxels of a slab 6 .. 36 m fr
 max_range = 50 and min_range = 1 in between, so no decision is borderline.  Duplicates of a voxel carry different coordinates (a
 downsample that kept another than the first one returns other numbers), and every cloud is shuffled.
 
-BUCKETS / tiles restate kicp_table_order.hpp reference_bucket_count and the tile rules of kicp_prestep.hip; the GPU tests assert
+BUCKETS / tiles restate kicp_table_order.hpp reference_bucket_count and the tile rules of kicp_pre.hip; the GPU tests assert
 them against the read-only counters of kicp_pre_get_option."""
 import functools
 
@@ -47,7 +47,7 @@ def table_tiles(n):
 
 
 def l2_workgroups(n_in, previous_n1):
-    """workgroups of the second level's launches (kicp_prestep.hip): a fresh handle (previous_n1 None) takes up to 1 024, a later
+    """workgroups of the second level's launches (kicp_pre.hip): a fresh handle (previous_n1 None) takes up to 1 024, a later
     frame twice the previous frame's second-table tiles (a frame without level-1 survivors counts as one tile), 32 at least"""
     sgrid = tiles(buckets(n_in))
     if previous_n1 is None:

@@ -1,4 +1,4 @@
-"""The PointCloud2 ingest on the GPU (kicp_pre.hpp k_ingest, kicp_prestep.hip ingest_run) in the regimes tests/test_ingest.py never
+"""The PointCloud2 ingest on the GPU (kicp_pre_ingest.hpp k_ingest, kicp_pre_ingest.hip ingest_run) in the regimes tests/test_ingest.py never
 enters: records longer than the 128 bytes that go through LDS (and 127, 128, 129), a point_step so long that every launch is one
 workgroup, the one-term neighbours of the `aligned` predicate, negative stamps, the nanosecond rule's boundary values and clouds that
 mix converting and non-converting stamps, full-range UINT32, extrema at tile and piece edges, in a one-record tail piece and in the

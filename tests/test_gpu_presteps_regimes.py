@@ -1,4 +1,4 @@
-"""The chained pre-steps on the GPU (kicp_pre.hpp k_frame_*, k_downsample_*, k_scan_blocks; kicp_prestep.hip pre_frame_chain) in
+"""The chained pre-steps on the GPU (kicp_pre.hpp k_frame_*, k_downsample_*, k_scan_blocks; kicp_pre.hip pre_frame_chain) in
 the regimes tests/test_gpu_presteps.py never provably enters: second-level launches whose workgroups walk several table tiles or
 find none, more point tiles than table tiles under a right guess and the reverse, tables of at most 512 buckets (the small path of
 replay_tile) at either level, survivor counts on a power-of-two bracket edge with the guess on either side of it, a hopeless guess
