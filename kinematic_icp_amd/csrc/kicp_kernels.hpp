@@ -11,10 +11,10 @@
 //                      (Removed after losing every A/B: round 1's variants with the neighbourhoods staged in LDS per wave, and - in
 //                      round 6 - the plain fp64 gather that served as the ablation's baseline; k_closest still runs the plain
 //                      fp64 search, search_global, which is also the exact fallback of the mirror search.)
-//   finish_pass : wave / workgroup reduction of the exact sums, then either tagged rows for the host (default: the host
-//                 adds the rows of the first-level groups and solves, Registration.cpp:119-125,159-167,181-184) or the
-//                 full device-side tree whose last workgroup solves on one lane (host_solve = 0) / leaves the totals
-//                 for an all-reduce (RCCL and callback modes).
+//   finish_pass : wave / workgroup reduction of the exact sums, then one of the four hand-offs (HandOff): tagged rows of the
+//                 first-level groups for the host (default), the launch's totals left on the device for a collective or a
+//                 publishing kernel, or the exchange over peer mailboxes.  The HOST adds what it gets and solves
+//                 (Registration.cpp:119-125,159-167,181-184; HostLoop::step): no kernel solves or updates a pose.
 //   k_closest   : GetClosestNeighbor for a batch of queries (API parity / tests).
 //
 // Roofline: gather + reduction, ~0.02 flop/B -> memory bound, no MFMA.
@@ -32,94 +32,88 @@
 
 namespace kicp {
 
-constexpr int kMaxLog = 32;
 constexpr int kNumSums = 7;           // JTJ00 JTJ01 JTJ11 JTr0 JTr1 ssq count
 constexpr int kNumLimbs = 3 * kNumSums;
 constexpr int kReduceWords = 24;      // all-reduce payload: 21 limb sums + padding (int64)
 constexpr double kFixScale = 1099511627776.0;  // 2^40
 constexpr double kFixLimit = 8796093022208.0;  // 2^43: |term| must stay below this (source points within ~2900 km of the base frame)
 
-// Result record in host-mapped pinned memory: written by the finalising lane, polled by the host.
+// Result record in host-mapped pinned memory, polled by the host: the totals of a pass that does not hand over group rows.
 struct HostRecord {
-    unsigned long long seq;  // (call_id << 16) | (done << 15) | completed iterations; written last, system-scope release
-    int32_t done, iter, converged, nan_flag;
-    Pose T;
-    double beta;
-    double log_ncorr[kMaxLog];
-    double log_sums[kMaxLog][6];
-    double log_dx[kMaxLog][2];
-    double sums[kNumSums];  // last pass, for kicp_pass_sums
-    uint32_t reserved[4];
-    long long words[kReduceWords];  // limb totals of the last pass (host-side solve / kicp_pass_words)
+    unsigned long long seq;  // (call id << 16) | (0x8000: kicp_pass_sums) | passes completed; written last, behind the payload
+    double sums[kNumSums];   // k_publish_sums, for kicp_pass_sums
+    uint32_t gave_up;        // set by a resident workgroup that left without a command: counts of a round that never completed may be
+                             // left in the groups' accumulators (clear_stale_tickets)
+    long long words[kReduceWords];  // limb totals of the last pass (k_publish_words, the peer hand-offs)
 };
 
-// Device-resident loop state of one ComputeRobotMotion call.
+// What a handle keeps on the device between the kernels of a pass.  (At least 24 bytes, whatever is in them: an empty scan's idle
+// lanes read "point 0" out of this block - flight_launch, run_batch_resident.)
 struct IcpState {
-    Pose T;  // current_estimate
-    double beta;
-    int32_t done, iter, converged, nan_flag;
-    unsigned int reserved_;
-    long long reduce[kReduceWords];      // limb sums of the running pass (multi-GPU: all-reduced in place)
-    unsigned int pad_[32];
+    long long reduce[kReduceWords];      // limb totals of the last pass (HandOff::Totals; multi-GPU: all-reduced in place)
+    unsigned int pad_[16];
     unsigned int ticket;                 // second-level arrival counter (own cache line)
     unsigned int pad2_[31];
 };
+static_assert(sizeof(IcpState) >= 24 && offsetof(IcpState, ticket) % 128 == 0 && sizeof(IcpState) - offsetof(IcpState, ticket) == 128, "see above");
 
 // What the per-correspondence terms need of the pose (Registration.cpp:86-93,108-113), the same for every
 // correspondence of a pass: J.col(0) = R UnitX = c0 and J.col(1) = R (-s.y, s.x, 0) = -s.y c0 + s.x c1 with c1 = R UnitY, and the
 // fixed-point term of JTJ(0,0) = |c0|^2, which every correspondence adds unchanged.  Computed ONCE per pass - by the host, next to
-// the pose it sends (set_pose), or by the kernel where the pose comes from the device (device-side solve, resident kernels) - by
-// this one function, so that every kernel and the host see the same doubles.
+// the pose it sends (set_pose), or by the kernel where the pose comes from the device (resident kernels: the command line; pose
+// lists) - by this one function, so that every kernel and the host see the same doubles.
 struct PassBasis {
     double c0x, c0y, c0z, c1x, c1y, c1z;
     int jtj00[4];  // to_fixed(|c0|^2): four signed 21-bit limbs (= 2^40 exactly for any unit quaternion)
 };
+// How a pass hands its exact sums on (finish_pass).  The host adds what it gets and solves; the pose of EVERY launched pass is the
+// host's and travels in the kernel arguments (pose0, basis) - resident kernels take later poses from their command line.
+// (The values are the ones finish_pass has always compared against, so that its code stays instruction for instruction what
+// it was: profiles/solve_residue_census.txt.  Every launch sets the member; a zero-initialised PassParams names no hand-off.)
+enum class HandOff : int32_t {
+    // Default (single GPU, shared segment, job lists): the reduction stops at the first-level groups of kGroup workgroups, whose
+    // tagged rows go straight to the host (pub_rows), which adds them - two dependent device-scope round trips instead of six.
+    // (Sending every workgroup's row was tried and is far slower: writes into host memory cost ~130 ns per transaction.)
+    GroupRows = 4,
+    // Two reduction levels; the last workgroup of the launch leaves the limb totals in st->reduce for what follows on the stream: a
+    // collective (RCCL, caller's all-reduce) and k_publish_words, or k_publish_sums (kicp_pass_sums / kicp_pass_words).
+    Totals = 3,
+    // Peer mailboxes (multi-GPU without a collective library), launches of at most kP2pMaxGroups groups: the
+    // last workgroup of every first-level group writes the group's row - tagged - into slot `p2p_rank` of EVERY rank's mailbox
+    // (its own included; the peers' are IPC mappings of their HBM, reached over xGMI), and the last workgroup of group 0 adds ALL
+    // ranks' group rows, in rank and group order, as they arrive and hands the node-wide totals to its host (pub_words, pub_seq).
+    PeerGroupRows = 6,
+    // Peer mailboxes, larger launches: two reduction levels as for Totals, then the launch's total travels as a SINGLE row of the
+    // same format, so ranks on either side of the limit still pair up.
+    PeerSingleRow = 7,
+};
 struct SolveParams {
     Pose pose0;
     PassBasis basis;  // of pose0 (set_pose)
-    int32_t pass;
-    int32_t max_iterations;
-    double convergence_criterion;
-    int32_t adaptive;
-    double fixed_regularization;
-    int32_t mode;  // 0 = solve inside the pass kernel; 1 = leave the limb totals in st->reduce (multi-GPU: all-reduce follows);
-                   // 3 = as 1, but the pose of every pass comes from the kernel argument (host-side solve, multi-GPU);
-                   // 2 = publish the limb totals to the host record, the HOST solves (a CPU core does the ~2000 serial fp64
-                   //     instructions of the solve in 0.2 us, one GPU lane needs ~5 us);
-                   // 4 = as 2, but the reduction stops at the first-level groups: their tagged rows go to the host, which
-                   //     adds them (default: two dependent device-scope round trips instead of six).  Sending every
-                   //     workgroup's row was tried and is far slower: writes into host memory cost ~130 ns per transaction
-    unsigned long long call_id;
-    HostRecord *rec;  // device pointer to the host-mapped record
-    // mode 2 hand-off target (host-mapped memory: the handle's own record, or this rank's slot of the node-wide
-    // shared segment in multi-process mode): 24 limb words, then the sequence word set to pub_value
+    HandOff mode;
+    HostRecord *rec;  // device pointer to the host-mapped record (the small-scan kernels set its gave_up word)
+    // where the peer hand-offs put the node-wide totals (host-mapped memory: the handle's own record): 24 limb words, then the
+    // sequence word set to pub_value
     long long *pub_words;
     unsigned long long *pub_seq;
     unsigned long long pub_value;
-    // mode 4 hand-off (default single-GPU / shared-segment mode): every first-level group's row goes straight to the
-    // host, each word carrying the 16-bit tag of this pass; the host adds the rows as they arrive
+    // GroupRows: every first-level group's row, each word carrying the 16-bit tag of this pass; the host adds the rows as they arrive
     unsigned long long *pub_rows;  // host-mapped [groups][kReduceWords]
     uint32_t tag;                  // 1..65535, unique per pass within an epoch (the buffers are cleared when it wraps)
-    // mode 5: one-shot exchange over peer mappings (multi-GPU without a collective library).  The
-    // last workgroup of the launch writes this rank's totals - tagged - into slot `p2p_rank` of EVERY rank's mailbox (its
-    // own included; the peers' mailboxes are IPC mappings of their HBM, reached over xGMI), collects the p2p_nranks slots of
-    // its own mailbox, adds them in rank order and hands the node-wide totals to its host as in mode 2.
+    // the peer hand-offs
     unsigned long long *const *p2p_peers;  // device array [p2p_nranks]: every rank's mailbox as seen from this GPU
     int32_t p2p_nranks, p2p_rank;
     uint32_t p2p_tag;     // 1..65535 (step % 65535 + 1); double-buffered by p2p_parity, so a stale slot can never match
     uint32_t p2p_parity;  // step & 1
-    // mode 6: as 5 without the second reduction level - the last workgroup of every first-level group writes the group's row
-    // into every rank's mailbox itself, and the last workgroup of group 0 adds ALL ranks' group rows (its own rank's included,
-    // in rank and group order) as they arrive.  For launches of at most kP2pMaxGroups groups; a larger launch reduces on two
-    // levels as mode 5 does and sends its total as a single row (mode 7), so ranks on either side of the limit still pair up.
     long long p2p_timeout_ticks;  // 100 MHz ticks a rank waits for its peers' slots (derived from the host's KICP_WAIT_TIMEOUT_S)
 };
-// a rank's mailbox: [2 parities][nranks][kP2pWords] tagged words; a 64-bit total travels as two tagged 32-bit halves
+// a rank's mailbox: first [2 parities][nranks][kP2pWords] words that no kernel of this version touches (an earlier wire format's
+// totals as tagged halves; the area stays so that the rows below are where every build expects them)
 constexpr int kP2pWords = 2 * 24;
 constexpr int kP2pMaxRanks = 16;
-// ... followed by the area of mode 6: [2 parities][nranks][kP2pMaxGroups] rows of 24 tagged words (value << 16 | tag, like the
-// rows of mode 4) - the first-level GROUP rows of every rank, written by the groups' last workgroups themselves
-constexpr int kP2pMaxGroups = 32;  // <= 1024 workgroups per rank and launch; larger launches exchange totals (mode 5)
+// ... followed by the rows of the peer hand-offs: [2 parities][nranks][kP2pMaxGroups] rows of 24 tagged words (value << 16 | tag,
+// like the host's group rows) - the first-level GROUP rows of every rank, written by the groups' last workgroups themselves
+constexpr int kP2pMaxGroups = 32;  // <= 1024 workgroups per rank and launch; larger launches send their total as one row (PeerSingleRow)
 constexpr int kP2pCountWord = 23;  // word of a row that carries the sender's group count (padding in the single-GPU layout)
 KICP_HD size_t p2p_rows_offset(int nranks) { return 2 * static_cast<size_t>(nranks) * kP2pWords; }
 KICP_HD size_t p2p_box_words(int nranks) { return p2p_rows_offset(nranks) + 2 * static_cast<size_t>(nranks) * kP2pMaxGroups * 24; }
@@ -512,12 +506,12 @@ __device__ __forceinline__ void accumulate(PlanarAcc &a, const PassBasis &B, dou
 
 // (The solve + pose update - Registration.cpp:119-125, 159-167, 181-184 - is the host's: kicp_reg_internal.hpp HostLoop::step.  The device-side
 //  twin that round 1 to 5 carried - the launch's last workgroup solving on one lane - lost every A/B and went in round 6.)
-// Workgroup epilogue of every pass kernel: exact workgroup sum, then a last-arriver tree.  Default (mode 4): ONE level -
-// the last workgroup of every group of kGroup sends the group's row, tagged, to the host.  Other modes: two levels, the
+// Workgroup epilogue of every pass kernel: exact workgroup sum, then a last-arriver tree.  Default (HandOff::GroupRows): ONE level -
+// the last workgroup of every group of kGroup sends the group's row, tagged, to the host.  Totals, PeerSingleRow: two levels, the
 // last workgroup of the launch finishes the iteration.  Inter-workgroup traffic follows cdna_hip_programming.md
 // Guideline 16 (form R1): payload as 8-byte write-through (sc1) stores, ONE relaxed agent-scope ticket atomic per
 // workgroup, readers use sc1 loads; no fences, no same-line atomic fan-in (tickets live on separate 128-B lines).  The
-// two-level modes order payload before ticket with `s_waitcnt vmcnt(0)`; mode 4 needs no ordering (tags).
+// two-level hand-offs order payload before ticket with `s_waitcnt vmcnt(0)`; tagged rows need no ordering.
 constexpr int kGroup = 32;        // workgroups per first-level group
 constexpr int kTicketStride = 32; // uint32 words between group tickets (128 B)
 constexpr int kAccStride = 32;                // 64-bit words between the groups' counting accumulators (256 B: one memory channel)
@@ -549,7 +543,7 @@ __device__ __forceinline__ long long sum_rows(const unsigned long long *rows, ui
     return v + __shfl_down(v, kReduceWords, 64);
 }
 
-// mode 4: the same fold over tagged rows (word = value << 16 | tag).  Returns the sum of the values; `ok` tells whether
+// the same fold over tagged rows (word = value << 16 | tag).  Returns the sum of the values; `ok` tells whether
 // every word carried `tag`, i.e. whether every row had landed (the caller retries otherwise).
 __device__ __forceinline__ long long sum_rows_tagged(const unsigned long long *rows, uint32_t count, int lane, uint32_t tag, bool &ok) {
     long long v = 0;
@@ -572,7 +566,7 @@ __device__ __forceinline__ long long sum_rows_tagged(const unsigned long long *r
     return v + __shfl_down(v, kReduceWords, 64);
 }
 
-// mode 6, the last workgroup of group 0 (wave 0): add every rank's group rows out of this rank's mailbox.  Lanes r < nranks first
+// HandOff::PeerGroupRows and PeerSingleRow, the collecting workgroup (wave 0): add every rank's group rows out of this rank's mailbox.  Lanes r < nranks first
 // learn rank r's group count (word kP2pCountWord of its row 0); then all rows are fetched the way sum_rows_tagged does it - 48
 // lanes, 16 loads each in flight, 32 rows per round over the flattened (rank, group) index - and re-fetched until every word
 // carries the tag.  Returns the node-wide totals in lanes 0..23; lane kNumLimbs + 1 is set to 1 when a row did not arrive in time.
@@ -653,7 +647,7 @@ __device__ __forceinline__ int wave_sum_to_lane63(int v) {
     return v;
 }
 
-// `row_tag` (tagged-row modes): the tag of this pass - p.sol.tag for a kernel that runs one pass, tag0 + pass for the resident
+// `row_tag` (tagged rows): the tag of this pass - p.sol.tag for a kernel that runs one pass, tag0 + pass for the resident
 // kernel.  `gave_up` (resident kernel): this workgroup saw no command in time and hands over empty sums; the group row's flag
 // word counts such workgroups in its upper half (kGaveUpUnit each) so that the host repeats the pass in a fresh launch.
 constexpr unsigned long long kGaveUpUnit = 1ull << 16;
@@ -718,7 +712,7 @@ __device__ __forceinline__ void workgroup_row_words(const int (*s_red)[kWaveLimb
     }
 }
 
-// ROWS_ONLY: the caller only ever runs mode 4 (the resident kernel): none of the other hand-offs is compiled in.
+// ROWS_ONLY: the caller only ever hands over group rows (the resident kernel): none of the other hand-offs is compiled in.
 // `parity` (resident kernel: pass & 1): workgroup rows, tickets and the groups' host rows are double-buffered by pass parity, so
 // that what a workgroup writes for pass k + 1 - in particular the marked empty row of a workgroup that gave up waiting for the
 // command of pass k + 1 - can never land on a row of pass k that its reader (the group's last workgroup, the host) has not
@@ -733,14 +727,9 @@ __device__ __forceinline__ void finish_pass(Acc &a, const PassParams &p, int (*s
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     IcpState *st = p.st;
     if (!ROWS_ONLY && dbg_is(p, 8)) {  // ablation (tools/gpu_dbg.py): no reduction at all, workgroup 0 hands over zeros
-        if (p.sol.mode == 4 && wave == 0 && blockIdx.x % kGroup == 0 && lane < kReduceWords)
+        if (p.sol.mode == HandOff::GroupRows && wave == 0 && blockIdx.x % kGroup == 0 && lane < kReduceWords)
             __hip_atomic_store(p.sol.pub_rows + static_cast<size_t>(blockIdx.x / kGroup) * kReduceWords + lane, static_cast<unsigned long long>(p.sol.tag),
                                __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        if (blockIdx.x == 0 && wave == 0 && p.sol.mode == 2) {
-            if (lane < kReduceWords) __hip_atomic_store(p.sol.pub_words + lane, 0ll, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            if (lane == 0) __hip_atomic_store(p.sol.pub_seq, p.sol.pub_value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
         return;
     }
     // Every lane contributes at most ONE correspondence per tile and serves at most kMaxPassTiles of them, so each of its seven
@@ -816,9 +805,9 @@ __device__ __forceinline__ void finish_pass(Acc &a, const PassParams &p, int (*s
     range_error = (*s_flag & 2) ? 1 : 0;
     // wave 0 only from here.
     const uint32_t b = blockIdx.x, g = b / kGroup, ngroups = (nblocks + kGroup - 1) / kGroup;
-    // (an ordinary launch in mode 4 - round 5: the accumulators alternate with the pass tag's parity, the host's row of group g stays
+    // (an ordinary launch of HandOff::GroupRows - round 5: the accumulators alternate with the pass tag's parity, the host's row of group g stays
     //  where it was; dbg 14: round 4's rows -> ticket -> reload, for the in-process A/B)
-    const bool counting = ROWS_ONLY || (p.sol.mode == 4 && dbg_not(p, 14));
+    const bool counting = ROWS_ONLY || (p.sol.mode == HandOff::GroupRows && dbg_not(p, 14));
     if (!ROWS_ONLY && counting) parity = row_tag & 1u;
     if (counting) {  // lane i < 7: the three row words of sum i straight from the waves' limb sums
         long long l[3];
@@ -835,7 +824,7 @@ __device__ __forceinline__ void finish_pass(Acc &a, const PassParams &p, int (*s
     unsigned long long *const rows0 = p.partials + (ROWS_ONLY ? static_cast<size_t>(parity) * nblocks * kReduceWords : 0u);
     unsigned int *const tickets0 = p.tickets + (ROWS_ONLY ? static_cast<size_t>(parity) * ngroups * kTicketStride : 0u);
     unsigned long long *row = rows0 + static_cast<size_t>(b) * kReduceWords;
-    if (ROWS_ONLY || p.sol.mode == 4 || p.sol.mode == 6) {
+    if (ROWS_ONLY || p.sol.mode == HandOff::GroupRows || p.sol.mode == HandOff::PeerGroupRows) {
         // Tagged rows: no store acknowledgement is awaited anywhere.  The ticket only elects the group's reader; whether
         // a row has landed is visible in the row itself.  Values: limbs < 2^40 (the top limb is a small signed number
         // within the documented range), so value << 16 | tag fits a word, and so does the sum of a group's 32 rows.
@@ -868,13 +857,13 @@ __device__ __forceinline__ void finish_pass(Acc &a, const PassParams &p, int (*s
             } while (!__all(ok) && !lost);
             if (!__all(ok)) total = lane == kNumLimbs ? static_cast<long long>(kLostRowUnit) : 0ll;  // nothing of an incomplete sum is handed on
         }
-        if (ROWS_ONLY || p.sol.mode == 4) {
+        if (ROWS_ONLY || p.sol.mode == HandOff::GroupRows) {
             if (lane < kReduceWords)
                 __hip_atomic_store(p.sol.pub_rows + (static_cast<size_t>(ROWS_ONLY ? parity * ngroups : 0u) + g) * kReduceWords + lane,
                                    (static_cast<unsigned long long>(total) << 16) | tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
             return;
         }
-        // mode 6: the group's row goes into EVERY rank's mailbox (over xGMI for the peers'), tagged with the step
+        // PeerGroupRows: the group's row goes into EVERY rank's mailbox (over xGMI for the peers'), tagged with the step
         const SolveParams &f = p.sol;
         if (lane < kReduceWords) {
             const unsigned long long value = lane == kP2pCountWord ? static_cast<unsigned long long>(ngroups) : static_cast<unsigned long long>(total);
@@ -883,7 +872,7 @@ __device__ __forceinline__ void finish_pass(Acc &a, const PassParams &p, int (*s
             for (int r = 0; r < f.p2p_nranks; ++r) __hip_atomic_store(f.p2p_peers[r] + at, w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         }
         if (g != 0) return;
-        // group 0's last workgroup collects for this rank and hands the node-wide totals to its host (as mode 5 does)
+        // group 0's last workgroup collects for this rank and hands the node-wide totals to its host
         const long long all = p2p_collect_rows(f, lane);
         if (lane < kReduceWords) __hip_atomic_store(f.pub_words + lane, all, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -920,8 +909,8 @@ __device__ __forceinline__ void finish_pass(Acc &a, const PassParams &p, int (*s
             total += sum_rows(p.partials + (static_cast<size_t>(nblocks) + base) * kReduceWords, min(static_cast<uint32_t>(kGroup), ngroups - base), lane);
     }
     // ---- last workgroup of the launch ------------------------------------------------------------------------
-    if (p.sol.mode == 7) {
-        // Group rows are what the ranks exchange (mode 6), but this launch has more groups than a rank's share of the mailbox
+    if (p.sol.mode == HandOff::PeerSingleRow) {
+        // Group rows are what the ranks exchange (PeerGroupRows), but this launch has more groups than a rank's share of the mailbox
         // holds: its total travels as ONE row.  A row's words carry 48 bits, so the limb sums are brought back into limb range
         // first (lane 3i + j: limb j of sum i).
         const SolveParams &f = p.sol;
@@ -945,7 +934,7 @@ __device__ __forceinline__ void finish_pass(Acc &a, const PassParams &p, int (*s
         total = p2p_collect_rows(f, lane);
     }
     if (lane < kReduceWords) st->reduce[lane] = total;
-    if (p.sol.mode == 7) {  // hand the totals to the host: write-through stores, one wait, then the sequence word
+    if (p.sol.mode == HandOff::PeerSingleRow) {  // hand the totals to the host: write-through stores, one wait, then the sequence word
         if (lane < kReduceWords) __hip_atomic_store(p.sol.pub_words + lane, total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         if (lane == 0) __hip_atomic_store(p.sol.pub_seq, p.sol.pub_value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -958,11 +947,6 @@ __device__ __forceinline__ double uniform_d(double v) {
     const long long b = __double_as_longlong(v);
     const int lo = __builtin_amdgcn_readfirstlane(static_cast<int>(b)), hi = __builtin_amdgcn_readfirstlane(static_cast<int>(b >> 32));
     return __longlong_as_double((static_cast<long long>(hi) << 32) | static_cast<unsigned int>(lo));
-}
-__device__ __forceinline__ Pose load_pose(const PassParams &p) {
-    if (p.sol.pass == 0 || p.sol.mode >= 2) return p.sol.pose0;
-    const Pose T = p.st->T;
-    return Pose{uniform_d(T.qx), uniform_d(T.qy), uniform_d(T.qz), uniform_d(T.qw), uniform_d(T.tx), uniform_d(T.ty), uniform_d(T.tz)};
 }
 #define KICP_PASS_SHARED(BLOCK)                       \
     __shared__ int s_red[(BLOCK) / 64][kWaveLimbs];   \
@@ -1364,7 +1348,8 @@ __device__ __forceinline__ float voxel_lower_bound(const Probe &P, int s, float 
 // The kernel arguments as they lie in the kernarg segment, through an opaque copy of its address: what is read through this view is
 // fetched (scalar loads, scalar cache) WHERE it is used instead of being loaded at the kernel's start and kept in scalar registers
 // through the search - the pass kernels' sixteen words of basis pushed as many other values out into vector registers, and the
-// four-waves build spilled.  Every pass kernel's first (or only) argument is its PassParams, at offset 0.
+// four-waves build spilled.  Every pass kernel's first (or only) argument is its PassParams, at offset 0 (asserted next to SmallParams
+// and ScoreParams, whose first member it is).
 typedef const PassParams __attribute__((address_space(4))) *PassKernarg;
 __device__ __forceinline__ const PassParams &args_at_point_of_use() {
     PassKernarg q = (PassKernarg)__builtin_amdgcn_kernarg_segment_ptr();
@@ -1381,6 +1366,7 @@ struct JobsParams {
     uint32_t nblocks[kMaxJobs];
     PassParams job[kMaxJobs];
 };
+static_assert(offsetof(JobsParams, job) == kMaxJobs * sizeof(uint32_t), "job_args: the jobs follow the counts without padding");
 typedef const JobsParams __attribute__((address_space(4))) *JobsKernarg;
 __device__ __forceinline__ const PassParams &job_args(uint32_t job) {
     JobsKernarg q = (JobsKernarg)__builtin_amdgcn_kernarg_segment_ptr();
@@ -1393,7 +1379,9 @@ __device__ __forceinline__ const PassParams &job_args_at_point_of_use(uint32_t j
 }
 // exact resolution of a finished search: the winner (and whatever lies within the margin of it) re-evaluated in fp64, the
 // reference's tie rule, the acceptance test and the per-correspondence terms (Registration.cpp:74-77, 86-93)
-// `host_pose`: T is the host's pose (the kernel arguments carry its basis); otherwise the basis is formed here, from T
+// HOST_POSE: T is the host's pose and the kernel arguments carry its basis (the launched passes: k_pass_gather32, k_pass_gather32_jobs);
+// otherwise the kernel got T from the device (resident and small-scan kernels, the pose lists of k_score_poses / k_planar_poses) and the
+// basis is formed here, from T
 // EXPORT (kicp_pass_correspondences): the decision is also written out per query - index, squared distance, coordinates
 __device__ __forceinline__ void export_correspondence(const PassParams &p, uint32_t i, uint32_t idx, double d2, double x, double y, double z) {
     p.corr_index[i] = idx == kNoIndex32 ? -1 : static_cast<int32_t>(idx);
@@ -1404,8 +1392,8 @@ __device__ __forceinline__ void export_correspondence(const PassParams &p, uint3
 // correspondence differs (its squared residual and the count - no basis, no Jacobian terms)
 // ACC = PlanarAcc (k_planar_poses): likewise; the basis is formed here from T, as for a pass whose pose is the device's
 // JOBS: the kernel arguments are a list of jobs and this workgroup's are those of job blockIdx.y (k_pass_gather32_jobs)
-template <bool EXPORT = false, class ACC = Acc, bool JOBS = false>
-__device__ __forceinline__ void resolve_and_accumulate(ACC &acc, const PassParams &p, bool host_pose, const double *__restrict__ src, const Pose &T, uint32_t i,
+template <bool HOST_POSE, bool EXPORT = false, class ACC = Acc, bool JOBS = false>
+__device__ __forceinline__ void resolve_and_accumulate(ACC &acc, const PassParams &p, const double *__restrict__ src, const Pose &T, uint32_t i,
                                                        const Best3 &t, const KeptQuery *kept = nullptr) {
     if (EXPORT && i != kNoIndex32) export_correspondence(p, i, kNoIndex32, 0.0, 0.0, 0.0, 0.0);  // (overwritten below when the query has a correspondence)
     if (i == kNoIndex32 || t.i1 == kNoIndex32 || (kDbgBuild && p.dbg != 0 && p.dbg != 9 && p.dbg != 11 && p.dbg != 12 && p.dbg != 13 && p.dbg != 14)) return;
@@ -1455,12 +1443,14 @@ __device__ __forceinline__ void resolve_and_accumulate(ACC &acc, const PassParam
         } else if constexpr (ACC::kKind == AccKind::Planar) {
             accumulate(acc, basis_of(T), kept ? kept->sx : src[3 * i], kept ? kept->sy : src[3 * i + 1], q.x, q.y, q.z, wx, wy, wz);
         } else {
-            // The basis is taken up HERE - behind an opaque copy of the flag, so that the compiler cannot merge its two sources ahead of
-            // the exact phase and carry sixteen registers through it (the four-waves build spilled them) - and, where it is the host's,
-            // read from the kernarg segment here rather than at the kernel's start (args_at_point_of_use).
+            // The basis is taken up HERE, not carried through the search and the exact phase (sixteen registers: the four-waves build
+            // spilled them).  HOST_POSE: `from_args` is the constant 1 and the basis is read from the kernarg segment at this point
+            // rather than at the kernel's start (args_at_point_of_use).  Otherwise it is 0 behind an opaque scalar: the branch on it
+            // is never taken and is what keeps the compiler from forming basis_of(T) ahead of the exact phase (without it
+            // k_pass_small<256, 4, true> goes from 124 to 130 VGPRs and from four waves per SIMD to three).
             if (dbg_is(p, 13)) return;  // (attribution, tools/valu_attribution.sh: the exact phase without the terms)
-            int from_args = __builtin_amdgcn_readfirstlane(host_pose ? 1 : 0);
-            asm volatile("; the basis is taken up here" : "+s"(from_args));
+            int from_args = __builtin_amdgcn_readfirstlane(HOST_POSE ? 1 : 0);
+            if constexpr (!HOST_POSE) asm volatile("; the basis is taken up here" : "+s"(from_args));
             PassBasis B;
             if (from_args) B = JOBS ? job_args_at_point_of_use(blockIdx.y).sol.basis : args_at_point_of_use().sol.basis;
             else B = basis_of(T);
@@ -1485,10 +1475,10 @@ __device__ __forceinline__ void resolve_and_accumulate(ACC &acc, const PassParam
 // coordinates the terms need while it searches - that build has no registers to keep them (128 VGPRs) and used to transform the
 // source point a second time for the exact phase (~70 fp64 instructions and three loads per lane).
 constexpr int kParkWords = 5;
-// `host_pose`: T is the host's pose (kernel arguments) and p.sol.basis its basis; where the kernel got T from the device the basis
-// is formed right before the exact phase, not kept through the search.
-template <int BLOCK, int G, bool SPLIT, bool LAT, bool PARK = false, bool EXPORT = false, class ACC = Acc, bool JOBS = false>
-__device__ __forceinline__ void gather32_pass(const PassParams &p, const Pose &T, bool host_pose, uint32_t tid, ACC &acc, const double *__restrict__ src, uint32_t n,
+// HOST_POSE: T is the host's pose (kernel arguments) and p.sol.basis its basis; where the kernel got T from the device the basis
+// is formed right before the exact phase, not kept through the search (resolve_and_accumulate).
+template <bool HOST_POSE, int BLOCK, int G, bool SPLIT, bool LAT, bool PARK = false, bool EXPORT = false, class ACC = Acc, bool JOBS = false>
+__device__ __forceinline__ void gather32_pass(const PassParams &p, const Pose &T, uint32_t tid, ACC &acc, const double *__restrict__ src, uint32_t n,
                                               uint32_t block, int *lend = nullptr, double *park = nullptr) {
     const MapView &m = p.map;
     const float margin = p.search.margin_u;
@@ -1646,7 +1636,7 @@ __device__ __forceinline__ void gather32_pass(const PassParams &p, const Pose &T
         kept.sx = park[3 * BLOCK + tid], kept.sy = park[4 * BLOCK + tid], kept.voxel = false;
     }
     if (sub == 0) {
-        resolve_and_accumulate<EXPORT, ACC, JOBS>(acc, p, host_pose, src, T, L.i, L.t, (LAT || PARK) ? &kept : nullptr);
+        resolve_and_accumulate<HOST_POSE, EXPORT, ACC, JOBS>(acc, p, src, T, L.i, L.t, (LAT || PARK) ? &kept : nullptr);
     }
     // dbg 10 (bench.py's latency model): no correspondences are formed; the "count" sum carries the number of visiting rounds
     // this WAVE ran - its chain of dependent bucket visits - from lane 0 (as rounds x 2^40: limb 1 holds bits 21..41, limb 2 the rest)
@@ -1679,12 +1669,11 @@ __device__ __forceinline__ int pass_tiles_loop(Acc &acc, int (*lend)[kLendWords]
         // included): the arguments and the pose are re-read from the kernarg segment and the lane index is taken up afresh, so
         // that the compiler cannot hoist what depends on them out of the loop and hold it through the search.
         const PassParams &pt = JOBS ? job_args_at_point_of_use(blockIdx.y) : args_at_point_of_use();
-        const Pose T = JOBS ? pt.sol.pose0 : load_pose(pt);
-        const bool host_pose = JOBS || pt.sol.pass == 0 || pt.sol.mode >= 2;  // (load_pose)
+        const Pose T = pt.sol.pose0;
         uint32_t lane_id = tid;
         asm volatile("; a tile starts here" : "+v"(lane_id));
         Acc one{};
-        gather32_pass<BLOCK, 1, false, false, true, EXPORT, Acc, JOBS>(pt, T, host_pose, lane_id, one, pt.src, pt.n, block, &lend[lane_id / 64u][0], park);
+        gather32_pass<true, BLOCK, 1, false, false, true, EXPORT, Acc, JOBS>(pt, T, lane_id, one, pt.src, pt.n, block, &lend[lane_id / 64u][0], park);
         holders += __popcll(__ballot(one.limb[6 * kTermLimbs + 1] != 0));
         range_error |= one.range_error;
         // (all wave-uniform from here, and read where they are used: the job's or the launch's workgroups, the tiles of each, the scan's blocks)
@@ -1717,11 +1706,8 @@ __device__ __forceinline__ int pass_tiles_loop(Acc &acc, int (*lend)[kLendWords]
 template <bool JOBS>
 __device__ __forceinline__ void pass_jtj00(int (&jtj)[kTermLimbs]) {
     const PassParams &p = JOBS ? job_args_at_point_of_use(blockIdx.y) : args_at_point_of_use();
-    PassBasis B;
-    if (JOBS || p.sol.pass == 0 || p.sol.mode >= 2) B = p.sol.basis;  // (load_pose: the host's pose and its basis)
-    else B = basis_of(load_pose(p));
 #pragma unroll
-    for (int k = 0; k < kTermLimbs; ++k) jtj[k] = B.jtj00[k];
+    for (int k = 0; k < kTermLimbs; ++k) jtj[k] = p.sol.basis.jtj00[k];
 }
 template <int BLOCK, int G, int OCC, bool SPLIT, bool LAT = false, bool EXPORT = false>
 __global__ __launch_bounds__(BLOCK, OCC) void k_pass_gather32(const PassParams p) {
@@ -1741,15 +1727,13 @@ __global__ __launch_bounds__(BLOCK, OCC) void k_pass_gather32(const PassParams p
         const PassParams &pf = args_at_point_of_use();  // (not `p`: its loads would be issued ahead of the loop and held through it)
         finish_pass<BLOCK, false, true>(acc, pf, s_red, &s_flag, pf.sol.tag, 0, 0u, gridDim.x, holders, jtj);
     } else {
-        const Pose T = load_pose(p);
-        const bool host_pose = p.sol.pass == 0 || p.sol.mode >= 2;  // (load_pose)
-        gather32_pass<BLOCK, G, SPLIT, LAT, kLends, EXPORT>(p, T, host_pose, threadIdx.x, acc, p.src, p.n, blockIdx.x, nullptr, s_park);
+        gather32_pass<true, BLOCK, G, SPLIT, LAT, kLends, EXPORT>(p, p.sol.pose0, threadIdx.x, acc, p.src, p.n, blockIdx.x, nullptr, s_park);
         if (BLOCK > 64) __syncthreads();
         finish_pass<BLOCK>(acc, p, s_red, &s_flag, p.sol.tag);
     }
 }
 // the four-waves build with one lane per query, for a list of jobs (JobsParams): every job's pose is its host's and its rows go to
-// that host in mode 4, group by group, through the job's own accumulators.  A launch's grid is as wide as its largest job: the
+// that host as group rows (HandOff::GroupRows), group by group, through the job's own accumulators.  A launch's grid is as wide as its largest job: the
 // workgroups beyond a smaller job's end leave at once.
 template <int BLOCK, int G, int OCC>
 __global__ __launch_bounds__(BLOCK, OCC) void k_pass_gather32_jobs(const JobsParams) {

@@ -44,7 +44,7 @@ static __global__ __launch_bounds__(kScoreBlock, 3) void k_planar_poses(const Sc
         const double *__restrict__ pq = sp.poses + static_cast<size_t>(k) * 7;
         const Pose T{uniform_d(pq[0]), uniform_d(pq[1]), uniform_d(pq[2]), uniform_d(pq[3]), uniform_d(pq[4]), uniform_d(pq[5]), uniform_d(pq[6])};
         PlanarAcc acc{};
-        gather32_pass<kScoreBlock, 1, false, false, true, false, PlanarAcc>(p, T, false, threadIdx.x, acc, p.src, p.n, tile, &s_lend[wave][0], s_park);
+        gather32_pass<false, kScoreBlock, 1, false, false, true, false, PlanarAcc>(p, T, threadIdx.x, acc, p.src, p.n, tile, &s_lend[wave][0], s_park);
         const int hits = __popcll(__ballot(acc.hit != 0));
         if (hits) {  // (wave-uniform branch; 64 limbs of 21 bits: int32)
 #pragma unroll

@@ -93,12 +93,12 @@ int kicp_reg_create(const kicp_reg_config *config, int device, kicp_reg **out) {
         kicp_reg_destroy(r);
         return fail(KICP_ERR_HIP, std::string("kicp_reg_create: ") + (rc ? last_error() : hipGetErrorString(e)));
     }
-    if (const char *env = std::getenv("KICP_WAIT")) r->wait_mode = std::atoi(env);
-    if (const char *env = std::getenv("KICP_QUERY_EVERY")) r->query_every = std::atoi(env);
-    if (const char *env = std::getenv("KICP_SMALL")) r->use_small = std::atoi(env) != 0;
-    if (const char *env = std::getenv("KICP_SMALL_RESIDENT")) r->small_resident = std::atoi(env) != 0;
-    if (const char *env = std::getenv("KICP_SMALL_CMD")) r->small_cmd = std::atoi(env) != 0;
-    if (const char *env = std::getenv("KICP_P2P_ROWS")) r->p2p_rows = std::atoi(env) == 2 ? 2 : 1;  // (test hook: 2 = the one-row format launches of more than 32 groups use)
+    r->wait_mode = static_cast<int>(env_int("KICP_WAIT", r->wait_mode));
+    r->query_every = static_cast<int>(env_int("KICP_QUERY_EVERY", r->query_every));
+    r->use_small = env_int("KICP_SMALL", r->use_small) != 0;
+    r->small_resident = env_int("KICP_SMALL_RESIDENT", r->small_resident) != 0;
+    r->small_cmd = env_int("KICP_SMALL_CMD", r->small_cmd) != 0;
+    r->p2p_rows = env_int("KICP_P2P_ROWS", r->p2p_rows) == 2 ? 2 : 1;  // (test hook: 2 = the one-row format launches of more than 32 groups use)
     *out = r;
     return KICP_OK;
 }
@@ -497,10 +497,10 @@ static int pass_once(kicp_reg *reg, kicp_map *map, const double *frame_xyz, size
     const unsigned long long call_id = ++reg->call_id;
     PassParams pp{};
     pp.partials = reg->d_partials.get(), pp.tickets = reg->d_tickets.get();
-    pp.src = reg->d_frame.get(), pp.n = static_cast<uint32_t>(n), pp.map = map->mirror.view, pp.tau = max_correspondence_distance;
-    pp.st = reg->d_state.get(), pp.search = search_params(max_correspondence_distance, map->mirror.view.voxel_size);
+    fill_pass(pp, reg, map, reg->d_frame.get(), n, max_correspondence_distance, search_params(max_correspondence_distance, map->mirror.view.voxel_size));
+    pp.dbg = 0;  // (one plain pass whatever the handle's ablation switch says)
     set_pose(pp.sol, pose_from(pose_qt));
-    pp.sol.pass = 0, pp.sol.mode = 1, pp.sol.call_id = call_id, pp.sol.rec = reg->rec.dev();
+    pp.sol.mode = HandOff::Totals, pp.sol.rec = reg->rec.dev();
     if (int rc = launch_pass(reg, pp)) return rc;
     hipLaunchKernelGGL(k_publish_sums, dim3(1), dim3(64), 0, reg->stream, reg->d_state.get(), reg->rec.dev(), call_id);
     HIP_TRY(hipGetLastError());

@@ -102,11 +102,10 @@ int run_batch_resident(kicp_reg *r, kicp_map *map, size_t count, const double *c
     if (!wave) pl.generic = true, pl.lat = true, pl.g = 1, pl.block = 256, pl.grid = grid;
     SmallParams sp{};
     PassParams &pp = sp.p;
-    pp.src = n[0] ? d_frames[0] : reinterpret_cast<const double *>(r->d_state.get()), pp.n = static_cast<uint32_t>(n[0]), pp.map = map->mirror.view, pp.tau = tau, pp.st = r->d_state.get();
-    pp.search = search_params(tau, map->mirror.view.voxel_size);
-    pp.dbg = r->dbg;
-    pp.sol.max_iterations = max_it, pp.sol.convergence_criterion = r->cfg.convergence_criterion, pp.sol.mode = 4;
-    pp.partials = r->d_partials.get(), pp.tickets = r->d_tickets.get(), pp.group_acc = r->d_group_acc.get(), pp.sol.pub_rows = r->rows.dev(), pp.sol.call_id = ++r->call_id, pp.sol.rec = r->rec.dev();
+    // (an empty first scan: an idle lane still reads point 0)
+    fill_pass(pp, r, map, n[0] ? d_frames[0] : reinterpret_cast<const double *>(r->d_state.get()), n[0], tau, search_params(tau, map->mirror.view.voxel_size));
+    pp.sol.mode = HandOff::GroupRows;
+    pp.partials = r->d_partials.get(), pp.tickets = r->d_tickets.get(), pp.group_acc = r->d_group_acc.get(), pp.sol.pub_rows = r->rows.dev(), pp.sol.rec = r->rec.dev();
     sp.cmd = r->cmd.dev(), sp.rows = r->rows.dev(), sp.cmd_dev = r->d_cmd_copies, sp.relay = (r->small_cmd == 1 && r->cmd_bar) ? 0 : 1;
     sp.timeout_ticks = static_cast<long long>(std::max(50.0, r->small_timeout_us) * 100.0);
     sp.scans = r->d_scans;
@@ -183,7 +182,7 @@ int run_batch_resident(kicp_reg *r, kicp_map *map, size_t count, const double *c
                     if (slots[j].active) rest += static_cast<unsigned long long>(std::max(1, max_it - slots[j].loop.iter));
                 const uint32_t cnt = static_cast<uint32_t>(std::min<unsigned long long>(kBatchMaxPasses, rest));
                 if (int rc = next_tag_range(r, cnt, &sp.tag0)) return leave(rc);
-                set_pose(pp.sol, f.loop.T), pp.sol.pass = f.loop.iter;
+                set_pose(pp.sol, f.loop.T);
                 sp.max_passes = cnt, sp.seq_base = r->cmd_seq, sp.scan0 = static_cast<uint32_t>(f.k);
                 r->cmd_seq += cnt;
                 sp.trace = r->d_trace.get(), sp.trace_pass = r->trace_pass;
@@ -277,8 +276,7 @@ int host_cpu_budget() {
             if (q1 > 0 && p1 > 0) break;
         }
         cap(q1, p1);
-        if (const char *e = std::getenv("KICP_CPU_BUDGET"))  // (tests; a deployment that knows better)
-            if (std::atoi(e) > 0) cpus = std::atoi(e);
+        if (const long asked = env_int("KICP_CPU_BUDGET", 0); asked > 0) cpus = asked;  // (tests; a deployment that knows better)
         return static_cast<int>(std::max<long long>(1, std::min<long long>(cpus, 1 << 20)));
     }();
     return budget;

@@ -180,10 +180,11 @@ int kicp_reg_shm_init(kicp_reg *reg, int nranks, int rank, const char *name) {
     return KICP_OK;
 }
 // ---- one-shot exchange over peer mappings -----------------------------------------------------
-// Each rank owns a mailbox in its own HBM: [2 parities][nranks][kP2pWords] tagged words, fine-grained so that a peer's stores
+// Each rank owns a mailbox in its own HBM (layout: kicp_kernels.hpp, p2p_box_words), fine-grained so that a peer's stores
 // (over xGMI) become visible to a kernel that is polling it.  Export -> the caller gathers every rank's handle (any
-// transport: torch.distributed, MPI, a file) -> connect opens the peers' mailboxes -> every pass kernel's last workgroup
-// writes this rank's totals into all mailboxes and collects its own (mode 5, kicp_kernels.hpp::p2p_exchange).
+// transport: torch.distributed, MPI, a file) -> connect opens the peers' mailboxes -> every pass kernel writes this rank's
+// group rows (or its total as one row) into all mailboxes and collects its own (HandOff::PeerGroupRows / PeerSingleRow,
+// kicp_kernels.hpp::finish_pass, p2p_collect_rows).
 int kicp_reg_p2p_destroy(kicp_reg *reg) {
     if (!reg) return fail(KICP_ERR_ARG, "null argument");
     if (reg->p2p_box || reg->d_p2p_table) {
@@ -206,7 +207,7 @@ int kicp_reg_p2p_export(kicp_reg *reg, int nranks, int rank, char handle[KICP_P2
     if (reg->comm || reg->shm || reg->allreduce_fn) return fail(KICP_ERR_ARG, "another exchange is already attached");
     kicp_reg_p2p_destroy(reg);
     if (int rc = set_device(reg->device)) return rc;
-    const size_t bytes = p2p_box_words(nranks) * sizeof(unsigned long long);  // totals area (mode 5) + group-row area (mode 6)
+    const size_t bytes = p2p_box_words(nranks) * sizeof(unsigned long long);  // the unused first area + the rows of the peer hand-offs
     // fine-grained: stores arriving from a peer GPU must be visible to a wave that is polling (no stale L2 line)
     hipError_t e = hipExtMallocWithFlags(reinterpret_cast<void **>(&reg->p2p_box), bytes, hipDeviceMallocFinegrained);
     if (e != hipSuccess) {

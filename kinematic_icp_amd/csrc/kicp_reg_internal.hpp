@@ -97,7 +97,7 @@ struct kicp_reg {
     DevBuf<unsigned long long> d_group_acc;  // the resident kernels' group accumulators (finish_pass, ROWS_ONLY)
     bool acc_dirty = false;       // a resident launch was left before all its passes were collected: accumulators / tickets may hold partial counts
     size_t partial_blocks = 0;    // blocks the three serve (ensure_partials: zero while they are being replaced)
-    // mode 4 hand-off: tagged rows of the first-level groups in host-mapped pinned memory, added up by the host
+    // HandOff::GroupRows: tagged rows of the first-level groups in host-mapped pinned memory, added up by the host
     PinnedBuf<unsigned long long> rows;  // kReduceWords per group
     uint32_t tag = 0;       // tag of the last pass (1..65535)
     DevBuf<double> d_frame;     // device copy of host frames (3 doubles per point)
@@ -152,7 +152,7 @@ struct kicp_reg {
     // mailboxes as IPC mappings, and the table of all of them the pass kernel reads
     unsigned long long *p2p_box = nullptr;
     int p2p_rows = 1;  // peer mailboxes, wire format (the same on every rank): 1 the first-level group rows themselves - a launch of more than
-                       // kP2pMaxGroups groups sends its total as one row -, 2 always that single row, 0 the totals as tagged halves (round 2's)
+                       // kP2pMaxGroups groups sends its total as one row -, 2 always that single row
     void *p2p_mapped[kP2pMaxRanks] = {};
     unsigned long long **d_p2p_table = nullptr;
     unsigned long long p2p_step = 0;  // exchanges issued so far (same on every rank)
@@ -305,6 +305,8 @@ const AqlKernel *aql_kernel_for(kicp_reg *r, int b, int g, int occ, bool split, 
 const AqlKernel *aql_resident_kernel_for(kicp_reg *r, bool lat);
 const AqlKernel *aql_small_kernel_for(kicp_reg *r, int block, int g, bool wave);
 int aql_quiesce(kicp_reg *r);
+// what every pass shares, whoever launches it (`search`: search_params(tau, the map's voxel size)); the rest is the caller's
+void fill_pass(PassParams &pp, const kicp_reg *r, const kicp_map *map, const double *src, size_t n, double tau, const SearchParams &search);
 int launch_pass(kicp_reg *r, const PassParams &p, bool allow_aql = false);
 const AqlKernel *aql_jobs_kernel_for(kicp_reg *r);
 int launch_jobs(kicp_reg *r, const JobsParams &jp, uint32_t jobs, uint32_t grid_x);

@@ -6,7 +6,7 @@ using namespace kicp::host;
 
 namespace kicp {
 namespace host {
-// host twin of kicp::limbs_to_double (same operations, so host- and device-side solves see the same doubles)
+// host twin of kicp::limbs_to_double (same operations, so the host's solve and k_publish_sums see the same doubles)
 double host_limbs_to_double(const long long l[3]) {
     unsigned __int128 t = static_cast<unsigned __int128>(static_cast<__int128>(l[0]));
     t += static_cast<unsigned __int128>(static_cast<__int128>(l[1])) << 40;
@@ -106,6 +106,13 @@ int aql_quiesce(kicp_reg *r) {
     }
     return fail(KICP_ERR_HIP, "the AQL queue did not drain (KICP_WAIT_TIMEOUT_S)");
 }
+// What the passes of every path share: the scan, the map and its search numbers, the handle's state block, the ablation switch and the
+// export buffers (nullptr outside kicp_pass_correspondences).  Pose, hand-off, reduction buffers and tags are the caller's.
+void fill_pass(PassParams &pp, const kicp_reg *r, const kicp_map *map, const double *src, size_t n, double tau, const SearchParams &search) {
+    pp.src = src, pp.n = static_cast<uint32_t>(n), pp.map = map->mirror.view, pp.tau = tau, pp.search = search;
+    pp.st = r->d_state.get(), pp.dbg = r->dbg;
+    pp.corr_index = r->corr_index, pp.corr_d2 = r->corr_d2, pp.corr_nn = r->corr_nn;
+}
 // allow_aql: nothing on the handle's HIP stream has to be ordered behind this kernel and the host will poll for the result
 // The generic pass kernel comes in four builds, all of 256-thread workgroups (round 6: the 64 / 128 / 512-thread workgroups, the
 // three-waves register budget, the voxel-dealing pair of sub-lanes and the plain fp64 gather never won an A/B and are gone):
@@ -194,7 +201,7 @@ int ensure_partials(kicp_reg *r, size_t blocks) {
     r->partial_blocks = want;
     return KICP_OK;
 }
-// host-mapped rows of the first-level groups (mode 4)
+// host-mapped rows of the first-level groups (HandOff::GroupRows)
 int ensure_rows(kicp_reg *r, size_t groups) {
     if (groups <= r->rows.capacity() / kReduceWords) return KICP_OK;
     if (int rc = aql_quiesce(r)) return rc;
@@ -283,7 +290,7 @@ long long row_flags(long long w) {
     const unsigned long long u = static_cast<unsigned long long>(w);
     return static_cast<long long>(((u & 0xFFull) ? 1ull : 0ull) | (((u >> 8) & 0xFFull) ? kLostRowUnit : 0ull) | ((u >> 16) ? kGaveUpUnit : 0ull));
 }
-// mode 4: add the tagged rows of the `groups` first-level groups as they arrive (word = value << 16 | tag)
+// HandOff::GroupRows: add the tagged rows of the `groups` first-level groups as they arrive (word = value << 16 | tag)
 int wait_rows(kicp_reg *r, size_t groups, uint32_t tag, long long out_words[kReduceWords], size_t first_row) {
     for (int i = 0; i < kReduceWords; ++i) out_words[i] = 0;
     const unsigned query_every = r->query_every > 0 ? static_cast<unsigned>(r->query_every) : 64u;

@@ -119,13 +119,10 @@ int flight_launch(BatchFlight &f, const kicp_map *map, const double *d_frame, si
     for (auto &t : f.total) t = 0;
     PassParams &pp = f.small ? f.sp.p : f.pp;
     if (n == 0) d_frame = reinterpret_cast<const double *>(h->d_state.get());  // (an empty shard: the one workgroup's lanes are all idle, but an idle lane still reads point 0)
-    pp.src = d_frame, pp.n = static_cast<uint32_t>(n), pp.map = map->mirror.view, pp.tau = tau, pp.st = h->d_state.get();
-    pp.search = search_params(tau, map->mirror.view.voxel_size);
-    pp.dbg = h->dbg;
+    fill_pass(pp, h, map, d_frame, n, tau, search_params(tau, map->mirror.view.voxel_size));
     SolveParams &sol = pp.sol;
     set_pose(sol, f.loop.T);
-    sol.pass = f.loop.iter, sol.mode = 4, sol.max_iterations = h->cfg.max_num_iterations;
-    sol.convergence_criterion = h->cfg.convergence_criterion;
+    sol.mode = HandOff::GroupRows;
     f.own_rows = f.small && !grouped_rows(h, f.pl, false);
     if (f.small) {  // one wave per query / sub-lanes per query; the launch serves this pass only
         if (f.own_rows) {  // every workgroup's row goes straight to the host
@@ -155,16 +152,17 @@ int flight_launch(BatchFlight &f, const kicp_map *map, const double *d_frame, si
     if (int rc = ensure_rows(h, f.rows)) return rc;
     if (int rc = clear_stale_tickets(h)) return rc;  // (nothing to do unless an earlier call left a pass uncollected)
     pp.partials = h->d_partials.get(), pp.tickets = h->d_tickets.get(), pp.group_acc = h->d_group_acc.get();
-    sol.call_id = ++h->call_id, sol.rec = h->rec.dev(), sol.pub_rows = h->rows.dev();
+    sol.rec = h->rec.dev(), sol.pub_rows = h->rows.dev();
     if (int rc = next_tag(h, &sol.tag)) return rc;
     f.tag = sol.tag;
     f.since = Deadline();
     if (f.via_comm) {  // device-side tree -> all-reduce on the lane's communicator -> the totals to the host, all on the lane's stream
-        sol.mode = 3;
-        f.comm_seq = (sol.call_id << 16) | static_cast<unsigned long long>(f.loop.iter + 1);
+        sol.mode = HandOff::Totals;
+        const unsigned long long call_id = ++h->call_id;
+        f.comm_seq = (call_id << 16) | static_cast<unsigned long long>(f.loop.iter + 1);
         if (int rc = launch_pass(h, pp, false)) return rc;
         if (int rc = enqueue_allreduce(h)) return rc;
-        hipLaunchKernelGGL(k_publish_words, dim3(1), dim3(64), 0, h->stream, h->d_state.get(), h->rec.dev(), sol.call_id, f.loop.iter);
+        hipLaunchKernelGGL(k_publish_words, dim3(1), dim3(64), 0, h->stream, h->d_state.get(), h->rec.dev(), call_id, f.loop.iter);
         HIP_TRY(hipGetLastError());
         return KICP_OK;
     }
@@ -209,17 +207,15 @@ static int group_launch(kicp_reg *r, GroupLane &L, int group, size_t slot_groups
         GroupJob &j = L.jobs[s];
         PassParams &pp = L.jp.job[s];
         pp = PassParams{};
-        pp.src = d_frames[j.k], pp.n = static_cast<uint32_t>(n[j.k]), pp.map = map->mirror.view, pp.tau = tau, pp.st = h->d_state.get();
-        pp.search = search, pp.dbg = h->dbg;
-        // (mode 4 hands over through the job's counting accumulators only - the rows -> ticket -> reload hand-over, "dbg" 14, keeps a
+        fill_pass(pp, h, map, d_frames[j.k], n[j.k], tau, search);
+        // (a job's group rows leave through its counting accumulators only - the rows -> ticket -> reload hand-over, "dbg" 14, keeps a
         //  launch per scan - so a job has no workgroup rows and no tickets: a slot's share of them would not hold grid + groups rows)
         pp.partials = nullptr, pp.tickets = nullptr;
         pp.group_acc = h->d_group_acc.get() + s * 2 * slot_groups * kAccStride;
         SolveParams &sol = pp.sol;
         set_pose(sol, j.loop.T);
-        sol.pass = j.loop.iter, sol.mode = 4, sol.max_iterations = h->cfg.max_num_iterations;
-        sol.convergence_criterion = h->cfg.convergence_criterion;
-        sol.call_id = ++h->call_id, sol.rec = h->rec.dev(), sol.pub_rows = h->rows.dev() + s * slot_groups * kReduceWords;
+        sol.mode = HandOff::GroupRows;
+        sol.rec = h->rec.dev(), sol.pub_rows = h->rows.dev() + s * slot_groups * kReduceWords;
         sol.tag = j.tag = tag0 + static_cast<uint32_t>(s);
         pp.tiles = pass_tiles(h, n[j.k], true);  // (per job: a list may mix tile counts)
         const uint32_t grid = pass_grid(h, n[j.k], true);

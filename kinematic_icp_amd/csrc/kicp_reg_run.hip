@@ -14,12 +14,12 @@ namespace host {
 // or the host left a launch with passes still out: counts of a round that never completed - the call ended first - may be left
 // behind in the groups' accumulators (and tickets).  Clear them before they are counted into this call's passes.
 int clear_stale_tickets(kicp_reg *r) {
-    if ((__atomic_load_n(&r->rec.get()->reserved[0], __ATOMIC_RELAXED) == 0u && !r->acc_dirty) || !r->d_tickets.get()) return KICP_OK;
+    if ((__atomic_load_n(&r->rec.get()->gave_up, __ATOMIC_RELAXED) == 0u && !r->acc_dirty) || !r->d_tickets.get()) return KICP_OK;
     if (int rc = aql_quiesce(r)) return rc;
     r->stream_dirty = true;
     HIP_TRY(hipMemsetAsync(r->d_tickets.get(), 0, (r->partial_blocks / kGroup + 2) * kTicketStride * sizeof(unsigned int), r->stream));
     HIP_TRY(hipMemsetAsync(r->d_group_acc.get(), 0, 2 * (r->partial_blocks / kGroup + 2) * kAccStride * sizeof(unsigned long long), r->stream));
-    __atomic_store_n(&r->rec.get()->reserved[0], 0u, __ATOMIC_RELAXED);
+    __atomic_store_n(&r->rec.get()->gave_up, 0u, __ATOMIC_RELAXED);
     r->acc_dirty = false;
     return KICP_OK;
 }
@@ -42,12 +42,9 @@ int run_small(kicp_reg *r, kicp_map *map, const double *d_frame, size_t n, const
     if (int rc = ensure_cmd(r)) return rc;
     SmallParams sp{};
     PassParams &pp = sp.p;
-    pp.src = d_frame, pp.n = static_cast<uint32_t>(n), pp.map = map->mirror.view, pp.tau = tau, pp.st = r->d_state.get();
-    pp.search = search_params(tau, map->mirror.view.voxel_size);
-    pp.sol.max_iterations = max_it, pp.sol.convergence_criterion = r->cfg.convergence_criterion, pp.sol.mode = 4;
-    pp.dbg = r->dbg;  // (0, or 14: the in-process A/B switch of the plain launch's hand-over)
-    pp.corr_index = r->corr_index, pp.corr_d2 = r->corr_d2, pp.corr_nn = r->corr_nn;  // (kicp_pass_correspondences; nullptr otherwise)
-    if (grouped) pp.partials = r->d_partials.get(), pp.tickets = r->d_tickets.get(), pp.group_acc = r->d_group_acc.get(), pp.sol.pub_rows = r->rows.dev(), pp.sol.call_id = ++r->call_id, pp.sol.rec = r->rec.dev();
+    fill_pass(pp, r, map, d_frame, n, tau, search_params(tau, map->mirror.view.voxel_size));  // (dbg: 0, or 14 - the in-process A/B switch of the plain launch's hand-over)
+    pp.sol.mode = HandOff::GroupRows;
+    if (grouped) pp.partials = r->d_partials.get(), pp.tickets = r->d_tickets.get(), pp.group_acc = r->d_group_acc.get(), pp.sol.pub_rows = r->rows.dev(), pp.sol.rec = r->rec.dev();
     if (grouped)
         if (int rc = clear_stale_tickets(r)) return rc;
     sp.cmd = r->cmd.dev(), sp.rows = r->rows.dev(), sp.cmd_dev = r->d_cmd_copies, sp.relay = (r->small_cmd == 1 && r->cmd_bar) ? 0 : 1;
@@ -74,7 +71,7 @@ int run_small(kicp_reg *r, kicp_map *map, const double *d_frame, size_t n, const
         const bool stay = r->small_resident == 1 ? (loop.iter > 0 || r->small_prev_iters > 1) : r->small_resident != 0;
         const uint32_t cnt = stay ? std::min(left, kSmallMaxPasses) : 1u;
         if (int rc = next_tag_range(r, cnt, &sp.tag0)) return rc;
-        set_pose(pp.sol, loop.T), pp.sol.pass = loop.iter;
+        set_pose(pp.sol, loop.T);
         sp.max_passes = cnt, sp.seq_base = r->cmd_seq;
         r->cmd_seq += cnt;  // every sequence number this launch may wait for is now spent
         sp.trace = r->d_trace.get(), sp.trace_pass = r->trace_pass;
@@ -189,15 +186,10 @@ int run_registration_impl(kicp_reg *r, kicp_map *map, const double *d_frame, siz
     const unsigned long long call_id = ++r->call_id;
 
     PassParams pp{};
-    pp.src = d_frame, pp.n = static_cast<uint32_t>(n), pp.map = map->mirror.view, pp.tau = tau, pp.st = r->d_state.get();
-    pp.search = search_params(tau, map->mirror.view.voxel_size);
+    fill_pass(pp, r, map, d_frame, n, tau, search_params(tau, map->mirror.view.voxel_size));
     pp.partials = r->d_partials.get(), pp.tickets = r->d_tickets.get(), pp.group_acc = r->d_group_acc.get();
-    pp.dbg = r->dbg;
-    pp.corr_index = r->corr_index, pp.corr_d2 = r->corr_d2, pp.corr_nn = r->corr_nn;  // (kicp_pass_correspondences; nullptr otherwise)
     SolveParams &sp = pp.sol;
-    set_pose(sp, T0), sp.max_iterations = max_it, sp.convergence_criterion = r->cfg.convergence_criterion;
-    sp.adaptive = r->cfg.use_adaptive_odometry_regularization, sp.fixed_regularization = r->cfg.fixed_regularization;
-    sp.mode = multi ? 1 : 0, sp.call_id = call_id, sp.rec = r->rec.dev();
+    sp.rec = r->rec.dev();
 
     if (r->timing) HIP_TRY(hipEventRecord(r->ev0, r->stream));
     const bool pass_events = r->timing == 2;
@@ -206,8 +198,7 @@ int run_registration_impl(kicp_reg *r, kicp_map *map, const double *d_frame, siz
     unsigned long long seq = 0;
     {
         // ---- one launch per iteration, the pose travels as a kernel argument, the host solves (Registration.cpp:119-125,159-167,
-        //      181-184).  (Round 6: the device-side solve - last workgroup of the launch, stepped or queued up front - is gone: it
-        //      lost every A/B since round 2 and no exchange needs it.)
+        //      181-184)
         HostRecord *rec = r->rec.get();
         HostLoop loop;
         loop.T = T0;
@@ -221,7 +212,7 @@ int run_registration_impl(kicp_reg *r, kicp_map *map, const double *d_frame, siz
             // (every rank must use the same wire format - option "p2p_rows" - but may be on either side of the group limit)
             const bool p2p_rows = p2p && r->p2p_rows == 1 && groups <= static_cast<size_t>(kP2pMaxGroups);  // (2: always the single row - tests)
             set_pose(sp, loop.T);
-            sp.pass = it, sp.mode = multi ? 3 : (p2p ? (p2p_rows ? 6 : 7) : 4);
+            sp.mode = multi ? HandOff::Totals : (p2p ? (p2p_rows ? HandOff::PeerGroupRows : HandOff::PeerSingleRow) : HandOff::GroupRows);
             if (p2p) {  // every rank issues the same sequence of exchanges: the step number doubles as tag and buffer parity
                 const unsigned long long step = r->p2p_step++;
                 sp.p2p_peers = r->d_p2p_table, sp.p2p_nranks = r->nranks, sp.p2p_rank = r->rank;
@@ -244,7 +235,7 @@ int run_registration_impl(kicp_reg *r, kicp_map *map, const double *d_frame, siz
                 if (int rc = next_tag(r, &sp.tag)) return rc;
                 sp.pub_rows = r->rows.dev();
             } else if (p2p_rows) {
-                if (int rc = next_tag(r, &sp.tag)) return rc;  // (the workgroups' rows inside a group are tagged like mode 4's)
+                if (int rc = next_tag(r, &sp.tag)) return rc;  // (the workgroups' rows inside a group are tagged like the host's group rows)
             }
             const bool ev = pass_events && it < KICP_MAX_LOG_PASSES;
             if (ev) HIP_TRY(hipEventRecord(r->evp[2 * it], r->stream));

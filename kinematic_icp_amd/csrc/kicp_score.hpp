@@ -35,6 +35,7 @@ struct ScoreParams {
     uint32_t count;                // poses
     unsigned long long item0, items;  // this launch's share of the tiles x count items
 };
+static_assert(offsetof(ScoreParams, pass) == 0, "args_at_point_of_use reads the PassParams at offset 0 of the kernarg segment");
 
 static __global__ __launch_bounds__(kScoreBlock, 4) void k_score_poses(const ScoreParams sp) {
     constexpr int kWaves = kScoreBlock / 64;
@@ -50,7 +51,7 @@ static __global__ __launch_bounds__(kScoreBlock, 4) void k_score_poses(const Sco
         const double *__restrict__ pq = sp.poses + static_cast<size_t>(k) * 7;
         const Pose T{uniform_d(pq[0]), uniform_d(pq[1]), uniform_d(pq[2]), uniform_d(pq[3]), uniform_d(pq[4]), uniform_d(pq[5]), uniform_d(pq[6])};
         ScoreAcc acc{};
-        gather32_pass<kScoreBlock, 1, false, false, true, false, ScoreAcc>(p, T, false, threadIdx.x, acc, p.src, p.n, tile, &s_lend[wave][0], s_park);
+        gather32_pass<false, kScoreBlock, 1, false, false, true, false, ScoreAcc>(p, T, threadIdx.x, acc, p.src, p.n, tile, &s_lend[wave][0], s_park);
         const int hits = __popcll(__ballot(acc.hit != 0));
         int limb[kTermLimbs];
 #pragma unroll

@@ -1,5 +1,5 @@
 // kicp_se3.hpp -- the fp64 rigid-body algebra of the registration loop, usable from host code and from
-// gfx950 device code (the device-side solve/update kernel runs it on one lane).
+// gfx950 device code (the kernels that take a pose from the device form its basis with it).
 //
 // Mirrors what the reference gets from Sophus::SE3d / Eigen at these call sites:
 //   registration/Registration.cpp:156      last_robot_pose * relative_wheel_odometry

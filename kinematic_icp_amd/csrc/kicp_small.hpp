@@ -55,7 +55,7 @@ KICP_HD unsigned long long cmd_fold(const unsigned long long w[7]) {
 }
 
 struct SmallParams {
-    PassParams p;                   // (p.sol.mode is not used: the host always solves; p.partials / p.tickets unused)
+    PassParams p;                   // (p.sol.mode is not read: these kernels hand over rows only; p.partials / p.tickets unused)
     const unsigned long long *cmd;  // device view of the host-mapped command lines (kPipeSlots x kCmdWords words, 64-byte aligned)
     unsigned long long *cmd_dev;    // kCmdReplicas copies of the command lines in device memory (await_command)
     int32_t relay;                  // 1: workgroup 0 relays the host line into the copies; 0: the host writes the copies (BAR)
@@ -73,6 +73,7 @@ struct SmallParams {
     uint32_t scan0, trace_pass;     // (trace_pass: the pass of the launch that `trace` stamps)
                                     // the launch starts on scans[scan0]; later passes: the scan their command names.  nullptr: p.src / p.n
 };
+static_assert(offsetof(SmallParams, p) == 0, "fresh_args / args_at_point_of_use read the PassParams at offset 0 of the kernarg segment");
 
 // Between the passes of a resident kernel NOTHING but the pose, the pass counter and the lane id is worth a register: the
 // compiler would otherwise hoist every loop-invariant address and product out of the pass loop and keep it live through the
@@ -240,7 +241,7 @@ __global__ __launch_bounds__(BLOCK) void k_pass_small(const SmallParams /* read 
                 o.i1 = __shfl_xor(L.t.i1, off, 64), o.i2 = __shfl_xor(L.t.i2, off, 64), o.o1 = __shfl_xor(L.t.o1, off, 64), o.o2 = __shfl_xor(L.t.o2, off, 64);
                 best3_merge(L.t, o);
             }
-            if (sub == 0) resolve_and_accumulate<EXPORT>(acc, p, false, p.src, T, L.i, L.t);
+            if (sub == 0) resolve_and_accumulate<false, EXPORT>(acc, p, p.src, T, L.i, L.t);
         }
         __syncthreads();  // s_flag is reset; (s_red of the previous pass has long been read)
         tid = fresh_tid();
@@ -250,7 +251,7 @@ __global__ __launch_bounds__(BLOCK) void k_pass_small(const SmallParams /* read 
         if (op != kCmdContinue) {
             if (op != 0u || !sp.group_rows) return;  // STOP - or, with a row per workgroup, the marked row is out (await_command)
             gave_up = 1;  // (group rows: the mark travels through the group's accumulators, like k_pass_resident's)
-            if (fresh_tid() == 0 && sp.p.sol.rec) __hip_atomic_store(&sp.p.sol.rec->reserved[0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            if (fresh_tid() == 0 && sp.p.sol.rec) __hip_atomic_store(&sp.p.sol.rec->gave_up, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
             continue;
         }
         T = Pose{uniform_d(__longlong_as_double(static_cast<long long>(s_cmd[0]))), uniform_d(__longlong_as_double(static_cast<long long>(s_cmd[1]))),
@@ -265,7 +266,7 @@ __global__ __launch_bounds__(BLOCK) void k_pass_small(const SmallParams /* read 
 // k_pass_resident: the GENERIC pass kernel (one lane per query, kicp_kernels.hpp) resident for the iterations of a call - scans
 // too large for the kernels above but small enough for every workgroup to be on the device at once (<= 512 workgroups of the
 // latency-oriented build, <= 1024 of the four-waves-per-SIMD build on 256 CUs).  Same search, same exact sums, same reduction:
-// tagged workgroup rows, a ticket per group of 32, the group's row to the host (finish_pass, mode 4) - with tag0 + pass as the
+// tagged workgroup rows, a ticket per group of 32, the group's row to the host (finish_pass, group rows) - with tag0 + pass as the
 // tag of pass `pass`.  What a pass after the first saves is the launch (doorbell -> packet -> dispatch of 2 048 waves, ~5 us)
 // against a polled command (~1.3 us).  A workgroup that sees no command in time hands over an EMPTY row marked kGaveUpUnit
 // for the pass it will not run - through the same group protocol, so the host finds the mark in the group's row - and leaves.
@@ -298,7 +299,7 @@ __global__ __launch_bounds__(BLOCK, OCC) void k_pass_resident(const SmallParams 
             const double *src = sp.p.src;
             uint32_t n = sp.p.n;
             if (sp.scans) src = sp.scans[scan].src, n = static_cast<uint32_t>(sp.scans[scan].n);  // (uniform: scalar loads)
-            gather32_pass<BLOCK, 1, false, LAT, kLends>(sp.p, T, false, tid, acc, src, n, share, kLends ? &s_lend[kLends ? tid / 64 : 0][0] : nullptr, s_park);
+            gather32_pass<false, BLOCK, 1, false, LAT, kLends>(sp.p, T, tid, acc, src, n, share, kLends ? &s_lend[kLends ? tid / 64 : 0][0] : nullptr, s_park);
             share += sp.rotate;
             if (share >= gridDim.x) share -= gridDim.x;
         }
@@ -315,7 +316,7 @@ __global__ __launch_bounds__(BLOCK, OCC) void k_pass_resident(const SmallParams 
             // tell the host that a workgroup of this launch gave up: should the call end before every workgroup has taken its ticket
             // of the give-up round (the host stops after the pass it was waiting for), the next launch must not inherit the
             // tickets taken so far - the host clears them when it finds this word set (run_small)
-            if (fresh_tid() == 0 && sp.p.sol.rec) __hip_atomic_store(&sp.p.sol.rec->reserved[0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            if (fresh_tid() == 0 && sp.p.sol.rec) __hip_atomic_store(&sp.p.sol.rec->gave_up, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
             continue;
         }
         scan = command_scan(s_cmd);
@@ -617,7 +618,7 @@ __global__ __launch_bounds__(BLOCK) void k_pass_wave(const SmallParams /* read t
         if (op != kCmdContinue && op != kCmdNewScan) {
             if (op != 0u || !sp.group_rows) return;  // STOP - or, with a row per workgroup, the marked row is out (await_command)
             gave_up = 1;  // (group rows: the mark travels through the group's accumulators, like k_pass_resident's)
-            if (fresh_tid() == 0 && sp.p.sol.rec) __hip_atomic_store(&sp.p.sol.rec->reserved[0], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            if (fresh_tid() == 0 && sp.p.sol.rec) __hip_atomic_store(&sp.p.sol.rec->gave_up, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
             continue;
         }
         if (sp.scans && command_scan(s_cmd) != scan) scan = command_scan(s_cmd), new_scan = true;

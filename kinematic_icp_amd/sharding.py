@@ -47,7 +47,7 @@ def unpack(words):
     return np.array([from_limbs(words[3 * i:3 * i + 3]) / float(1 << FIX_BITS) for i in range(NUM_SUMS)], dtype=np.float64)
 
 
-# ---- tagged rows of the hand-off (kicp_kernels.hpp finish_pass, mode 4; kicp_reg_launch.hip wait_rows) ----------------------
+# ---- tagged rows of the hand-off (kicp_kernels.hpp finish_pass, HandOff::GroupRows; kicp_reg_launch.hip wait_rows) ----------------------
 # Every word of a workgroup's / group's row carries the 16-bit tag of its pass in the low bits: word = value << 16 | tag.
 # A reader knows a row has landed when all its words carry the current tag - no store acknowledgement, no fence.
 TAG_BITS = 16
