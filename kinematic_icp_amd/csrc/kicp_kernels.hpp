@@ -263,6 +263,36 @@ KICP_HD void to_fixed(double x, int *limb, int &range_error) {
     const double r1 = fma(q1, -0x1p21, r2);
     limb[0] = static_cast<int>(r1), limb[1] = static_cast<int>(q1), limb[2] = static_cast<int>(q2), limb[3] = static_cast<int>(q3);
 }
+// The five terms of a correspondence (correspondence_terms) into limb[0 .. 5 kTermLimbs): the limbs and the range flag of five to_fixed
+// calls, bit for bit.  Where all five are below 2^22 in magnitude - every term of a scan whose points lie within 2 048 m of the base
+// frame - the integer T = rint(x 2^40) is at most 2^62 in magnitude, so to_fixed's q3 = trunc(T 2^-63) is +-0, its r3 is T itself and
+// its range test cannot fail: the short path leaves out the top limb's division, the range selects and the flag, and writes 0 for the
+// limb (static_cast<int>(-0.0) is 0 too).  The five compares are false for a NaN, which therefore takes to_fixed and raises the flag
+// there.  A lane's branch: a wave whose lanes all take the short side skips the general one with scalar instructions alone.
+constexpr double kShortTermLimit = 0x1p22;
+KICP_HD bool terms_are_short(const double (&term)[5]) {
+    bool is_short = true;
+#pragma unroll
+    for (int i = 0; i < 5; ++i) is_short = is_short && fabs(term[i]) < kShortTermLimit;
+    return is_short;
+}
+KICP_HD void terms_to_fixed(const double (&term)[5], int *limb, int &range_error) {
+    if (terms_are_short(term)) {
+#pragma unroll
+        for (int i = 0; i < 5; ++i) {
+            const double t = rint(term[i] * kFixScale);
+            const double q2 = trunc(t * 0x1p-42);
+            const double r2 = fma(q2, -0x1p42, t);
+            const double q1 = trunc(r2 * 0x1p-21);
+            const double r1 = fma(q1, -0x1p21, r2);
+            int *l = limb + i * kTermLimbs;
+            l[0] = static_cast<int>(r1), l[1] = static_cast<int>(q1), l[2] = static_cast<int>(q2), l[3] = 0;
+        }
+    } else {
+#pragma unroll
+        for (int i = 0; i < 5; ++i) to_fixed(term[i], limb + i * kTermLimbs, range_error);
+    }
+}
 KICP_HD PassBasis basis_of(const Pose &T) {
     PassBasis b;
     quat_rotate(T, 1.0, 0.0, 0.0, b.c0x, b.c0y, b.c0z);  // J.col(0) = R * UnitX (Registration.cpp:90)
@@ -481,13 +511,21 @@ __device__ __forceinline__ void accumulate(ScoreAcc &a, double qx, double qy, do
     to_fixed(squared_residual(rx, ry, rz), a.limb, a.range_error);
     a.hit = 1;
 }
+// SHORT: the terms go through terms_to_fixed and its short path.  Not in the EXPORT twins: the second path's live ranges cost the split
+// one (k_pass_gather32<256, 2, 4, true, false, true>) two vector registers it does not have - it spilled - and nobody times them.
+// (Like query_from's COMPONENTS this parameter only keeps an untimed kernel's registers where they were; it can go when that twin has two to spare.)
+template <bool SHORT>
 __device__ __forceinline__ void accumulate(Acc &a, const PassBasis &B, double sx, double sy, double qx, double qy, double qz, double tx, double ty, double tz) {
     double term[5];
     correspondence_terms(B, sx, sy, qx, qy, qz, tx, ty, tz, term);
 #pragma unroll
     for (int k = 0; k < kTermLimbs; ++k) a.limb[k] = B.jtj00[k];
+    if constexpr (SHORT) {
+        terms_to_fixed(term, a.limb + kTermLimbs, a.range_error);
+    } else {
 #pragma unroll
-    for (int i = 0; i < 5; ++i) to_fixed(term[i], a.limb + (i + 1) * kTermLimbs, a.range_error);
+        for (int i = 0; i < 5; ++i) to_fixed(term[i], a.limb + (i + 1) * kTermLimbs, a.range_error);
+    }
     a.limb[6 * kTermLimbs + 1] = 1 << 19;  // the count: 1.0 = 2^40 = 2^19 * 2^21 (the other limbs stay 0)
 }
 // the pass kernels' terms from their own function, s.x and b next to them (kicp_planar_sums)
@@ -1216,7 +1254,8 @@ __device__ __forceinline__ bool process_trip(const uint4 (&c)[N / 2], uint32_t p
     // reference's first minimum).  The 5 dropped mantissa bits are part of the margin's error model.
     // Empty slots need no test: their second word reads 4.3e9 units (kicp_common.hpp).  x and y are converted from their 16-bit
     // halves; z is stored as the float itself: no conversion, only a register copy per pair of points to bring the two z words of a
-    // load into one register pair (profiles/mirror_z_ab.txt).
+    // load into one register pair (profiles/mirror_z_ab.txt; a device layout that pairs the z words was built, measured and lost its
+    // A/B: profiles/visit_trim_ab.txt).
     uint32_t key[N];
 #pragma unroll
     for (int u = 0; u < N / 2; ++u) {
@@ -1260,17 +1299,44 @@ __device__ __forceinline__ bool process_trip(const uint4 (&c)[N / 2], uint32_t p
 // the query as seen from the corner of neighbour voxel `s`, both lanes of the packed arithmetic
 // (Reading the 27 triples shift x 65536 from a table in device memory - one 16-byte load per lane beside the load of nb[s] - takes 31
 // VALU instructions per wave and block out of this and was SLOWER by the clock, cfg5 + 2.3 %: profiles/lane_start_ab.txt.  Not kept.)
+// Per axis the value is l - d 65536 with d = the shift's component, -1, 0 or 1.  The order's components are packed once more for this
+// (kFromX / Y / Z), two bits per shift that ARE the top two bits of the float -2 d: 00 -> 0, 01 -> 2.0 (d = -1), 11 -> -2.0 (d = 1).  A
+// shift right by 2 s, a shift left by 30 (which drops the other shifts' bits: no mask) and one fma, l + (-2 d) 32768: the product is
+// exact, so the sum is rounded once - the same float as l - d 65536 formed from the integer d (tests/cpp/query_from_test.cpp).  Three
+// instructions per axis where extracting d, converting and multiplying it took six.
+// (The equality holds for every finite l, negative ones included - one exact product, one rounding - with one exception that cannot
+// matter: l = -0 with d = 0 gives +0 where the subtraction gave -0, and the value is only ever subtracted from and squared.)
+constexpr uint64_t pack_axis_from(int axis) {
+    uint64_t v = 0;
+    for (int s = 0; s < 27; ++s) v |= static_cast<uint64_t>(kShiftTable[s][axis] > 0 ? 3 : (kShiftTable[s][axis] < 0 ? 1 : 0)) << (2 * s);
+    return v;
+}
+constexpr uint64_t kFromX = pack_axis_from(0), kFromY = pack_axis_from(1), kFromZ = pack_axis_from(2);
+KICP_HD float axis_from(float l, uint64_t packed, int s) {
+    const float minus_two_d = __builtin_bit_cast(float, static_cast<uint32_t>(packed >> (2 * s)) << 30);
+    return fmaf(minus_two_d, 0.5f * kCell, l);
+}
 struct QueryFrom {
     v2f x, y, z;
 };
+// COMPONENTS: the form before, from the integer components - the same floats.  visit_bucket of the pose-scoring kernels asks for it -
+// the only visit those kernels compile (they have no written-out first round and are not the latency build, so visit_first and
+// visit_two are dead code there): k_score_poses sits at 128 VGPRs and spilled two of them with the shorter form's schedule.  A second
+// form of the same floats is kept for that reason alone; it can go as soon as k_score_poses has a register to spare.
+template <bool COMPONENTS = false>
 __device__ __forceinline__ QueryFrom query_from(const Probe &P, int s) {
-    const int dx = shift_component(kShiftX, s), dy = shift_component(kShiftY, s), dz = shift_component(kShiftZ, s);
-    return QueryFrom{{P.lx - dx * kCell, P.lx - dx * kCell}, {P.ly - dy * kCell, P.ly - dy * kCell}, {P.lz - dz * kCell, P.lz - dz * kCell}};
+    if constexpr (COMPONENTS) {
+        const int dx = shift_component(kShiftX, s), dy = shift_component(kShiftY, s), dz = shift_component(kShiftZ, s);
+        return QueryFrom{{P.lx - dx * kCell, P.lx - dx * kCell}, {P.ly - dy * kCell, P.ly - dy * kCell}, {P.lz - dz * kCell, P.lz - dz * kCell}};
+    } else {
+        const float x = axis_from(P.lx, kFromX, s), y = axis_from(P.ly, kFromY, s), z = axis_from(P.lz, kFromZ, s);
+        return QueryFrom{{x, x}, {y, y}, {z, z}};
+    }
 }
 // scan the bucket of neighbour voxel `s` of query P and merge what it finds into t.  PARTS = 2: two neighbouring lanes serve the
 // same query and share every bucket - this lane takes points [10 part, 10 part + 10) of each 20-point trip (five 16-byte loads),
 // the records are merged by the caller.
-template <int PARTS>
+template <int PARTS, bool COMPONENTS = false>
 __device__ __forceinline__ void visit_bucket(const Probe &P, Best3 &t, const MapView &m, int s, float margin, int part = 0) {
     static_assert(PARTS == 1 || PARTS == 2, "a trip is dealt to one lane or to two");
     constexpr int kMine = kTrip / PARTS;  // points of a trip this lane looks at
@@ -1279,7 +1345,7 @@ __device__ __forceinline__ void visit_bucket(const Probe &P, Best3 &t, const Map
     const uint32_t base = bucket * m.cap;  // index into the fp64 pool
     const uint32_t stride16 = m.cap16;
     const uint4 *b = reinterpret_cast<const uint4 *>(m.pool16 + static_cast<size_t>(bucket) * stride16);
-    const QueryFrom q = query_from(P, s);
+    const QueryFrom q = query_from<COMPONENTS>(P, s);
     const uint32_t first = static_cast<uint32_t>(part) * kMine;  // this lane's first point within a trip
     for (uint32_t k0 = 0; k0 < stride16; k0 += kTrip) {  // (the mirror's bucket stride is a multiple of kTrip: a trip never leaves the bucket)
         uint4 c[kMine / 2];
@@ -1455,7 +1521,7 @@ __device__ __forceinline__ void resolve_and_accumulate(ACC &acc, const PassParam
             if (from_args) B = JOBS ? job_args_at_point_of_use(blockIdx.y).sol.basis : args_at_point_of_use().sol.basis;
             else B = basis_of(T);
             // the untransformed source point again (L1 / L2 hit) unless the build kept it: cheaper than registers kept live through the search
-            accumulate(acc, B, kept ? kept->sx : src[3 * i], kept ? kept->sy : src[3 * i + 1], q.x, q.y, q.z, wx, wy, wz);
+            accumulate<!EXPORT>(acc, B, kept ? kept->sx : src[3 * i], kept ? kept->sy : src[3 * i + 1], q.x, q.y, q.z, wx, wy, wz);
         }
     }
 }
@@ -1582,18 +1648,18 @@ __device__ __forceinline__ void gather32_pass(const PassParams &p, const Pose &T
                         const int e = lend[slot];
                         from = e & 63, s = e >> 8;
                     }
-                    const float glx = __shfl(L.q.lx, from, 64), gly = __shfl(L.q.ly, from, 64), glz = __shfl(L.q.lz, from, 64);
-                    const uint32_t gslot = __shfl(L.q.slot0, from, 64);
+                    // every lane takes the probe the shuffle returns - its own from `from == lane`, the lender's where it helps: no select
+                    // per word (all 64 lanes are active here: every condition around this block is wave-uniform)
+                    L.q = Probe{__shfl(L.q.lx, from, 64), __shfl(L.q.ly, from, 64), __shfl(L.q.lz, from, 64), __shfl(L.q.slot0, from, 64)};
                     if (helps) {  // (a lane with nothing to do never needs its own probe again; its record waits in LDS)
                         int *keep = lend + kLendJobs + 7 * slot;
                         keep[0] = __float_as_int(L.t.b1), keep[1] = __float_as_int(L.t.b2), keep[2] = __float_as_int(L.t.b3);
                         keep[3] = static_cast<int>(L.t.i1), keep[4] = static_cast<int>(L.t.i2), keep[5] = static_cast<int>(L.t.o1), keep[6] = static_cast<int>(L.t.o2);
-                        L.q = Probe{glx, gly, glz, gslot};
                         L.t = Best3{p.search.bound_u, p.search.bound_u, p.search.bound_u, kNoIndex32, kNoIndex32, 0u, 0u};
                     }
                 }
             }
-            if (busy || helps) visit_bucket<1>(L.q, L.t, m, s, margin, 0);
+            if (busy || helps) visit_bucket<1, ACC::kKind != AccKind::Pass>(L.q, L.t, m, s, margin, 0);
             if (__any(helps)) {  // (wave-uniform) the lent lanes' records go home
                 if (helps) {
                     int *back = lend + kLendJobs + 7 * kLendJobs + 7 * slot;
@@ -1616,7 +1682,7 @@ __device__ __forceinline__ void gather32_pass(const PassParams &p, const Pose &T
         } else if (L.todo) {
             const int s = __ffs(L.todo) - 1;
             L.todo &= L.todo - 1u;
-            visit_bucket<SPLIT ? 2 : 1>(L.q, L.t, m, s, margin, SPLIT ? sub : 0);
+            visit_bucket<SPLIT ? 2 : 1, ACC::kKind != AccKind::Pass>(L.q, L.t, m, s, margin, SPLIT ? sub : 0);
         }
         cull = L.t.b1;
 #pragma unroll
