@@ -143,7 +143,7 @@ size_t kicp_map_pointcloud(const kicp_map *map, double *out_xyz, size_t cap_poin
  * code: a pending deferred update is collected first and its error is returned. */
 int kicp_map_pointcloud_f32(const kicp_map *map, float *out_xyz, size_t cap_points, size_t *out_total);
 /* GetClosestNeighbor(query) for n queries -- Registration.cpp:74.  Host arrays in/out; runs on `device` the plain fp64 search
- * over the 27 neighbour voxels (kicp_kernels.hpp search_global: the reference's loop, and the exact fallback of the fused pass
+ * over the 27 neighbour voxels (kicp_nn_exact.hpp search_global: the reference's loop, and the exact fallback of the fused pass
  * kernels - NOT their mirror pre-selection: what the shipped pass kernels pick per query is what kicp_pass_correspondences returns).
  * No candidate -> nn = (0,0,0), dist = DBL_MAX, exactly like the reference. */
 int kicp_map_closest(kicp_map *map, int device, const double *queries_xyz, size_t n, double *out_nn_xyz, double *out_dist);

@@ -1,6 +1,6 @@
 // kicp_internal.hpp -- what the translation units behind include/kicp.h share: error handling, tracing, the staging
 // policy for caller memory, the HBM mirror of the voxel map and the handle behind kicp_map.  Host code only; the kernels
-// live in kicp_kernels.hpp (registration passes), kicp_mapdev.hpp (map maintenance) and kicp_pre*.hpp (pre-steps), all with
+// live in kicp_kernels.hpp and the headers it includes (registration passes), kicp_mapdev.hpp (map maintenance) and kicp_pre*.hpp (pre-steps), all with
 // internal linkage so that every translation unit may include what it launches.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -2,7 +2,7 @@
 // delta upload, lazy refresh of the host copy), the device-side Update / re-hash / Pointcloud (kicp_mapdev.hpp) and the
 // batch GetClosestNeighbor.
 #include "kicp_internal.hpp"
-#include "kicp_kernels.hpp"
+#include "kicp_map_kernels.hpp"  // k_scatter_rows, k_closest
 #include "kicp_mapdev.hpp"
 #include "kicp_scan_blocks.hpp"  // k_scan_blocks
 

@@ -2,7 +2,7 @@
 // check it on the host (tests/cpp/pass_tiles_test.cpp): the row words of a workgroup's limb sums, and the automatic tile count.
 //
 // A workgroup of the one-lane-per-query four-waves build searches `tiles` blocks of 256 queries and runs ONE epilogue
-// (kicp_kernels.hpp: pass_tiles_loop, finish_pass).  The sums are exact integers, so the tile count changes no bit of a result -
+// (kicp_kernels.hpp: pass_tiles_loop; kicp_pass_finish.hpp: finish_pass).  The sums are exact integers, so the tile count changes no bit of a result -
 // only how often the epilogue's fixed cost is paid, and how many workgroups a pass has.
 #pragma once
 #include <algorithm>

@@ -1,5 +1,6 @@
 // kicp_reg_api.hip -- the C-ABI entry points of the registration (see kicp_reg_internal.hpp)
 #include "kicp_reg_internal.hpp"
+#include "kicp_small.hpp"  // kPipeSlots
 
 using namespace kicp;
 using namespace kicp::host;
@@ -502,7 +503,7 @@ static int pass_once(kicp_reg *reg, kicp_map *map, const double *frame_xyz, size
     set_pose(pp.sol, pose_from(pose_qt));
     pp.sol.mode = HandOff::Totals, pp.sol.rec = reg->rec.dev();
     if (int rc = launch_pass(reg, pp)) return rc;
-    hipLaunchKernelGGL(k_publish_sums, dim3(1), dim3(64), 0, reg->stream, reg->d_state.get(), reg->rec.dev(), call_id);
+    publish_sums(reg->stream, reg->d_state.get(), reg->rec.dev(), call_id);
     HIP_TRY(hipGetLastError());
     unsigned long long seq = 0;
     if (int rc = wait_record(reg, call_id, 1, true, &seq)) return rc;

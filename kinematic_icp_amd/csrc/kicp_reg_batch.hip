@@ -1,5 +1,6 @@
 // kicp_reg_batch.hip -- batches of independent scans on resident kernels (see kicp_reg_internal.hpp)
 #include "kicp_reg_internal.hpp"
+#include "kicp_small.hpp"  // the small-scan path's constants, ScanRef and SmallParams
 
 using namespace kicp;
 using namespace kicp::host;

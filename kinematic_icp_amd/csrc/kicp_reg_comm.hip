@@ -180,11 +180,11 @@ int kicp_reg_shm_init(kicp_reg *reg, int nranks, int rank, const char *name) {
     return KICP_OK;
 }
 // ---- one-shot exchange over peer mappings -----------------------------------------------------
-// Each rank owns a mailbox in its own HBM (layout: kicp_kernels.hpp, p2p_box_words), fine-grained so that a peer's stores
+// Each rank owns a mailbox in its own HBM (layout: kicp_pass_params.hpp, p2p_box_words), fine-grained so that a peer's stores
 // (over xGMI) become visible to a kernel that is polling it.  Export -> the caller gathers every rank's handle (any
 // transport: torch.distributed, MPI, a file) -> connect opens the peers' mailboxes -> every pass kernel writes this rank's
 // group rows (or its total as one row) into all mailboxes and collects its own (HandOff::PeerGroupRows / PeerSingleRow,
-// kicp_kernels.hpp::finish_pass, p2p_collect_rows).
+// kicp_pass_finish.hpp::finish_pass, p2p_collect_rows).
 int kicp_reg_p2p_destroy(kicp_reg *reg) {
     if (!reg) return fail(KICP_ERR_ARG, "null argument");
     if (reg->p2p_box || reg->d_p2p_table) {

@@ -27,8 +27,15 @@
 
 #include "kicp_aql.hpp"
 #include "kicp_internal.hpp"
-#include "kicp_kernels.hpp"
-#include "kicp_small.hpp"
+#include "kicp_pass_params.hpp"
+
+// The handle and the functions below need the pass kernels' arguments and records, not the kernels: kicp_reg_launch.hip and
+// kicp_score.hip, which instantiate kernels, include kicp_kernels.hpp (through kicp_small.hpp / kicp_score.hpp) themselves; the units
+// that drive the small-scan path include kicp_small.hpp for its constants and SmallParams, which are only named here.
+namespace kicp {
+struct SmallParams;
+struct ScanRef;
+}  // namespace kicp
 
 // (an internal header of six translation units that all begin this way)
 using namespace kicp;
@@ -315,6 +322,9 @@ int ensure_frame(kicp_reg *r, size_t n);  // room for a host frame of n points i
 int ensure_rows(kicp_reg *r, size_t groups);
 int next_tag(kicp_reg *r, uint32_t *tag);
 int enqueue_allreduce(kicp_reg *r);
+// k_publish_words / k_publish_sums, one wave on `stream` (kicp_reg_launch.hip, the one unit that holds and launches them)
+void publish_words(hipStream_t stream, IcpState *st, HostRecord *rec, unsigned long long call_id, int pass);
+void publish_sums(hipStream_t stream, IcpState *st, HostRecord *rec, unsigned long long call_id);
 int wait_record(kicp_reg *r, unsigned long long call_id, unsigned min_iter, bool need_done, unsigned long long *seq_out);
 long long row_flags(long long w);
 int wait_rows(kicp_reg *r, size_t groups, uint32_t tag, long long out_words[kReduceWords], size_t first_row = 0);

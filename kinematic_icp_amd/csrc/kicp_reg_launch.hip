@@ -1,10 +1,32 @@
 // kicp_reg_launch.hip -- the pass kernels' launches, the handle's buffers and tags, the waits for rows and records (see kicp_reg_internal.hpp)
+#include "kicp_kernels.hpp"  // the pass kernels this unit instantiates, and limbs_to_double
 #include "kicp_reg_internal.hpp"
+#include "kicp_small.hpp"  // k_pass_small, k_pass_wave, k_pass_resident
 
 using namespace kicp;
 using namespace kicp::host;
 
 namespace kicp {
+// The two kernels that follow a HandOff::Totals pass on its stream (launched by publish_words / publish_sums below, nowhere else)
+// multi-GPU with host-side solve: hand the all-reduced limb totals to the host
+static __global__ __launch_bounds__(64) void k_publish_words(IcpState *st, HostRecord *rec, unsigned long long call_id, int pass) {
+    const int lane = threadIdx.x;
+    if (lane < kReduceWords) __hip_atomic_store(&rec->words[lane], st->reduce[lane], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    if (lane == 0) __hip_atomic_store(&rec->seq, (call_id << 16) | static_cast<unsigned long long>(pass + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
+// publish the raw sums of the last pass (kicp_pass_sums)
+static __global__ __launch_bounds__(64) void k_publish_sums(IcpState *st, HostRecord *rec, unsigned long long call_id) {
+    if (threadIdx.x != 0) return;
+    for (int i = 0; i < kNumSums; ++i)
+        __hip_atomic_store(reinterpret_cast<unsigned long long *>(&rec->sums[i]),
+                           static_cast<unsigned long long>(__double_as_longlong(limbs_to_double(st->reduce + 3 * i))), __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_SYSTEM);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __hip_atomic_store(&rec->seq, (call_id << 16) | 0x8001ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+
 namespace host {
 // host twin of kicp::limbs_to_double (same operations, so the host's solve and k_publish_sums see the same doubles)
 double host_limbs_to_double(const long long l[3]) {
@@ -239,6 +261,13 @@ int enqueue_allreduce(kicp_reg *r) {
     const ncclResult_t rc = g_comm.AllReduce(buf, buf, kReduceWords, ncclInt64, ncclSum, r->comm, r->stream);
     if (rc != ncclSuccess) return fail(KICP_ERR_COMM, std::string("ncclAllReduce: ") + g_comm.GetErrorString(rc));
     return KICP_OK;
+}
+// what follows a HandOff::Totals pass (and its collective) on `stream`: one wave that hands st->reduce to the host's record
+void publish_words(hipStream_t stream, IcpState *st, HostRecord *rec, unsigned long long call_id, int pass) {
+    hipLaunchKernelGGL(k_publish_words, dim3(1), dim3(64), 0, stream, st, rec, call_id, pass);
+}
+void publish_sums(hipStream_t stream, IcpState *st, HostRecord *rec, unsigned long long call_id) {
+    hipLaunchKernelGGL(k_publish_sums, dim3(1), dim3(64), 0, stream, st, rec, call_id);
 }
 
 // wait until the record carries `call_id` with at least `min_iter` completed iterations (or its done bit);

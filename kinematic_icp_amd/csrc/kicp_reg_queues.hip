@@ -1,6 +1,7 @@
 // kicp_reg_queues.hip -- batches with several scans in flight on queues of their own, sharded or not (see kicp_reg_internal.hpp)
 #include "kicp_reg_internal.hpp"
 #include "kicp_batch_groups.hpp"
+#include "kicp_small.hpp"  // kCmd*, kPipeSlots, SmallParams
 
 using namespace kicp;
 using namespace kicp::host;
@@ -162,7 +163,7 @@ int flight_launch(BatchFlight &f, const kicp_map *map, const double *d_frame, si
         f.comm_seq = (call_id << 16) | static_cast<unsigned long long>(f.loop.iter + 1);
         if (int rc = launch_pass(h, pp, false)) return rc;
         if (int rc = enqueue_allreduce(h)) return rc;
-        hipLaunchKernelGGL(k_publish_words, dim3(1), dim3(64), 0, h->stream, h->d_state.get(), h->rec.dev(), call_id, f.loop.iter);
+        publish_words(h->stream, h->d_state.get(), h->rec.dev(), call_id, f.loop.iter);
         HIP_TRY(hipGetLastError());
         return KICP_OK;
     }

@@ -1,5 +1,6 @@
 // kicp_reg_run.hip -- one registration: the host-side solve loop and the small-scan path (see kicp_reg_internal.hpp)
 #include "kicp_reg_internal.hpp"
+#include "kicp_small.hpp"  // the small-scan path's constants, ScanRef and SmallParams
 
 using namespace kicp;
 using namespace kicp::host;
@@ -244,7 +245,7 @@ int run_registration_impl(kicp_reg *r, kicp_map *map, const double *d_frame, siz
             if (ev) HIP_TRY(hipEventRecord(r->evp[2 * it + 1], r->stream));
             if (multi) {
                 if (int rc = enqueue_allreduce(r)) return rc;
-                hipLaunchKernelGGL(k_publish_words, dim3(1), dim3(64), 0, r->stream, r->d_state.get(), r->rec.dev(), call_id, it);
+                publish_words(r->stream, r->d_state.get(), r->rec.dev(), call_id, it);
             }
             if (rows_mode) {
                 if (int rc = wait_rows(r, groups, sp.tag, words)) {

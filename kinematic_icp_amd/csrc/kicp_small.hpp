@@ -9,7 +9,7 @@
 //     there is NO inter-workgroup reduction tree: every workgroup folds its lanes in LDS and stores its row - two 64-byte lines of
 //     self-validating words - straight into host-mapped memory, where the host adds the (<= 16) rows; or (round 5, group_rows:
 //     the wave-per-query kernel's hundreds of workgroups) adds it into its group's counting accumulators, whose completing
-//     additions send ONE row per 32 workgroups to the host (kicp_kernels.hpp::counting_hand_over);
+//     additions send ONE row per 32 workgroups to the host (kicp_pass_finish.hpp::counting_hand_over);
 //   * the kernel stays RESIDENT for the iterations of one ComputeRobotMotion call: after publishing the rows of pass k it
 //     polls one 64-byte command line in host-mapped memory for the pose of pass k + 1 (or STOP).  A host -> GPU -> host round
 //     trip through a polled line costs ~3.5 us against ~7.5 us through a launch (profiles/r02a_micro_handoff.txt); the kernel
@@ -168,7 +168,7 @@ __device__ __forceinline__ void small_publish(const Acc &a, const SmallParams &s
     }
     __syncthreads();
     if (wave != 0) return;
-    if (sp.group_rows) {  // one row per group of 32 workgroups reaches the host (kicp_kernels.hpp::counting_hand_over)
+    if (sp.group_rows) {  // one row per group of 32 workgroups reaches the host (kicp_pass_finish.hpp::counting_hand_over)
         long long l[3];
         workgroup_row_words<BLOCK / 64>(s_red, lane, l);
         counting_hand_over(l, (*s_flag & 2) ? 1 : 0, gave_up, sp.p, tag, pass % kPipeSlots, pass % kPipeSlots, lane);
@@ -573,7 +573,7 @@ __global__ __launch_bounds__(BLOCK) void k_pass_wave(const SmallParams /* read t
             if (EXPORT && lane == 0) export_correspondence(p, qi, take ? best.idx : kNoIndex32, best.d2, take ? best.x : 0.0, take ? best.y : 0.0, take ? best.z : 0.0);
             if (take) {
                 accepted = true;
-                // the terms of kicp_kernels.hpp::correspondence_terms (one function for every pass kernel: the same doubles), lane k < 6
+                // the terms of kicp_pass_fixed.hpp::correspondence_terms (one function for every pass kernel: the same doubles), lane k < 6
                 // taking term k to convert and park; JTJ(0,0) is the expression basis_of converts
                 double term[5];
                 correspondence_terms(B, sx, sy, q.x, q.y, q.z, best.x, best.y, best.z, term);
@@ -598,7 +598,7 @@ __global__ __launch_bounds__(BLOCK) void k_pass_wave(const SmallParams /* read t
             I128 t{0ull, 0ll};
             if (ln < kNumSums)
                 for (int w = 0; w < kWaves; ++w) i128_add(t, I128{s_term[w][2 * ln], static_cast<long long>(s_term[w][2 * ln + 1])});
-            if (sp.group_rows) {  // one row per group of 32 workgroups reaches the host (kicp_kernels.hpp::counting_hand_over)
+            if (sp.group_rows) {  // one row per group of 32 workgroups reaches the host (kicp_pass_finish.hpp::counting_hand_over)
                 counting_hand_over(t, (s_flag & 2) ? 1 : 0, gave_up, sp.p, sp.tag0 + pass, pass % kPipeSlots, pass % kPipeSlots, ln);
             } else {
                 const unsigned long long m48 = (1ull << 48) - 1;

@@ -2,7 +2,7 @@
 per-rank sums travel through the all-reduce.
 
 The device accumulates each of the seven sums exactly: every per-correspondence term is rounded once to a multiple
-of 2^-40 and added as a 128-bit integer (kicp_kernels.hpp).  For the collective the 128-bit total T is split into
+of 2^-40 and added as a 128-bit integer (kicp_pass_fixed.hpp).  For the collective the 128-bit total T is split into
 three signed 64-bit limbs, T = l0 + l1*2^40 + l2*2^80 (0 <= l0,l1 < 2^40), so that a plain int64 sum-all-reduce of
 24 words (21 limbs + range flag + padding) is exact for any number of ranks and any reduction order.  These helpers
 are the reference of that encoding; tests/test_sharding.py drives them through a real world_size-2 gloo all-reduce.
@@ -47,7 +47,7 @@ def unpack(words):
     return np.array([from_limbs(words[3 * i:3 * i + 3]) / float(1 << FIX_BITS) for i in range(NUM_SUMS)], dtype=np.float64)
 
 
-# ---- tagged rows of the hand-off (kicp_kernels.hpp finish_pass, HandOff::GroupRows; kicp_reg_launch.hip wait_rows) ----------------------
+# ---- tagged rows of the hand-off (kicp_pass_finish.hpp finish_pass, HandOff::GroupRows; kicp_reg_launch.hip wait_rows) ----------------------
 # Every word of a workgroup's / group's row carries the 16-bit tag of its pass in the low bits: word = value << 16 | tag.
 # A reader knows a row has landed when all its words carry the current tag - no store acknowledgement, no fence.
 TAG_BITS = 16

@@ -1,4 +1,4 @@
-// to_fixed / basis_of of kicp_kernels.hpp on the HOST (the functions are __host__ __device__: the device runs the same operations):
+// to_fixed / basis_of of kicp_pass_fixed.hpp on the HOST (the functions are __host__ __device__: the device runs the same operations):
 //   * the four signed 21-bit limbs add up to rint(x 2^40) - checked against round 4's route (two 64-bit conversions and 128-bit integer
 //     arithmetic) over magnitudes from 2^-60 to the range limit 2^43, ties at the 2^-41 grid, signs, zeros;
 //   * the range flag for |x| >= 2^43, infinities and NaN;
@@ -9,7 +9,7 @@
 #include <cstdlib>
 #include <random>
 
-#include "kicp_kernels.hpp"
+#include "kicp_pass_fixed.hpp"
 
 using namespace kicp;
 

@@ -1,4 +1,4 @@
-// axis_from of kicp_kernels.hpp on the HOST (__host__ __device__: the device runs the same operations): the query's offset as seen from
+// axis_from of kicp_pass_visit.hpp on the HOST (__host__ __device__: the device runs the same operations): the query's offset as seen from
 // the corner of neighbour voxel s, l - d 65536 with d the component of shift s, from the order packed as the top bits of the float
 // -2 d.  It must be THE SAME FLOAT as the form it replaced - the integer component extracted (shift_component), converted and
 // multiplied, then subtracted - for all 27 shifts on all three axes and
@@ -13,7 +13,7 @@
 #include <cstring>
 #include <random>
 
-#include "kicp_kernels.hpp"
+#include "kicp_pass_visit.hpp"
 
 using namespace kicp;
 

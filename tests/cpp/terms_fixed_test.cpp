@@ -1,4 +1,4 @@
-// terms_to_fixed of kicp_kernels.hpp on the HOST (__host__ __device__: the device runs the same operations): the twenty limbs and the
+// terms_to_fixed of kicp_pass_fixed.hpp on the HOST (__host__ __device__: the device runs the same operations): the twenty limbs and the
 // range flag it leaves for five terms must be those of five to_fixed calls, whichever path it takes.
 //   * 0 and -0, ties of the 2^-41 grid and their neighbours, the short path's last value 2^22 - 2^-30 and its first excluded one 2^22
 //     (terms_are_short says which path a set of terms takes), 2^43 - 1 and the range error at 2^43, NaN and the infinities - each of
@@ -11,7 +11,7 @@
 #include <cstring>
 #include <random>
 
-#include "kicp_kernels.hpp"
+#include "kicp_pass_fixed.hpp"
 
 using namespace kicp;
 

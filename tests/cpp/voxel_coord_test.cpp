@@ -1,4 +1,4 @@
-// PointToVoxel without a division (kicp_kernels.hpp::voxel_coord, voxel_coord_offset) on the HOST - the functions are __host__
+// PointToVoxel without a division (kicp_pass_visit.hpp::voxel_coord, voxel_coord_offset) on the HOST - the functions are __host__
 // __device__, the device runs the same operations.  For voxel sizes 1, 0.5, 0.3, 0.1 and 0.05, at coordinates k vs -+ j ulps (j = 0 .. 4;
 // k = 0, +-1, ... +-2^20), at random coordinates, at fractions on either side of the guard and at |c / vs| just below 2^31:
 //   * voxel_coord and voxel_coord_offset give the integer of the formula they replaced, kept below as text (parent_voxel_coord), and
@@ -12,7 +12,7 @@
 #include <cstdio>
 #include <random>
 
-#include "kicp_kernels.hpp"
+#include "kicp_pass_visit.hpp"
 
 using namespace kicp;
 

@@ -1,4 +1,4 @@
-"""Scenes for the start of a lane and the set-up of a visit in the pass kernels (kicp_kernels.hpp: voxel_coord's constant guard, the
+"""Scenes for the start of a lane and the set-up of a visit in the pass kernels (kicp_pass_visit.hpp: voxel_coord's constant guard, the
 lane offsets taken from its fraction, query_from for each of the 27 shifts, the lending round), each built so that one regime is provably
 entered - premises() proves it on the CPU from the oracle's data.  Every map fills at most the 27 voxels of one block; a scan is one or
 two blocks of 256 queries (1, 255, 256, 257 and 512 queries).
@@ -31,7 +31,7 @@ SHIFTS = np.array([(0, 0, 0), (1, 0, 0), (-1, 0, 0), (0, 1, 0), (0, -1, 0), (0, 
                    (1, 0, 1), (1, 0, -1), (-1, 0, 1), (-1, 0, -1), (0, 1, 1), (0, 1, -1), (0, -1, 1), (0, -1, -1), (1, 1, 1), (1, 1, -1),
                    (1, -1, 1), (1, -1, -1), (-1, 1, 1), (-1, 1, -1), (-1, -1, 1), (-1, -1, -1)], dtype=np.float64)
 EPS = 2.0 ** -20       # of a voxel: inside the constant guard
-GUARD = 1.0e-6         # kicp_kernels.hpp::kVoxelGuard
+GUARD = 1.0e-6         # kicp_pass_visit.hpp::kVoxelGuard
 
 
 class Scene:

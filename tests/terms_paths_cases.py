@@ -1,4 +1,4 @@
-"""Scenes for the two paths of the pass kernels' limb split (kicp_kernels.hpp::terms_to_fixed): the short one where all five terms of a
+"""Scenes for the two paths of the pass kernels' limb split (kicp_pass_fixed.hpp::terms_to_fixed): the short one where all five terms of a
 correspondence are below 2^22 in magnitude, to_fixed's where one is not.  A term that large is s.x^2 + s.y^2 of a source point more than
 2 048 m from the base frame, so the far queries sit at about 3 000 m.
 

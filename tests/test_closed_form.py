@@ -1,4 +1,4 @@
-"""The per-correspondence terms of the pass kernels (kicp_kernels.hpp::correspondence_terms, to_fixed, basis_of) without a GPU.
+"""The per-correspondence terms of the pass kernels (kicp_pass_fixed.hpp::correspondence_terms, to_fixed, basis_of) without a GPU.
 
 The reference forms J = [R UnitX | R (-s.y, s.x, 0)] and r = T s - t per correspondence and adds J^T J and J^T r
 (/root/reference/cpp/kinematic_icp/registration/Registration.cpp:86-93,108-113).  The kernels evaluate the closed form of SURVEY.md
@@ -36,7 +36,7 @@ def test_closed_form_equals_the_literal_products_to_1e_12():
         j0 = quat_rotate(q, np.array([1.0, 0.0, 0.0]))
         j1 = quat_rotate(q, np.array([-s[1], s[0], 0.0]))
         lit = np.array([j0 @ j0, j0 @ j1, j1 @ j1, j0 @ r, j1 @ r])
-        # closed form (kicp_kernels.hpp::correspondence_terms)
+        # closed form (kicp_pass_fixed.hpp::correspondence_terms)
         c0, c1 = j0, quat_rotate(q, np.array([0.0, 1.0, 0.0]))
         a, b = c0 @ r, c1 @ r
         closed = np.array([1.0, -s[1], s[0] * s[0] + s[1] * s[1], a, s[0] * b - s[1] * a])

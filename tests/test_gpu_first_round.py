@@ -1,5 +1,5 @@
-"""The first visiting round of the one-lane-per-query four-waves pass kernel (kicp_kernels.hpp: the first round of gather32_pass,
-visit_first, process_trip FRESH - k_pass_gather32<256, 1, 4, false, false>, its EXPORT twin, k_pass_gather32_jobs) on the scenes of
+"""The first visiting round of the one-lane-per-query four-waves pass kernel (kicp_kernels.hpp: the first round of gather32_pass;
+kicp_pass_visit.hpp: visit_first, process_trip FRESH - k_pass_gather32<256, 1, 4, false, false>, its EXPORT twin, k_pass_gather32_jobs) on the scenes of
 tests/first_round_cases.py, whose premises() proves on the CPU that each regime is entered: an empty own voxel next to occupied ones,
 the nearest point across a face with exact ties, buckets of two trips, own-voxel candidates around tau and around the kernel's bound,
 near-equal candidates, scans that leave lanes of the last wave without a query, queries without any entry.

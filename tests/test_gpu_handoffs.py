@@ -1,4 +1,4 @@
-"""The three single-GPU hand-offs of the generic pass kernel (kicp_kernels.hpp: HandOff, finish_pass) give the same sums of pass 0,
+"""The three single-GPU hand-offs of the generic pass kernel (kicp_pass_params.hpp: HandOff; kicp_pass_finish.hpp: finish_pass) give the same sums of pass 0,
 as doubles, exactly:
   * group rows to the host: a registration of one iteration (stats.sums[0], stats.n_corr[0]);
   * totals left on the device, then k_publish_sums: kicp_pass_sums at the same pose;

@@ -1,4 +1,4 @@
-"""The start of a lane and the set-up of a visit (kicp_kernels.hpp: voxel_coord's constant guard, the lane offsets taken from its
+"""The start of a lane and the set-up of a visit (kicp_pass_visit.hpp: voxel_coord's constant guard, the lane offsets taken from its
 fraction, query_from for each of the 27 shifts, the lending round's integer minima) through every build of the pass kernel a handle can
 pick, on the scenes of tests/lane_start_cases.py, whose premises() proves on the CPU that each regime is entered: a query whose accepted
 neighbour lies in each of the 27 shifts, coordinates exactly on voxel faces, coordinates inside the constant guard but outside the one

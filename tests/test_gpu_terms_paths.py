@@ -1,4 +1,4 @@
-"""The two paths of the pass kernels' limb split (kicp_kernels.hpp::terms_to_fixed) on the GPU, on the scenes of
+"""The two paths of the pass kernels' limb split (kicp_pass_fixed.hpp::terms_to_fixed) on the GPU, on the scenes of
 tests/terms_paths_cases.py (whose premises() proves on the CPU which queries leave the short path): one lane of a wave, sixteen lanes of
 every wave, every lane of one wave and none of the others, every lane, no lane, and the second of two tiles of a workgroup hold a
 correspondence whose s.x^2 + s.y^2 is 2^22 or more - source points at about 3 000 m.

@@ -4,7 +4,7 @@ decide what it can decide safely: two candidates are told apart there only if th
 That is sound iff every key is within margin/2 of the true squared distance.  This test re-enacts the kernel's arithmetic
 in numpy (quantised mirror coordinates, query offset in units seen from the neighbour's corner, fma-accumulated squares,
 5 mantissa bits dropped for the integer tournament) on random queries / map points over the whole 27-voxel neighbourhood
-and checks the documented error model (search_params() in kicp_kernels.hpp) - including voxel sizes that are not
+and checks the documented error model (search_params() in kicp_pass_params.hpp) - including voxel sizes that are not
 representable in fp32, points hugging the voxel's upper faces (where the 16-bit range is clamped) and thresholds larger
 than a voxel."""
 import numpy as np

@@ -1,4 +1,4 @@
-"""The query's offset from a neighbour voxel's corner (kicp_kernels.hpp::axis_from, query_from), without a GPU:
+"""The query's offset from a neighbour voxel's corner (kicp_pass_visit.hpp::axis_from, query_from), without a GPU:
 tests/cpp/query_from_test.cpp holds the three-instruction form to the float of the form it replaced, l - d 65536 from the integer
 component, for every shift and axis over all 2^16 integer offsets, fractions beside them and random offsets.  A host-only program of
 its own, built with the address and undefined-behaviour sanitizers."""

@@ -1,4 +1,4 @@
-"""The pass kernels' five terms through terms_to_fixed (kicp_kernels.hpp) against five to_fixed calls, without a GPU:
+"""The pass kernels' five terms through terms_to_fixed (kicp_pass_fixed.hpp) against five to_fixed calls, without a GPU:
 tests/cpp/terms_fixed_test.cpp compares all twenty limbs and the range flag at zeros, ties, both sides of the short path's limit 2^22,
 the range limit 2^43, NaN and infinities in every position, 10^5 random values per binade from 2^-45 to 2^44 and mixtures with one
 large term.  A host-only program of its own, built with the address and undefined-behaviour sanitizers."""

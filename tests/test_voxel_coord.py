@@ -1,4 +1,4 @@
-"""PointToVoxel with a constant guard, and the lane offsets taken from its fraction (kicp_kernels.hpp::voxel_coord, voxel_coord_offset),
+"""PointToVoxel with a constant guard, and the lane offsets taken from its fraction (kicp_pass_visit.hpp::voxel_coord, voxel_coord_offset),
 without a GPU: tests/cpp/voxel_coord_test.cpp holds them to the formula they replaced, to the reference's floor(c / vs) and to the error
 bound stated above start_lane, at voxel faces -+ 0 .. 4 ulps for k up to 2^20, either side of the guard, random coordinates and
 |c / vs| just below 2^31.  A host-only program of its own, built with the address and undefined-behaviour sanitizers."""

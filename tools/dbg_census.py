@@ -1,4 +1,4 @@
-"""The generic pass kernel taken apart with the ablation switches of kicp_kernels.hpp (option "dbg").  The switches exist in
+"""The generic pass kernel taken apart with the ablation switches of the pass kernels (option "dbg"; kicp_pass_params.hpp::dbg_is).  The switches exist in
 libkicp_amd_dbg.so only (make -C kinematic_icp_amd/csrc dbg, built by __graft_entry__.build()): the production library's kernels
 carry none of them.  bench.py runs this script in a process of its own for two figures of its latency model:
 
