@@ -551,6 +551,32 @@ int kicp_grid_occupancy_from_counts(const unsigned short *counts, size_t cells, 
 int kicp_grid_save_map(const kicp_grid *grid, const char *prefix, unsigned int min_observations, double occupied_thresh, double free_thresh);
 int kicp_grid_write_map(const char *prefix, const signed char *occupancy, unsigned int width, unsigned int height, double cell, double origin_x,
                         double origin_y, double occupied_thresh, double free_thresh);
+/* THE FILL: the unknown cells of one grid from the readout of another - what puts the free space this grid's rays carve under a grid of
+ * classes that kicp_elev_to_grid* wrote (uneven ground, below), as a step of its own between two grids.  With the fill configuration
+ * min_observations >= 1, free_max <= 100 and free_max < occupied_min <= 101 (KICP_ERR_ARG otherwise; occupied_min = 101 never takes
+ * the source's obstacles), a SOURCE cell with counters (hits, misses) reads v = the readout above at min_observations; it is FREE when
+ * 0 <= v <= free_max, OCCUPIED when v >= occupied_min, and otherwise says nothing.  A DESTINATION cell is unknown when both its
+ * counters are 0, an obstacle when hits > 0, otherwise traversable.  The fill changes only unknown destination cells: to (hits 0,
+ * misses 1) where the source is FREE, to (1, 0) where it is OCCUPIED; every other counter keeps its bits, so the destination always
+ * wins where it knows something.  out_counts (nullable) is seven words (KICP_GRID_FILL_COUNTS): kept obstacle, kept traversable,
+ * filled free, filled occupied, left unknown - these five sum to the cell count - and two disagreements, as diagnostics: traversable
+ * over a source OCCUPIED, and obstacle over a source FREE.  A second call leaves the counters as the first left them and counts the
+ * filled cells as kept.
+ * kicp_grid_fill_unknown: dst != src, their cell, origin_x, origin_y, width and height bit-equal, both on the same device (KICP_ERR_ARG
+ * otherwise, and nothing is written).  src is not changed.  For dst the counters change as under kicp_grid_set_counts - the frame
+ * count and the last window stay -, and BESIDE THAT THE PLAN IS INVALIDATED (kicp_grid_has_plan reads 0): the fill is the last step
+ * of the chain that prepares the counters a new plan is made on, and a plan of the unfilled grid must not be scored by accident.  The
+ * call returns after its kernel has completed.  kicp_grid_fill_unknown_counts is the same arithmetic as pure host code over counters
+ * in kicp_grid_counts' layout (dst_counts != src_counts; null pointers only with cells == 0) and needs no GPU. */
+typedef struct kicp_grid_fill_config {
+    unsigned int min_observations; /* >= 1: the source's readout */
+    unsigned int free_max;         /* 0 .. 100: a source value of 0 .. free_max is FREE */
+    unsigned int occupied_min;     /* free_max < occupied_min <= 101: a source value of occupied_min or more is OCCUPIED */
+} kicp_grid_fill_config;
+#define KICP_GRID_FILL_COUNTS 7
+int kicp_grid_fill_unknown(kicp_grid *dst, const kicp_grid *src, const kicp_grid_fill_config *config, unsigned long long out_counts[7]);
+int kicp_grid_fill_unknown_counts(unsigned short *dst_counts, const unsigned short *src_counts, size_t cells, const kicp_grid_fill_config *config,
+                                  unsigned long long out_counts[7]);
 
 /* ---- what a planner plans on: the clearance of every cell and a Nav2-style costmap of the grid (kicp_grid_plan.hip) --------------------
  * Everything below is exact and integer: squared cell distances, and a lookup table for the cost.
@@ -939,6 +965,35 @@ int kicp_grid_gain(const kicp_grid *grid, const kicp_gain_config *config, const 
  * floor(((max_tangent cell) / slab) 1024), each operation rounded on its own; KICP_ERR_ARG when that is not finite, is negative or
  * exceeds 65 535 (of the configuration only cell and slab are read: positive and finite).
  *
+ * ROUGH.  BODY, STEP and SLOPE do not look at how badly the grounds fit the plane: rubble whose neighbouring grounds differ by less
+ * than S slabs around a level plane passes all three.  kicp_elev_traversability_rough adds the class ROUGH from the residual of the SAME
+ * fit: the fit set, the window, the gate, min_cells and "HAS A FIT" are the slope limit's, unchanged.  A tenth sum is taken over the fit
+ * set, Szz = sum z^2 (at most 289 * 63^2 = 1 147 041), and a fourth determinant, the intercept's:
+ *   Dc = Sxx (Syy Sz - Sy Syz) - Sxy (Sxy Sz - Sx Syz) + Sxz (Sxy Sy - Syy Sx)
+ *   Q  = D Szz - Da Sxz - Db Syz - Dc Sz
+ * Q is D times the residual sum of squares of the fit set to its least-squares plane: in exact arithmetic 0 <= Q <= D Szz < 2^55.  With
+ * the rough configuration num (0 .. 65535) and den (1 .. 65535) (KICP_ERR_ARG otherwise) a cell is
+ *   ROUGH when it has a fit and Q den > num n D - strictly, on exact integers, without a division or floating point:
+ * the mean squared residual exceeds num / den slabs^2.  The value of a cell is -1 when it is unknown, 100 when BODY, STEP, SLOPE or
+ * ROUGH, else 0; BODY, STEP and SLOPE are exactly as above, so wherever a cell is not "ROUGH only" its value equals
+ * kicp_elev_traversability_slope's.  out_counts (nullable) is six words (KICP_ELEV_ROUGH_COUNTS): unknown, traversable, BODY, STEP only,
+ * SLOPE only, ROUGH only - ROUGH without BODY, STEP or SLOPE.  out_fit (nullable): w * h times five values D, Da, Db, Q, n, all zero where
+ * the cell has no fit; the first three equal the slope entry's triple.  The widths, at L = 8 and K = 63: |Sx|, |Sy| <= 612 < 2^10, Sxx,
+ * Syy, |Sxy| < 2^13, |Sz| < 2^15, |Sxz|, |Syz| < 2^17, Szz < 2^21, so each of Dc's three terms stays below 2^42 and |Dc| < 2^44; the four
+ * products of Q stay below 2^55 (D Szz), 2^58 (Da Sxz, Db Syz) and 2^59 (Dc Sz), together below 2^61, so Q is formed in 64-bit
+ * integers with no partial sum near the sign bit.  Q den reaches 2^71 and is a 128-bit product; num n D stays below 2^59.  The
+ * rectangle and window rules are the slope limit's: a rectangle's result equals the full layer's restricted to it, and a frame changes
+ * results only inside kicp_elev_last_window grown by max(1, L).  kicp_elev_traversability_rough_from_columns is the same arithmetic as
+ * pure host code and needs no GPU; kicp_elev_to_grid_rough follows kicp_elev_to_grid's rules - the same checks, the same counters
+ * written.  kicp_elev_rough_limit turns an r.m.s. residual in metres into a limit for a layer's slab: den = 1024 and num =
+ * floor(((rms / slab) (rms / slab)) 1024), each operation rounded on its own; KICP_ERR_ARG when that is not finite, is negative or
+ * exceeds 65 535 (of the configuration only slab is read: positive and finite).
+ *
+ * WHAT THE LAYER DOES NOT KNOW.  The layer knows only cells that returned a point; between a lidar's rings most of the floor is
+ * unknown to it, while the mapping grid's rays have carved those cells free.  kicp_grid_fill_unknown (with the grid, above) fills the
+ * unknown cells of the grid that kicp_elev_to_grid* wrote from the mapping grid, on the GPU, and never changes a cell the layer knows.
+ * A filled cell has no ground, so it takes no part in STEP or in a fit, and a hole that the rays cross is free, as it is in the grid.
+ *
  * CARVING ALONG THE FRAME'S RAYS.  kicp_elev_integrate only ever sets bits.  An UPDATE of a frame (kicp_elev_update*) is a CARVE - bits
  * that the frame's rays pass through are cleared - and then the mark that kicp_elev_integrate does, so a frame's own returns always
  * survive it.  With the carve configuration G = margin_steps, W = widen_slabs (0 .. 64) and keep_ground (0 or 1; KICP_ERR_ARG
@@ -972,8 +1027,7 @@ int kicp_grid_gain(const kicp_grid *grid, const kicp_gain_config *config, const 
  * carve.  With keep_ground, a cell whose floor was never seen keeps a passer-by's lowest bit until a floor return arrives; without it
  * grazing rays erode the floor.  One spurious low return lowers a cell's ground for good: keep_ground keeps exactly that bit.  A cell that has only
  * ever returned an overhang, its ground unseen, reads as a high ground and is marked STEP until a ground return arrives - conservative
- * by choice.  The slope limit is a class, not a cost, and it has no roughness measure - the residual to the fitted plane is not looked
- * at - and no robustness to outliers beyond the gate; there is no merge with the free space the grid's rays carve.
+ * by choice.  SLOPE and ROUGH are classes, not costs, and the fit has no robustness to outliers beyond the gate.
  *
  * Limits: width * height <= 2^28 and reach <= 4095 (KICP_ERR_CAPACITY, the size in the message); cell, max_ray and slab positive and
  * finite, the origin and z_origin finite, width and height >= 1, no null pointer but the nullable outputs (KICP_ERR_ARG).  Every
@@ -1045,6 +1099,23 @@ int kicp_elev_traversability_slope_from_columns(const unsigned long long *column
 int kicp_elev_to_grid_slope(const kicp_elev *elev, const kicp_elev_traversability_config *config, const kicp_elev_slope_config *slope_config,
                             kicp_grid *grid);
 int kicp_elev_slope_limit(const kicp_elev_config *config, double max_tangent, unsigned int *rise_slabs, unsigned int *run_cells);
+/* ROUGH (above): the traversability with the classes SLOPE and ROUGH from the plane fit and its residual. */
+typedef struct kicp_elev_rough_config {
+    unsigned int num; /* 0 .. 65535 */
+    unsigned int den; /* 1 .. 65535: the limit is a mean squared residual of num / den slabs^2 */
+} kicp_elev_rough_config;
+#define KICP_ELEV_ROUGH_COUNTS 6
+int kicp_elev_traversability_rough(const kicp_elev *elev, const kicp_elev_traversability_config *config, const kicp_elev_slope_config *slope_config,
+                                   const kicp_elev_rough_config *rough_config, unsigned int x0, unsigned int y0, unsigned int w, unsigned int h,
+                                   signed char *out, unsigned char *out_ground, long long *out_fit, unsigned long long out_counts[6], size_t cap);
+int kicp_elev_traversability_rough_from_columns(const unsigned long long *columns, unsigned int width, unsigned int height,
+                                                const kicp_elev_traversability_config *config, const kicp_elev_slope_config *slope_config,
+                                                const kicp_elev_rough_config *rough_config, unsigned int x0, unsigned int y0, unsigned int w,
+                                                unsigned int h, signed char *out, unsigned char *out_ground, long long *out_fit,
+                                                unsigned long long out_counts[6], size_t cap);
+int kicp_elev_to_grid_rough(const kicp_elev *elev, const kicp_elev_traversability_config *config, const kicp_elev_slope_config *slope_config,
+                            const kicp_elev_rough_config *rough_config, kicp_grid *grid);
+int kicp_elev_rough_limit(const kicp_elev_config *config, double rms_metres, unsigned int *num, unsigned int *den);
 
 /* ---- map points the new frame sees through: a cube-map depth test (kicp_view.hip) ----------------------------------------------------
  * The local map loses points by distance only (RemovePointsFarFromLocation); whatever stood in view for one frame - a person crossing,

@@ -113,6 +113,18 @@ class ElevationSlopeConfig(C.Structure):
     _fields_ = [("radius_cells", C.c_uint), ("gate_slabs", C.c_uint), ("min_cells", C.c_uint), ("rise_slabs", C.c_uint), ("run_cells", C.c_uint)]
 
 
+class ElevationRoughConfig(C.Structure):
+    """kicp_elev_rough_config: the class ROUGH of the slope limit's plane fit - a cell with a fit is ROUGH when the mean squared residual
+    of its fit set to the fitted plane exceeds num (0 .. 65535) / den (1 .. 65535) slabs^2"""
+    _fields_ = [("num", C.c_uint), ("den", C.c_uint)]
+
+
+class GridFillConfig(C.Structure):
+    """kicp_grid_fill_config: how OccupancyGrid.fill_unknown reads its source - the readout at min_observations (>= 1) is FREE at
+    0 .. free_max (<= 100), OCCUPIED from occupied_min (free_max < occupied_min <= 101; 101: never) and otherwise says nothing"""
+    _fields_ = [("min_observations", C.c_uint), ("free_max", C.c_uint), ("occupied_min", C.c_uint)]
+
+
 class ViewConfig(C.Structure):
     """kicp_view_config: a cube map of res x res pixels per face; the verdict looks at (2 window + 1)^2 pixels, needs min_rays returns
     among them and a gap of more than margin + margin_per_metre * depth; max_ray bounds the (Chebyshev) depth on both sides"""
@@ -273,6 +285,16 @@ _SIGNATURES = {
                                                               C.POINTER(C.c_longlong), C.POINTER(C.c_ulonglong), C.c_size_t]),
     "kicp_elev_to_grid_slope": (C.c_int, [C.c_void_p, C.POINTER(ElevationTraversabilityConfig), C.POINTER(ElevationSlopeConfig), C.c_void_p]),
     "kicp_elev_slope_limit": (C.c_int, [C.POINTER(ElevationConfig), C.c_double, C.POINTER(C.c_uint), C.POINTER(C.c_uint)]),
+    "kicp_elev_traversability_rough": (C.c_int, [C.c_void_p, C.POINTER(ElevationTraversabilityConfig), C.POINTER(ElevationSlopeConfig), C.POINTER(ElevationRoughConfig),
+                                                 C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.POINTER(C.c_byte), C.POINTER(C.c_ubyte), C.POINTER(C.c_longlong),
+                                                 C.POINTER(C.c_ulonglong), C.c_size_t]),
+    "kicp_elev_traversability_rough_from_columns": (C.c_int, [C.POINTER(C.c_ulonglong), C.c_uint, C.c_uint, C.POINTER(ElevationTraversabilityConfig),
+                                                              C.POINTER(ElevationSlopeConfig), C.POINTER(ElevationRoughConfig), C.c_uint, C.c_uint, C.c_uint, C.c_uint,
+                                                              C.POINTER(C.c_byte), C.POINTER(C.c_ubyte), C.POINTER(C.c_longlong), C.POINTER(C.c_ulonglong), C.c_size_t]),
+    "kicp_elev_to_grid_rough": (C.c_int, [C.c_void_p, C.POINTER(ElevationTraversabilityConfig), C.POINTER(ElevationSlopeConfig), C.POINTER(ElevationRoughConfig), C.c_void_p]),
+    "kicp_elev_rough_limit": (C.c_int, [C.POINTER(ElevationConfig), C.c_double, C.POINTER(C.c_uint), C.POINTER(C.c_uint)]),
+    "kicp_grid_fill_unknown": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(GridFillConfig), C.POINTER(C.c_ulonglong)]),
+    "kicp_grid_fill_unknown_counts": (C.c_int, [C.POINTER(C.c_ushort), C.POINTER(C.c_ushort), C.c_size_t, C.POINTER(GridFillConfig), C.POINTER(C.c_ulonglong)]),
     "kicp_planar_grid": (C.c_size_t,[_dp, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _dp, C.c_size_t]),
     "kicp_map_save_pcd": (C.c_int, [C.c_void_p, C.c_char_p]),
     "kicp_map_load_pcd": (C.c_int, [C.c_char_p, C.c_double, C.c_double, C.c_uint, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]),
@@ -887,12 +909,13 @@ def _slope_config(slope):
     return ElevationSlopeConfig(*[int(v) for v in slope])
 
 
-def _traversability_slope_call(call, w, h, return_ground, return_fit, return_counts):
-    """_traversability_call for the two entries with the slope limit: the fit is int64 (h, w, 3) - D, Da, Db - and the counts are five"""
+def _traversability_slope_call(call, w, h, return_ground, return_fit, return_counts, fit_values=3, count_words=5):
+    """_traversability_call for the entries with a plane fit: the fit is int64 (h, w, 3) - D, Da, Db - and the counts are five; with
+    ROUGH (h, w, 5) - D, Da, Db, Q, n - and six"""
     out = np.empty((h, w), dtype=np.int8)
     ground = np.empty((h, w), dtype=np.uint8) if return_ground else None
-    fit = np.empty((h, w, 3), dtype=np.int64) if return_fit else None
-    counts = np.zeros(5, dtype=np.uint64)
+    fit = np.empty((h, w, fit_values), dtype=np.int64) if return_fit else None
+    counts = np.zeros(count_words, dtype=np.uint64)
     _check(call(out.ctypes.data_as(C.POINTER(C.c_byte)), ground.ctypes.data_as(C.POINTER(C.c_ubyte)) if return_ground else None,
                 fit.ctypes.data_as(C.POINTER(C.c_longlong)) if return_fit else None, counts.ctypes.data_as(C.POINTER(C.c_ulonglong)) if return_counts else None, out.size))
     if not (return_ground or return_fit or return_counts):
@@ -922,6 +945,52 @@ def elev_slope_limit(cell, slab, max_tangent):
     cfg, rise, run = ElevationConfig(float(cell), 0.0, 0.0, 0, 0, 0.0, float(slab), 0.0), C.c_uint(), C.c_uint()
     _check(lib().kicp_elev_slope_limit(C.byref(cfg), float(max_tangent), C.byref(rise), C.byref(run)))
     return rise.value, run.value
+
+
+def _rough_config(rough):
+    """an ElevationRoughConfig, or (num, den), or a dict with those fields"""
+    if isinstance(rough, ElevationRoughConfig):
+        return rough
+    if isinstance(rough, dict):
+        rough = [rough[name] for name, _ in ElevationRoughConfig._fields_]
+    return ElevationRoughConfig(*[int(v) for v in rough])
+
+
+def traversability_rough_from_columns(columns, step_slabs, robot_slabs, slope, rough, rect=None, return_ground=False, return_fit=False, return_counts=False):
+    """kicp_elev_traversability_rough_from_columns: traversability_slope_from_columns with the class ROUGH - a cell with a fit is also an
+    obstacle when the mean squared residual of its fit set to the fitted plane exceeds rough.num / rough.den slabs^2 (include/kicp.h
+    states Q).  rough: an ElevationRoughConfig, or (num, den), or a dict.  return_fit adds int64 (h, w, 5): D, Da, Db, Q, n - the mean
+    squared residual is Q / (n D) -, zeros where a cell has no fit; return_counts adds (unknown, traversable, BODY, STEP only, SLOPE
+    only, ROUGH only).  Pure host code: needs no GPU."""
+    c = np.ascontiguousarray(columns, dtype=np.uint64)
+    if c.ndim != 2 or c.size == 0:
+        raise KicpError(KICP_ERR_ARG, "columns must be shaped (height, width), both at least 1")
+    x0, y0, w, h = _rect(rect, c.shape[1], c.shape[0])
+    cfg, scfg, rcfg = ElevationTraversabilityConfig(int(step_slabs), int(robot_slabs)), _slope_config(slope), _rough_config(rough)
+    return _traversability_slope_call(lambda o, g, f, n, cap: lib().kicp_elev_traversability_rough_from_columns(
+        c.ctypes.data_as(C.POINTER(C.c_ulonglong)), c.shape[1], c.shape[0], C.byref(cfg), C.byref(scfg), C.byref(rcfg), x0, y0, w, h, o, g, f, n, cap), w, h, return_ground,
+        return_fit, return_counts, 5, 6)
+
+
+def elev_rough_limit(slab, rms_metres):
+    """kicp_elev_rough_limit: -> (num, den) of the ROUGH limit whose r.m.s. residual is rms_metres on slabs of `slab` metres: den = 1024,
+    num = floor((rms_metres / slab)^2 * 1024)"""
+    cfg, num, den = ElevationConfig(0.0, 0.0, 0.0, 0, 0, 0.0, float(slab), 0.0), C.c_uint(), C.c_uint()
+    _check(lib().kicp_elev_rough_limit(C.byref(cfg), float(rms_metres), C.byref(num), C.byref(den)))
+    return num.value, den.value
+
+
+def fill_unknown_counts(dst_counts, src_counts, min_observations=1, free_max=25, occupied_min=101, return_counts=False):
+    """kicp_grid_fill_unknown_counts: OccupancyGrid.fill_unknown as pure host code over counters in counts()' layout - uint16 (..., 2),
+    the same shape - -> the destination's counters after the fill, a new array (the arguments are not changed); return_counts adds
+    the seven counts.  Needs no GPU."""
+    d, s = np.array(dst_counts, dtype=np.uint16, order="C"), np.ascontiguousarray(src_counts, dtype=np.uint16)
+    if d.shape != s.shape or d.size % 2:
+        raise KicpError(KICP_ERR_ARG, "the two arrays must have one shape and hold (hits, misses) pairs")
+    cfg, counts = GridFillConfig(int(min_observations), int(free_max), int(occupied_min)), np.zeros(7, dtype=np.uint64)
+    _check(lib().kicp_grid_fill_unknown_counts(d.ctypes.data_as(C.POINTER(C.c_ushort)), s.ctypes.data_as(C.POINTER(C.c_ushort)), d.size // 2, C.byref(cfg),
+                                               counts.ctypes.data_as(C.POINTER(C.c_ulonglong)) if return_counts else None))
+    return (d, tuple(int(v) for v in counts)) if return_counts else d
 
 
 def elev_update_columns(config, columns, frame, pose, sensor_xyz=(0.0, 0.0, 0.0), margin_steps=2, widen_slabs=1, keep_ground=1):
@@ -998,6 +1067,17 @@ class OccupancyGrid:
         if c.size % 2:
             raise KicpError(KICP_ERR_ARG, "counts must hold (hits, misses) pairs")
         _check(lib().kicp_grid_set_counts(self._h, c.ctypes.data_as(C.POINTER(C.c_ushort)), c.size // 2))
+
+    def fill_unknown(self, src, min_observations=1, free_max=25, occupied_min=101, return_counts=False):
+        """kicp_grid_fill_unknown: on the GPU, the unknown cells of this grid - both counters 0 - become traversable (0, 1) where `src`,
+        an OccupancyGrid of the same geometry, reads 0 .. free_max at min_observations, and obstacles (1, 0) where it reads occupied_min
+        or more (101: never); every other counter keeps its bits, `src` is not changed, and the plan of this grid is invalidated.
+        return_counts -> (kept obstacle, kept traversable, filled free, filled occupied, left unknown, traversable over a source
+        OCCUPIED, obstacle over a source FREE)"""
+        cfg, counts = GridFillConfig(int(min_observations), int(free_max), int(occupied_min)), np.zeros(7, dtype=np.uint64)
+        _check(lib().kicp_grid_fill_unknown(self._h, src._h if src is not None else None, C.byref(cfg),
+                                            counts.ctypes.data_as(C.POINTER(C.c_ulonglong)) if return_counts else None))
+        return tuple(int(v) for v in counts) if return_counts else None
 
     def occupancy(self, min_observations=1):
         """kicp_grid_occupancy: the readout on the GPU -> int8 (height, width): -1 unknown, else 0 .. 100 - a nav_msgs/OccupancyGrid's data"""
@@ -1216,6 +1296,23 @@ class ElevationLayer:
         """kicp_elev_to_grid_slope: to_grid with the slope limit - a SLOPE cell is an obstacle (1, 0) like a BODY or STEP one"""
         cfg, scfg = ElevationTraversabilityConfig(int(step_slabs), int(robot_slabs)), _slope_config(slope)
         _check(lib().kicp_elev_to_grid_slope(self._h, C.byref(cfg), C.byref(scfg), grid._h))
+
+    def traversability_rough(self, step_slabs, robot_slabs, slope, rough, rect=None, return_ground=False, return_fit=False, return_counts=False):
+        """kicp_elev_traversability_rough: on the GPU, traversability_rough_from_columns' result on the columns where they are; a frame
+        changes it only inside last_window() grown by max(1, slope.radius_cells) cells"""
+        x0, y0, w, h = _rect(rect, self.width, self.height)
+        cfg, scfg, rcfg = ElevationTraversabilityConfig(int(step_slabs), int(robot_slabs)), _slope_config(slope), _rough_config(rough)
+        return _traversability_slope_call(lambda o, g, f, n, cap: lib().kicp_elev_traversability_rough(self._h, C.byref(cfg), C.byref(scfg), C.byref(rcfg), x0, y0, w, h, o, g,
+                                                                                                       f, n, cap), w, h, return_ground, return_fit, return_counts, 5, 6)
+
+    def to_grid_rough(self, grid, step_slabs, robot_slabs, slope, rough):
+        """kicp_elev_to_grid_rough: to_grid_slope with the class ROUGH - a ROUGH cell is an obstacle (1, 0) too"""
+        cfg, scfg, rcfg = ElevationTraversabilityConfig(int(step_slabs), int(robot_slabs)), _slope_config(slope), _rough_config(rough)
+        _check(lib().kicp_elev_to_grid_rough(self._h, C.byref(cfg), C.byref(scfg), C.byref(rcfg), grid._h))
+
+    def rough_limit(self, rms_metres):
+        """elev_rough_limit for this layer's slab -> (num, den)"""
+        return elev_rough_limit(self.info()["slab"], rms_metres)
 
     def slope_limit(self, max_tangent):
         """elev_slope_limit for this layer's cell and slab -> (rise_slabs, run_cells)"""

@@ -237,6 +237,12 @@ using ElevationCarveStats = std::array<unsigned long long, KICP_ELEV_UPDATE_STAT
 // what KinematicICP::ElevationTraversabilitySlope takes beside the traversability configuration: radius_cells, gate_slabs, min_cells,
 // rise_slabs, run_cells of the plane fit (kicp.h THE SLOPE LIMIT); KinematicICP::ElevationSlopeLimit fills the last two from a tangent
 using ElevationSlopeConfig = kicp_elev_slope_config;
+// what KinematicICP::ElevationTraversabilityRough adds to that: num / den slabs^2, the limit of the fit's mean squared residual (kicp.h
+// ROUGH); KinematicICP::ElevationRoughLimit makes one from an r.m.s. residual in metres.  GridFillConfig is what
+// KinematicICP::ElevationIntoGrid takes to fill the planner's grid from the pipeline's own (kicp.h THE FILL), GridFillCounts its seven words.
+using ElevationRoughConfig = kicp_elev_rough_config;
+using GridFillConfig = kicp_grid_fill_config;
+using GridFillCounts = std::array<unsigned long long, KICP_GRID_FILL_COUNTS>;
 inline std::shared_ptr<kicp_elev> make_elevation(const ElevationConfig &config, int device = -1) {
     kicp_elev *elev = nullptr;
     check(kicp_elev_create(&config, device < 0 ? default_device() : device, &elev), "kicp_bridge::make_elevation");

@@ -543,6 +543,56 @@ public:
         kicp_bridge::check(kicp_elev_slope_limit(&layer, max_tangent, &slope.rise_slabs, &slope.run_cells), "ElevationSlopeLimit");
         return slope;
     }
+    // The same with the class ROUGH (kicp.h ROUGH): a cell with a fit is also an obstacle when the mean squared residual of its fit set to
+    // the fitted plane exceeds rough.num / rough.den slabs^2.  counts (nullable): unknown, traversable, BODY, STEP only, SLOPE only, ROUGH
+    // only; fit (nullable): D, Da, Db, Q, n per cell, zeros without a fit.  The window rule and the errors are the slope entry's.
+    void ElevationTraversabilityRough(const kicp_bridge::ElevationTraversabilityConfig &config, const kicp_bridge::ElevationSlopeConfig &slope,
+                                      const kicp_bridge::ElevationRoughConfig &rough, std::vector<int8_t> &data, const kicp_bridge::GridRect *rect = nullptr,
+                                      std::vector<uint8_t> *ground = nullptr, std::array<unsigned long long, KICP_ELEV_ROUGH_COUNTS> *counts = nullptr,
+                                      std::vector<long long> *fit = nullptr) const {
+        const kicp_elev *elev = RequireElevation("ElevationTraversabilityRough");
+        kicp_bridge::GridRect r;
+        if (rect) {
+            r = *rect;
+        } else {
+            kicp_elev_config layer{};
+            kicp_bridge::check(kicp_elev_info(elev, &layer, nullptr, nullptr), "ElevationTraversabilityRough");
+            r.w = layer.width, r.h = layer.height;
+        }
+        data.resize(static_cast<size_t>(r.w) * r.h);
+        if (ground) ground->resize(data.size());
+        if (fit) fit->resize(5 * data.size());
+        kicp_bridge::check(kicp_elev_traversability_rough(elev, &config, &slope, &rough, r.x0, r.y0, r.w, r.h, reinterpret_cast<signed char *>(data.data()),
+                                                          ground ? ground->data() : nullptr, fit ? fit->data() : nullptr, counts ? counts->data() : nullptr, data.size()),
+                           "ElevationTraversabilityRough");
+    }
+    // the ROUGH limit of an r.m.s. residual in metres on this layer's slab (kicp_elev_rough_limit)
+    kicp_bridge::ElevationRoughConfig ElevationRoughLimit(double rms_metres) const {
+        kicp_elev_config layer{};
+        kicp_bridge::ElevationRoughConfig rough{};
+        kicp_bridge::check(kicp_elev_info(RequireElevation("ElevationRoughLimit"), &layer, nullptr, nullptr), "ElevationRoughLimit");
+        kicp_bridge::check(kicp_elev_rough_limit(&layer, rms_metres, &rough.num, &rough.den), "ElevationRoughLimit");
+        return rough;
+    }
+    // A node's call after a frame: the layer's classes into the grid it dedicates to its planner (same cell, origin, width and height as
+    // the layer, same device) - kicp_elev_to_grid without `slope`, kicp_elev_to_grid_slope with it, kicp_elev_to_grid_rough with `slope`
+    // and `rough` (`rough` without `slope`: std::invalid_argument) -, and with `fill` the cells the layer does not know from the
+    // pipeline's own occupancy grid (kicp_grid_fill_unknown; needs EnableGrid), whose seven words go to fill_counts (nullable).  Never
+    // called inside RegisterFrame: the node decides when it plans.
+    void ElevationIntoGrid(kicp_grid *planner_grid, const kicp_bridge::ElevationTraversabilityConfig &config, const kicp_bridge::ElevationSlopeConfig *slope = nullptr,
+                           const kicp_bridge::ElevationRoughConfig *rough = nullptr, const kicp_bridge::GridFillConfig *fill = nullptr,
+                           kicp_bridge::GridFillCounts *fill_counts = nullptr) const {
+        const kicp_elev *elev = RequireElevation("ElevationIntoGrid");
+        if (rough && !slope) throw std::invalid_argument("KinematicICP::ElevationIntoGrid: rough needs slope - ROUGH is the residual of the slope limit's fit");
+        const kicp_grid *source = fill ? RequireGrid("ElevationIntoGrid") : nullptr;
+        if (rough)
+            kicp_bridge::check(kicp_elev_to_grid_rough(elev, &config, slope, rough, planner_grid), "ElevationIntoGrid");
+        else if (slope)
+            kicp_bridge::check(kicp_elev_to_grid_slope(elev, &config, slope, planner_grid), "ElevationIntoGrid");
+        else
+            kicp_bridge::check(kicp_elev_to_grid(elev, &config, planner_grid), "ElevationIntoGrid");
+        if (fill) kicp_bridge::check(kicp_grid_fill_unknown(planner_grid, source, fill, fill_counts ? fill_counts->data() : nullptr), "ElevationIntoGrid");
+    }
     // the window of the last integrated frame clipped to the layer; empty() when it lies outside, and before any frame
     kicp_bridge::GridRect ElevationLastWindow() const {
         kicp_bridge::GridRect r;

@@ -27,13 +27,13 @@ struct kicp_elev {
         FrameUpload upload;  // kicp_elev_integrate's points
         DevBuf<unsigned long long> d_rays;  // kicp_elev_update*: the carve list, room for one record per point
     } frame;
-    // kicp_elev_traversability: the classes, the ground bytes and the four counts in their shards
+    // kicp_elev_traversability*: the classes, the ground bytes and the four, five or six counts in their shards
     mutable struct {
         DevBuf<int8_t> d_classes;
         DevBuf<uint8_t> d_ground;
         DevBuf<unsigned int> d_counts;
         PinnedBuf<unsigned int> h_counts;
-        DevBuf<long long> d_fit;  // kicp_elev_traversability_slope: D, Da, Db per cell
+        DevBuf<long long> d_fit;  // kicp_elev_traversability_slope: D, Da, Db per cell; kicp_elev_traversability_rough: D, Da, Db, Q, n
     } readout;
     ~kicp_elev() {
         if (stream) (void)hipStreamSynchronize(stream), (void)hipStreamDestroy(stream);
@@ -151,7 +151,26 @@ SlopeToGridKernel slope_to_grid_kernel(uint32_t radius) {
                                                              k_elev_slope_to_grid<5>, k_elev_slope_to_grid<6>, k_elev_slope_to_grid<7>, k_elev_slope_to_grid<8>};
     return k[radius - 1u];
 }
-// what kicp_elev_to_grid and kicp_elev_to_grid_slope ask of the grid: the layer's plane, on the layer's device
+int check_rough_config(const kicp_elev_rough_config *cfg, ElevRoughParams &p) {
+    p = ElevRoughParams{cfg->num, cfg->den};
+    if (cfg->num > kElevRoughMaxRatio) return fail(KICP_ERR_ARG, "num must lie in 0 .. 65535");
+    if (cfg->den < 1u || cfg->den > kElevRoughMaxRatio) return fail(KICP_ERR_ARG, "den must lie in 1 .. 65535");
+    return KICP_OK;
+}
+// the rough kernels' instantiation for L = radius, as the slope kernels'
+using RoughKernel = void (*)(const unsigned long long *, uint32_t, uint32_t, ElevParams, ElevSlopeParams, ElevRoughParams, ElevRect, uint32_t, int8_t *, uint8_t *, long long *,
+                             unsigned int *);
+using RoughToGridKernel = void (*)(const unsigned long long *, uint32_t, uint32_t, ElevParams, ElevSlopeParams, ElevRoughParams, ElevRect, uint32_t, uint16_t *);
+RoughKernel rough_kernel(uint32_t radius) {
+    static const RoughKernel k[kElevSlopeMaxRadius] = {k_elev_rough<1>, k_elev_rough<2>, k_elev_rough<3>, k_elev_rough<4>, k_elev_rough<5>, k_elev_rough<6>, k_elev_rough<7>, k_elev_rough<8>};
+    return k[radius - 1u];
+}
+RoughToGridKernel rough_to_grid_kernel(uint32_t radius) {
+    static const RoughToGridKernel k[kElevSlopeMaxRadius] = {k_elev_rough_to_grid<1>, k_elev_rough_to_grid<2>, k_elev_rough_to_grid<3>, k_elev_rough_to_grid<4>,
+                                                             k_elev_rough_to_grid<5>, k_elev_rough_to_grid<6>, k_elev_rough_to_grid<7>, k_elev_rough_to_grid<8>};
+    return k[radius - 1u];
+}
+// what kicp_elev_to_grid, kicp_elev_to_grid_slope and kicp_elev_to_grid_rough ask of the grid: the layer's plane, on the layer's device
 int check_to_grid(const kicp_elev *elev, const kicp_grid *grid) {
     const kicp_grid_config &gc = grid->cfg;
     const kicp_elev_config &ec = elev->cfg;
@@ -415,6 +434,92 @@ int kicp_elev_to_grid_slope(const kicp_elev *elev, const kicp_elev_traversabilit
                        ElevRect{0u, 0u, ec.width, ec.height}, tiles_x, grid->d_counts.get());
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(elev->stream));
+    return KICP_OK;
+}
+int kicp_elev_traversability_rough(const kicp_elev *elev, const kicp_elev_traversability_config *cfg, const kicp_elev_slope_config *slope,
+                                   const kicp_elev_rough_config *rough, unsigned int x0, unsigned int y0, unsigned int w, unsigned int h, signed char *out,
+                                   unsigned char *out_ground, long long *out_fit, unsigned long long out_counts[6], size_t cap) {
+    KICP_TRACE_CALL();
+    if (!elev || !cfg || !slope || !rough || !out) return fail(KICP_ERR_ARG, "null argument");
+    ElevParams p;
+    ElevSlopeParams sp;
+    ElevRoughParams rp;
+    const ElevRect r{x0, y0, w, h};
+    if (int rc = check_elev_params(cfg, p)) return rc;
+    if (int rc = check_slope_config(slope, sp)) return rc;
+    if (int rc = check_rough_config(rough, rp)) return rc;
+    if (int rc = check_elev_rect(elev->cfg.width, elev->cfg.height, r, cap)) return rc;
+    if (int rc = set_device(elev->device)) return rc;
+    auto &ro = elev->readout;
+    if (int rc = ro.d_classes.reserve(cap)) return rc;
+    if (out_ground)
+        if (int rc = ro.d_ground.reserve(cap)) return rc;
+    if (out_fit)
+        if (int rc = ro.d_fit.reserve(5 * cap)) return rc;
+    if (out_counts) {
+        if (int rc = ro.d_counts.reserve(kElevCountWords)) return rc;
+        if (int rc = ro.h_counts.reserve(kElevCountWords, hipHostMallocDefault, false)) return rc;
+    }
+    hipStream_t st = elev->stream;
+    if (out_counts) HIP_TRY(hipMemsetAsync(ro.d_counts.get(), 0, kElevCountWords * sizeof(unsigned int), st));
+    const uint32_t tiles_x = elev_tiles(w), tiles_y = elev_tiles(h);  // (their product stays below 2^25: cells <= 2^28)
+    hipLaunchKernelGGL(rough_kernel(sp.radius), dim3(tiles_x * tiles_y), dim3(kElevBlock), 0, st, elev->d_columns.get(), elev->cfg.width, elev->cfg.height, p, sp, rp, r, tiles_x,
+                       ro.d_classes.get(), out_ground ? ro.d_ground.get() : static_cast<uint8_t *>(nullptr), out_fit ? ro.d_fit.get() : static_cast<long long *>(nullptr),
+                       out_counts ? ro.d_counts.get() : static_cast<unsigned int *>(nullptr));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, ro.d_classes.get(), cap, hipMemcpyDeviceToHost, st));
+    if (out_ground) HIP_TRY(hipMemcpyAsync(out_ground, ro.d_ground.get(), cap, hipMemcpyDeviceToHost, st));
+    if (out_fit) HIP_TRY(hipMemcpyAsync(out_fit, ro.d_fit.get(), 5 * cap * sizeof(long long), hipMemcpyDeviceToHost, st));
+    if (out_counts) HIP_TRY(hipMemcpyAsync(ro.h_counts.get(), ro.d_counts.get(), kElevCountWords * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (out_counts)
+        for (int k = 0; k < KICP_ELEV_ROUGH_COUNTS; ++k) out_counts[k] = shard_sum(ro.h_counts.get(), k);
+    return KICP_OK;
+}
+int kicp_elev_traversability_rough_from_columns(const unsigned long long *columns, unsigned int width, unsigned int height, const kicp_elev_traversability_config *cfg,
+                                                const kicp_elev_slope_config *slope, const kicp_elev_rough_config *rough, unsigned int x0, unsigned int y0,
+                                                unsigned int w, unsigned int h, signed char *out, unsigned char *out_ground, long long *out_fit,
+                                                unsigned long long out_counts[6], size_t cap) {
+    if (!columns || !cfg || !slope || !rough || !out) return fail(KICP_ERR_ARG, "null argument");
+    ElevParams p;
+    ElevSlopeParams sp;
+    ElevRoughParams rp;
+    const ElevRect r{x0, y0, w, h};
+    if (int rc = check_elev_params(cfg, p)) return rc;
+    if (int rc = check_slope_config(slope, sp)) return rc;
+    if (int rc = check_rough_config(rough, rp)) return rc;
+    if (int rc = check_grid_dims(width, height)) return rc;
+    if (int rc = check_elev_rect(width, height, r, cap)) return rc;
+    elev_host::classify_rough(reinterpret_cast<const uint64_t *>(columns), width, height, p, sp, rp, r, reinterpret_cast<int8_t *>(out), out_ground, out_fit, out_counts);
+    return KICP_OK;
+}
+int kicp_elev_to_grid_rough(const kicp_elev *elev, const kicp_elev_traversability_config *cfg, const kicp_elev_slope_config *slope,
+                            const kicp_elev_rough_config *rough, kicp_grid *grid) {
+    KICP_TRACE_CALL();
+    if (!elev || !cfg || !slope || !rough || !grid) return fail(KICP_ERR_ARG, "null argument");
+    ElevParams p;
+    ElevSlopeParams sp;
+    ElevRoughParams rp;
+    if (int rc = check_elev_params(cfg, p)) return rc;
+    if (int rc = check_slope_config(slope, sp)) return rc;
+    if (int rc = check_rough_config(rough, rp)) return rc;
+    if (int rc = check_to_grid(elev, grid)) return rc;
+    if (int rc = set_device(elev->device)) return rc;
+    const kicp_elev_config &ec = elev->cfg;
+    const uint32_t tiles_x = elev_tiles(ec.width), tiles_y = elev_tiles(ec.height);  // (the streams: as kicp_elev_to_grid)
+    hipLaunchKernelGGL(rough_to_grid_kernel(sp.radius), dim3(tiles_x * tiles_y), dim3(kElevBlock), 0, elev->stream, elev->d_columns.get(), ec.width, ec.height, p, sp, rp,
+                       ElevRect{0u, 0u, ec.width, ec.height}, tiles_x, grid->d_counts.get());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(elev->stream));
+    return KICP_OK;
+}
+int kicp_elev_rough_limit(const kicp_elev_config *config, double rms_metres, unsigned int *num, unsigned int *den) {
+    if (!config || !num || !den) return fail(KICP_ERR_ARG, "null argument");
+    if (!(config->slab > 0.0) || !std::isfinite(config->slab)) return fail(KICP_ERR_ARG, "slab must be positive and finite");
+    const double limit = std::floor(((rms_metres / config->slab) * (rms_metres / config->slab)) * 1024.0);
+    if (!(limit >= 0.0 && limit <= static_cast<double>(kElevRoughMaxRatio)))  // (a NaN fails both)
+        return fail(KICP_ERR_ARG, "rms_metres gives a limit of " + std::to_string(limit) + " / 1024 slabs^2: it must be finite and lie in 0 .. 65535");
+    *num = static_cast<unsigned int>(limit), *den = 1024u;
     return KICP_OK;
 }
 int kicp_elev_slope_limit(const kicp_elev_config *config, double max_tangent, unsigned int *rise_slabs, unsigned int *run_cells) {

@@ -20,6 +20,9 @@
 //                    in 128-bit integers - adds the class SLOPE; the optional determinants and five counts are written.  One
 //                    instantiation per L, so that the walk unrolls
 //   k_elev_slope_to_grid<L>  that classification (elev_slope_cell, one device function for both) as a kicp_grid's counters
+//   k_elev_rough<L>  k_elev_slope<L>'s shape with a tenth sum, z^2: the residual of the fitted plane, Q, in 64-bit integers, compared as a
+//                    128-bit product, adds the class ROUGH; the optional D, Da, Db, Q, n and six counts are written
+//   k_elev_rough_to_grid<L>  that classification (elev_rough_cell, one device function for both) as a kicp_grid's counters
 // The atomics besides the OR and the AND are the statistics and the list's length: one add per wave per word that has something to add.
 // No kernel uses scratch; the mark, list and carve kernels use no LDS.
 #pragma once
@@ -326,6 +329,110 @@ static __global__ __launch_bounds__(kElevBlock) void k_elev_slope_to_grid(const 
     uint32_t which;
     int64_t d, da, db;
     if (!elev_slope_cell<L>(columns, width, height, p, sp, r, tiles_x, grounds, value, ground, which, d, da, db)) return;  // (behind the barrier)
+    const uint32_t x = (blockIdx.x % tiles_x) * kElevTile + threadIdx.x % kElevTile, y = (blockIdx.x / tiles_x) * kElevTile + threadIdx.x / kElevTile;
+    reinterpret_cast<uint32_t *>(grid_counts)[static_cast<size_t>(y) * width + x] = value < 0 ? 0u : value ? 1u : 0x10000u;
+}
+
+// ---- ROUGH (kicp_elev_traversability_rough, kicp_elev_to_grid_rough) ----------------------------------------------------------------
+// elev_slope_walk with the tenth sum.  A DEVICE FUNCTION OF ITS OWN, like elev_rough_cell below: the slope kernels keep the code they
+// were measured with, and the rough kernels repeat their shape.
+template <int L>
+static __device__ __forceinline__ void elev_rough_walk(const uint8_t *centre, uint32_t ground, uint32_t gate, ElevRoughSums &s) {
+    constexpr int32_t side = static_cast<int32_t>(kElevTile) + 2 * L;
+#pragma unroll
+    for (int32_t dy = -L; dy <= L; ++dy)
+#pragma unroll
+        for (int32_t dx = -L; dx <= L; ++dx) elev_rough_add(s, ground, centre[dy * side + dx], dx, dy, gate);
+}
+// elev_slope_cell with the class ROUGH: the same tile, the same halo of L cells staged the same way - EVERY LOAD BEHIND THE
+// INSIDE-THE-GRID TEST -, the same barrier that every lane of the workgroup reaches, unknown lanes skip the walk, every loop bounded by
+// L <= 8.  A cell with a fit also gets the residual Q (64-bit, by elev_rough_residual's bounds) and the 128-bit comparison.
+// -> inside: the cell lies in the rectangle; value, ground, which (elev_rough_value) and fit[5] = D, Da, Db, Q, n (zeros without a fit).
+template <int L>
+static __device__ __forceinline__ bool elev_rough_cell(const unsigned long long *__restrict__ columns, uint32_t width, uint32_t height, const ElevParams &p,
+                                                       const ElevSlopeParams &sp, const ElevRoughParams &rp, const ElevRect &r, uint32_t tiles_x, uint8_t *grounds,
+                                                       int8_t &value, uint8_t &ground, uint32_t &which, int64_t (&fit)[5]) {
+    static_assert(L >= 1 && L <= static_cast<int>(kElevSlopeMaxRadius), "the halo is 1 .. 8 cells");
+    constexpr uint32_t side = kElevTile + 2u * L;
+    const uint32_t tx = threadIdx.x % kElevTile, ty = threadIdx.x / kElevTile;
+    const uint32_t bx = r.x0 + (blockIdx.x % tiles_x) * kElevTile, by = r.y0 + (blockIdx.x / tiles_x) * kElevTile;  // the tile's corner: inside the rectangle
+    const uint32_t x = bx + tx, y = by + ty;
+    const bool inside = x - r.x0 < r.w && y - r.y0 < r.h;  // (inside the rectangle implies inside the grid)
+#pragma unroll
+    for (uint32_t k = threadIdx.x; k < side * side; k += kElevBlock) {  // at most four trips
+        const uint32_t hx = k % side, hy = k / side;
+        const int64_t gx = static_cast<int64_t>(bx) + hx - L, gy = static_cast<int64_t>(by) + hy - L;
+        const bool ok = gx >= 0 && gy >= 0 && gx < static_cast<int64_t>(width) && gy < static_cast<int64_t>(height);
+        grounds[k] = ok ? elev_ground(columns[static_cast<size_t>(gy) * width + static_cast<size_t>(gx)]) : kElevNoGround;
+    }
+    __syncthreads();
+    const uint8_t *centre = grounds + (ty + L) * side + (tx + L);
+    ground = *centre;
+    const bool known = ground != kElevNoGround;
+    bool body = false, step = false, slope = false, rough = false;
+    fit[0] = fit[1] = fit[2] = fit[3] = fit[4] = 0;
+    if (known) {  // (a known cell lies inside the grid: the load is behind that test)
+        body = elev_body(columns[static_cast<size_t>(y) * width + x], ground, p);
+#pragma unroll
+        for (int32_t dy = -1; dy <= 1; ++dy)
+#pragma unroll
+            for (int32_t dx = -1; dx <= 1; ++dx)
+                if (dx || dy) step = step || elev_step(ground, centre[dy * static_cast<int32_t>(side) + dx], p);
+        ElevRoughSums s{};
+        elev_rough_walk<L>(centre, ground, sp.gate, s);
+        int64_t d, da, db;
+        elev_slope_determinants(s.fit, d, da, db);
+        if (elev_slope_has_fit(s.fit, d, sp)) {
+            int64_t dc;
+            const int64_t q = elev_rough_residual(s, d, da, db, dc);
+            slope = elev_slope_exceeds(d, da, db, sp);
+            rough = elev_rough_exceeds(q, d, s.fit.n, rp);
+            fit[0] = d, fit[1] = da, fit[2] = db, fit[3] = q, fit[4] = s.fit.n;
+        }
+    }
+    value = elev_rough_value(known, body, step, slope, rough, which);
+    return inside;
+}
+
+// out / out_ground (nullable) / out_fit (nullable: D, Da, Db, Q, n per cell): r.h * r.w entries; counts (nullable): kElevCountShards x
+// kElevCountStride words, a wave adds unknown, traversable, BODY, STEP only, SLOPE only, ROUGH only to words 0 .. 5 of its shard
+template <int L>
+static __global__ __launch_bounds__(kElevBlock) void k_elev_rough(const unsigned long long *__restrict__ columns, uint32_t width, uint32_t height, ElevParams p,
+                                                                  ElevSlopeParams sp, ElevRoughParams rp, ElevRect r, uint32_t tiles_x, int8_t *__restrict__ out,
+                                                                  uint8_t *__restrict__ out_ground, long long *__restrict__ out_fit, unsigned int *__restrict__ counts) {
+    __shared__ uint8_t grounds[(kElevTile + 2u * L) * (kElevTile + 2u * L)];
+    int8_t value;
+    uint8_t ground;
+    uint32_t which;
+    int64_t fit[5];
+    const bool inside = elev_rough_cell<L>(columns, width, height, p, sp, rp, r, tiles_x, grounds, value, ground, which, fit);
+    if (inside) {
+        const uint32_t rx = (blockIdx.x % tiles_x) * kElevTile + threadIdx.x % kElevTile, ry = (blockIdx.x / tiles_x) * kElevTile + threadIdx.x / kElevTile;
+        const size_t o = static_cast<size_t>(ry) * r.w + rx;
+        out[o] = value;
+        if (out_ground) out_ground[o] = ground;
+        if (out_fit) {
+#pragma unroll
+            for (uint32_t k = 0; k < 5u; ++k) out_fit[5 * o + k] = fit[k];
+        }
+    }
+    if (counts) {
+        unsigned int *shard = elev_shard(counts);
+        for (uint32_t k = 0; k < 6u; ++k) elev_wave_add(&shard[k], inside && which == k);
+    }
+}
+
+// k_elev_to_grid with the classes SLOPE and ROUGH: the rectangle is the full grid
+template <int L>
+static __global__ __launch_bounds__(kElevBlock) void k_elev_rough_to_grid(const unsigned long long *__restrict__ columns, uint32_t width, uint32_t height, ElevParams p,
+                                                                          ElevSlopeParams sp, ElevRoughParams rp, ElevRect r, uint32_t tiles_x,
+                                                                          uint16_t *__restrict__ grid_counts) {
+    __shared__ uint8_t grounds[(kElevTile + 2u * L) * (kElevTile + 2u * L)];
+    int8_t value;
+    uint8_t ground;
+    uint32_t which;
+    int64_t fit[5];
+    if (!elev_rough_cell<L>(columns, width, height, p, sp, rp, r, tiles_x, grounds, value, ground, which, fit)) return;  // (behind the barrier)
     const uint32_t x = (blockIdx.x % tiles_x) * kElevTile + threadIdx.x % kElevTile, y = (blockIdx.x / tiles_x) * kElevTile + threadIdx.x / kElevTile;
     reinterpret_cast<uint32_t *>(grid_counts)[static_cast<size_t>(y) * width + x] = value < 0 ? 0u : value ? 1u : 0x10000u;
 }

@@ -1,10 +1,10 @@
 // kicp_elev_host.hpp -- the arithmetic of the height columns (kicp_elev_*, include/kicp.h): the class of one point, the ground of one
 // column, BODY and STEP of one cell, the slope limit - one window cell into the nine sums of a plane fit, its determinants and the
-// 128-bit comparison -, and the carve along a frame's rays: which points carve, the slab of a ray at a step, a step's mask
-// and what it clears of a column.  ONE text for the kernels (kicp_elev.hpp), for the pure-host entries
-// (kicp_elev_traversability_from_columns, kicp_elev_traversability_slope_from_columns, kicp_elev_update_columns) and for
-// elev_host::integrate / carve / update / classify / classify_slope, the host restatements that stand-alone programs run under
-// sanitizers (tests/cpp/elev_host_test.cpp, tests/cpp/elev_carve_host_test.cpp, tests/cpp/elev_slope_host_test.cpp).
+// 128-bit comparison -, ROUGH - a tenth sum, the fit's residual and its comparison -, and the carve along a frame's rays: which points
+// carve, the slab of a ray at a step, a step's mask and what it clears of a column.  ONE text for the kernels (kicp_elev.hpp), for the
+// pure-host entries (kicp_elev_traversability_from_columns, .._slope_from_columns, .._rough_from_columns, kicp_elev_update_columns) and
+// for elev_host::integrate / carve / update / classify / classify_slope / classify_rough, the host restatements that stand-alone
+// programs run under sanitizers (tests/cpp/elev_host_test.cpp, elev_carve_host_test.cpp, elev_slope_host_test.cpp, elev_rough_host_test.cpp).
 // Everything is exact and integer from the floor on.
 #pragma once
 #include "kicp_grid_host.hpp"
@@ -129,8 +129,50 @@ KICP_HD int8_t elev_slope_value(bool known, bool body, bool step, bool slope, ui
     return !known ? static_cast<int8_t>(-1) : static_cast<int8_t>((body || step || slope) ? 100 : 0);
 }
 
+// ---- ROUGH: the residual of that plane fit (kicp_elev_traversability_rough*) ------------------------------------------------------
+constexpr uint32_t kElevRoughMaxRatio = 65535;
+
+struct ElevRoughParams {
+    uint32_t num, den;  // the limit: a mean squared residual of num / den slabs^2
+};
+// The slope's nine sums and a tenth, Szz = sum z^2 <= 289 * 63^2 = 1 147 041 over the same fit set.
+struct ElevRoughSums {
+    ElevSlopeSums fit;
+    int32_t szz;
+};
+// elev_slope_add's twin: the same ONE comparison decides, the same nine sums, and z^2
+KICP_HD void elev_rough_add(ElevRoughSums &s, uint32_t ground, uint8_t neighbour_ground, int32_t dx, int32_t dy, uint32_t gate) {
+    if (static_cast<uint32_t>(neighbour_ground) - ground + gate > 2u * gate) return;
+    const int32_t z = static_cast<int32_t>(neighbour_ground) - static_cast<int32_t>(ground);
+    ElevSlopeSums &f = s.fit;
+    f.n += 1, f.sx += dx, f.sy += dy, f.sxx += dx * dx, f.sxy += dx * dy, f.syy += dy * dy, f.sz += z, f.sxz += dx * z, f.syz += dy * z;
+    s.szz += z * z;
+}
+// Q = D Szz - Da Sxz - Db Syz - Dc Sz: D times the residual sum of squares of the fit set to its least-squares plane, Dc the intercept's
+// determinant (the third column of the normal equations replaced).  IN 64 BITS, by these bounds at L = 8, K = 63: |Sx|, |Sy| <= 17 * 36 =
+// 612 < 2^10, Sxx, Syy, |Sxy| < 2^13, |Sz| < 2^15, |Sxz|, |Syz| < 2^17, Szz < 2^21.  The three terms of Dc: |Sxx (Syy Sz - Sy Syz)| <
+// 2^13 (2^28 + 2^27) < 2^42, |Sxy (Sxy Sz - Sx Syz)| < 2^42 likewise, |Sxz (Sxy Sy - Syy Sx)| < 2^17 * 2^24 = 2^41: |Dc| < 2^44.  The four
+// products: D Szz < 2^34 * 2^21 = 2^55, |Da Sxz|, |Db Syz| < 2^41 * 2^17 = 2^58, |Dc Sz| < 2^44 * 2^15 = 2^59; their absolute values sum
+// to less than 2^61, so no partial sum leaves 63 bits.  In exact arithmetic 0 <= Q <= D Szz < 2^55.
+KICP_HD int64_t elev_rough_residual(const ElevRoughSums &s, int64_t d, int64_t da, int64_t db, int64_t &dc) {
+    const int64_t sx = s.fit.sx, sy = s.fit.sy, sxx = s.fit.sxx, sxy = s.fit.sxy, syy = s.fit.syy, sz = s.fit.sz, sxz = s.fit.sxz, syz = s.fit.syz;
+    dc = sxx * (syy * sz - sy * syz) - sxy * (sxy * sz - sx * syz) + sxz * (sxy * sy - syy * sx);
+    return d * static_cast<int64_t>(s.szz) - da * sxz - db * syz - dc * sz;
+}
+// ROUGH of a cell that has a fit: Q den > num n D, strictly, on exact integers: the left side reaches 2^71 - a 128-bit product -, the
+// right stays below 2^16 * 2^9 * 2^34 = 2^59.  No division, no floating point.
+KICP_HD bool elev_rough_exceeds(int64_t q, int64_t d, int32_t n, const ElevRoughParams &p) {
+    typedef unsigned __int128 u128;
+    return static_cast<u128>(static_cast<uint64_t>(q)) * p.den > static_cast<u128>(static_cast<uint64_t>(p.num) * static_cast<uint64_t>(n) * static_cast<uint64_t>(d));
+}
+// the value of a cell and the count it adds to: 0 unknown, 1 traversable, 2 BODY, 3 STEP only, 4 SLOPE only, 5 ROUGH only
+KICP_HD int8_t elev_rough_value(bool known, bool body, bool step, bool slope, bool rough, uint32_t &which) {
+    which = !known ? 0u : body ? 2u : step ? 3u : slope ? 4u : rough ? 5u : 1u;
+    return !known ? static_cast<int8_t>(-1) : static_cast<int8_t>((body || step || slope || rough) ? 100 : 0);
+}
+
 // ---- carving along the frame's rays (kicp_elev_update*) --------------------------------------------------------------------------
-constexpr uint32_t kElevMaxWiden = 64;                      // widen_slabs
+constexpr uint32_t kElevMaxWiden = 64;                     // widen_slabs
 constexpr double kElevSlabMin = -32768.0, kElevSlabMax = 32767.0;  // the slabs a ray may start or end in
 
 struct ElevCarveParams {
@@ -307,6 +349,50 @@ inline void classify_slope(const uint64_t *columns, uint32_t width, uint32_t hei
         }
     if (counts)
         for (int k = 0; k < 5; ++k) counts[k] = sums[k];
+}
+// The same with the class ROUGH, as k_elev_rough computes it: fit (nullable) takes D, Da, Db, Q, n per cell, zeros where the cell has no
+// fit; counts (nullable): unknown, traversable, BODY, STEP only, SLOPE only, ROUGH only.
+inline void classify_rough(const uint64_t *columns, uint32_t width, uint32_t height, const ElevParams &p, const ElevSlopeParams &sp, const ElevRoughParams &rp,
+                           const ElevRect &r, int8_t *out, uint8_t *ground, long long *fit, unsigned long long counts[6]) {
+    unsigned long long sums[6] = {0, 0, 0, 0, 0, 0};
+    const int32_t L = static_cast<int32_t>(sp.radius);
+    for (uint32_t ry = 0; ry < r.h; ++ry)
+        for (uint32_t rx = 0; rx < r.w; ++rx) {
+            const uint32_t x = r.x0 + rx, y = r.y0 + ry;
+            const uint64_t c = columns[static_cast<size_t>(y) * width + x];
+            const uint8_t gr = elev_ground(c);
+            bool body = false, step = false, slope = false, rough = false;
+            int64_t d = 0, da = 0, db = 0, q = 0, n = 0;
+            if (c) {
+                body = elev_body(c, gr, p);
+                ElevRoughSums s{};
+                for (int32_t dy = -L; dy <= L; ++dy)
+                    for (int32_t dx = -L; dx <= L; ++dx) {
+                        const int64_t nx = static_cast<int64_t>(x) + dx, ny = static_cast<int64_t>(y) + dy;
+                        if (nx < 0 || ny < 0 || nx >= static_cast<int64_t>(width) || ny >= static_cast<int64_t>(height)) continue;
+                        const uint8_t gn = elev_ground(columns[static_cast<size_t>(ny) * width + static_cast<size_t>(nx)]);
+                        elev_rough_add(s, gr, gn, dx, dy, sp.gate);
+                        if ((dx || dy) && dx >= -1 && dx <= 1 && dy >= -1 && dy <= 1) step = step || elev_step(gr, gn, p);
+                    }
+                elev_slope_determinants(s.fit, d, da, db);
+                if (elev_slope_has_fit(s.fit, d, sp)) {
+                    int64_t dc;
+                    slope = elev_slope_exceeds(d, da, db, sp);
+                    q = elev_rough_residual(s, d, da, db, dc), n = s.fit.n;
+                    rough = elev_rough_exceeds(q, d, s.fit.n, rp);
+                } else {
+                    d = da = db = 0;
+                }
+            }
+            uint32_t which;
+            const size_t o = static_cast<size_t>(ry) * r.w + rx;
+            out[o] = elev_rough_value(c != 0ull, body, step, slope, rough, which);
+            if (ground) ground[o] = gr;
+            if (fit) fit[5 * o] = d, fit[5 * o + 1] = da, fit[5 * o + 2] = db, fit[5 * o + 3] = q, fit[5 * o + 4] = n;
+            ++sums[which];
+        }
+    if (counts)
+        for (int k = 0; k < 6; ++k) counts[k] = sums[k];
 }
 }  // namespace elev_host
 

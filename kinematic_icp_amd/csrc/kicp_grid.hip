@@ -3,6 +3,7 @@
 // kicp_grid.hpp; the geometry they share with the host entries: kicp_grid_host.hpp.  The handle, and which file holds what a planner
 // reads off the counters: kicp_grid_internal.hpp.
 #include <cerrno>
+#include <cstring>
 #include <memory>
 
 #include "kicp_grid.hpp"
@@ -12,6 +13,14 @@ namespace {
 int check_thresholds(double occupied_thresh, double free_thresh) {
     if (!(0.0 <= free_thresh && free_thresh < occupied_thresh && occupied_thresh <= 1.0))
         return fail(KICP_ERR_ARG, "thresholds must satisfy 0 <= free_thresh < occupied_thresh <= 1");
+    return KICP_OK;
+}
+constexpr size_t kFillCountWords = static_cast<size_t>(kGridFillShards) * kGridFillStride;  // the fill's sharded counts (kicp_grid.hpp)
+int check_fill_config(const kicp_grid_fill_config *cfg, GridFillParams &p) {
+    p = GridFillParams{cfg->min_observations, cfg->free_max, cfg->occupied_min};
+    if (cfg->min_observations < 1u) return fail(KICP_ERR_ARG, "min_observations must be at least 1");
+    if (!(cfg->free_max <= 100u && cfg->free_max < cfg->occupied_min && cfg->occupied_min <= 101u))
+        return fail(KICP_ERR_ARG, "the fill needs free_max <= 100 and free_max < occupied_min <= 101");
     return KICP_OK;
 }
 // the frame at d_xyz (n points; arguments checked): three launches, the statistics back, the stream drained
@@ -160,6 +169,52 @@ int kicp_grid_occupancy_from_counts(const unsigned short *counts, size_t cells, 
     if ((!counts || !out) && cells) return fail(KICP_ERR_ARG, "null argument");
     if (min_observations < 1u) return fail(KICP_ERR_ARG, "min_observations must be at least 1");
     for (size_t i = 0; i < cells; ++i) out[i] = grid_readout(counts[2 * i], counts[2 * i + 1], min_observations);
+    return KICP_OK;
+}
+int kicp_grid_fill_unknown(kicp_grid *dst, const kicp_grid *src, const kicp_grid_fill_config *cfg, unsigned long long out_counts[7]) {
+    KICP_TRACE_CALL();
+    if (!dst || !src || !cfg) return fail(KICP_ERR_ARG, "null argument");
+    GridFillParams p;
+    if (int rc = check_fill_config(cfg, p)) return rc;
+    if (dst == src) return fail(KICP_ERR_ARG, "the destination and the source must be two grids");
+    const kicp_grid_config &a = dst->cfg, &b = src->cfg;
+    auto same_bits = [](double x, double y) { return std::memcmp(&x, &y, sizeof x) == 0; };
+    if (!(same_bits(a.cell, b.cell) && same_bits(a.origin_x, b.origin_x) && same_bits(a.origin_y, b.origin_y) && a.width == b.width && a.height == b.height))
+        return fail(KICP_ERR_ARG, "the two grids' cell, origin, width and height must be equal");
+    if (dst->device != src->device)
+        return fail(KICP_ERR_ARG, "the destination lives on device " + std::to_string(dst->device) + ", the source on device " + std::to_string(src->device));
+    if (int rc = set_device(dst->device)) return rc;
+    auto &fl = dst->fill;
+    if (out_counts) {
+        if (int rc = fl.d_counts.reserve(kFillCountWords)) return rc;
+        if (int rc = fl.h_counts.reserve(kFillCountWords, hipHostMallocDefault, false)) return rc;
+    }
+    // Both handles' streams are idle (the stream rule); the launch runs on the destination's and is waited for.
+    hipStream_t st = dst->stream;
+    if (out_counts) HIP_TRY(hipMemsetAsync(fl.d_counts.get(), 0, kFillCountWords * sizeof(unsigned int), st));
+    const uint32_t blocks = static_cast<uint32_t>(std::min<size_t>((dst->cells + kGridBlock - 1) / kGridBlock, kGridFillBlocks));
+    hipLaunchKernelGGL(k_grid_fill_unknown, dim3(blocks), dim3(kGridBlock), 0, st, reinterpret_cast<uint32_t *>(dst->d_counts.get()),
+                       reinterpret_cast<const uint32_t *>(src->d_counts.get()), static_cast<uint32_t>(dst->cells), p,
+                       out_counts ? fl.d_counts.get() : static_cast<unsigned int *>(nullptr));
+    HIP_TRY(hipGetLastError());
+    if (out_counts) HIP_TRY(hipMemcpyAsync(fl.h_counts.get(), fl.d_counts.get(), kFillCountWords * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    dst->plan.valid = false;  // the plan was made on other counters: the fill is part of the chain that ends in a new one
+    if (out_counts)
+        for (uint32_t k = 0; k < kGridFillCounts; ++k) {
+            out_counts[k] = 0;
+            for (uint32_t shard = 0; shard < kGridFillShards; ++shard) out_counts[k] += fl.h_counts.get()[shard * kGridFillStride + k];
+        }
+    return KICP_OK;
+}
+int kicp_grid_fill_unknown_counts(unsigned short *dst_counts, const unsigned short *src_counts, size_t cells, const kicp_grid_fill_config *cfg,
+                                  unsigned long long out_counts[7]) {
+    if (!cfg || ((!dst_counts || !src_counts) && cells)) return fail(KICP_ERR_ARG, "null argument");
+    GridFillParams p;
+    if (int rc = check_fill_config(cfg, p)) return rc;
+    if (dst_counts == src_counts && cells) return fail(KICP_ERR_ARG, "the destination and the source must be two grids");
+    static_assert(sizeof(unsigned short) == sizeof(uint16_t), "a counter is 16 bits");
+    grid_host::fill_unknown(dst_counts, src_counts, cells, p, out_counts);
     return KICP_OK;
 }
 int kicp_grid_last_window(const kicp_grid *grid, unsigned int *x0, unsigned int *y0, unsigned int *w, unsigned int *h) {

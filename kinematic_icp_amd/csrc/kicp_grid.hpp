@@ -14,6 +14,8 @@
 //                 planes are cleared for the next frame
 // The counters are touched by exactly one lane per cell, without atomics.  The other atomics are the frame statistics and the list's
 // length (one add per wave that has something to add).  No kernel uses LDS or scratch.
+// Beside the frame: k_grid_readout, the occupancy byte of every cell, and k_grid_fill_unknown, which fills one grid's unknown cells
+// from another grid's readout (kicp_grid_fill_unknown; described at the kernel).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -114,6 +116,33 @@ static __global__ __launch_bounds__(kGridBlock) void k_grid_readout(const uint16
     if (i >= cells) return;
     const uint32_t pair = reinterpret_cast<const uint32_t *>(counts)[i];
     out[i] = grid_readout(pair & 0xFFFFu, pair >> 16, min_observations);
+}
+
+// ---- kicp_grid_fill_unknown: the unknown cells of one grid from the readout of another ------------------------------------------------
+// A FIXED number of workgroups (at most kGridFillBlocks) stride over the cells: one 32-bit load per cell from each grid, a store only
+// where the destination's pair changes.  Every lane keeps the seven tallies in registers over all its cells; at its end a wave sums
+// each and its first lane adds what is not zero to the wave's shard of `counts` (nullable: kGridFillShards x kGridFillStride words, each
+// shard on a 128-byte line of its own, summed on the host) - seven adds per wave whatever the grid's size, where an add per wave and
+// 64 cells to one word queues for about 11 ns each.  cells <= 2^28 and the stride is 2^18, so i stays inside 32 bits.  No LDS, no scratch.
+constexpr uint32_t kGridFillBlocks = 1024, kGridFillShards = 64, kGridFillStride = 32;
+static __global__ __launch_bounds__(kGridBlock) void k_grid_fill_unknown(uint32_t *__restrict__ dst_pairs, const uint32_t *__restrict__ src_pairs, uint32_t cells,
+                                                                         GridFillParams p, unsigned int *__restrict__ counts) {
+    uint32_t tally[kGridFillCounts] = {0u, 0u, 0u, 0u, 0u, 0u, 0u};
+    for (uint32_t i = blockIdx.x * kGridBlock + threadIdx.x; i < cells; i += gridDim.x * kGridBlock) {  // (every access is behind i < cells)
+        const uint32_t d = dst_pairs[i];
+        uint32_t which, disagree;
+        const uint32_t after = grid_fill_pair(d, src_pairs[i], p, which, disagree);
+        if (after != d) dst_pairs[i] = after;
+#pragma unroll
+        for (uint32_t k = 0; k < kGridFillCounts; ++k) tally[k] += (which == k || (k >= 5u && disagree == k)) ? 1u : 0u;  // (constant indices: registers)
+    }
+    if (!counts) return;
+    unsigned int *shard = counts + ((blockIdx.x * (kGridBlock / 64u) + threadIdx.x / 64u) % kGridFillShards) * kGridFillStride;
+#pragma unroll
+    for (uint32_t k = 0; k < kGridFillCounts; ++k) {
+        const uint32_t sum = grid_wave_sum(tally[k]);
+        if ((threadIdx.x & 63u) == 0u && sum) atomicAdd(&shard[k], sum);
+    }
 }
 
 }  // namespace kicp

@@ -1,7 +1,9 @@
 // kicp_grid_host.hpp -- the geometry of the 2-D occupancy grid (kicp_grid_*, include/kicp.h): the cell of a coordinate, one step of
-// the ray walk, the readout of one cell and the pixel of one value.  ONE text for the kernels (kicp_grid.hpp), for the two pure-host
-// entries (kicp_grid_occupancy_from_counts, kicp_grid_write_map) and for grid_host::integrate, the host restatement of a whole frame
-// that a stand-alone program runs under sanitizers (tests/cpp/grid_host_test.cpp).  Everything is exact and integer from the floor on.
+// the ray walk, the readout of one cell, the pixel of one value and the fill of one unknown cell from another grid.  ONE text for the
+// kernels (kicp_grid.hpp), for the pure-host entries (kicp_grid_occupancy_from_counts, kicp_grid_write_map,
+// kicp_grid_fill_unknown_counts) and for grid_host::integrate and grid_host::fill_unknown, the host restatements that stand-alone
+// programs run under sanitizers (tests/cpp/grid_host_test.cpp, tests/cpp/elev_rough_host_test.cpp).  Everything is exact and integer
+// from the floor on.
 #pragma once
 #include <cmath>
 #include <cstddef>
@@ -74,6 +76,31 @@ KICP_HD uint8_t grid_pixel(int8_t value, double occupied_thresh, double free_thr
     return 205u;
 }
 
+// ---- the fill of one grid's unknown cells from another (kicp_grid_fill_unknown*) ---------------------------------------------------
+constexpr uint32_t kGridFillCounts = 7;
+struct GridFillParams {
+    uint32_t min_observations, free_max, occupied_min;  // >= 1; free_max <= 100; free_max < occupied_min <= 101
+};
+// One cell: the pairs (hits | misses << 16) of the destination and the source -> the destination's pair afterwards.  `which` is the
+// tally the cell adds to - 0 kept obstacle, 1 kept traversable, 2 filled free, 3 filled occupied, 4 left unknown - and `disagree` 0, or
+// 5: traversable over a source OCCUPIED, or 6: obstacle over a source FREE.  Only an unknown destination (0, 0) changes: to (0, 1) where
+// the source is FREE, to (1, 0) where it is OCCUPIED.
+KICP_HD uint32_t grid_fill_pair(uint32_t dst, uint32_t src, const GridFillParams &p, uint32_t &which, uint32_t &disagree) {
+    const int32_t v = grid_readout(src & 0xFFFFu, src >> 16, p.min_observations);
+    const bool is_free = v >= 0 && v <= static_cast<int32_t>(p.free_max), is_occupied = v >= static_cast<int32_t>(p.occupied_min);
+    disagree = 0u;
+    if (dst & 0xFFFFu) {  // an obstacle
+        which = 0u, disagree = is_free ? 6u : 0u;
+        return dst;
+    }
+    if (dst) {  // traversable
+        which = 1u, disagree = is_occupied ? 5u : 0u;
+        return dst;
+    }
+    which = is_free ? 2u : is_occupied ? 3u : 4u;
+    return is_free ? 0x10000u : is_occupied ? 1u : 0u;
+}
+
 // the frame constants of a pose and a sensor origin (host: pose_to_rt is evaluated here, once per frame)
 inline GridFrame grid_frame(const GridGeom &g, const double pose_qt[7], const double sensor_xyz[3]) {
     const Rt m = pose_to_rt(Pose{pose_qt[0], pose_qt[1], pose_qt[2], pose_qt[3], pose_qt[4], pose_qt[5], pose_qt[6]});
@@ -136,6 +163,22 @@ inline void integrate(const GridGeom &g, uint16_t *counts, const double *xyz, si
             else
                 counts[2 * c + 1] = grid_bump(counts[2 * c + 1]), ++stats[3];
         }
+}
+// The fill on the host, as k_grid_fill_unknown does it: dst and src are cells x 2 counters (hits, misses); a counter is written only
+// where its cell changes.  counts (nullable): the seven words.
+inline void fill_unknown(uint16_t *dst, const uint16_t *src, size_t cells, const GridFillParams &p, unsigned long long counts[7]) {
+    unsigned long long sums[kGridFillCounts] = {0, 0, 0, 0, 0, 0, 0};
+    for (size_t i = 0; i < cells; ++i) {
+        const uint32_t d = static_cast<uint32_t>(dst[2 * i]) | static_cast<uint32_t>(dst[2 * i + 1]) << 16;
+        const uint32_t s = static_cast<uint32_t>(src[2 * i]) | static_cast<uint32_t>(src[2 * i + 1]) << 16;
+        uint32_t which, disagree;
+        const uint32_t after = grid_fill_pair(d, s, p, which, disagree);
+        if (after != d) dst[2 * i] = static_cast<uint16_t>(after & 0xFFFFu), dst[2 * i + 1] = static_cast<uint16_t>(after >> 16);
+        ++sums[which];
+        if (disagree) ++sums[disagree];
+    }
+    if (counts)
+        for (uint32_t k = 0; k < kGridFillCounts; ++k) counts[k] = sums[k];
 }
 }  // namespace grid_host
 

@@ -2,7 +2,7 @@
 // the rules its entries keep, and the argument checks that more than one of them makes.  include/kicp.h states the semantics.  The
 // pieces, each the only translation unit that includes its kernel headers (the arithmetic they share with the host: *_host.hpp):
 //   kicp_grid.hip          the grid itself (kicp_grid.hpp): create / destroy / info / clear, integrate, counts / set_counts, the
-//                          occupancy readout, last_window, write_map / save_map
+//                          occupancy readout, last_window, write_map / save_map, fill_unknown and its host twin
 //   kicp_grid_plan.hip     what a planner plans on (kicp_clear.hpp, kicp_nav.hpp): clearance and costmap with their host twins,
 //                          kicp_grid_cost_table_nav2, kicp_plan_weights, the three potential entries, kicp_potential_path, kicp_plan_q,
 //                          kicp_grid_has_plan - one file because kicp_grid_potential queues the costmap's launches in front of the field's
@@ -47,6 +47,11 @@ struct kicp_grid {
         FrameUpload upload;             // kicp_grid_integrate's points
     } frame;
     mutable struct { DevBuf<int8_t> d_occupancy; } readout;  // kicp_grid_occupancy
+    // kicp_grid_fill_unknown (this handle the destination): the seven counts in their shards
+    struct {
+        DevBuf<unsigned int> d_counts;
+        PinnedBuf<unsigned int> h_counts;
+    } fill;
     // kicp_grid_clearance / kicp_grid_costmap: the column distances, the caller's table and the two results
     mutable struct {
         DevBuf<uint8_t> d_coldist, d_cost_table, d_cost;

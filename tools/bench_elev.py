@@ -26,9 +26,14 @@ have completed.  Warm; everything that is compared alternates in the same proces
     case's 1 600 x 1 600 layer at L = 2, 4 and 8 - the full layer, the last window grown by L, the full layer with every optional
     output, and into a grid - beside kicp_elev_traversability and kicp_elev_to_grid of this build and, with --ab parent=LIBRARY, of
     the parent commit's library on the same columns, alternating (raw output kept as profiles/elev_slope_bench.json).
+  - with --rough INSTEAD of the above: the class ROUGH (kicp_elev_traversability_rough, kicp_elev_to_grid_rough) at L = 2, 4 and 8 on that
+    sparse layer and on a fully known one of the same size, beside the slope limit's and the plain calls of this build and, with
+    --ab parent=LIBRARY (twice, two builds of the parent commit: the spread between them is the yardstick), of the parent's, on the
+    same columns, alternating; with --fill also kicp_grid_fill_unknown of the grid kicp_elev_to_grid wrote from the mapping grid of
+    the same frame, beside kicp_elev_to_grid (raw output kept as profiles/elev_rough_bench.json).
 Prints one JSON line.
 
-    python tools/bench_elev.py [--rounds 30] [--carve | --slope] [--ab NAME=LIB] [--pipeline] [--pipeline-rounds 3] [--pipeline-frames 16] [--contender NAME=EXE:LIBDIR]
+    python tools/bench_elev.py [--rounds 30] [--carve | --slope | --rough [--fill]] [--ab NAME=LIB] [--pipeline] [--pipeline-rounds 3] [--pipeline-frames 16] [--contender NAME=EXE:LIBDIR]
 """
 import argparse
 import ctypes as C
@@ -112,6 +117,28 @@ class RawClasses:
 
     def to_grid(self):
         assert self.lib.kicp_elev_to_grid(self._h, C.byref(self.cfg), self._g) == 0
+
+    def traversability_slope(self, slope):
+        h, w = self.out.shape
+        scfg = K.ElevationSlopeConfig(*slope)
+        assert self.lib.kicp_elev_traversability_slope(self._h, C.byref(self.cfg), C.byref(scfg), 0, 0, w, h, self.out.ctypes.data_as(C.POINTER(C.c_byte)), None, None, None,
+                                                       self.out.size) == 0
+        return self.out
+
+    def to_grid_slope(self, slope):
+        scfg = K.ElevationSlopeConfig(*slope)
+        assert self.lib.kicp_elev_to_grid_slope(self._h, C.byref(self.cfg), C.byref(scfg), self._g) == 0
+
+    def traversability_rough(self, slope, rough):
+        h, w = self.out.shape
+        scfg, rcfg = K.ElevationSlopeConfig(*slope), K.ElevationRoughConfig(*rough)
+        assert self.lib.kicp_elev_traversability_rough(self._h, C.byref(self.cfg), C.byref(scfg), C.byref(rcfg), 0, 0, w, h, self.out.ctypes.data_as(C.POINTER(C.c_byte)), None,
+                                                       None, None, self.out.size) == 0
+        return self.out
+
+    def to_grid_rough(self, slope, rough):
+        scfg, rcfg = K.ElevationSlopeConfig(*slope), K.ElevationRoughConfig(*rough)
+        assert self.lib.kicp_elev_to_grid_rough(self._h, C.byref(self.cfg), C.byref(scfg), C.byref(rcfg), self._g) == 0
 
     def __del__(self):
         lib = getattr(self, "lib", None)
@@ -300,6 +327,88 @@ def slope_rows(rounds, contenders):
     return [row]
 
 
+ROUGH_LIMIT = (512, 1024)  # half a slab^2
+
+
+def known_columns(width, height):
+    """a fully known layer: one bit per column, the ground rising by a slab every 64 cells in x under two slabs of noise"""
+    rng = np.random.default_rng(5)
+    ground = 4 + np.arange(width)[None, :] // 64 + rng.integers(0, 3, (height, width))
+    return (np.uint64(1) << ground.astype(np.uint64)).astype(np.uint64)
+
+
+def rough_rows(rounds, contenders, fill):
+    """ROUGH (kicp_elev_traversability_rough, kicp_elev_to_grid_rough) at L = 2, 4 and 8 on slope_rows' sparse 1 600 x 1 600 layer and on
+    a fully known one of that size, beside kicp_elev_traversability_slope / kicp_elev_to_grid_slope and the plain calls of this build
+    and of every --ab contender (the parent commit's library, built twice: the spread between the two is the yardstick for this
+    build's existing calls), on the same columns, alternating.  With --fill also kicp_grid_fill_unknown of the grid kicp_elev_to_grid
+    wrote, from the mapping grid of the same frame, without and with the seven counts, beside kicp_elev_to_grid as its yardstick."""
+    name = "cfg1"
+    cfg, scene, dirs, rng = scene_and_beams(name)
+    pose = syn.planar_pose(1.2, -0.7, 0.9)
+    frame = np.ascontiguousarray(syn.make_scan(scene, pose, dirs, cfg.sensor_height, rng))
+    sensor = np.array([0.0, 0.0, cfg.sensor_height])
+    gcfg = dict(grid_config(name, 0.05), max_ray=12.0, reach=240)
+    mapping = make_grid(gcfg)
+    mapping.integrate(frame, pose, sensor)
+    rows = []
+    for kind in ("sparse", "known"):
+        layer, other = make_layer(gcfg), make_grid(gcfg)
+        if kind == "sparse":
+            layer.integrate(frame, pose, sensor)
+        else:
+            layer.set_columns(known_columns(gcfg["width"], gcfg["height"]))
+        columns = layer.columns()
+        # EVERY build through the same caller, this one too: RawClasses on a preallocated output (K.ElevationLayer's methods allocate
+        # theirs per call, which costs about a tenth of a plain call at this size)
+        raws = {"this": RawClasses(K.lib(), gcfg, columns)}
+        raws.update({who: RawClasses(lib, gcfg, columns) for who, lib in contenders.items()})
+        mine = raws["this"]
+        rise, run = layer.slope_limit(np.tan(np.deg2rad(20.0)))
+        slopes = {L: (L, (STEP_SLABS + 1) * L, 12, rise, run) for L in SLOPE_RADII}
+        t, results, fills = {}, {}, None
+        for r in range(rounds + 3):  # (the first three rounds warm)
+            now, plain = {}, None
+            turn = list(raws.items())[r % len(raws):] + list(raws.items())[:r % len(raws)]  # the builds take turns at going first
+            for who, raw in turn:
+                now["traversability_full_ms_" + who], theirs = timed(raw.traversability)
+                now["to_grid_ms_" + who], _ = timed(raw.to_grid)
+                plain = theirs.copy() if plain is None else plain
+                assert np.array_equal(theirs, plain)  # every build computes the same
+            if fill:
+                layer.to_grid(other, STEP_SLABS, ROBOT_SLABS)
+                now["fill_unknown_ms"], _ = timed(lambda: other.fill_unknown(mapping))
+                layer.to_grid(other, STEP_SLABS, ROBOT_SLABS)
+                now["fill_unknown_with_counts_ms"], fills = timed(lambda: other.fill_unknown(mapping, return_counts=True))
+            for L in SLOPE_RADII:
+                steep = None
+                for who, raw in turn:
+                    now["slope_full_ms_L%d_%s" % (L, who)], theirs = timed(lambda: raw.traversability_slope(slopes[L]))
+                    now["to_grid_slope_ms_L%d_%s" % (L, who)], _ = timed(lambda: raw.to_grid_slope(slopes[L]))
+                    steep = theirs.copy() if steep is None else steep
+                    assert np.array_equal(theirs, steep)
+                now["rough_full_ms_L%d" % L], full = timed(lambda: mine.traversability_rough(slopes[L], ROUGH_LIMIT))
+                full = full.copy()
+                now["to_grid_rough_ms_L%d" % L], _ = timed(lambda: mine.to_grid_rough(slopes[L], ROUGH_LIMIT))
+                layer.to_grid_rough(other, STEP_SLABS, ROBOT_SLABS, slopes[L], ROUGH_LIMIT)
+                now["rough_full_with_ground_fit_and_counts_ms_L%d" % L], counted = timed(
+                    lambda: layer.traversability_rough(STEP_SLABS, ROBOT_SLABS, slopes[L], ROUGH_LIMIT, return_ground=True, return_fit=True, return_counts=True))
+                assert np.array_equal(counted[0], full) and np.array_equal(other.occupancy(1), full)
+                assert np.array_equal(full[full != steep], np.full(int((full != steep).sum()), 100, dtype=np.int8)) and counted[3][5] == int((full != steep).sum())
+                results[L] = counted[3]
+            if r >= 3:
+                for key, ms in now.items():
+                    t.setdefault(key, []).append(ms)
+        row = {"scene": name, "layer": kind, "known_cells": int(np.count_nonzero(columns)), "cell_m": 0.05, "slab_m": SLAB, "layer_cells": [gcfg["width"], gcfg["height"]],
+               "step_slabs": STEP_SLABS, "robot_slabs": ROBOT_SLABS, "slope_configs_L_K_min_rise_run": [list(slopes[L]) for L in SLOPE_RADII], "rough_num_den": list(ROUGH_LIMIT),
+               "unknown_traversable_body_step_slope_rough": {"L%d" % L: list(results[L]) for L in SLOPE_RADII}}
+        if fill:
+            row["fill_kept_obstacle_kept_traversable_filled_free_filled_occupied_left_unknown_over_occupied_over_free"] = list(fills)
+        row.update({key: spread(v) for key, v in t.items()})
+        rows.append(row)
+    return rows
+
+
 def pipeline_rows(rounds, n_frames, contenders, carve=False):
     import test_elev_facade
     import test_elev_carve_facade
@@ -357,6 +466,8 @@ def main():
     ap.add_argument("--rounds", type=int, default=30)
     ap.add_argument("--carve", action="store_true")
     ap.add_argument("--slope", action="store_true")
+    ap.add_argument("--rough", action="store_true")
+    ap.add_argument("--fill", action="store_true")
     ap.add_argument("--ab", action="append", default=[], metavar="NAME=LIB")
     ap.add_argument("--pipeline", action="store_true")
     ap.add_argument("--pipeline-rounds", type=int, default=3)
@@ -367,7 +478,9 @@ def main():
     if bind:
         bind()
     libs = {spec.split("=", 1)[0]: load_contender(spec.split("=", 1)[1]) for spec in a.ab}
-    if a.slope:
+    if a.rough or a.fill:
+        res = {"caller_process": where, "rounds": a.rounds, "rough": rough_rows(a.rounds, libs, a.fill)}
+    elif a.slope:
         res = {"caller_process": where, "rounds": a.rounds, "slope": slope_rows(a.rounds, libs)}
     elif a.carve:
         res = {"caller_process": where, "rounds": a.rounds, "carve": carve_rows(a.rounds, libs)}
