@@ -873,17 +873,48 @@ def gain_from_occupancy(occupancy, views, range_cells, min_observations=1, occup
     return out
 
 
-def _traversability_call(call, w, h, return_ground, return_counts):
-    """what the two traversability entries share: the outputs, the call, and what is returned - the classes alone, or a tuple with the
-    ground bytes and / or the four counts behind them"""
+def _struct(cls, value):
+    """a ctypes struct of integers: an instance of cls, or its fields as a tuple or a dict"""
+    if isinstance(value, cls):
+        return value
+    if isinstance(value, dict):
+        value = [value[name] for name, _ in cls._fields_]
+    return cls(*[int(v) for v in value])
+
+
+def _traversability_call(call, w, h, return_ground, return_fit, return_counts, fit_values, count_words):
+    """what the traversability entries share: the outputs, the call, and what is returned - the classes alone, or a tuple with the
+    ground bytes, the fit and / or the counts behind them.  fit_values = 0: the entry has no fit argument; 3: the fit is int64 (h, w, 3)
+    - D, Da, Db - and the counts are five; 5: with ROUGH (h, w, 5) - D, Da, Db, Q, n - and six"""
     out = np.empty((h, w), dtype=np.int8)
     ground = np.empty((h, w), dtype=np.uint8) if return_ground else None
-    counts = np.zeros(4, dtype=np.uint64)
-    _check(call(out.ctypes.data_as(C.POINTER(C.c_byte)), ground.ctypes.data_as(C.POINTER(C.c_ubyte)) if return_ground else None,
+    fit = np.empty((h, w, fit_values), dtype=np.int64) if return_fit else None
+    counts = np.zeros(count_words, dtype=np.uint64)
+    fit_arg = [fit.ctypes.data_as(C.POINTER(C.c_longlong)) if return_fit else None] if fit_values else []
+    _check(call(out.ctypes.data_as(C.POINTER(C.c_byte)), ground.ctypes.data_as(C.POINTER(C.c_ubyte)) if return_ground else None, *fit_arg,
                 counts.ctypes.data_as(C.POINTER(C.c_ulonglong)) if return_counts else None, out.size))
-    if not (return_ground or return_counts):
+    if not (return_ground or return_fit or return_counts):
         return out
-    return (out,) + ((ground,) if return_ground else ()) + ((tuple(int(v) for v in counts),) if return_counts else ())
+    return (out,) + ((ground,) if return_ground else ()) + ((fit,) if return_fit else ()) + ((tuple(int(v) for v in counts),) if return_counts else ())
+
+
+def _elev_classes(step_slabs, robot_slabs, *fit):
+    """a classification - plain, with a slope config, or with a slope and a rough config (each a struct, a tuple or a dict) -> the suffix
+    of its entries' names, its configs by reference, fit_values and count_words (_traversability_call)"""
+    cfgs = [ElevationTraversabilityConfig(int(step_slabs), int(robot_slabs))] + [_struct(cls, v) for cls, v in zip((ElevationSlopeConfig, ElevationRoughConfig), fit)]
+    return ("", "_slope", "_rough")[len(fit)], [C.byref(v) for v in cfgs], (0, 3, 5)[len(fit)], 4 + len(fit)
+
+
+def _traversability_from_columns(columns, rect, return_ground, return_fit, return_counts, step_slabs, robot_slabs, *fit):
+    """what the three *_from_columns functions share"""
+    c = np.ascontiguousarray(columns, dtype=np.uint64)
+    if c.ndim != 2 or c.size == 0:
+        raise KicpError(KICP_ERR_ARG, "columns must be shaped (height, width), both at least 1")
+    x0, y0, w, h = _rect(rect, c.shape[1], c.shape[0])
+    suffix, cfgs, fit_values, count_words = _elev_classes(step_slabs, robot_slabs, *fit)
+    entry = getattr(lib(), "kicp_elev_traversability" + suffix + "_from_columns")
+    return _traversability_call(lambda *outs: entry(c.ctypes.data_as(C.POINTER(C.c_ulonglong)), c.shape[1], c.shape[0], *cfgs, x0, y0, w, h, *outs), w, h, return_ground,
+                                return_fit, return_counts, fit_values, count_words)
 
 
 def traversability_from_columns(columns, step_slabs, robot_slabs, rect=None, return_ground=False, return_counts=False):
@@ -891,36 +922,7 @@ def traversability_from_columns(columns, step_slabs, robot_slabs, rect=None, ret
     shaped (height, width), uint64 -> int8 (h, w): -1 unknown, 0 traversable, 100 obstacle (BODY: something between step_slabs and
     robot_slabs over the cell's ground; STEP: an 8-neighbour's ground more than step_slabs below).  return_ground adds uint8 (h, w), the
     ground's slab, 255 unknown; return_counts adds (unknown, traversable, BODY, STEP only).  Pure host code: needs no GPU."""
-    c = np.ascontiguousarray(columns, dtype=np.uint64)
-    if c.ndim != 2 or c.size == 0:
-        raise KicpError(KICP_ERR_ARG, "columns must be shaped (height, width), both at least 1")
-    x0, y0, w, h = _rect(rect, c.shape[1], c.shape[0])
-    cfg = ElevationTraversabilityConfig(int(step_slabs), int(robot_slabs))
-    return _traversability_call(lambda o, g, n, cap: lib().kicp_elev_traversability_from_columns(c.ctypes.data_as(C.POINTER(C.c_ulonglong)), c.shape[1], c.shape[0],
-                                                                                                  C.byref(cfg), x0, y0, w, h, o, g, n, cap), w, h, return_ground, return_counts)
-
-
-def _slope_config(slope):
-    """an ElevationSlopeConfig, or (radius_cells, gate_slabs, min_cells, rise_slabs, run_cells), or a dict with those fields"""
-    if isinstance(slope, ElevationSlopeConfig):
-        return slope
-    if isinstance(slope, dict):
-        slope = [slope[name] for name, _ in ElevationSlopeConfig._fields_]
-    return ElevationSlopeConfig(*[int(v) for v in slope])
-
-
-def _traversability_slope_call(call, w, h, return_ground, return_fit, return_counts, fit_values=3, count_words=5):
-    """_traversability_call for the entries with a plane fit: the fit is int64 (h, w, 3) - D, Da, Db - and the counts are five; with
-    ROUGH (h, w, 5) - D, Da, Db, Q, n - and six"""
-    out = np.empty((h, w), dtype=np.int8)
-    ground = np.empty((h, w), dtype=np.uint8) if return_ground else None
-    fit = np.empty((h, w, fit_values), dtype=np.int64) if return_fit else None
-    counts = np.zeros(count_words, dtype=np.uint64)
-    _check(call(out.ctypes.data_as(C.POINTER(C.c_byte)), ground.ctypes.data_as(C.POINTER(C.c_ubyte)) if return_ground else None,
-                fit.ctypes.data_as(C.POINTER(C.c_longlong)) if return_fit else None, counts.ctypes.data_as(C.POINTER(C.c_ulonglong)) if return_counts else None, out.size))
-    if not (return_ground or return_fit or return_counts):
-        return out
-    return (out,) + ((ground,) if return_ground else ()) + ((fit,) if return_fit else ()) + ((tuple(int(v) for v in counts),) if return_counts else ())
+    return _traversability_from_columns(columns, rect, return_ground, False, return_counts, step_slabs, robot_slabs)
 
 
 def traversability_slope_from_columns(columns, step_slabs, robot_slabs, slope, rect=None, return_ground=False, return_fit=False, return_counts=False):
@@ -929,31 +931,7 @@ def traversability_slope_from_columns(columns, step_slabs, robot_slabs, slope, r
     per slope.run_cells cells.  slope: an ElevationSlopeConfig, or its five fields as a tuple or a dict.  return_fit adds int64
     (h, w, 3): the determinants D, Da, Db of the fit - the gradient is (Da / D, Db / D) slabs per cell -, zeros where a cell has no fit;
     return_counts adds (unknown, traversable, BODY, STEP only, SLOPE only).  Pure host code: needs no GPU."""
-    c = np.ascontiguousarray(columns, dtype=np.uint64)
-    if c.ndim != 2 or c.size == 0:
-        raise KicpError(KICP_ERR_ARG, "columns must be shaped (height, width), both at least 1")
-    x0, y0, w, h = _rect(rect, c.shape[1], c.shape[0])
-    cfg, scfg = ElevationTraversabilityConfig(int(step_slabs), int(robot_slabs)), _slope_config(slope)
-    return _traversability_slope_call(lambda o, g, f, n, cap: lib().kicp_elev_traversability_slope_from_columns(
-        c.ctypes.data_as(C.POINTER(C.c_ulonglong)), c.shape[1], c.shape[0], C.byref(cfg), C.byref(scfg), x0, y0, w, h, o, g, f, n, cap), w, h, return_ground, return_fit,
-        return_counts)
-
-
-def elev_slope_limit(cell, slab, max_tangent):
-    """kicp_elev_slope_limit: -> (rise_slabs, run_cells) of the slope limit whose tangent is max_tangent on cells of side `cell` and
-    slabs of `slab` metres: run_cells = 1024, rise_slabs = floor(max_tangent * cell / slab * 1024)"""
-    cfg, rise, run = ElevationConfig(float(cell), 0.0, 0.0, 0, 0, 0.0, float(slab), 0.0), C.c_uint(), C.c_uint()
-    _check(lib().kicp_elev_slope_limit(C.byref(cfg), float(max_tangent), C.byref(rise), C.byref(run)))
-    return rise.value, run.value
-
-
-def _rough_config(rough):
-    """an ElevationRoughConfig, or (num, den), or a dict with those fields"""
-    if isinstance(rough, ElevationRoughConfig):
-        return rough
-    if isinstance(rough, dict):
-        rough = [rough[name] for name, _ in ElevationRoughConfig._fields_]
-    return ElevationRoughConfig(*[int(v) for v in rough])
+    return _traversability_from_columns(columns, rect, return_ground, return_fit, return_counts, step_slabs, robot_slabs, slope)
 
 
 def traversability_rough_from_columns(columns, step_slabs, robot_slabs, slope, rough, rect=None, return_ground=False, return_fit=False, return_counts=False):
@@ -962,14 +940,15 @@ def traversability_rough_from_columns(columns, step_slabs, robot_slabs, slope, r
     states Q).  rough: an ElevationRoughConfig, or (num, den), or a dict.  return_fit adds int64 (h, w, 5): D, Da, Db, Q, n - the mean
     squared residual is Q / (n D) -, zeros where a cell has no fit; return_counts adds (unknown, traversable, BODY, STEP only, SLOPE
     only, ROUGH only).  Pure host code: needs no GPU."""
-    c = np.ascontiguousarray(columns, dtype=np.uint64)
-    if c.ndim != 2 or c.size == 0:
-        raise KicpError(KICP_ERR_ARG, "columns must be shaped (height, width), both at least 1")
-    x0, y0, w, h = _rect(rect, c.shape[1], c.shape[0])
-    cfg, scfg, rcfg = ElevationTraversabilityConfig(int(step_slabs), int(robot_slabs)), _slope_config(slope), _rough_config(rough)
-    return _traversability_slope_call(lambda o, g, f, n, cap: lib().kicp_elev_traversability_rough_from_columns(
-        c.ctypes.data_as(C.POINTER(C.c_ulonglong)), c.shape[1], c.shape[0], C.byref(cfg), C.byref(scfg), C.byref(rcfg), x0, y0, w, h, o, g, f, n, cap), w, h, return_ground,
-        return_fit, return_counts, 5, 6)
+    return _traversability_from_columns(columns, rect, return_ground, return_fit, return_counts, step_slabs, robot_slabs, slope, rough)
+
+
+def elev_slope_limit(cell, slab, max_tangent):
+    """kicp_elev_slope_limit: -> (rise_slabs, run_cells) of the slope limit whose tangent is max_tangent on cells of side `cell` and
+    slabs of `slab` metres: run_cells = 1024, rise_slabs = floor(max_tangent * cell / slab * 1024)"""
+    cfg, rise, run = ElevationConfig(float(cell), 0.0, 0.0, 0, 0, 0.0, float(slab), 0.0), C.c_uint(), C.c_uint()
+    _check(lib().kicp_elev_slope_limit(C.byref(cfg), float(max_tangent), C.byref(rise), C.byref(run)))
+    return rise.value, run.value
 
 
 def elev_rough_limit(slab, rms_metres):
@@ -1270,45 +1249,45 @@ class ElevationLayer:
         _check(lib().kicp_elev_last_window(self._h, *[C.byref(x) for x in v]))
         return tuple(x.value for x in v)
 
+    def _traversability(self, rect, return_ground, return_fit, return_counts, step_slabs, robot_slabs, *fit):
+        """what the three traversability* methods share"""
+        x0, y0, w, h = _rect(rect, self.width, self.height)
+        suffix, cfgs, fit_values, count_words = _elev_classes(step_slabs, robot_slabs, *fit)
+        entry = getattr(lib(), "kicp_elev_traversability" + suffix)
+        return _traversability_call(lambda *outs: entry(self._h, *cfgs, x0, y0, w, h, *outs), w, h, return_ground, return_fit, return_counts, fit_values, count_words)
+
+    def _to_grid(self, grid, step_slabs, robot_slabs, *fit):
+        """what the three to_grid* methods share"""
+        suffix, cfgs, _, _ = _elev_classes(step_slabs, robot_slabs, *fit)
+        _check(getattr(lib(), "kicp_elev_to_grid" + suffix)(self._h, *cfgs, grid._h))
+
     def traversability(self, step_slabs, robot_slabs, rect=None, return_ground=False, return_counts=False):
         """kicp_elev_traversability: on the GPU, traversability_from_columns' result on the columns where they are"""
-        x0, y0, w, h = _rect(rect, self.width, self.height)
-        cfg = ElevationTraversabilityConfig(int(step_slabs), int(robot_slabs))
-        return _traversability_call(lambda o, g, n, cap: lib().kicp_elev_traversability(self._h, C.byref(cfg), x0, y0, w, h, o, g, n, cap), w, h, return_ground,
-                                    return_counts)
+        return self._traversability(rect, return_ground, False, return_counts, step_slabs, robot_slabs)
 
     def to_grid(self, grid, step_slabs, robot_slabs):
         """kicp_elev_to_grid: on the GPU, the classes of every cell into the counters of `grid`, an OccupancyGrid of equal cell, origin,
         width and height on the same device that the caller dedicates to it: obstacle (1, 0), traversable (0, 1), unknown (0, 0).  At
         min_observations = 1 grid.costmap, .potential, .score_arcs, .frontiers and .gain then run on traversability."""
-        cfg = ElevationTraversabilityConfig(int(step_slabs), int(robot_slabs))
-        _check(lib().kicp_elev_to_grid(self._h, C.byref(cfg), grid._h))
+        self._to_grid(grid, step_slabs, robot_slabs)
 
     def traversability_slope(self, step_slabs, robot_slabs, slope, rect=None, return_ground=False, return_fit=False, return_counts=False):
         """kicp_elev_traversability_slope: on the GPU, traversability_slope_from_columns' result on the columns where they are; a frame
         changes it only inside last_window() grown by max(1, slope.radius_cells) cells"""
-        x0, y0, w, h = _rect(rect, self.width, self.height)
-        cfg, scfg = ElevationTraversabilityConfig(int(step_slabs), int(robot_slabs)), _slope_config(slope)
-        return _traversability_slope_call(lambda o, g, f, n, cap: lib().kicp_elev_traversability_slope(self._h, C.byref(cfg), C.byref(scfg), x0, y0, w, h, o, g, f, n, cap),
-                                          w, h, return_ground, return_fit, return_counts)
+        return self._traversability(rect, return_ground, return_fit, return_counts, step_slabs, robot_slabs, slope)
 
     def to_grid_slope(self, grid, step_slabs, robot_slabs, slope):
         """kicp_elev_to_grid_slope: to_grid with the slope limit - a SLOPE cell is an obstacle (1, 0) like a BODY or STEP one"""
-        cfg, scfg = ElevationTraversabilityConfig(int(step_slabs), int(robot_slabs)), _slope_config(slope)
-        _check(lib().kicp_elev_to_grid_slope(self._h, C.byref(cfg), C.byref(scfg), grid._h))
+        self._to_grid(grid, step_slabs, robot_slabs, slope)
 
     def traversability_rough(self, step_slabs, robot_slabs, slope, rough, rect=None, return_ground=False, return_fit=False, return_counts=False):
         """kicp_elev_traversability_rough: on the GPU, traversability_rough_from_columns' result on the columns where they are; a frame
         changes it only inside last_window() grown by max(1, slope.radius_cells) cells"""
-        x0, y0, w, h = _rect(rect, self.width, self.height)
-        cfg, scfg, rcfg = ElevationTraversabilityConfig(int(step_slabs), int(robot_slabs)), _slope_config(slope), _rough_config(rough)
-        return _traversability_slope_call(lambda o, g, f, n, cap: lib().kicp_elev_traversability_rough(self._h, C.byref(cfg), C.byref(scfg), C.byref(rcfg), x0, y0, w, h, o, g,
-                                                                                                       f, n, cap), w, h, return_ground, return_fit, return_counts, 5, 6)
+        return self._traversability(rect, return_ground, return_fit, return_counts, step_slabs, robot_slabs, slope, rough)
 
     def to_grid_rough(self, grid, step_slabs, robot_slabs, slope, rough):
         """kicp_elev_to_grid_rough: to_grid_slope with the class ROUGH - a ROUGH cell is an obstacle (1, 0) too"""
-        cfg, scfg, rcfg = ElevationTraversabilityConfig(int(step_slabs), int(robot_slabs)), _slope_config(slope), _rough_config(rough)
-        _check(lib().kicp_elev_to_grid_rough(self._h, C.byref(cfg), C.byref(scfg), C.byref(rcfg), grid._h))
+        self._to_grid(grid, step_slabs, robot_slabs, slope, rough)
 
     def rough_limit(self, rms_metres):
         """elev_rough_limit for this layer's slab -> (num, den)"""

@@ -4,6 +4,7 @@
 // kicp_elev_host.hpp.  kicp_elev_to_grid writes the classes into a kicp_grid's counters, so this file sees that handle too.
 #include <cstring>
 #include <memory>
+#include <utility>
 
 #include "kicp_elev.hpp"
 #include "kicp_grid_internal.hpp"
@@ -139,36 +140,44 @@ int check_frame_args(const kicp_elev *elev, const double *xyz, size_t n, const d
     return FrameUpload::check(elev && pose_qt && sensor_xyz && (xyz || !n), n, "frame too large");
 }
 uint32_t elev_tiles(uint32_t cells_side) { return (cells_side + kElevTile - 1u) / kElevTile; }
-// the slope kernels' instantiation for L = radius (1 .. 8: check_slope_config)
-using SlopeKernel = void (*)(const unsigned long long *, uint32_t, uint32_t, ElevParams, ElevSlopeParams, ElevRect, uint32_t, int8_t *, uint8_t *, long long *, unsigned int *);
-using SlopeToGridKernel = void (*)(const unsigned long long *, uint32_t, uint32_t, ElevParams, ElevSlopeParams, ElevRect, uint32_t, uint16_t *);
-SlopeKernel slope_kernel(uint32_t radius) {
-    static const SlopeKernel k[kElevSlopeMaxRadius] = {k_elev_slope<1>, k_elev_slope<2>, k_elev_slope<3>, k_elev_slope<4>, k_elev_slope<5>, k_elev_slope<6>, k_elev_slope<7>, k_elev_slope<8>};
-    return k[radius - 1u];
-}
-SlopeToGridKernel slope_to_grid_kernel(uint32_t radius) {
-    static const SlopeToGridKernel k[kElevSlopeMaxRadius] = {k_elev_slope_to_grid<1>, k_elev_slope_to_grid<2>, k_elev_slope_to_grid<3>, k_elev_slope_to_grid<4>,
-                                                             k_elev_slope_to_grid<5>, k_elev_slope_to_grid<6>, k_elev_slope_to_grid<7>, k_elev_slope_to_grid<8>};
-    return k[radius - 1u];
-}
 int check_rough_config(const kicp_elev_rough_config *cfg, ElevRoughParams &p) {
     p = ElevRoughParams{cfg->num, cfg->den};
     if (cfg->num > kElevRoughMaxRatio) return fail(KICP_ERR_ARG, "num must lie in 0 .. 65535");
     if (cfg->den < 1u || cfg->den > kElevRoughMaxRatio) return fail(KICP_ERR_ARG, "den must lie in 1 .. 65535");
     return KICP_OK;
 }
-// the rough kernels' instantiation for L = radius, as the slope kernels'
-using RoughKernel = void (*)(const unsigned long long *, uint32_t, uint32_t, ElevParams, ElevSlopeParams, ElevRoughParams, ElevRect, uint32_t, int8_t *, uint8_t *, long long *,
-                             unsigned int *);
-using RoughToGridKernel = void (*)(const unsigned long long *, uint32_t, uint32_t, ElevParams, ElevSlopeParams, ElevRoughParams, ElevRect, uint32_t, uint16_t *);
-RoughKernel rough_kernel(uint32_t radius) {
-    static const RoughKernel k[kElevSlopeMaxRadius] = {k_elev_rough<1>, k_elev_rough<2>, k_elev_rough<3>, k_elev_rough<4>, k_elev_rough<5>, k_elev_rough<6>, k_elev_rough<7>, k_elev_rough<8>};
+// The classes an entry reads out: the plain ones, with the slope limit (fit), with ROUGH too (fit and rough).
+struct ElevClasses {
+    ElevParams p{};
+    ElevSlopeParams sp{};
+    ElevRoughParams rp{};
+    bool fit = false, rough = false;
+    size_t fit_values() const { return !fit ? 0u : rough ? kElevFitValues<true> : kElevFitValues<false>; }  // per cell
+    int counts() const { return !fit ? 4 : static_cast<int>(rough ? kElevFitCounts<true> : kElevFitCounts<false>); }
+};
+// cfg and, where the entry takes them (else null), slope and rough; an entry with rough has slope
+int check_classes(const kicp_elev_traversability_config *cfg, const kicp_elev_slope_config *slope, const kicp_elev_rough_config *rough, ElevClasses &c) {
+    c.fit = slope != nullptr, c.rough = rough != nullptr;
+    if (int rc = check_elev_params(cfg, c.p)) return rc;
+    if (slope)
+        if (int rc = check_slope_config(slope, c.sp)) return rc;
+    if (rough)
+        if (int rc = check_rough_config(rough, c.rp)) return rc;
+    return KICP_OK;
+}
+// The fit kernels' instantiations for L = radius (1 .. 8: check_slope_config), with and without ROUGH.
+struct FitKernels {
+    void (*readout)(const unsigned long long *, uint32_t, uint32_t, ElevParams, ElevSlopeParams, ElevRoughParams, ElevRect, uint32_t, int8_t *, uint8_t *, long long *, unsigned int *);
+    void (*to_grid)(const unsigned long long *, uint32_t, uint32_t, ElevParams, ElevSlopeParams, ElevRoughParams, ElevRect, uint32_t, uint16_t *);
+};
+template <bool Rough, size_t... I>
+FitKernels fit_kernels(uint32_t radius, std::index_sequence<I...>) {
+    static const FitKernels k[] = {{k_elev_fit<static_cast<int>(I) + 1, Rough>, k_elev_fit_to_grid<static_cast<int>(I) + 1, Rough>}...};
     return k[radius - 1u];
 }
-RoughToGridKernel rough_to_grid_kernel(uint32_t radius) {
-    static const RoughToGridKernel k[kElevSlopeMaxRadius] = {k_elev_rough_to_grid<1>, k_elev_rough_to_grid<2>, k_elev_rough_to_grid<3>, k_elev_rough_to_grid<4>,
-                                                             k_elev_rough_to_grid<5>, k_elev_rough_to_grid<6>, k_elev_rough_to_grid<7>, k_elev_rough_to_grid<8>};
-    return k[radius - 1u];
+FitKernels fit_kernels(const ElevClasses &c) {
+    constexpr std::make_index_sequence<kElevSlopeMaxRadius> radii{};
+    return c.rough ? fit_kernels<true>(c.sp.radius, radii) : fit_kernels<false>(c.sp.radius, radii);
 }
 // what kicp_elev_to_grid, kicp_elev_to_grid_slope and kicp_elev_to_grid_rough ask of the grid: the layer's plane, on the layer's device
 int check_to_grid(const kicp_elev *elev, const kicp_grid *grid) {
@@ -179,6 +188,76 @@ int check_to_grid(const kicp_elev *elev, const kicp_grid *grid) {
         return fail(KICP_ERR_ARG, "the grid's cell, origin, width and height must equal the layer's");
     if (grid->device != elev->device)
         return fail(KICP_ERR_ARG, "the grid lives on device " + std::to_string(grid->device) + ", the layer on device " + std::to_string(elev->device));
+    return KICP_OK;
+}
+// The classes c of the rectangle r (arguments checked up to here) on the device: the launch, the results back, the stream drained.
+// out_ground, out_fit (c.fit_values() per cell; null without a fit) and out_counts (c.counts() words) are nullable.
+int readout_on_device(const kicp_elev *elev, const ElevClasses &c, const ElevRect &r, signed char *out, unsigned char *out_ground, long long *out_fit,
+                      unsigned long long *out_counts, size_t cap) {
+    if (int rc = check_elev_rect(elev->cfg.width, elev->cfg.height, r, cap)) return rc;
+    if (int rc = set_device(elev->device)) return rc;
+    auto &ro = elev->readout;
+    const size_t fit_values = c.fit_values() * cap;
+    if (int rc = ro.d_classes.reserve(cap)) return rc;
+    if (out_ground)
+        if (int rc = ro.d_ground.reserve(cap)) return rc;
+    if (out_fit)
+        if (int rc = ro.d_fit.reserve(fit_values)) return rc;
+    if (out_counts) {
+        if (int rc = ro.d_counts.reserve(kElevCountWords)) return rc;
+        if (int rc = ro.h_counts.reserve(kElevCountWords, hipHostMallocDefault, false)) return rc;
+    }
+    hipStream_t st = elev->stream;
+    if (out_counts) HIP_TRY(hipMemsetAsync(ro.d_counts.get(), 0, kElevCountWords * sizeof(unsigned int), st));
+    const uint32_t tiles_x = elev_tiles(r.w), tiles_y = elev_tiles(r.h);  // (their product stays below 2^25: cells <= 2^28)
+    uint8_t *d_ground = out_ground ? ro.d_ground.get() : nullptr;
+    long long *d_fit = out_fit ? ro.d_fit.get() : nullptr;
+    unsigned int *d_counts = out_counts ? ro.d_counts.get() : nullptr;
+    if (c.fit)
+        hipLaunchKernelGGL(fit_kernels(c).readout, dim3(tiles_x * tiles_y), dim3(kElevBlock), 0, st, elev->d_columns.get(), elev->cfg.width, elev->cfg.height, c.p, c.sp, c.rp, r,
+                           tiles_x, ro.d_classes.get(), d_ground, d_fit, d_counts);
+    else
+        hipLaunchKernelGGL(k_elev_classify, dim3(tiles_x * tiles_y), dim3(kElevBlock), 0, st, elev->d_columns.get(), elev->cfg.width, elev->cfg.height, c.p, r, tiles_x,
+                           ro.d_classes.get(), d_ground, d_counts);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(out, ro.d_classes.get(), cap, hipMemcpyDeviceToHost, st));
+    if (out_ground) HIP_TRY(hipMemcpyAsync(out_ground, ro.d_ground.get(), cap, hipMemcpyDeviceToHost, st));
+    if (out_fit) HIP_TRY(hipMemcpyAsync(out_fit, ro.d_fit.get(), fit_values * sizeof(long long), hipMemcpyDeviceToHost, st));
+    if (out_counts) HIP_TRY(hipMemcpyAsync(ro.h_counts.get(), ro.d_counts.get(), kElevCountWords * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (out_counts)
+        for (int k = 0; k < c.counts(); ++k) out_counts[k] = shard_sum(ro.h_counts.get(), k);
+    return KICP_OK;
+}
+// The classes c of every cell into the grid's counters.  Both handles' streams are idle (the stream rule); the launch runs on the
+// layer's and is waited for, so the grid's next entry finds its counters written.
+int to_grid_on_device(const kicp_elev *elev, const ElevClasses &c, kicp_grid *grid) {
+    if (int rc = check_to_grid(elev, grid)) return rc;
+    if (int rc = set_device(elev->device)) return rc;
+    const kicp_elev_config &ec = elev->cfg;
+    const ElevRect r{0u, 0u, ec.width, ec.height};
+    const uint32_t tiles_x = elev_tiles(ec.width), tiles_y = elev_tiles(ec.height);
+    if (c.fit)
+        hipLaunchKernelGGL(fit_kernels(c).to_grid, dim3(tiles_x * tiles_y), dim3(kElevBlock), 0, elev->stream, elev->d_columns.get(), ec.width, ec.height, c.p, c.sp, c.rp, r,
+                           tiles_x, grid->d_counts.get());
+    else
+        hipLaunchKernelGGL(k_elev_to_grid, dim3(tiles_x * tiles_y), dim3(kElevBlock), 0, elev->stream, elev->d_columns.get(), ec.width, ec.height, c.p, r, tiles_x,
+                           grid->d_counts.get());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(elev->stream));
+    return KICP_OK;
+}
+// The classes c of the rectangle r of columns given on the host (the *_from_columns entries; c checked): the outputs as readout_on_device's.
+int classify_columns(const unsigned long long *columns, unsigned int width, unsigned int height, const ElevClasses &c, const ElevRect &r, signed char *out,
+                     unsigned char *out_ground, long long *out_fit, unsigned long long *out_counts, size_t cap) {
+    if (int rc = check_grid_dims(width, height)) return rc;
+    if (int rc = check_elev_rect(width, height, r, cap)) return rc;
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "a column is 64 bits");
+    const uint64_t *col = reinterpret_cast<const uint64_t *>(columns);
+    int8_t *classes = reinterpret_cast<int8_t *>(out);
+    if (!c.fit) elev_host::classify(col, width, height, c.p, r, classes, out_ground, out_counts);
+    else if (!c.rough) elev_host::classify_fit<false>(col, width, height, c.p, c.sp, c.rp, r, classes, out_ground, out_fit, out_counts);
+    else elev_host::classify_fit<true>(col, width, height, c.p, c.sp, c.rp, r, classes, out_ground, out_fit, out_counts);
     return KICP_OK;
 }
 }  // namespace
@@ -309,209 +388,74 @@ int kicp_elev_traversability(const kicp_elev *elev, const kicp_elev_traversabili
                              signed char *out, unsigned char *out_ground, unsigned long long out_counts[4], size_t cap) {
     KICP_TRACE_CALL();
     if (!elev || !cfg || !out) return fail(KICP_ERR_ARG, "null argument");
-    ElevParams p;
-    const ElevRect r{x0, y0, w, h};
-    if (int rc = check_elev_params(cfg, p)) return rc;
-    if (int rc = check_elev_rect(elev->cfg.width, elev->cfg.height, r, cap)) return rc;
-    if (int rc = set_device(elev->device)) return rc;
-    auto &ro = elev->readout;
-    if (int rc = ro.d_classes.reserve(cap)) return rc;
-    if (out_ground)
-        if (int rc = ro.d_ground.reserve(cap)) return rc;
-    if (out_counts) {
-        if (int rc = ro.d_counts.reserve(kElevCountWords)) return rc;
-        if (int rc = ro.h_counts.reserve(kElevCountWords, hipHostMallocDefault, false)) return rc;
-    }
-    hipStream_t st = elev->stream;
-    if (out_counts) HIP_TRY(hipMemsetAsync(ro.d_counts.get(), 0, kElevCountWords * sizeof(unsigned int), st));
-    const uint32_t tiles_x = elev_tiles(w), tiles_y = elev_tiles(h);  // (their product stays below 2^25: cells <= 2^28)
-    hipLaunchKernelGGL(k_elev_classify, dim3(tiles_x * tiles_y), dim3(kElevBlock), 0, st, elev->d_columns.get(), elev->cfg.width, elev->cfg.height, p, r, tiles_x,
-                       ro.d_classes.get(), out_ground ? ro.d_ground.get() : static_cast<uint8_t *>(nullptr),
-                       out_counts ? ro.d_counts.get() : static_cast<unsigned int *>(nullptr));
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(out, ro.d_classes.get(), cap, hipMemcpyDeviceToHost, st));
-    if (out_ground) HIP_TRY(hipMemcpyAsync(out_ground, ro.d_ground.get(), cap, hipMemcpyDeviceToHost, st));
-    if (out_counts) HIP_TRY(hipMemcpyAsync(ro.h_counts.get(), ro.d_counts.get(), kElevCountWords * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (out_counts)
-        for (int k = 0; k < 4; ++k) out_counts[k] = shard_sum(ro.h_counts.get(), k);
-    return KICP_OK;
+    ElevClasses c;
+    if (int rc = check_classes(cfg, nullptr, nullptr, c)) return rc;
+    return readout_on_device(elev, c, ElevRect{x0, y0, w, h}, out, out_ground, nullptr, out_counts, cap);
 }
 int kicp_elev_traversability_from_columns(const unsigned long long *columns, unsigned int width, unsigned int height, const kicp_elev_traversability_config *cfg,
                                           unsigned int x0, unsigned int y0, unsigned int w, unsigned int h, signed char *out, unsigned char *out_ground,
                                           unsigned long long out_counts[4], size_t cap) {
     if (!columns || !cfg || !out) return fail(KICP_ERR_ARG, "null argument");
-    ElevParams p;
-    const ElevRect r{x0, y0, w, h};
-    if (int rc = check_elev_params(cfg, p)) return rc;
-    if (int rc = check_grid_dims(width, height)) return rc;
-    if (int rc = check_elev_rect(width, height, r, cap)) return rc;
-    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "a column is 64 bits");
-    elev_host::classify(reinterpret_cast<const uint64_t *>(columns), width, height, p, r, reinterpret_cast<int8_t *>(out), out_ground, out_counts);
-    return KICP_OK;
+    ElevClasses c;
+    if (int rc = check_classes(cfg, nullptr, nullptr, c)) return rc;
+    return classify_columns(columns, width, height, c, ElevRect{x0, y0, w, h}, out, out_ground, nullptr, out_counts, cap);
 }
 int kicp_elev_to_grid(const kicp_elev *elev, const kicp_elev_traversability_config *cfg, kicp_grid *grid) {
     KICP_TRACE_CALL();
     if (!elev || !cfg || !grid) return fail(KICP_ERR_ARG, "null argument");
-    ElevParams p;
-    if (int rc = check_elev_params(cfg, p)) return rc;
-    const kicp_elev_config &ec = elev->cfg;
-    if (int rc = check_to_grid(elev, grid)) return rc;
-    if (int rc = set_device(elev->device)) return rc;
-    // Both handles' streams are idle (the stream rule); the launch runs on the layer's and is waited for, so the grid's next entry
-    // finds its counters written.
-    const uint32_t tiles_x = elev_tiles(ec.width), tiles_y = elev_tiles(ec.height);
-    hipLaunchKernelGGL(k_elev_to_grid, dim3(tiles_x * tiles_y), dim3(kElevBlock), 0, elev->stream, elev->d_columns.get(), ec.width, ec.height, p,
-                       ElevRect{0u, 0u, ec.width, ec.height}, tiles_x, grid->d_counts.get());
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(elev->stream));
-    return KICP_OK;
+    ElevClasses c;
+    if (int rc = check_classes(cfg, nullptr, nullptr, c)) return rc;
+    return to_grid_on_device(elev, c, grid);
 }
 int kicp_elev_traversability_slope(const kicp_elev *elev, const kicp_elev_traversability_config *cfg, const kicp_elev_slope_config *slope, unsigned int x0,
                                    unsigned int y0, unsigned int w, unsigned int h, signed char *out, unsigned char *out_ground, long long *out_fit,
                                    unsigned long long out_counts[5], size_t cap) {
     KICP_TRACE_CALL();
     if (!elev || !cfg || !slope || !out) return fail(KICP_ERR_ARG, "null argument");
-    ElevParams p;
-    ElevSlopeParams sp;
-    const ElevRect r{x0, y0, w, h};
-    if (int rc = check_elev_params(cfg, p)) return rc;
-    if (int rc = check_slope_config(slope, sp)) return rc;
-    if (int rc = check_elev_rect(elev->cfg.width, elev->cfg.height, r, cap)) return rc;
-    if (int rc = set_device(elev->device)) return rc;
-    auto &ro = elev->readout;
-    if (int rc = ro.d_classes.reserve(cap)) return rc;
-    if (out_ground)
-        if (int rc = ro.d_ground.reserve(cap)) return rc;
-    if (out_fit)
-        if (int rc = ro.d_fit.reserve(3 * cap)) return rc;
-    if (out_counts) {
-        if (int rc = ro.d_counts.reserve(kElevCountWords)) return rc;
-        if (int rc = ro.h_counts.reserve(kElevCountWords, hipHostMallocDefault, false)) return rc;
-    }
-    hipStream_t st = elev->stream;
-    if (out_counts) HIP_TRY(hipMemsetAsync(ro.d_counts.get(), 0, kElevCountWords * sizeof(unsigned int), st));
-    const uint32_t tiles_x = elev_tiles(w), tiles_y = elev_tiles(h);  // (their product stays below 2^25: cells <= 2^28)
-    hipLaunchKernelGGL(slope_kernel(sp.radius), dim3(tiles_x * tiles_y), dim3(kElevBlock), 0, st, elev->d_columns.get(), elev->cfg.width, elev->cfg.height, p, sp, r, tiles_x,
-                       ro.d_classes.get(), out_ground ? ro.d_ground.get() : static_cast<uint8_t *>(nullptr), out_fit ? ro.d_fit.get() : static_cast<long long *>(nullptr),
-                       out_counts ? ro.d_counts.get() : static_cast<unsigned int *>(nullptr));
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(out, ro.d_classes.get(), cap, hipMemcpyDeviceToHost, st));
-    if (out_ground) HIP_TRY(hipMemcpyAsync(out_ground, ro.d_ground.get(), cap, hipMemcpyDeviceToHost, st));
-    if (out_fit) HIP_TRY(hipMemcpyAsync(out_fit, ro.d_fit.get(), 3 * cap * sizeof(long long), hipMemcpyDeviceToHost, st));
-    if (out_counts) HIP_TRY(hipMemcpyAsync(ro.h_counts.get(), ro.d_counts.get(), kElevCountWords * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (out_counts)
-        for (int k = 0; k < KICP_ELEV_SLOPE_COUNTS; ++k) out_counts[k] = shard_sum(ro.h_counts.get(), k);
-    return KICP_OK;
+    ElevClasses c;
+    if (int rc = check_classes(cfg, slope, nullptr, c)) return rc;
+    return readout_on_device(elev, c, ElevRect{x0, y0, w, h}, out, out_ground, out_fit, out_counts, cap);
 }
 int kicp_elev_traversability_slope_from_columns(const unsigned long long *columns, unsigned int width, unsigned int height, const kicp_elev_traversability_config *cfg,
                                                 const kicp_elev_slope_config *slope, unsigned int x0, unsigned int y0, unsigned int w, unsigned int h, signed char *out,
                                                 unsigned char *out_ground, long long *out_fit, unsigned long long out_counts[5], size_t cap) {
     if (!columns || !cfg || !slope || !out) return fail(KICP_ERR_ARG, "null argument");
-    ElevParams p;
-    ElevSlopeParams sp;
-    const ElevRect r{x0, y0, w, h};
-    if (int rc = check_elev_params(cfg, p)) return rc;
-    if (int rc = check_slope_config(slope, sp)) return rc;
-    if (int rc = check_grid_dims(width, height)) return rc;
-    if (int rc = check_elev_rect(width, height, r, cap)) return rc;
-    elev_host::classify_slope(reinterpret_cast<const uint64_t *>(columns), width, height, p, sp, r, reinterpret_cast<int8_t *>(out), out_ground, out_fit, out_counts);
-    return KICP_OK;
+    ElevClasses c;
+    if (int rc = check_classes(cfg, slope, nullptr, c)) return rc;
+    return classify_columns(columns, width, height, c, ElevRect{x0, y0, w, h}, out, out_ground, out_fit, out_counts, cap);
 }
 int kicp_elev_to_grid_slope(const kicp_elev *elev, const kicp_elev_traversability_config *cfg, const kicp_elev_slope_config *slope, kicp_grid *grid) {
     KICP_TRACE_CALL();
     if (!elev || !cfg || !slope || !grid) return fail(KICP_ERR_ARG, "null argument");
-    ElevParams p;
-    ElevSlopeParams sp;
-    if (int rc = check_elev_params(cfg, p)) return rc;
-    if (int rc = check_slope_config(slope, sp)) return rc;
-    if (int rc = check_to_grid(elev, grid)) return rc;
-    if (int rc = set_device(elev->device)) return rc;
-    const kicp_elev_config &ec = elev->cfg;
-    const uint32_t tiles_x = elev_tiles(ec.width), tiles_y = elev_tiles(ec.height);  // (the streams: as kicp_elev_to_grid)
-    hipLaunchKernelGGL(slope_to_grid_kernel(sp.radius), dim3(tiles_x * tiles_y), dim3(kElevBlock), 0, elev->stream, elev->d_columns.get(), ec.width, ec.height, p, sp,
-                       ElevRect{0u, 0u, ec.width, ec.height}, tiles_x, grid->d_counts.get());
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(elev->stream));
-    return KICP_OK;
+    ElevClasses c;
+    if (int rc = check_classes(cfg, slope, nullptr, c)) return rc;
+    return to_grid_on_device(elev, c, grid);
 }
 int kicp_elev_traversability_rough(const kicp_elev *elev, const kicp_elev_traversability_config *cfg, const kicp_elev_slope_config *slope,
                                    const kicp_elev_rough_config *rough, unsigned int x0, unsigned int y0, unsigned int w, unsigned int h, signed char *out,
                                    unsigned char *out_ground, long long *out_fit, unsigned long long out_counts[6], size_t cap) {
     KICP_TRACE_CALL();
     if (!elev || !cfg || !slope || !rough || !out) return fail(KICP_ERR_ARG, "null argument");
-    ElevParams p;
-    ElevSlopeParams sp;
-    ElevRoughParams rp;
-    const ElevRect r{x0, y0, w, h};
-    if (int rc = check_elev_params(cfg, p)) return rc;
-    if (int rc = check_slope_config(slope, sp)) return rc;
-    if (int rc = check_rough_config(rough, rp)) return rc;
-    if (int rc = check_elev_rect(elev->cfg.width, elev->cfg.height, r, cap)) return rc;
-    if (int rc = set_device(elev->device)) return rc;
-    auto &ro = elev->readout;
-    if (int rc = ro.d_classes.reserve(cap)) return rc;
-    if (out_ground)
-        if (int rc = ro.d_ground.reserve(cap)) return rc;
-    if (out_fit)
-        if (int rc = ro.d_fit.reserve(5 * cap)) return rc;
-    if (out_counts) {
-        if (int rc = ro.d_counts.reserve(kElevCountWords)) return rc;
-        if (int rc = ro.h_counts.reserve(kElevCountWords, hipHostMallocDefault, false)) return rc;
-    }
-    hipStream_t st = elev->stream;
-    if (out_counts) HIP_TRY(hipMemsetAsync(ro.d_counts.get(), 0, kElevCountWords * sizeof(unsigned int), st));
-    const uint32_t tiles_x = elev_tiles(w), tiles_y = elev_tiles(h);  // (their product stays below 2^25: cells <= 2^28)
-    hipLaunchKernelGGL(rough_kernel(sp.radius), dim3(tiles_x * tiles_y), dim3(kElevBlock), 0, st, elev->d_columns.get(), elev->cfg.width, elev->cfg.height, p, sp, rp, r, tiles_x,
-                       ro.d_classes.get(), out_ground ? ro.d_ground.get() : static_cast<uint8_t *>(nullptr), out_fit ? ro.d_fit.get() : static_cast<long long *>(nullptr),
-                       out_counts ? ro.d_counts.get() : static_cast<unsigned int *>(nullptr));
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(out, ro.d_classes.get(), cap, hipMemcpyDeviceToHost, st));
-    if (out_ground) HIP_TRY(hipMemcpyAsync(out_ground, ro.d_ground.get(), cap, hipMemcpyDeviceToHost, st));
-    if (out_fit) HIP_TRY(hipMemcpyAsync(out_fit, ro.d_fit.get(), 5 * cap * sizeof(long long), hipMemcpyDeviceToHost, st));
-    if (out_counts) HIP_TRY(hipMemcpyAsync(ro.h_counts.get(), ro.d_counts.get(), kElevCountWords * sizeof(unsigned int), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (out_counts)
-        for (int k = 0; k < KICP_ELEV_ROUGH_COUNTS; ++k) out_counts[k] = shard_sum(ro.h_counts.get(), k);
-    return KICP_OK;
+    ElevClasses c;
+    if (int rc = check_classes(cfg, slope, rough, c)) return rc;
+    return readout_on_device(elev, c, ElevRect{x0, y0, w, h}, out, out_ground, out_fit, out_counts, cap);
 }
 int kicp_elev_traversability_rough_from_columns(const unsigned long long *columns, unsigned int width, unsigned int height, const kicp_elev_traversability_config *cfg,
                                                 const kicp_elev_slope_config *slope, const kicp_elev_rough_config *rough, unsigned int x0, unsigned int y0,
                                                 unsigned int w, unsigned int h, signed char *out, unsigned char *out_ground, long long *out_fit,
                                                 unsigned long long out_counts[6], size_t cap) {
     if (!columns || !cfg || !slope || !rough || !out) return fail(KICP_ERR_ARG, "null argument");
-    ElevParams p;
-    ElevSlopeParams sp;
-    ElevRoughParams rp;
-    const ElevRect r{x0, y0, w, h};
-    if (int rc = check_elev_params(cfg, p)) return rc;
-    if (int rc = check_slope_config(slope, sp)) return rc;
-    if (int rc = check_rough_config(rough, rp)) return rc;
-    if (int rc = check_grid_dims(width, height)) return rc;
-    if (int rc = check_elev_rect(width, height, r, cap)) return rc;
-    elev_host::classify_rough(reinterpret_cast<const uint64_t *>(columns), width, height, p, sp, rp, r, reinterpret_cast<int8_t *>(out), out_ground, out_fit, out_counts);
-    return KICP_OK;
+    ElevClasses c;
+    if (int rc = check_classes(cfg, slope, rough, c)) return rc;
+    return classify_columns(columns, width, height, c, ElevRect{x0, y0, w, h}, out, out_ground, out_fit, out_counts, cap);
 }
 int kicp_elev_to_grid_rough(const kicp_elev *elev, const kicp_elev_traversability_config *cfg, const kicp_elev_slope_config *slope,
                             const kicp_elev_rough_config *rough, kicp_grid *grid) {
     KICP_TRACE_CALL();
     if (!elev || !cfg || !slope || !rough || !grid) return fail(KICP_ERR_ARG, "null argument");
-    ElevParams p;
-    ElevSlopeParams sp;
-    ElevRoughParams rp;
-    if (int rc = check_elev_params(cfg, p)) return rc;
-    if (int rc = check_slope_config(slope, sp)) return rc;
-    if (int rc = check_rough_config(rough, rp)) return rc;
-    if (int rc = check_to_grid(elev, grid)) return rc;
-    if (int rc = set_device(elev->device)) return rc;
-    const kicp_elev_config &ec = elev->cfg;
-    const uint32_t tiles_x = elev_tiles(ec.width), tiles_y = elev_tiles(ec.height);  // (the streams: as kicp_elev_to_grid)
-    hipLaunchKernelGGL(rough_to_grid_kernel(sp.radius), dim3(tiles_x * tiles_y), dim3(kElevBlock), 0, elev->stream, elev->d_columns.get(), ec.width, ec.height, p, sp, rp,
-                       ElevRect{0u, 0u, ec.width, ec.height}, tiles_x, grid->d_counts.get());
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(elev->stream));
-    return KICP_OK;
+    ElevClasses c;
+    if (int rc = check_classes(cfg, slope, rough, c)) return rc;
+    return to_grid_on_device(elev, c, grid);
 }
 int kicp_elev_rough_limit(const kicp_elev_config *config, double rms_metres, unsigned int *num, unsigned int *den) {
     if (!config || !num || !den) return fail(KICP_ERR_ARG, "null argument");

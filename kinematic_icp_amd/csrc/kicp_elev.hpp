@@ -15,14 +15,13 @@
 //                    neighbours in LDS; the classes, the optional ground bytes and per-wave sums of the four counts are written
 //   k_elev_to_grid   the same classification (elev_classify_cell, one device function for both) written as the two 16-bit counters
 //                    of a kicp_grid
-//   k_elev_slope<L>  the same tile with a halo of L <= 8 cells in LDS: a lane whose cell is known also walks its (2 L + 1)^2 window of
-//                    grounds into nine integer sums, and a least-squares plane through them - three 64-bit determinants, compared
-//                    in 128-bit integers - adds the class SLOPE; the optional determinants and five counts are written.  One
-//                    instantiation per L, so that the walk unrolls
-//   k_elev_slope_to_grid<L>  that classification (elev_slope_cell, one device function for both) as a kicp_grid's counters
-//   k_elev_rough<L>  k_elev_slope<L>'s shape with a tenth sum, z^2: the residual of the fitted plane, Q, in 64-bit integers, compared as a
-//                    128-bit product, adds the class ROUGH; the optional D, Da, Db, Q, n and six counts are written
-//   k_elev_rough_to_grid<L>  that classification (elev_rough_cell, one device function for both) as a kicp_grid's counters
+//   k_elev_fit<L, Rough>  the same tile with a halo of L <= 8 cells in LDS: a lane whose cell is known also walks its (2 L + 1)^2 window
+//                    of grounds into nine integer sums, and a least-squares plane through them - three 64-bit determinants, compared
+//                    in 128-bit integers - adds the class SLOPE; the optional determinants and five counts are written.  With Rough
+//                    a tenth sum, z^2: the residual of the fitted plane, Q, in 64-bit integers, compared as a 128-bit product, adds the
+//                    class ROUGH; the optional D, Da, Db, Q, n and six counts are written.  One instantiation per L, so that the
+//                    walk unrolls; ONE text for both classes (elev_fit_cell), `if constexpr (Rough)` around what ROUGH adds
+//   k_elev_fit_to_grid<L, Rough>  that classification (elev_fit_cell, one device function for both) as a kicp_grid's counters
 // The atomics besides the OR and the AND are the statistics and the list's length: one add per wave per word that has something to add.
 // No kernel uses scratch; the mark, list and carve kernels use no LDS.
 #pragma once
@@ -48,6 +47,12 @@ static __device__ __forceinline__ void elev_wave_add(unsigned int *counter, bool
     const unsigned long long b = __ballot(flag);
     if ((threadIdx.x & 63u) == 0u && b) atomicAdd(counter, static_cast<unsigned int>(__popcll(b)));
 }
+// this lane's cell of a classification's tiles, relative to the rectangle's corner
+static __device__ __forceinline__ void elev_lane_cell(uint32_t tiles_x, uint32_t &rx, uint32_t &ry) {
+    rx = (blockIdx.x % tiles_x) * kElevTile + threadIdx.x % kElevTile, ry = (blockIdx.x / tiles_x) * kElevTile + threadIdx.x / kElevTile;
+}
+// a class as the (hits, misses) pair of a kicp_grid's cell, one 32-bit word: obstacle (1, 0), traversable (0, 1), unknown (0, 0)
+static __device__ __forceinline__ uint32_t elev_grid_word(int8_t value) { return value < 0 ? 0u : value ? 1u : 0x10000u; }
 
 // stats: kElevCountShards x kElevCountStride words; a wave adds skipped, outside_grid, outside_column, new_bits, new_cells to words
 // 0 .. 4 of its shard.  The used points are what the host derives: in steady state nearly every point is used and nothing is new, and
@@ -196,7 +201,7 @@ static __device__ __forceinline__ bool elev_classify_cell(const unsigned long lo
             for (uint32_t dx = 0; dx < 3u; ++dx)
                 if (dx != 1u || dy != 1u) step = step || elev_step(ground, grounds[(ty + dy) * kElevHalo + (tx + dx)], p);
     }
-    value = elev_value(c != 0ull, body, step, which);
+    value = elev_value(which, c != 0ull, body, step);
     return inside;
 }
 
@@ -211,7 +216,8 @@ static __global__ __launch_bounds__(kElevBlock) void k_elev_classify(const unsig
     uint32_t which;
     const bool inside = elev_classify_cell(columns, width, height, p, r, tiles_x, grounds, value, ground, which);
     if (inside) {
-        const uint32_t rx = (blockIdx.x % tiles_x) * kElevTile + threadIdx.x % kElevTile, ry = (blockIdx.x / tiles_x) * kElevTile + threadIdx.x / kElevTile;
+        uint32_t rx, ry;
+        elev_lane_cell(tiles_x, rx, ry);
         const size_t o = static_cast<size_t>(ry) * r.w + rx;
         out[o] = value;
         if (out_ground) out_ground[o] = ground;
@@ -231,127 +237,37 @@ static __global__ __launch_bounds__(kElevBlock) void k_elev_to_grid(const unsign
     uint8_t ground;
     uint32_t which;
     if (!elev_classify_cell(columns, width, height, p, r, tiles_x, grounds, value, ground, which)) return;  // (behind the barrier)
-    const uint32_t x = (blockIdx.x % tiles_x) * kElevTile + threadIdx.x % kElevTile, y = (blockIdx.x / tiles_x) * kElevTile + threadIdx.x / kElevTile;
-    reinterpret_cast<uint32_t *>(grid_counts)[static_cast<size_t>(y) * width + x] = value < 0 ? 0u : value ? 1u : 0x10000u;
+    uint32_t x, y;
+    elev_lane_cell(tiles_x, x, y);
+    reinterpret_cast<uint32_t *>(grid_counts)[static_cast<size_t>(y) * width + x] = elev_grid_word(value);
 }
 
-// ---- the slope limit (kicp_elev_traversability_slope, kicp_elev_to_grid_slope) ------------------------------------------------------
-// The window of a known cell out of LDS into the nine sums.  L IS A TEMPLATE ARGUMENT: both loops unroll, dx, dy, their products and
-// the byte offsets become constants, and the walk of a fully known 1 600 x 1 600 layer at L = 8 takes 0.29 ms where the same loops
-// bounded by a kernel argument took 0.70.
-template <int L>
-static __device__ __forceinline__ void elev_slope_walk(const uint8_t *centre, uint32_t ground, uint32_t gate, ElevSlopeSums &s) {
+// ---- the plane fit: the slope limit and ROUGH (kicp_elev_traversability_slope / _rough, kicp_elev_to_grid_slope / _rough) --------------
+// The window of a known cell out of LDS into the nine sums, with Rough the tenth.  L IS A TEMPLATE ARGUMENT: both loops unroll, dx, dy,
+// their products and the byte offsets become constants, and the walk of a fully known 1 600 x 1 600 layer at L = 8 takes 0.29 ms where
+// the same loops bounded by a kernel argument took 0.70.
+template <int L, bool Rough>
+static __device__ __forceinline__ void elev_fit_walk(const uint8_t *centre, uint32_t ground, uint32_t gate, ElevFitSums &s) {
     constexpr int32_t side = static_cast<int32_t>(kElevTile) + 2 * L;
 #pragma unroll
     for (int32_t dy = -L; dy <= L; ++dy)
 #pragma unroll
-        for (int32_t dx = -L; dx <= L; ++dx) elev_slope_add(s, ground, centre[dy * side + dx], dx, dy, gate);
+        for (int32_t dx = -L; dx <= L; ++dx) elev_fit_add<Rough>(s, ground, centre[dy * side + dx], dx, dy, gate);
 }
-// The class of this lane's cell with the slope limit, the lane's cell as in elev_classify_cell: every lane of the workgroup calls it
-// (it holds the barrier).  L = sp.radius (the host picks the instantiation).  grounds: side^2 bytes of LDS, side = kElevTile + 2 L:
-// the tile's grounds and a halo of L cells, loaded by all lanes in a strided loop along rows, EVERY LOAD BEHIND THE INSIDE-THE-GRID
-// TEST; a cell outside the grid reads 255 like an unknown one.  After the barrier a lane whose cell is known walks its (2 L + 1)^2
-// window out of LDS into the nine sums; a lane whose cell is unknown skips the walk - most of a real layer is unknown, and a wave with
-// no known cell branches over it.  STEP comes from the same bytes, BODY from the lane's own column.  Every loop is bounded by L <= 8.
-// -> inside: the cell lies in the rectangle; value, ground, which (elev_slope_value) and d, da, db (zeros without a fit) are its results.
-template <int L>
-static __device__ __forceinline__ bool elev_slope_cell(const unsigned long long *__restrict__ columns, uint32_t width, uint32_t height, const ElevParams &p,
-                                                       const ElevSlopeParams &sp, const ElevRect &r, uint32_t tiles_x, uint8_t *grounds, int8_t &value, uint8_t &ground,
-                                                       uint32_t &which, int64_t &d, int64_t &da, int64_t &db) {
-    static_assert(L >= 1 && L <= static_cast<int>(kElevSlopeMaxRadius), "the halo is 1 .. 8 cells");
-    constexpr uint32_t side = kElevTile + 2u * L;
-    const uint32_t tx = threadIdx.x % kElevTile, ty = threadIdx.x / kElevTile;
-    const uint32_t bx = r.x0 + (blockIdx.x % tiles_x) * kElevTile, by = r.y0 + (blockIdx.x / tiles_x) * kElevTile;  // the tile's corner: inside the rectangle
-    const uint32_t x = bx + tx, y = by + ty;
-    const bool inside = x - r.x0 < r.w && y - r.y0 < r.h;  // (inside the rectangle implies inside the grid)
-#pragma unroll
-    for (uint32_t k = threadIdx.x; k < side * side; k += kElevBlock) {  // at most four trips
-        const uint32_t hx = k % side, hy = k / side;
-        const int64_t gx = static_cast<int64_t>(bx) + hx - L, gy = static_cast<int64_t>(by) + hy - L;
-        const bool ok = gx >= 0 && gy >= 0 && gx < static_cast<int64_t>(width) && gy < static_cast<int64_t>(height);
-        grounds[k] = ok ? elev_ground(columns[static_cast<size_t>(gy) * width + static_cast<size_t>(gx)]) : kElevNoGround;
-    }
-    __syncthreads();
-    const uint8_t *centre = grounds + (ty + L) * side + (tx + L);
-    ground = *centre;
-    const bool known = ground != kElevNoGround;
-    bool body = false, step = false, slope = false;
-    d = da = db = 0;
-    if (known) {  // (a known cell lies inside the grid: the load is behind that test)
-        body = elev_body(columns[static_cast<size_t>(y) * width + x], ground, p);
-#pragma unroll
-        for (int32_t dy = -1; dy <= 1; ++dy)
-#pragma unroll
-            for (int32_t dx = -1; dx <= 1; ++dx)
-                if (dx || dy) step = step || elev_step(ground, centre[dy * static_cast<int32_t>(side) + dx], p);
-        ElevSlopeSums s{};
-        elev_slope_walk<L>(centre, ground, sp.gate, s);
-        elev_slope_determinants(s, d, da, db);
-        if (elev_slope_has_fit(s, d, sp)) slope = elev_slope_exceeds(d, da, db, sp);
-        else d = da = db = 0;
-    }
-    value = elev_slope_value(known, body, step, slope, which);
-    return inside;
-}
-
-// out / out_ground (nullable) / out_fit (nullable: triples D, Da, Db): r.h * r.w entries; counts (nullable): kElevCountShards x
-// kElevCountStride words, a wave adds unknown, traversable, BODY, STEP only, SLOPE only to words 0 .. 4 of its shard
-template <int L>
-static __global__ __launch_bounds__(kElevBlock) void k_elev_slope(const unsigned long long *__restrict__ columns, uint32_t width, uint32_t height, ElevParams p,
-                                                                  ElevSlopeParams sp, ElevRect r, uint32_t tiles_x, int8_t *__restrict__ out,
-                                                                  uint8_t *__restrict__ out_ground, long long *__restrict__ out_fit, unsigned int *__restrict__ counts) {
-    __shared__ uint8_t grounds[(kElevTile + 2u * L) * (kElevTile + 2u * L)];
-    int8_t value;
-    uint8_t ground;
-    uint32_t which;
-    int64_t d, da, db;
-    const bool inside = elev_slope_cell<L>(columns, width, height, p, sp, r, tiles_x, grounds, value, ground, which, d, da, db);
-    if (inside) {
-        const uint32_t rx = (blockIdx.x % tiles_x) * kElevTile + threadIdx.x % kElevTile, ry = (blockIdx.x / tiles_x) * kElevTile + threadIdx.x / kElevTile;
-        const size_t o = static_cast<size_t>(ry) * r.w + rx;
-        out[o] = value;
-        if (out_ground) out_ground[o] = ground;
-        if (out_fit) out_fit[3 * o] = d, out_fit[3 * o + 1] = da, out_fit[3 * o + 2] = db;
-    }
-    if (counts) {
-        unsigned int *shard = elev_shard(counts);
-        for (uint32_t k = 0; k < 5u; ++k) elev_wave_add(&shard[k], inside && which == k);
-    }
-}
-
-// k_elev_to_grid with the slope limit: the rectangle is the full grid
-template <int L>
-static __global__ __launch_bounds__(kElevBlock) void k_elev_slope_to_grid(const unsigned long long *__restrict__ columns, uint32_t width, uint32_t height, ElevParams p,
-                                                                          ElevSlopeParams sp, ElevRect r, uint32_t tiles_x, uint16_t *__restrict__ grid_counts) {
-    __shared__ uint8_t grounds[(kElevTile + 2u * L) * (kElevTile + 2u * L)];
-    int8_t value;
-    uint8_t ground;
-    uint32_t which;
-    int64_t d, da, db;
-    if (!elev_slope_cell<L>(columns, width, height, p, sp, r, tiles_x, grounds, value, ground, which, d, da, db)) return;  // (behind the barrier)
-    const uint32_t x = (blockIdx.x % tiles_x) * kElevTile + threadIdx.x % kElevTile, y = (blockIdx.x / tiles_x) * kElevTile + threadIdx.x / kElevTile;
-    reinterpret_cast<uint32_t *>(grid_counts)[static_cast<size_t>(y) * width + x] = value < 0 ? 0u : value ? 1u : 0x10000u;
-}
-
-// ---- ROUGH (kicp_elev_traversability_rough, kicp_elev_to_grid_rough) ----------------------------------------------------------------
-// elev_slope_walk with the tenth sum.  A DEVICE FUNCTION OF ITS OWN, like elev_rough_cell below: the slope kernels keep the code they
-// were measured with, and the rough kernels repeat their shape.
-template <int L>
-static __device__ __forceinline__ void elev_rough_walk(const uint8_t *centre, uint32_t ground, uint32_t gate, ElevRoughSums &s) {
-    constexpr int32_t side = static_cast<int32_t>(kElevTile) + 2 * L;
-#pragma unroll
-    for (int32_t dy = -L; dy <= L; ++dy)
-#pragma unroll
-        for (int32_t dx = -L; dx <= L; ++dx) elev_rough_add(s, ground, centre[dy * side + dx], dx, dy, gate);
-}
-// elev_slope_cell with the class ROUGH: the same tile, the same halo of L cells staged the same way - EVERY LOAD BEHIND THE
-// INSIDE-THE-GRID TEST -, the same barrier that every lane of the workgroup reaches, unknown lanes skip the walk, every loop bounded by
-// L <= 8.  A cell with a fit also gets the residual Q (64-bit, by elev_rough_residual's bounds) and the 128-bit comparison.
-// -> inside: the cell lies in the rectangle; value, ground, which (elev_rough_value) and fit[5] = D, Da, Db, Q, n (zeros without a fit).
-template <int L>
-static __device__ __forceinline__ bool elev_rough_cell(const unsigned long long *__restrict__ columns, uint32_t width, uint32_t height, const ElevParams &p,
-                                                       const ElevSlopeParams &sp, const ElevRoughParams &rp, const ElevRect &r, uint32_t tiles_x, uint8_t *grounds,
-                                                       int8_t &value, uint8_t &ground, uint32_t &which, int64_t (&fit)[5]) {
+// The class of this lane's cell with the slope limit and, with Rough, the class ROUGH; the lane's cell as in elev_classify_cell: every
+// lane of the workgroup calls it (it holds the barrier).  L = sp.radius (the host picks the instantiation).  grounds: side^2 bytes of
+// LDS, side = kElevTile + 2 L: the tile's grounds and a halo of L cells, loaded by all lanes in a strided loop along rows, EVERY LOAD
+// BEHIND THE INSIDE-THE-GRID TEST; a cell outside the grid reads 255 like an unknown one.  After the barrier a lane whose cell is known
+// walks its (2 L + 1)^2 window out of LDS into the sums; a lane whose cell is unknown skips the walk - most of a real layer is unknown,
+// and a wave with no known cell branches over it.  STEP comes from the same bytes, BODY from the lane's own column.  Every loop is
+// bounded by L <= 8.  With Rough a cell with a fit also gets the residual Q (64-bit, by elev_rough_residual's bounds) and the 128-bit
+// comparison; rp is read with Rough only.
+// -> inside: the cell lies in the rectangle; value, ground, which (elev_value) and fit = D, Da, Db, with Rough also Q, n (zeros without
+// a fit) are its results.
+template <int L, bool Rough>
+static __device__ __forceinline__ bool elev_fit_cell(const unsigned long long *__restrict__ columns, uint32_t width, uint32_t height, const ElevParams &p,
+                                                     const ElevSlopeParams &sp, const ElevRoughParams &rp, const ElevRect &r, uint32_t tiles_x, uint8_t *grounds,
+                                                     int8_t &value, uint8_t &ground, uint32_t &which, int64_t (&fit)[kElevFitValues<Rough>]) {
     static_assert(L >= 1 && L <= static_cast<int>(kElevSlopeMaxRadius), "the halo is 1 .. 8 cells");
     constexpr uint32_t side = kElevTile + 2u * L;
     const uint32_t tx = threadIdx.x % kElevTile, ty = threadIdx.x / kElevTile;
@@ -370,7 +286,8 @@ static __device__ __forceinline__ bool elev_rough_cell(const unsigned long long 
     ground = *centre;
     const bool known = ground != kElevNoGround;
     bool body = false, step = false, slope = false, rough = false;
-    fit[0] = fit[1] = fit[2] = fit[3] = fit[4] = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < kElevFitValues<Rough>; ++k) fit[k] = 0;
     if (known) {  // (a known cell lies inside the grid: the load is behind that test)
         body = elev_body(columns[static_cast<size_t>(y) * width + x], ground, p);
 #pragma unroll
@@ -378,63 +295,69 @@ static __device__ __forceinline__ bool elev_rough_cell(const unsigned long long 
 #pragma unroll
             for (int32_t dx = -1; dx <= 1; ++dx)
                 if (dx || dy) step = step || elev_step(ground, centre[dy * static_cast<int32_t>(side) + dx], p);
-        ElevRoughSums s{};
-        elev_rough_walk<L>(centre, ground, sp.gate, s);
+        ElevFitSums s{};
+        elev_fit_walk<L, Rough>(centre, ground, sp.gate, s);
         int64_t d, da, db;
-        elev_slope_determinants(s.fit, d, da, db);
-        if (elev_slope_has_fit(s.fit, d, sp)) {
-            int64_t dc;
-            const int64_t q = elev_rough_residual(s, d, da, db, dc);
+        elev_slope_determinants(s, d, da, db);
+        if (elev_slope_has_fit(s, d, sp)) {  // THE ORDER COUNTS: residual, SLOPE, ROUGH, then the triple - stored first it costs 7 .. 10 VGPRs
+            if constexpr (Rough) {
+                int64_t dc;
+                fit[3] = elev_rough_residual(s, d, da, db, dc), fit[4] = s.n;
+            }
             slope = elev_slope_exceeds(d, da, db, sp);
-            rough = elev_rough_exceeds(q, d, s.fit.n, rp);
-            fit[0] = d, fit[1] = da, fit[2] = db, fit[3] = q, fit[4] = s.fit.n;
+            if constexpr (Rough) rough = elev_rough_exceeds(fit[3], d, s.n, rp);
+            fit[0] = d, fit[1] = da, fit[2] = db;
         }
     }
-    value = elev_rough_value(known, body, step, slope, rough, which);
+    value = elev_value(which, known, body, step, slope, rough);
     return inside;
 }
 
-// out / out_ground (nullable) / out_fit (nullable: D, Da, Db, Q, n per cell): r.h * r.w entries; counts (nullable): kElevCountShards x
-// kElevCountStride words, a wave adds unknown, traversable, BODY, STEP only, SLOPE only, ROUGH only to words 0 .. 5 of its shard
-template <int L>
-static __global__ __launch_bounds__(kElevBlock) void k_elev_rough(const unsigned long long *__restrict__ columns, uint32_t width, uint32_t height, ElevParams p,
-                                                                  ElevSlopeParams sp, ElevRoughParams rp, ElevRect r, uint32_t tiles_x, int8_t *__restrict__ out,
-                                                                  uint8_t *__restrict__ out_ground, long long *__restrict__ out_fit, unsigned int *__restrict__ counts) {
+// out / out_ground (nullable) / out_fit (nullable: kElevFitValues<Rough> values per cell): r.h * r.w entries; counts (nullable):
+// kElevCountShards x kElevCountStride words, a wave adds unknown, traversable, BODY, STEP only, SLOPE only and with Rough ROUGH only to
+// words 0 .. 4 or 5 of its shard
+template <int L, bool Rough>
+static __global__ __launch_bounds__(kElevBlock) void k_elev_fit(const unsigned long long *__restrict__ columns, uint32_t width, uint32_t height, ElevParams p,
+                                                                ElevSlopeParams sp, ElevRoughParams rp, ElevRect r, uint32_t tiles_x, int8_t *__restrict__ out,
+                                                                uint8_t *__restrict__ out_ground, long long *__restrict__ out_fit, unsigned int *__restrict__ counts) {
+    constexpr uint32_t values = kElevFitValues<Rough>;
     __shared__ uint8_t grounds[(kElevTile + 2u * L) * (kElevTile + 2u * L)];
     int8_t value;
     uint8_t ground;
     uint32_t which;
-    int64_t fit[5];
-    const bool inside = elev_rough_cell<L>(columns, width, height, p, sp, rp, r, tiles_x, grounds, value, ground, which, fit);
+    int64_t fit[values];
+    const bool inside = elev_fit_cell<L, Rough>(columns, width, height, p, sp, rp, r, tiles_x, grounds, value, ground, which, fit);
     if (inside) {
-        const uint32_t rx = (blockIdx.x % tiles_x) * kElevTile + threadIdx.x % kElevTile, ry = (blockIdx.x / tiles_x) * kElevTile + threadIdx.x / kElevTile;
+        uint32_t rx, ry;
+        elev_lane_cell(tiles_x, rx, ry);
         const size_t o = static_cast<size_t>(ry) * r.w + rx;
         out[o] = value;
         if (out_ground) out_ground[o] = ground;
         if (out_fit) {
 #pragma unroll
-            for (uint32_t k = 0; k < 5u; ++k) out_fit[5 * o + k] = fit[k];
+            for (uint32_t k = 0; k < values; ++k) out_fit[values * o + k] = fit[k];
         }
     }
     if (counts) {
         unsigned int *shard = elev_shard(counts);
-        for (uint32_t k = 0; k < 6u; ++k) elev_wave_add(&shard[k], inside && which == k);
+        for (uint32_t k = 0; k < kElevFitCounts<Rough>; ++k) elev_wave_add(&shard[k], inside && which == k);
     }
 }
 
-// k_elev_to_grid with the classes SLOPE and ROUGH: the rectangle is the full grid
-template <int L>
-static __global__ __launch_bounds__(kElevBlock) void k_elev_rough_to_grid(const unsigned long long *__restrict__ columns, uint32_t width, uint32_t height, ElevParams p,
-                                                                          ElevSlopeParams sp, ElevRoughParams rp, ElevRect r, uint32_t tiles_x,
-                                                                          uint16_t *__restrict__ grid_counts) {
+// k_elev_to_grid with the slope limit and, with Rough, the class ROUGH: the rectangle is the full grid
+template <int L, bool Rough>
+static __global__ __launch_bounds__(kElevBlock) void k_elev_fit_to_grid(const unsigned long long *__restrict__ columns, uint32_t width, uint32_t height, ElevParams p,
+                                                                        ElevSlopeParams sp, ElevRoughParams rp, ElevRect r, uint32_t tiles_x,
+                                                                        uint16_t *__restrict__ grid_counts) {
     __shared__ uint8_t grounds[(kElevTile + 2u * L) * (kElevTile + 2u * L)];
     int8_t value;
     uint8_t ground;
     uint32_t which;
-    int64_t fit[5];
-    if (!elev_rough_cell<L>(columns, width, height, p, sp, rp, r, tiles_x, grounds, value, ground, which, fit)) return;  // (behind the barrier)
-    const uint32_t x = (blockIdx.x % tiles_x) * kElevTile + threadIdx.x % kElevTile, y = (blockIdx.x / tiles_x) * kElevTile + threadIdx.x / kElevTile;
-    reinterpret_cast<uint32_t *>(grid_counts)[static_cast<size_t>(y) * width + x] = value < 0 ? 0u : value ? 1u : 0x10000u;
+    int64_t fit[kElevFitValues<Rough>];
+    if (!elev_fit_cell<L, Rough>(columns, width, height, p, sp, rp, r, tiles_x, grounds, value, ground, which, fit)) return;  // (behind the barrier)
+    uint32_t x, y;
+    elev_lane_cell(tiles_x, x, y);
+    reinterpret_cast<uint32_t *>(grid_counts)[static_cast<size_t>(y) * width + x] = elev_grid_word(value);
 }
 
 }  // namespace kicp

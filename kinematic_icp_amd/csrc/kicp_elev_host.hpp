@@ -3,7 +3,7 @@
 // 128-bit comparison -, ROUGH - a tenth sum, the fit's residual and its comparison -, and the carve along a frame's rays: which points
 // carve, the slab of a ray at a step, a step's mask and what it clears of a column.  ONE text for the kernels (kicp_elev.hpp), for the
 // pure-host entries (kicp_elev_traversability_from_columns, .._slope_from_columns, .._rough_from_columns, kicp_elev_update_columns) and
-// for elev_host::integrate / carve / update / classify / classify_slope / classify_rough, the host restatements that stand-alone
+// for elev_host::integrate / carve / update / classify / classify_fit (behind classify_slope and classify_rough), the host restatements that stand-alone
 // programs run under sanitizers (tests/cpp/elev_host_test.cpp, elev_carve_host_test.cpp, elev_slope_host_test.cpp, elev_rough_host_test.cpp).
 // Everything is exact and integer from the floor on.
 #pragma once
@@ -80,10 +80,17 @@ KICP_HD bool elev_body(uint64_t column, uint32_t ground, const ElevParams &p) {
 KICP_HD bool elev_step(uint32_t ground, uint8_t neighbour_ground, const ElevParams &p) {
     return neighbour_ground != kElevNoGround && ground > static_cast<uint32_t>(neighbour_ground) + p.step_slabs;
 }
-// the value of a cell and the count it adds to: 0 unknown, 1 traversable, 2 BODY, 3 STEP only
-KICP_HD int8_t elev_value(bool known, bool body, bool step, uint32_t &which) {
-    which = !known ? 0u : body ? 2u : step ? 3u : 1u;
-    return !known ? static_cast<int8_t>(-1) : static_cast<int8_t>((body || step) ? 100 : 0);
+// the value of a cell and the count it adds to: 0 unknown, 1 traversable, 2 BODY, 3 STEP only, 4 SLOPE only, 5 ROUGH only; the plain
+// classification passes neither slope nor rough, the slope limit no rough.  The count as a chain of overrides from the weakest reason
+// to the strongest: written so, the plain kernels compile to the code they had with a function of their own.
+KICP_HD int8_t elev_value(uint32_t &which, bool known, bool body, bool step, bool slope = false, bool rough = false) {
+    which = 1u;
+    if (rough) which = 5u;
+    if (slope) which = 4u;
+    if (step) which = 3u;
+    if (body) which = 2u;
+    if (!known) which = 0u;
+    return !known ? static_cast<int8_t>(-1) : static_cast<int8_t>((body || step || slope || rough) ? 100 : 0);
 }
 
 // ---- the slope limit: a least-squares plane through the known grounds of a window (kicp_elev_traversability_slope*) ---------------
@@ -93,28 +100,30 @@ struct ElevSlopeParams {
     uint32_t radius, gate, min_cells, rise, run;  // L, K, the fewest cells of a fit, and the limit: rise slabs per run cells
 };
 // The nine sums over a cell's FIT SET, z = g_n - g.  At L = 8: n <= 289, Sxx, Syy <= 6 936, |Sxy| <= 5 184, |Sz| <= 18 207, |Sxz|, |Syz| <=
-// 77 112 - 32 bits with room.
-struct ElevSlopeSums {
-    int32_t n, sx, sy, sxx, sxy, syy, sz, sxz, syz;
+// 77 112 - 32 bits with room.  ROUGH's tenth, Szz = sum z^2 <= 289 * 63^2 = 1 147 041 over the same set, stays zero for the slope limit.
+struct ElevFitSums {
+    int32_t n, sx, sy, sxx, sxy, syy, sz, sxz, syz, szz;
 };
 // One window cell (dx, dy) with ground byte neighbour_ground into the sums of a cell with ground g, when it belongs: known and
 // |g_n - g| <= K.  ONE unsigned comparison does both: K <= 63 and g <= 63, so the 255 of an unknown cell (or of one outside the grid)
-// gives 255 - g + K >= 192 + K > 2 K.
-KICP_HD void elev_slope_add(ElevSlopeSums &s, uint32_t ground, uint8_t neighbour_ground, int32_t dx, int32_t dy, uint32_t gate) {
+// gives 255 - g + K >= 192 + K > 2 K.  Rough: z^2 too.
+template <bool Rough>
+KICP_HD void elev_fit_add(ElevFitSums &s, uint32_t ground, uint8_t neighbour_ground, int32_t dx, int32_t dy, uint32_t gate) {
     if (static_cast<uint32_t>(neighbour_ground) - ground + gate > 2u * gate) return;
     const int32_t z = static_cast<int32_t>(neighbour_ground) - static_cast<int32_t>(ground);
     s.n += 1, s.sx += dx, s.sy += dy, s.sxx += dx * dx, s.sxy += dx * dy, s.syy += dy * dy, s.sz += z, s.sxz += dx * z, s.syz += dy * z;
+    if constexpr (Rough) s.szz += z * z;
 }
 // Cramer's rule on the normal equations of z ~ a dx + b dy + c: the gradient is (Da / D, Db / D) slabs per cell.  D is a Gram
 // determinant: >= 0, and 0 when the set lies on one line.  D < 2^34, |Da|, |Db| < 2^41, every product below 2^42: 64 bits.
-KICP_HD void elev_slope_determinants(const ElevSlopeSums &s, int64_t &d, int64_t &da, int64_t &db) {
+KICP_HD void elev_slope_determinants(const ElevFitSums &s, int64_t &d, int64_t &da, int64_t &db) {
     const int64_t n = s.n, sx = s.sx, sy = s.sy, sxx = s.sxx, sxy = s.sxy, syy = s.syy, sz = s.sz, sxz = s.sxz, syz = s.syz;
     d = sxx * (syy * n - sy * sy) - sxy * (sxy * n - sy * sx) + sx * (sxy * sy - syy * sx);
     da = sxz * (syy * n - sy * sy) - sxy * (syz * n - sy * sz) + sx * (syz * sy - syy * sz);
     db = sxx * (syz * n - sz * sy) - sxz * (sxy * n - sy * sx) + sx * (sxy * sz - syz * sx);
 }
 // the cell HAS A FIT
-KICP_HD bool elev_slope_has_fit(const ElevSlopeSums &s, int64_t d, const ElevSlopeParams &p) { return static_cast<uint32_t>(s.n) >= p.min_cells && d > 0; }
+KICP_HD bool elev_slope_has_fit(const ElevFitSums &s, int64_t d, const ElevSlopeParams &p) { return static_cast<uint32_t>(s.n) >= p.min_cells && d > 0; }
 // SLOPE of a cell that has a fit: (Da^2 + Db^2) run^2 > rise^2 D^2, strictly, on exact integers: the left side stays below 2^115, the
 // right below 2^100 - 128-bit products, no division, no floating point.
 KICP_HD bool elev_slope_exceeds(int64_t d, int64_t da, int64_t db, const ElevSlopeParams &p) {
@@ -123,11 +132,6 @@ KICP_HD bool elev_slope_exceeds(int64_t d, int64_t da, int64_t db, const ElevSlo
     const uint64_t run2 = static_cast<uint64_t>(p.run) * p.run, rise2 = static_cast<uint64_t>(p.rise) * p.rise;
     return (a * a + b * b) * run2 > dd * dd * rise2;
 }
-// the value of a cell and the count it adds to: 0 unknown, 1 traversable, 2 BODY, 3 STEP only, 4 SLOPE only
-KICP_HD int8_t elev_slope_value(bool known, bool body, bool step, bool slope, uint32_t &which) {
-    which = !known ? 0u : body ? 2u : step ? 3u : slope ? 4u : 1u;
-    return !known ? static_cast<int8_t>(-1) : static_cast<int8_t>((body || step || slope) ? 100 : 0);
-}
 
 // ---- ROUGH: the residual of that plane fit (kicp_elev_traversability_rough*) ------------------------------------------------------
 constexpr uint32_t kElevRoughMaxRatio = 65535;
@@ -135,27 +139,19 @@ constexpr uint32_t kElevRoughMaxRatio = 65535;
 struct ElevRoughParams {
     uint32_t num, den;  // the limit: a mean squared residual of num / den slabs^2
 };
-// The slope's nine sums and a tenth, Szz = sum z^2 <= 289 * 63^2 = 1 147 041 over the same fit set.
-struct ElevRoughSums {
-    ElevSlopeSums fit;
-    int32_t szz;
-};
-// elev_slope_add's twin: the same ONE comparison decides, the same nine sums, and z^2
-KICP_HD void elev_rough_add(ElevRoughSums &s, uint32_t ground, uint8_t neighbour_ground, int32_t dx, int32_t dy, uint32_t gate) {
-    if (static_cast<uint32_t>(neighbour_ground) - ground + gate > 2u * gate) return;
-    const int32_t z = static_cast<int32_t>(neighbour_ground) - static_cast<int32_t>(ground);
-    ElevSlopeSums &f = s.fit;
-    f.n += 1, f.sx += dx, f.sy += dy, f.sxx += dx * dx, f.sxy += dx * dy, f.syy += dy * dy, f.sz += z, f.sxz += dx * z, f.syz += dy * z;
-    s.szz += z * z;
-}
+// what a cell's fit and the counts hold: D, Da, Db and five classes; with ROUGH also Q, n and a sixth
+template <bool Rough>
+constexpr uint32_t kElevFitValues = Rough ? 5u : 3u;
+template <bool Rough>
+constexpr uint32_t kElevFitCounts = Rough ? 6u : 5u;
 // Q = D Szz - Da Sxz - Db Syz - Dc Sz: D times the residual sum of squares of the fit set to its least-squares plane, Dc the intercept's
 // determinant (the third column of the normal equations replaced).  IN 64 BITS, by these bounds at L = 8, K = 63: |Sx|, |Sy| <= 17 * 36 =
 // 612 < 2^10, Sxx, Syy, |Sxy| < 2^13, |Sz| < 2^15, |Sxz|, |Syz| < 2^17, Szz < 2^21.  The three terms of Dc: |Sxx (Syy Sz - Sy Syz)| <
 // 2^13 (2^28 + 2^27) < 2^42, |Sxy (Sxy Sz - Sx Syz)| < 2^42 likewise, |Sxz (Sxy Sy - Syy Sx)| < 2^17 * 2^24 = 2^41: |Dc| < 2^44.  The four
 // products: D Szz < 2^34 * 2^21 = 2^55, |Da Sxz|, |Db Syz| < 2^41 * 2^17 = 2^58, |Dc Sz| < 2^44 * 2^15 = 2^59; their absolute values sum
 // to less than 2^61, so no partial sum leaves 63 bits.  In exact arithmetic 0 <= Q <= D Szz < 2^55.
-KICP_HD int64_t elev_rough_residual(const ElevRoughSums &s, int64_t d, int64_t da, int64_t db, int64_t &dc) {
-    const int64_t sx = s.fit.sx, sy = s.fit.sy, sxx = s.fit.sxx, sxy = s.fit.sxy, syy = s.fit.syy, sz = s.fit.sz, sxz = s.fit.sxz, syz = s.fit.syz;
+KICP_HD int64_t elev_rough_residual(const ElevFitSums &s, int64_t d, int64_t da, int64_t db, int64_t &dc) {
+    const int64_t sx = s.sx, sy = s.sy, sxx = s.sxx, sxy = s.sxy, syy = s.syy, sz = s.sz, sxz = s.sxz, syz = s.syz;
     dc = sxx * (syy * sz - sy * syz) - sxy * (sxy * sz - sx * syz) + sxz * (sxy * sy - syy * sx);
     return d * static_cast<int64_t>(s.szz) - da * sxz - db * syz - dc * sz;
 }
@@ -164,11 +160,6 @@ KICP_HD int64_t elev_rough_residual(const ElevRoughSums &s, int64_t d, int64_t d
 KICP_HD bool elev_rough_exceeds(int64_t q, int64_t d, int32_t n, const ElevRoughParams &p) {
     typedef unsigned __int128 u128;
     return static_cast<u128>(static_cast<uint64_t>(q)) * p.den > static_cast<u128>(static_cast<uint64_t>(p.num) * static_cast<uint64_t>(n) * static_cast<uint64_t>(d));
-}
-// the value of a cell and the count it adds to: 0 unknown, 1 traversable, 2 BODY, 3 STEP only, 4 SLOPE only, 5 ROUGH only
-KICP_HD int8_t elev_rough_value(bool known, bool body, bool step, bool slope, bool rough, uint32_t &which) {
-    which = !known ? 0u : body ? 2u : step ? 3u : slope ? 4u : rough ? 5u : 1u;
-    return !known ? static_cast<int8_t>(-1) : static_cast<int8_t>((body || step || slope || rough) ? 100 : 0);
 }
 
 // ---- carving along the frame's rays (kicp_elev_update*) --------------------------------------------------------------------------
@@ -305,56 +296,21 @@ inline void classify(const uint64_t *columns, uint32_t width, uint32_t height, c
             }
             uint32_t which;
             const size_t o = static_cast<size_t>(ry) * r.w + rx;
-            out[o] = elev_value(c != 0ull, body, step, which);
+            out[o] = elev_value(which, c != 0ull, body, step);
             if (ground) ground[o] = gr;
             ++sums[which];
         }
     if (counts)
         for (int k = 0; k < 4; ++k) counts[k] = sums[k];
 }
-// The same with the slope limit, as k_elev_slope computes it: fit (nullable) takes D, Da, Db per cell, zeros where the cell has no fit;
-// counts (nullable): unknown, traversable, BODY, STEP only, SLOPE only.
-inline void classify_slope(const uint64_t *columns, uint32_t width, uint32_t height, const ElevParams &p, const ElevSlopeParams &sp, const ElevRect &r, int8_t *out,
-                           uint8_t *ground, long long *fit, unsigned long long counts[5]) {
-    unsigned long long sums[5] = {0, 0, 0, 0, 0};
-    const int32_t L = static_cast<int32_t>(sp.radius);
-    for (uint32_t ry = 0; ry < r.h; ++ry)
-        for (uint32_t rx = 0; rx < r.w; ++rx) {
-            const uint32_t x = r.x0 + rx, y = r.y0 + ry;
-            const uint64_t c = columns[static_cast<size_t>(y) * width + x];
-            const uint8_t gr = elev_ground(c);
-            bool body = false, step = false, slope = false;
-            int64_t d = 0, da = 0, db = 0;
-            if (c) {
-                body = elev_body(c, gr, p);
-                ElevSlopeSums s{};
-                for (int32_t dy = -L; dy <= L; ++dy)
-                    for (int32_t dx = -L; dx <= L; ++dx) {
-                        const int64_t nx = static_cast<int64_t>(x) + dx, ny = static_cast<int64_t>(y) + dy;
-                        if (nx < 0 || ny < 0 || nx >= static_cast<int64_t>(width) || ny >= static_cast<int64_t>(height)) continue;
-                        const uint8_t gn = elev_ground(columns[static_cast<size_t>(ny) * width + static_cast<size_t>(nx)]);
-                        elev_slope_add(s, gr, gn, dx, dy, sp.gate);
-                        if ((dx || dy) && dx >= -1 && dx <= 1 && dy >= -1 && dy <= 1) step = step || elev_step(gr, gn, p);
-                    }
-                elev_slope_determinants(s, d, da, db);
-                if (elev_slope_has_fit(s, d, sp)) slope = elev_slope_exceeds(d, da, db, sp);
-                else d = da = db = 0;
-            }
-            uint32_t which;
-            const size_t o = static_cast<size_t>(ry) * r.w + rx;
-            out[o] = elev_slope_value(c != 0ull, body, step, slope, which);
-            if (ground) ground[o] = gr;
-            if (fit) fit[3 * o] = d, fit[3 * o + 1] = da, fit[3 * o + 2] = db;
-            ++sums[which];
-        }
-    if (counts)
-        for (int k = 0; k < 5; ++k) counts[k] = sums[k];
-}
-// The same with the class ROUGH, as k_elev_rough computes it: fit (nullable) takes D, Da, Db, Q, n per cell, zeros where the cell has no
-// fit; counts (nullable): unknown, traversable, BODY, STEP only, SLOPE only, ROUGH only.
-inline void classify_rough(const uint64_t *columns, uint32_t width, uint32_t height, const ElevParams &p, const ElevSlopeParams &sp, const ElevRoughParams &rp,
-                           const ElevRect &r, int8_t *out, uint8_t *ground, long long *fit, unsigned long long counts[6]) {
-    unsigned long long sums[6] = {0, 0, 0, 0, 0, 0};
+// The same with a plane fit, as k_elev_fit<L, Rough> computes it: the slope limit and, with Rough, the class ROUGH.  fit (nullable) takes
+// kElevFitValues<Rough> values per cell - D, Da, Db, with Rough also Q, n -, zeros where the cell has no fit; counts (nullable):
+// kElevFitCounts<Rough> words - unknown, traversable, BODY, STEP only, SLOPE only, with Rough also ROUGH only.  rp is read with Rough only.
+template <bool Rough>
+inline void classify_fit(const uint64_t *columns, uint32_t width, uint32_t height, const ElevParams &p, const ElevSlopeParams &sp, const ElevRoughParams &rp,
+                         const ElevRect &r, int8_t *out, uint8_t *ground, long long *fit, unsigned long long *counts) {
+    constexpr uint32_t values = kElevFitValues<Rough>;
+    unsigned long long sums[kElevFitCounts<Rough>] = {};
     const int32_t L = static_cast<int32_t>(sp.radius);
     for (uint32_t ry = 0; ry < r.h; ++ry)
         for (uint32_t rx = 0; rx < r.w; ++rx) {
@@ -362,37 +318,49 @@ inline void classify_rough(const uint64_t *columns, uint32_t width, uint32_t hei
             const uint64_t c = columns[static_cast<size_t>(y) * width + x];
             const uint8_t gr = elev_ground(c);
             bool body = false, step = false, slope = false, rough = false;
-            int64_t d = 0, da = 0, db = 0, q = 0, n = 0;
+            int64_t v[5] = {0, 0, 0, 0, 0};  // D, Da, Db, Q, n
             if (c) {
                 body = elev_body(c, gr, p);
-                ElevRoughSums s{};
+                ElevFitSums s{};
                 for (int32_t dy = -L; dy <= L; ++dy)
                     for (int32_t dx = -L; dx <= L; ++dx) {
                         const int64_t nx = static_cast<int64_t>(x) + dx, ny = static_cast<int64_t>(y) + dy;
                         if (nx < 0 || ny < 0 || nx >= static_cast<int64_t>(width) || ny >= static_cast<int64_t>(height)) continue;
                         const uint8_t gn = elev_ground(columns[static_cast<size_t>(ny) * width + static_cast<size_t>(nx)]);
-                        elev_rough_add(s, gr, gn, dx, dy, sp.gate);
+                        elev_fit_add<Rough>(s, gr, gn, dx, dy, sp.gate);
                         if ((dx || dy) && dx >= -1 && dx <= 1 && dy >= -1 && dy <= 1) step = step || elev_step(gr, gn, p);
                     }
-                elev_slope_determinants(s.fit, d, da, db);
-                if (elev_slope_has_fit(s.fit, d, sp)) {
-                    int64_t dc;
-                    slope = elev_slope_exceeds(d, da, db, sp);
-                    q = elev_rough_residual(s, d, da, db, dc), n = s.fit.n;
-                    rough = elev_rough_exceeds(q, d, s.fit.n, rp);
+                elev_slope_determinants(s, v[0], v[1], v[2]);
+                if (elev_slope_has_fit(s, v[0], sp)) {
+                    slope = elev_slope_exceeds(v[0], v[1], v[2], sp);
+                    if constexpr (Rough) {
+                        int64_t dc;
+                        v[3] = elev_rough_residual(s, v[0], v[1], v[2], dc), v[4] = s.n;
+                        rough = elev_rough_exceeds(v[3], v[0], s.n, rp);
+                    }
                 } else {
-                    d = da = db = 0;
+                    v[0] = v[1] = v[2] = 0;
                 }
             }
             uint32_t which;
             const size_t o = static_cast<size_t>(ry) * r.w + rx;
-            out[o] = elev_rough_value(c != 0ull, body, step, slope, rough, which);
+            out[o] = elev_value(which, c != 0ull, body, step, slope, rough);
             if (ground) ground[o] = gr;
-            if (fit) fit[5 * o] = d, fit[5 * o + 1] = da, fit[5 * o + 2] = db, fit[5 * o + 3] = q, fit[5 * o + 4] = n;
+            if (fit)
+                for (uint32_t k = 0; k < values; ++k) fit[values * o + k] = v[k];
             ++sums[which];
         }
     if (counts)
-        for (int k = 0; k < 6; ++k) counts[k] = sums[k];
+        for (uint32_t k = 0; k < kElevFitCounts<Rough>; ++k) counts[k] = sums[k];
+}
+// the two names the stand-alone programs call
+inline void classify_slope(const uint64_t *columns, uint32_t width, uint32_t height, const ElevParams &p, const ElevSlopeParams &sp, const ElevRect &r, int8_t *out,
+                           uint8_t *ground, long long *fit, unsigned long long counts[5]) {
+    classify_fit<false>(columns, width, height, p, sp, ElevRoughParams{}, r, out, ground, fit, counts);
+}
+inline void classify_rough(const uint64_t *columns, uint32_t width, uint32_t height, const ElevParams &p, const ElevSlopeParams &sp, const ElevRoughParams &rp,
+                           const ElevRect &r, int8_t *out, uint8_t *ground, long long *fit, unsigned long long counts[6]) {
+    classify_fit<true>(columns, width, height, p, sp, rp, r, out, ground, fit, counts);
 }
 }  // namespace elev_host
 

@@ -130,6 +130,11 @@ def all_cases():
     return small_cases() + random_cases()
 
 
+def radius_cases():
+    """sc.radius_cases() with the squares' limit at L = 1 for ROUGH"""
+    return [(name, columns, params, slope, (1, 4), rects) for name, columns, params, slope, rects in sc.radius_cases()]
+
+
 _expected = {}
 
 

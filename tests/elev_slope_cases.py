@@ -165,6 +165,17 @@ def all_cases():
     return small_cases() + random_cases()
 
 
+RADIUS_RECTS = [None, (15, 15, 2, 2)]
+
+
+def radius_cases():
+    """One case per radius the fit kernels are instantiated for, L = 1 .. 8 - the suites above only ever launch 1, 2, 4 and 8 - on one
+    33 x 33 layer: three tiles per side, the last overhanging, and at L = 8 a halo wider than one trip of the tile's staging loop.  Every
+    ground admitted, the fewest cells, the squares' limit."""
+    columns = tilted_square(33, 133)
+    return [("radius_L%d" % L, columns, (2, 8), (L, 63, 3, 4, 5), RADIUS_RECTS) for L in range(1, 9)]
+
+
 _expected = {}
 
 

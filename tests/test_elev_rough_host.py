@@ -41,6 +41,15 @@ def test_host_entry_against_the_restatement(which):
         assert np.array_equal(fit[:, :, :3], triple), name
 
 
+@pytest.mark.parametrize("case", rc.radius_cases(), ids=lambda case: case[0])
+def test_host_entry_at_every_radius(case):
+    name, columns, (S, H), slope, rough, rects = case
+    assert (rc.expected(case).fit[:, :, 0] > 0).any(), name  # some cell has a fit
+    for rect in rects:
+        got, ground, fit, counts = K.traversability_rough_from_columns(columns, S, H, slope, rough, rect=rect, return_ground=True, return_fit=True, return_counts=True)
+        rc.check_result(case, rect, got, ground, fit, counts)
+
+
 def _build(tmp_path, name, extra):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     include = os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(hipcc))), "include")

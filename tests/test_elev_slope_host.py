@@ -37,6 +37,15 @@ def test_host_entry_against_the_restatement(which):
         assert np.array_equal(got[~only], plain[~only]) and (got[only] == 100).all() and (plain[only] == 0).all(), name
 
 
+@pytest.mark.parametrize("case", sc.radius_cases(), ids=lambda case: case[0])
+def test_host_entry_at_every_radius(case):
+    name, columns, (S, H), slope, rects = case
+    assert (sc.expected(case).fit[:, :, 0] > 0).any(), name  # some cell has a fit
+    for rect in rects:
+        got, ground, fit, counts = K.traversability_slope_from_columns(columns, S, H, slope, rect=rect, return_ground=True, return_fit=True, return_counts=True)
+        sc.check_result(case, rect, got, ground, fit, counts)
+
+
 def _build(tmp_path, name, extra):
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     include = os.path.join(os.path.dirname(os.path.dirname(os.path.realpath(hipcc))), "include")

@@ -60,6 +60,20 @@ def test_random_columns(kind):
             assert np.array_equal(fit[:, :, :3], triple)
 
 
+@pytest.mark.parametrize("case", rc.radius_cases(), ids=lambda case: case[0])
+def test_every_radius(case):
+    """the instantiation of each L = 1 .. 8, read out and into a grid"""
+    name, columns, (S, H), slope, rough, rects = case
+    assert (rc.expected(case).fit[:, :, 0] > 0).any(), name  # some cell has a fit
+    layer = layer_for(columns)
+    for rect in rects:
+        got, ground, fit, counts = layer.traversability_rough(S, H, slope, rough, rect=rect, return_ground=True, return_fit=True, return_counts=True)
+        rc.check_result(case, rect, got, ground, fit, counts)
+    grid = K.OccupancyGrid(0.25, 0.0, 0.0, columns.shape[1], columns.shape[0], -1.0, 1.0, 2.0)
+    layer.to_grid_rough(grid, S, H, slope, rough)
+    assert np.array_equal(grid.occupancy(1), rc.expected(case).classes), name
+
+
 def test_all_six_counts():
     case = [c for c in rc.random_cases() if c[0] == "random_sparse_1"][0]
     got, counts = layer_for(case[1]).traversability_rough(*case[2], case[3], case[4], return_counts=True)

@@ -58,6 +58,20 @@ def test_random_columns(kind):
             assert np.array_equal(got[~only], plain[~only]) and (got[only] == 100).all() and (plain[only] == 0).all()
 
 
+@pytest.mark.parametrize("case", sc.radius_cases(), ids=lambda case: case[0])
+def test_every_radius(case):
+    """the instantiation of each L = 1 .. 8, read out and into a grid"""
+    name, columns, (S, H), slope, rects = case
+    assert (sc.expected(case).fit[:, :, 0] > 0).any(), name  # some cell has a fit
+    layer = layer_for(columns)
+    for rect in rects:
+        got, ground, fit, counts = layer.traversability_slope(S, H, slope, rect=rect, return_ground=True, return_fit=True, return_counts=True)
+        sc.check_result(case, rect, got, ground, fit, counts)
+    grid = K.OccupancyGrid(0.25, 0.0, 0.0, columns.shape[1], columns.shape[0], -1.0, 1.0, 2.0)
+    layer.to_grid_slope(grid, S, H, slope)
+    assert np.array_equal(grid.occupancy(1), sc.expected(case).classes), name
+
+
 def test_to_grid_slope():
     case = [c for c in sc.random_cases() if c[0] == "random_sparse_1"][0]
     name, columns, (S, H), slope, _ = case

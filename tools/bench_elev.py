@@ -28,8 +28,8 @@ have completed.  Warm; everything that is compared alternates in the same proces
     the parent commit's library on the same columns, alternating (raw output kept as profiles/elev_slope_bench.json).
   - with --rough INSTEAD of the above: the class ROUGH (kicp_elev_traversability_rough, kicp_elev_to_grid_rough) at L = 2, 4 and 8 on that
     sparse layer and on a fully known one of the same size, beside the slope limit's and the plain calls of this build and, with
-    --ab parent=LIBRARY (twice, two builds of the parent commit: the spread between them is the yardstick), of the parent's, on the
-    same columns, alternating; with --fill also kicp_grid_fill_unknown of the grid kicp_elev_to_grid wrote from the mapping grid of
+    --ab parent=LIBRARY (twice, two builds of the parent commit: the spread between them is the yardstick), all three of the parent's
+    where it has them, on the same columns, alternating; with --fill also kicp_grid_fill_unknown of the grid kicp_elev_to_grid wrote from the mapping grid of
     the same frame, beside kicp_elev_to_grid (raw output kept as profiles/elev_rough_bench.json).
 Prints one JSON line.
 
@@ -339,9 +339,9 @@ def known_columns(width, height):
 
 def rough_rows(rounds, contenders, fill):
     """ROUGH (kicp_elev_traversability_rough, kicp_elev_to_grid_rough) at L = 2, 4 and 8 on slope_rows' sparse 1 600 x 1 600 layer and on
-    a fully known one of that size, beside kicp_elev_traversability_slope / kicp_elev_to_grid_slope and the plain calls of this build
-    and of every --ab contender (the parent commit's library, built twice: the spread between the two is the yardstick for this
-    build's existing calls), on the same columns, alternating.  With --fill also kicp_grid_fill_unknown of the grid kicp_elev_to_grid
+    a fully known one of that size, beside kicp_elev_traversability_slope / kicp_elev_to_grid_slope and the plain calls, each of this
+    build and of every --ab contender that has the entry (the parent commit's library, built twice: the spread between the two is the
+    yardstick for this build's existing calls), on the same columns, alternating.  With --fill also kicp_grid_fill_unknown of the grid kicp_elev_to_grid
     wrote, from the mapping grid of the same frame, without and with the seven counts, beside kicp_elev_to_grid as its yardstick."""
     name = "cfg1"
     cfg, scene, dirs, rng = scene_and_beams(name)
@@ -363,7 +363,6 @@ def rough_rows(rounds, contenders, fill):
         # theirs per call, which costs about a tenth of a plain call at this size)
         raws = {"this": RawClasses(K.lib(), gcfg, columns)}
         raws.update({who: RawClasses(lib, gcfg, columns) for who, lib in contenders.items()})
-        mine = raws["this"]
         rise, run = layer.slope_limit(np.tan(np.deg2rad(20.0)))
         slopes = {L: (L, (STEP_SLABS + 1) * L, 12, rise, run) for L in SLOPE_RADII}
         t, results, fills = {}, {}, None
@@ -387,9 +386,14 @@ def rough_rows(rounds, contenders, fill):
                     now["to_grid_slope_ms_L%d_%s" % (L, who)], _ = timed(lambda: raw.to_grid_slope(slopes[L]))
                     steep = theirs.copy() if steep is None else steep
                     assert np.array_equal(theirs, steep)
-                now["rough_full_ms_L%d" % L], full = timed(lambda: mine.traversability_rough(slopes[L], ROUGH_LIMIT))
-                full = full.copy()
-                now["to_grid_rough_ms_L%d" % L], _ = timed(lambda: mine.to_grid_rough(slopes[L], ROUGH_LIMIT))
+                full = None
+                for who, raw in turn:
+                    if not hasattr(raw.lib, "kicp_elev_traversability_rough"):  # (a contender from before ROUGH)
+                        continue
+                    now["rough_full_ms_L%d_%s" % (L, who)], theirs = timed(lambda: raw.traversability_rough(slopes[L], ROUGH_LIMIT))
+                    now["to_grid_rough_ms_L%d_%s" % (L, who)], _ = timed(lambda: raw.to_grid_rough(slopes[L], ROUGH_LIMIT))
+                    full = theirs.copy() if full is None else full
+                    assert np.array_equal(theirs, full)
                 layer.to_grid_rough(other, STEP_SLABS, ROBOT_SLABS, slopes[L], ROUGH_LIMIT)
                 now["rough_full_with_ground_fit_and_counts_ms_L%d" % L], counted = timed(
                     lambda: layer.traversability_rough(STEP_SLABS, ROBOT_SLABS, slopes[L], ROUGH_LIMIT, return_ground=True, return_fit=True, return_counts=True))
