@@ -123,7 +123,9 @@ unsigned long long kicp_map_device_updates(const kicp_map *map);
  *   5  launches of the wave-per-voxel insertion kernel           6  launches of the thread-per-voxel insertion kernel
  *   7  scans over many workgroups (> 16384 points)               8  updates handed to the host map
  *   9  updates left pending by kicp_map_update_pose_device_begin
- *  10  voxels touched by the last collected device-side update   11 0 (reserved) */
+ *  10  voxels touched by the last collected device-side update
+ *  11  pieces of kicp_map_pointcloud_f32 calls that the device announced and the host copied out (calls answered from the host
+ *      copy, the fallback behind a failed device path included, leave it alone) */
 int kicp_map_update_counts(const kicp_map *map, unsigned long long out[12]);
 /* Preferred device for BULK host-side insertions (not part of the reference API): with device >= 0, kicp_map_add_points /
  * kicp_map_update_origin / kicp_map_update_pose calls of 4096 points or more stage their points into HBM and insert them
@@ -1301,6 +1303,9 @@ size_t kicp_pre_ingested_count(const kicp_pre *pre);
  *            launches and 256-bucket tiles of its second table (from the returned count; 0 when the guess was wrong).
  *   "scan_launches" (read only): launches of the separate block-count scan this handle has made so far - one per compaction
  *            or gather whose grid exceeds 4 096 workgroups.
+ *   "push_launches" / "push_pieces" (read only): launches of the kernel that pushes a chained call's returned frame into host
+ *            memory, piece by piece / pieces the copy worker has followed to their flag, summed over frames (it stops behind the
+ *            first piece shorter than the frame's piece size; read it after kicp_pre_download_finish has collected the frame).
  * Which way the last decode went (read only, host-side bookkeeping; for tests that must prove the regime they ran in).
  * "ingest_*": the last kicp_pre_ingest that decoded its message itself (not one that took a look-ahead slot, not an empty one);
  * "ahead_*": the last look-ahead decode (kicp_pre_ingest_ahead + the chained pre-steps; read it after the kicp_pre_ingest call

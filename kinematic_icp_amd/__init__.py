@@ -1466,11 +1466,12 @@ class VoxelHashMap:
         return lib().kicp_map_device_updates(self._h)
 
     UPDATE_COUNTS = ("one_queue", "staged", "second_claims", "rehashes", "pool_growths", "apply_wave", "apply_thread", "wide_scans",
-                     "host_updates", "deferred", "touched", "reserved")
+                     "host_updates", "deferred", "touched", "record_pieces")
 
     def update_counts(self):
         """Which way this map's updates went so far (kicp_map_update_counts, include/kicp.h): a dict of the twelve host-side
-        counters; reads no device state and does not collect a pending update."""
+        counters; reads no device state and does not collect a pending update.  "record_pieces": pieces of PointcloudF32 /
+        kicp_map_pointcloud_f32 calls that the device announced and the host copied (the host path and the fallback leave it alone)."""
         out = (C.c_ulonglong * 12)()
         _check(lib().kicp_map_update_counts(self._h, out))
         return dict(zip(self.UPDATE_COUNTS, out))

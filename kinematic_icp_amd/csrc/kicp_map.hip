@@ -186,7 +186,7 @@ int decode_update_error(uint32_t error) {
 
 // the entries of kicp_map::update_counts (kicp_map_update_counts, include/kicp.h)
 enum UpdateCount { kCountOneQueue = 0, kCountStaged, kCountSecondClaims, kCountRehashes, kCountPoolGrowths, kCountApplyWave, kCountApplyThread,
-                   kCountWideScans, kCountHostUpdates, kCountDeferred, kCountTouched };
+                   kCountWideScans, kCountHostUpdates, kCountDeferred, kCountTouched, kCountRecordPieces };
 
 // make the device pools (and the free-list stack) hold at least `want_buckets` buckets, keeping their contents
 int grow_pools(kicp_map *map, size_t want_buckets) {
@@ -729,6 +729,7 @@ int kicp_map_pointcloud_f32(const kicp_map *cmap, float *out_xyz, size_t cap_poi
             if (i + kSlots < pieces)
                 if (int rc = queue(i + kSlots)) return rc;
         }
+        map->update_counts[kCountRecordPieces] += pieces;  // (all of them, or the fallback answers and none counts)
         return KICP_OK;
     };
     if (int rc = gather()) {  // as kicp_map_pointcloud: the host copy, refreshed, is the answer then

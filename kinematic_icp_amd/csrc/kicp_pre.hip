@@ -490,6 +490,8 @@ double kicp_pre_get_option(const kicp_pre *p, const char *name) {
     if (n == "l2_workgroups") return static_cast<double>(p->chain.last_l2_workgroups);
     if (n == "l2_tiles") return static_cast<double>(p->chain.last_l2_tiles);
     if (n == "scan_launches") return static_cast<double>(p->scan_launches);
+    if (n == "push_launches") return static_cast<double>(p->egress.push_launches);
+    if (n == "push_pieces") return static_cast<double>(p->egress.push_pieces);
     for (int slot = 0; slot < 2; ++slot) {  // "ingest_<counter>" / "ahead_<counter>": the last ingest_run of the slot
         const std::string prefix = slot ? "ahead_" : "ingest_";
         if (n.compare(0, prefix.size(), prefix) != 0) continue;

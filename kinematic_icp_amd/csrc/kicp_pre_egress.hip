@@ -76,6 +76,7 @@ int follow_pushed_pieces(kicp_pre *p, const EgressJob &job, size_t want) {
         const double left_ms = 2000.0 - std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
         rc = wait_word(flags + i, tag, 0xFFFFFFFF00000000ull, p->egress.stream, left_ms, "a piece of the frame was never announced", &f);
         if (rc) break;
+        ++p->egress.push_pieces;
         const size_t len = static_cast<size_t>(f & 0xFFFFFFFFull), off = job.piece_bytes * i;
         if (g_trace) landed_us[i] = std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count();
         if (len && job.dst && off < want) std::memcpy(static_cast<unsigned char *>(job.dst) + off, p->egress.host.get() + off, std::min(len, want - off));
@@ -175,6 +176,7 @@ int egress_start_frame(kicp_pre *p, size_t n_in, void *out, size_t cap_points, b
         if (f32) hipLaunchKernelGGL(k_push_frame_f32, dim3(push_grid), dim3(256), 0, g.stream, q);
         else hipLaunchKernelGGL(k_push_frame, dim3(push_grid), dim3(256), 0, g.stream, q);
         HIP_TRY(hipGetLastError());
+        ++g.push_launches;
         job.mode = EgressJob::kPushed, job.piece_bytes = q.piece_bytes, job.push_seq = q.seq;
     } else {  // no mapped landing area: the worker also queues the DMA transfer, in pieces (its dozen API calls cost the calling thread ~40 us)
         job = transfer_job(out, cap_points, n_in);

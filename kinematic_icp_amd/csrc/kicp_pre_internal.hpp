@@ -140,6 +140,9 @@ struct kicp_pre {
         DevBuf<unsigned long long> d_push_tickets;  // [kPushPieces] device counters of k_push_frame, never reset
         unsigned long long push_drawn = 0;
         uint32_t push_seq = 0;
+        // read-only diagnostics (kicp_pre_get_option "push_launches" / "push_pieces"): push kernels queued by the caller's thread; pieces
+        // the worker has followed to their flag - written by the worker, read once its job has been joined
+        unsigned long long push_launches = 0, push_pieces = 0;
         // the registration source (buffer 2, ~100 KB) also lands in host memory as the fused chain's last launch writes it: the pipeline
         // returns it too (KinematicICP.cpp:84), and a copy + stream synchronisation for it cost the frame ~40 us
         PinnedBuf<unsigned char> h_src;  // (dev() == nullptr: not mapped)
