@@ -134,13 +134,13 @@ int kicp_map_update_counts(const kicp_map *map, unsigned long long out[12]);
 int kicp_map_set_device(kicp_map *map, int device);
 size_t kicp_map_num_points(const kicp_map *map);
 size_t kicp_map_num_voxels(const kicp_map *map);
-/* Pointcloud() -- KinematicICP.hpp:92.  Writes min(cap_points, total) points, returns total. */
+/* Pointcloud() -- KinematicICP.hpp:92.  Writes min(cap_points, total) points, returns total (0 if a pending update fails). */
 size_t kicp_map_pointcloud(const kicp_map *map, double *out_xyz, size_t cap_points);
 /* The same cloud as the PointCloud2 `data` the node publishes for it (ros/.../utils/RosUtils.cpp:40-63 EigenToPointCloud2 of
  * LocalMap(), called from LidarOdometryServer.cpp:240-263 PublishClouds): x y z FLOAT32 records of 12 bytes (offsets 0 4 8,
  * little-endian), static_cast<float> of kicp_map_pointcloud's doubles, its order and its count.  Writes min(cap_points, total)
  * records (out_xyz may be NULL with cap_points 0: *out_total only).  A map whose HBM copy is the current one is narrowed on the
- * GPU, which writes the records into host-mapped memory piece by piece (kicp_mapdev.hpp k_pc_records; no fp64 copy crosses
+ * GPU, which writes the records into host-mapped memory piece by piece (kicp_map_pc.hpp k_pc_records; no fp64 copy crosses
  * PCIe); a map that lives on the host is narrowed there, with the same bits.  Unlike kicp_map_pointcloud it returns an error
  * code: a pending deferred update is collected first and its error is returned. */
 int kicp_map_pointcloud_f32(const kicp_map *map, float *out_xyz, size_t cap_points, size_t *out_total);

@@ -46,7 +46,7 @@ public:
     const std::vector<uint32_t> &free_list() const { return free_; }
     size_t num_entries() const { return n_entries_; }
     // a voxel beyond the range the device-side maintenance can pack (+-(2^20 - 1), one voxel of head-room for the neighbours) has
-    // been occupied since the last Clear(): updates of this map belong on the host (kicp_map.hip::map_update_device)
+    // been occupied since the last Clear(): updates of this map belong on the host (kicp_map_update.hip::map_update_device)
     bool has_far_voxel() const { return has_far_voxel_; }
     // make room so that `extra_entries` more table entries keep the load factor <= 0.25 (re-hashes if necessary)
     void ReserveEntries(size_t extra_entries) {

@@ -1,6 +1,6 @@
 // kicp_internal.hpp -- what the translation units behind include/kicp.h share: error handling, tracing, the staging
 // policy for caller memory, the HBM mirror of the voxel map and the handle behind kicp_map.  Host code only; the kernels
-// live in kicp_kernels.hpp and the headers it includes (registration passes), kicp_mapdev.hpp (map maintenance) and kicp_pre*.hpp (pre-steps), all with
+// live in kicp_kernels.hpp and the headers it includes (registration passes), kicp_mapdev.hpp / kicp_map_pc.hpp (map maintenance, Pointcloud) and kicp_pre*.hpp (pre-steps), all with
 // internal linkage so that every translation unit may include what it launches.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -352,9 +352,9 @@ struct kicp_map {
 
 namespace kicp {
 namespace host {
-// make the HBM mirror on `device` current / bring the host copy up to date after device-side updates (kicp_map.hip)
+// make the HBM mirror on `device` current / bring the host copy up to date after device-side updates (kicp_map.hip; kicp_map_internal.hpp: what else the map's units share)
 int map_sync(kicp_map *map, int device, hipStream_t stream);
 int ensure_host_current(kicp_map *map);
-int map_finish_pending(kicp_map *map);  // collect an update begun with kicp_map_update_pose_device_begin (no-op without one)
+int map_finish_pending(kicp_map *map);  // (kicp_map_update.hip) collect an update begun with kicp_map_update_pose_device_begin (no-op without one)
 }  // namespace host
 }  // namespace kicp

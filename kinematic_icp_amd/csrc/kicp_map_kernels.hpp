@@ -1,4 +1,4 @@
-// kicp_map_kernels.hpp -- the two kernels of kicp_map.hip that are not map maintenance (that is kicp_mapdev.hpp): the scatter of a delta
+// kicp_map_kernels.hpp -- the two kernels of kicp_map.hip, neither of them map maintenance (that is kicp_mapdev.hpp, kicp_map_update.hip): the scatter of a delta
 // upload's staged rows and the batch GetClosestNeighbor.  `static __global__`: a unit that includes this header emits both, so only
 // kicp_map.hip, which launches them, does.
 #pragma once

@@ -7,7 +7,7 @@
 // are deterministic and equal to the sequential reference's, order included.
 // HBM bound streaming kernels: 24-32 B read + <= 24 B written per point, fp64 throughout.
 // The kernels of the steps and of the fused chain; included by kicp_pre.hip alone.  The ingest's are in kicp_pre_ingest.hpp, the
-// frame's way back in kicp_pre_egress.hpp, the block scan (shared with kicp_map.hip) in kicp_scan_blocks.hpp.
+// frame's way back in kicp_pre_egress.hpp, the block scan (shared with kicp_map_cloud.hip) in kicp_scan_blocks.hpp.
 #pragma once
 #include <cmath>
 #include "kicp_common.hpp"

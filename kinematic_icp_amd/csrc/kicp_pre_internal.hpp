@@ -1,7 +1,7 @@
 // kicp_pre_internal.hpp -- what the translation units of the pipeline's pre-steps (kicp_pre*.hip) share: the handle behind kicp_pre,
 // the rules its entries keep, and what more than one of them calls.  include/kicp.h states the semantics.  The pieces, each the only
 // translation unit that includes its kernel header:
-//   kicp_pre.hip         the steps and the fused chain (kicp_pre.hpp; the block scan, kicp_scan_blocks.hpp, it shares with kicp_map.hip):
+//   kicp_pre.hip         the steps and the fused chain (kicp_pre.hpp; the block scan, kicp_scan_blocks.hpp, it shares with kicp_map_cloud.hip):
 //                        create / destroy, the options and the probe limit, kicp_pre_upload, kicp_pre_device_ptr, kicp_pre_preprocess*,
 //                        kicp_pre_voxel_downsample, kicp_pre_frame*
 //   kicp_pre_ingest.hip  a sensor message into the ingest slot (kicp_pre_ingest.hpp): kicp_pre_ingest, _ingest_scan, _ingest_ahead and

@@ -1,6 +1,6 @@
 // kicp_scan_blocks.hpp -- the exclusive scan of per-workgroup counts that order-preserving compactions share: as a launch of its
 // own (k_scan_blocks) or folded into the consumer (block_offset).  Included by the pre-steps (kicp_pre.hip) and by the map's
-// Pointcloud() (kicp_map.hip): the one kernel header that two translation units include, so k_scan_blocks is emitted twice.
+// Pointcloud() (kicp_map_cloud.hip): the one kernel header that two translation units include, so k_scan_blocks is emitted twice.
 #pragma once
 #include "kicp_common.hpp"
 

@@ -5,7 +5,7 @@
 // A handle owns its stream, its frame upload (kicp_internal.hpp) and its device memory: the image, the sweep's voxel list and the statistics.
 #include <memory>
 
-#include "kicp_internal.hpp"
+#include "kicp_map_internal.hpp"  // dev_map
 #include "kicp_view.hpp"
 
 using namespace kicp;
@@ -161,14 +161,10 @@ int kicp_map_remove_seen_through(kicp_map *map, kicp_view *view, unsigned long l
     hipStream_t st = nullptr;  // the map's kernels run on the null stream; the image is complete (the render drained its stream)
     if (n_voxels > view->d_list.capacity())
         if (int rc = view->d_list.reserve(n_voxels + n_voxels / 2)) return rc;
-    const uint32_t cap = map->host.cap();
-    const size_t slots = mr.live_slots, bucket_cap = mr.d_pool.capacity() / (static_cast<size_t>(cap) * 3);
-    const DevMap m{mr.d_table.get(), mr.d_keys64.get(), static_cast<uint32_t>(slots - 1), mr.d_pool.get(), mr.d_pool16.get(), cap, map->host.count_bits(),
-                   static_cast<uint32_t>(bucket_cap), map->host.voxel_size(), map->host.max_distance(), mr.d_free_list.get(), mr.d_cnt.get(), mr.d_seg_start.get(),
-                   mr.d_ctr.get()};
+    const DevMap m = dev_map(*map);
     unsigned int *d_sweep = view->d_stats.get() + 4, *d_n_list = view->d_stats.get() + 3;
     HIP_TRY(hipMemsetAsync(d_n_list, 0, (kStatWords - 3) * sizeof(unsigned int), st));
-    hipLaunchKernelGGL(k_view_list, dim3(static_cast<uint32_t>(std::min<size_t>((slots / 4 + kViewBlock - 1) / kViewBlock, 8192))), dim3(kViewBlock), 0, st, m, view->geom,
+    hipLaunchKernelGGL(k_view_list, dim3(static_cast<uint32_t>(std::min<size_t>((mr.live_slots / 4 + kViewBlock - 1) / kViewBlock, 8192))), dim3(kViewBlock), 0, st, m, view->geom,
                        view->frame, view->d_list.get(), d_n_list);
     // one wave per listed voxel; the list's length is on the device, the host's voxel count bounds it
     hipLaunchKernelGGL(k_view_sweep, dim3(static_cast<uint32_t>((n_voxels + kSweepWaves - 1) / kSweepWaves)), dim3(64 * kSweepWaves), 0, st, m, view->geom, view->frame,

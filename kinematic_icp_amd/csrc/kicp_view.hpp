@@ -22,7 +22,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "kicp_mapdev.hpp"
+#include "kicp_devmap.hpp"  // DevMap, dev_find: all the view needs of the map's device code, and no kernel comes with it
 #include "kicp_view_host.hpp"
 
 namespace kicp {

@@ -1,7 +1,7 @@
 """The case table of the regime tests of the clouds' way back to the host, shared by tests/test_egress_cases.py (CPU: the premises
 of every case, from the oracle and the rules restated here alone) and tests/test_gpu_egress_regimes.py (GPU: kicp_pre_egress.hpp
-k_push_frame / k_push_frame_f32 / k_narrow_f32, kicp_pre_egress.hip follow_pushed_pieces, kicp_mapdev.hpp k_pc_records and
-kicp_map.hip kicp_map_pointcloud_f32).
+k_push_frame / k_push_frame_f32 / k_narrow_f32, kicp_pre_egress.hip follow_pushed_pieces, kicp_map_pc.hpp k_pc_records and
+kicp_map_cloud.hip kicp_map_pointcloud_f32).
 
 The three piece rules are RESTATED from include/kicp.h and the comments of those files, not imported: a frame of n_in input points
 goes back in kPushPieces = 8 pieces of ceil(ceil(n_in * rec / 8) / 4096) * 4096 bytes (rec: 24 bytes a point as doubles, 12 as
@@ -22,7 +22,7 @@ PUSH_ALIGN = 4096          # a piece is a multiple of the bytes one workgroup st
 PUSH_SWEEP = 16 * 4096     # bytes one sweep of the default grid (16 workgroups) stores
 NARROW_GRID_WORDS = 1024 * 256  # words one turn of k_narrow_f32's grid narrows
 MAP_SLOTS = 4              # DeviceMirror::kRecSlots (kicp_internal.hpp)
-MAP_ROUND = 2048           # kPcRoundRecords (kicp_mapdev.hpp)
+MAP_ROUND = 2048           # kPcRoundRecords (kicp_map_pc.hpp)
 MAP_PIECE_MIN, MAP_PIECE_MAX = 1024, 65536
 BULK = 4096                # updates of at least this many points run on the map's device
 

@@ -193,6 +193,42 @@ def too_tight_premise(n, entries=0, slots=START_SLOTS):
     return (entries + n) * 2 <= slots, (entries + 27 * n) * 4 > 3 * slots, (entries + n + 26 * n) * 4 > 3 * slots
 
 
+# ---- two frames whose cloud comes out in ONE order ---------------------------------------------------------------------------
+# Pointcloud() lists the occupied voxels in table order, and a slot is claimed by whichever thread comes first: two maps that took the
+# same frames agree on the ORDER of their clouds only where no two voxels claimed in one launch compete for a slot.  The two frames
+# below are chosen so (tests/test_mapdev_scenes.py proves it from the table's arithmetic restated here).
+ORDERED_FRAMES = ((100, 0), (300, 2))  # (voxels, region) of the first and the second frame, one point per voxel
+ORDERED_SLOTS = 32768  # the table after the first frame: too tight in the fresh 1 024 slots, re-hashed for 4 (32 * 100 + 1 024) slots
+
+
+def ordered_frames():
+    """-> the two frames' world points (identity pose; a map with max_distance 1 000 prunes neither)"""
+    return [one_per_voxel(n, region, 0)["points"] for n, region in ORDERED_FRAMES]
+
+
+def voxel_hash(keys):
+    """kicp_common.hpp voxel_hash over rows of integer keys"""
+    k = np.asarray(keys, dtype=np.int64)
+    h = ((k[:, 0] * 73856093) ^ (k[:, 1] * 19349669) ^ (k[:, 2] * 83492791)) & 0xFFFFFFFF
+    h ^= h >> 16
+    h = (h * 0x85ebca6b) & 0xFFFFFFFF
+    h ^= h >> 13
+    h = (h * 0xc2b2ae35) & 0xFFFFFFFF
+    return h ^ (h >> 16)
+
+
+def slots_taken_alone(filled, keys):
+    """the slot each key takes by linear probing into `filled` (bool per slot) when it is the only one inserted.  Where these are
+    distinct every insertion order gives them: a key's walk only passes slots that were filled before, never another key's"""
+    out = []
+    for home in voxel_hash(keys) % len(filled):
+        s = int(home)
+        while filled[s]:
+            s = (s + 1) % len(filled)
+        out.append(s)
+    return np.array(out)
+
+
 # ---- queries for the final checks ----------------------------------------------------------------------------------------------
 def jittered_queries(cloud, vs, n=2000, seed=0):
     """about n queries: points of `cloud` moved by a tenth of a voxel (gaussian), a tenth of them by a voxel or more"""

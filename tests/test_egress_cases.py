@@ -27,9 +27,9 @@ def constant(text, name):
 
 def test_the_restated_rules_rest_on_the_sources_constants():
     assert constant(source("kicp_pre_shared.hpp"), "kPushPieces") == ec.PUSH_PIECES == 8
-    assert constant(source("kicp_mapdev.hpp"), "kPcRoundRecords") == ec.MAP_ROUND == 2048
+    assert constant(source("kicp_map_pc.hpp"), "kPcRoundRecords") == ec.MAP_ROUND == 2048
     assert constant(source("kicp_internal.hpp"), "kRecSlots") == ec.MAP_SLOTS == 4
-    egress, kernels, mapsrc = source("kicp_pre_egress.hip"), source("kicp_pre_egress.hpp"), source("kicp_map.hip")
+    egress, kernels, mapsrc = source("kicp_pre_egress.hip"), source("kicp_pre_egress.hpp"), source("kicp_map_cloud.hip")
     # the frame's piece size, the default grid and what one workgroup stores per sweep
     assert "((n_in * job.rec_bytes + kPushPieces - 1) / kPushPieces + 4095) / 4096 * 4096" in egress
     assert 'env_int("KICP_PRE_PUSH_WGS", 16)' in egress and "if (len < job.piece_bytes) break;" in egress

@@ -1,5 +1,5 @@
 """The published clouds as PointCloud2 `data` on the GPU (RosUtils.cpp:40-63 EigenToPointCloud2, LidarOdometryServer.cpp:240-263
-PublishClouds): the device map's records (kicp_mapdev.hpp k_pc_records), the frame's (kicp_pre_egress.hpp k_push_frame_f32) and the keypoints',
+PublishClouds): the device map's records (kicp_map_pc.hpp k_pc_records), the frame's (kicp_pre_egress.hpp k_push_frame_f32) and the keypoints',
 each compared bit for bit, as uint32 words, with static_cast<float> of the fp64 path's clouds."""
 import os
 import subprocess

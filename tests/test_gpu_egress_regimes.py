@@ -1,5 +1,5 @@
 """The clouds' way back to the host on the GPU (kicp_pre_egress.hpp k_push_frame / k_push_frame_f32 / k_narrow_f32, kicp_pre_egress.hip
-follow_pushed_pieces / egress_settle / kicp_pre_download_finish, kicp_mapdev.hpp k_pc_records, kicp_map.hip kicp_map_pointcloud_f32)
+follow_pushed_pieces / egress_settle / kicp_pre_download_finish, kicp_map_pc.hpp k_pc_records, kicp_map_cloud.hip kicp_map_pointcloud_f32)
 in the regimes tests/test_gpu_egress.py and tests/test_gpu_presteps_regimes.py never provably enter: frames that end on, just
 before and just behind a piece boundary, all eight pieces full, no survivor, one to four records, a piece longer than one sweep
 of the grid; one handle whose piece size shrinks and whose landing area grows, with stale flags behind it, an uncollected frame, a

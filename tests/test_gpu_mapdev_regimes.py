@@ -1,4 +1,4 @@
-"""VoxelHashMap::Update on the GPU (kicp_mapdev.hpp, map_update_device in kicp_map.hip) in the regimes the drive-through tests of
+"""VoxelHashMap::Update on the GPU (kicp_mapdev.hpp, map_update_device in kicp_map_update.hip) in the regimes the drive-through tests of
 tests/test_gpu_mapdev.py never enter: more than 8 192 touched voxels in the one-workgroup scan, the size edges of the one-queue
 path, buckets deeper than a wave, the acceptance and pruning radii met exactly, the "too tight" second claim, the free list emptied,
 refilled and handed between host and device.  Every test drives K.VoxelHashMap and the oracle(s) in lock step (mapdev_ref.Oracles);
@@ -7,6 +7,8 @@ downloaded host copy) and check() == 0; at the end GetClosestNeighbor bit for bi
 the device copy (accepted count exactly, sums to the 1e-10 of test_pass_sums_match_oracle) - the masks and the 16-bit mirror the
 pass kernels read.  Each test asserts from update_counts() that it took the path it is named after, so that a moved threshold fails
 here instead of silently uncovering the path.  The scenes' premises are proved on the CPU in tests/test_mapdev_scenes.py."""
+import ctypes as C
+
 import numpy as np
 import pytest
 
@@ -289,3 +291,34 @@ def test_device_updates_does_not_collect_a_pending_update():
     assert c["deferred"] == 1 and c["apply_wave"] == 2 and c["rehashes"] >= 1
     L.g.Clear()
     assert L.g.Empty() and L.counts() == c and L.g.device_updates() == before + 1
+
+
+# ---- the fp64 Pointcloud() collects a pending update ---------------------------------------------------------------------------------
+def test_pointcloud_between_begin_and_finish_equals_the_twins_cloud():
+    """Pointcloud() between UpdateDeviceBegin and UpdateFinish: the cloud of a twin map that took the same two frames through UpdateDevice,
+    bit for bit and in the same order (sc.ordered_frames: frames whose table order is settled), and by the counters the pending update
+    was collected and counted and the host map took nothing over.  This pins the answer, not the road to it: the fall-back through the
+    host copy, which answered before kicp_map_pointcloud collected a pending update itself, leaves the same cloud and counters."""
+    first, second = sc.ordered_frames()
+    maps = [K.VoxelHashMap(1.0, 1000.0, 20) for _ in range(2)]
+    for g in maps:
+        c0 = g.update_counts()
+        assert g.UpdateDevice(K.DeviceFrame(first), sc.IDENTITY)
+        rose(c0, g.update_counts(), staged=1, second_claims=1, rehashes=1, host_updates=0)  # (the table sc.ORDERED_SLOTS stands for)
+    pending, twin = maps
+    frame = K.DeviceFrame(second)
+    c0, before = pending.update_counts(), pending.device_updates()
+    pending.UpdateDeviceBegin(frame, sc.IDENTITY)
+    rose(c0, pending.update_counts(), deferred=1, one_queue=1)
+    assert pending.device_updates() == before == 1  # the update really is pending
+    # (K.VoxelHashMap.Pointcloud asks for num_points() first, which collects: kicp_map_pointcloud itself is called here)
+    cloud = np.empty((400, 3))
+    assert K.lib().kicp_map_pointcloud(pending._h, cloud.ctypes.data_as(C.POINTER(C.c_double)), 400) == 400
+    rose(c0, pending.update_counts(), deferred=1, host_updates=0)
+    assert pending.device_updates() == before + 1
+    assert twin.UpdateDevice(K.DeviceFrame(second), sc.IDENTITY)
+    want = twin.Pointcloud()
+    assert cloud.shape == want.shape == (400, 3) and np.array_equal(cloud, want)
+    assert np.array_equal(bucket_sorted(cloud, 1.0), bucket_sorted(np.concatenate([first, second]), 1.0))
+    assert pending.UpdateFinish() and pending.device_updates() == before + 1 and pending.update_counts()["host_updates"] == 0
+    assert pending.check() == 0 and twin.update_counts()["host_updates"] == 0

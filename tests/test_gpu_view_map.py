@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import kinematic_icp_amd as K
+import mapdev_scenes as sc
 import view_cases as vc
 import view_ref as vr
 from checkers import okicp
@@ -217,3 +218,23 @@ def test_update_sweep_update_sweep_and_a_rehash(wall):
     before = bucket_sorted(omap.Pointcloud(), vs)
     assert np.array_equal(bucket_sorted(gmap.Pointcloud(), vs), before)
     check_sweep(gmap, view, vc.WALL_CFG, wall["depth"], wall["c"], before, vs, cap, rng)
+
+
+def test_sweep_straight_after_an_update_that_rehashed_and_grew_the_pools(wall):
+    """the first device update into a fresh map (tests/test_gpu_mapdev_regimes.py's n = 8 192, region 0 scene) replaces the table, the key
+    array and both pools; the sweep that follows must see the new ones"""
+    vs, cap, max_distance = 1.0, 20, 150.0
+    s = sc.one_per_voxel(8192, 0, 1000)
+    t = sc.region_centre(0)
+    local, _ = sc.in_local_frame(s["points"], t)
+    gmap = K.VoxelHashMap(vs, max_distance, cap)
+    c0 = gmap.update_counts()
+    assert gmap.UpdateDevice(K.DeviceFrame(local), sc.translation(t))
+    c1 = gmap.update_counts()
+    assert (c1["rehashes"] - c0["rehashes"], c1["pool_growths"] - c0["pool_growths"], c1["one_queue"], c1["host_updates"]) == (1, 1, 1, 0)
+    omap = okicp.VoxelHashMap(vs, max_distance, cap)
+    omap.Update(local, sc.translation(t))
+    before = bucket_sorted(omap.Pointcloud(), vs)
+    assert len(before) == 8192 + 1000 == gmap.num_points()
+    _, _, stats = check_sweep(gmap, wall_view(wall), vc.WALL_CFG, wall["depth"], wall["c"], before, vs, cap, np.random.default_rng(7), max_distance)
+    assert stats[1] > 0 and stats[3] > 0 and gmap.update_counts()["host_updates"] == 0  # points left, voxels were erased, all on the device

@@ -179,6 +179,34 @@ def test_shallow_voxels_and_queries():
     np.testing.assert_array_equal(bucket_sorted(pts, 1.0), o.buckets())
 
 
+def test_ordered_frames_claim_distinct_slots():
+    """the premise of sc.ordered_frames: in both claim launches every new voxel takes a slot no other new voxel of the launch wants"""
+    first, second = [sc.voxel_keys(f, 1.0) for f in sc.ordered_frames()]
+    n1, n2 = len(first), len(second)
+    assert (n1, n2) == (100, 300) and len(np.unique(np.concatenate([first, second]), axis=0)) == n1 + n2
+    # the first frame: staged and too tight in the fresh table, so the table is re-hashed - empty - and claimed again
+    assert sc.too_tight_premise(n1) == (True, True, True)
+    want = 1024
+    while (0 + 32 * n1 + 1024) * 4 > want:
+        want *= 2
+    assert want == sc.ORDERED_SLOTS
+    filled = np.zeros(want, dtype=bool)
+    s1 = sc.slots_taken_alone(filled, first)
+    assert len(set(s1)) == n1
+    filled[s1] = True
+    # its apply step adds the 26 neighbours of every voxel (whatever their order: the SET of filled slots does not depend on it)
+    shifts = np.stack(np.meshgrid(*[np.arange(-1, 2)] * 3, indexing="ij"), -1).reshape(-1, 3)
+    halo = np.unique((first[:, None, :] + shifts[None]).reshape(-1, 3), axis=0)
+    halo = halo[~(halo[:, None, :] == first[None]).all(-1).any(1)]
+    for key in halo:
+        filled[sc.slots_taken_alone(filled, key[None])] = True
+    entries = int(filled.sum())
+    # the second frame: no re-hash, room for the worst case - one queue, which a begin leaves pending
+    assert (entries + n2) * 2 <= want and (entries + 27 * n2) * 4 <= 3 * want
+    assert not (second[:, None, :] == np.concatenate([first, halo])[None]).all(-1).any()  # every voxel of it is a new entry
+    assert len(set(sc.slots_taken_alone(filled, second))) == n2
+
+
 def test_update_counts_of_a_map_that_never_left_the_host():
     """kicp_map_update_counts / kicp_map_device_updates read host-side counters only: they work without a GPU, and host-side calls
     leave all twelve at zero"""
