@@ -768,6 +768,57 @@ int kicp_grid_has_plan(const kicp_grid *grid); /* 1 when the handle holds a vali
 int kicp_grid_score_arcs(const kicp_grid *grid, const double start[4], const double *arcs, size_t n_arcs, unsigned int n_steps, const double *footprint_xy,
                          size_t n_samples, unsigned int *out, size_t cap);
 
+/* ---- commands that change along a trajectory: a tree of arc segments scored on the plan (kicp_grid_arc_tree.hip) ---------------------
+ * An arc above repeats ONE step n_steps times, so a candidate's command never changes: a fan of arcs cannot turn and then go straight,
+ * round a corner or swerve and return.  A tree of segments can: every path from the root is a sequence of primitives, each held for
+ * its level's steps.  The B^D sequences of D segments share almost all of their prefixes, and the rollout below is exact and stated
+ * operation by operation, so a prefix is rolled once and continued: every node gets the bits a rollout of its whole path from `start`
+ * gives.  PLAN, START, FOOTPRINT, the recurrence and the collision rule are those of the section above.
+ *
+ * TREE.  depth = D, 1 <= D <= 8.  Level d = 1 .. D has branch[d - 1] = B_d >= 1 primitives and steps[d - 1] = L_d >= 1 steps.
+ * primitives holds (B_1 + ... + B_D) x 4 doubles, level 1's rows first, then level 2's, and so on; each row is one step
+ * (dx, dy, dc, ds), exactly an arc's row (kicp_arc_steps makes them).  Level d has n_d = B_1 * ... * B_d nodes; the tree has
+ * N = n_1 + ... + n_D nodes and its paths T = L_1 + ... + L_D steps.
+ *
+ * NUMBERING.  Nodes are level-major: level d occupies the rows off_d .. off_d + n_d - 1, off_1 = 0, off_{d+1} = off_d + n_d.  Inside
+ * a level, the child that takes primitive b under the parent with in-level index j has in-level index j * B_d + b; the path
+ * (b_1 .. b_d) of a node follows from its in-level index by repeated division.
+ *
+ * RESULT.  Four unsigned int per node, out[4 r .. 4 r + 3] for row r, with the meaning they have for an arc.  They describe ONE
+ * trajectory: from `start`, L_1 steps of level 1's primitive b_1, then L_2 steps of level 2's primitive b_2, and so on through the
+ * node's level d.  Every pose is checked with the footprint, the rollout ends at the first colliding pose, free_steps counts along
+ * the whole path (0 .. L_1 + ... + L_d), cost_sum and cost_max run over those free poses, end_potential is read at the last free pose.
+ * A node whose parent ended early therefore has its parent's four words.  A tree with D = 1 gives word for word what
+ * kicp_grid_score_arcs gives for arcs = primitives, n_steps = L_1.  Values that are not finite in primitives or footprint_xy are
+ * legal and collide.
+ *
+ * LIMITS.  D <= 8, N <= 2^20, T <= 1024 (which keeps cost_sum's bound), n_samples <= 4096: above is KICP_ERR_CAPACITY with the limit in
+ * the message.  D = 0, a zero in branch or steps, n_samples = 0, a start that is not finite or a null pointer: KICP_ERR_ARG.  cap must
+ * be 4 * N (KICP_ERR_ARG).
+ *
+ * ENTRIES.  kicp_grid_score_arc_tree scores on the handle's plan where it lies in HBM - one launch per level, a wave per node, each
+ * level continuing the records the level above left on the device - and returns after the N x 4 words have arrived; without a valid
+ * plan it is KICP_ERR_ARG, as kicp_grid_score_arcs.  kicp_score_arc_tree_from_plan is the same arithmetic as pure host code over the
+ * caller's arrays (q, potential, cell, origin_x, origin_y, width, height as kicp_score_arcs_from_plan takes them) and needs no GPU.
+ *
+ * kicp_arc_tree_nodes performs the checks on depth, branch and steps and returns the counts (pure host code): *out_n_nodes = N,
+ * *out_n_leaves = n_D, *out_total_steps = T, and out_level_offset[d - 1] = off_d for the D levels when it is not NULL (the only
+ * pointer that may be).  Callers size `out` with it.  On an error the three counts are 0.
+ *
+ * kicp_arc_tree_best ranks the LEAVES (level D) only, from the N x 4 results as the scoring entries write them (pure host code).
+ * Admissibility and score are those of kicp_arcs_best with n_steps = T, ties go to the lowest in-level index.  *out_leaf is the
+ * leaf's in-level index, or n_D when no leaf is admissible (0 on an error); out_path[e - 1] = b_e for e = 1 .. D is filled when a leaf
+ * was found - out_path[0] is the command to execute now. */
+int kicp_arc_tree_nodes(unsigned int depth, const unsigned int *branch, const unsigned int *steps, size_t *out_n_nodes, size_t *out_n_leaves,
+                        unsigned int *out_total_steps, size_t *out_level_offset /* depth, nullable */);
+int kicp_arc_tree_best(const unsigned int *results /* N x 4 */, unsigned int depth, const unsigned int *branch, const unsigned int *steps, unsigned int w_potential,
+                       unsigned int w_cost, unsigned int w_blocked, unsigned int min_free_steps, size_t *out_leaf, unsigned int *out_path /* depth */);
+int kicp_score_arc_tree_from_plan(const unsigned char *q, const unsigned int *potential, double cell, double origin_x, double origin_y, unsigned int width,
+                                  unsigned int height, const double start[4], unsigned int depth, const unsigned int *branch, const unsigned int *steps,
+                                  const double *primitives, const double *footprint_xy, size_t n_samples, unsigned int *out, size_t cap);
+int kicp_grid_score_arc_tree(const kicp_grid *grid, const double start[4], unsigned int depth, const unsigned int *branch, const unsigned int *steps,
+                             const double *primitives, const double *footprint_xy, size_t n_samples, unsigned int *out, size_t cap);
+
 /* ---- where to go while mapping: the exploration frontiers of the grid, ranked by the plan (kicp_grid_explore.hip) ----------------------
  * A robot that is still mapping has no goal from outside: its goal is the edge of what it has seen.  These entries find the free cells
  * that border unknown space, group them into frontiers and sum ten words per frontier - what explore_lite or a Nav2 exploration node

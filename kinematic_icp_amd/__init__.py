@@ -254,6 +254,13 @@ _SIGNATURES = {
                                             _dp, C.c_size_t, C.POINTER(C.c_uint), C.c_size_t]),
     "kicp_grid_has_plan": (C.c_int, [C.c_void_p]),
     "kicp_grid_score_arcs": (C.c_int, [C.c_void_p, _dp, _dp, C.c_size_t, C.c_uint, _dp, C.c_size_t, C.POINTER(C.c_uint), C.c_size_t]),
+    "kicp_arc_tree_nodes": (C.c_int, [C.c_uint, C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.POINTER(C.c_uint),
+                                      C.POINTER(C.c_size_t)]),
+    "kicp_arc_tree_best": (C.c_int, [C.POINTER(C.c_uint), C.c_uint, C.POINTER(C.c_uint), C.POINTER(C.c_uint), C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.POINTER(C.c_size_t),
+                                     C.POINTER(C.c_uint)]),
+    "kicp_score_arc_tree_from_plan": (C.c_int, [C.POINTER(C.c_ubyte), C.POINTER(C.c_uint), C.c_double, C.c_double, C.c_double, C.c_uint, C.c_uint, _dp, C.c_uint,
+                                                C.POINTER(C.c_uint), C.POINTER(C.c_uint), _dp, _dp, C.c_size_t, C.POINTER(C.c_uint), C.c_size_t]),
+    "kicp_grid_score_arc_tree": (C.c_int, [C.c_void_p, _dp, C.c_uint, C.POINTER(C.c_uint), C.POINTER(C.c_uint), _dp, _dp, C.c_size_t, C.POINTER(C.c_uint), C.c_size_t]),
     "kicp_frontiers_from_occupancy": (C.c_int, [C.POINTER(C.c_byte), C.c_uint, C.c_uint, C.POINTER(FrontierConfig), C.POINTER(C.c_uint), C.POINTER(C.c_ulonglong), C.c_size_t,
                                                 C.POINTER(C.c_size_t), C.POINTER(C.c_uint), C.c_size_t]),
     "kicp_grid_frontiers": (C.c_int, [C.c_void_p, C.POINTER(FrontierConfig), C.c_int, C.POINTER(C.c_ulonglong), C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_uint),
@@ -785,6 +792,82 @@ def arcs_best(results, n_steps, w_potential=1, w_cost=0, w_blocked=0, min_free_s
     return None if index.value == len(r) else int(index.value)
 
 
+ARC_TREE_MAX_DEPTH, ARC_TREE_MAX_NODES, ARC_TREE_MAX_T = 8, 1 << 20, 1024
+
+
+def _arc_tree_levels(branch, steps):
+    """-> (branch, steps) as uint32 arrays with one entry per level; what the library cannot be handed is refused here"""
+    b, s = np.asarray(branch).reshape(-1), np.asarray(steps).reshape(-1)
+    if b.size != s.size:
+        raise KicpError(KICP_ERR_ARG, "branch and steps must have the same length: one entry per level")
+    for a in (b, s):
+        if a.size and (a.dtype.kind not in "iu" or int(a.min()) < 0 or int(a.max()) > 0xFFFFFFFF):
+            raise KicpError(KICP_ERR_ARG, "branch and steps hold unsigned 32-bit integers, at least 1")
+    return np.ascontiguousarray(b, dtype=np.uint32), np.ascontiguousarray(s, dtype=np.uint32)
+
+
+def arc_tree_nodes(branch, steps):
+    """kicp_arc_tree_nodes: the counts of the tree with branch[d] primitives and steps[d] steps at level d + 1 ->
+    (n_nodes, n_leaves, total_steps, level_offset): the rows of all levels, the nodes of the last one, the steps along a path and the row
+    each level begins at.  Raises on a tree the scoring entries refuse (depth above 8, more than 2^20 nodes, more than 1 024 steps along
+    a path: KICP_ERR_CAPACITY; no level, a zero: KICP_ERR_ARG).  Pure host code."""
+    b, s = _arc_tree_levels(branch, steps)
+    n_nodes, n_leaves, total = C.c_size_t(), C.c_size_t(), C.c_uint()
+    offsets = (C.c_size_t * max(b.size, 1))()
+    _check(lib().kicp_arc_tree_nodes(b.size, _u32(b), _u32(s), C.byref(n_nodes), C.byref(n_leaves), C.byref(total), offsets))
+    return int(n_nodes.value), int(n_leaves.value), int(total.value), tuple(int(v) for v in offsets[:b.size])
+
+
+def _arc_tree_args(start, branch, steps, primitives, footprint):
+    """-> (start [4], branch [D], steps [D], primitives (sum of branch, 4), footprint (P, 2), n_nodes)"""
+    b, st = _arc_tree_levels(branch, steps)
+    n_nodes = arc_tree_nodes(b, st)[0]
+    s = np.ascontiguousarray(start, dtype=np.float64).reshape(-1)
+    p, f = np.ascontiguousarray(primitives, dtype=np.float64), np.ascontiguousarray(footprint, dtype=np.float64)
+    if s.size != 4:
+        raise KicpError(KICP_ERR_ARG, "the start must be (x, y, cosine, sine)")
+    if p.ndim != 2 or p.shape != (int(b.sum(dtype=np.uint64)), 4):
+        raise KicpError(KICP_ERR_ARG, "the primitives must be shaped (sum of branch, 4) = (%d, 4): dx, dy, dc, ds, level 1's rows first" % int(b.sum(dtype=np.uint64)))
+    if f.ndim != 2 or f.shape[1] != 2:
+        raise KicpError(KICP_ERR_ARG, "the footprint must be shaped (P, 2)")
+    return s, b, st, p, f, n_nodes
+
+
+def score_arc_tree_from_plan(q, potential, cell, origin_x, origin_y, start, branch, steps, primitives, footprint, out=None):
+    """kicp_score_arc_tree_from_plan: a tree of arc segments on the plan score_arcs_from_plan takes.  Level d + 1 has branch[d]
+    primitives - rows (dx, dy, dc, ds) of `primitives`, level 1's first - each held for steps[d] steps; a node's trajectory runs from
+    `start` through the primitives of its path -> uint32 (N, 4), the rows level-major (arc_tree_nodes gives N and where each level
+    begins; the child with primitive b of the node j of a level is the node j * branch + b of the next): free_steps along the whole
+    path, cost_sum, cost_max, end_potential.  A node under one that collided repeats its four words.  out: a uint32 (N, 4) array to
+    write into.  Pure host code: needs no GPU."""
+    qa, pot = np.ascontiguousarray(q, dtype=np.uint8), np.ascontiguousarray(potential, dtype=np.uint32)
+    if qa.ndim != 2 or qa.size == 0 or pot.shape != qa.shape:
+        raise KicpError(KICP_ERR_ARG, "q and the potential must be shaped (height, width), both at least 1")
+    s, b, st, p, f, n_nodes = _arc_tree_args(start, branch, steps, primitives, footprint)
+    out = _out_array(out, (n_nodes, 4), np.uint32, "(N, 4) = (%d, 4)" % n_nodes)
+    _check(lib().kicp_score_arc_tree_from_plan(_u8(qa), _u32(pot), float(cell), float(origin_x), float(origin_y), qa.shape[1], qa.shape[0], C.cast(s.ctypes.data, _dp),
+                                               b.size, _u32(b), _u32(st), C.cast(p.ctypes.data, _dp), C.cast(f.ctypes.data, _dp), len(f), _u32(out), out.size))
+    return out
+
+
+def arc_tree_best(results, branch, steps, w_potential=1, w_cost=0, w_blocked=0, min_free_steps=1):
+    """kicp_arc_tree_best: among the LEAVES of a scored tree (results: uint32 (N, 4) as the scoring entries write them) the admissible
+    one of least score, by arcs_best's rule with n_steps = the steps along a path, the lowest in-level index on a tie ->
+    (leaf, path): the leaf's in-level index and the primitive its path takes at every level - path[0] is the command to execute
+    now; None when no leaf is admissible.  Pure host code."""
+    b, st = _arc_tree_levels(branch, steps)
+    n_nodes, n_leaves = arc_tree_nodes(b, st)[:2]
+    r = np.ascontiguousarray(results, dtype=np.uint32)
+    if r.shape != (n_nodes, 4):
+        raise KicpError(KICP_ERR_ARG, "the results must be shaped (N, 4) = (%d, 4)" % n_nodes)
+    args = [int(v) for v in (w_potential, w_cost, w_blocked, min_free_steps)]
+    if min(args) < 0 or max(args) > 0xFFFFFFFF:
+        raise KicpError(KICP_ERR_ARG, "the weights and min_free_steps are unsigned 32-bit integers")
+    leaf, path = C.c_size_t(), np.zeros(b.size, dtype=np.uint32)
+    _check(lib().kicp_arc_tree_best(_u32(r), b.size, _u32(b), _u32(st), *args, C.byref(leaf), _u32(path)))
+    return None if leaf.value == n_leaves else (int(leaf.value), tuple(int(v) for v in path))
+
+
 FRONTIER_WORDS = 10
 
 
@@ -1122,6 +1205,16 @@ class OccupancyGrid:
         out = _out_array(out, (len(a), 4), np.uint32, "(K, 4)")
         _check(lib().kicp_grid_score_arcs(self._h, C.cast(s.ctypes.data, _dp), C.cast(a.ctypes.data, _dp), len(a), n_steps, C.cast(f.ctypes.data, _dp), len(f), _u32(out),
                                           out.size))
+        return out
+
+    def score_arc_tree(self, start, branch, steps, primitives, footprint, out=None):
+        """kicp_grid_score_arc_tree: on the GPU, score_arc_tree_from_plan's result on the plan the last potential() or
+        potential_of_costmap() left in the handle (KICP_ERR_ARG when there is none) -> uint32 (N, 4), one launch per level; the plan
+        never leaves HBM.  out: as score_arc_tree_from_plan's."""
+        s, b, st, p, f, n_nodes = _arc_tree_args(start, branch, steps, primitives, footprint)
+        out = _out_array(out, (n_nodes, 4), np.uint32, "(N, 4) = (%d, 4)" % n_nodes)
+        _check(lib().kicp_grid_score_arc_tree(self._h, C.cast(s.ctypes.data, _dp), b.size, _u32(b), _u32(st), C.cast(p.ctypes.data, _dp), C.cast(f.ctypes.data, _dp), len(f),
+                                              _u32(out), out.size))
         return out
 
     def frontiers(self, min_observations=1, occupied_thresh=0.65, min_size=1, use_plan=False, return_labels=False):

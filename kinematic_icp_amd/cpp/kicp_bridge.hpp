@@ -177,6 +177,49 @@ inline size_t best_arc(const std::vector<ArcResult> &results, unsigned int n_ste
           "kicp_bridge::best_arc");
     return index;
 }
+// ArcTree, ArcTreeCounts, ArcTreeLeaf, arc_tree_nodes and best_arc_tree_leaf go with KinematicICP::ScoreArcTree (kicp.h
+// kicp_arc_tree_nodes .. kicp_grid_score_arc_tree): a tree of arc segments - level d + 1 offers branch[d] primitives, each held for
+// steps[d] steps; primitives holds the levels' rows one after the other, level 1's first - the counts that size its results, and the
+// leaf a ranking picks with the primitive its path takes at every level (path[0] is the command to execute now).
+struct ArcTree {
+    std::vector<unsigned int> branch, steps;
+    std::vector<ArcStep> primitives;
+};
+struct ArcTreeCounts {
+    size_t n_nodes = 0, n_leaves = 0;
+    unsigned int total_steps = 0;
+    std::vector<size_t> level_offset;  // the row each level's nodes begin at
+};
+struct ArcTreeLeaf {
+    bool found = false;
+    size_t leaf = 0;  // the in-level index at the last level; n_leaves when none is admissible
+    std::vector<unsigned int> path;
+};
+inline ArcTreeCounts arc_tree_nodes(const ArcTree &tree) {
+    if (tree.branch.size() != tree.steps.size()) throw std::runtime_error("kicp_bridge::arc_tree_nodes: branch and steps must have the same length");
+    ArcTreeCounts counts;
+    counts.level_offset.resize(tree.branch.size());
+    check(kicp_arc_tree_nodes(static_cast<unsigned int>(tree.branch.size()), tree.branch.data(), tree.steps.data(), &counts.n_nodes, &counts.n_leaves, &counts.total_steps,
+                              counts.level_offset.data()),
+          "kicp_bridge::arc_tree_nodes");
+    size_t rows = 0;
+    for (unsigned int b : tree.branch) rows += b;
+    if (tree.primitives.size() != rows) throw std::runtime_error("kicp_bridge::arc_tree_nodes: the tree needs " + std::to_string(rows) + " primitives, one row per entry of branch");
+    return counts;
+}
+inline ArcTreeLeaf best_arc_tree_leaf(const std::vector<ArcResult> &results, const ArcTree &tree, unsigned int w_potential = 1, unsigned int w_cost = 0,
+                                      unsigned int w_blocked = 0, unsigned int min_free_steps = 1) {
+    const ArcTreeCounts counts = arc_tree_nodes(tree);
+    if (results.size() != counts.n_nodes) throw std::runtime_error("kicp_bridge::best_arc_tree_leaf: the tree has " + std::to_string(counts.n_nodes) + " nodes, one result each");
+    ArcTreeLeaf best;
+    best.path.resize(tree.branch.size());
+    check(kicp_arc_tree_best(results.front().data(), static_cast<unsigned int>(tree.branch.size()), tree.branch.data(), tree.steps.data(), w_potential, w_cost, w_blocked,
+                             min_free_steps, &best.leaf, best.path.data()),
+          "kicp_bridge::best_arc_tree_leaf");
+    best.found = best.leaf < counts.n_leaves;
+    if (!best.found) best.path.clear();
+    return best;
+}
 // FrontierConfig and Frontier go with KinematicICP::GridFrontiers (kicp.h kicp_grid_frontiers): the classes' thresholds and the least
 // size of a frontier that is output, and one frontier - the ten words of its row by name.  The centroid is in cells, as doubles: the
 // middle of cell (x, y) lies at origin + (x + 0.5, y + 0.5) * cell in the world.

@@ -415,6 +415,33 @@ public:
                    unsigned int min_free_steps = 1) const {
         return kicp_bridge::best_arc(results, n_steps, w_potential, w_cost, w_blocked, min_free_steps);
     }
+    // Commands that change along a trajectory (kicp.h kicp_arc_tree_nodes .. kicp_grid_score_arc_tree): a tree of arc segments on the
+    // same plan.  Level d + 1 of `tree` offers branch[d] primitives (rows as ArcSteps makes them, level 1's first), each held for
+    // steps[d] steps; a node's trajectory runs from `start` through the primitives of its path, and shared prefixes are rolled once on
+    // the GPU, one launch per level.  results: one ArcResult per node, level by level (kicp_bridge::arc_tree_nodes gives the counts and
+    // the row each level begins at); the child that takes primitive b under node j of a level is node j * branch + b of the next;
+    // free_steps counts along the whole path, and a node under one that collided repeats its result.  Throws without a grid and
+    // without a plan ("call GridPotential first").  BestArcTreeLeaf ranks the leaves by BestArc's rule with n_steps = the steps along
+    // a path: found, the leaf's index in the last level and its path - path[0] is the command to execute now.
+    void ScoreArcTree(std::vector<kicp_bridge::ArcResult> &results, const kicp_bridge::ArcStart &start, const kicp_bridge::ArcTree &tree,
+                      const std::vector<kicp_bridge::FootprintSample> &footprint) const {
+        const kicp_grid *grid = RequireGrid("ScoreArcTree");
+        if (!kicp_grid_has_plan(grid)) throw std::runtime_error("KinematicICP::ScoreArcTree: call GridPotential first (or GridPotentialOfCostmap): the grid holds no plan");
+        results.resize(kicp_bridge::arc_tree_nodes(tree).n_nodes);
+        kicp_bridge::check(kicp_grid_score_arc_tree(grid, start.data(), static_cast<unsigned int>(tree.branch.size()), tree.branch.data(), tree.steps.data(),
+                                                    tree.primitives.front().data(), footprint.empty() ? nullptr : footprint.front().data(), footprint.size(),
+                                                    results.front().data(), 4 * results.size()),
+                           "ScoreArcTree");
+    }
+    // the same from a pose - pose() for the robot as it stands
+    void ScoreArcTree(std::vector<kicp_bridge::ArcResult> &results, const Sophus::SE3d &pose, const kicp_bridge::ArcTree &tree,
+                      const std::vector<kicp_bridge::FootprintSample> &footprint) const {
+        ScoreArcTree(results, kicp_bridge::arc_start(pose), tree, footprint);
+    }
+    kicp_bridge::ArcTreeLeaf BestArcTreeLeaf(const std::vector<kicp_bridge::ArcResult> &results, const kicp_bridge::ArcTree &tree, unsigned int w_potential = 1,
+                                             unsigned int w_cost = 0, unsigned int w_blocked = 0, unsigned int min_free_steps = 1) const {
+        return kicp_bridge::best_arc_tree_leaf(results, tree, w_potential, w_cost, w_blocked, min_free_steps);
+    }
     // Where to go while mapping (kicp.h kicp_grid_frontiers): the frontiers of the grid as it stands - the clear cells with an unknown
     // edge neighbour, joined over their eight neighbours - found on the GPU from the counters, those of at least config.min_size cells
     // in ascending label order.  With use_plan, best_potential and best_cell come from the plan the last GridPotential or

@@ -8,18 +8,23 @@
 //                          kicp_grid_has_plan - one file because kicp_grid_potential queues the costmap's launches in front of the field's
 //   kicp_grid_arcs.hip     a fan of arcs scored on the plan (kicp_arcs.hpp): kicp_grid_score_arcs, its host twin, kicp_arc_steps,
 //                          kicp_footprint_box, kicp_arcs_best
+//   kicp_grid_arc_tree.hip a tree of arc segments scored on the plan (kicp_arc_tree.hpp): kicp_grid_score_arc_tree, its host twin,
+//                          kicp_arc_tree_nodes, kicp_arc_tree_best
 //   kicp_grid_explore.hip  where to go while mapping (kicp_front.hpp, kicp_gain.hpp): the frontiers and the viewpoints' gain, each
 //                          with its host twin
 #pragma once
 #include "kicp_clear_host.hpp"
 #include "kicp_internal.hpp"
 
-// (an internal header of four translation units that all begin this way)
+// (an internal header of five translation units that all begin this way)
 using namespace kicp;
 using namespace kicp::host;
+namespace kicp {
+struct ArcTreeNode;  // kicp_arc_tree_host.hpp: the handle only holds a buffer of them
+}
 
 // CONST ENTRIES.  The C-ABI takes `const kicp_grid *` wherever a call leaves the map as it was: info, counts, occupancy, clearance,
-// costmap, the two potential entries, has_plan, score_arcs, frontiers, gain, last_window, save_map.  Such an entry reads the top-level
+// costmap, the two potential entries, has_plan, score_arcs, score_arc_tree, frontiers, gain, last_window, save_map.  Such an entry reads the top-level
 // members - the counters among them - and writes only the groups declared `mutable` below: scratch whose contents no later call
 // relies on, but for the plan, which is the one thing a const entry leaves behind on purpose.
 //
@@ -58,7 +63,7 @@ struct kicp_grid {
         DevBuf<uint16_t> d_clearance;
     } clear;
     // kicp_grid_potential*.  THE PLAN is d_q (= weight[costmap]) and d_pot as the last potential call left them, and `valid` says
-    // that it succeeded: what kicp_grid_score_arcs and kicp_grid_frontiers(use_plan) read.  The costmap is not part of it.  Beside
+    // that it succeeded: what kicp_grid_score_arcs, kicp_grid_score_arc_tree and kicp_grid_frontiers(use_plan) read.  The costmap is not part of it.  Beside
     // it the call's scratch: the weight table, the goal list, the tiles' activity flags (two planes) and the counters - raised flags
     // of each round of a batch, then the cells below and at max_potential.
     mutable struct {
@@ -73,6 +78,14 @@ struct kicp_grid {
         DevBuf<uint32_t> d_out;
         PinnedBuf<uint32_t> h_out;
     } arcs;
+    // kicp_grid_score_arc_tree: its uploads, the records of two levels (each level's nodes read the half the level above wrote), the
+    // rows of all levels and the pinned buffer they come back through
+    mutable struct {
+        DevBuf<double> d_primitives, d_footprint;
+        DevBuf<ArcTreeNode> d_records;
+        DevBuf<uint32_t> d_out;
+        PinnedBuf<uint32_t> h_out;
+    } arc_tree;
     // kicp_grid_frontiers: a byte per cell, the parent plane that becomes the label plane, the roots' row numbers, the count of
     // roots, the rows and where they and the count land
     mutable struct {
