@@ -31,7 +31,9 @@ def test_library_contains_gfx950_code_and_no_oracle():
     out = subprocess.run(["strings", "-n", "6", K.LIB_PATH], capture_output=True, text=True).stdout
     assert "gfx950" in out
     assert "okicp_" not in out  # the product never links the oracle
-    src = "".join(open(os.path.join(ROOT, "kinematic_icp_amd", f)).read() for f in ("__init__.py", "synthetic.py"))
+    package = sorted(f for f in os.listdir(os.path.join(ROOT, "kinematic_icp_amd")) if f.endswith(".py"))
+    assert {"__init__.py", "_ffi.py", "registration.py", "synthetic.py"} <= set(package)
+    src = "".join(open(os.path.join(ROOT, "kinematic_icp_amd", f)).read() for f in package)
     assert "oracle" not in src.replace("the oracle", "").replace("oracle's", "") or "import oracle" not in src
     for f in (x for x in os.listdir(os.path.join(ROOT, "kinematic_icp_amd", "csrc")) if x.endswith((".hpp", ".hip", "Makefile"))):
         assert "oracle/" not in open(os.path.join(ROOT, "kinematic_icp_amd", "csrc", f)).read()
