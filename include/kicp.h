@@ -939,6 +939,83 @@ int kicp_gain_from_occupancy(const signed char *occupancy, unsigned int width, u
                              size_t n_views, unsigned int *out /* n_views x 4 */, size_t cap_out);
 int kicp_grid_gain(const kicp_grid *grid, const kicp_gain_config *config, const unsigned int *views, size_t n_views, unsigned int *out, size_t cap_out);
 
+/* ---- what stands in known free space right now: the transient obstacles of one frame (kicp_grid_transient.hip) --------------------------
+ * A cell the rays have crossed m times becomes a source of the clearance only after more than (occupied_thresh / (1 - occupied_thresh)) m
+ * hits: somebody who steps into a corridor that was carved 200 times is lethal in the costmap half a minute later.  Nav2 closes that gap
+ * with an obstacle layer fed by the current observation; these entries are its counterpart.  DETECTION finds the returns of one frame that
+ * end in cells the counters know as free and groups them into transients, one row of integers each.  THE SWITCH makes those cells sources
+ * of the clearance, the costmap and the potential.  Everything below is integer from the floor on and the result is unique: the host
+ * and the device entries return equal arrays.
+ *
+ * USED POINT, ENDPOINT CELL, SENSOR CELL (sx, sy).  Exactly kicp_grid_integrate's: the same arithmetic, the same z band, the same reach
+ * test.  The sensor cell may lie outside the grid.  n(c) is the number of used points whose endpoint cell is c, for c inside the grid;
+ * endpoints outside the grid count nowhere.  n == 0 is legal; n > 0x7FFFFFF0 / 3 is KICP_ERR_CAPACITY, as for kicp_grid_integrate.
+ *
+ * TRANSIENT CELL.  With v the readout of the cell's counters as they stand at the call, at `min_observations`: cell c is a transient cell
+ * when n(c) >= min_points and 0 <= v <= free_max.  An unknown cell (v < 0) never is one.  The call reads the counters and never writes
+ * them; call it BEFORE integrating the same frame, so that the frame's own hit is not part of v yet.
+ *
+ * TRANSIENT.  Transient cells are joined to each of their eight neighbours that is a transient cell, with no corner rule.  A transient
+ * is a connected component; its label is the least cell index y * width + x among its cells.  The label plane is width * height words
+ * of unsigned int: the label on a transient cell, 0xFFFFFFFF on every other, and is NOT filtered by min_size.
+ *
+ * ROW.  Per transient KICP_TRANSIENT_WORDS = 10 words of unsigned long long:
+ *   0           the label
+ *   1           the size in cells
+ *   2           the returns: the sum of n(c) over its cells
+ *   3, 4        the sums of n(c) * x and n(c) * y (the centroid is the caller's division by word 2: none enters the contract)
+ *   5, 6, 7, 8  min x, max x, min y, max y
+ *   9           nearest: the least key d2(c) * 2^32 + c over its cells, d2(c) = (x - sx)^2 + (y - sy)^2
+ * The reach test keeps |x - sx| and |y - sy| at or below 4095, so d2 < 2^25: the high half of word 9 is the squared distance in cells
+ * from the sensor to the transient's nearest cell, the low half that cell - among equally near cells the least index.
+ *
+ * OUTPUT.  The rows with size >= min_size, in ascending label order.  *out_n, cap_rows, KICP_ERR_CAPACITY, out_labels and cap_labels
+ * behave exactly as in kicp_grid_frontiers.  out_stats is nullable, four words: the points used, the used points whose endpoint cell
+ * lies inside the grid, the cells with n(c) > 0, and the transient cells before min_size.
+ *
+ * THE TRANSIENT PLANE.  The handle keeps a byte per cell: 1 on the cells of the transients of the last call that passed min_size.  It is
+ * all 0 before the first call, after kicp_grid_clear, and after a call with n == 0 or without any transient.  Every call replaces it
+ * completely: nothing of the previous frame stays.  A call that returns KICP_ERR_CAPACITY for its rows has still replaced the plane; a
+ * call that fails its argument checks leaves it as it was.  kicp_grid_transient_plane downloads it (cap_cells must be width * height).
+ *
+ * THE SWITCH.  kicp_grid_use_transients sets it, kicp_grid_uses_transients reads it; it is off at creation and kicp_grid_clear does not
+ * change it.  While it is on, a cell whose plane byte is 1 is a SOURCE in kicp_grid_clearance, kicp_grid_costmap and kicp_grid_potential
+ * whatever its counters say, and its base cost is 254.  Nothing else in those contracts changes: the result for a rectangle still
+ * equals the full grid's restricted to it, and for occupied_thresh < 1 it equals what the kicp_grid_*_from_occupancy entries return over
+ * the readout with those cells set to 100.  Occupancy, save_map and counts, kicp_grid_fill_unknown, kicp_grid_potential_of_costmap,
+ * kicp_grid_frontiers and kicp_grid_gain ignore the plane whatever the switch says: a person is not a wall and must not open or close a
+ * frontier.  A plan is a snapshot as before: it holds the transients of the moment kicp_grid_potential ran, and a later
+ * kicp_grid_transients neither changes nor invalidates it.  What a node has to refresh after a frame is the union of the last two
+ * frames' windows grown by R: the old plane's cells lay in the previous window.
+ *
+ * ENTRIES.  kicp_grid_transients takes the frame from host memory, kicp_grid_transients_device from HBM (the registered frame of the
+ * pre-steps, say).  Both take the handle non-const because the plane is state they leave behind on purpose; they change no counter, not
+ * the frame count, not the last window and not the plan, and return with the stream drained.  kicp_transients_from_counts is pure host
+ * code over counters in kicp_grid_counts' layout and the grid's configuration (checked as kicp_grid_create checks it) and needs no GPU;
+ * out_plane is nullable: cap_plane must be width * height with a plane and 0 without one.
+ * A null handle / counts / configuration, pose, sensor, config or out_n, null points with n > 0, min_observations < 1, free_max > 100,
+ * min_points < 1, min_size < 1 and a bad cap_labels or cap_plane are KICP_ERR_ARG; *out_n is 0 after any of them. */
+typedef struct kicp_transient_config {
+    unsigned int min_observations; /* >= 1 */
+    unsigned int free_max;         /* 0 .. 100: known free is 0 <= v <= free_max; floor(occupied_thresh * 100) leaves no gap below the sources */
+    unsigned int min_points;       /* >= 1: returns a cell needs */
+    unsigned int min_size;         /* >= 1: cells a transient needs to be output and to enter the plane */
+} kicp_transient_config;
+#define KICP_TRANSIENT_WORDS 10
+int kicp_grid_transients(kicp_grid *grid, const double *frame_xyz, size_t n, const double pose_qt[7], const double sensor_xyz[3],
+                         const kicp_transient_config *config, unsigned long long *out_rows, size_t cap_rows, size_t *out_n, unsigned int *out_labels,
+                         size_t cap_labels, unsigned long long out_stats[4]);
+int kicp_grid_transients_device(kicp_grid *grid, const double *d_frame_xyz, size_t n, const double pose_qt[7], const double sensor_xyz[3],
+                                const kicp_transient_config *config, unsigned long long *out_rows, size_t cap_rows, size_t *out_n,
+                                unsigned int *out_labels, size_t cap_labels, unsigned long long out_stats[4]);
+int kicp_transients_from_counts(const unsigned short *counts, const kicp_grid_config *grid_config, const double *frame_xyz, size_t n, const double pose_qt[7],
+                                const double sensor_xyz[3], const kicp_transient_config *config, unsigned long long *out_rows, size_t cap_rows,
+                                size_t *out_n, unsigned int *out_labels, size_t cap_labels, unsigned long long out_stats[4], unsigned char *out_plane,
+                                size_t cap_plane /* 0 or width * height */);
+int kicp_grid_transient_plane(const kicp_grid *grid, unsigned char *out, size_t cap_cells);
+int kicp_grid_use_transients(kicp_grid *grid, int on);
+int kicp_grid_uses_transients(const kicp_grid *grid);
+
 /* ---- uneven ground: a column of heights per cell, and traversability by height over the local ground (kicp_elev.hip) -----------------
  * The grid above calls a return an obstacle when its BASE-FRAME z lies in a fixed band.  Where the floor is not one plane that is
  * wrong: a ramp ahead rises into the band and becomes a wall, a kerb or a drop below the band is invisible, a ceiling or a table top is

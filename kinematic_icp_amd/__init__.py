@@ -16,7 +16,7 @@ The binding is one module per feature, cut as the C side's files are (DESIGN.md 
 Every feature module is imported below, so the signature table is complete before lib() can first be called.  The loaded library
 itself is `_ffi._lib` and is not re-exported: a copy made at import would stay None.
 """
-from . import _ffi, device, elevation, explore, grid, plan, presteps, registration, search, view, voxel_map  # noqa: F401
+from . import _ffi, device, elevation, explore, grid, plan, presteps, registration, search, transients, view, voxel_map  # noqa: F401
 from ._ffi import (KICP_ERR_ARG, KICP_ERR_CAPACITY, KICP_ERR_COMM, KICP_ERR_HIP, KICP_ERR_INTERNAL, KICP_OK, KICP_WARN_NO_CORRESPONDENCES,  # noqa: F401
                    KICP_WARN_TABLE_ORDER, LIB_PATH, KicpError, lib)
 from ._ffi import (_HERE, _PTR_CACHE, _SIGNATURES, _check, _d, _dp, _occupancy_2d, _out_array, _pose_ptr, _rect, _u8, _u32)  # noqa: F401
@@ -37,5 +37,7 @@ from .plan import _arc_tree_args, _arc_tree_levels, _arcs_args, _plan_args, _pot
 from .presteps import FIELD_FLOAT32, FIELD_FLOAT64, FIELD_UINT32, CloudLayout, LaserScan, PreSteps  # noqa: F401
 from .registration import MAX_LOG_PASSES, P2P_HANDLE_BYTES, KinematicRegistration, RegConfig, Stats, _Batch, planar_grid, planar_step  # noqa: F401
 from .search import OccupancyPyramid, SearchWindow, search_window_around, search_yaws  # noqa: F401
+from .transients import TRANSIENT_WORDS, TransientConfig, transients_from_counts  # noqa: F401
+from .transients import _transient_call, _transient_config  # noqa: F401
 from .view import DepthView, ViewConfig  # noqa: F401
 from .voxel_map import VoxelHashMap  # noqa: F401

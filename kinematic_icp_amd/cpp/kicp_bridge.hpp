@@ -239,6 +239,26 @@ inline Frontier frontier_of_row(const unsigned long long *row) {
     f.best_potential = static_cast<uint32_t>(row[8]), f.best_cell = static_cast<uint32_t>(row[9]);
     return f;
 }
+// TransientConfig and Transient go with KinematicICP::EnableTransients and ::Transients (kicp.h kicp_grid_transients): what makes a cell
+// of known free space a transient cell and the least size of a transient that counts, and one transient - the ten words of its row by
+// name.  The centroid is weighted by the returns, in cells, as doubles; nearest_d2 is the squared distance in cells from the sensor's
+// cell to nearest_cell, the transient's cell closest to it.
+using TransientConfig = kicp_transient_config;
+struct Transient {
+    uint32_t label = 0;  // the least cell index y * width + x of its cells
+    uint64_t size = 0, returns = 0, sum_nx = 0, sum_ny = 0;
+    uint32_t min_x = 0, max_x = 0, min_y = 0, max_y = 0;
+    uint32_t nearest_d2 = 0, nearest_cell = 0;
+    double centroid_x() const { return static_cast<double>(sum_nx) / static_cast<double>(returns); }
+    double centroid_y() const { return static_cast<double>(sum_ny) / static_cast<double>(returns); }
+};
+inline Transient transient_of_row(const unsigned long long *row) {
+    Transient t;
+    t.label = static_cast<uint32_t>(row[0]), t.size = row[1], t.returns = row[2], t.sum_nx = row[3], t.sum_ny = row[4];
+    t.min_x = static_cast<uint32_t>(row[5]), t.max_x = static_cast<uint32_t>(row[6]), t.min_y = static_cast<uint32_t>(row[7]), t.max_y = static_cast<uint32_t>(row[8]);
+    t.nearest_d2 = static_cast<uint32_t>(row[9] >> 32), t.nearest_cell = static_cast<uint32_t>(row[9] & 0xFFFFFFFFull);
+    return t;
+}
 // GainConfig and Gain go with KinematicICP::GridGain (kicp.h kicp_grid_gain): the classes' thresholds and the sensor's range in cells,
 // and what one candidate viewpoint would see - the four words of its row by name.
 using GainConfig = kicp_gain_config;
@@ -263,6 +283,7 @@ inline std::shared_ptr<kicp_grid> clone_grid(const kicp_grid *grid, int device =
     check(kicp_grid_counts(grid, counts.data(), cells), "kicp_bridge::clone_grid");
     auto copy = make_grid(config, device);
     check(kicp_grid_set_counts(copy.get(), counts.data(), cells), "kicp_bridge::clone_grid");
+    check(kicp_grid_use_transients(copy.get(), kicp_grid_uses_transients(grid)), "kicp_bridge::clone_grid");  // the switch; the copy's transient plane starts empty
     return copy;
 }
 // The height columns a mapping run keeps for uneven ground (kicp.h kicp_elev_*): KinematicICP::EnableElevation takes an ElevationConfig

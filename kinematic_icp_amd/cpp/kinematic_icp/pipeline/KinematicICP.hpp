@@ -82,6 +82,8 @@ public:
           preprocessor_(o.preprocessor_),
           local_map_(o.local_map_),
           grid_(kicp_bridge::clone_grid(o.grid_.get())),
+          transients_enabled_(o.transients_enabled_),
+          transient_config_(o.transient_config_),
           elev_(kicp_bridge::clone_elevation(o.elev_.get())),
           last_elev_stats_(o.last_elev_stats_),
           elev_carving_(o.elev_carving_),
@@ -103,6 +105,9 @@ public:
           local_map_(std::move(o.local_map_)),
           pre_(o.pre_),
           grid_(std::move(o.grid_)),
+          transients_enabled_(o.transients_enabled_),
+          transient_config_(o.transient_config_),
+          last_transients_(std::move(o.last_transients_)),
           elev_(std::move(o.elev_)),
           last_elev_stats_(o.last_elev_stats_),
           elev_carving_(o.elev_carving_),
@@ -120,6 +125,7 @@ public:
         local_map_ = std::move(o.local_map_);
         std::swap(pre_, o.pre_);
         std::swap(elev_carving_, o.elev_carving_), std::swap(elev_carve_, o.elev_carve_), std::swap(last_elev_carve_stats_, o.last_elev_carve_stats_);
+        std::swap(transients_enabled_, o.transients_enabled_), std::swap(transient_config_, o.transient_config_), std::swap(last_transients_, o.last_transients_);
         std::swap(grid_, o.grid_), std::swap(elev_, o.elev_), std::swap(last_elev_stats_, o.last_elev_stats_), std::swap(view_, o.view_), std::swap(last_removal_, o.last_removal_), std::swap(sensor_in_base_, o.sensor_in_base_);
         return *this;
     }
@@ -159,6 +165,7 @@ public:
         if (view_ && config_.update_map) RemoveSeenThrough(kicp_bridge::xyz(preprocessed_frame_in_base), preprocessed_frame_in_base.size(), false, new_pose);
         if (config_.update_map) local_map_.Update(frame_downsample, new_pose);
         last_pose_ = new_pose;
+        if (grid_ && transients_enabled_) DetectTransients(kicp_bridge::xyz(preprocessed_frame_in_base), preprocessed_frame_in_base.size(), false);
         if (grid_) IntegrateGrid(kicp_bridge::xyz(preprocessed_frame_in_base), preprocessed_frame_in_base.size(), false);
         if (elev_) IntegrateElevation(kicp_bridge::xyz(preprocessed_frame_in_base), preprocessed_frame_in_base.size(), false);
         return {preprocessed_frame_in_base, source};
@@ -317,8 +324,9 @@ public:
     // kicp_grid_*).  Poses, thresholds, returned clouds and the map are what they are without the grid.  Config::update_map = false
     // does not stop it: localising in a saved map while drawing a grid of what is seen now is legitimate.  SetPose leaves it alone.
     // Grid() is the shared handle (null without a grid): a node may keep it for the kicp_grid_* calls of its map publisher.
-    void EnableGrid(const kicp_bridge::GridConfig &config) { grid_ = kicp_bridge::make_grid(config); }
-    void DisableGrid() { grid_.reset(); }
+    // (A new grid, or none, ends EnableTransients below: its plane and switch went with the old handle.)
+    void EnableGrid(const kicp_bridge::GridConfig &config) { grid_ = kicp_bridge::make_grid(config), transients_enabled_ = false, last_transients_.clear(); }
+    void DisableGrid() { grid_.reset(), transients_enabled_ = false, last_transients_.clear(); }
     std::shared_ptr<kicp_grid> Grid() const { return grid_; }
     // the readout, a nav_msgs/OccupancyGrid's `data`: width * height bytes, row-major from the origin, -1 unknown, else 0 .. 100
     void GridOccupancy(std::vector<int8_t> &data, unsigned int min_observations = 1) const {
@@ -469,6 +477,39 @@ public:
         kicp_bridge::check(rc, "GridFrontiers");
         frontiers.resize(n);
         for (size_t i = 0; i < n; ++i) frontiers[i] = kicp_bridge::frontier_of_row(rows.data() + i * KICP_FRONTIER_WORDS);
+    }
+    // What stands in known free space right now (kicp.h kicp_grid_transients): while enabled, RegisterFrame and its variants run the
+    // detection on the frame they return, at the new pose, immediately before that frame is integrated into the grid - from HBM on the
+    // chained path, from the host points on the other - so the counters it is judged by do not hold its own hits yet.  Transients() are
+    // the last frame's, of at least config.min_size cells in ascending label order.  With as_sources the grid's switch is raised: the
+    // cells of those transients are sources in GridClearance, GridCostmap and GridPotential until the next frame replaces them, while
+    // GridOccupancy, GridFrontiers, GridGain and SaveGrid never see them.  Poses, clouds, the map and the grid's counters are what they
+    // are without it.  A copied pipeline copies the switch and the configuration and starts with an empty plane.  Throws without a grid.
+    void EnableTransients(const kicp_bridge::TransientConfig &config, bool as_sources = true) {
+        kicp_grid *grid = MutableGrid("EnableTransients");
+        size_t n = 0;
+        const double pose[7] = {0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0}, sensor[3] = {0.0, 0.0, 0.0};
+        kicp_bridge::check(kicp_grid_transients(grid, nullptr, 0, pose, sensor, &config, nullptr, 0, &n, nullptr, 0, nullptr), "EnableTransients");  // (checks config)
+        kicp_bridge::check(kicp_grid_use_transients(grid, as_sources ? 1 : 0), "EnableTransients");
+        transient_config_ = config, transients_enabled_ = true, last_transients_.clear();
+    }
+    // empties the plane and lowers the switch; without a grid there is nothing to do
+    void DisableTransients() {
+        if (grid_ && transients_enabled_) {
+            size_t n = 0;
+            const double pose[7] = {0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0}, sensor[3] = {0.0, 0.0, 0.0};
+            kicp_bridge::check(kicp_grid_transients(grid_.get(), nullptr, 0, pose, sensor, &transient_config_, nullptr, 0, &n, nullptr, 0, nullptr), "DisableTransients");
+            kicp_bridge::check(kicp_grid_use_transients(grid_.get(), 0), "DisableTransients");
+        }
+        transients_enabled_ = false, last_transients_.clear();
+    }
+    bool TransientsEnabled() const { return transients_enabled_; }
+    const std::vector<kicp_bridge::Transient> &Transients() const { return last_transients_; }
+    // the plane of the last frame's transients, a byte per cell: what GridCostmap treats as lethal while the switch is on
+    void TransientPlane(std::vector<uint8_t> &plane) const {
+        const kicp_bridge::GridRect r = GridRectOrAll(nullptr, "TransientPlane");
+        plane.resize(static_cast<size_t>(r.w) * r.h);
+        kicp_bridge::check(kicp_grid_transient_plane(grid_.get(), plane.data(), plane.size()), "TransientPlane");
     }
     // What the robot would see from there (kicp.h kicp_grid_gain): per candidate viewpoint - a cell index y * width + x, such as the
     // best_cell of GridFrontiers' frontiers under a plan - the distinct unknown cells a sensor of config.range_cells' range (1 .. 361)
@@ -651,6 +692,10 @@ protected:
         if (!grid_) throw std::runtime_error(std::string("KinematicICP::") + who + ": call EnableGrid first");
         return grid_.get();
     }
+    kicp_grid *MutableGrid(const char *who) {
+        if (!grid_) throw std::runtime_error(std::string("KinematicICP::") + who + ": call EnableGrid first");
+        return grid_.get();
+    }
     const kicp_elev *RequireElevation(const char *who) const {
         if (!elev_) throw std::runtime_error(std::string("KinematicICP::") + who + ": call EnableElevation first");
         return elev_.get();
@@ -670,6 +715,27 @@ protected:
         const double sensor[3] = {sensor_in_base_.x(), sensor_in_base_.y(), sensor_in_base_.z()};
         kicp_bridge::check(on_device ? kicp_grid_integrate_device(grid_.get(), xyz, n, pose, sensor, nullptr) : kicp_grid_integrate(grid_.get(), xyz, n, pose, sensor, nullptr),
                            "occupancy grid");
+    }
+    // the transients of one frame at last_pose_ (already the new pose) against the counters as they stand, from HBM or from host memory
+    void DetectTransients(const double *xyz, size_t n_points, bool on_device) {
+        double pose[7];
+        kicp_bridge::to_params(last_pose_, pose);
+        const double sensor[3] = {sensor_in_base_.x(), sensor_in_base_.y(), sensor_in_base_.z()};
+        transient_rows_.resize(std::max<size_t>(transient_rows_.size(), 64 * static_cast<size_t>(KICP_TRANSIENT_WORDS)));
+        size_t n = 0;
+        auto call = [&] {
+            const size_t cap = transient_rows_.size() / KICP_TRANSIENT_WORDS;
+            return on_device ? kicp_grid_transients_device(grid_.get(), xyz, n_points, pose, sensor, &transient_config_, transient_rows_.data(), cap, &n, nullptr, 0, nullptr)
+                             : kicp_grid_transients(grid_.get(), xyz, n_points, pose, sensor, &transient_config_, transient_rows_.data(), cap, &n, nullptr, 0, nullptr);
+        };
+        int rc = call();
+        if (rc == KICP_ERR_CAPACITY && n > transient_rows_.size() / KICP_TRANSIENT_WORDS) {  // more transients than that: their number came back
+            transient_rows_.resize(n * KICP_TRANSIENT_WORDS);
+            rc = call();
+        }
+        kicp_bridge::check(rc, "transients");
+        last_transients_.resize(n);
+        for (size_t i = 0; i < n; ++i) last_transients_[i] = kicp_bridge::transient_of_row(transient_rows_.data() + i * KICP_TRANSIENT_WORDS);
     }
     // one frame into the height columns at last_pose_ (already the new pose), from HBM or from host memory
     void IntegrateElevation(const double *xyz, size_t n, bool on_device) {
@@ -725,6 +791,8 @@ protected:
         if (config_.update_map) local_map_.UpdateDeviceBegin(kicp_pre_device_ptr(pre_, 1, nullptr), n_down, new_pose);
         last_pose_ = new_pose;
         // the occupancy grid, when enabled: the whole preprocessed frame (buffer 0, complete since the pre-steps returned) at the new pose
+        // the transients, when enabled: the same frame against the counters as they stand, before its own hits go into them
+        if (grid_ && transients_enabled_) DetectTransients(kicp_pre_device_ptr(pre_, 0, nullptr), counts[0], true);
         if (grid_) IntegrateGrid(kicp_pre_device_ptr(pre_, 0, nullptr), counts[0], true);
         // the height columns, when enabled: the same frame at the same pose
         if (elev_) IntegrateElevation(kicp_pre_device_ptr(pre_, 0, nullptr), counts[0], true);
@@ -790,6 +858,10 @@ protected:
     kicp_pre *pre_ = nullptr;  // device workspace of the pre-steps (backend detail)
     std::shared_ptr<kicp_occ> occupancy_;  // BuildOccupancy's snapshot of the map (backend detail)
     std::shared_ptr<kicp_grid> grid_;      // EnableGrid's occupancy grid (backend detail); null: no grid
+    bool transients_enabled_ = false;      // EnableTransients: every frame is searched for transients before it goes into the grid
+    kicp_bridge::TransientConfig transient_config_{};
+    std::vector<kicp_bridge::Transient> last_transients_;  // the last frame's
+    std::vector<unsigned long long> transient_rows_;       // where their rows land (scratch that keeps its size)
     std::shared_ptr<kicp_elev> elev_;      // EnableElevation's height columns (backend detail); null: no layer
     kicp_bridge::ElevationStats last_elev_stats_{};  // the last frame's statistics of that layer
     bool elev_carving_ = false;                      // EnableElevationCarving: frames go into the layer as updates

@@ -11,6 +11,9 @@
 //                    into LDS (at most 764 bytes), each lane scans outwards from its cell (clear_row_scan) and stores the clearance as
 //                    16 bits, or - the costmap - looks its class up again from its counters, the cost in the caller's table (65 KB at
 //                    most, read by every lane: it stays in cache) and stores a byte.
+// THE TRANSIENT PLANE (kicp_grid_use_transients): both kernels take a bool template parameter kPlane and a pointer to a byte per cell.
+// With kPlane a cell whose byte is 1 is a source in the columns' sweep and has the source's class in the costmap's lookup, whatever its
+// counters say; without it the pointer is never read and the code is what it was before the plane existed.
 // No atomics, no floating point, no scratch.  Both grids are one-dimensional: a column of 2^28 cells has more strips than a grid's y
 // dimension admits.
 #pragma once
@@ -23,15 +26,22 @@ namespace kicp {
 constexpr uint32_t kClearBlock = 256;
 static_assert(kClearBlock == kClearSegment, "one lane per cell of a segment");
 
-static __device__ __forceinline__ bool clear_source_at(const uint32_t *__restrict__ pairs, size_t cell, const ClearParams &p) {
+template <bool kPlane>
+static __device__ __forceinline__ bool clear_source_at(const uint32_t *__restrict__ pairs, const uint8_t *__restrict__ plane, size_t cell, const ClearParams &p) {
     const uint32_t pair = pairs[cell];
-    return clear_is_source(clear_class(grid_readout(pair & 0xFFFFu, pair >> 16, p.min_observations), p.source_min), p.unknown_is_obstacle);
+    const bool source = clear_is_source(clear_class(grid_readout(pair & 0xFFFFu, pair >> 16, p.min_observations), p.source_min), p.unknown_is_obstacle);
+    if constexpr (kPlane)
+        return source || plane[cell] != 0u;
+    else
+        return source;
 }
 
 // coldist: r.h rows of cw bytes, column cx0 + i of the grid at byte i; blockIdx.x = strip * col_blocks + block of 256 columns;
 // strip s holds the rows r.y0 + s * strip_rows .. of the rectangle
+template <bool kPlane>
 static __global__ __launch_bounds__(kClearBlock) void k_clear_columns(const uint16_t *__restrict__ counts, uint32_t width, uint32_t height, ClearParams p, ClearRect r,
-                                                                      uint32_t cx0, uint32_t cw, uint32_t strip_rows, uint32_t col_blocks, uint8_t *coldist) {
+                                                                      uint32_t cx0, uint32_t cw, uint32_t strip_rows, uint32_t col_blocks, uint8_t *coldist,
+                                                                      const uint8_t *__restrict__ plane) {
     const uint32_t col = (blockIdx.x % col_blocks) * kClearBlock + threadIdx.x;
     if (col >= cw) return;
     const uint32_t *pairs = reinterpret_cast<const uint32_t *>(counts);
@@ -40,13 +50,13 @@ static __global__ __launch_bounds__(kClearBlock) void k_clear_columns(const uint
     const uint32_t lo = ys > p.radius ? ys - p.radius : 0u, hi = ye + p.radius < height ? ye + p.radius : height;
     uint32_t d = kClearNone;
     for (uint32_t y = lo; y < ye; ++y) {
-        d = clear_sweep(d, clear_source_at(pairs, static_cast<size_t>(y) * width + x, p));
+        d = clear_sweep(d, clear_source_at<kPlane>(pairs, plane, static_cast<size_t>(y) * width + x, p));
         if (y >= ys) coldist[static_cast<size_t>(y - r.y0) * cw + col] = static_cast<uint8_t>(d);
     }
     d = kClearNone;
     for (uint32_t y = hi; y-- > ys;) {
         if (y >= ye) {
-            d = clear_sweep(d, clear_source_at(pairs, static_cast<size_t>(y) * width + x, p));
+            d = clear_sweep(d, clear_source_at<kPlane>(pairs, plane, static_cast<size_t>(y) * width + x, p));
             continue;
         }
         uint8_t *o = coldist + static_cast<size_t>(y - r.y0) * cw + col;
@@ -58,10 +68,10 @@ static __global__ __launch_bounds__(kClearBlock) void k_clear_columns(const uint
 }
 
 // blockIdx.x = row * segments + segment; out: r.h rows of r.w values, 16 bits each (the clearance) or 8 (kCost: the cost)
-template <bool kCost>
+template <bool kCost, bool kPlane>
 static __global__ __launch_bounds__(kClearBlock) void k_clear_rows(const uint8_t *__restrict__ coldist, uint32_t cx0, uint32_t cw, const uint16_t *__restrict__ counts,
                                                                    uint32_t width, ClearParams p, ClearRect r, uint32_t segments, const uint8_t *__restrict__ table,
-                                                                   uint32_t inflate_unknown, void *__restrict__ out) {
+                                                                   uint32_t inflate_unknown, void *__restrict__ out, const uint8_t *__restrict__ plane) {
     __shared__ uint8_t g[kClearSegment + 2 * kClearMaxRadius];
     const uint32_t row = blockIdx.x / segments, first = r.x0 + (blockIdx.x % segments) * kClearSegment;  // the segment's first cell
     const uint8_t *line = coldist + static_cast<size_t>(row) * cw;
@@ -75,8 +85,10 @@ static __global__ __launch_bounds__(kClearBlock) void k_clear_rows(const uint8_t
     const uint32_t c = clear_row_scan(g + p.radius + threadIdx.x, p.radius);
     const size_t at = static_cast<size_t>(row) * r.w + (x - r.x0);
     if constexpr (kCost) {
-        const uint32_t pair = reinterpret_cast<const uint32_t *>(counts)[static_cast<size_t>(r.y0 + row) * width + x];
-        const uint32_t cls = clear_class(grid_readout(pair & 0xFFFFu, pair >> 16, p.min_observations), p.source_min);
+        const size_t cell = static_cast<size_t>(r.y0 + row) * width + x;
+        const uint32_t pair = reinterpret_cast<const uint32_t *>(counts)[cell];
+        uint32_t cls = clear_class(grid_readout(pair & 0xFFFFu, pair >> 16, p.min_observations), p.source_min);
+        if constexpr (kPlane) cls = plane[cell] != 0u ? static_cast<uint32_t>(kClearSource) : cls;
         static_cast<uint8_t *>(out)[at] = clear_cost(cls, p.unknown_is_obstacle, table[c], inflate_unknown);
     } else {
         static_cast<uint16_t *>(out)[at] = static_cast<uint16_t>(c);

@@ -18,6 +18,7 @@
 //                    and the sums, min and max for the box, min for the key pot(c) * 2^32 + c.  All of them commute, so the rows do
 //                    not depend on the order of arrival.  Lanes of a wave that share a root are not combined first: frontier cells
 //                    are about one in a hundred, and a wave seldom holds more than a few of one frontier.
+// k_front_local, k_front_border and k_front_flatten take any flag plane: kicp_grid_transient.hip runs them over its own (kicp_transient.hpp).
 //
 // THE INVARIANT that keeps the union-find safe where nothing may wait: parent[c] <= c ALWAYS, AND A STORED PARENT ONLY EVER FALLS.
 // A cell starts as its own parent (or, in global memory, under its tile's root, which is the least index of its tile's component);

@@ -42,14 +42,20 @@ inline void front_row_add(unsigned long long *row, uint32_t x, uint32_t y, unsig
     row[6] = std::min<unsigned long long>(row[6], y), row[7] = std::max<unsigned long long>(row[7], y);
     row[8] = std::min(row[8], key);
 }
-// The output of n summed rows (in any order): those of at least min_size cells in ascending label order, the key split into
-// best_potential and best_cell; the first `cap` of them are stored.  Returns the number that passed the filter.
-inline size_t front_emit(const unsigned long long *rows, size_t n, uint32_t min_size, unsigned long long *out, size_t cap) {
+// Which of n summed rows (in any order) are output and in which order: those of at least min_size cells (word 1), by ascending label
+// (word 0).  The transients' rows keep the same two words there (kicp_transient_host.hpp).
+inline std::vector<size_t> front_order(const unsigned long long *rows, size_t n, uint32_t min_size) {
     std::vector<size_t> order;
     order.reserve(n);
     for (size_t i = 0; i < n; ++i)
         if (rows[i * kFrontWords + 1] >= min_size) order.push_back(i);
     std::sort(order.begin(), order.end(), [&](size_t a, size_t b) { return rows[a * kFrontWords] < rows[b * kFrontWords]; });
+    return order;
+}
+// The output of n summed rows: those front_order keeps, the key split into best_potential and best_cell; the first `cap` of them are
+// stored.  Returns the number that passed the filter.
+inline size_t front_emit(const unsigned long long *rows, size_t n, uint32_t min_size, unsigned long long *out, size_t cap) {
+    const std::vector<size_t> order = front_order(rows, n, min_size);
     for (size_t k = 0; k < order.size() && k < cap; ++k) {
         const unsigned long long *row = rows + order[k] * kFrontWords;
         unsigned long long *o = out + k * kFrontWords;

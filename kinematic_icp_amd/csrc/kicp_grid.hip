@@ -114,6 +114,7 @@ int kicp_grid_clear(kicp_grid *grid) {
     if (!grid) return fail(KICP_ERR_ARG, "null argument");
     if (int rc = set_device(grid->device)) return rc;
     HIP_TRY(hipMemsetAsync(grid->d_counts.get(), 0, 2 * grid->cells * sizeof(uint16_t), grid->stream));
+    if (grid->d_transient_plane.get()) HIP_TRY(hipMemsetAsync(grid->d_transient_plane.get(), 0, grid->cells, grid->stream));  // (the switch stays as it is)
     HIP_TRY(hipStreamSynchronize(grid->stream));
     grid->frames = 0, grid->has_window = false;
     return KICP_OK;

@@ -12,11 +12,14 @@
 //                          kicp_arc_tree_nodes, kicp_arc_tree_best
 //   kicp_grid_explore.hip  where to go while mapping (kicp_front.hpp, kicp_gain.hpp): the frontiers and the viewpoints' gain, each
 //                          with its host twin
+//   kicp_grid_transient.hip what stands in known free space right now (kicp_transient.hpp, and kicp_front.hpp once more for its
+//                          union-find - the one kernel header two units include): kicp_grid_transients and its host twin, the
+//                          transient plane and the switch that makes its cells sources of the clearance
 #pragma once
 #include "kicp_clear_host.hpp"
 #include "kicp_internal.hpp"
 
-// (an internal header of five translation units that all begin this way)
+// (an internal header of six translation units that all begin this way)
 using namespace kicp;
 using namespace kicp::host;
 namespace kicp {
@@ -26,7 +29,9 @@ struct ArcTreeNode;  // kicp_arc_tree_host.hpp: the handle only holds a buffer o
 // CONST ENTRIES.  The C-ABI takes `const kicp_grid *` wherever a call leaves the map as it was: info, counts, occupancy, clearance,
 // costmap, the two potential entries, has_plan, score_arcs, score_arc_tree, frontiers, gain, last_window, save_map.  Such an entry reads the top-level
 // members - the counters among them - and writes only the groups declared `mutable` below: scratch whose contents no later call
-// relies on, but for the plan, which is the one thing a const entry leaves behind on purpose.
+// relies on, but for the plan, which is the one thing a const entry leaves behind on purpose.  kicp_grid_transients* and
+// kicp_grid_use_transients take the handle non-const: the transient plane and the switch are top-level state that clearance, costmap
+// and potential read; kicp_grid_transient_plane and kicp_grid_uses_transients only read them.
 //
 // THE STREAM RULE.  Every entry returns with the handle's stream drained, so the next one finds it idle and may let a buffer grow
 // (DevBuf::reserve frees the old memory) without a synchronisation of its own.  The one exception: kicp_grid_potential queues the
@@ -43,6 +48,10 @@ struct kicp_grid {
     unsigned long long frames = 0;
     bool has_window = false;  // a frame has been integrated since creation or the last clear: (win_x0, win_y0) is its window's lower corner
     int32_t win_x0 = 0, win_y0 = 0;
+    // THE TRANSIENT PLANE, a byte per cell: 1 on the cells of the last kicp_grid_transients call's transients that passed min_size.  Not
+    // allocated (and read as all 0) until the first such call.  use_transients is the switch: clear_on_device ORs the plane into its sources.
+    DevBuf<uint8_t> d_transient_plane;
+    bool use_transients = false;
     // kicp_grid_integrate*: the two frame-local planes over the window, zero between frames, and the frame in flight
     struct {
         uint32_t plane_words = 0;       // ceil((2 reach + 1)^2 / 4)
@@ -95,6 +104,18 @@ struct kicp_grid {
         PinnedBuf<uint32_t> h_ctr;
         std::vector<unsigned long long> h_rows;
     } front;
+    // kicp_grid_transients*: the returns and the flags per cell (both zero between calls), the touched list (room for one entry per
+    // point), the parent plane that becomes the label plane, the roots' row numbers, the statistics and the count of roots (word 4),
+    // the rows and where they land
+    struct {
+        bool ready = false;  // the planes are allocated and zero
+        DevBuf<uint32_t> d_returns, d_touched, d_parent, d_row_of;
+        DevBuf<uint8_t> d_flags;
+        DevBuf<unsigned int> d_stats;
+        PinnedBuf<unsigned int> h_stats;
+        DevBuf<unsigned long long> d_rows;
+        std::vector<unsigned long long> h_rows;
+    } transient;
     // kicp_grid_gain: a byte per cell, the viewpoints' upload, their rows and the pinned buffer the rows come back through
     mutable struct {
         DevBuf<uint8_t> d_classes;

@@ -30,7 +30,9 @@ int check_cost_table(const ClearParams &p, size_t table_len) {
 }
 // The clearance (table == nullptr: 16 bits per cell into `out`) or the costmap (a byte per cell) of a rectangle; arguments checked.
 // Two launches, one copy, the stream drained.  out == nullptr: the costmap stays in d_cost for the launches the caller queues behind
-// these; nothing is copied or waited for (the stream rule's exception).
+// these; nothing is copied or waited for (the stream rule's exception).  With the handle's switch on (kicp_grid_use_transients) and a
+// transient plane to read, the kPlane instantiations run: the plane's cells are sources.  The clearance's rows take no class, so they
+// have no such instantiation.
 int clear_on_device(const kicp_grid *grid, const ClearParams &p, const ClearRect &r, const unsigned char *table, uint32_t inflate_unknown, void *out) {
     if (int rc = set_device(grid->device)) return rc;
     const size_t cells = static_cast<size_t>(r.w) * r.h;
@@ -50,14 +52,18 @@ int clear_on_device(const kicp_grid *grid, const ClearParams &p, const ClearRect
     // a strip of at least R rows keeps the rows a workgroup reads beside its own at or below twice its own
     const uint32_t strip = std::max(32u, p.radius), strips = (r.h + strip - 1u) / strip, col_blocks = (cw + kClearBlock - 1u) / kClearBlock;
     const uint32_t segments = (r.w + kClearSegment - 1u) / kClearSegment;  // (both products stay below 2^29: cells <= 2^28)
-    hipLaunchKernelGGL(k_clear_columns, dim3(strips * col_blocks), dim3(kClearBlock), 0, st, grid->d_counts.get(), grid->cfg.width, grid->cfg.height, p, r, cx0, cw, strip,
-                       col_blocks, c.d_coldist.get());
+    const uint8_t *plane = grid->use_transients ? grid->d_transient_plane.get() : nullptr;  // (no plane yet: all 0)
+    const auto columns = plane ? &k_clear_columns<true> : &k_clear_columns<false>;
+    const auto cost_rows = plane ? &k_clear_rows<true, true> : &k_clear_rows<true, false>;
+    const auto clearance_rows = &k_clear_rows<false, false>;
+    hipLaunchKernelGGL(columns, dim3(strips * col_blocks), dim3(kClearBlock), 0, st, grid->d_counts.get(), grid->cfg.width, grid->cfg.height, p, r, cx0, cw, strip,
+                       col_blocks, c.d_coldist.get(), plane);
     if (table)
-        hipLaunchKernelGGL(k_clear_rows<true>, dim3(r.h * segments), dim3(kClearBlock), 0, st, c.d_coldist.get(), cx0, cw, grid->d_counts.get(), grid->cfg.width, p, r,
-                           segments, c.d_cost_table.get(), inflate_unknown, static_cast<void *>(c.d_cost.get()));
+        hipLaunchKernelGGL(cost_rows, dim3(r.h * segments), dim3(kClearBlock), 0, st, c.d_coldist.get(), cx0, cw, grid->d_counts.get(), grid->cfg.width, p, r, segments,
+                           c.d_cost_table.get(), inflate_unknown, static_cast<void *>(c.d_cost.get()), plane);
     else
-        hipLaunchKernelGGL(k_clear_rows<false>, dim3(r.h * segments), dim3(kClearBlock), 0, st, c.d_coldist.get(), cx0, cw, grid->d_counts.get(), grid->cfg.width, p, r,
-                           segments, static_cast<const uint8_t *>(nullptr), 0u, static_cast<void *>(c.d_clearance.get()));
+        hipLaunchKernelGGL(clearance_rows, dim3(r.h * segments), dim3(kClearBlock), 0, st, c.d_coldist.get(), cx0, cw, grid->d_counts.get(), grid->cfg.width, p, r, segments,
+                           static_cast<const uint8_t *>(nullptr), 0u, static_cast<void *>(c.d_clearance.get()), static_cast<const uint8_t *>(nullptr));
     HIP_TRY(hipGetLastError());
     if (!out) return KICP_OK;
     if (table)

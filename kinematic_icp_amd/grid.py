@@ -1,5 +1,6 @@
 """The 2-D occupancy grid (kicp_grid_*): the counters a mapping run draws frame by frame, their readout and map files, clearance and
-Nav2-style costmaps, the fill from another grid - and, on the grid's handle, the plan (plan.py) and the exploration (explore.py)."""
+Nav2-style costmaps, the fill from another grid - and, on the grid's handle, the plan (plan.py), the exploration (explore.py) and the
+transient obstacles (transients.py)."""
 import ctypes as C
 import math
 import os
@@ -9,6 +10,7 @@ import numpy as np
 from ._ffi import (KICP_ERR_ARG, Handle, KicpError, _check, _declare, _dp, _frame_args, _hp, _i8, _i8p, _info, _last_window, _occupancy_2d,
                    _out_array, _rect, _szp, _u8, _u8p, _u16, _u16p, _u32, _u32p, _u64, _u64p, lib)
 from .explore import GAIN_WORDS, FrontierConfig, GainConfig, _frontier_call, _frontier_config, _gain_config, _gain_views
+from .transients import TransientConfig, _transient_call, _transient_config
 from .plan import MAX_POTENTIAL, PlanConfig, _arc_tree_args, _arcs_args, _plan_args, _potential_out, _potential_result
 
 
@@ -33,6 +35,7 @@ class GridFillConfig(C.Structure):
 
 _vp, _u, _f64, _sz = C.c_void_p, C.c_uint, C.c_double, C.c_size_t
 _clear, _plan, _fill = C.POINTER(GridClearanceConfig), C.POINTER(PlanConfig), C.POINTER(GridFillConfig)
+_transient_tail = [_dp, _dp, C.POINTER(TransientConfig), _u64p, _sz, _szp, _u32p, _sz, _u64p]  # pose, sensor, config, rows, labels, stats
 
 _ENTRIES = _declare({
     "kicp_grid_create": (C.c_int, [C.POINTER(GridConfig), C.c_int, _hp]),
@@ -63,6 +66,11 @@ _ENTRIES = _declare({
     "kicp_grid_score_arc_tree": (C.c_int, [_vp, _dp, _u, _u32p, _u32p, _dp, _dp, _sz, _u32p, _sz]),
     "kicp_grid_frontiers": (C.c_int, [_vp, C.POINTER(FrontierConfig), C.c_int, _u64p, _sz, _szp, _u32p, _sz]),
     "kicp_grid_gain": (C.c_int, [_vp, C.POINTER(GainConfig), _u32p, _sz, _u32p, _sz]),
+    "kicp_grid_transients": (C.c_int, [_vp, _dp, _sz] + _transient_tail),
+    "kicp_grid_transients_device": (C.c_int, [_vp, _vp, _sz] + _transient_tail),
+    "kicp_grid_transient_plane": (C.c_int, [_vp, _u8p, _sz]),
+    "kicp_grid_use_transients": (C.c_int, [_vp, C.c_int]),
+    "kicp_grid_uses_transients": (C.c_int, [_vp]),
 })
 
 
@@ -301,6 +309,40 @@ class OccupancyGrid(Handle):
         out = np.empty((len(v), GAIN_WORDS), dtype=np.uint32)
         _check(lib().kicp_grid_gain(self._h, C.byref(cfg), _u32(v), len(v), _u32(out), out.size))
         return out
+
+    def transients(self, frame, pose, sensor_xyz=(0.0, 0.0, 0.0), min_observations=1, free_max=65, min_points=1, min_size=1, return_labels=False,
+                   return_stats=False):
+        """kicp_grid_transients: on the GPU, transients_from_counts' result for one frame of points in the base frame (host memory) at
+        `pose` on the counters where they are -> uint64 (T, 10), then uint32 (height, width) labels with return_labels and (points used,
+        used points that end inside the grid, cells with a return, transient cells) with return_stats.  Call it before integrate() of
+        the same frame.  The counters, the frame count, the last window and the plan are not changed; the handle's transient plane is
+        replaced by the cells of the transients that are output."""
+        cfg = _transient_config(min_observations, free_max, min_points, min_size)
+        head = (self._h, *_frame_args(pose, sensor_xyz, frame=frame), C.byref(cfg))
+        return _transient_call(lambda *tail: lib().kicp_grid_transients(*head, *tail), (self.height, self.width), return_labels, return_stats)
+
+    def transients_device(self, device_frame, pose, sensor_xyz=(0.0, 0.0, 0.0), n=None, min_observations=1, free_max=65, min_points=1, min_size=1,
+                          return_labels=False, return_stats=False):
+        """kicp_grid_transients_device: the same for a DeviceFrame (or anything with .ptr and .n) already in HBM"""
+        cfg = _transient_config(min_observations, free_max, min_points, min_size)
+        head = (self._h, *_frame_args(pose, sensor_xyz, device_frame=device_frame, n=n), C.byref(cfg))
+        return _transient_call(lambda *tail: lib().kicp_grid_transients_device(*head, *tail), (self.height, self.width), return_labels, return_stats)
+
+    def transient_plane(self):
+        """kicp_grid_transient_plane: -> uint8 (height, width), 1 on the cells of the last transients() call's transients that passed
+        min_size; all 0 before the first call, after clear() and after a call that found none"""
+        out = np.empty((self.height, self.width), dtype=np.uint8)
+        _check(lib().kicp_grid_transient_plane(self._h, _u8(out), out.size))
+        return out
+
+    def use_transients(self, on=True):
+        """kicp_grid_use_transients: while on, the transient plane's cells are sources in clearance(), costmap() and potential() whatever
+        their counters say; everything else ignores the plane.  Off at creation; clear() does not change it."""
+        _check(lib().kicp_grid_use_transients(self._h, 1 if on else 0))
+
+    def uses_transients(self):
+        """kicp_grid_uses_transients: is the switch on?"""
+        return bool(lib().kicp_grid_uses_transients(self._h))
 
     def last_window(self):
         """kicp_grid_last_window: (x0, y0, w, h) of the last integrated frame's window clipped to the grid; w = h = 0 when it lies
