@@ -1247,6 +1247,63 @@ int kicp_elev_to_grid_rough(const kicp_elev *elev, const kicp_elev_traversabilit
                             const kicp_elev_rough_config *rough_config, kicp_grid *grid);
 int kicp_elev_rough_limit(const kicp_elev_config *config, double rms_metres, unsigned int *num, unsigned int *den);
 
+/* ---- the map follows the robot: scrolling the grid and the height layer (kicp_grid.hip, kicp_elev.hip; kernel kicp_scroll.hpp) ---------
+ * A handle's width, height and cell are fixed, its origin is not: a SCROLL moves the window of the world the handle covers by whole
+ * cells, on the GPU, and keeps every cell that stays inside.  Everything below is exact: integers, and two rounded fp64 operations for
+ * the origin.
+ *
+ * THE SHIFT OF A PLANE.  A plane is width x height elements, element (ix, iy) at iy * width + ix.  Shifted by (dx, dy), element
+ * (ix, iy) of the result is the input's element (ix + dx, iy + dy) where that lies inside the plane, and 0 elsewhere.  dx > 0 moves the
+ * window towards +x: the columns 0 .. dx - 1 leave, and dx empty columns enter at the high end.  |dx| >= width or |dy| >= height leaves
+ * all zeros; (0, 0) is the identity.  kicp_shift_plane is that shift as pure host code for elements of elem_bytes = 1, 2, 4 or 8 - the
+ * host twin for the transient plane, a single counter plane, the counter pairs and the height columns; `in` and `out` must not overlap,
+ * width and height >= 1 (KICP_ERR_ARG otherwise), width * height <= 2^28 (KICP_ERR_CAPACITY).  It needs no GPU.
+ *
+ * kicp_grid_scroll by (dx, dy):
+ *   - shifts the counters, one 32-bit element per cell - the hits and misses pair -, and the transient plane if it is allocated;
+ *   - sets origin_x = origin_x + (double)dx * cell - the product rounded, then the sum rounded, never one fused operation - and origin_y
+ *     likewise with dy;
+ *   - translates the last frame's window by (-dx, -dy); kicp_grid_last_window clips it as before, so it may come out empty (a window
+ *     pushed more than 2^30 cells from the grid is forgotten, as if no frame had been integrated: no shift brings a cell of it back);
+ *   - INVALIDATES THE PLAN (kicp_grid_has_plan reads 0 until the next potential call): the plan's cells no longer mean what they meant;
+ *   - leaves the frame count, the transient switch and every field of the configuration but the origin as they are.
+ * There is no hidden state: after the call the handle is indistinguishable from one created with the configuration kicp_grid_info now
+ * reports and given the shifted counters by kicp_grid_set_counts (and the shifted plane); every later entry returns the same bytes on
+ * both.  dx == dy == 0 changes nothing, the plan included.  A new origin that is not finite is KICP_ERR_ARG, and nothing changes.  The
+ * shift writes into a second buffer of the counters' size, which the handle allocates at the first shift that needs it and keeps - a
+ * scrolled handle holds its counters twice -; when that allocation fails the call fails as any allocation does, and nothing has
+ * changed.  A shift that empties the plane needs no second buffer.  The call returns after its work on the GPU has completed.
+ * kicp_elev_scroll is the same for the height columns, one 64-bit element per cell, with the layer's origin and last window.  A planner
+ * grid fed by kicp_elev_to_grid* is scrolled by the same (dx, dy) by its owner; the same sequence of shifts gives both the same origin,
+ * bit for bit, because the rule is the same arithmetic.
+ *
+ * FOLLOWING.  kicp_follow_shift is the rule for one axis, pure host code: for a cell index c on an axis of `size` cells, *d = 0 when
+ * margin <= c < size - margin; for c < margin, *d = -step * ceil((margin - c) / step); for c >= size - margin,
+ * *d = step * ceil((c - (size - margin) + 1) / step), in integers.  It requires margin >= 1, step >= 1 and 2 * margin + step <= size
+ * (KICP_ERR_ARG otherwise, and when d would leave 64 bits); under these the cell lands in the band: margin <= c - d < size - margin.
+ * kicp_grid_follow computes the cell of (x, y) with the grid's own arithmetic, floor((x - origin_x) / cell) and floor((y - origin_y) /
+ * cell), applies the rule per axis with width and height, scrolls ONCE by both and reports the shift applied (out_dx, out_dy, each
+ * nullable).  (0, 0) is the common case: host arithmetic only, no launch.  A position that is not finite, or whose cell lies beyond
+ * +-2^30, and a bad margin or step are KICP_ERR_ARG with nothing changed.  kicp_elev_follow does the same for the height layer.
+ *
+ * RECTANGLES OF COUNTERS.  kicp_grid_counts_rect and kicp_grid_set_counts_rect are kicp_grid_counts and kicp_grid_set_counts
+ * restricted to the rectangle x0, y0, w, h: inside the grid, w and h >= 1, cap_cells / cells == w * h (KICP_ERR_ARG otherwise); the
+ * layout is row-major from (x0, y0), two words per cell.  kicp_grid_set_counts_rect invalidates nothing and is otherwise a write like
+ * kicp_grid_set_counts.  With them a caller pages what leaves the window into a larger map of their own: before a scroll by (dx, dy)
+ * the cells that leave are the |dx| columns at the low (dx > 0) or high (dx < 0) end over all rows, and the |dy| rows at the low or
+ * high end over the remaining columns; after a scroll back the same two rectangles take them again.
+ *
+ * NOT THERE.  A grid that grows; toroidal addressing; automatic paging; rectangles of height columns; a plan carried across a scroll;
+ * a voxel map that scrolls. */
+int kicp_grid_scroll(kicp_grid *grid, int dx, int dy);
+int kicp_grid_follow(kicp_grid *grid, double x, double y, unsigned int margin, unsigned int step, int *out_dx, int *out_dy);
+int kicp_grid_counts_rect(const kicp_grid *grid, unsigned int x0, unsigned int y0, unsigned int w, unsigned int h, unsigned short *out, size_t cap_cells);
+int kicp_grid_set_counts_rect(kicp_grid *grid, unsigned int x0, unsigned int y0, unsigned int w, unsigned int h, const unsigned short *in, size_t cells);
+int kicp_elev_scroll(kicp_elev *elev, int dx, int dy);
+int kicp_elev_follow(kicp_elev *elev, double x, double y, unsigned int margin, unsigned int step, int *out_dx, int *out_dy);
+int kicp_shift_plane(const void *in, void *out, unsigned int width, unsigned int height, unsigned int elem_bytes, int dx, int dy);
+int kicp_follow_shift(long long c, unsigned int size, unsigned int margin, unsigned int step, long long *d);
+
 /* ---- map points the new frame sees through: a cube-map depth test (kicp_view.hip) ----------------------------------------------------
  * The local map loses points by distance only (RemovePointsFarFromLocation); whatever stood in view for one frame - a person crossing,
  * a forklift, a door leaf - stays until the robot is max_range away.  A kicp_view holds a depth image of ONE frame, and

@@ -28,7 +28,7 @@ from .elevation import _elev_classes, _struct, _traversability_call, _traversabi
 from .explore import FRONTIER_WORDS, GAIN_WORDS, FrontierConfig, GainConfig, frontiers_from_occupancy, gain_from_occupancy  # noqa: F401
 from .explore import _frontier_call, _frontier_config, _gain_config, _gain_views  # noqa: F401
 from .grid import (GridClearanceConfig, GridConfig, GridFillConfig, OccupancyGrid, clearance_from_occupancy, costmap_from_occupancy,  # noqa: F401
-                   fill_unknown_counts, nav2_cost_table, occupancy_from_counts, write_map)
+                   fill_unknown_counts, follow_shift, nav2_cost_table, occupancy_from_counts, shift_plane, write_map)
 from .grid import _clearance_config, _cost_table, _table_radius  # noqa: F401
 from .plan import (ARC_TREE_MAX_DEPTH, ARC_TREE_MAX_NODES, ARC_TREE_MAX_T, ARCS_MAX_K, ARCS_MAX_P, ARCS_MAX_T, MAX_POTENTIAL, UNREACHED,  # noqa: F401
                    PlanConfig, arc_start, arc_steps, arc_tree_best, arc_tree_nodes, arcs_best, footprint_box, plan_q, plan_weights,

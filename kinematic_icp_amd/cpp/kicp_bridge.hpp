@@ -286,6 +286,20 @@ inline std::shared_ptr<kicp_grid> clone_grid(const kicp_grid *grid, int device =
     check(kicp_grid_use_transients(copy.get(), kicp_grid_uses_transients(grid)), "kicp_bridge::clone_grid");  // the switch; the copy's transient plane starts empty
     return copy;
 }
+// Following (kicp.h FOLLOWING): what KinematicICP::EnableGridFollow and EnableElevationFollow keep - the band's margin and the step, in
+// cells, and the shift the last frame applied.  make_follow checks the pair against the handle's width and height by
+// kicp_follow_shift's own rule (std::invalid_argument).
+struct Follow {
+    bool enabled = false;
+    unsigned int margin_cells = 0, step_cells = 0;
+    std::array<int, 2> last{{0, 0}};  // (dx, dy) of the last frame; (0, 0) before the first and while following is off
+};
+inline Follow make_follow(unsigned int width, unsigned int height, unsigned int margin_cells, unsigned int step_cells, const char *what) {
+    long long d = 0;
+    if (kicp_follow_shift(0, width, margin_cells, step_cells, &d) != KICP_OK || kicp_follow_shift(0, height, margin_cells, step_cells, &d) != KICP_OK)
+        throw std::invalid_argument(std::string(what) + ": " + kicp_last_error());
+    return Follow{true, margin_cells, step_cells, {{0, 0}}};
+}
 // The height columns a mapping run keeps for uneven ground (kicp.h kicp_elev_*): KinematicICP::EnableElevation takes an ElevationConfig
 // and holds the handle shared, so a node can keep KinematicICP::Elevation() - for kicp_elev_to_grid into its planner's grid, say.
 // clone_elevation is the deep copy a copied pipeline gets: a layer of the same configuration with the same columns (its frame count

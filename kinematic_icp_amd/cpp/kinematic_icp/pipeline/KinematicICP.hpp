@@ -84,7 +84,9 @@ public:
           grid_(kicp_bridge::clone_grid(o.grid_.get())),
           transients_enabled_(o.transients_enabled_),
           transient_config_(o.transient_config_),
+          grid_follow_(o.grid_follow_),
           elev_(kicp_bridge::clone_elevation(o.elev_.get())),
+          elev_follow_(o.elev_follow_),
           last_elev_stats_(o.last_elev_stats_),
           elev_carving_(o.elev_carving_),
           elev_carve_(o.elev_carve_),
@@ -108,7 +110,9 @@ public:
           transients_enabled_(o.transients_enabled_),
           transient_config_(o.transient_config_),
           last_transients_(std::move(o.last_transients_)),
+          grid_follow_(o.grid_follow_),
           elev_(std::move(o.elev_)),
+          elev_follow_(o.elev_follow_),
           last_elev_stats_(o.last_elev_stats_),
           elev_carving_(o.elev_carving_),
           elev_carve_(o.elev_carve_),
@@ -126,6 +130,7 @@ public:
         std::swap(pre_, o.pre_);
         std::swap(elev_carving_, o.elev_carving_), std::swap(elev_carve_, o.elev_carve_), std::swap(last_elev_carve_stats_, o.last_elev_carve_stats_);
         std::swap(transients_enabled_, o.transients_enabled_), std::swap(transient_config_, o.transient_config_), std::swap(last_transients_, o.last_transients_);
+        std::swap(grid_follow_, o.grid_follow_), std::swap(elev_follow_, o.elev_follow_);
         std::swap(grid_, o.grid_), std::swap(elev_, o.elev_), std::swap(last_elev_stats_, o.last_elev_stats_), std::swap(view_, o.view_), std::swap(last_removal_, o.last_removal_), std::swap(sensor_in_base_, o.sensor_in_base_);
         return *this;
     }
@@ -165,6 +170,7 @@ public:
         if (view_ && config_.update_map) RemoveSeenThrough(kicp_bridge::xyz(preprocessed_frame_in_base), preprocessed_frame_in_base.size(), false, new_pose);
         if (config_.update_map) local_map_.Update(frame_downsample, new_pose);
         last_pose_ = new_pose;
+        FollowPose();
         if (grid_ && transients_enabled_) DetectTransients(kicp_bridge::xyz(preprocessed_frame_in_base), preprocessed_frame_in_base.size(), false);
         if (grid_) IntegrateGrid(kicp_bridge::xyz(preprocessed_frame_in_base), preprocessed_frame_in_base.size(), false);
         if (elev_) IntegrateElevation(kicp_bridge::xyz(preprocessed_frame_in_base), preprocessed_frame_in_base.size(), false);
@@ -324,9 +330,26 @@ public:
     // kicp_grid_*).  Poses, thresholds, returned clouds and the map are what they are without the grid.  Config::update_map = false
     // does not stop it: localising in a saved map while drawing a grid of what is seen now is legitimate.  SetPose leaves it alone.
     // Grid() is the shared handle (null without a grid): a node may keep it for the kicp_grid_* calls of its map publisher.
-    // (A new grid, or none, ends EnableTransients below: its plane and switch went with the old handle.)
-    void EnableGrid(const kicp_bridge::GridConfig &config) { grid_ = kicp_bridge::make_grid(config), transients_enabled_ = false, last_transients_.clear(); }
-    void DisableGrid() { grid_.reset(), transients_enabled_ = false, last_transients_.clear(); }
+    // (A new grid, or none, ends EnableTransients below - its plane and switch went with the old handle - and EnableGridFollow.)
+    void EnableGrid(const kicp_bridge::GridConfig &config) {
+        grid_ = kicp_bridge::make_grid(config), transients_enabled_ = false, last_transients_.clear(), grid_follow_ = {};
+    }
+    void DisableGrid() { grid_.reset(), transients_enabled_ = false, last_transients_.clear(), grid_follow_ = {}; }
+    // FOLLOWING (off by default; a new grid starts with it off).  With it on, the grid follows the robot (kicp.h kicp_grid_follow): in
+    // every frame, after the registration and before the transients and the integration, it scrolls - by multiples of step_cells per
+    // axis - so that the cell of the new pose's translation lies at least margin_cells from every edge; cells that leave are forgotten,
+    // cells that enter are unknown, the grid's origin moves (GridOccupancy and SaveGrid report it) and the plan is invalidated.  Most
+    // frames do not scroll, which costs no launch.  LastGridScroll(): the (dx, dy) the last frame applied.  A pair the rule refuses -
+    // margin_cells or step_cells 0, 2 * margin_cells + step_cells above the width or the height - is std::invalid_argument.  Poses,
+    // thresholds, returned clouds and the voxel map are what they are without following: the grid never feeds the registration.
+    void EnableGridFollow(unsigned int margin_cells, unsigned int step_cells) {
+        kicp_grid_config config{};
+        kicp_bridge::check(kicp_grid_info(RequireGrid("EnableGridFollow"), &config, nullptr, nullptr), "EnableGridFollow");
+        grid_follow_ = kicp_bridge::make_follow(config.width, config.height, margin_cells, step_cells, "KinematicICP::EnableGridFollow");
+    }
+    void DisableGridFollow() { grid_follow_ = {}; }
+    bool GridFollowEnabled() const { return grid_follow_.enabled; }
+    std::array<int, 2> LastGridScroll() const { return grid_follow_.last; }
     std::shared_ptr<kicp_grid> Grid() const { return grid_; }
     // the readout, a nav_msgs/OccupancyGrid's `data`: width * height bytes, row-major from the origin, -1 unknown, else 0 .. 100
     void GridOccupancy(std::vector<int8_t> &data, unsigned int min_observations = 1) const {
@@ -544,8 +567,20 @@ public:
     // traversability into a grid a node dedicates to its planner, and kicp_elev_to_grid_slope(Elevation().get(), &config, &slope,
     // planner_grid.get()) the traversability with the slope limit.  LastElevationStats(): used, skipped, outside_grid, outside_column,
     // new_bits, new_cells of the last frame (zeros before the first).
-    void EnableElevation(const kicp_bridge::ElevationConfig &config) { elev_ = kicp_bridge::make_elevation(config), last_elev_stats_ = {}, DisableElevationCarving(); }
-    void DisableElevation() { elev_.reset(), last_elev_stats_ = {}, DisableElevationCarving(); }
+    void EnableElevation(const kicp_bridge::ElevationConfig &config) {
+        elev_ = kicp_bridge::make_elevation(config), last_elev_stats_ = {}, elev_follow_ = {}, DisableElevationCarving();
+    }
+    void DisableElevation() { elev_.reset(), last_elev_stats_ = {}, elev_follow_ = {}, DisableElevationCarving(); }
+    // FOLLOWING for the layer, as EnableGridFollow for the grid (kicp.h kicp_elev_follow; off by default, a new layer starts with it
+    // off).  A planner grid fed by kicp_elev_to_grid* is scrolled by its owner, by LastElevationScroll().
+    void EnableElevationFollow(unsigned int margin_cells, unsigned int step_cells) {
+        kicp_elev_config config{};
+        kicp_bridge::check(kicp_elev_info(RequireElevation("EnableElevationFollow"), &config, nullptr, nullptr), "EnableElevationFollow");
+        elev_follow_ = kicp_bridge::make_follow(config.width, config.height, margin_cells, step_cells, "KinematicICP::EnableElevationFollow");
+    }
+    void DisableElevationFollow() { elev_follow_ = {}; }
+    bool ElevationFollowEnabled() const { return elev_follow_.enabled; }
+    std::array<int, 2> LastElevationScroll() const { return elev_follow_.last; }
     std::shared_ptr<kicp_elev> Elevation() const { return elev_; }
     const kicp_bridge::ElevationStats &LastElevationStats() const { return last_elev_stats_; }
     // CARVING (off by default; a new layer starts with it off).  With it on, a frame goes into the layer as an UPDATE (kicp.h
@@ -709,6 +744,16 @@ protected:
         return all;
     }
     // one frame into the grid at last_pose_ (already the new pose), from HBM or from host memory
+    // the grid and the layer follow the new pose's translation, where following is on
+    void FollowPose() {
+        const Eigen::Vector3d at = last_pose_.translation();
+        if (grid_ && grid_follow_.enabled)
+            kicp_bridge::check(kicp_grid_follow(grid_.get(), at.x(), at.y(), grid_follow_.margin_cells, grid_follow_.step_cells, &grid_follow_.last[0], &grid_follow_.last[1]),
+                               "KinematicICP: following with the grid");
+        if (elev_ && elev_follow_.enabled)
+            kicp_bridge::check(kicp_elev_follow(elev_.get(), at.x(), at.y(), elev_follow_.margin_cells, elev_follow_.step_cells, &elev_follow_.last[0], &elev_follow_.last[1]),
+                               "KinematicICP: following with the height layer");
+    }
     void IntegrateGrid(const double *xyz, size_t n, bool on_device) {
         double pose[7];
         kicp_bridge::to_params(last_pose_, pose);
@@ -791,6 +836,8 @@ protected:
         if (config_.update_map) local_map_.UpdateDeviceBegin(kicp_pre_device_ptr(pre_, 1, nullptr), n_down, new_pose);
         last_pose_ = new_pose;
         // the occupancy grid, when enabled: the whole preprocessed frame (buffer 0, complete since the pre-steps returned) at the new pose
+        // following, when enabled: the grid and the layer scroll towards the new pose before the frame goes into them
+        FollowPose();
         // the transients, when enabled: the same frame against the counters as they stand, before its own hits go into them
         if (grid_ && transients_enabled_) DetectTransients(kicp_pre_device_ptr(pre_, 0, nullptr), counts[0], true);
         if (grid_) IntegrateGrid(kicp_pre_device_ptr(pre_, 0, nullptr), counts[0], true);
@@ -862,7 +909,9 @@ protected:
     kicp_bridge::TransientConfig transient_config_{};
     std::vector<kicp_bridge::Transient> last_transients_;  // the last frame's
     std::vector<unsigned long long> transient_rows_;       // where their rows land (scratch that keeps its size)
+    kicp_bridge::Follow grid_follow_;      // EnableGridFollow: the grid scrolls after the robot
     std::shared_ptr<kicp_elev> elev_;      // EnableElevation's height columns (backend detail); null: no layer
+    kicp_bridge::Follow elev_follow_;      // EnableElevationFollow: the layer does
     kicp_bridge::ElevationStats last_elev_stats_{};  // the last frame's statistics of that layer
     bool elev_carving_ = false;                      // EnableElevationCarving: frames go into the layer as updates
     kicp_bridge::ElevationCarveConfig elev_carve_{};

@@ -8,6 +8,7 @@
 
 #include "kicp_elev.hpp"
 #include "kicp_grid_internal.hpp"
+#include "kicp_scroll.hpp"
 
 // The handle keeps the grid's rules (kicp_grid_internal.hpp): const entries write only the `mutable` group, and every entry returns
 // with the stream drained.
@@ -17,6 +18,7 @@ struct kicp_elev {
     ElevGeom geom{};
     size_t cells = 0;
     DevBuf<unsigned long long> d_columns;  // the layer: one column per cell
+    DevBuf<unsigned long long> d_columns_spare;  // kicp_elev_scroll: what a shift writes into, swapped with d_columns afterwards; as kicp_grid's
     hipStream_t stream = nullptr;
     unsigned long long frames = 0;
     bool has_window = false;  // as kicp_grid's
@@ -138,6 +140,27 @@ int integrate_on_device(kicp_elev *elev, const double *d_xyz, size_t n, const do
 }
 int check_frame_args(const kicp_elev *elev, const double *xyz, size_t n, const double *pose_qt, const double *sensor_xyz) {
     return FrameUpload::check(elev && pose_qt && sensor_xyz && (xyz || !n), n, "frame too large");
+}
+// The shift by (dx, dy), not both 0 (the handle checked): as the grid's scroll_on_device (kicp_grid.hip), for the columns.
+int scroll_on_device(kicp_elev *elev, int dx, int dy) {
+    kicp_elev_config &cfg = elev->cfg;
+    const double origin_x = scroll_host::scroll_origin(cfg.origin_x, dx, cfg.cell), origin_y = scroll_host::scroll_origin(cfg.origin_y, dy, cfg.cell);
+    if (!std::isfinite(origin_x) || !std::isfinite(origin_y)) return fail(KICP_ERR_ARG, "the origin after the shift is not finite");
+    if (int rc = set_device(elev->device)) return rc;
+    const bool empties = scroll_empties(cfg.width, cfg.height, dx, dy);
+    if (empties) {
+        HIP_TRY(hipMemsetAsync(elev->d_columns.get(), 0, elev->cells * sizeof(unsigned long long), elev->stream));
+    } else {
+        if (int rc = elev->d_columns_spare.reserve(elev->cells)) return rc;
+        hipLaunchKernelGGL(k_scroll_plane<unsigned long long>, dim3(scroll_blocks<unsigned long long>(elev->cells)), dim3(kScrollBlock), 0, elev->stream,
+                           elev->d_columns.get(), elev->d_columns_spare.get(), cfg.width, cfg.height, dx, dy);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipStreamSynchronize(elev->stream));
+    if (!empties) std::swap(elev->d_columns, elev->d_columns_spare);
+    cfg.origin_x = elev->geom.plane.origin_x = origin_x, cfg.origin_y = elev->geom.plane.origin_y = origin_y;
+    if (elev->has_window) elev->has_window = scroll_host::scroll_window(elev->win_x0, elev->win_y0, dx, dy);
+    return KICP_OK;
 }
 uint32_t elev_tiles(uint32_t cells_side) { return (cells_side + kElevTile - 1u) / kElevTile; }
 int check_rough_config(const kicp_elev_rough_config *cfg, ElevRoughParams &p) {
@@ -371,6 +394,26 @@ int kicp_elev_set_columns(kicp_elev *elev, const unsigned long long *in, size_t 
     if (int rc = set_device(elev->device)) return rc;
     HIP_TRY(hipMemcpyAsync(elev->d_columns.get(), in, elev->cells * sizeof(unsigned long long), hipMemcpyHostToDevice, elev->stream));
     HIP_TRY(hipStreamSynchronize(elev->stream));
+    return KICP_OK;
+}
+int kicp_elev_scroll(kicp_elev *elev, int dx, int dy) {
+    KICP_TRACE_CALL();
+    if (!elev) return fail(KICP_ERR_ARG, "null argument");
+    if (dx == 0 && dy == 0) return KICP_OK;
+    return scroll_on_device(elev, dx, dy);
+}
+int kicp_elev_follow(kicp_elev *elev, double x, double y, unsigned int margin, unsigned int step, int *out_dx, int *out_dy) {
+    KICP_TRACE_CALL();
+    if (!elev) return fail(KICP_ERR_ARG, "null argument");
+    const kicp_elev_config &cfg = elev->cfg;
+    int32_t dx = 0, dy = 0;
+    const int bad = scroll_host::follow_shifts(x, y, cfg.origin_x, cfg.origin_y, cfg.cell, cfg.width, cfg.height, margin, step, &dx, &dy);
+    if (bad == 1) return fail(KICP_ERR_ARG, "the position must be finite and its cell within 2^30 cells of the layer's first");
+    if (bad) return fail(KICP_ERR_ARG, "following needs margin >= 1, step >= 1 and 2 * margin + step <= width and height");
+    if (dx != 0 || dy != 0)
+        if (int rc = scroll_on_device(elev, dx, dy)) return rc;
+    if (out_dx) *out_dx = dx;
+    if (out_dy) *out_dy = dy;
     return KICP_OK;
 }
 int kicp_elev_last_window(const kicp_elev *elev, unsigned int *x0, unsigned int *y0, unsigned int *w, unsigned int *h) {

@@ -1,13 +1,15 @@
 // kicp_grid.hip -- the 2-D occupancy grid a mapping run draws beside its voxel map (kicp_grid_*; include/kicp.h states the semantics):
 // per frame the used points' endpoint cells are HIT and the cells their rays cross are MISS, once per cell per frame.  Kernels:
 // kicp_grid.hpp; the geometry they share with the host entries: kicp_grid_host.hpp.  The handle, and which file holds what a planner
-// reads off the counters: kicp_grid_internal.hpp.
+// reads off the counters: kicp_grid_internal.hpp.  The grid scrolls (kicp_grid_scroll, kicp_grid_follow): kernel kicp_scroll.hpp,
+// arithmetic kicp_scroll_host.hpp.
 #include <cerrno>
 #include <cstring>
 #include <memory>
 
 #include "kicp_grid.hpp"
 #include "kicp_grid_internal.hpp"
+#include "kicp_scroll.hpp"
 
 namespace {
 int check_thresholds(double occupied_thresh, double free_thresh) {
@@ -56,6 +58,48 @@ int integrate_on_device(kicp_grid *grid, const double *d_xyz, size_t n, const do
 }
 int check_frame_args(const kicp_grid *grid, const double *xyz, size_t n, const double *pose_qt, const double *sensor_xyz) {
     return FrameUpload::check(grid && pose_qt && sensor_xyz && (xyz || !n), n, "frame too large");
+}
+int check_counts_rect(const kicp_grid *grid, unsigned int x0, unsigned int y0, unsigned int w, unsigned int h, size_t cap) {
+    const unsigned int width = grid->cfg.width, height = grid->cfg.height;
+    if (w < 1u || h < 1u || x0 >= width || y0 >= height || w > width - x0 || h > height - y0)
+        return fail(KICP_ERR_ARG, "the rectangle must lie inside the grid of " + std::to_string(width) + " x " + std::to_string(height) + " cells, w and h at least 1");
+    if (cap != static_cast<size_t>(w) * h) return fail(KICP_ERR_ARG, "the number of cells must be w * h = " + std::to_string(static_cast<size_t>(w) * h));
+    return KICP_OK;
+}
+// The shift by (dx, dy), not both 0 (the handle checked): the counters and the transient plane, then the handle's bookkeeping; the
+// stream drained.  Nothing of the map changes when it fails before the launches (with a plane, the counters' spare may by then be
+// allocated while the plane's failed: it is kept for the next call); a failure behind them returns without the swap, so the handle keeps
+// its counters and its origin.
+int scroll_on_device(kicp_grid *grid, int dx, int dy) {
+    kicp_grid_config &cfg = grid->cfg;
+    const double origin_x = scroll_host::scroll_origin(cfg.origin_x, dx, cfg.cell), origin_y = scroll_host::scroll_origin(cfg.origin_y, dy, cfg.cell);
+    if (!std::isfinite(origin_x) || !std::isfinite(origin_y)) return fail(KICP_ERR_ARG, "the origin after the shift is not finite");
+    if (int rc = set_device(grid->device)) return rc;
+    hipStream_t st = grid->stream;
+    const bool plane = grid->d_transient_plane.get() != nullptr, empties = scroll_empties(cfg.width, cfg.height, dx, dy);
+    if (empties) {  // nothing survives: no spare needed
+        HIP_TRY(hipMemsetAsync(grid->d_counts.get(), 0, 2 * grid->cells * sizeof(uint16_t), st));
+        if (plane) HIP_TRY(hipMemsetAsync(grid->d_transient_plane.get(), 0, grid->cells, st));
+    } else {
+        if (int rc = grid->d_counts_spare.reserve(2 * grid->cells)) return rc;
+        if (plane)
+            if (int rc = grid->d_transient_spare.reserve(grid->cells)) return rc;
+        hipLaunchKernelGGL(k_scroll_plane<uint32_t>, dim3(scroll_blocks<uint32_t>(grid->cells)), dim3(kScrollBlock), 0, st,
+                           reinterpret_cast<const uint32_t *>(grid->d_counts.get()), reinterpret_cast<uint32_t *>(grid->d_counts_spare.get()), cfg.width, cfg.height, dx, dy);
+        if (plane)
+            hipLaunchKernelGGL(k_scroll_plane<uint8_t>, dim3(scroll_blocks<uint8_t>(grid->cells)), dim3(kScrollBlock), 0, st, grid->d_transient_plane.get(),
+                               grid->d_transient_spare.get(), cfg.width, cfg.height, dx, dy);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    if (!empties) {
+        std::swap(grid->d_counts, grid->d_counts_spare);
+        if (plane) std::swap(grid->d_transient_plane, grid->d_transient_spare);
+    }
+    cfg.origin_x = grid->geom.origin_x = origin_x, cfg.origin_y = grid->geom.origin_y = origin_y;
+    if (grid->has_window) grid->has_window = scroll_host::scroll_window(grid->win_x0, grid->win_y0, dx, dy);
+    grid->plan.valid = false;  // the plan's cells no longer mean what they meant
+    return KICP_OK;
 }
 }  // namespace
 
@@ -149,6 +193,63 @@ int kicp_grid_set_counts(kicp_grid *grid, const unsigned short *in, size_t cells
     if (int rc = set_device(grid->device)) return rc;
     HIP_TRY(hipMemcpyAsync(grid->d_counts.get(), in, 2 * grid->cells * sizeof(uint16_t), hipMemcpyHostToDevice, grid->stream));
     HIP_TRY(hipStreamSynchronize(grid->stream));
+    return KICP_OK;
+}
+int kicp_grid_counts_rect(const kicp_grid *grid, unsigned int x0, unsigned int y0, unsigned int w, unsigned int h, unsigned short *out, size_t cap_cells) {
+    KICP_TRACE_CALL();
+    if (!grid || !out) return fail(KICP_ERR_ARG, "null argument");
+    if (int rc = check_counts_rect(grid, x0, y0, w, h, cap_cells)) return rc;
+    if (int rc = set_device(grid->device)) return rc;
+    constexpr size_t pair = 2 * sizeof(uint16_t);
+    HIP_TRY(hipMemcpy2DAsync(out, w * pair, grid->d_counts.get() + 2 * (static_cast<size_t>(y0) * grid->cfg.width + x0), grid->cfg.width * pair, w * pair, h,
+                             hipMemcpyDeviceToHost, grid->stream));
+    HIP_TRY(hipStreamSynchronize(grid->stream));
+    return KICP_OK;
+}
+int kicp_grid_set_counts_rect(kicp_grid *grid, unsigned int x0, unsigned int y0, unsigned int w, unsigned int h, const unsigned short *in, size_t cells) {
+    KICP_TRACE_CALL();
+    if (!grid || !in) return fail(KICP_ERR_ARG, "null argument");
+    if (int rc = check_counts_rect(grid, x0, y0, w, h, cells)) return rc;
+    if (int rc = set_device(grid->device)) return rc;
+    constexpr size_t pair = 2 * sizeof(uint16_t);
+    HIP_TRY(hipMemcpy2DAsync(grid->d_counts.get() + 2 * (static_cast<size_t>(y0) * grid->cfg.width + x0), grid->cfg.width * pair, in, w * pair, w * pair, h,
+                             hipMemcpyHostToDevice, grid->stream));
+    HIP_TRY(hipStreamSynchronize(grid->stream));
+    return KICP_OK;
+}
+int kicp_grid_scroll(kicp_grid *grid, int dx, int dy) {
+    KICP_TRACE_CALL();
+    if (!grid) return fail(KICP_ERR_ARG, "null argument");
+    if (dx == 0 && dy == 0) return KICP_OK;
+    return scroll_on_device(grid, dx, dy);
+}
+int kicp_grid_follow(kicp_grid *grid, double x, double y, unsigned int margin, unsigned int step, int *out_dx, int *out_dy) {
+    KICP_TRACE_CALL();
+    if (!grid) return fail(KICP_ERR_ARG, "null argument");
+    const kicp_grid_config &cfg = grid->cfg;
+    int32_t dx = 0, dy = 0;
+    const int bad = scroll_host::follow_shifts(x, y, cfg.origin_x, cfg.origin_y, cfg.cell, cfg.width, cfg.height, margin, step, &dx, &dy);
+    if (bad == 1) return fail(KICP_ERR_ARG, "the position must be finite and its cell within 2^30 cells of the grid's first");
+    if (bad) return fail(KICP_ERR_ARG, "following needs margin >= 1, step >= 1 and 2 * margin + step <= width and height");
+    if (dx != 0 || dy != 0)
+        if (int rc = scroll_on_device(grid, dx, dy)) return rc;
+    if (out_dx) *out_dx = dx;
+    if (out_dy) *out_dy = dy;
+    return KICP_OK;
+}
+int kicp_shift_plane(const void *in, void *out, unsigned int width, unsigned int height, unsigned int elem_bytes, int dx, int dy) {
+    if (!in || !out) return fail(KICP_ERR_ARG, "null argument");
+    if (elem_bytes != 1u && elem_bytes != 2u && elem_bytes != 4u && elem_bytes != 8u) return fail(KICP_ERR_ARG, "elem_bytes must be 1, 2, 4 or 8");
+    if (int rc = check_grid_dims(width, height)) return rc;
+    const uintptr_t a = reinterpret_cast<uintptr_t>(in), b = reinterpret_cast<uintptr_t>(out), bytes = static_cast<uintptr_t>(width) * height * elem_bytes;
+    if (a < b + bytes && b < a + bytes) return fail(KICP_ERR_ARG, "in and out must not overlap");
+    scroll_host::shift_plane(in, out, width, height, elem_bytes, dx, dy);
+    return KICP_OK;
+}
+int kicp_follow_shift(long long c, unsigned int size, unsigned int margin, unsigned int step, long long *d) {
+    if (!d) return fail(KICP_ERR_ARG, "null argument");
+    if (!scroll_host::follow_shift(c, size, margin, step, d))
+        return fail(KICP_ERR_ARG, "following needs margin >= 1, step >= 1 and 2 * margin + step <= size (and a shift inside 64 bits)");
     return KICP_OK;
 }
 int kicp_grid_occupancy(const kicp_grid *grid, unsigned int min_observations, signed char *out, size_t cap_cells) {

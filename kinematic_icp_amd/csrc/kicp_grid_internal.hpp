@@ -1,8 +1,10 @@
 // kicp_grid_internal.hpp -- what the translation units of the 2-D occupancy grid (kicp_grid*.hip) share: the handle behind kicp_grid,
 // the rules its entries keep, and the argument checks that more than one of them makes.  include/kicp.h states the semantics.  The
 // pieces, each the only translation unit that includes its kernel headers (the arithmetic they share with the host: *_host.hpp):
-//   kicp_grid.hip          the grid itself (kicp_grid.hpp): create / destroy / info / clear, integrate, counts / set_counts, the
-//                          occupancy readout, last_window, write_map / save_map, fill_unknown and its host twin
+//   kicp_grid.hip          the grid itself (kicp_grid.hpp): create / destroy / info / clear, integrate, counts / set_counts and their
+//                          rectangles, the occupancy readout, last_window, write_map / save_map, fill_unknown and its host twin, and
+//                          the window that follows the robot (kicp_scroll.hpp - the second kernel header two units include:
+//                          kicp_elev.hip scrolls its columns with it): scroll, follow, kicp_shift_plane, kicp_follow_shift
 //   kicp_grid_plan.hip     what a planner plans on (kicp_clear.hpp, kicp_nav.hpp): clearance and costmap with their host twins,
 //                          kicp_grid_cost_table_nav2, kicp_plan_weights, the three potential entries, kicp_potential_path, kicp_plan_q,
 //                          kicp_grid_has_plan - one file because kicp_grid_potential queues the costmap's launches in front of the field's
@@ -52,6 +54,10 @@ struct kicp_grid {
     // allocated (and read as all 0) until the first such call.  use_transients is the switch: clear_on_device ORs the plane into its sources.
     DevBuf<uint8_t> d_transient_plane;
     bool use_transients = false;
+    // kicp_grid_scroll: the buffers a shift writes into, swapped with d_counts and d_transient_plane afterwards.  Not allocated until
+    // the first shift that needs them, then kept: a scrolled handle holds its counters (and its plane, if it has one) twice.
+    DevBuf<uint16_t> d_counts_spare;
+    DevBuf<uint8_t> d_transient_spare;
     // kicp_grid_integrate*: the two frame-local planes over the window, zero between frames, and the frame in flight
     struct {
         uint32_t plane_words = 0;       // ceil((2 reach + 1)^2 / 4)

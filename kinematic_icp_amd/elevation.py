@@ -58,6 +58,8 @@ _ENTRIES = _declare({
     "kicp_elev_columns": (C.c_int, [_vp, _u64p, _sz]),
     "kicp_elev_set_columns": (C.c_int, [_vp, _u64p, _sz]),
     "kicp_elev_last_window": (C.c_int, [_vp, _u32p, _u32p, _u32p, _u32p]),
+    "kicp_elev_scroll": (C.c_int, [_vp, C.c_int, C.c_int]),
+    "kicp_elev_follow": (C.c_int, [_vp, C.c_double, C.c_double, C.c_uint, C.c_uint, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "kicp_elev_traversability": (C.c_int, [_vp, _trav] + _rect_out + [_u64p, _sz]),
     "kicp_elev_traversability_from_columns": (C.c_int, [_u64p, _u, _u, _trav] + _rect_out + [_u64p, _sz]),
     "kicp_elev_to_grid": (C.c_int, [_vp, _trav, _vp]),
@@ -237,6 +239,18 @@ class ElevationLayer(Handle):
     def set_columns(self, columns):
         c = np.ascontiguousarray(columns, dtype=np.uint64)
         _check(lib().kicp_elev_set_columns(self._h, _u64(c), c.size))
+
+    def scroll(self, dx, dy):
+        """kicp_elev_scroll: OccupancyGrid.scroll for the columns: the window moves by (dx, dy) cells on the GPU, columns that enter are
+        zero, the origin becomes origin + d * cell and the last window is translated.  A planner grid fed by to_grid* is scrolled by
+        the same (dx, dy) by its owner."""
+        _check(lib().kicp_elev_scroll(self._h, int(dx), int(dy)))
+
+    def follow(self, x, y, margin, step):
+        """kicp_elev_follow: OccupancyGrid.follow for the layer -> the (dx, dy) applied"""
+        dx, dy = C.c_int(), C.c_int()
+        _check(lib().kicp_elev_follow(self._h, float(x), float(y), int(margin), int(step), C.byref(dx), C.byref(dy)))
+        return int(dx.value), int(dy.value)
 
     def last_window(self):
         """kicp_elev_last_window: (x0, y0, w, h) of the last integrated frame's window clipped to the layer, by OccupancyGrid.last_window's

@@ -71,7 +71,34 @@ _ENTRIES = _declare({
     "kicp_grid_transient_plane": (C.c_int, [_vp, _u8p, _sz]),
     "kicp_grid_use_transients": (C.c_int, [_vp, C.c_int]),
     "kicp_grid_uses_transients": (C.c_int, [_vp]),
+    # the window that follows the robot (the height layer's two entries: elevation.py)
+    "kicp_grid_scroll": (C.c_int, [_vp, C.c_int, C.c_int]),
+    "kicp_grid_follow": (C.c_int, [_vp, _f64, _f64, _u, _u, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "kicp_grid_counts_rect": (C.c_int, [_vp, _u, _u, _u, _u, _u16p, _sz]),
+    "kicp_grid_set_counts_rect": (C.c_int, [_vp, _u, _u, _u, _u, _u16p, _sz]),
+    "kicp_shift_plane": (C.c_int, [_vp, _vp, _u, _u, _u, C.c_int, C.c_int]),
+    "kicp_follow_shift": (C.c_int, [C.c_longlong, _u, _u, _u, C.POINTER(C.c_longlong)]),
 })
+
+
+def shift_plane(plane, dx, dy):
+    """kicp_shift_plane: `plane`, shaped (height, width) or (height, width, k) with 1, 2, 4 or 8 bytes per cell in all (a transient
+    plane, counters (height, width, 2) uint16, uint64 columns), shifted by (dx, dy) -> a new array of the same shape and dtype:
+    out[iy, ix] = plane[iy + dy, ix + dx] where that lies inside, 0 elsewhere.  Pure host code: needs no GPU."""
+    a = np.ascontiguousarray(plane)
+    if a.ndim not in (2, 3) or a.size == 0:
+        raise KicpError(KICP_ERR_ARG, "the plane must be shaped (height, width) or (height, width, k), none of them 0")
+    out = np.empty_like(a)
+    _check(lib().kicp_shift_plane(a.ctypes.data, out.ctypes.data, a.shape[1], a.shape[0], a.itemsize * (a.shape[2] if a.ndim == 3 else 1), int(dx), int(dy)))
+    return out
+
+
+def follow_shift(c, size, margin, step):
+    """kicp_follow_shift: the shift along one axis of `size` cells that brings cell index c into [margin, size - margin) -> int: 0 when
+    it is there, else the least multiple of `step` that does (negative below the band).  Pure host code."""
+    d = C.c_longlong()
+    _check(lib().kicp_follow_shift(int(c), int(size), int(margin), int(step), C.byref(d)))
+    return int(d.value)
 
 
 def occupancy_from_counts(counts, min_observations=1):
@@ -205,6 +232,35 @@ class OccupancyGrid(Handle):
         if c.size % 2:
             raise KicpError(KICP_ERR_ARG, "counts must hold (hits, misses) pairs")
         _check(lib().kicp_grid_set_counts(self._h, _u16(c), c.size // 2))
+
+    def counts_rect(self, rect):
+        """kicp_grid_counts_rect: the counters of `rect` = (x0, y0, w, h), inside the grid -> uint16 (h, w, 2)"""
+        x0, y0, w, h = _rect(rect, self.width, self.height)
+        out = np.empty((h, w, 2), dtype=np.uint16)
+        _check(lib().kicp_grid_counts_rect(self._h, x0, y0, w, h, _u16(out), out.size // 2))
+        return out
+
+    def set_counts_rect(self, rect, counts):
+        """kicp_grid_set_counts_rect: writes `counts`, uint16 (h, w, 2), over the cells of `rect` = (x0, y0, w, h); every other cell and
+        the plan stay"""
+        x0, y0, w, h = _rect(rect, self.width, self.height)
+        c = np.ascontiguousarray(counts, dtype=np.uint16)
+        if c.size % 2:
+            raise KicpError(KICP_ERR_ARG, "counts must hold (hits, misses) pairs")
+        _check(lib().kicp_grid_set_counts_rect(self._h, x0, y0, w, h, _u16(c), c.size // 2))
+
+    def scroll(self, dx, dy):
+        """kicp_grid_scroll: on the GPU, the window moves by (dx, dy) cells: cell (ix, iy) afterwards holds what (ix + dx, iy + dy) held,
+        cells that enter are unknown, the transient plane moves along, the origin becomes origin + d * cell, the last window is
+        translated and the plan is invalidated.  (0, 0) changes nothing."""
+        _check(lib().kicp_grid_scroll(self._h, int(dx), int(dy)))
+
+    def follow(self, x, y, margin, step):
+        """kicp_grid_follow: scrolls, in multiples of `step` cells per axis, so that the cell of the world position (x, y) lies at least
+        `margin` cells from every edge -> the (dx, dy) applied; (0, 0), the common case, costs no launch"""
+        dx, dy = C.c_int(), C.c_int()
+        _check(lib().kicp_grid_follow(self._h, float(x), float(y), int(margin), int(step), C.byref(dx), C.byref(dy)))
+        return int(dx.value), int(dy.value)
 
     def fill_unknown(self, src, min_observations=1, free_max=25, occupied_min=101, return_counts=False):
         """kicp_grid_fill_unknown: on the GPU, the unknown cells of this grid - both counters 0 - become traversable (0, 1) where `src`,
